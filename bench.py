@@ -10,9 +10,23 @@ GEMM arithmetic (--dtype): "f16x3" (default: every operand tensor written by its
 S x = h + l/2048, three fp16 MFMAs per product on two fp32 accumulators -- fp32-grade results, meets the 1e-3 mm
 parity gate), "bf16x6" (fp32 operands split into three bf16 pieces inside the GEMM, six MFMAs -- also fp32-grade),
 "fp32" (exact v_mfma_f32_32x32x2_f32) or "bf16" (operands rounded to bf16, ~1 mm: never the parity-gated number).
-The modes not chosen are measured beside the headline (other_modes).
+The modes not chosen are measured beside the headline (other_modes, --full).
 
-One JSON line on rank 0 (contract in the task statement).  Also in that line:
+One JSON line on rank 0: metric, value (poses/s), unit, higher_is_better, dtype, ms_per_step (one timed step), steps,
+warmup, config.  A plain run does only that: set up, warm up, time --steps steps, [--dump-outputs], print the line.
+  config.launch how the timed steps were issued at N = 1: "eager" (one call per kernel) or "hipgraph" (one replay of the
+                captured step, train.GraphedTrainStep) -- --launch auto times a few untimed steps of each during warm-up
+                and takes the faster (a busy host core makes the eager loop launch-bound: 0.95 instead of 0.61 ms per
+                step on one box of round 3).  Under hipgraph the roofline's HIP events bracket eager steps right behind
+                the timed region (events cannot be read out of a replayed graph); N > 1 is always eager.
+
+--dump-outputs DIR  after the timed steps, what the last timed step computed as DIR/<name>.npy: `loss` and `pred` (the
+                    (loss, y_hat) train_step returns) and `param.<state_dict key>` (the model after that step), float32
+                    (integer buffers as float64), at most 64 MB in all (a larger array is cut to a fixed, seeded sample of
+                    its elements).  Rank 0.  The inputs depend only on the arguments, so two builds compare file by file.
+
+--full adds everything else this file measures or checks, in the same line (--no-prof / --no-extras /
+--no-cpu-baseline leave parts of it out):
   roofline      the dominant kernel by time, the backward dual launch (dX = dz W and dW = dz^T a of one
                 layer, 2 x 8.59 GFLOP): ALGORITHMIC FLOPs per launch / mean launch duration, measured
                 with HIP events recorded on the launch stream around every such launch INSIDE the
@@ -26,15 +40,13 @@ One JSON line on rank 0 (contract in the task statement).  Also in that line:
                 value) and B = 64 (batch_64) -- rank 0, N=1 only.  A reported baseline, not the target.
   batch_64      the HIP step's latency at the reference's own batch size (config 0), same protocol, issued as one hipGraph
                 replay and as an eager train_step (the lower of the two; both are in the entry).
-  config.launch how the timed steps were issued at N = 1: "eager" (one call per kernel) or "hipgraph" (one replay of the
-                captured step, train.GraphedTrainStep) -- --launch auto times a few untimed steps of each during warm-up
-                and takes the faster (a busy host core makes the eager loop launch-bound: 0.95 instead of 0.61 ms per
-                step on one box of round 3).  Under hipgraph the roofline's HIP events bracket eager steps right behind
-                the timed region (events cannot be read out of a replayed graph); N > 1 is always eager.
   parity        eval-forward MPJPE (mm) of the HIP path against the numpy oracle on the bench
                 batch, in the same run (gate 1e-3 mm, BASELINE.json).
   other_modes   this library's other arithmetic modes and stock PyTorch-ROCm eager of the same module
                 (fp32 and bf16 autocast) on the same GPU, same batch, same step.
+  fwd_bwd_only_poses_per_s_per_gpu   forward + backward alone, without the optimizer.
+  allreduce     N > 1: what the gradient all-reduce costs the step (the same steps with it stubbed out).
+  --workload cycle: cpu_baseline of the cycle step.
 Inputs are synthetic H3.6M-shaped batches resident in HBM before the timed region starts.
 """
 import argparse
@@ -70,11 +82,16 @@ def prof_every(steps):
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 200; --workload cycle: 10)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed steps before them (default 20; --workload cycle: 3)")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline: roofline, fwd+bwd-only rate, eval parity vs the numpy oracle, "
+                         "batch_64, other_modes, cpu_baseline, the all-reduce cost at N > 1 (off: a lean headline run)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, <= 64 MB in all)")
     ap.add_argument("--batch", type=int, default=BATCH, help="per-GPU batch (default: BASELINE config 4096)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-prof", action="store_true", help="do not bracket GEMM launches with HIP events")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline")
+    ap.add_argument("--no-prof", action="store_true", help="--full without bracketing GEMM launches with HIP events (no roofline)")
     ap.add_argument("--dtype", choices=["fp32", "bf16", "bf16x6", "f16x3"], default="f16x3",
                     help="GEMM arithmetic of the headline run.  f16x3 (default), bf16x6 and fp32 meet the 1e-3 mm "
                          "parity gate; bf16 does not (about 1 mm)")
@@ -83,7 +100,7 @@ def parse():
     ap.add_argument("--sync-bn", action="store_true",
                     help="N>1 only: BatchNorm statistics over the global batch (10 small all-gathers per step); "
                          "off by default = statistics per shard, the DDP convention")
-    ap.add_argument("--no-extras", action="store_true", help="skip the bf16-mode and PyTorch-eager side measurements")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the other-mode and PyTorch-eager side measurements")
     ap.add_argument("--launch", choices=["auto", "eager", "hipgraph"], default="auto",
                     help="how the timed steps are issued at N=1: one Python call per launch (eager), one hipGraph replay per "
                          "step (GraphedTrainStep), or whichever a short calibration during warm-up finds faster (auto: a slow "
@@ -96,9 +113,43 @@ def parse():
     a = ap.parse_args()
     if a.workload == "cycle" and a.batch == BATCH:
         a.batch = 128                                       # configs[4]: batch 1024 over 8 GPUs
-    if a.workload == "cycle" and a.steps == 200 and a.warmup == 20:
-        a.steps, a.warmup = 10, 3                           # a cycle step is ~0.1 s: defaults that finish in minutes
+    steps, warmup = (10, 3) if a.workload == "cycle" else (200, 20)   # a cycle step is ~0.1 s: defaults that finish in minutes
+    if a.steps is None:
+        a.steps = steps
+    if a.warmup is None:
+        a.warmup = warmup
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     return a
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """DIR/<name>.npy for every (name, array): float32, float64 where the source is float64 or integer, at most
+    DUMP_BYTES in all.  Past that, each array of more than 4096 elements is cut to the same share of its elements,
+    chosen by a fixed seed (sorted flat indices; the same every run for the same shapes)."""
+    import numpy as np
+    out = {}
+    for k, v in arrays.items():
+        v = np.asarray(v)
+        out[k] = np.array(v, dtype=np.float64 if v.dtype == np.float64 or v.dtype.kind in "iub" else np.float32)
+    budget = DUMP_BYTES - 1024 * len(out)                   # (room for the .npy headers)
+    total = sum(v.nbytes for v in out.values())
+    if total > budget:
+        small = sum(v.nbytes for v in out.values() if v.size <= 4096)
+        share = (budget - small) / (total - small)
+        rng = np.random.default_rng(0)
+        for k, v in out.items():
+            if v.size > 4096:
+                idx = np.sort(rng.choice(v.size, size=max(1, int(v.size * share)), replace=False))
+                out[k] = v.reshape(-1)[idx]
+        print(f"# --dump-outputs: {total} bytes > {budget}: arrays of more than 4096 elements sampled "
+              f"({share:.4f} of their elements, seed 0)", file=sys.stderr)
+    os.makedirs(path, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), v)
 
 
 def self_launch(a):
@@ -447,11 +498,11 @@ def cycle_workload(pkg, a, rank, local, world):
     torch.cuda.synchronize()
 
     def run(n, first=0):
-        loss = None
+        res = None
         for i in range(first, first + n):
             fr, y1, y2 = pool[i % len(pool)]
-            loss = pkg.cycle_step(m2, m3, lift, opts, fr, y1, y2, crit, model_proj=proj, Flip=a.flip)[0]
-        return loss
+            res = pkg.cycle_step(m2, m3, lift, opts, fr, y1, y2, crit, model_proj=proj, Flip=a.flip)
+        return res                                          # (loss, y1_hat, y2_hat) of the last step
 
     def barrier():
         if world > 1:
@@ -459,9 +510,12 @@ def cycle_workload(pkg, a, rank, local, world):
     run(a.warmup)
     barrier(); torch.cuda.synchronize()
     t0 = time.perf_counter()
-    loss = run(a.steps, a.warmup)
+    last = run(a.steps, a.warmup)
     torch.cuda.synchronize(); barrier()
     dt = time.perf_counter() - t0
+    loss = last[0]
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {k: t.detach().float().cpu().numpy() for k, t in zip(("loss", "y1_hat", "y2_hat"), last)})
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -484,7 +538,7 @@ def cycle_workload(pkg, a, rank, local, world):
                             "frac": round(tf / world / PEAK_BF16_MATRIX_TFLOPS, 4), "traffic": None,
                             "kernel": "whole step (about 2,200 launches; no single dominant kernel), convolution FLOPs only",
                             "flop_per_frame": flop_frame, "mfma_issue_frac": round(3 * tf / world / PEAK_BF16_MATRIX_TFLOPS, 4)}}
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             out["cpu_baseline"] = cycle_cpu_baseline(pkg, a.flip)
         print(json.dumps(out), flush=True)
     if world > 1:
@@ -555,9 +609,11 @@ def main():
             dist.barrier()
 
     def run(n, first=0):
+        res = None
         for i in range(first, first + n):
             x, y = pool[i % len(pool)]
-            pkg.train_step(model, opt, x, y, grad_sync=sync)
+            res = pkg.train_step(model, opt, x, y, grad_sync=sync)
+        return res                                          # (loss, y_hat) of the last step
 
     if world > 1:                                           # RCCL communicator + the bucket sizes the step
         for _, _, lo, hi in model._bwd_ranges():            # uses are set up before anything is timed,
@@ -572,8 +628,10 @@ def main():
         cal = max(10, min(a.warmup, 30))
 
         def run_graph(n, first=0):
+            res = None
             for i in range(first, first + n):
-                gstep(*pool[i % len(pool)])
+                res = gstep(*pool[i % len(pool)])
+            return res
         try:
             gstep = pkg.GraphedTrainStep(model, opt, *pool[0])
             tc = []
@@ -589,21 +647,26 @@ def main():
             if a.launch == "hipgraph":
                 raise
     timed = run if launch == "eager" else run_graph
-    if not a.no_prof and launch == "eager":
+    prof = a.full and not a.no_prof                         # HIP events around the GEMM launches: --full's roofline
+    if prof and launch == "eager":
         L.pl_prof_enable(prof_every(a.steps))
     barrier(); torch.cuda.synchronize()
     t0 = time.perf_counter()
-    timed(a.steps, a.warmup)
+    last = timed(a.steps, a.warmup)
     torch.cuda.synchronize(); barrier()
     dt = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:                        # before anything else runs on the model
+        sd = {"param." + k: v.detach().cpu().numpy() for k, v in model.state_dict().items()}
+        dump_outputs(a.dump_outputs, {"loss": last[0].detach().float().cpu().numpy(),
+                                      "pred": last[1].detach().float().cpu().numpy(), **sd})
     roofline = roofline_single = None
-    if not a.no_prof and launch == "hipgraph":
+    if prof and launch == "hipgraph":
         # (events cannot be read out of a replayed graph: the same kernels are sampled on eager steps right behind the timed region)
         n_prof = min(a.steps, 64)
         L.pl_prof_enable(prof_every(n_prof))
         run(n_prof, a.warmup + a.steps)
         torch.cuda.synchronize()
-    if not a.no_prof:
+    if prof:
         one = 2.0 * a.batch * 1024 * 1024                  # one 1024-wide GEMM: 8.59 GFLOP at B=4096
         traffic = None
         tpath = os.path.join(ROOT, "profiles", "traffic.json")
@@ -620,7 +683,7 @@ def main():
     # N > 1: what the gradient all-reduce costs the step -- the same steps with the collective stubbed out (every
     # rank keeps its local gradients; results are discarded).  exposed = synchronised step - stubbed step.
     exposed_us = None
-    if world > 1:
+    if world > 1 and a.full:
         class _NoSync(pkg.dp.GradSync):
             def launch_bucket(self, flat_slice):
                 pass
@@ -649,27 +712,17 @@ def main():
             x, y = pool[i % len(pool)]
             model.zero_grad(set_to_none=True)
             pkg.mse_loss(model(x).reshape(y.shape), y).backward()
-    run_fb(5)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    nfb = max(10, a.steps // 4)
-    run_fb(nfb)
-    torch.cuda.synchronize()
-    dt_fb = time.perf_counter() - t1
+    if a.full:
+        run_fb(5)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        nfb = max(10, a.steps // 4)
+        run_fb(nfb)
+        torch.cuda.synchronize()
+        dt_fb = time.perf_counter() - t1
 
     out = None
     if rank == 0:
-        # parity in the same run: eval forward vs the numpy oracle on a bench batch
-        import numpy as np
-        from oracle import lifter_oracle as orc
-        model.eval()
-        x, _ = pool[0]
-        with torch.no_grad():
-            y_gpu = model(x).cpu().numpy()
-        st = {k: v.detach().cpu().numpy() for k, v in model.state_dict().items()}
-        y_orc, _ = orc.forward(st, x.cpu().numpy(), num_stage=2, train=False)
-        mpjpe = orc.mpjpe_mm(y_gpu, y_orc)
-        model.train()
         poses = a.batch * world * a.steps
         value = poses / dt
         out = {
@@ -695,25 +748,38 @@ def main():
             "step_tflops": round(value * FLOP_PER_POSE / 1e12, 2),
             "step_frac_of_matrix_peak": round(value * FLOP_PER_POSE / 1e12 / (
                 (PEAK_F32_MATRIX_TFLOPS if a.dtype == "fp32" else PEAK_BF16_MATRIX_TFLOPS) * world), 4),
-            "fwd_bwd_only_poses_per_s_per_gpu": round(a.batch * nfb / dt_fb, 1),
-            "mpjpe_mm_eval_fwd_vs_oracle": float(f"{mpjpe:.3e}"),
-            "roofline": roofline,
-            "roofline_forward_gemm": roofline_single,
         }
-        if launch == "hipgraph":
-            for rf in (roofline, roofline_single):
-                if rf:
-                    rf["sampling"] += " -- of eager steps right behind the timed region (the timed steps are graph replays)"
-        if world > 1:
-            out["allreduce"] = {"overlap": not a.no_overlap, "exposed_us_per_step": exposed_us,
-                                "bytes": int(model.flat_grads.numel()) * 4,
-                                "how": "step time with the collective minus the same steps with it stubbed out"}
-        if world == 1:
-            out["batch_64"] = batch64_latency(pkg, a, dev)
-        if world == 1 and not a.no_extras:
-            out["other_modes"] = side_measurements(pkg, a, dev, x, y_orc)
-        if world == 1 and not a.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(a.batch)
+        if a.full:
+            # parity in the same run: eval forward vs the numpy oracle on a bench batch
+            from oracle import lifter_oracle as orc
+            model.eval()
+            x, _ = pool[0]
+            with torch.no_grad():
+                y_gpu = model(x).cpu().numpy()
+            st = {k: v.detach().cpu().numpy() for k, v in model.state_dict().items()}
+            y_orc, _ = orc.forward(st, x.cpu().numpy(), num_stage=2, train=False)
+            mpjpe = orc.mpjpe_mm(y_gpu, y_orc)
+            model.train()
+            out.update({
+                "fwd_bwd_only_poses_per_s_per_gpu": round(a.batch * nfb / dt_fb, 1),
+                "mpjpe_mm_eval_fwd_vs_oracle": float(f"{mpjpe:.3e}"),
+                "roofline": roofline,
+                "roofline_forward_gemm": roofline_single,
+            })
+            if launch == "hipgraph":
+                for rf in (roofline, roofline_single):
+                    if rf:
+                        rf["sampling"] += " -- of eager steps right behind the timed region (the timed steps are graph replays)"
+            if world > 1:
+                out["allreduce"] = {"overlap": not a.no_overlap, "exposed_us_per_step": exposed_us,
+                                    "bytes": int(model.flat_grads.numel()) * 4,
+                                    "how": "step time with the collective minus the same steps with it stubbed out"}
+            if world == 1:
+                out["batch_64"] = batch64_latency(pkg, a, dev)
+            if world == 1 and not a.no_extras:
+                out["other_modes"] = side_measurements(pkg, a, dev, x, y_orc)
+            if world == 1 and not a.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(a.batch)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

@@ -14,7 +14,7 @@ for a in args:
 res = {n: [] for n, _ in variants}
 for r in range(rounds):
     for name, env in variants:
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "100", "--warmup", "20",
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "100", "--warmup", "20",
                               "--no-cpu-baseline", "--no-extras"], env={**os.environ, **env}, capture_output=True,
                              text=True, timeout=600)
         line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]

@@ -6,7 +6,7 @@ n = int(sys.argv[1]) if len(sys.argv) > 1 else 6
 for extra in ([], ["--no-prof"]):
     vals = []
     for _ in range(n):
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "200", "--warmup", "20", "--no-cpu-baseline",
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "200", "--warmup", "20", "--no-cpu-baseline",
                               "--no-extras"] + extra, capture_output=True, text=True, timeout=600)
         vals.append(json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])["ms_per_step"])
     print(" ".join(extra) or "default", " ".join(f"{v:.4f}" for v in vals), flush=True)

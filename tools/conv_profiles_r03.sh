@@ -9,7 +9,7 @@ cd $R
 python tools/bench_model3d_train.py --B 256 --iters 5 > $O/m3d_b256.txt 2>&1; echo b256 rc=$?
 python tools/bench_model3d_train.py --B 32 --iters 10 --graph --skip-eager > $O/m3d_b32.txt 2>&1; echo b32 rc=$?
 python tools/bench_model3d_train.py --B 8 --iters 20 --graph > $O/m3d_b8.txt 2>&1; echo b8 rc=$?
-python bench.py --workload cycle > $O/cycle_b128.json 2> $O/cycle_b128.err; echo cycle rc=$?
+python bench.py --full --workload cycle > $O/cycle_b128.json 2> $O/cycle_b128.err; echo cycle rc=$?
 python bench.py --workload cycle --flip --no-cpu-baseline > $O/cycle_b128_flip.json 2> $O/cycle_flip.err; echo cycle-flip rc=$?
 python tools/bench_cycle.py --B 128 > $O/cycle_vs_eager_b128.txt 2>&1; echo cycle-eager rc=$?
 (echo "persistent form (default)"; python tools/bench_conv_gemm.py 20; echo; echo "one workgroup per tile (POSELIFT_PERSIST=0)"; POSELIFT_PERSIST=0 python tools/bench_conv_gemm.py 20) > $O/conv_gemm_shapes.txt 2>/dev/null; echo shapes rc=$?

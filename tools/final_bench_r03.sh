@@ -5,8 +5,8 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/final_r03b
 rm -rf $O; mkdir -p $O
 cd $R
-python bench.py > $O/bench_1gpu.json 2> $O/bench_1gpu.err; echo bench rc=$?
-POSELIFT_DIST_BACKEND=gloo python bench.py --gpus 2 --steps 20 --warmup 5 --no-extras > $O/dp2_gloo.json 2> $O/dp2.err; echo dp2 rc=$?
+python bench.py --full > $O/bench_1gpu.json 2> $O/bench_1gpu.err; echo bench rc=$?
+POSELIFT_DIST_BACKEND=gloo python bench.py --full --gpus 2 --steps 20 --warmup 5 --no-extras > $O/dp2_gloo.json 2> $O/dp2.err; echo dp2 rc=$?
 POSELIFT_DIST_BACKEND=gloo python bench.py --gpus 2 --workload cycle --batch 16 --steps 3 --warmup 1 > $O/cycle_dp2_gloo.json 2> $O/cycle_dp2.err; echo cycle-dp2 rc=$?
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -o f -- python3 $R/bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-prof --launch eager > $O/pmc_fetch.json 2> $O/pmc_fetch.err; echo fetch rc=$?
