@@ -13,4 +13,5 @@ from .heads import soft_argmax_2d, soft_argmax_3d, soft_argmax_3d_nhwc  # noqa: 
 from .losses import TriangleLoss, l1_loss, l1_terms  # noqa: F401
 from .backbone import Model_2D, Model_3D, ResNet  # noqa: F401
 from .data import PoseFeeder, epoch_indices  # noqa: F401
-from . import arena, backbone, conv, data, dp, layout, synth  # noqa: F401
+from .vit import MyViT  # noqa: F401
+from . import arena, backbone, conv, data, dp, layout, synth, vit  # noqa: F401

@@ -197,6 +197,22 @@ SIGNATURES = {
     "pl_conv2d_planes_wgrad_hw": (_c.c_int, [_c.c_int, _P, _c.c_int64, _P, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64,
                                              _c.c_int64, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
                                              _c.c_int, _P, _c.c_float, _P, _P, _P]),
+    "pl_vit_attn_supported": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int]),
+    "pl_vit_embed_fwd": (_c.c_int, [_P, _c.c_int64, _c.c_int, _c.c_int, _P, _P, _P, _c.c_int, _P, _P]),
+    "pl_vit_embed_bwd_scratch_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int, _c.c_int]),
+    "pl_vit_embed_bwd": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _P, _P, _P]),
+    "pl_vit_ln_fwd": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int, _c.c_int, _P, _P, _P, _P, _c.c_float, _P, _P, _P, _P]),
+    "pl_vit_ln_bwd_scratch_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int, _c.c_int]),
+    "pl_vit_ln_bwd": (_c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_int, _c.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "pl_vit_attn_fwd": (_c.c_int, [_P, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _c.c_float, _P, _P, _P]),
+    "pl_vit_attn_bwd": (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _c.c_float, _P, _P]),
+    "pl_vit_gelu_fwd": (_c.c_int, [_P, _c.c_int64, _P, _P]),
+    "pl_vit_gelu_bwd": (_c.c_int, [_P, _P, _c.c_int64, _P, _P]),
+    "pl_vit_head_fwd": (_c.c_int, [_P, _c.c_int64, _c.c_int, _P, _P, _c.c_int, _P, _P]),
+    "pl_vit_head_bwd_scratch_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int, _c.c_int]),
+    "pl_vit_head_bwd": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int, _P, _c.c_int, _P, _P, _P, _P]),
+    "pl_vit_planes_scratch_bytes": (_c.c_size_t, []),
+    "pl_vit_planes_dyn": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _c.c_int64, _P, _P, _P, _P, _P]),
     "pl_prof_enable": (_c.c_int, [_c.c_int]),
     "pl_prof_read": (_c.c_int, [_c.c_double, _c.c_double, _c.POINTER(_c.c_double), _c.POINTER(_c.c_int64),
                                 _c.POINTER(_c.c_double)]),

@@ -12,7 +12,7 @@ ResNet, the way optim.FlatAdamW does for the lifter:
     the first backward of a step overwrites, a second one in the same step (two forward passes: the phase5 Flip branch)
     accumulates.  No `p.grad += dw` launches, no layout copies.
   * FlatAdam.step(): ONE pl_adamw_flat launch over the whole arena (weight_decay 0 = torch.optim.Adam's default; Adam's
-    coupled L2 decay is not implemented), in torch's single-tensor update order; the 1/world average of a data-parallel sum
+    coupled L2 decay is not implemented; decoupled_weight_decay=True is torch.optim.AdamW), in torch's single-tensor update order; the 1/world average of a data-parallel sum
     folds into it (grad_scale).  zero_grad() sets .grad to None and launches nothing.
 A torch.optim.Optimizer subclass: LR schedulers and the stock Adam state_dict layout ('step', 'exp_avg', 'exp_avg_sq' per
 parameter) work unchanged; capturable=True keeps the step count on the device for train.GraphedModuleStep.
@@ -71,6 +71,15 @@ class ModuleArena:
         return runs
 
 
+_generation = 0
+
+
+def weight_generation():
+    """Advanced by every FlatAdam.step(): the step writes the parameters through raw pointers (their _version does not
+    move), so caches derived from parameter values (the f16x3 weight planes of vit.MyViT) key on this counter too."""
+    return _generation
+
+
 def arena_of(module):
     a = getattr(module, "_pl_arena", None)
     if a is None or not a.intact():
@@ -81,11 +90,15 @@ def arena_of(module):
 class FlatAdam(torch.optim.Optimizer):
     """torch.optim.Adam(module.parameters(), lr, betas, eps) as one library launch over the module's flat arenas."""
 
-    def __init__(self, module, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable=False):
-        if weight_decay != 0.0:
-            raise NotImplementedError("FlatAdam: Adam's coupled L2 weight decay is not implemented (the reference uses 0)")
+    def __init__(self, module, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable=False,
+                 decoupled_weight_decay=False):
+        if weight_decay != 0.0 and not decoupled_weight_decay:
+            raise NotImplementedError("FlatAdam: Adam's coupled L2 weight decay is not implemented (the reference uses 0); "
+                                      "decoupled_weight_decay=True is AdamW")
         self.arena = arena_of(module)
-        super().__init__(self.arena.params, dict(lr=lr, betas=betas, eps=eps, weight_decay=0.0, capturable=bool(capturable)))
+        super().__init__(self.arena.params, dict(lr=lr, betas=betas, eps=eps, weight_decay=float(weight_decay),
+                                                 capturable=bool(capturable),
+                                                 decoupled_weight_decay=bool(decoupled_weight_decay)))
         a = self.arena
         self._m, self._v = torch.zeros_like(a.flat), torch.zeros_like(a.flat)
         self._t = 0
@@ -115,6 +128,8 @@ class FlatAdam(torch.optim.Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None, grad_scale=1.0):
+        global _generation
+        _generation += 1
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -125,6 +140,7 @@ class FlatAdam(torch.optim.Optimizer):
                                      "build the optimizer after moving the module")
         runs = a.gather_grads()
         L, lr = _lib.lib(), g["lr"]
+        wd = float(g["weight_decay"]) if g.get("decoupled_weight_decay", False) else 0.0
         cap = bool(g.get("capturable", False))
         with _lib.on_device(a.flat.device):
             if cap:
@@ -137,7 +153,7 @@ class FlatAdam(torch.optim.Optimizer):
                 for lo, hi in runs:
                     _lib.check(L.pl_adamw_flat_dev(a.flat.data_ptr() + 4 * lo, a.grad.data_ptr() + 4 * lo, self._m.data_ptr() + 4 * lo,
                                                    self._v.data_ptr() + 4 * lo, hi - lo, lr_ptr, float(g["betas"][0]),
-                                                   float(g["betas"][1]), float(g["eps"]), 0.0, 1, self._t_dev.data_ptr(),
+                                                   float(g["betas"][1]), float(g["eps"]), wd, 1, self._t_dev.data_ptr(),
                                                    float(grad_scale), _lib.current_stream_ptr()), "pl_adamw_flat_dev")
                 _lib.check(L.pl_counter_add(self._t_dev.data_ptr(), 1, _lib.current_stream_ptr()), "pl_counter_add")
             else:
@@ -145,7 +161,7 @@ class FlatAdam(torch.optim.Optimizer):
                 for lo, hi in runs:
                     _lib.check(L.pl_adamw_flat(a.flat.data_ptr() + 4 * lo, a.grad.data_ptr() + 4 * lo, self._m.data_ptr() + 4 * lo,
                                                self._v.data_ptr() + 4 * lo, hi - lo, float(lr), float(g["betas"][0]),
-                                               float(g["betas"][1]), float(g["eps"]), 0.0, self._t, float(grad_scale),
+                                               float(g["betas"][1]), float(g["eps"]), wd, self._t, float(grad_scale),
                                                _lib.current_stream_ptr()), "pl_adamw_flat")
                 self._step_tensor.fill_(float(self._t))
         return loss

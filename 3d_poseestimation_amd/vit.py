@@ -1,0 +1,379 @@
+"""MyViT, the transformer lifter of phase1_lifting/baselineModel.py:220-362 (the model train_1.py:35 trains; phase5's
+3D->2D projector is MyViT(chw=(1,17,3), out_d=2)), on the HIP library.
+
+Per token (T = seq * B rows of H = hidden_d features):
+    x = x2d Wm^T + bm + pos_embed                       pl_vit_embed_fwd
+    per block:  x += to_out(attn(mhsa.norm(norm1(x))))  pl_vit_ln_fwd (both LayerNorms, one pass), GEMM, pl_vit_attn_fwd, GEMM
+                x += mlp.2(GELU(mlp.0(norm2(x))))       pl_vit_ln_fwd (the residual add in front), GEMM, pl_vit_gelu_fwd, GEMM
+    head:       mlp.2(ReLU(mlp.0(x)))                   pl_vit_ln_fwd (the last residual add), GEMM, pl_vit_head_fwd
+The whole forward is ONE autograd node (_ViTFn); its backward runs the same kernels' backward forms and returns every
+parameter gradient (pos_embed's only when it requires one).  No dropout, no BatchNorm: train and eval forward are one path.
+
+compute_dtype
+  "fp32"   every Linear on the fp32 MFMA GEMM (pl_gemm_f32).
+  "f16x3"  the block Linears (qkv, to_out, mlp.0, mlp.2: forward, data and weight gradients) on the planes GEMM
+           (pl_gemm_planes_raw: two fp16 planes per operand, three MFMAs per product).  Activations and gradients are
+           split with a power-of-two scale chosen on the device from their max |x| (pl_vit_planes_dyn) -- never a fixed
+           scale; the weights with the static weight-plane scale, cached until the next FlatAdam step (arena.weight_generation)
+           or the next in-place change of the parameter (its _version).  The token head's Linears stay fp32 (the
+           residual stream they read is not normalised).
+"""
+import numpy as np
+import torch
+from torch import nn
+
+from . import _lib, arena, conv
+
+DIM_HEAD = 64
+_DTYPES = ("f16x3", "fp32")
+
+
+def positional_embeddings(seq, d):
+    """pos[i][j] = sin(i / 10000^(j/d)) for even j, cos(i / 10000^((j-1)/d)) for odd j: evaluated per element in float64
+    (numpy's sin / cos of the double quotient) and rounded to float32, as the reference builds it."""
+    out = torch.ones(seq, d)
+    for i in range(seq):
+        for j in range(d):
+            e = j if j % 2 == 0 else j - 1
+            arg = i / ((1e4) ** (e / d))
+            out[i][j] = np.sin(arg) if j % 2 == 0 else np.cos(arg)
+    return out
+
+
+class Attention(nn.Module):
+    """Parameter holder with the reference's names: norm, attend (no parameters), to_qkv, to_out."""
+
+    def __init__(self, dim, heads, dim_head):
+        super().__init__()
+        self.heads, self.scale = heads, dim_head ** -0.5
+        self.norm = nn.LayerNorm(dim)
+        self.attend = nn.Softmax(dim=-1)
+        self.to_qkv = nn.Linear(dim, dim_head * heads * 3, bias=False)
+        self.to_out = nn.Linear(dim_head * heads, dim, bias=False)
+
+
+class MyViTBlock(nn.Module):
+    def __init__(self, hidden_d, n_heads, mlp_ratio=4):
+        super().__init__()
+        self.hidden_d, self.n_heads = hidden_d, n_heads
+        self.norm1 = nn.LayerNorm(hidden_d)
+        self.mhsa = Attention(hidden_d, n_heads, int(hidden_d / n_heads))
+        self.norm2 = nn.LayerNorm(hidden_d)
+        self.mlp = nn.Sequential(nn.Linear(hidden_d, mlp_ratio * hidden_d), nn.GELU(), nn.Linear(mlp_ratio * hidden_d, hidden_d))
+
+
+def _check_shape(chw, n_blocks, hidden_d, n_heads, out_d):
+    seq, in_d = int(chw[1]), int(chw[2])
+    if n_heads < 1 or hidden_d % n_heads or hidden_d // n_heads != DIM_HEAD:
+        raise _lib.PoseliftError(f"MyViT: dim_head = hidden_d / n_heads must be {DIM_HEAD} (hidden_d={hidden_d}, n_heads={n_heads})")
+    if not 1 <= seq <= 32:
+        raise _lib.PoseliftError(f"MyViT: the attention kernels take sequences of 1 .. 32 tokens, not {seq}")
+    if not 1 <= in_d <= 8:
+        raise _lib.PoseliftError(f"MyViT: token input width {in_d} (1 .. 8 supported)")
+    # pl_vit_attn_bwd stages a sample's q, k, v, dO and two [heads][seq][32] score tiles in LDS (160 KB)
+    lds = 4 * (seq * (3 * hidden_d + 1) + seq * (hidden_d + 1) + 2 * n_heads * seq * 32)
+    if hidden_d > 512 or lds > 160 * 1024:
+        raise _lib.PoseliftError(f"MyViT: hidden_d {hidden_d} with {seq} tokens does not fit the attention kernels")
+    if not 1 <= out_d <= 4:
+        raise _lib.PoseliftError(f"MyViT: out_d {out_d} unsupported (1 .. 4)")
+    if n_blocks < 1:
+        raise _lib.PoseliftError("MyViT: at least one block")
+
+
+class MyViT(nn.Module):
+    """baselineModel.MyViT with the same submodules, names, creation order (a seeded construction draws the reference's
+    initial weights) and state_dict; compute_dtype selects the GEMM arithmetic (module docstring)."""
+
+    def __init__(self, chw=(1, 17, 2), n_blocks=2, hidden_d=256, n_heads=4, out_d=3, compute_dtype="f16x3"):
+        super().__init__()
+        if compute_dtype not in _DTYPES:
+            raise _lib.PoseliftError(f"MyViT: compute_dtype {compute_dtype!r} (one of {_DTYPES})")
+        _check_shape(chw, n_blocks, hidden_d, n_heads, out_d)
+        self.chw, self.n_block, self.n_heads, self.hidden_d, self.out_d = tuple(chw), n_blocks, n_heads, hidden_d, out_d
+        self.compute_dtype = compute_dtype
+        self.input_d = chw[2]
+        self.linear_mapper = nn.Linear(self.input_d, self.hidden_d)
+        self.pos_embed = nn.Parameter(positional_embeddings(chw[1], self.hidden_d))
+        self.pos_embed.requires_grad = False
+        self.blocks = nn.ModuleList([MyViTBlock(hidden_d, n_heads) for _ in range(n_blocks)])
+        self.mlp = nn.Sequential(nn.Linear(self.hidden_d, int(self.hidden_d / 2)), nn.ReLU(), nn.Linear(int(self.hidden_d / 2), out_d))
+        self._wcache = {}
+
+    def _params(self):
+        ps = [self.linear_mapper.weight, self.linear_mapper.bias, self.pos_embed]
+        for b in self.blocks:
+            ps += [b.norm1.weight, b.norm1.bias, b.mhsa.norm.weight, b.mhsa.norm.bias, b.mhsa.to_qkv.weight, b.mhsa.to_out.weight,
+                   b.norm2.weight, b.norm2.bias, b.mlp[0].weight, b.mlp[0].bias, b.mlp[2].weight, b.mlp[2].bias]
+        ps += [self.mlp[0].weight, self.mlp[0].bias, self.mlp[2].weight, self.mlp[2].bias]
+        return ps
+
+    def _wplanes(self, w):
+        """(planes of W [N][K], planes of W^T [K][N]) with the weight-plane scale; rebuilt after a FlatAdam step or any
+        in-place change of the parameter."""
+        key = (arena.weight_generation(), w._version, w.data_ptr())
+        hit = self._wcache.get(id(w))
+        if hit is not None and hit[0] == key:
+            return hit[1]
+        wd = w.detach()
+        planes = (conv._planes_of(wd, conv.WEIGHT_PLANE_SCALE), conv._planes_of(wd.t(), conv.WEIGHT_PLANE_SCALE))
+        self._wcache[id(w)] = (key, planes)
+        return planes
+
+    def forward(self, images):
+        if images.dim() != 3 or images.shape[1] != self.chw[1] or images.shape[2] != self.input_d:
+            raise ValueError(f"MyViT expects (B, {self.chw[1]}, {self.input_d}) input, got {tuple(images.shape)}")
+        x = images.float().contiguous()
+        _lib.require_device_tensor(x, "input")
+        ps = self._params()
+        for p in ps:
+            _lib.require_device_tensor(p.data, "parameter")
+        need = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in ps))
+        return _ViTFn.apply(self, need, x, *ps)
+
+
+# ------------------------------------------------------------------------------------------------ host-side launch helpers
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _run(name, *args):
+    _lib.check(getattr(_lib.lib(), name)(*args, _lib.current_stream_ptr()), name)
+
+
+def _gemm_f32(layout, A, B, M, N, K, bias=None, out=None):
+    """C [M][N] = op(A) op(B) (+ bias) on the fp32 MFMA GEMM; weight gradients (TN) split over the token rows."""
+    C = torch.empty(M, N, device=A.device) if out is None else out
+    split, slabs = 1, None
+    if layout == 2:
+        tiles = ((M + 127) // 128) * ((N + 127) // 128)
+        split = max(1, min(32, 256 // tiles, K // 512))
+        if split > 1:
+            slabs = torch.empty(split * M * N, device=A.device)
+    _run("pl_gemm_f32", layout, A.data_ptr(), B.data_ptr(), C.data_ptr(), M, N, K, _ptr(bias), split, _ptr(slabs))
+    return C
+
+
+def _pad32(n):
+    return (n + 31) // 32 * 32
+
+
+class _Planes:
+    """fp16 planes of an activation / gradient [rows][cols] in a [rows_pad][cols] carrier, and its device scale
+    {S, 1/S, 1/(S S_other)}."""
+    __slots__ = ("p", "scale", "rows", "cols", "rows_pad")
+
+    def __init__(self, x, rows_pad, other=None):
+        rows, cols = x.shape
+        self.rows, self.cols, self.rows_pad = rows, cols, rows_pad
+        self.p = torch.empty(rows_pad, cols, device=x.device)
+        self.scale = torch.empty(4, device=x.device)
+        scratch = torch.empty(_lib.lib().pl_vit_planes_scratch_bytes(), dtype=torch.uint8, device=x.device)
+        _run("pl_vit_planes_dyn", x.data_ptr(), rows, cols, rows_pad, _ptr(other.scale if other is not None else None),
+             self.scale.data_ptr(), self.p.data_ptr(), scratch.data_ptr())
+
+
+def _pgemm_fwd(ap, wp, N, bias=None):
+    """y [rows][N] = a W^T (+ bias): a as dynamic planes, W [N][K] as weight planes."""
+    L, K, M = _lib.lib(), ap.cols, ap.rows
+    C = torch.empty(M, N, device=ap.p.device)
+    splits = L.pl_gemm_planes_splits(M, N, K)
+    slabs = torch.empty(splits * M * N, device=C.device) if splits > 1 else None
+    _run("pl_gemm_planes_raw", 0, _lib.PL_F16X3, ap.p.data_ptr(), ap.rows_pad * K, K, wp.data_ptr(), N * K, K, C.data_ptr(),
+         M, N, K, _ptr(bias if splits == 1 else None), 1.0 / conv.WEIGHT_PLANE_SCALE, ap.scale.data_ptr() + 4, _ptr(slabs), None)
+    if bias is not None and splits > 1:
+        C.add_(bias)
+    return C
+
+
+def _pgemm_wgrad(gp, ap):
+    """dW [gp.cols][ap.cols] = g^T a over the (zero-padded) token rows, both operands as dynamic planes; gp was split with
+    other=ap, so gp.scale[2] = 1 / (S_g S_a)."""
+    return conv._gemm_planes_raw(2, gp.p, (gp.rows_pad, gp.cols), ap.p, (ap.rows_pad, ap.cols), gp.cols, ap.cols, gp.rows_pad,
+                                 1.0, gp.scale[2:3])
+
+
+def _pgemm_dgrad(gp, wtp, K_in):
+    """dx [rows][K_in] = g W: g as dynamic planes, W^T [K_in][N] as weight planes (NT)."""
+    return conv._gemm_planes_raw(0, gp.p, (gp.rows_pad, gp.cols), wtp, (K_in, gp.cols), gp.rows, K_in, gp.cols,
+                                 1.0 / conv.WEIGHT_PLANE_SCALE, gp.scale[1:2])
+
+
+def _colsum(x):
+    rows, cols = x.shape
+    out = torch.empty(cols, device=x.device)
+    scratch = torch.empty(_lib.lib().pl_colsum_scratch_bytes(rows, cols), dtype=torch.uint8, device=x.device)
+    _run("pl_colsum", x.data_ptr(), rows, cols, out.data_ptr(), scratch.data_ptr())
+    return out
+
+
+class _ViTFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, model, want, x2d, *ps):
+        B, seq, in_d = x2d.shape
+        H, heads, out_d = model.hidden_d, model.n_heads, model.out_d
+        T, dev, f16 = B * seq, x2d.device, model.compute_dtype == "f16x3"
+        Tp = _pad32(T)
+        eps = 1e-5
+        Wm, bm, pos = ps[0], ps[1], ps[2]
+        saved = []
+        with _lib.on_device(dev):
+            x = torch.empty(T, H, device=dev)
+            _run("pl_vit_embed_fwd", x2d.data_ptr(), T, in_d, seq, Wm.data_ptr(), bm.data_ptr(), pos.data_ptr(), H, x.data_ptr())
+            add = None
+            for bi in range(model.n_block):
+                (g1, b1, g2, b2, wqkv, wout, g3, b3, w0, b0, w2, b2m) = ps[3 + 12 * bi: 15 + 12 * bi]
+                xb = torch.empty(T, H, device=dev) if add is not None else x
+                a = torch.empty(T, H, device=dev)
+                st12 = torch.empty(4, T, device=dev)
+                _run("pl_vit_ln_fwd", x.data_ptr(), _ptr(add), T, H, 2, g1.data_ptr(), b1.data_ptr(), g2.data_ptr(), b2.data_ptr(),
+                     eps, _ptr(xb if add is not None else None), a.data_ptr(), st12.data_ptr())
+                if f16:
+                    ap = _Planes(a, Tp)
+                    qkv = _pgemm_fwd(ap, model._wplanes(wqkv)[0], 3 * H)
+                else:
+                    qkv = _gemm_f32(0, a, wqkv, T, 3 * H, H)
+                o = torch.empty(T, H, device=dev)
+                lse = torch.empty(B, heads, seq, device=dev)
+                _run("pl_vit_attn_fwd", qkv.data_ptr(), B, seq, heads, DIM_HEAD, DIM_HEAD ** -0.5, o.data_ptr(), lse.data_ptr())
+                if f16:
+                    op = _Planes(o, Tp)
+                    u = _pgemm_fwd(op, model._wplanes(wout)[0], H)
+                else:
+                    u = _gemm_f32(0, o, wout, T, H, H)
+                xa = torch.empty(T, H, device=dev)
+                n2 = torch.empty(T, H, device=dev)
+                st3 = torch.empty(2, T, device=dev)
+                _run("pl_vit_ln_fwd", xb.data_ptr(), u.data_ptr(), T, H, 1, g3.data_ptr(), b3.data_ptr(), None, None, eps,
+                     xa.data_ptr(), n2.data_ptr(), st3.data_ptr())
+                if f16:
+                    n2p = _Planes(n2, Tp)
+                    h = _pgemm_fwd(n2p, model._wplanes(w0)[0], 4 * H, b0)
+                else:
+                    h = _gemm_f32(0, n2, w0, T, 4 * H, H, b0)
+                g = torch.empty_like(h)
+                _run("pl_vit_gelu_fwd", h.data_ptr(), h.numel(), g.data_ptr())
+                if f16:
+                    gp = _Planes(g, Tp)
+                    m = _pgemm_fwd(gp, model._wplanes(w2)[0], H, b2m)
+                else:
+                    m = _gemm_f32(0, g, w2, T, H, 4 * H, b2m)
+                if want:
+                    if f16:
+                        saved.append(dict(xb=xb, st12=st12, ap=ap, qkv=qkv, lse=lse, op=op, xa=xa, st3=st3, n2p=n2p, h=h, gp=gp))
+                    else:
+                        saved.append(dict(xb=xb, st12=st12, a=a, qkv=qkv, lse=lse, o=o, xa=xa, st3=st3, n2=n2, h=h, g=g))
+                x, add = xa, m
+            xf = torch.empty(T, H, device=dev)
+            _run("pl_vit_ln_fwd", x.data_ptr(), add.data_ptr(), T, H, 0, None, None, None, None, eps, xf.data_ptr(), None, None)
+            wh, bh, wl, bl = ps[-4:]
+            z = _gemm_f32(0, xf, wh, T, H // 2, H, bh)
+            y = torch.empty(B, seq, out_d, device=dev)
+            _run("pl_vit_head_fwd", z.data_ptr(), T, H // 2, wl.data_ptr(), bl.data_ptr(), out_d, y.data_ptr())
+        if want:
+            ctx.model, ctx.saved, ctx.x2d, ctx.xf, ctx.z, ctx.ps = model, saved, x2d, xf, z, ps
+            ctx.dims = (B, seq, in_d, T, Tp, f16)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        model, saved, ps = ctx.model, ctx.saved, ctx.ps
+        B, seq, in_d, T, Tp, f16 = ctx.dims
+        H, heads, out_d = model.hidden_d, model.n_heads, model.out_d
+        dev = dy.device
+        dy = dy.float().contiguous()
+        grads = [None] * len(ps)
+        L = _lib.lib()
+        with _lib.on_device(dev):
+            wh, bh, wl, bl = ps[-4:]
+            dz = torch.empty(T, H // 2, device=dev)
+            dwbl = torch.empty(out_d * (H // 2) + out_d, device=dev)
+            scratch = torch.empty(L.pl_vit_head_bwd_scratch_bytes(T, H // 2, out_d), dtype=torch.uint8, device=dev)
+            _run("pl_vit_head_bwd", dy.data_ptr(), ctx.z.data_ptr(), T, H // 2, wl.data_ptr(), out_d, dz.data_ptr(),
+                 dwbl.data_ptr(), scratch.data_ptr())
+            grads[-2], grads[-1] = dwbl[:out_d * (H // 2)].view(out_d, H // 2), dwbl[out_d * (H // 2):]
+            grads[-4] = _gemm_f32(2, dz, ctx.xf, H // 2, H, T)
+            grads[-3] = _colsum(dz)
+            dx = _gemm_f32(1, dz, wh, T, H, H // 2)              # d(block output) = d(x_final)
+            lnscratch = torch.empty(max(L.pl_vit_ln_bwd_scratch_bytes(T, H, 2), 4), dtype=torch.uint8, device=dev)
+            for bi in reversed(range(model.n_block)):
+                (g1, b1, g2, b2, wqkv, wout, g3, b3, w0, b0, w2, b2m) = ps[3 + 12 * bi: 15 + 12 * bi]
+                s = saved[bi]
+                base = 3 + 12 * bi
+                # mlp: m = mlp.2(GELU(mlp.0(n2)));  dm = dx
+                if f16:
+                    dmp = _Planes(dx, Tp, other=s["gp"])
+                    grads[base + 10] = _pgemm_wgrad(dmp, s["gp"])
+                    dg = _pgemm_dgrad(dmp, model._wplanes(w2)[1], 4 * H)
+                else:
+                    grads[base + 10] = _gemm_f32(2, dx, s["g"], H, 4 * H, T)
+                    dg = _gemm_f32(1, dx, w2, T, 4 * H, H)
+                grads[base + 11] = _colsum(dx)
+                dh = dg
+                _run("pl_vit_gelu_bwd", s["h"].data_ptr(), dg.data_ptr(), dg.numel(), dh.data_ptr())
+                if f16:
+                    dhp = _Planes(dh, Tp, other=s["n2p"])
+                    grads[base + 8] = _pgemm_wgrad(dhp, s["n2p"])
+                    dn2 = _pgemm_dgrad(dhp, model._wplanes(w0)[1], H)
+                else:
+                    grads[base + 8] = _gemm_f32(2, dh, s["n2"], 4 * H, H, T)
+                    dn2 = _gemm_f32(1, dh, w0, T, H, 4 * H)
+                grads[base + 9] = _colsum(dh)
+                del dg, dh
+                # norm2 with the residual: dxa = dx + LN3'(dn2)
+                dxa = torch.empty(T, H, device=dev)
+                dgb3 = torch.empty(2 * H, device=dev)
+                _run("pl_vit_ln_bwd", dn2.data_ptr(), dx.data_ptr(), s["xa"].data_ptr(), s["st3"].data_ptr(), T, H, 1,
+                     g3.data_ptr(), None, None, dxa.data_ptr(), dgb3.data_ptr(), lnscratch.data_ptr())
+                grads[base + 6], grads[base + 7] = dgb3[:H], dgb3[H:]
+                # attention: u = to_out(o)
+                if f16:
+                    dup = _Planes(dxa, Tp, other=s["op"])
+                    grads[base + 5] = _pgemm_wgrad(dup, s["op"])
+                    do = _pgemm_dgrad(dup, model._wplanes(wout)[1], H)
+                else:
+                    grads[base + 5] = _gemm_f32(2, dxa, s["o"], H, H, T)
+                    do = _gemm_f32(1, dxa, wout, T, H, H)
+                dqkv = torch.empty(T, 3 * H, device=dev)
+                _run("pl_vit_attn_bwd", s["qkv"].data_ptr(), s["lse"].data_ptr(), do.data_ptr(), B, seq, heads, DIM_HEAD,
+                     DIM_HEAD ** -0.5, dqkv.data_ptr())
+                if f16:
+                    dqp = _Planes(dqkv, Tp, other=s["ap"])
+                    grads[base + 4] = _pgemm_wgrad(dqp, s["ap"])
+                    da = _pgemm_dgrad(dqp, model._wplanes(wqkv)[1], H)
+                else:
+                    grads[base + 4] = _gemm_f32(2, dqkv, s["a"], 3 * H, H, T)
+                    da = _gemm_f32(1, dqkv, wqkv, T, H, 3 * H)
+                # norm1 -> mhsa.norm with the residual: dx = dxa + LN1'(LN2'(da))
+                dxb = torch.empty(T, H, device=dev)
+                dgb12 = torch.empty(4 * H, device=dev)
+                _run("pl_vit_ln_bwd", da.data_ptr(), dxa.data_ptr(), s["xb"].data_ptr(), s["st12"].data_ptr(), T, H, 2,
+                     g1.data_ptr(), b1.data_ptr(), g2.data_ptr(), dxb.data_ptr(), dgb12.data_ptr(), lnscratch.data_ptr())
+                grads[base + 0], grads[base + 1] = dgb12[:H], dgb12[H:2 * H]
+                grads[base + 2], grads[base + 3] = dgb12[2 * H:3 * H], dgb12[3 * H:]
+                dx = dxb
+            Wm, pos = ps[0], ps[2]
+            dwb = torch.empty(H * in_d + H, device=dev)
+            dpos = torch.empty(seq, H, device=dev) if ctx.needs_input_grad[5] else None
+            need_x = ctx.needs_input_grad[2]
+            dx2d = torch.empty(B, seq, in_d, device=dev) if need_x else None
+            scratch = torch.empty(L.pl_vit_embed_bwd_scratch_bytes(T, in_d, H), dtype=torch.uint8, device=dev)
+            _run("pl_vit_embed_bwd", dx.data_ptr(), ctx.x2d.data_ptr(), T, in_d, seq, H, Wm.data_ptr(), dwb.data_ptr(),
+                 _ptr(dpos), _ptr(dx2d), scratch.data_ptr())
+            grads[0], grads[1], grads[2] = dwb[:H * in_d].view(H, in_d), dwb[H * in_d:], dpos
+        ctx.saved = ctx.ps = ctx.xf = ctx.z = ctx.x2d = None
+        out = []
+        for i, (p, gr) in enumerate(zip(ps, grads)):
+            out.append(gr.view(p.shape) if (gr is not None and ctx.needs_input_grad[3 + i]) else None)
+        return (None, None, dx2d) + tuple(out)
+
+
+def supported(seq, hidden_d, n_heads):
+    """Shapes the kernels take (the constructor raises PoseliftError on the others)."""
+    try:
+        _check_shape((1, seq, 2), 1, hidden_d, n_heads, 3)
+    except _lib.PoseliftError:
+        return False
+    return True
+
+
+__all__ = ["MyViT", "positional_embeddings", "supported"]

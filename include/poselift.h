@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define PL_VERSION 109 /* 0.1.9: + pl_conv2d_planes_fwd_hw, pl_conv2d_planes_wgrad_hw (the stem on the planes GEMM); 0.1.8: + pl_lifter_train_step, pl_lifter_step_carries_adamw; 0.1.7: + pl_workspace_bitmap_format (small-batch layer kernels); 0.1.6: + pl_counter_add; 0.1.5: + pl_flip_pose_ex, pl_flip_w_nhwc (phase5 Flip branch); 0.1.4: + pl_planes_split_strided; 0.1.3: + pl_bn_join_bwd (0.1.2: operand-plane outputs of the BatchNorm / join kernels, pl_gemm_planes_raw) */
+#define PL_VERSION 110 /* 0.1.10: + pl_vit_* (the MyViT transformer lifter); 0.1.9: + pl_conv2d_planes_fwd_hw, pl_conv2d_planes_wgrad_hw (the stem on the planes GEMM); 0.1.8: + pl_lifter_train_step, pl_lifter_step_carries_adamw; 0.1.7: + pl_workspace_bitmap_format (small-batch layer kernels); 0.1.6: + pl_counter_add; 0.1.5: + pl_flip_pose_ex, pl_flip_w_nhwc (phase5 Flip branch); 0.1.4: + pl_planes_split_strided; 0.1.3: + pl_bn_join_bwd (0.1.2: operand-plane outputs of the BatchNorm / join kernels, pl_gemm_planes_raw) */
 
 typedef enum PLStatus {
   PL_OK = 0,
@@ -584,6 +584,55 @@ int pl_softargmax_fwd(const float* logits, int64_t BJ, int64_t D, int64_t H, int
 int pl_softargmax_bwd(const float* logits, const float* stats, const float* gcoords, int64_t BJ,
                       int64_t D, int64_t H, int64_t W, int ncoord, int centred, float* dlogits,
                       void* stream);
+
+/* ---- MyViT, the transformer lifter (phase1_lifting/baselineModel.py:220-362) ------------ */
+/* The non-GEMM parts of its forward and backward (vit.hip); its Linears run on pl_gemm_f32 / pl_gemm_planes_raw.
+ * T = B * seq token rows of H features, row-major.  Parameter gradients are reduced in a fixed order (per-256-row
+ * partial sums in `scratch`, then one ordered pass): bitwise repeatable.
+ *   pl_vit_embed_fwd : x = x2d W^T + b + pos[t % seq]   (x2d [T][in_d], W [H][in_d], pos [seq][H]); in_d <= 8
+ *   pl_vit_embed_bwd : dWb [H*in_d + H] = dW (the parameter's layout), then db; dpos [seq][H] (NULL: not wanted);
+ *                      dx2d [T][in_d] (NULL: not wanted; needs W)
+ *   pl_vit_ln_fwd    : x_out = x + add (add may be NULL: no residual add, x_out unused), then nnorm chained
+ *                      LayerNorms (0, 1 or 2: norm1 then mhsa.norm) -> y; stats [nnorm][2][T] = row mean about the row's
+ *                      first element (exact for a large mean and a small spread), 1/std.
+ *                      H % 4 == 0, H <= 1024, 16-byte aligned rows
+ *   pl_vit_ln_bwd    : dx = dres (may be NULL) + the chained LayerNorm backward of dy; x is the first LayerNorm's
+ *                      input; dgb [nnorm][2][H] = dgamma, dbeta of each LayerNorm; b1 is needed when nnorm == 2
+ *   pl_vit_attn_fwd  : qkv [B*seq][3*heads*64] (q | k | v, "b n (h d)") -> o [B*seq][heads*64] =
+ *                      softmax(scale q k^T) v per (sample, head); lse [B][heads][seq] for the backward.  seq <= 32,
+ *                      dim_head == 64 (pl_vit_attn_supported)
+ *   pl_vit_attn_bwd  : dqkv from qkv, lse and dO (P recomputed)
+ *   pl_vit_gelu_*    : exact GELU 0.5 u (1 + erf(u / sqrt 2)); du = dy GELU'(u)
+ *   pl_vit_head_fwd  : y = relu(z) W^T + b  (z [T][K], W [out_d][K]); K <= 256, out_d <= 4
+ *   pl_vit_head_bwd  : dz = [z > 0] dy W; dWb [out_d*K + out_d] = dW, then db
+ *   pl_vit_planes_dyn: PL_F16X3 operand planes of x [rows][cols] (cols % 4 == 0) in a [rows_pad][cols] carrier (rows
+ *                      past `rows` zero: a padded contraction for the TN weight gradients) with S the power of two
+ *                      that maps max |x| into [2^13, 2^14), chosen on the device; scale (device, 3 floats) = {S, 1/S,
+ *                      other_scale[1] / S} (other_scale may be NULL: then 1/S).  scratch: pl_vit_planes_scratch_bytes() */
+int pl_vit_attn_supported(int seq, int heads, int dim_head);
+int pl_vit_embed_fwd(const float* x2d, int64_t T, int in_d, int seq, const float* W, const float* b, const float* pos,
+                     int H, float* x, void* stream);
+size_t pl_vit_embed_bwd_scratch_bytes(int64_t T, int in_d, int H);
+int pl_vit_embed_bwd(const float* dx, const float* x2d, int64_t T, int in_d, int seq, int H, const float* W, float* dWb,
+                     float* dpos, float* dx2d, void* scratch, void* stream);
+int pl_vit_ln_fwd(const float* x, const float* add, int64_t T, int H, int nnorm, const float* g1, const float* b1,
+                  const float* g2, const float* b2, float eps, float* x_out, float* y, float* stats, void* stream);
+size_t pl_vit_ln_bwd_scratch_bytes(int64_t T, int H, int nnorm);
+int pl_vit_ln_bwd(const float* dy, const float* dres, const float* x, const float* stats, int64_t T, int H, int nnorm,
+                  const float* g1, const float* b1, const float* g2, float* dx, float* dgb, void* scratch, void* stream);
+int pl_vit_attn_fwd(const float* qkv, int64_t B, int seq, int heads, int dim_head, float scale, float* o, float* lse,
+                    void* stream);
+int pl_vit_attn_bwd(const float* qkv, const float* lse, const float* dout, int64_t B, int seq, int heads, int dim_head,
+                    float scale, float* dqkv, void* stream);
+int pl_vit_gelu_fwd(const float* u, int64_t n, float* y, void* stream);
+int pl_vit_gelu_bwd(const float* u, const float* dy, int64_t n, float* du, void* stream);
+int pl_vit_head_fwd(const float* z, int64_t T, int K, const float* W, const float* b, int out_d, float* y, void* stream);
+size_t pl_vit_head_bwd_scratch_bytes(int64_t T, int K, int out_d);
+int pl_vit_head_bwd(const float* dy, const float* z, int64_t T, int K, const float* W, int out_d, float* dz, float* dWb,
+                    void* scratch, void* stream);
+size_t pl_vit_planes_scratch_bytes(void);
+int pl_vit_planes_dyn(const float* x, int64_t rows, int64_t cols, int64_t rows_pad, const float* other_scale, float* scale,
+                      void* planes, void* scratch, void* stream);
 
 /* ---- measurement hook (bench.py; not part of the reference interface) ------------------ */
 /* While enabled (on = n > 0), every n-th GEMM launch (n = 1: every one) is bracketed by two HIP events
