@@ -37,6 +37,7 @@ class ModuleArena:
             self.offsets.append(off)
             off += (p.numel() + 63) // 64 * 64
         self.numel = off
+        self.generation = 0                 # FlatAdam steps taken on this arena (vit._ViTFn checks it in backward)
         self.flat = torch.zeros(off, dtype=torch.float32, device=dev)
         self.grad = torch.zeros(off, dtype=torch.float32, device=dev)
         for p, o in zip(params, self.offsets):
@@ -138,6 +139,7 @@ class FlatAdam(torch.optim.Optimizer):
         if not a.intact():
             raise _lib.PoseliftError("FlatAdam: the module's parameters left their arena (.to() / .data reassigned): "
                                      "build the optimizer after moving the module")
+        a.generation += 1
         runs = a.gather_grads()
         L, lr = _lib.lib(), g["lr"]
         wd = float(g["weight_decay"]) if g.get("decoupled_weight_decay", False) else 0.0

@@ -206,6 +206,26 @@ def _colsum(x):
     return out
 
 
+def _param_versions(model, ps):
+    """What backward() needs unchanged: every parameter's version counter, and the step count of the model's FlatAdam
+    arena (a step writes the parameters through raw pointers: no version counter moves)."""
+    ar = getattr(model, "_pl_arena", None)
+    return tuple(p._version for p in ps), (ar, ar.generation if ar is not None else None)
+
+
+def _check_versions(model, ps, saved):
+    """Eager torch's rule for tensors saved for backward: the backward reads the parameters as they are now (the GEMMs,
+    the weight planes), so a parameter changed in place since the forward would mix two versions of the weights."""
+    (vers, (ar, gen)) = saved
+    for i, (p, v) in enumerate(zip(ps, vers)):
+        if p._version != v:
+            name = next((n for n, q in model.named_parameters() if q is p), f"#{i}")
+            raise RuntimeError(f"MyViT backward: parameter {name} was modified by an inplace operation after the forward "
+                               f"(version {v} -> {p._version})")
+    if ar is not None and ar.generation != gen:
+        raise RuntimeError("MyViT backward: FlatAdam.step() changed the parameters after the forward")
+
+
 class _ViTFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, want, x2d, *ps):
@@ -272,11 +292,13 @@ class _ViTFn(torch.autograd.Function):
         if want:
             ctx.model, ctx.saved, ctx.x2d, ctx.xf, ctx.z, ctx.ps = model, saved, x2d, xf, z, ps
             ctx.dims = (B, seq, in_d, T, Tp, f16)
+            ctx.versions = _param_versions(model, ps)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         model, saved, ps = ctx.model, ctx.saved, ctx.ps
+        _check_versions(model, ps, ctx.versions)
         B, seq, in_d, T, Tp, f16 = ctx.dims
         H, heads, out_d = model.hidden_d, model.n_heads, model.out_d
         dev = dy.device

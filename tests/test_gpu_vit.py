@@ -1,5 +1,5 @@
 """MyViT on the MI355X: against the reference's own numbers (tests/golden/g12_vit.npz, tools/make_golden_vit.py) and
-against an fp64 twin written here in plain torch from the model's definition (phase1_lifting/baselineModel.py:220-362):
+against the fp64 twin of oracle/vit_twin.py (plain torch, from the model's definition):
 outputs, every gradient, AdamW steps, the kernels alone on hard inputs, determinism, the weight-plane caches, and the
 generic train / eval helpers."""
 import numpy as np
@@ -8,6 +8,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import load_golden
+from oracle.vit_twin import twin
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -35,33 +36,6 @@ def _stream():
 def _mpjpe_mm(a, b):
     a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
     return float(np.linalg.norm(a - b, axis=-1).mean() * 1000.0)
-
-
-# ---------------------------------------------------------------------------------------------- fp64 twin
-def twin(sd, x, t, n_heads=4):
-    """Forward + MSE + backward of the model in float64 on the CPU, plain torch ops.  Returns (y, {name: grad})."""
-    p = {k: v.detach().double().cpu().clone().requires_grad_(k != "pos_embed") for k, v in sd.items()}
-    H = p["linear_mapper.weight"].shape[0]
-    nb = len({k.split(".")[1] for k in p if k.startswith("blocks.")})
-    x = torch.as_tensor(x).double()
-    B, n, _ = x.shape
-    h = x @ p["linear_mapper.weight"].T + p["linear_mapper.bias"] + p["pos_embed"]
-    for i in range(nb):
-        q_ = f"blocks.{i}."
-        a = F.layer_norm(h, (H,), p[q_ + "norm1.weight"], p[q_ + "norm1.bias"], 1e-5)
-        a = F.layer_norm(a, (H,), p[q_ + "mhsa.norm.weight"], p[q_ + "mhsa.norm.bias"], 1e-5)
-        q, k, v = (a @ p[q_ + "mhsa.to_qkv.weight"].T).chunk(3, dim=-1)
-        q, k, v = (z.reshape(B, n, n_heads, H // n_heads).transpose(1, 2) for z in (q, k, v))
-        att = torch.softmax((q @ k.transpose(-1, -2)) * (H // n_heads) ** -0.5, dim=-1)
-        o = (att @ v).transpose(1, 2).reshape(B, n, H)
-        h = h + o @ p[q_ + "mhsa.to_out.weight"].T
-        n2 = F.layer_norm(h, (H,), p[q_ + "norm2.weight"], p[q_ + "norm2.bias"], 1e-5)
-        u = F.gelu(F.linear(n2, p[q_ + "mlp.0.weight"], p[q_ + "mlp.0.bias"]))
-        h = h + F.linear(u, p[q_ + "mlp.2.weight"], p[q_ + "mlp.2.bias"])
-    y = F.linear(torch.relu(F.linear(h, p["mlp.0.weight"], p["mlp.0.bias"])), p["mlp.2.weight"], p["mlp.2.bias"])
-    loss = ((y - torch.as_tensor(t).double()) ** 2).mean()
-    loss.backward()
-    return y.detach().numpy(), {k: v.grad.numpy() for k, v in p.items() if v.grad is not None}
 
 
 def _gpu_fwd_bwd(pkg, m, x, t):

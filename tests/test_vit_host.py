@@ -106,3 +106,34 @@ def test_vit_entry_points_reject_bad_arguments(pkg):
     assert L.pl_vit_planes_dyn(one, 17, 6, 32, None, one, one, one, None) != 0         # cols % 4
     assert L.pl_vit_ln_bwd_scratch_bytes(17 * 64, 256, 2) == 4 * 5 * 4 * 256
     assert L.pl_vit_planes_scratch_bytes() > 0
+
+
+# the (seq, heads) at the LDS limit of pl_vit_attn_bwd for every heads count the constructor takes (hidden_d <= 512)
+LDS_CORNERS = [(32, 1), (32, 2), (32, 3), (31, 4), (25, 5), (21, 6), (18, 7), (15, 8)]
+
+
+def test_supported_constructor_and_kernel_limits_agree(pkg):
+    """vit.supported, whether MyViT constructs, and the library's own limit (plus hidden_d <= 512) are one rule."""
+    L = pkg.lib()
+    for hidden_d in range(64, 1025, 64):
+        heads = hidden_d // 64
+        for seq in range(1, 41):
+            want = bool(L.pl_vit_attn_supported(seq, heads, 64)) and hidden_d <= 512
+            assert pkg.vit.supported(seq, hidden_d, heads) == want, (seq, hidden_d)
+            try:
+                pkg.MyViT(chw=(1, seq, 2), n_blocks=1, hidden_d=hidden_d, n_heads=heads, compute_dtype="fp32")
+                built = True
+            except pkg.PoseliftError:
+                built = False
+            assert built == want, (seq, hidden_d)
+
+
+@pytest.mark.parametrize("seq,heads", LDS_CORNERS)
+def test_every_lds_corner_is_accepted_and_one_more_token_is_not(pkg, seq, heads):
+    L = pkg.lib()
+    assert L.pl_vit_attn_supported(seq, heads, 64) == 1
+    assert L.pl_vit_attn_supported(seq + 1, heads, 64) == 0
+    assert pkg.vit.supported(seq, 64 * heads, heads) and not pkg.vit.supported(seq + 1, 64 * heads, heads)
+    one = ctypes.c_void_p(16)
+    assert L.pl_vit_attn_bwd(one, one, one, 1, seq + 1, heads, 64, 0.125, one, None) != 0
+    assert L.pl_vit_attn_fwd(one, 1, 33, heads, 64, 0.125, one, one, None) != 0
