@@ -23,12 +23,6 @@ from . import conv
 from .heads import soft_argmax_2d, soft_argmax_3d, soft_argmax_3d_nhwc
 
 
-def _stem_on_planes():
-    """POSELIFT_STEM_PLANES=0: the direct fp32 stem kernel of rounds 1-2 (same-box A/B)."""
-    import os
-    return os.environ.get("POSELIFT_STEM_PLANES", "1") != "0"
-
-
 class Bottleneck(nn.Module):
     expansion = 4
 
@@ -108,7 +102,7 @@ class ResNet(nn.Module):
         with torch.no_grad():
             s, b = f["bn1"]
             Bf, Hf, Wf, _ = x_nhwc.shape
-            if _stem_on_planes() and conv.stem_planes_supported(Bf, Hf, Wf, 3, self.conv1.out_channels, 7, 7, 2, 3):
+            if conv.stem_planes_supported(Bf, Hf, Wf, 3, self.conv1.out_channels, 7, 7, 2, 3):
                 # the stem as a planes GEMM on the frame's pixel-pair view, folded BatchNorm + ReLU in its epilogue
                 x, _ = cpe(conv.stem_input_planes(x_nhwc, mode), f["conv1@pairs"], (self.conv1.out_channels, 7, 4, 8), (2, 1), (3, 2, 1),
                            s, b, relu=1, mode=mode)
@@ -148,7 +142,7 @@ class ResNet(nn.Module):
             return conv.conv2d_nhwc_autograd(inp, w(m), stride, padding, ar)
         planes = self.compute_dtype in ("f16x3", "bf16p")
         Bf, Hf, Wf, _ = x.shape
-        if planes and _stem_on_planes() and conv.stem_planes_supported(Bf, Hf, Wf, 3, self.conv1.out_channels, 7, 7, 2, 3):
+        if planes and conv.stem_planes_supported(Bf, Hf, Wf, 3, self.conv1.out_channels, 7, 7, 2, 3):
             # the stem as a planes GEMM on the frame's pixel-pair view (conv.stem_planes), BatchNorm from its epilogue statistics
             mode = conv._lib.PL_F16X3 if self.compute_dtype == "f16x3" else conv._lib.PL_BF16
             link = conv.PlaneLink(mode)

@@ -90,19 +90,16 @@ inline int planes_kind(const PLDesc* d, int64_t B) {       // PlaneOut::kind of 
 }
 // BatchNorm-backward pass 1 of hidden layer l is folded into the epilogue of the dX GEMM of layer l+1 (which produces
 // its incoming gradient) whenever that GEMM is a planes GEMM: every hidden layer but the top one.  A pure function of
-// (descriptor, layer), so the ranges of a cut backward agree on it.  POSELIFT_BNR_UNFUSED=1: the separate pass (A/B).
+// (descriptor, layer), so the ranges of a cut backward agree on it.
 // The top layer's incoming gradient comes from the 51-wide output layer (g = dy W5, skinny.hip): that kernel carries the
-// same epilogue (POSELIFT_BNR_TOP_UNFUSED=1: the stand-alone pass for the top layer only).
+// same epilogue.
 inline bool fused_reduce(const PLDesc* d, bool planes, int l, int L, bool eval_bn) {
-  static const bool off = [] { const char* e = getenv("POSELIFT_BNR_UNFUSED"); return e && e[0] == '1'; }();
-  static const bool top_off = [] { const char* e = getenv("POSELIFT_BNR_TOP_UNFUSED"); return e && e[0] == '1'; }();
-  if (!planes || !d->bn || eval_bn || off) return false;
-  return l < L - 1 || (!top_off && skinny_supported(d->out_dim, d->hidden));
+  if (!planes || !d->bn || eval_bn) return false;
+  return l < L - 1 || skinny_supported(d->out_dim, d->hidden);
 }
 // hidden layers of a small local batch off the planes path: one fused launch per BatchNorm direction (elementwise.hip)
 inline bool bn_small_ok(const PLDesc* d, bool planes, int64_t B) {
-  static const bool off = [] { const char* e = getenv("POSELIFT_BN_SMALL"); return e && e[0] == '0'; }();   // =0: same-box A/B
-  return !off && d->bn && !planes && sync_world(d) == 1 && B >= 2 && B <= kBnSmallRows;
+  return d->bn && !planes && sync_world(d) == 1 && B >= 2 && B <= kBnSmallRows;
 }
 // ... and behind the first layer the Linear in front of it / the dX GEMM behind it ride in the same launch (small_layer.hip).
 // A pure function of (descriptor, batch): forward and backward agree on which bitmap format a layer has.
@@ -115,10 +112,6 @@ inline bool small_top_on(const PLDesc* d, bool planes, int64_t B) { return small
 // the fused train step at small batch: no launch for the output Linear (the last hidden layer's launch leaves its slabs)
 inline bool small_head_on(const PLDesc* d, bool planes, int64_t B) {
   return small_top_on(d, planes, B) && (d->num_stage > 0 || small_first_on(d, planes, B));
-}
-inline bool adam_ride_on() {        // POSELIFT_SMALL_ADAM=0: the AdamW step of pl_lifter_train_step as one launch of its own (A/B)
-  static const bool off = [] { const char* e = getenv("POSELIFT_SMALL_ADAM"); return e && e[0] == '0'; }();
-  return !off;
 }
 inline int arith_of(const PLDesc* d) { return d->dtype == PL_F16X3 ? (int)PL_BF16X6 : d->dtype; }
 
@@ -234,8 +227,8 @@ Ws plan(const PLDesc* d, int64_t B) {
     // partials of the skinny-layer kernels (skinny.hip)
     slab = std::max(slab, (size_t)skinny_chunks((int)B) * std::max(d->in_dim, d->out_dim) * H * 4);
     slab = std::max(slab, skinny_narrow_out_part_floats((int)B, H) * 4);
-    if (B <= thin_gemm_max_m() && B % 128) slab = std::max(slab, thin_gemm_scratch_floats((int)B, H, H) * 4);
-    if (B <= thin_gemm_max_m()) slab = std::max(slab, (size_t)(H / 16 + 1) * B * 64 * 4);    // output-layer slabs of small_layer.hip
+    if (B <= kThinGemmMaxM && B % 128) slab = std::max(slab, thin_gemm_scratch_floats((int)B, H, H) * 4);
+    if (B <= kThinGemmMaxM) slab = std::max(slab, (size_t)(H / 16 + 1) * B * 64 * 4);    // output-layer slabs of small_layer.hip
   }
   w.slab_floats = slab / 4;
   w.slabs = take(slab);
@@ -255,7 +248,7 @@ Ws plan(const PLDesc* d, int64_t B) {
     w.amax = take(std::max((size_t)((H + 255) / 256) * w.RC, (size_t)(B / 64) * (H / 32)) * 2 * 4);
     w.dzscale = take((size_t)w.L * 2 * 4);
   }
-  if (d->dtype == PL_F16X3 && B <= thin_gemm_max_m())
+  if (d->dtype == PL_F16X3 && B <= kThinGemmMaxM)
     for (int l = 0; l + 1 < w.L; ++l) w.sactp.push_back(take(w.act_bytes));           // two fp16 planes = 4 B per element
   w.total = o;
   return w;
@@ -290,34 +283,29 @@ BnrSlab bnr_slab(const PLDesc* d, const Ws& w, void* ws, int rc, int n_amax, boo
 inline bool bn_small(const PLDesc* d, const Ws& w, int64_t B) { return bn_small_ok(d, w.planes, B); }
 
 // Training forward of 128 ... 512 rows on the operand-planes path (fp16 pairs, local statistics): the 1024-wide Linears on the
-// layer kernels' contraction (launch_small_linear_stats).  POSELIFT_MID_LINEAR=0: the tile GEMM (same-box A/B).
+// layer kernels' contraction (launch_small_linear_stats).
 inline bool mid_linear_on(const PLDesc* d, const Ws& w, int64_t B) {
-  static const bool off = [] { const char* e = getenv("POSELIFT_MID_LINEAR"); return e && e[0] == '0'; }();
   // (under SyncBN only where the concatenated batch would come here too: "the shards compute what one process computes on the
   //  concatenated batch, bit for bit" holds because both sides run the same kernel)
-  return !off && w.planes && w.pkind == 2 && B * sync_world(d) <= 512 && small_layer_ok(2, d->hidden, d->hidden);
+  return w.planes && w.pkind == 2 && B * sync_world(d) <= 512 && small_layer_ok(2, d->hidden, d->hidden);
 }
 
 // The BatchNorm statistics finalize inside the apply launch (bn_apply_kernel, BnFin): local statistics, <= 4 groups (256
-// rows).  Measured same-box, step in ms with / without (POSELIFT_BN_FIN_FUSED=0): B = 96 0.312 / 0.319, 128 0.295 / 0.300,
+// rows).  Measured same-box, step in ms with / without: B = 96 0.312 / 0.319, 128 0.295 / 0.300,
 // 256 0.298 / 0.304 -- and, when tried up to 16 groups, 512 0.353 / 0.351, 1,024 0.419 / 0.391: the dependent prologue in
 // every workgroup costs what the 4.9 us launch did as soon as there are more than a few groups (round 2 saw the same at 64).
 inline bool fin_in_apply(const PLDesc* d, int groups) {
-  static const bool off = [] { const char* e = getenv("POSELIFT_BN_FIN_FUSED"); return e && e[0] == '0'; }();
-  return !off && sync_world(d) == 1 && groups >= 1 && groups <= 4 && d->hidden % 4 == 0;
+  return sync_world(d) == 1 && groups >= 1 && groups <= 4 && d->hidden % 4 == 0;
 }
 inline bool mid_linear_f32_on(const PLDesc* d, int64_t B) {
-  static const bool off = [] { const char* e = getenv("POSELIFT_MID_LINEAR"); return e && e[0] == '0'; }();
-  return !off && d->bn && d->dtype != PL_BF16 && B > kBnSmallRows && B * sync_world(d) <= 512 &&
+  return d->bn && d->dtype != PL_BF16 && B > kBnSmallRows && B * sync_world(d) <= 512 &&
          small_layer_ok(2, d->hidden, d->hidden);
 }
 
 // PL_F16X3 descriptors: the small-batch layer kernels contract on fp16 planes (three MFMAs per product) instead of exact fp32
 // MFMAs -- forward and evaluation; the first layer's launch (which must then be one of them) writes the first planes.
-// POSELIFT_SMALL_F16=0: exact fp32 there, as for every other dtype (same-box A/B).
 inline bool small_f16_on(const PLDesc* d, const Ws& w) {
-  static const bool off = [] { const char* e = getenv("POSELIFT_SMALL_F16"); return e && e[0] == '0'; }();
-  return !off && d->dtype == PL_F16X3 && !w.sactp.empty() && small_first_ok(d->in_dim);
+  return d->dtype == PL_F16X3 && !w.sactp.empty() && small_first_ok(d->in_dim);
 }
 
 struct Layer {
@@ -519,11 +507,9 @@ extern "C" int pl_lifter_fwd_eval(const PLDesc* d, const float* x, float* y, int
   // -- Linear, the BatchNorm fold on the running statistics, ReLU, residual -- on the layer kernels of small_layer.hip with
   // the grid also over 64-row blocks, the first layer on its vector-unit form, the output layer from the slabs the last
   // launch leaves: 6 launches instead of 16 at B = 64 (97 -> 47 us), every row the same bits whatever the batch.
-  // POSELIFT_SMALL_EVAL=0: the thin-GEMM route (A/B).
-  static const bool small_eval_off = [] { const char* e = getenv("POSELIFT_SMALL_EVAL"); return e && e[0] == '0'; }();
   // (whole-tile batches up to 512 rows, too: on the operand-planes path an evaluation of 128 ... 512 rows is ~20 launches of
   //  8 ... 32 tiles each -- 143 us at any of these sizes -- where the layer kernels take 50 ... 110 us)
-  if (!small_eval_off && d->bn && d->bn_running && B <= thin_gemm_max_m() && small_layer_ok(2, H, H) &&
+  if (d->bn && d->bn_running && B <= kThinGemmMaxM && small_layer_ok(2, H, H) &&
       small_first_ok(d->in_dim) && small_top_ok(d->out_dim)) {
     const float* a_in = x;
     for (int l = 0; l < w.L; ++l) {
@@ -762,8 +748,7 @@ static int bwd_impl(const PLDesc* d, const float* x, const float* dy, int64_t B,
   const int n_loss_part = loss_partials > 0 ? loss_partials : mse_partials(B * O);   // partial sums of the loss in w.mse
   const bool top_fused = do_output && sl_all && small_top_on(d, w.planes, B) && l_hi == w.L - 1 && l_hi >= l_lo;
   // the AdamW step carried by the backward launches (pl_lifter_train_step): which slice of the arena rides with layer l
-  static const bool dw_off = [] { const char* e = getenv("POSELIFT_SMALL_DW"); return e && e[0] == '0'; }();
-  const bool adam_rides = adam && top_fused && l_lo == 0 && !dw_off && H % 128 == 0 && adam_ride_on();
+  const bool adam_rides = adam && top_fused && l_lo == 0 && H % 128 == 0;
   auto ride = [&](int64_t lo, int64_t hi) {
     AdamWRide r = {};
     r.p = const_cast<float*>(d->params) + lo; r.g = grads + lo; r.m = adam->m + lo; r.v = adam->v + lo; r.n = hi - lo;
@@ -893,8 +878,8 @@ static int bwd_impl(const PLDesc* d, const float* x, const float* dy, int64_t B,
       GemmArgs t = {};
       t.arith = arith_of(d);
       t.A = DZl; t.B = a_in; t.M = H; t.N = H; t.K = Bi; t.lda = H; t.ldb = H; t.ldc = H; t.split_k = 1; t.C = ly.gW;
-      // (the weight gradient as extra workgroups of the same launch: POSELIFT_SMALL_DW=0 keeps it a launch of its own, A/B)
-      const bool dw_rides = !dw_off && H % 128 == 0;
+      // (the weight gradient as extra workgroups of the same launch)
+      const bool dw_rides = H % 128 == 0;
       if (l - 1 >= l_lo) {
         // (l == 1: the first layer's weight gradient dW1 = dz_0^T x follows its BatchNorm backward in the same workgroups)
         first_wgrad_done = l == 1 && small_first_ok(d->in_dim);
@@ -1012,12 +997,8 @@ extern "C" int pl_gemm_f32(int layout, const float* A, const float* Bm, float* C
 extern "C" int pl_gemm_arith(int layout, int arith, const float* A, const float* Bm, float* C, int64_t M,
                              int64_t N, int64_t K, const float* bias, int split_k, float* slabs, void* stream) {
   if (layout < 0 || layout > 2) PL_FAIL(PL_EINVAL, "pl_gemm_f32: layout %d", layout);
-#ifdef PL_ABLATE
-  if (arith < 0 || arith > 4) PL_FAIL(PL_EDTYPE, "pl_gemm_arith: arith %d", arith);
-#else
   // 5 / 6: test hooks forcing the PL_BF16X6 planes / fragment-split main loop (2 = the library's choice)
   if ((arith < 0 || arith > 2) && arith != 5 && arith != 6) PL_FAIL(PL_EDTYPE, "pl_gemm_arith: arith %d", arith);
-#endif
   if (M <= 0 || N <= 0 || K <= 0 || M > INT32_MAX || N > INT32_MAX || K > INT32_MAX)
     PL_FAIL(PL_ESHAPE, "pl_gemm_f32: bad shape");
   GemmArgs g = {};
@@ -1314,8 +1295,7 @@ extern "C" int pl_lifter_step_carries_adamw(const PLDesc* d, int64_t B) {
   PL_TRY(check_desc(d, false));
   if (B <= 0) return 0;
   const bool planes = planes_kind(d, B) != 0;
-  static const bool dw_off = [] { const char* e = getenv("POSELIFT_SMALL_DW"); return e && e[0] == '0'; }();
-  return (bn_small_ok(d, planes, B) && small_head_on(d, planes, B) && !dw_off && d->hidden % 128 == 0 && adam_ride_on()) ? 1 : 0;
+  return (bn_small_ok(d, planes, B) && small_head_on(d, planes, B) && d->hidden % 128 == 0) ? 1 : 0;
 }
 
 extern "C" int pl_lifter_train_step(const PLDesc* d, const float* x, const float* target, int64_t B, void* ws, size_t ws_bytes,
@@ -1341,16 +1321,15 @@ static int train_fwd_bwd_impl(const PLDesc* d, const float* x, const float* targ
   bool small_head = false;      // the loss partials in w.mse are launch_small_mse's
   if (hi == L) {
     const int H = d->hidden, O = d->out_dim;
-    static const bool head_off = [] { const char* e = getenv("POSELIFT_HEAD_UNFUSED"); return e && e[0] == '1'; }();
     const int so = skinny_narrow_out_supported(H, O) ? skinny_narrow_out_splits((int)B, H) : 0;
-    if (!head_off && bn_small(d, w, B) && small_head_on(d, w.planes, B)) {
+    if (bn_small(d, w, B) && small_head_on(d, w.planes, B)) {
       // small batches: the output Linear's slabs come from the last hidden layer's launch (small_layer.hip)
       PL_TRY(fwd_saved_impl(d, x, y, B, ws, ws_bytes, seed, step, nullptr, stream, false, true));
       const ParamLayout P = param_layout(d);
       PL_TRY(launch_small_mse(f32(ws, w.slabs), H / 16, (int)B, O, d->params + P.off[4 * L + 1], target, 1.0f, y, dy,
                               f32(ws, w.mse), (hipStream_t)stream));
       small_head = true;
-    } else if (!head_off && so && mse_from_slabs_supported(so, O)) {
+    } else if (so && mse_from_slabs_supported(so, O)) {
       // the output Linear's slab reduce folded into the MSE pass: one launch less, the same bits
       PL_TRY(fwd_saved_impl(d, x, y, B, ws, ws_bytes, seed, step, nullptr, stream, false, true));
       const ParamLayout P = param_layout(d);

@@ -1449,7 +1449,7 @@ int launch_bn_apply(const float* z, const float* scale, const float* shift, cons
                     const uint64_t* step_dev, const BnFinalizeArgs* finalize) {
   int mode = 0;
   PlaneOut po = planes ? *planes : PlaneOut{nullptr, nullptr, 1.f, nullptr, 0};
-  po.nt = (nontemporal_on() && (int64_t)B * H * 4 >= kNontemporalBytes) ? 1 : 0;
+  po.nt = (int64_t)B * H * 4 >= kNontemporalBytes ? 1 : 0;
   if (!act && !po.kind) PL_FAIL(PL_EINVAL, "bn_apply: nothing to write");
   float kscale = 1.f;
   if (p >= 1.f) mode = 3;
@@ -1560,17 +1560,12 @@ int launch_bn_bwd_dz(const float* g, const uint64_t* bits, const float* z, const
                      float* dz, float* part_db, hipStream_t s, int Hc, const PlaneOut* planes, int rc) {
   dim3 grid((H + 255) / 256, rc > 0 ? rc : bwd_row_chunks(B, H));
   PlaneOut po = planes ? *planes : PlaneOut{nullptr, nullptr, 1.f, nullptr, 0};
-  po.nt = (nontemporal_on() && (int64_t)B * H * 4 >= kNontemporalBytes) ? 1 : 0;
+  po.nt = (int64_t)B * H * 4 >= kNontemporalBytes ? 1 : 0;
   if (!dz && !po.kind) PL_FAIL(PL_EINVAL, "bn_bwd_dz: nothing to write");
   hipLaunchKernelGGL(bn_bwd_dz_kernel, grid, dim3(NTHR), 0, s, g, bits, z, mean, rstd, coef, keep_scale,
                      bn, B, H, dz, part_db, Hc > 0 ? Hc : H, po);
   PL_CHECK_LAUNCH("bn_bwd_dz");
   return PL_OK;
-}
-
-bool nontemporal_on() {
-  static const bool on = [] { const char* e = getenv("POSELIFT_NT"); return !(e && e[0] == '0'); }();
-  return on;
 }
 
 int launch_split_planes(const float* x, int64_t n, const PlaneOut& out, hipStream_t s) {
@@ -1776,14 +1771,16 @@ extern "C" int pl_mpjpe_accum(const float* pred, const float* tgt, int64_t B, in
   return PL_OK;
 }
 
+// (same-box sweep, B = 64 step: 256 / 512 / 1024 / 2048 blocks -> 0.1297 / 0.1289 / 0.1295 / 0.1304 ms; B = 4096: no difference)
+constexpr int kAdamBlocks = 512;
+
 static int adamw_launch(float* p, const float* g, float* m, float* v, int64_t n, const AdamWIn& in, void* stream) {
   if (!p || !g || !m || !v) PL_FAIL(PL_EINVAL, "pl_adamw_flat: null pointer");
   if (n <= 0 || in.t < (in.t_dev ? 0 : 1)) PL_FAIL(PL_ESHAPE, "pl_adamw_flat: n=%lld t=%lld", (long long)n, (long long)in.t);
   const int vec = aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v);
   int64_t work = vec ? (n >> 2) : n;
   int blocks = (int)((work + NTHR - 1) / NTHR);
-  static const int cap = [] { const char* e = getenv("POSELIFT_ADAM_BLOCKS"); return e ? atoi(e) : 512; }();   // (same-box sweep, B = 64 step: 256 / 512 / 1024 / 2048 -> 0.1297 / 0.1289 / 0.1295 / 0.1304 ms; B = 4096: no difference)
-  if (blocks > cap) blocks = cap;
+  if (blocks > kAdamBlocks) blocks = kAdamBlocks;
   if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL(adamw_kernel, dim3(blocks), dim3(NTHR), 0, (hipStream_t)stream, p, g, m, v, n, in, vec);
   PL_CHECK_LAUNCH("adamw");

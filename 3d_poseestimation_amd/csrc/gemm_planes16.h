@@ -1,10 +1,11 @@
-// The planes GEMM main loop on v_mfma_f32_16x16x32 (gemm_planes.h has the 32x32x16 form and everything shared).
+// The planes GEMM main loops on v_mfma_f32_16x16x32 (gemm_planes.h has what they share).
 //
-// Why a second shape: under this loop's load the chip holds a higher matrix clock on the 16x16x32 shape (the guide's
-// DVFS note; measured here with a timing-only build that issues each 32x32x16 MFMA as two 16x16x32 ones on the same
-// registers: 30.0 -> 27.4 us per 4096x1024x1024 f16x3 GEMM, MFMA-only 23.9 -> 22.5 us).  Same tile (128x128, BK 32,
-// three LDS stages, four computing + four loader wavefronts), same DMA, same planes; what changes is the fragment
-// geometry, the accumulator layout (and with it the epilogue, which is LDS-staged throughout: gemm_planes.hip).
+// Why not 32x32x16 (the first form, removed; in git history): under this loop's load the chip holds a higher matrix
+// clock on the 16x16x32 shape (the guide's DVFS note; measured with a timing-only build that issued each 32x32x16 MFMA
+// as two 16x16x32 ones on the same registers: 30.0 -> 27.4 us per 4096x1024x1024 f16x3 GEMM, MFMA-only 23.9 -> 22.5 us).
+// Same tile (128x128, BK 32, three LDS stages, four computing + four loader wavefronts), same DMA, same planes; what
+// changed is the fragment geometry, the accumulator layout (and with it the epilogue, which is LDS-staged throughout:
+// gemm_planes.hip).
 //
 //   v_mfma_f32_16x16x32_{f16,bf16}: lane l holds A[row l&15][k = 8 (l>>4) + j], B[k = 8 (l>>4) + j][col l&15], j < 8;
 //   D: col l&15, row 4 (l>>4) + reg, reg < 4.  A wave's 64x64 block = 4x4 such tiles: acc[4][4] of 4 floats.
@@ -40,7 +41,7 @@ __device__ __forceinline__ uint32_t glds_lane_off16(int rb, int lane, int ld, in
     const int ch = (lane & 3) ^ kc16_swz(row);
     return (uint32_t)(min(row, left - 1) * ld * 2 + ch * 16);
   }
-  // k-strided image: as the 32x32x16 loop (the guide's layout (b)): 4 k-rows x 256 B per instruction
+  // k-strided image (the guide's layout (b)): 4 k-rows x 256 B per instruction
   const int krow = rb * 4 + (lane >> 4);
   const int ch = (lane & 15) ^ ((((lane >> 4) & 3) << 2) | (rb & 3));
   return (uint32_t)(krow * ld * 2 + min(ch, (left >> 3) - 1) * 16);
@@ -90,7 +91,7 @@ __device__ __forceinline__ f32x4v mfma16x16(const s16x8 a, const s16x8 b, const 
 }
 
 // acc[c][rt][ct][reg]: row = m0 + wm*64 + rt*16 + 4*(lane>>4) + reg, col = n0 + wn*64 + ct*16 + (lane&15)
-// Whole tiles only (as planes_mainloop); 512 threads; the loader waves never call `epi`.
+// Whole tiles only; 512 threads; the loader waves never call `epi`.
 // EDGE: M and N need not be multiples of 128 (M: any for a k-contiguous A, % 8 for a k-strided one; N % 8): see
 // glds_lane_off16.  K stays a whole number of 32-k tiles per slice.
 // CONV = 1 (with !A_KS, !B_KS): A gathered as an implicit-GEMM convolution input; CONV = 2 (A_KS, B_KS): B gathered as the
@@ -243,7 +244,6 @@ __device__ __forceinline__ void planes_run16(const PlanesArgs& p, const int bloc
       }
     };
     auto issue = [&](const int stage_off) {
-      if (p.abl & 2) return;
       const int sa = kt * ga_step, sb = kt * gb_step;
       char* d = lds + stage_off + lw * 1024;
       int va[JA], vb[JB];
@@ -364,7 +364,6 @@ __device__ __forceinline__ void planes_run16(const PlanesArgs& p, const int bloc
   } while (0)
 #define PLP16_ROWS(set, r0, r1)                                                              \
   do {                                                                                       \
-    if (p.abl & 4) break;                                                                    \
     _Pragma("unroll") for (int rt = (r0); rt < (r1); ++rt)                                   \
     _Pragma("unroll") for (int ct = 0; ct < 4; ++ct) PLP16_MFS(set, rt, ct);                 \
   } while (0)
@@ -815,7 +814,6 @@ __device__ __forceinline__ void planes_run16w(const PlanesArgs& p, const int blo
       }
     };
     auto issue = [&](const int stage_off) {
-      if (p.abl & 2) return;
       const int sa = pp * ga_step, sb = pp * gb_step;
       char* d = lds + stage_off + lw * 1024;
       int va[4] = {oa[0], oa[1], oa[2], oa[3]};
@@ -901,7 +899,6 @@ __device__ __forceinline__ void planes_run16w(const PlanesArgs& p, const int blo
   } while (0)
 #define PLW_ROWS(set, r0, r1)                                                                \
   do {                                                                                       \
-    if (p.abl & 4) break;                                                                    \
     _Pragma("unroll") for (int rt = (r0); rt < (r1); ++rt)                                   \
     _Pragma("unroll") for (int ct = 0; ct < 4; ++ct) PLW_MFS(set, rt, ct);                   \
   } while (0)

@@ -9,7 +9,6 @@
 // fixed order and applies the epilogue of gemm_epilogue.h (bias, skip-gradient addend, eval-BN fold, ReLU, residual,
 // training-mode BatchNorm partial statistics per 64-row group).  Replaces the same ATen addmm calls as gemm_f32.hip
 // (reference phase1_lifting/baselineModel.py:33,39 and their autograd).
-#include <stdlib.h>
 
 #include "pl_internal.h"
 
@@ -164,12 +163,6 @@ __global__ __launch_bounds__(NTHR) void thin_reduce_kernel(GemmArgs p, const flo
 
 }  // namespace
 
-// largest M taken (POSELIFT_THIN_MAX_M overrides: same-box sweeps)
-int thin_gemm_max_m() {
-  static const int m = [] { const char* e = getenv("POSELIFT_THIN_MAX_M"); return e ? atoi(e) : 512; }();
-  return m;
-}
-
 // K slices: a function of (N, K) only -- the contraction order, hence every output bit, is the same for every batch size
 // that takes this path.  Enough wave tasks at ONE 64-row block for half the chip's SIMDs, slices of >= 32 k, <= 16 slabs.
 int thin_gemm_splits(int N, int K) {
@@ -184,7 +177,7 @@ size_t thin_gemm_scratch_floats(int M, int N, int K) { return (size_t)thin_gemm_
 bool thin_gemm_ok(GemmLayout layout, const GemmArgs& a) {
   if (layout != kNT && layout != kNN) return false;
   if (a.split_k > 1 || a.conv_cin || a.bnr_z) return false;
-  if (a.M < 1 || a.M > thin_gemm_max_m() || a.N < 32 || (a.N & 3) || a.K < 8 || (a.K & 7)) return false;
+  if (a.M < 1 || a.M > kThinGemmMaxM || a.N < 32 || (a.N & 3) || a.K < 8 || (a.K & 7)) return false;
   if ((a.lda & 3) || (a.ldc & 3) || (layout == kNT && (a.ldb & 3))) return false;
   if ((a.stat_sum != nullptr) != (a.stat_m2 != nullptr)) return false;
   if ((a.col_scale != nullptr) != (a.col_shift != nullptr)) return false;

@@ -110,7 +110,6 @@ struct PlaneOut {
 };
 // outputs at least this large are streamed past the caches (their consumer reads them from HBM whatever the store policy)
 constexpr long long kNontemporalBytes = 64ll << 20;
-bool nontemporal_on();     // POSELIFT_NT=0: plain stores everywhere (same-box A/B)
 constexpr float kActPlaneScale = 1.0f;      // activations: fp16 covers 6e-5 .. 65504 in h, the remainder in l
 constexpr float kWeightPlaneScale = 16.0f;  // weights (|w| ~ 0.03 at init): 3.8e-6 .. 4094
 // conv path: eval-mode feature maps of an unnormalised network reach 1e5 (seeded test weights: 6.7e4 after the first
@@ -138,9 +137,9 @@ int launch_split_planes(const float* x, int64_t n, const PlaneOut& out, hipStrea
 int plane_out_of(int mode, void* planes, int64_t n, float scale, const float* dyn, PlaneOut* po, const char* who);
 
 int launch_gemm_f32(GemmLayout layout, const GemmArgs& a, hipStream_t s);
-// M <= thin_gemm_max_m() rows (NT, NN): the contraction split over the chip, exact fp32 MFMA, slabs + one reduce/epilogue
+// M <= kThinGemmMaxM rows (NT, NN): the contraction split over the chip, exact fp32 MFMA, slabs + one reduce/epilogue
 // launch (gemm_thin.hip); launch_gemm_f32 takes it for problems that are not whole tiles when a.thin_scratch is set
-int thin_gemm_max_m();
+constexpr int kThinGemmMaxM = 512;
 bool thin_gemm_ok(GemmLayout layout, const GemmArgs& a);
 size_t thin_gemm_scratch_floats(int M, int N, int K);
 int launch_gemm_thin(GemmLayout layout, const GemmArgs& a, float* scratch, size_t scratch_floats, hipStream_t s);
@@ -214,11 +213,11 @@ int launch_bn_small_bwd(const float* g, const uint64_t* bits, const float* z, co
 // Small batches, hidden layers behind the first (small_layer.hip): a workgroup owns 16 columns for all B <= 64 rows, so one
 // launch is Linear + BatchNorm1d (batch statistics) + ReLU + Dropout (+ skip) forward, and one launch is dX = dz W (+ skip
 // gradient) followed by the BatchNorm backward of the layer below.  Their ReLU & keep bitmap is in the "tile format" of
-// small_layer.hip (tile_bits above: bn_small_bwd reading such a layer).  POSELIFT_SMALL_LAYER=0 switches them off (A/B).
+// small_layer.hip (tile_bits above: bn_small_bwd reading such a layer).
 bool small_layer_ok(int B, int H, int K);
 // ... the first layer (K = in_dim <= 256 inputs: contraction on the vector unit) forward, its weight gradient in the backward
 // launch of the layer above, and the whole top of the backward pass (g = dy W2, BatchNorm backward of the last hidden layer,
-// dW2, db2; out_dim <= 64) as one launch.  POSELIFT_SMALL_ENDS=0 switches these off (A/B).
+// dW2, db2; out_dim <= 64) as one launch.
 bool small_first_ok(int K);
 bool small_top_ok(int O);
 int launch_small_layer_fwd(const float* a, const float* W, const float* bias, const float* gamma, const float* beta, float eps,

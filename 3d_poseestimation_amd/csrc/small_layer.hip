@@ -64,7 +64,7 @@ constexpr int LDR = 36;                                   // floats per row of t
 constexpr int LDH = 40;                                   // halves per row of one PLANE's step image (f16x3 form below)
 // per wave: 64 rows of A, 16 of B -- fp32 rows of LDR floats, or two fp16 planes of LDH halves each (the larger of the two)
 constexpr int STAGE = (ROWS + COLS) * (LDR > LDH ? LDR : LDH);
-template <int STEPS, bool B_KS, int ABL = 0>
+template <int STEPS, bool B_KS>
 __device__ __forceinline__ void contract(const float* __restrict__ A, int lda, int M, const float* __restrict__ Bm, int ldb,
                                          int c0, float* __restrict__ part, float* __restrict__ stage) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -120,19 +120,11 @@ __device__ __forceinline__ void contract(const float* __restrict__ A, int lda, i
     }
     b[0] = ld4(img + (ROWS + i) * LDR + 8 * kq);
     b[1] = ld4(img + (ROWS + i) * LDR + 8 * kq + 4);
-    if (ABL == 2) {        // timing only: everything but the MFMAs
 #pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        acc[t][0] += a[t][0].x + a[t][1].x + b[0].x; acc[t][1] += a[t][0].y + a[t][1].y + b[1].y;
-        acc[t][2] += a[t][0].z + a[t][1].z; acc[t][3] += a[t][0].w + a[t][1].w;
-      }
-    } else {
+    for (int e = 0; e < 8; ++e)
 #pragma unroll
-      for (int e = 0; e < 8; ++e)
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-          acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(comp(a[t][e >> 2], e & 3), comp(b[e >> 2], e & 3), acc[t], 0, 0, 0);
-    }
+      for (int t = 0; t < 4; ++t)
+        acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(comp(a[t][e >> 2], e & 3), comp(b[e >> 2], e & 3), acc[t], 0, 0, 0);
   }
   float* mine = part + wave * (ROWS * COLS);
 #pragma unroll
@@ -510,7 +502,7 @@ __device__ __forceinline__ void stats_tail(const FwdArgs& p, float4 z, const Fwd
   }
 }
 
-template <int STEPS, int ABL = 0>
+template <int STEPS>
 __global__ __launch_bounds__(NTHR) void small_fwd_kernel(FwdArgs p_in) {
   __shared__ float part[NWAVE * ROWS * COLS];
   __shared__ float stage[NWAVE * STAGE];
@@ -529,10 +521,10 @@ __global__ __launch_bounds__(NTHR) void small_fwd_kernel(FwdArgs p_in) {
     return;
   }
   const FwdPre pre = fwd_prefetch(p, c);
-  if (ABL == 0 && p.ap)
+  if (p.ap)
     contract_f16<STEPS>(p.ap, p.a_plane, p.K, p.B, p.W, p.K, c0, kWeightPlaneScale, 1.0f / (kActPlaneScale * kWeightPlaneScale), part,
                         stage);
-  else if (ABL != 1) contract<STEPS, false, ABL>(p.a, p.K, p.B, p.W, p.K, c0, part, stage);
+  else contract<STEPS, false>(p.a, p.K, p.B, p.W, p.K, c0, part, stage);
   __syncthreads();
   float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
   if (tid < 256) z = gather_part(part);
@@ -906,23 +898,23 @@ __global__ __launch_bounds__(256) void small_mse_kernel(const float* __restrict_
 
 inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
+// workgroups of the AdamW slice a backward launch carries: ~2 K float4 per workgroup pass, 1 M parameters on 64 workgroups
+constexpr int kSmallAdamBlocks = 64;
+
 }  // namespace
 
 // shapes the layer kernels take: B rows in one tile, 16-column blocks, K split over eight waves in 32-k steps
 bool small_layer_ok(int B, int H, int K) {
-  static const bool off = [] { const char* e = getenv("POSELIFT_SMALL_LAYER"); return e && e[0] == '0'; }();   // =0: same-box A/B
-  if (off || B < 2 || B > ROWS || (H & 15) || H < 16) return false;
+  if (B < 2 || B > ROWS || (H & 15) || H < 16) return false;
   const int steps = K / (NWAVE * 32);
   return K % (NWAVE * 32) == 0 && (steps == 1 || steps == 2 || steps == 4);
 }
 // ... and the first layer (K = in_dim inputs) / the output layer (O = out_dim outputs) beside such hidden layers
 bool small_first_ok(int K) {
-  static const bool off = [] { const char* e = getenv("POSELIFT_SMALL_ENDS"); return e && e[0] == '0'; }();    // =0: same-box A/B
-  return !off && K >= 1 && K <= kFirstMaxK;
+  return K >= 1 && K <= kFirstMaxK;
 }
 bool small_top_ok(int O) {
-  static const bool off = [] { const char* e = getenv("POSELIFT_SMALL_ENDS"); return e && e[0] == '0'; }();
-  return !off && O >= 1 && O <= 64;
+  return O >= 1 && O <= 64;
 }
 
 // the output Linear of an evaluation forward from the slabs the last hidden layer's launch left: y = bias + sum of slabs
@@ -962,7 +954,7 @@ int launch_small_layer_eval(const float* a, const float* W, const float* bias, c
   else switch (K / (NWAVE * 32)) {
     case 1: hipLaunchKernelGGL(small_fwd_kernel<1>, grid, block, 0, s, p); break;
     case 2: hipLaunchKernelGGL(small_fwd_kernel<2>, grid, block, 0, s, p); break;
-    default: hipLaunchKernelGGL((small_fwd_kernel<4, 0>), grid, block, 0, s, p); break;
+    default: hipLaunchKernelGGL(small_fwd_kernel<4>, grid, block, 0, s, p); break;
   }
   prof_end(prof, s);
   PL_CHECK_LAUNCH("small_layer_eval");
@@ -990,7 +982,7 @@ int launch_small_linear_stats(const float* a, const unsigned short* a_planes, co
   switch (K / (NWAVE * 32)) {
     case 1: hipLaunchKernelGGL(small_fwd_kernel<1>, grid, block, 0, s, p); break;
     case 2: hipLaunchKernelGGL(small_fwd_kernel<2>, grid, block, 0, s, p); break;
-    default: hipLaunchKernelGGL((small_fwd_kernel<4, 0>), grid, block, 0, s, p); break;
+    default: hipLaunchKernelGGL(small_fwd_kernel<4>, grid, block, 0, s, p); break;
   }
   prof_end(prof, s);
   PL_CHECK_LAUNCH("small_linear_stats");
@@ -1035,13 +1027,7 @@ int launch_small_layer_fwd(const float* a, const float* W, const float* bias, co
     switch (K / (NWAVE * 32)) {
       case 1: hipLaunchKernelGGL(small_fwd_kernel<1>, grid, block, 0, s, p); break;
       case 2: hipLaunchKernelGGL(small_fwd_kernel<2>, grid, block, 0, s, p); break;
-      default: {
-        static const int abl = [] { const char* e = getenv("POSELIFT_SL_ABL"); return e ? atoi(e) : 0; }();   // timing only
-        if (abl == 1) hipLaunchKernelGGL((small_fwd_kernel<4, 1>), grid, block, 0, s, p);
-        else if (abl == 2) hipLaunchKernelGGL((small_fwd_kernel<4, 2>), grid, block, 0, s, p);
-        else hipLaunchKernelGGL((small_fwd_kernel<4, 0>), grid, block, 0, s, p);
-        break;
-      }
+      default: hipLaunchKernelGGL(small_fwd_kernel<4>, grid, block, 0, s, p); break;
     }
   }
   prof_end(prof, s);
@@ -1089,9 +1075,7 @@ int launch_small_layer_bwd(const float* dz, const float* W, const float* addend,
         !al16(adam->v) || (adam->lr_dev != nullptr) != (adam->t_dev != nullptr))
       PL_FAIL(PL_EINVAL, "small_layer_bwd: AdamW slice");
     p.adam = *adam;
-    // ~2 K float4 per workgroup pass: 1 M parameters on 64 workgroups
-    static const int cap = [] { const char* e = getenv("POSELIFT_SMALL_ADAM_BLOCKS"); return e ? atoi(e) : 64; }();   // (A/B)
-    p.nblk_adam = (int)std::min<int64_t>(cap, (adam->n / 4 + NTHR - 1) / NTHR);
+    p.nblk_adam = (int)std::min<int64_t>(kSmallAdamBlocks, (adam->n / 4 + NTHR - 1) / NTHR);
     extra += p.nblk_adam;
   }
   const dim3 grid(H / COLS + extra), block(NTHR);

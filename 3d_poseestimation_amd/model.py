@@ -9,7 +9,6 @@ holders only: their tensors are views into flat arenas and every FLOP of forward
 backward runs in the HIP library.  There is no CPU or eager fallback.
 """
 import ctypes
-import os
 import weakref
 
 import torch
@@ -213,7 +212,7 @@ class LinearModel(nn.Module):
         # and the next forward refreshes them first).
         self._wplanes, self._wplanes_ver = None, None
         nbytes = 0
-        if flat.is_cuda and os.environ.get("POSELIFT_NO_WPLANES") != "1":     # (=1: same-box A/B of the per-call split)
+        if flat.is_cuda:
             try:
                 nbytes = _lib.lib().pl_wplanes_bytes(ctypes.byref(self._desc))
             except _lib.PoseliftError:

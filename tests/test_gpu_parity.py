@@ -241,7 +241,7 @@ def test_g2_train_nodrop_vs_reference(pkg, tag):
                 # B = 128 on the operand-planes path: the forward Linears run on the layer kernels' contraction (another
                 # summation order than the tile GEMM's and the reference's), and a ReLU decision that flips on a
                 # round-off-sized pre-activation moves the samples of the rows it touches by 1 / B of their size.  With the
-                # decisions forced (tools/r3_mid_accuracy.py, same shape) every gradient tensor is within 7e-7 of the fp64
+                # decisions forced (a one-off script, in git history; same shape) every gradient tensor is within 7e-7 of the fp64
                 # oracle in relative L2 -- the fp32 oracle itself: 1.3e-6; the tile GEMM: 8e-7 -- and
                 # test_ragged_shapes_vs_oracle[128-1024-2-...-f16x3] holds that in the suite.  Here, against the reference's own
                 # decisions: the typical sample within 1e-3 of the scale, none beyond 2 %.

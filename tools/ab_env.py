@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""A/B the bench under different environment switches on the SAME box, interleaved (clock / box variation
-between gpurun calls is several percent):  python tools/ab_env.py [rounds] -- NAME=ENV1=1,ENV2=1 NAME2= ..."""
+"""A/B the bench under different environments on the SAME box, interleaved (clock / box variation between calls is
+several percent).  The library has no switches: an A/B builds both versions and loads one through POSELIFT_LIB.
+    python tools/ab_env.py [rounds] -- NAME=POSELIFT_LIB=/path/to/libposelift.so NAME2= ..."""
 import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 args = sys.argv[1:]

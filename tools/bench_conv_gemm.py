@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """The conv path's 1x1-convolution GEMM shapes through pl_gemm_planes_raw (NT, f16x3 planes, BatchNorm statistics in the
-epilogue), timed back to back: what the persistent form (POSELIFT_PERSIST, round 3) does per shape, with the bytes each
-launch has to move and its FLOPs.
-    python tools/bench_conv_gemm.py [iters]          (run once per POSELIFT_PERSIST value for the A/B)"""
+epilogue), timed back to back: what the persistent form (round 3) does per shape, with the bytes each launch has to move
+and its FLOPs.
+    python tools/bench_conv_gemm.py [iters]          (an A/B runs it once per build, POSELIFT_LIB: tools/ab_env.py)"""
 import importlib, os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 pkg = importlib.import_module("3d_poseestimation_amd")
@@ -13,7 +13,6 @@ dev = "cuda"
 # gradients are the same shapes with N and K exchanged)
 SHAPES = [(1 << 20, 256, 64), (1 << 20, 64, 256), (1 << 20, 64, 64), (1 << 18, 512, 128), (1 << 18, 128, 512), (1 << 18, 128, 256),
           (1 << 16, 1024, 256), (1 << 16, 256, 1024), (1 << 14, 2048, 512), (1 << 14, 512, 2048), (1 << 20, 1088, 256)]
-print(f"POSELIFT_PERSIST={os.environ.get('POSELIFT_PERSIST', '(default 1)')}")
 for M, N, K in SHAPES:
     A = (torch.randn(2, M, K, device=dev) * 0.5).half()
     W = (torch.randn(2, N, K, device=dev) * 0.5).half()
