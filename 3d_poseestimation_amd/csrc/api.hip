@@ -88,31 +88,6 @@ inline int planes_kind(const PLDesc* d, int64_t B) {       // PlaneOut::kind of 
   if (B % (32 * (int64_t)tn_splits(d->hidden, d->hidden, (int)B)) != 0) return 0;
   return d->dtype == PL_F16X3 ? 2 : (d->dtype == PL_BF16 ? 1 : 0);
 }
-// BatchNorm-backward pass 1 of hidden layer l is folded into the epilogue of the dX GEMM of layer l+1 (which produces
-// its incoming gradient) whenever that GEMM is a planes GEMM: every hidden layer but the top one.  A pure function of
-// (descriptor, layer), so the ranges of a cut backward agree on it.
-// The top layer's incoming gradient comes from the 51-wide output layer (g = dy W5, skinny.hip): that kernel carries the
-// same epilogue.
-inline bool fused_reduce(const PLDesc* d, bool planes, int l, int L, bool eval_bn) {
-  if (!planes || !d->bn || eval_bn) return false;
-  return l < L - 1 || skinny_supported(d->out_dim, d->hidden);
-}
-// hidden layers of a small local batch off the planes path: one fused launch per BatchNorm direction (elementwise.hip)
-inline bool bn_small_ok(const PLDesc* d, bool planes, int64_t B) {
-  return d->bn && !planes && sync_world(d) == 1 && B >= 2 && B <= kBnSmallRows;
-}
-// ... and behind the first layer the Linear in front of it / the dX GEMM behind it ride in the same launch (small_layer.hip).
-// A pure function of (descriptor, batch): forward and backward agree on which bitmap format a layer has.
-inline bool small_layer_on(const PLDesc* d, bool planes, int64_t B) {
-  return bn_small_ok(d, planes, B) && small_layer_ok((int)B, d->hidden, d->hidden);
-}
-// ... the first layer's forward likewise (tile-format bitmap for layer 0, too), and the top of the backward pass in one launch
-inline bool small_first_on(const PLDesc* d, bool planes, int64_t B) { return small_layer_on(d, planes, B) && small_first_ok(d->in_dim); }
-inline bool small_top_on(const PLDesc* d, bool planes, int64_t B) { return small_layer_on(d, planes, B) && small_top_ok(d->out_dim); }
-// the fused train step at small batch: no launch for the output Linear (the last hidden layer's launch leaves its slabs)
-inline bool small_head_on(const PLDesc* d, bool planes, int64_t B) {
-  return small_top_on(d, planes, B) && (d->num_stage > 0 || small_first_on(d, planes, B));
-}
 inline int arith_of(const PLDesc* d) { return d->dtype == PL_F16X3 ? (int)PL_BF16X6 : d->dtype; }
 
 struct ParamLayout {
@@ -153,6 +128,51 @@ int out_splits(int M, int N, int K) {
   return s < 1 ? 1 : s;
 }
 
+// The route: which kernels run each part of the lifter, decided by plan() from the descriptor and the batch alone -- so
+// every call (forward, backward, a cut range of it, the queries) agrees on it and the workspace holds what they touch.  A
+// call combines it only with its own arguments; eval_bn (no batch statistics) takes none of the small-batch routes.
+enum class Lin : uint8_t {     // forward Linear of a hidden layer when it is a launch of its own (under eval_bn: always)
+  Skinny, Planes, Gemm,        // first layer on skinny.hip; the planes tile GEMM; launch_gemm_f32
+  // launch_small_linear_stats, 128 ... 512 training rows on the operand planes (fp16 pairs): the tile GEMM has 8 ... 32
+  // tiles for 256 CUs there (22 us whatever the size); one 64-row block x 16 columns per workgroup instead, same planes,
+  // same statistics partials.  (Under SyncBN only where the concatenated batch would come here too: "the shards compute
+  // what one process computes on the concatenated batch, bit for bit" holds because both sides run the same kernel.)
+  PlanesMid,
+  // ... on fp32 operands (exact-fp32 MFMA) off the planes path (ragged rows, exact-fp32 / bf16x6 descriptors), 65 ... 512
+  // rows, instead of the thin GEMM + its reduce or an 8 ... 32-tile GEMM
+  F32Mid,
+};
+enum class Stats : uint8_t {   // BatchNorm statistics of a training forward
+  None,
+  InLayer,                     // small batches: Linear, statistics, finalize, apply in one small_layer.hip launch (tile bitmap)
+  Small,                       // small batches: the Linear, then the rest in one launch (bn_small_fwd_kernel, row bitmap)
+  // The statistics finalize inside the apply launch (bn_apply_kernel, BnFin): local statistics, <= 4 groups (256
+  // rows).  Measured same-box, step in ms with / without: B = 96 0.312 / 0.319, 128 0.295 / 0.300,
+  // 256 0.298 / 0.304 -- and, when tried up to 16 groups, 512 0.353 / 0.351, 1,024 0.419 / 0.391: the dependent prologue in
+  // every workgroup costs what the 4.9 us launch did as soon as there are more than a few groups (round 2 saw the same at 64).
+  InApply,
+  Finalize,                    // a finalize launch of its own
+};
+enum class Bwd : uint8_t {     // backward of a hidden layer's Linear in training (eval_bn: F32Pair, or First)
+  PlanesPair, F32Pair,         // dX = dz W and dW = dz^T a in one launch, on the operand planes / on fp32
+  SmallLayer, SmallLayerDw,    // dX and the layer below's BatchNorm backward in one small_layer.hip launch; dW a GEMM / in it
+  InAbove,                     // first layer: dW1 follows its BatchNorm backward in layer 1's launch (when in the range) ...
+  First,                       // ... else on the family of its forward Linear: skinny.hip / gemm_tn_reduced
+};
+struct LayerRoute {
+  Lin lin;
+  Stats stats;                 // InLayer: the tile-format bitmap (pl_workspace_bitmap_format)
+  Bwd bwd;
+  int groups;                  // 64-row statistics groups the Linear's epilogue emits
+  // BatchNorm-backward pass 1 of this layer is folded into the epilogue of the dX GEMM of layer l+1 (which produces its
+  // incoming gradient) whenever that GEMM is a planes GEMM: every hidden layer but the top one.  The top layer's incoming
+  // gradient comes from the 51-wide output layer (g = dy W5, skinny.hip): that kernel carries the same epilogue.
+  bool bnr_fused;
+};
+// the fused train step's MSE: launch_small_mse on the slabs the last hidden layer's launch left (small_head); the output
+// Linear's slab reduce folded into the MSE pass (one launch less, the same bits); y from the forward, then mse_partial_only
+enum class Loss : uint8_t { SmallMse, FromSlabs, PartialOnly };
+
 // Workspace plan; every region starts on a 256-byte boundary.
 struct Ws {
   int L, G, RC;
@@ -171,6 +191,17 @@ struct Ws {
   // partial sums whose combine is deferred to the ONE reduce launch at the end of a backward range
   size_t skp_out, skp_in;             // skinny weight-gradient partials of the output / input layer
   std::vector<size_t> wslab;          // split-K slabs of the 1024-wide weight gradients, one set per layer (planes path)
+  // the route
+  std::vector<LayerRoute> layer;
+  bool bn_small;                      // the BatchNorm of every hidden layer in small-batch launches (Stats InLayer / Small)
+  bool small_layer;                   // ... and layers 1.. in the small_layer.hip launches (Stats InLayer, Bwd SmallLayer*)
+  bool top_fused;                     // the output layer and the top hidden layer's BatchNorm backward in one launch
+  bool adam_rides;                    // the AdamW step of pl_lifter_train_step rides in the backward launches
+  bool small_f16;                     // the small-batch layer launches contract on the fp16 planes in sactp
+  bool eval_small;                    // pl_lifter_fwd_eval on the layer kernels of small_layer.hip
+  bool out_narrow;                    // output Linear forward: launch_skinny_narrow_out (else the tile GEMM)
+  bool out_skinny;                    // output Linear backward: skinny.hip (else gemm_tn_reduced, colsum, an NN GEMM)
+  Loss loss;
 };
 
 Ws plan(const PLDesc* d, int64_t B) {
@@ -251,6 +282,38 @@ Ws plan(const PLDesc* d, int64_t B) {
   if (d->dtype == PL_F16X3 && B <= kThinGemmMaxM)
     for (int l = 0; l + 1 < w.L; ++l) w.sactp.push_back(take(w.act_bytes));           // two fp16 planes = 4 B per element
   w.total = o;
+
+  const int world = sync_world(d);
+  const bool first_ok = small_first_ok(d->in_dim), mid_ok = B * world <= 512 && small_layer_ok(2, H, H);
+  w.bn_small = d->bn && !w.planes && world == 1 && B >= 2 && B <= kBnSmallRows;
+  w.small_layer = w.bn_small && small_layer_ok((int)B, H, H);
+  w.top_fused = w.small_layer && small_top_ok(d->out_dim);
+  const bool small_head = w.top_fused && (d->num_stage > 0 || first_ok);
+  w.adam_rides = small_head && H % 128 == 0;
+  // PL_F16X3 descriptors: the small-batch layer kernels contract on fp16 planes (three MFMAs per product) instead of exact
+  // fp32 MFMAs -- forward and evaluation; the first layer's launch (which must then be one of them) writes the first planes.
+  w.small_f16 = d->dtype == PL_F16X3 && !w.sactp.empty() && first_ok;
+  w.eval_small = d->bn && B <= kThinGemmMaxM && small_layer_ok(2, H, H) && first_ok && small_top_ok(d->out_dim);
+  w.out_narrow = skinny_narrow_out_supported(H, d->out_dim);
+  w.out_skinny = skinny_supported(d->out_dim, H);
+  const int so = w.out_narrow ? skinny_narrow_out_splits((int)B, H) : 0;
+  w.loss = small_head ? Loss::SmallMse : (so && mse_from_slabs_supported(so, d->out_dim)) ? Loss::FromSlabs : Loss::PartialOnly;
+  for (int l = 0; l < w.L; ++l) {
+    LayerRoute r;
+    if (l == 0) r.lin = skinny_supported(d->in_dim, H) ? Lin::Skinny : Lin::Gemm;
+    else if (w.planes) r.lin = w.pkind == 2 && mid_ok ? Lin::PlanesMid : Lin::Planes;
+    else r.lin = d->bn && d->dtype != PL_BF16 && B > kBnSmallRows && mid_ok ? Lin::F32Mid : Lin::Gemm;
+    r.groups = r.lin == Lin::Skinny ? skinny_stat_groups((int)B) : w.G;
+    const bool tile = w.small_layer && (l > 0 || first_ok);
+    if (!d->bn) r.stats = Stats::None;
+    else if (w.bn_small) r.stats = tile ? Stats::InLayer : Stats::Small;
+    else r.stats = world == 1 && r.groups >= 1 && r.groups <= 4 ? Stats::InApply : Stats::Finalize;
+    if (l == 0) r.bwd = tile && w.L > 1 ? Bwd::InAbove : Bwd::First;
+    else if (!w.small_layer) r.bwd = w.planes ? Bwd::PlanesPair : Bwd::F32Pair;
+    else r.bwd = H % 128 == 0 ? Bwd::SmallLayerDw : Bwd::SmallLayer;
+    r.bnr_fused = w.planes && (l < w.L - 1 || w.out_skinny);      // (the planes path implies BatchNorm)
+    w.layer.push_back(r);
+  }
   return w;
 }
 
@@ -278,34 +341,6 @@ BnrSlab bnr_slab(const PLDesc* d, const Ws& w, void* ws, int rc, int n_amax, boo
   b.amax_mine = b.mine + sums;
   b.amax0 = stat + sums;
   return b;
-}
-
-inline bool bn_small(const PLDesc* d, const Ws& w, int64_t B) { return bn_small_ok(d, w.planes, B); }
-
-// Training forward of 128 ... 512 rows on the operand-planes path (fp16 pairs, local statistics): the 1024-wide Linears on the
-// layer kernels' contraction (launch_small_linear_stats).
-inline bool mid_linear_on(const PLDesc* d, const Ws& w, int64_t B) {
-  // (under SyncBN only where the concatenated batch would come here too: "the shards compute what one process computes on the
-  //  concatenated batch, bit for bit" holds because both sides run the same kernel)
-  return w.planes && w.pkind == 2 && B * sync_world(d) <= 512 && small_layer_ok(2, d->hidden, d->hidden);
-}
-
-// The BatchNorm statistics finalize inside the apply launch (bn_apply_kernel, BnFin): local statistics, <= 4 groups (256
-// rows).  Measured same-box, step in ms with / without: B = 96 0.312 / 0.319, 128 0.295 / 0.300,
-// 256 0.298 / 0.304 -- and, when tried up to 16 groups, 512 0.353 / 0.351, 1,024 0.419 / 0.391: the dependent prologue in
-// every workgroup costs what the 4.9 us launch did as soon as there are more than a few groups (round 2 saw the same at 64).
-inline bool fin_in_apply(const PLDesc* d, int groups) {
-  return sync_world(d) == 1 && groups >= 1 && groups <= 4 && d->hidden % 4 == 0;
-}
-inline bool mid_linear_f32_on(const PLDesc* d, int64_t B) {
-  return d->bn && d->dtype != PL_BF16 && B > kBnSmallRows && B * sync_world(d) <= 512 &&
-         small_layer_ok(2, d->hidden, d->hidden);
-}
-
-// PL_F16X3 descriptors: the small-batch layer kernels contract on fp16 planes (three MFMAs per product) instead of exact fp32
-// MFMAs -- forward and evaluation; the first layer's launch (which must then be one of them) writes the first planes.
-inline bool small_f16_on(const PLDesc* d, const Ws& w) {
-  return d->dtype == PL_F16X3 && !w.sactp.empty() && small_first_ok(d->in_dim);
 }
 
 struct Layer {
@@ -345,6 +380,9 @@ int check_ws(const Ws& w, void* ws, size_t bytes) {
 }
 
 inline unsigned short* u16(void* ws, size_t off) { return reinterpret_cast<unsigned short*>(static_cast<char*>(ws) + off); }
+// the small-batch layer launches' fp16 input / output planes of hidden layer l (Ws::small_f16), or NULL
+inline const unsigned short* sact_in(const Ws& w, void* ws, int l) { return w.small_f16 && l > 0 ? u16(ws, w.sactp[l - 1]) : nullptr; }
+inline unsigned short* sact_out(const Ws& w, void* ws, int l) { return w.small_f16 && l + 1 < w.L ? u16(ws, w.sactp[l]) : nullptr; }
 
 // operand planes of hidden layer l's weight: in the caller's persistent buffer (PLDesc.wplanes) or in the workspace
 inline unsigned short* wplane(const PLDesc* d, const Ws& w, void* ws, int l) {
@@ -381,9 +419,9 @@ PlanesGemmArgs planes_args(int pkind, const unsigned short* A, int64_t a_plane, 
   return g;
 }
 
-int gemm_out_layer(const float* h, const float* W, const float* bias, float* y, int M, int N, int K,
+int gemm_out_layer(bool narrow, const float* h, const float* W, const float* bias, float* y, int M, int N, int K,
                    float* slabs, hipStream_t s) {
-  if (skinny_narrow_out_supported(K, N)) return launch_skinny_narrow_out(h, W, bias, y, M, K, N, slabs, s);
+  if (narrow) return launch_skinny_narrow_out(h, W, bias, y, M, K, N, slabs, s);
   GemmArgs g = {};
   g.A = h; g.B = W; g.M = M; g.N = N; g.K = K; g.lda = K; g.ldb = K; g.ldc = N;
   const int splits = out_splits(M, N, K);
@@ -449,11 +487,10 @@ extern "C" float pl_weight_plane_scale(void) { return kWeightPlaneScale; }
 // refresh PLDesc.wplanes from the current parameters (what a forward call does first when wplanes_valid == 0)
 extern "C" int pl_wplanes_refresh(const PLDesc* d, void* stream) {
   PL_TRY(check_desc(d, true));
-  if (!d->wplanes || pl_wplanes_bytes(d) == 0) PL_FAIL(PL_EINVAL, "pl_wplanes_refresh: this descriptor has no weight planes");
   PLDesc t = *d;
   t.wplanes_valid = 0;
   const Ws w = plan(&t, 128);            // any batch on the planes path: only the layer count and plane kind are used
-  if (!w.planes) PL_FAIL(PL_EINVAL, "pl_wplanes_refresh: this descriptor has no planes path");
+  if (!d->wplanes || !w.planes) PL_FAIL(PL_EINVAL, "pl_wplanes_refresh: this descriptor has no weight planes");
   return split_weight_planes(&t, param_layout(&t), w, nullptr, (hipStream_t)stream);
 }
 
@@ -486,8 +523,7 @@ extern "C" int pl_workspace_view(const PLDesc* d, int64_t B, int which, int64_t 
 extern "C" int pl_workspace_bitmap_format(const PLDesc* d, int64_t B, int64_t layer) {
   PL_TRY(check_desc(d, false));
   if (B <= 0 || layer < 0 || layer >= 1 + 2 * (int64_t)d->num_stage) PL_FAIL(PL_EINVAL, "pl_workspace_bitmap_format: bad arguments");
-  const bool planes = planes_kind(d, B) != 0;
-  return (layer > 0 ? small_layer_on(d, planes, B) : small_first_on(d, planes, B)) ? 1 : 0;
+  return plan(d, B).layer[layer].stats == Stats::InLayer ? 1 : 0;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -509,20 +545,17 @@ extern "C" int pl_lifter_fwd_eval(const PLDesc* d, const float* x, float* y, int
   // launch leaves: 6 launches instead of 16 at B = 64 (97 -> 47 us), every row the same bits whatever the batch.
   // (whole-tile batches up to 512 rows, too: on the operand-planes path an evaluation of 128 ... 512 rows is ~20 launches of
   //  8 ... 32 tiles each -- 143 us at any of these sizes -- where the layer kernels take 50 ... 110 us)
-  if (d->bn && d->bn_running && B <= kThinGemmMaxM && small_layer_ok(2, H, H) &&
-      small_first_ok(d->in_dim) && small_top_ok(d->out_dim)) {
+  if (w.eval_small) {
     const float* a_in = x;
     for (int l = 0; l < w.L; ++l) {
       const Layer ly = layer_of(d, P, nullptr, l);
       const float* resid = (l >= 2 && (l % 2) == 0) ? f32(ws, w.act[l - 2]) : nullptr;
       const bool last = l == w.L - 1;
-      const bool f16 = small_f16_on(d, w);
       // (a whole-tile batch's plan keeps no fp32 activation for the odd layers: their output goes through the z buffer)
       float* out = w.act_f32[l] ? f32(ws, w.act[l]) : f32(ws, w.z[l]);
       PL_TRY(launch_small_layer_eval(a_in, ly.W, ly.b, ly.gamma, ly.beta, d->bn_eps, ly.rm, ly.rv, resid, out,
                                      (int)B, H, ly.K, s, l == 0, last ? d->params + P.off[4 * w.L] : nullptr,
-                                     last ? f32(ws, w.slabs) : nullptr, d->out_dim,
-                                     (f16 && l > 0) ? u16(ws, w.sactp[l - 1]) : nullptr, (f16 && !last) ? u16(ws, w.sactp[l]) : nullptr));
+                                     last ? f32(ws, w.slabs) : nullptr, d->out_dim, sact_in(w, ws, l), sact_out(w, ws, l)));
       a_in = out;
     }
     return launch_small_out(f32(ws, w.slabs), H / 16, (int)B, d->out_dim, d->params + P.off[4 * w.L + 1], y, s);
@@ -562,7 +595,7 @@ extern "C" int pl_lifter_fwd_eval(const PLDesc* d, const float* x, float* y, int
     }
     a_in = out;
   }
-  return gemm_out_layer(a_in, d->params + P.off[4 * w.L], d->params + P.off[4 * w.L + 1], y, (int)B,
+  return gemm_out_layer(w.out_narrow, a_in, d->params + P.off[4 * w.L], d->params + P.off[4 * w.L + 1], y, (int)B,
                         d->out_dim, H, f32(ws, w.slabs), s);
 }
 
@@ -605,80 +638,65 @@ static int fwd_saved_impl(const PLDesc* d, const float* x, float* y, int64_t B, 
   const int64_t BH = B * H;
   if (w.planes) PL_TRY(split_weight_planes(d, P, w, ws, s));
   // (small batches, fused train step: the last hidden layer's launch leaves the output Linear's slabs -- small_layer.hip)
-  const bool head_slabs = defer_out_reduce && !eval_bn && bn_small(d, w, B) && small_head_on(d, w.planes, B);
+  const bool head_slabs = defer_out_reduce && w.loss == Loss::SmallMse;
   for (int l = 0; l < w.L; ++l) {
     const Layer ly = layer_of(d, P, nullptr, l);
+    const LayerRoute& r = w.layer[l];
+    const Stats st = eval_bn ? Stats::None : r.stats;         // (eval_bn: the running statistics, below)
     GemmArgs g = {};
     g.A = a_in; g.B = ly.W; g.C = f32(ws, w.z[l]); g.bias = ly.b;
     g.M = (int)B; g.N = H; g.K = ly.K; g.lda = ly.K; g.ldb = ly.K; g.ldc = H; g.split_k = 1;
     g.arith = arith_of(d);
     g.thin_scratch = f32(ws, w.slabs); g.thin_scratch_floats = w.slab_floats;
-    const bool skinny = l == 0 && skinny_supported(ly.K, H);
-    const int groups = skinny ? skinny_stat_groups((int)B) : w.G;
     float* stat = f32(ws, w.stat);
-    // small batches: statistics, finalize and apply in ONE launch straight from z (bn_small_fwd_kernel) -- no partials
-    const bool small = bn_small(d, w, B) && !eval_bn;
-    if (small && (l > 0 ? small_layer_on(d, w.planes, B) : small_first_on(d, w.planes, B))) {
-      // ... and the Linear rides in the same launch
-      const float* resid = (l >= 2 && (l % 2) == 0) ? f32(ws, w.act[l - 2]) : nullptr;
+    const float* resid = (l >= 2 && (l % 2) == 0) ? f32(ws, w.act[l - 2]) : nullptr;
+    if (st == Stats::InLayer) {
       const bool slabs_here = head_slabs && l == w.L - 1;
       PL_TRY(launch_small_layer_fwd(a_in, ly.W, ly.b, ly.gamma, ly.beta, d->bn_eps, d->bn_momentum, ly.rm, ly.rv, ly.nbt,
                                     f32(ws, w.mean[l]), f32(ws, w.rstd[l]), resid, g.C, f32(ws, w.act[l]), u64(ws, w.bits[l]),
                                     (int)B, H, ly.K, d->p_dropout, seed, step, l,
                                     inject_keep ? inject_keep + (size_t)l * inj_stride : nullptr, s, d->step_dev, l == 0,
                                     slabs_here ? d->params + P.off[4 * w.L] : nullptr, slabs_here ? f32(ws, w.slabs) : nullptr,
-                                    d->out_dim, (small_f16_on(d, w) && l > 0) ? u16(ws, w.sactp[l - 1]) : nullptr,
-                                    (small_f16_on(d, w) && l + 1 < w.L) ? u16(ws, w.sactp[l]) : nullptr));
+                                    d->out_dim, sact_in(w, ws, l), sact_out(w, ws, l)));
       a_in = f32(ws, w.act[l]);
       continue;
     }
-    if (d->bn && !eval_bn && !small) {
-      g.stat_sum = stat + (size_t)sync_rank(d) * 2 * groups * H;
-      g.stat_m2 = g.stat_sum + (size_t)groups * H;
+    if (st == Stats::InApply || st == Stats::Finalize) {
+      g.stat_sum = stat + (size_t)sync_rank(d) * 2 * r.groups * H;
+      g.stat_m2 = g.stat_sum + (size_t)r.groups * H;
     }
-    if (skinny) {
+    if (r.lin == Lin::Skinny) {
       PL_TRY(launch_skinny_wide_out(a_in, ly.W, ly.b, g.C, (int)B, ly.K, H, false, g.stat_sum, g.stat_m2, s));
-    } else if (w.planes && l > 0 && mid_linear_on(d, w, B)) {
-      // 128 ... 512 rows: the tile GEMM has 8 ... 32 tiles for 256 CUs (22 us whatever the size); one 64-row block x 16 columns
-      // per workgroup on the layer kernels' contraction instead, same operand planes, same statistics partials
-      PL_TRY(launch_small_linear_stats(nullptr, u16(ws, w.actp[l - 1]), ly.W, ly.b, g.C, (int)B, H, H, g.stat_sum, g.stat_m2, groups, s));
-    } else if (w.planes && l > 0) {
+    } else if (r.lin == Lin::PlanesMid) {
+      PL_TRY(launch_small_linear_stats(nullptr, u16(ws, w.actp[l - 1]), ly.W, ly.b, g.C, (int)B, H, H, g.stat_sum, g.stat_m2, r.groups, s));
+    } else if (r.lin == Lin::Planes) {
       PlanesGemmArgs pg = planes_args(w.pkind, u16(ws, w.actp[l - 1]), BH, H, wplane(d, w, ws, l), (int64_t)H * H, H, g.C, (int)B, H, H,
                                       1.0f / (kActPlaneScale * kWeightPlaneScale), nullptr);
       pg.e.bias = ly.b; pg.e.stat_sum = g.stat_sum; pg.e.stat_m2 = g.stat_m2;
       PL_TRY(launch_gemm_planes(kNT, pg, s));
-    } else if (l > 0 && !w.planes && mid_linear_f32_on(d, B)) {
-      // off the planes path (ragged rows, exact-fp32 / bf16x6 descriptors), up to 512 rows: the same kernel on fp32 operands
-      // (exact-fp32 MFMA) instead of the thin GEMM + its reduce or an 8 ... 32-tile GEMM
-      PL_TRY(launch_small_linear_stats(a_in, nullptr, ly.W, ly.b, g.C, (int)B, H, H, g.stat_sum, g.stat_m2, groups, s));
+    } else if (r.lin == Lin::F32Mid) {
+      PL_TRY(launch_small_linear_stats(a_in, nullptr, ly.W, ly.b, g.C, (int)B, H, H, g.stat_sum, g.stat_m2, r.groups, s));
     } else {
       PL_TRY(launch_gemm_f32(kNT, g, s));
     }
     const float *scale = nullptr, *shift = nullptr;
     BnFinalizeArgs fin = {};
-    bool use_fin = false;
+    float* sc = f32(ws, w.scale) + (size_t)l * H;
+    float* sh = f32(ws, w.shift) + (size_t)l * H;
     if (d->bn && eval_bn) {
-      float* sc = f32(ws, w.scale) + (size_t)l * H;
-      float* sh = f32(ws, w.shift) + (size_t)l * H;
       PL_TRY(launch_bn_eval_stats(ly.gamma, ly.beta, ly.rm, ly.rv, d->bn_eps, H, f32(ws, w.mean[l]), f32(ws, w.rstd[l]),
                                   sc, sh, s));
       scale = sc; shift = sh;
-    } else if (d->bn && !small && fin_in_apply(d, groups)) {
-      // local statistics of at most 4 groups (<= 256 rows): finalized inside the apply launch below
-      fin = BnFinalizeArgs{stat, groups, 64, ly.gamma, ly.beta, d->bn_eps, d->bn_momentum, ly.rm, ly.rv, ly.nbt,
+    } else if (st == Stats::InApply) {
+      fin = BnFinalizeArgs{stat, r.groups, 64, ly.gamma, ly.beta, d->bn_eps, d->bn_momentum, ly.rm, ly.rv, ly.nbt,
                            f32(ws, w.mean[l]), f32(ws, w.rstd[l])};
-      use_fin = true;
-    } else if (d->bn && !small) {
-      float* sc = f32(ws, w.scale) + (size_t)l * H;
-      float* sh = f32(ws, w.shift) + (size_t)l * H;
-      PL_TRY(sync_gather(d, stat, (int64_t)2 * groups * H, s));
-      PL_TRY(launch_bn_finalize(stat, groups, sync_world(d), (int)B, H, ly.gamma, ly.beta, d->bn_eps,
+    } else if (st == Stats::Finalize) {
+      PL_TRY(sync_gather(d, stat, (int64_t)2 * r.groups * H, s));
+      PL_TRY(launch_bn_finalize(stat, r.groups, sync_world(d), (int)B, H, ly.gamma, ly.beta, d->bn_eps,
                                 d->bn_momentum, ly.rm, ly.rv, ly.nbt, f32(ws, w.mean[l]),
                                 f32(ws, w.rstd[l]), sc, sh, s));
       scale = sc; shift = sh;
-    }
-    const float* resid = (l >= 2 && (l % 2) == 0) ? f32(ws, w.act[l - 2]) : nullptr;
-    if (small) {
+    } else if (st == Stats::Small) {
       PL_TRY(launch_bn_small_fwd(g.C, ly.gamma, ly.beta, d->bn_eps, d->bn_momentum, ly.rm, ly.rv, ly.nbt, f32(ws, w.mean[l]),
                                  f32(ws, w.rstd[l]), resid, f32(ws, w.act[l]), u64(ws, w.bits[l]), (int)B, H, d->p_dropout, seed,
                                  step, l, inject_keep ? inject_keep + (size_t)l * inj_stride : nullptr, s, d->step_dev));
@@ -691,14 +709,14 @@ static int fwd_saved_impl(const PLDesc* d, const float* x, float* y, int64_t B, 
     PL_TRY(launch_bn_apply(g.C, scale, shift, resid, act, u64(ws, w.bits[l]), (int)B, H,
                            eval_bn ? 0.f : d->p_dropout, seed, step, l,
                            inject_keep ? inject_keep + (size_t)l * inj_stride : nullptr, s, &po,
-                           eval_bn ? nullptr : d->step_dev, use_fin ? &fin : nullptr));
+                           eval_bn ? nullptr : d->step_dev, st == Stats::InApply ? &fin : nullptr));
     a_in = act;
   }
   if (head_slabs) return PL_OK;
   if (defer_out_reduce)   // (the fused train step: y = bias + slabs is formed by the MSE pass, mse_partial_from_slabs)
     return launch_skinny_narrow_out(a_in, d->params + P.off[4 * w.L], d->params + P.off[4 * w.L + 1], y, (int)B, H, d->out_dim,
                                     f32(ws, w.slabs), s, false);
-  return gemm_out_layer(a_in, d->params + P.off[4 * w.L], d->params + P.off[4 * w.L + 1], y, (int)B,
+  return gemm_out_layer(w.out_narrow, a_in, d->params + P.off[4 * w.L], d->params + P.off[4 * w.L + 1], y, (int)B,
                         d->out_dim, H, f32(ws, w.slabs), s);
 }
 
@@ -735,20 +753,19 @@ static int bwd_impl(const PLDesc* d, const float* x, const float* dy, int64_t B,
     jpart.push_back(part); jout.push_back(out); jR.push_back(R); jH.push_back(Hj); jkind.push_back(kind); jtrans.push_back(transK);
   };
 
-  // small batches (small_layer.hip): which layers' forward left a tile-format bitmap, and what describes a layer's BatchNorm
-  const bool sl_all = bn_small(d, w, B) && !eval_bn && small_layer_on(d, w.planes, B);
-  const bool sl_first = sl_all && small_first_on(d, w.planes, B);
+  // small batches (small_layer.hip): what describes a layer's BatchNorm -- and its bitmap's format
+  const bool small = !eval_bn && w.bn_small, sl = !eval_bn && w.small_layer;
   auto bn_layer = [&](int l) {
     const Layer y = layer_of(d, P, grads, l);
     SmallBnLayer b = {f32(ws, w.z[l]), f32(ws, w.mean[l]), f32(ws, w.rstd[l]), y.gamma, u64(ws, w.bits[l]),
-                      l == 0 && !sl_first, y.ggamma, y.gbeta, y.gb};
+                      w.layer[l].stats != Stats::InLayer, y.ggamma, y.gbeta, y.gb};
     return b;
   };
   // the output layer and the BatchNorm backward of the top hidden layer in one launch (dz of that layer: DZ)
   const int n_loss_part = loss_partials > 0 ? loss_partials : mse_partials(B * O);   // partial sums of the loss in w.mse
-  const bool top_fused = do_output && sl_all && small_top_on(d, w.planes, B) && l_hi == w.L - 1 && l_hi >= l_lo;
+  const bool top_fused = do_output && !eval_bn && w.top_fused && l_hi == w.L - 1 && l_hi >= l_lo;
   // the AdamW step carried by the backward launches (pl_lifter_train_step): which slice of the arena rides with layer l
-  const bool adam_rides = adam && top_fused && l_lo == 0 && H % 128 == 0;
+  const bool adam_rides = adam && top_fused && l_lo == 0 && w.adam_rides;
   auto ride = [&](int64_t lo, int64_t hi) {
     AdamWRide r = {};
     r.p = const_cast<float*>(d->params) + lo; r.g = grads + lo; r.m = adam->m + lo; r.v = adam->v + lo; r.n = hi - lo;
@@ -760,72 +777,62 @@ static int bwd_impl(const PLDesc* d, const float* x, const float* dy, int64_t B,
     PL_TRY(launch_small_top_bwd(dy, d->params + P.off[4 * w.L], f32(ws, w.act[w.L - 1]), Bi, H, O, GA, grads + P.off[4 * w.L],
                                 grads + P.off[4 * w.L + 1], bn_layer(w.L - 1), kscale, DZ, s, f32(ws, w.mse),
                                 n_loss_part, 1.0f / (float)(B * O), loss_out, const_cast<uint64_t*>(d->step_dev)));
-  } else if (do_output) {
-  // final Linear (LinearModel.w2): dW = dy^T h, db = sum dy, g = dy W
-  const float* W5 = d->params + P.off[4 * w.L];
-  const float* h_last = f32(ws, w.act[w.L - 1]);
-  if (skinny_supported(O, H)) {
+  } else if (do_output && w.out_skinny) {
+    // final Linear (LinearModel.w2): dW = dy^T h, db = sum dy, g = dy W
     // dW5 partials, and -- the kernel holds every row of dy in its A fragments -- the bias gradient's partial column sums
     // (Round 3 tried this launch on a side stream -- nothing reads its output before the closing reduce, and it and the head of
     //  the chain below are both latency-bound -- forked and joined with events: 0.627 -> 0.660 ms per step eager, 0.644 -> 0.663
     //  replayed from a graph, same box: the two cross-stream dependencies cost more than the 13 us launch they hide.)
-    PL_TRY(launch_skinny_wide_in(dy, h_last, grads + P.off[4 * w.L], Bi, O, H, false, f32(ws, w.skp_out), s, false,
-                                 f32(ws, w.outpart)));
+    PL_TRY(launch_skinny_wide_in(dy, f32(ws, w.act[w.L - 1]), grads + P.off[4 * w.L], Bi, O, H, false, f32(ws, w.skp_out), s,
+                                 false, f32(ws, w.outpart)));
     job(f32(ws, w.skp_out), grads + P.off[4 * w.L], skinny_in_chunks(Bi), O * H, 0, 0);
     job(f32(ws, w.outpart), grads + P.off[4 * w.L + 1], skinny_in_chunks(Bi), O, 0, 0);
-  } else {
-    PL_TRY(gemm_tn_reduced(dy, O, h_last, H, grads + P.off[4 * w.L], O, H, Bi, slabs, s));
+    GemmArgs be = {};
+    const int lt = w.L - 1;
+    if (!eval_bn && w.layer[lt].bnr_fused) {      // pass 1 of the top hidden layer, on the block just produced
+      const BnrSlab sl = bnr_slab(d, w, ws, Bi / 64, (w.pkind == 2 && lt > 0) ? (Bi / 64) * (H / 32) : 0, eval_bn);
+      be.bnr_z = f32(ws, w.z[lt]); be.bnr_bits = u64(ws, w.bits[lt]);
+      be.bnr_mean = f32(ws, w.mean[lt]); be.bnr_rstd = f32(ws, w.rstd[lt]); be.bnr_kscale = kscale;
+      be.bnr_part_dy = sl.mine; be.bnr_part_dyz = sl.mine + (size_t)(Bi / 64) * H;
+      be.bnr_amax = (w.pkind == 2 && lt > 0) ? sl.amax_mine : nullptr;
+    }
+    PL_TRY(launch_skinny_wide_out(dy, d->params + P.off[4 * w.L], nullptr, GA, Bi, O, H, true, nullptr, nullptr, s, &be));
+  } else if (do_output) {
+    PL_TRY(gemm_tn_reduced(dy, O, f32(ws, w.act[w.L - 1]), H, grads + P.off[4 * w.L], O, H, Bi, slabs, s));
     PL_TRY(launch_colsum_partial(dy, Bi, O, f32(ws, w.outpart), s));
     job(f32(ws, w.outpart), grads + P.off[4 * w.L + 1], colsum_chunks(Bi), O, 0, 0);
-  }
-  {
     GemmArgs g = {};
-    g.A = dy; g.B = W5; g.C = GA; g.M = Bi; g.N = H; g.K = O; g.lda = O; g.ldb = H; g.ldc = H; g.split_k = 1;
-    if (skinny_supported(O, H)) {
-      GemmArgs be = {};
-      const int lt = w.L - 1;
-      if (fused_reduce(d, w.planes, lt, w.L, eval_bn)) {      // pass 1 of the top hidden layer, on the block just produced
-        const BnrSlab sl = bnr_slab(d, w, ws, Bi / 64, (w.pkind == 2 && lt > 0) ? (Bi / 64) * (H / 32) : 0, eval_bn);
-        be.bnr_z = f32(ws, w.z[lt]); be.bnr_bits = u64(ws, w.bits[lt]);
-        be.bnr_mean = f32(ws, w.mean[lt]); be.bnr_rstd = f32(ws, w.rstd[lt]); be.bnr_kscale = kscale;
-        be.bnr_part_dy = sl.mine; be.bnr_part_dyz = sl.mine + (size_t)(Bi / 64) * H;
-        be.bnr_amax = (w.pkind == 2 && lt > 0) ? sl.amax_mine : nullptr;
-      }
-      PL_TRY(launch_skinny_wide_out(dy, W5, nullptr, GA, Bi, O, H, true, nullptr, nullptr, s, &be));
-    } else {
-      PL_TRY(launch_gemm_f32(kNN, g, s));
-    }
+    g.A = dy; g.B = d->params + P.off[4 * w.L]; g.C = GA; g.M = Bi; g.N = H; g.K = O; g.lda = O; g.ldb = H; g.ldc = H;
+    g.split_k = 1;
+    PL_TRY(launch_gemm_f32(kNN, g, s));
   }
-  }  // do_output
 
-  bool first_wgrad_done = false;
   for (int l = l_hi; l >= l_lo; --l) {
     const Layer ly = layer_of(d, P, grads, l);
+    const LayerRoute& r = w.layer[l];
     // gradient w.r.t. this layer's activation: GA for layer 0 and even layers, GB for odd ones
     const float* gin = (l % 2 == 1) ? GB : GA;
     const uint64_t* bits = u64(ws, w.bits[l]);
     const float* z = f32(ws, w.z[l]);
-    const bool pl_layer = w.planes && l > 0;       // this layer's dz feeds the planes GEMM pair
+    const bool pl_layer = r.bwd == Bwd::PlanesPair;       // this layer's dz feeds the planes GEMM pair
     float* dzs = (pl_layer && w.pkind == 2) ? f32(ws, w.dzscale) + 2 * l : nullptr;   // fp16 planes of dz are range-scaled
     PlaneOut dzo = {nullptr, nullptr, 1.0f, dzs, 0};
     if (pl_layer) { dzo.h = u16(ws, w.dzp); dzo.l = dzo.h + BH; dzo.kind = w.pkind; }
-    const bool small = bn_small(d, w, B) && !eval_bn;
     // small batches, layer kernels (small_layer.hip): the dX launch of layer l + 1 already ran this layer's BatchNorm backward
     // (dz_l sits in dzbuf(l)) unless this layer heads the range
-    const bool sl = small && small_layer_on(d, w.planes, B);
     auto dzbuf = [&](int layer) { return (sl && (layer & 1)) ? GB : DZ; };   // (alternating: a launch reads dz_l and writes dz_{l-1})
     float* DZl = dzbuf(l);
-    if (small && sl && (l < l_hi || top_fused)) {
+    if (sl && (l < l_hi || top_fused)) {
       // (nothing: done by launch_small_layer_bwd of layer l + 1 / by launch_small_top_bwd)
     } else if (small) {
       // pass 1, the coefficients, dz, the bias gradient and dgamma / dbeta of this layer in one launch (small batches)
       PL_TRY(launch_bn_small_bwd(gin, bits, z, f32(ws, w.mean[l]), f32(ws, w.rstd[l]), ly.gamma, kscale, Bi, H, DZl, ly.ggamma,
-                                 ly.gbeta, ly.gb, s, sl && (l > 0 || sl_first)));
+                                 ly.gbeta, ly.gb, s, r.stats == Stats::InLayer));
     } else if (d->bn) {
       // pass 1 (column sums of dy and dy*zhat): a streaming kernel of its own, or -- round 2 -- already done by the
       // LDS-staged epilogue of the planes GEMM that produced `gin` (round 1 tried it in the dword-per-lane epilogue of
       // the fp32-operand GEMM: +17 us per GEMM for the 7.5 us kernel it removed)
-      const bool fr = fused_reduce(d, w.planes, l, w.L, eval_bn);
+      const bool fr = !eval_bn && r.bnr_fused;
       const int rc_l = fr ? Bi / 64 : w.RC;
       const int n_amax_l = fr ? (Bi / 64) * (l == w.L - 1 ? H / 32 : H / 64) : n_amax;   // (top layer: skinny epilogue, 32-column strips)
       const BnrSlab sl = bnr_slab(d, w, ws, rc_l, dzs ? n_amax_l : 0, eval_bn);
@@ -854,7 +861,7 @@ static int bwd_impl(const PLDesc* d, const float* x, const float* dy, int64_t B,
       PlanesGemmArgs nn = planes_args(w.pkind, u16(ws, w.dzp), BH, H, wplane(d, w, ws, l), (int64_t)H * H, H,
                                       (l % 2 == 1) ? GA : GB, Bi, H, H, 1.0f / kWeightPlaneScale, dzs ? dzs + 1 : nullptr);
       if (l % 2 == 1) nn.e.addend = GA;
-      if (fused_reduce(d, w.planes, l - 1, w.L, eval_bn)) {      // pass 1 of the layer below, on the block just produced
+      if (!eval_bn && w.layer[l - 1].bnr_fused) {      // pass 1 of the layer below, on the block just produced
         const bool lower_scaled = w.pkind == 2 && l - 1 > 0;       // its dz planes (fp16) want the range maxima too
         const BnrSlab sl = bnr_slab(d, w, ws, Bi / 64, lower_scaled ? (Bi / 64) * (H / 64) : 0, eval_bn);
         nn.e.bnr_z = f32(ws, w.z[l - 1]);
@@ -872,57 +879,50 @@ static int bwd_impl(const PLDesc* d, const float* x, const float* dy, int64_t B,
       tn.e.split_k = splits;
       PL_TRY(launch_gemm_planes_pair(nn, tn, s));
       if (splits > 1) job(wsl, ly.gW, splits, H * H, 1, 0);
-    } else if (l > 0 && sl) {
-      // small batches: dX = dz W (+ the skip gradient) and the BatchNorm backward of the layer below in one launch when that
-      // layer belongs to this range; the weight gradient is one whole-K launch (K = B <= 64)
-      GemmArgs t = {};
-      t.arith = arith_of(d);
-      t.A = DZl; t.B = a_in; t.M = H; t.N = H; t.K = Bi; t.lda = H; t.ldb = H; t.ldc = H; t.split_k = 1; t.C = ly.gW;
-      // (the weight gradient as extra workgroups of the same launch)
-      const bool dw_rides = H % 128 == 0;
-      if (l - 1 >= l_lo) {
-        // (l == 1: the first layer's weight gradient dW1 = dz_0^T x follows its BatchNorm backward in the same workgroups)
-        first_wgrad_done = l == 1 && small_first_ok(d->in_dim);
-        // AdamW on this launch's spare workgroups: this layer's bias and BatchNorm parameters (their gradients came with the
-        // launch before) and everything above them up to where the launch before started -- the weight matrix of layer
-        // l + 1 (its gradient, too), or the output layer behind the top hidden layer
-        AdamWRide ar = {};
-        if (adam_rides) ar = ride(P.off[4 * l + 1], l == w.L - 1 ? P.total : P.off[4 * (l + 1) + 1]);
-        PL_TRY(launch_small_layer_bwd(DZl, ly.W, (l % 2 == 1) ? GA : nullptr, (l % 2 == 1) ? GA : nullptr, Bi, H, H,
-                                      bn_layer(l - 1), kscale, dzbuf(l - 1), s, dw_rides ? a_in : nullptr,
-                                      dw_rides ? ly.gW : nullptr, first_wgrad_done ? x : nullptr,
-                                      first_wgrad_done ? grads + P.off[0] : nullptr, d->in_dim, adam_rides ? &ar : nullptr));
-        if (dw_rides) continue;
-      } else {
-        GemmArgs g = {};
-        g.A = DZl; g.B = ly.W; g.M = Bi; g.N = H; g.K = H; g.lda = H; g.ldb = H; g.ldc = H; g.split_k = 1;
-        if (l % 2 == 1) { g.C = GA; g.addend = GA; } else { g.C = GB; }
-        g.arith = arith_of(d);
-        g.thin_scratch = slabs; g.thin_scratch_floats = w.slab_floats;
-        PL_TRY(launch_gemm_f32(kNN, g, s));
-      }
-      PL_TRY(launch_gemm_f32(kTN, t, s));
     } else if (l > 0) {
-      // da_in = dz W and dW = dz^T a_in share dz and are independent: ONE launch.  A residual
-      // block's first Linear also receives the skip gradient (in GA, added in the epilogue).
-      // (Tried: dW on a side stream so that the next layer's BatchNorm-backward kernels overlap it --
-      //  -2 % per step only: two single-GEMM workgroups do not fit one CU together, so dX and dW
-      //  time-slice the CUs and the dual launch's co-residency is lost.  Same-box A/B, tools/ab_env.py.)
+      // off the planes path: dX = dz W (+ the skip gradient a residual block's first Linear receives in GA, added in the
+      // epilogue) and dW = dz^T a_in
       GemmArgs g = {};
-      g.A = DZ; g.B = ly.W; g.M = Bi; g.N = H; g.K = H; g.lda = H; g.ldb = H; g.ldc = H; g.split_k = 1;
+      g.A = DZl; g.B = ly.W; g.M = Bi; g.N = H; g.K = H; g.lda = H; g.ldb = H; g.ldc = H; g.split_k = 1;
       if (l % 2 == 1) { g.C = GA; g.addend = GA; } else { g.C = GB; }
       g.arith = arith_of(d);
       g.thin_scratch = slabs; g.thin_scratch_floats = w.slab_floats;   // (the pair runs as two launches off the tile grid)
       GemmArgs t = {};
       t.arith = g.arith;
-      t.A = DZ; t.B = a_in; t.M = H; t.N = H; t.K = Bi; t.lda = H; t.ldb = H; t.ldc = H;
+      t.A = DZl; t.B = a_in; t.M = H; t.N = H; t.K = Bi; t.lda = H; t.ldb = H; t.ldc = H; t.split_k = 1; t.C = ly.gW;
+      if (sl && (r.bwd == Bwd::SmallLayer || r.bwd == Bwd::SmallLayerDw)) {
+        // small batches: dX and the BatchNorm backward of the layer below in one launch when that layer belongs to this
+        // range; the weight gradient is one whole-K launch (K = B <= 64) or extra workgroups of the same launch
+        const bool dw_rides = r.bwd == Bwd::SmallLayerDw;
+        if (l - 1 >= l_lo) {
+          const bool w1 = l == 1 && w.layer[0].bwd == Bwd::InAbove;
+          // AdamW on this launch's spare workgroups: this layer's bias and BatchNorm parameters (their gradients came with the
+          // launch before) and everything above them up to where the launch before started -- the weight matrix of layer
+          // l + 1 (its gradient, too), or the output layer behind the top hidden layer
+          AdamWRide ar = {};
+          if (adam_rides) ar = ride(P.off[4 * l + 1], l == w.L - 1 ? P.total : P.off[4 * (l + 1) + 1]);
+          PL_TRY(launch_small_layer_bwd(DZl, ly.W, (l % 2 == 1) ? GA : nullptr, (l % 2 == 1) ? GA : nullptr, Bi, H, H,
+                                        bn_layer(l - 1), kscale, dzbuf(l - 1), s, dw_rides ? a_in : nullptr,
+                                        dw_rides ? ly.gW : nullptr, w1 ? x : nullptr, w1 ? grads + P.off[0] : nullptr, d->in_dim,
+                                        adam_rides ? &ar : nullptr));
+          if (dw_rides) continue;
+        } else {
+          PL_TRY(launch_gemm_f32(kNN, g, s));
+        }
+        PL_TRY(launch_gemm_f32(kTN, t, s));
+        continue;
+      }
+      // dX and dW share dz and are independent: ONE launch.
+      // (Tried: dW on a side stream so that the next layer's BatchNorm-backward kernels overlap it --
+      //  -2 % per step only: two single-GEMM workgroups do not fit one CU together, so dX and dW
+      //  time-slice the CUs and the dual launch's co-residency is lost.  Same-box A/B, tools/ab_env.py.)
       const int splits = tn_splits(H, H, Bi);
       t.split_k = splits; t.C = splits > 1 ? slabs : ly.gW;
       PL_TRY(launch_gemm_f32_pair(g, t, s));
       if (splits > 1) PL_TRY(launch_reduce_slabs(slabs, splits, (int64_t)H * H, ly.gW, s));
-    } else if (first_wgrad_done) {
+    } else if (r.bwd == Bwd::InAbove && sl && l_hi > 0) {
       // (layer 0's weight gradient came with its BatchNorm backward, small_layer.hip)
-    } else if (skinny_supported(ly.K, H)) {
+    } else if (r.lin == Lin::Skinny) {
       PL_TRY(launch_skinny_wide_in(a_in, DZ, ly.gW, Bi, ly.K, H, true, f32(ws, w.skp_in), s, false));
       job(f32(ws, w.skp_in), ly.gW, skinny_in_chunks(Bi), ly.K * H, 0, ly.K);
     } else {
@@ -1293,9 +1293,7 @@ extern "C" int pl_lifter_train_fwd_bwd(const PLDesc* d, const float* x, const fl
 
 extern "C" int pl_lifter_step_carries_adamw(const PLDesc* d, int64_t B) {
   PL_TRY(check_desc(d, false));
-  if (B <= 0) return 0;
-  const bool planes = planes_kind(d, B) != 0;
-  return (bn_small_ok(d, planes, B) && small_head_on(d, planes, B) && d->hidden % 128 == 0) ? 1 : 0;
+  return B > 0 && plan(d, B).adam_rides ? 1 : 0;
 }
 
 extern "C" int pl_lifter_train_step(const PLDesc* d, const float* x, const float* target, int64_t B, void* ws, size_t ws_bytes,
@@ -1318,28 +1316,20 @@ static int train_fwd_bwd_impl(const PLDesc* d, const float* x, const float* targ
   PL_TRY(check_ws(w, ws, ws_bytes));
   float* dy = f32(ws, w.dyout);
   const int L = 1 + 2 * d->num_stage;
-  bool small_head = false;      // the loss partials in w.mse are launch_small_mse's
-  if (hi == L) {
+  if (hi == L && w.loss == Loss::PartialOnly) {
+    PL_TRY(pl_lifter_fwd_train(d, x, y, B, ws, ws_bytes, seed, step, nullptr, stream));
+    PL_TRY(mse_partial_only(y, target, B * d->out_dim, 1.0f, dy, f32(ws, w.mse), stream));
+  } else if (hi == L) {
+    // the forward leaves the output Linear's slabs, the MSE pass adds them up
     const int H = d->hidden, O = d->out_dim;
-    const int so = skinny_narrow_out_supported(H, O) ? skinny_narrow_out_splits((int)B, H) : 0;
-    if (bn_small(d, w, B) && small_head_on(d, w.planes, B)) {
-      // small batches: the output Linear's slabs come from the last hidden layer's launch (small_layer.hip)
-      PL_TRY(fwd_saved_impl(d, x, y, B, ws, ws_bytes, seed, step, nullptr, stream, false, true));
-      const ParamLayout P = param_layout(d);
-      PL_TRY(launch_small_mse(f32(ws, w.slabs), H / 16, (int)B, O, d->params + P.off[4 * L + 1], target, 1.0f, y, dy,
-                              f32(ws, w.mse), (hipStream_t)stream));
-      small_head = true;
-    } else if (so && mse_from_slabs_supported(so, O)) {
-      // the output Linear's slab reduce folded into the MSE pass: one launch less, the same bits
-      PL_TRY(fwd_saved_impl(d, x, y, B, ws, ws_bytes, seed, step, nullptr, stream, false, true));
-      const ParamLayout P = param_layout(d);
-      PL_TRY(mse_partial_from_slabs(f32(ws, w.slabs), so, (int)B, O, d->params + P.off[4 * L + 1], target, 1.0f, y, dy,
+    PL_TRY(fwd_saved_impl(d, x, y, B, ws, ws_bytes, seed, step, nullptr, stream, false, true));
+    const float* bias = d->params + param_layout(d).off[4 * L + 1];
+    if (w.loss == Loss::SmallMse)
+      PL_TRY(launch_small_mse(f32(ws, w.slabs), H / 16, (int)B, O, bias, target, 1.0f, y, dy, f32(ws, w.mse), (hipStream_t)stream));
+    else
+      PL_TRY(mse_partial_from_slabs(f32(ws, w.slabs), skinny_narrow_out_splits((int)B, H), (int)B, O, bias, target, 1.0f, y, dy,
                                     f32(ws, w.mse), stream));
-    } else {
-      PL_TRY(pl_lifter_fwd_train(d, x, y, B, ws, ws_bytes, seed, step, nullptr, stream));
-      PL_TRY(mse_partial_only(y, target, B * d->out_dim, 1.0f, dy, f32(ws, w.mse), stream));
-    }
   }
   return bwd_impl(d, x, dy, B, ws, ws_bytes, nullptr, grads, stream, hi == L, hi == L ? L - 1 : hi, lo, false,
-                  hi == L ? loss : nullptr, small_head ? small_mse_partials((int)B, d->out_dim) : 0, adam);
+                  hi == L ? loss : nullptr, w.loss == Loss::SmallMse ? small_mse_partials((int)B, d->out_dim) : 0, adam);
 }

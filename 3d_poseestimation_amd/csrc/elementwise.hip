@@ -416,7 +416,7 @@ __device__ __forceinline__ void bn_apply_rows(
   }
 }
 
-// The statistics finalize inside the apply launch (BnFin::stat != NULL; local statistics, at most 16 groups = 1,024 rows):
+// The statistics finalize inside the apply launch (BnFin::stat != NULL; local statistics, at most 4 groups = 256 rows):
 // every workgroup re-derives mean / rstd / scale / shift of its four columns per lane from the partials -- with <= 16 groups
 // bn_finalize_kernel's part p holds group p alone, so its result is the sum over the groups in order, which is what is done
 // here, bit for bit -- and the workgroups with blockIdx.y == 0 write mean, rstd and the running statistics.  At B = 4096 (64

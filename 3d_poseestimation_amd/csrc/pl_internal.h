@@ -164,7 +164,7 @@ int launch_bn_finalize(const float* stat, int G, int world, int B, int H,
 
 // act = [resid +] dropout(relu(z*scale + shift)); bits = keep&positive bitmap
 // planes: also (act == NULL: only) write the activation as GEMM operand planes
-// finalize != NULL: the statistics finalize (launch_bn_finalize's job: local statistics, at most 16 groups) inside this launch;
+// finalize != NULL: the statistics finalize (launch_bn_finalize's job: local statistics, at most 4 groups) inside this launch;
 // scale / shift are then not read
 struct BnFinalizeArgs {
   const float* stat;            // [2][G][H] partials of this process
