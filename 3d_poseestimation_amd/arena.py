@@ -16,8 +16,11 @@ ResNet, the way optim.FlatAdamW does for the lifter:
     folds into it (grad_scale).  zero_grad() sets .grad to None and launches nothing.
 A torch.optim.Optimizer subclass: LR schedulers and the stock Adam state_dict layout ('step', 'exp_avg', 'exp_avg_sq' per
 parameter) work unchanged; capturable=True keeps the step count on the device for train.GraphedModuleStep.
+Every host call that writes a parameter or buffer through a raw pointer bumps the version counters of the tensors it wrote
+(torch.autograd.graph.increment_version), so caches and backward-time checks key on `_version` (and `data_ptr`) alone.
 """
 import torch
+from torch.autograd.graph import increment_version
 
 from . import _lib
 
@@ -37,7 +40,6 @@ class ModuleArena:
             self.offsets.append(off)
             off += (p.numel() + 63) // 64 * 64
         self.numel = off
-        self.generation = 0                 # FlatAdam steps taken on this arena (vit._ViTFn checks it in backward)
         self.flat = torch.zeros(off, dtype=torch.float32, device=dev)
         self.grad = torch.zeros(off, dtype=torch.float32, device=dev)
         for p, o in zip(params, self.offsets):
@@ -70,15 +72,6 @@ class ModuleArena:
             else:
                 runs.append((o, end))
         return runs
-
-
-_generation = 0
-
-
-def weight_generation():
-    """Advanced by every FlatAdam.step(): the step writes the parameters through raw pointers (their _version does not
-    move), so caches derived from parameter values (the f16x3 weight planes of vit.MyViT) key on this counter too."""
-    return _generation
 
 
 def arena_of(module):
@@ -129,8 +122,6 @@ class FlatAdam(torch.optim.Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None, grad_scale=1.0):
-        global _generation
-        _generation += 1
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -139,7 +130,6 @@ class FlatAdam(torch.optim.Optimizer):
         if not a.intact():
             raise _lib.PoseliftError("FlatAdam: the module's parameters left their arena (.to() / .data reassigned): "
                                      "build the optimizer after moving the module")
-        a.generation += 1
         runs = a.gather_grads()
         L, lr = _lib.lib(), g["lr"]
         wd = float(g["weight_decay"]) if g.get("decoupled_weight_decay", False) else 0.0
@@ -166,4 +156,5 @@ class FlatAdam(torch.optim.Optimizer):
                                                float(g["betas"][1]), float(g["eps"]), wd, self._t, float(grad_scale),
                                                _lib.current_stream_ptr()), "pl_adamw_flat")
                 self._step_tensor.fill_(float(self._t))
+        increment_version(a.params)
         return loss

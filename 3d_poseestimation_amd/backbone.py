@@ -23,6 +23,12 @@ from . import conv
 from .heads import soft_argmax_2d, soft_argmax_3d, soft_argmax_3d_nhwc
 
 
+def _weights_key(ts):
+    """What weights folded from the tensors `ts` were derived from: their version counters (the library's raw-pointer
+    writes bump them as well, arena.py) and addresses."""
+    return tuple(t._version for t in ts) + tuple(t.data_ptr() for t in ts)
+
+
 class Bottleneck(nn.Module):
     expansion = 4
 
@@ -68,12 +74,8 @@ class ResNet(nn.Module):
         return nn.Sequential(*layers)
 
     # ---- folded weights: OHWI kernels and (scale, shift) per BatchNorm, rebuilt when a parameter changes
-    def _versions(self):
-        return tuple(t._version for t in list(self.parameters()) + list(self.buffers())) + \
-            tuple(t.data_ptr() for t in self.parameters())
-
     def _folded(self):
-        v = self._versions()
+        v = _weights_key(list(self.parameters()) + list(self.buffers()))
         if self._cache is None or self._cache[0] != v:
             f = {}
             for name, m in self.named_modules():
@@ -257,7 +259,7 @@ class _HeatmapNet(nn.Module):
 
     def _folded(self):
         ts = list(self.deconv_layers.parameters()) + list(self.deconv_layers.buffers()) + list(self.final_layer.parameters())
-        v = tuple(t._version for t in ts) + tuple(t.data_ptr() for t in ts)
+        v = _weights_key(ts)
         if self._cache is None or self._cache[0] != v:
             f = {}
             for i in (0, 3, 6):

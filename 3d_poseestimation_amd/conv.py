@@ -13,6 +13,7 @@ end to end: a feature map IS the [B*H*W][C] matrix the MFMA GEMM wants, a 1x1 co
 convolution is the same GEMM with a gathering A loader (implicit GEMM, no im2col buffer).
 """
 import torch
+from torch.autograd.graph import increment_version
 
 from . import _lib
 
@@ -286,13 +287,13 @@ class _BNReLUFn(torch.autograd.Function):
                                    y.data_ptr(), bits.data_ptr(), mean.data_ptr(), rstd.data_ptr(), scratch.data_ptr(),
                                    _lib.current_stream_ptr())
         _lib.check(rc, "pl_bn_train_fwd")
-        ctx.save_for_backward(z2, bits, mean, rstd, gamma)
-        ctx.shape, ctx.gparam, ctx.bparam = shape, gamma, beta
+        ctx.save_for_backward(z2, bits, mean, rstd, gamma, beta)
+        ctx.shape = shape
         return y.reshape(shape)
 
     @staticmethod
     def backward(ctx, dy):
-        z2, bits, mean, rstd, gamma = ctx.saved_tensors
+        z2, bits, mean, rstd, gamma, beta = ctx.saved_tensors
         rows, C = z2.shape
         dy2 = dy.contiguous().reshape(rows, C)
         dev, L = z2.device, _lib.lib()
@@ -305,7 +306,7 @@ class _BNReLUFn(torch.autograd.Function):
                                        gamma.data_ptr(), rows, C, dz.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
                                        scratch.data_ptr(), _lib.current_stream_ptr())
             _lib.check(rc, "pl_bn_train_bwd")
-        dgamma, dbeta = _pgrad2(ctx.gparam, ctx.bparam, C, dev, run)
+        dgamma, dbeta = _pgrad2(gamma, beta, C, dev, run)
         return dz.reshape(ctx.shape), dgamma, dbeta, None, None, None, None, None, None
 
 
@@ -314,8 +315,10 @@ def batchnorm_relu_train(z, bn, relu=True):
     every leading dimension); updates bn.running_mean / running_var / num_batches_tracked in place."""
     if bn.momentum is None:
         raise NotImplementedError("cumulative moving average (momentum=None)")
-    return _BNReLUFn.apply(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
-                           float(bn.eps), float(bn.momentum), bool(relu))
+    y = _BNReLUFn.apply(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
+                        float(bn.eps), float(bn.momentum), bool(relu))
+    increment_version((bn.running_mean, bn.running_var, bn.num_batches_tracked))
+    return y
 
 
 class _AddReLUFn(torch.autograd.Function):
@@ -581,8 +584,8 @@ class _Conv1x1PlanesFn(torch.autograd.Function):
                 else torch.empty(0, device=xp.device))
         z = _gemm_planes_raw(0, xp, (rows, cin), wp, (cout, cin), rows, cout, cin,
                              1.0 / (ACT_PLANE_SCALE * WEIGHT_PLANE_SCALE), None, link.mode, stat if stat.numel() else None)
-        ctx.save_for_backward(xp)
-        ctx.link, ctx.wparam = link, wparam
+        ctx.save_for_backward(xp, wparam)
+        ctx.link = link
         ctx.mark_non_differentiable(stat)
         ctx.set_materialize_grads(False)       # (no zero tensor the size of `stat` per backward)
         return z, stat
@@ -591,8 +594,7 @@ class _Conv1x1PlanesFn(torch.autograd.Function):
     def backward(ctx, dzp, _gstat):
         if dzp is None:
             return None, None, None
-        (xp,) = ctx.saved_tensors
-        wparam = ctx.wparam
+        xp, wparam = ctx.saved_tensors
         rows, cin = xp.shape
         cout = wparam.shape[0]
         w = wparam.detach().float().reshape(cout, cin)
@@ -650,13 +652,13 @@ class _BNPlanesFn(torch.autograd.Function):
                                       rstd.data_ptr(), scratch.data_ptr(), y.data_ptr() if out_planes else None,
                                       mode, gstat.data_ptr() if gstat is not None else None, None, _lib.current_stream_ptr())
         _lib.check(rc, "pl_bn_train_fwd_ex")
-        ctx.save_for_backward(z2, bits, mean, rstd, gamma)
-        ctx.shape, ctx.link, ctx.gparam, ctx.bparam = shape, link, gamma, beta
+        ctx.save_for_backward(z2, bits, mean, rstd, gamma, beta)
+        ctx.shape, ctx.link = shape, link
         return y.reshape(shape)
 
     @staticmethod
     def backward(ctx, dy):
-        z2, bits, mean, rstd, gamma = ctx.saved_tensors
+        z2, bits, mean, rstd, gamma, beta = ctx.saved_tensors
         rows, C = z2.shape
         dy2 = dy.contiguous().reshape(rows, C)
         dev, L = z2.device, _lib.lib()
@@ -675,16 +677,18 @@ class _BNPlanesFn(torch.autograd.Function):
                                           link.mode if link is not None else _lib.PL_F16X3,
                                           link.dz_scale.data_ptr() if link is not None else None, _lib.current_stream_ptr())
             _lib.check(rc, "pl_bn_train_bwd_ex")
-        dgamma, dbeta = _pgrad2(ctx.gparam, ctx.bparam, C, dev, run)
+        dgamma, dbeta = _pgrad2(gamma, beta, C, dev, run)
         return dz.reshape(ctx.shape), dgamma, dbeta, None, None, None, None, None, None, None, None, None
 
 
 def batchnorm_relu_train_planes(z, bn, relu=True, out_planes=False, link=None, mode=_lib.PL_F16X3):
     if bn.momentum is None:
         raise NotImplementedError("cumulative moving average (momentum=None)")
-    return _BNPlanesFn.apply(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
-                             float(bn.eps), float(bn.momentum), bool(relu), bool(out_planes), link,
-                             link.mode if link is not None else mode)
+    y = _BNPlanesFn.apply(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
+                          float(bn.eps), float(bn.momentum), bool(relu), bool(out_planes), link,
+                          link.mode if link is not None else mode)
+    increment_version((bn.running_mean, bn.running_var, bn.num_batches_tracked))
+    return y
 
 
 class _AddReLUPlanesFn(torch.autograd.Function):
@@ -804,8 +808,8 @@ class _ConvKxKPlanesFn(torch.autograd.Function):
         stat = _stat_buffer(rows, cout, xp.device)
         z = _conv_planes_fwd(xp, xp.shape, wp, w.shape, stride, pad, 1.0 / (ACT_PLANE_SCALE * WEIGHT_PLANE_SCALE), None, link.mode,
                              stat)
-        ctx.save_for_backward(xp)
-        ctx.geom, ctx.link, ctx.wparam = (stride, pad), link, wparam
+        ctx.save_for_backward(xp, wparam)
+        ctx.geom, ctx.link = (stride, pad), link
         ctx.mark_non_differentiable(stat)
         ctx.set_materialize_grads(False)
         return z, stat
@@ -814,8 +818,7 @@ class _ConvKxKPlanesFn(torch.autograd.Function):
     def backward(ctx, dzp, _gstat):
         if dzp is None:
             return None, None, None, None, None
-        (xp,) = ctx.saved_tensors
-        wparam = ctx.wparam
+        xp, wparam = ctx.saved_tensors
         w = wparam.detach().float().permute(0, 2, 3, 1)
         stride, pad = ctx.geom
         B, H, W, cin = xp.shape
@@ -920,8 +923,8 @@ class _StemPlanesFn(torch.autograd.Function):
         stat = _stat_buffer(rows, 64, xp.device)
         z = _conv_planes_fwd(xp, xp.shape, wp, (64, 7, 4, 8), (2, 1), (3, 2, 1), 1.0 / (ACT_PLANE_SCALE * WEIGHT_PLANE_SCALE), None,
                              link.mode, stat)
-        ctx.save_for_backward(xp)
-        ctx.link, ctx.wparam = link, wparam
+        ctx.save_for_backward(xp, wparam)
+        ctx.link = link
         ctx.mark_non_differentiable(stat)
         ctx.set_materialize_grads(False)
         return z, stat
@@ -930,8 +933,7 @@ class _StemPlanesFn(torch.autograd.Function):
     def backward(ctx, dzp, _gstat):
         if dzp is None or not ctx.needs_input_grad[1]:
             return None, None, None
-        (xp,) = ctx.saved_tensors
-        wparam = ctx.wparam
+        xp, wparam = ctx.saved_tensors
         B, H, W2, _ = xp.shape
         _, ho, wo, cout = dzp.shape
         dzp = dzp.contiguous()
@@ -1000,14 +1002,13 @@ class _DeconvPlanesFn(torch.autograd.Function):
                                                       1.0 / (ACT_PLANE_SCALE * WEIGHT_PLANE_SCALE), None,
                                                       _lib.current_stream_ptr())
         _lib.check(rc, "pl_deconv4x4s2_planes_fwd")
-        ctx.save_for_backward(xp)
-        ctx.link, ctx.wparam = link, weight
+        ctx.save_for_backward(xp, weight)
+        ctx.link = link
         return y
 
     @staticmethod
     def backward(ctx, dyp):
-        (xp,) = ctx.saved_tensors
-        weight = ctx.wparam
+        xp, weight = ctx.saved_tensors
         B, H, W, cin = xp.shape
         cout = weight.shape[1]
         dyp = dyp.contiguous()
@@ -1060,14 +1061,13 @@ class _ConvBiasPlanesFn(torch.autograd.Function):
                                       cout, cin, bias.data_ptr(), 1.0 / (ACT_PLANE_SCALE * WEIGHT_PLANE_SCALE), None, None, None,
                                       _lib.current_stream_ptr())
         _lib.check(rc, "pl_gemm_planes_raw")
-        ctx.save_for_backward(xp)
-        ctx.link, ctx.wparam, ctx.bparam = link, wparam, bias
+        ctx.save_for_backward(xp, wparam, bias)
+        ctx.link = link
         return y
 
     @staticmethod
     def backward(ctx, dyp):
-        (xp,) = ctx.saved_tensors
-        wparam, bparam = ctx.wparam, ctx.bparam
+        xp, wparam, bparam = ctx.saved_tensors
         rows, cin = xp.shape
         cout = wparam.shape[0]
         w = wparam.detach().float().reshape(cout, cin)
@@ -1186,14 +1186,14 @@ class _BNJoinPlanesFn(torch.autograd.Function):
                                       link.mode, gstat.data_ptr() if gstat is not None else None, id2.data_ptr(),
                                       _lib.current_stream_ptr())
         _lib.check(rc, "pl_bn_train_fwd_ex")
-        ctx.save_for_backward(z2, bits, mean, rstd, gamma)
-        ctx.shape, ctx.link, ctx.gparam, ctx.bparam = shape, link, gamma, beta
+        ctx.save_for_backward(z2, bits, mean, rstd, gamma, beta)
+        ctx.shape, ctx.link = shape, link
         ctx.set_materialize_grads(False)
         return x.reshape(shape), xp.reshape(shape)
 
     @staticmethod
     def backward(ctx, g, gp):
-        z2, bits, mean, rstd, gamma = ctx.saved_tensors
+        z2, bits, mean, rstd, gamma, beta = ctx.saved_tensors
         rows, C = z2.shape
         dev, L, link = z2.device, _lib.lib(), ctx.link
         if g is None:
@@ -1225,12 +1225,14 @@ class _BNJoinPlanesFn(torch.autograd.Function):
                                               gamma.data_ptr(), rows, C, None, dgamma.data_ptr(), dbeta.data_ptr(), scratch.data_ptr(),
                                               dz.data_ptr(), link.mode, link.dz_scale.data_ptr(), _lib.current_stream_ptr())
                     _lib.check(rc, "pl_bn_train_bwd_ex")
-        dgamma, dbeta = _pgrad2(ctx.gparam, ctx.bparam, C, dev, run)
+        dgamma, dbeta = _pgrad2(gamma, beta, C, dev, run)
         return dz.reshape(ctx.shape), dx.reshape(ctx.shape), dgamma, dbeta, None, None, None, None, None, None
 
 
 def bn_join_planes(z, identity, bn, link):
     if bn.momentum is None:
         raise NotImplementedError("cumulative moving average (momentum=None)")
-    return _BNJoinPlanesFn.apply(z, identity, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
-                                 float(bn.eps), float(bn.momentum), link)
+    x, xp = _BNJoinPlanesFn.apply(z, identity, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
+                                  float(bn.eps), float(bn.momentum), link)
+    increment_version((bn.running_mean, bn.running_var, bn.num_batches_tracked))
+    return x, xp

@@ -13,6 +13,7 @@ import os
 
 import torch
 import torch.distributed as dist
+from torch.autograd.graph import increment_version
 
 
 def init_from_env(backend=None):
@@ -149,6 +150,7 @@ def broadcast_model(model, src=0, group=None):
     dist.broadcast(model.flat_params, src, group=group)
     dist.broadcast(model._bn_running, src, group=group)
     dist.broadcast(model._bn_batches, src, group=group)
+    increment_version(model._arena_tensors)
 
 
 class FlatGrads:

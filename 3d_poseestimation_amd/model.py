@@ -13,6 +13,7 @@ import weakref
 
 import torch
 from torch import nn
+from torch.autograd.graph import increment_version
 
 from . import _lib
 from .layout import bitmap_words_per_row, hidden_layer_prefixes, param_slots
@@ -55,14 +56,14 @@ class _LifterEvalFn(torch.autograd.Function):
         ctx.ticket = _GraphTicket(model)
         weakref.finalize(ctx, LinearModel._release_workspace, ws, ws["busy"])
         weakref.finalize(ctx, ctx.ticket.close)
-        ctx.save_for_backward(x2)
+        ctx.save_for_backward(x2, *params)     # (backward reads the parameter arena: autograd checks their versions)
         ctx.need_dx = x2.requires_grad
         model.last_workspace = ws
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        (x2,) = ctx.saved_tensors
+        x2 = ctx.saved_tensors[0]
         model, ws = ctx.model, ctx.ws
         if not ctx.ticket.open:
             raise _lib.PoseliftError("second backward through the same LinearModel forward (retain_graph): the saved "
@@ -110,13 +111,13 @@ class _LifterFn(torch.autograd.Function):
         ctx.ticket = _GraphTicket(model)
         weakref.finalize(ctx, LinearModel._release_workspace, ws, ws["busy"])
         weakref.finalize(ctx, ctx.ticket.close)          # a graph dropped without backward
-        ctx.save_for_backward(x2)
+        ctx.save_for_backward(x2, *params)               # (backward reads the parameter arena)
         ctx.need_dx = x2.requires_grad
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        (x2,) = ctx.saved_tensors
+        x2 = ctx.saved_tensors[0]
         model, ws = ctx.model, ctx.ws
         if not ctx.ticket.open:
             # the workspace was handed back after the first backward and may hold a later forward by now
@@ -198,6 +199,10 @@ class LinearModel(nn.Module):
         self._flat, self._bn_running, self._bn_batches = flat, running, batches
         self._flat_grad = self._flat_grad_tmp = None
         self._param_list = [named[s.name] for s in self._slots]
+        # what the library writes through raw pointers (training forwards: the BatchNorm buffers; AdamW: the parameters);
+        # every such call bumps these tensors' version counters (arena.py)
+        self._bn_buffers = [t for _, bn in holders for t in (bn.running_mean, bn.running_var, bn.num_batches_tracked)]
+        self._arena_tensors = self._param_list + self._bn_buffers
         self._ws_pool = {}
         self._desc = _lib.PLDesc(
             in_dim=self.input_size, hidden=H, out_dim=self.output_size, num_stage=self.num_stage,
@@ -208,8 +213,8 @@ class LinearModel(nn.Module):
             self._desc.sync = ctypes.pointer(self._sync_struct)
         # GEMM operand planes of the 1024-wide weights (PL_F16X3 / PL_BF16), kept across calls: FlatAdamW refreshes them
         # while it updates the parameters, so the forward has no weight-split pass.  _wplanes_ver = _planes_key() of the
-        # parameters they were derived from (any in-place torch op on a parameter changes the key: then they are stale
-        # and the next forward refreshes them first).
+        # parameters they were derived from (any write to a parameter changes the key: then they are stale and the next
+        # forward refreshes them first).
         self._wplanes, self._wplanes_ver = None, None
         nbytes = 0
         if flat.is_cuda:
@@ -224,8 +229,9 @@ class LinearModel(nn.Module):
     def _planes_key(self):
         """What the persistent weight planes were derived from.  The parameters are attached to the arena with
         `p.data = view`, so every Parameter keeps its OWN version counter: an in-place torch op on a parameter
-        (load_state_dict, nn.init.*, torch.optim.*.step) bumps p._version, never the arena's -- the key therefore holds
-        every parameter's counter next to the arena's (and the arena's address: .to() / re-flattening)."""
+        (load_state_dict, nn.init.*, torch.optim.*.step) or a raw-pointer write of the library bumps p._version, never
+        the arena's -- the key therefore holds every parameter's counter next to the arena's (and the arena's address:
+        .to() / re-flattening)."""
         return (self._flat.data_ptr(), self._flat._version) + tuple(p._version for p in self._param_list)
 
     def _mark_wplanes(self):
@@ -464,6 +470,7 @@ class LinearModel(nn.Module):
             ctypes.byref(self._desc), x2.data_ptr(), y.data_ptr(), B, ws["buf"].data_ptr(), ws["bytes"],
             self._seed, self._step, inj.data_ptr() if inj is not None else None,
             _lib.current_stream_ptr()), "pl_lifter_fwd_train")
+        increment_version(self._bn_buffers)
         self.last_workspace = ws
         return y
 
@@ -553,13 +560,13 @@ class LinearModel(nn.Module):
                     ctypes.byref(self._desc), x2.data_ptr(), target.data_ptr(), B, ws["buf"].data_ptr(), ws["bytes"],
                     self._seed, self._step, y.data_ptr(), loss.data_ptr(), grads.data_ptr(), ctypes.byref(adamw),
                     _lib.current_stream_ptr()), "pl_lifter_train_step")
-                self._wplanes_ver = None          # the parameters changed under the persistent weight planes
             elif sync is not None and sync.world() > 1 and _overlap_ok(sync):
                 for hi, lo, a_lo, a_hi in self._bwd_ranges():
                     call(hi, lo)
                     sync.launch_bucket(grads[a_lo:a_hi])
             else:
                 call(len(self._named_holders()), 0)
+            increment_version(self._arena_tensors if adamw is not None else self._bn_buffers)
         finally:
             self._desc.step_dev = None
             self._release_workspace(ws)

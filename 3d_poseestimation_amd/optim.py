@@ -9,6 +9,7 @@ AdamW structure (per-parameter 'step', 'exp_avg', 'exp_avg_sq'), so the referenc
 checkpoint envelope {'epoch','batch_size','model','optimizer'} (train_1.py:186) round-trips.
 """
 import torch
+from torch.autograd.graph import increment_version
 
 from . import _lib
 
@@ -91,7 +92,8 @@ class FlatAdamW(torch.optim.Optimizer):
 
     def _launch(self, lr, lr_dev, t, t_dev, grad_scale):
         """One pl_adamw_flat_planes launch per run of active tensors.  With the whole arena active (the normal case)
-        the same launch refreshes the model's persistent GEMM weight planes while the new parameters are in registers."""
+        the same launch refreshes the model's persistent GEMM weight planes while the new parameters are in registers.
+        Returns whether it did."""
         model = self._model
         flat, grads = model.flat_params, model.flat_grads
         g = self.param_groups[0]
@@ -106,8 +108,10 @@ class FlatAdamW(torch.optim.Optimizer):
                     t_dev.data_ptr() if t_dev is not None else None, float(grad_scale),
                     _lib.ctypes.byref(planes) if planes is not None else None, _lib.current_stream_ptr())
                 _lib.check(rc, "pl_adamw_flat_planes")
-        # the raw-pointer write bumps no version counter: say explicitly what the planes now are
-        model._wplanes_ver = model._planes_key() if planes is not None else None
+        increment_version(model._param_list)
+        if planes is not None:                # the planes are those of the parameters just written
+            model._wplanes_ver = model._planes_key()
+        return planes is not None
 
     # ---- the step inside the model's fused call (pl_lifter_train_step) ------------------------------------------
     def _step_struct(self, lr, lr_dev, t, t_dev):
@@ -126,9 +130,9 @@ class FlatAdamW(torch.optim.Optimizer):
     # ---- graph replay (train.GraphedTrainStep): the step with t and lr read from device memory ----------------
     def _enqueue_dev(self, lr_dev, t_base, t_dev, grad_scale=1.0):
         """Enqueue (or capture) one step whose t = t_base + *t_dev and lr = *lr_dev; host-side counters are the
-        caller's business (a captured launch runs many times)."""
+        caller's business (a captured launch runs many times).  Returns whether the launch refreshes the weight planes."""
         self._bind()
-        self._launch(0.0, lr_dev, t_base, t_dev, grad_scale)
+        return self._launch(0.0, lr_dev, t_base, t_dev, grad_scale)
 
     def _advance_host(self, n=1):
         self._t += n

@@ -8,6 +8,7 @@
 All arithmetic is in libposelift.so; tensors must live on the ROCm device.
 """
 import torch
+from torch.autograd.graph import increment_version
 
 from . import _lib
 
@@ -220,6 +221,7 @@ class GraphedTrainStep:
                 dst.copy_(src)
             model._step, optimizer._t = step0, t0
             optimizer._step_tensor.fill_(float(t0))
+            increment_version(model._arena_tensors)      # (the copies above wrote the arenas, not these views)
             model._ensure_wplanes()          # restoring the snapshot made the persistent weight planes stale
             torch.cuda.synchronize(dev)
             self.graph = torch.cuda.CUDAGraph()
@@ -228,9 +230,10 @@ class GraphedTrainStep:
             with torch.cuda.graph(self.graph):
                 if adamw is not None:        # small batches: the optimizer step is inside the same call's launches
                     self.loss, y_hat = model.fused_train_fwd_bwd(self._x, self._y, None, step_dev=self._tick, adamw=adamw)
+                    self._refreshes_planes = False
                 else:
                     self.loss, y_hat = model.fused_train_fwd_bwd(self._x, self._y, None, step_dev=self._tick)
-                    optimizer._enqueue_dev(self._lr_dev, t0, self._tick)
+                    self._refreshes_planes = optimizer._enqueue_dev(self._lr_dev, t0, self._tick)
             self.y_hat = y_hat.reshape(self._out_shape)
             model._step = step0                                              # capturing ran nothing
         # the graph owns the dropout-stream step and AdamW's t (both = the capture-time base + the device counter):
@@ -273,10 +276,11 @@ class GraphedTrainStep:
         if not self._in_call:
             self.model._ensure_wplanes()     # parameters changed behind the graph's back (load_state_dict, ...)
         self.graph.replay()
-        if self._in_call:
-            # a small-batch step neither reads nor refreshes the persistent weight planes: they are stale from here on, and
-            # the next call that wants them (an evaluation at a batch on the planes path) refreshes them
-            self.model._wplanes_ver = None
+        # the replay wrote the parameters and BatchNorm buffers through raw pointers; a small-batch step (AdamW in the same
+        # call) leaves the persistent weight planes stale, the separate AdamW launch refreshed them with the parameters
+        increment_version(self.model._arena_tensors)
+        if self._refreshes_planes:
+            self.model._wplanes_ver = self.model._planes_key()
         self.model._step += 1
         self.opt._advance_host(1)
         self.replays += 1
@@ -311,6 +315,7 @@ class GraphedModuleStep:
                 raise _lib.PoseliftError("GraphedModuleStep: the optimizer must be built with capturable=True "
                                          "(its step counter has to live on the device)")
         self.model, self.opt, self.loss_fn = model, optimizer, loss_fn
+        self._state = list(model.parameters()) + list(model.buffers())      # what a replay writes behind autograd's back
         self._in = tuple(t.detach().clone() for t in inputs)
         self._target = target.detach().clone()
         with _lib.on_device(dev):
@@ -353,6 +358,7 @@ class GraphedModuleStep:
             dst.copy_(src)
         self._target.copy_(target)
         self.graph.replay()
+        increment_version(self._state)
         self.replays += 1
         return self.loss
 

@@ -14,15 +14,15 @@ compute_dtype
   "f16x3"  the block Linears (qkv, to_out, mlp.0, mlp.2: forward, data and weight gradients) on the planes GEMM
            (pl_gemm_planes_raw: two fp16 planes per operand, three MFMAs per product).  Activations and gradients are
            split with a power-of-two scale chosen on the device from their max |x| (pl_vit_planes_dyn) -- never a fixed
-           scale; the weights with the static weight-plane scale, cached until the next FlatAdam step (arena.weight_generation)
-           or the next in-place change of the parameter (its _version).  The token head's Linears stay fp32 (the
-           residual stream they read is not normalised).
+           scale; the weights with the static weight-plane scale, cached until the parameter's _version moves (an
+           in-place change or a FlatAdam step).  The token head's Linears stay fp32 (the residual stream they read is not
+           normalised).
 """
 import numpy as np
 import torch
 from torch import nn
 
-from . import _lib, arena, conv
+from . import _lib, conv
 
 DIM_HEAD = 64
 _DTYPES = ("f16x3", "fp32")
@@ -110,7 +110,7 @@ class MyViT(nn.Module):
     def _wplanes(self, w):
         """(planes of W [N][K], planes of W^T [K][N]) with the weight-plane scale; rebuilt after a FlatAdam step or any
         in-place change of the parameter."""
-        key = (arena.weight_generation(), w._version, w.data_ptr())
+        key = (w._version, w.data_ptr())
         hit = self._wcache.get(id(w))
         if hit is not None and hit[0] == key:
             return hit[1]
@@ -206,24 +206,14 @@ def _colsum(x):
     return out
 
 
-def _param_versions(model, ps):
-    """What backward() needs unchanged: every parameter's version counter, and the step count of the model's FlatAdam
-    arena (a step writes the parameters through raw pointers: no version counter moves)."""
-    ar = getattr(model, "_pl_arena", None)
-    return tuple(p._version for p in ps), (ar, ar.generation if ar is not None else None)
-
-
-def _check_versions(model, ps, saved):
+def _check_versions(model, ps, vers):
     """Eager torch's rule for tensors saved for backward: the backward reads the parameters as they are now (the GEMMs,
-    the weight planes), so a parameter changed in place since the forward would mix two versions of the weights."""
-    (vers, (ar, gen)) = saved
+    the weight planes), so a parameter changed since the forward would mix two versions of the weights."""
     for i, (p, v) in enumerate(zip(ps, vers)):
         if p._version != v:
             name = next((n for n, q in model.named_parameters() if q is p), f"#{i}")
-            raise RuntimeError(f"MyViT backward: parameter {name} was modified by an inplace operation after the forward "
-                               f"(version {v} -> {p._version})")
-    if ar is not None and ar.generation != gen:
-        raise RuntimeError("MyViT backward: FlatAdam.step() changed the parameters after the forward")
+            raise RuntimeError(f"MyViT backward: parameter {name} was modified by an inplace operation or a FlatAdam step "
+                               f"after the forward (version {v} -> {p._version})")
 
 
 class _ViTFn(torch.autograd.Function):
@@ -292,7 +282,7 @@ class _ViTFn(torch.autograd.Function):
         if want:
             ctx.model, ctx.saved, ctx.x2d, ctx.xf, ctx.z, ctx.ps = model, saved, x2d, xf, z, ps
             ctx.dims = (B, seq, in_d, T, Tp, f16)
-            ctx.versions = _param_versions(model, ps)
+            ctx.versions = tuple(p._version for p in ps)     # (a FlatAdam step bumps them too)
         return y
 
     @staticmethod

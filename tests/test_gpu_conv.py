@@ -1062,3 +1062,67 @@ def test_flat_adam_accumulates_a_second_backward_of_the_same_step(pkg):
         assert p.grad is not None and q.grad is not None, k
         den = float(p.grad.abs().max()) + 1e-30
         assert float((p.grad - q.grad).abs().max()) <= 1e-5 * den, (k, float((p.grad - q.grad).abs().max()), den)
+
+
+@pytest.mark.parametrize("dtype", ["f16x3", "bf16x6"])
+@pytest.mark.parametrize("how", ["flat_adam", "graphed"])
+def test_eval_after_training_steps_uses_the_trained_weights(pkg, dtype, how):
+    """phase4's loop (train.py:67 train, :105 eval, every epoch): an eval forward, two training steps whose optimizer and
+    BatchNorm kernels write parameters and running statistics through raw pointers (FlatAdam; GraphedModuleStep replays of
+    torch's capturable Adam), then an eval forward -- bit for bit what a fresh model loaded from the trained state_dict
+    computes, not the folded weights of the first evaluation."""
+    frames = [pkg.synth.structured_frames(4, 120 + i, size=128).to(DEV) for i in range(3)]
+    target = (torch.randn(4, 51, generator=torch.Generator().manual_seed(123)) * 0.3).to(DEV)
+    m = pkg.Model_3D(compute_dtype=dtype)
+    m.load_state_dict(pkg.synth.seeded_state(m.state_dict(), 124))
+    with torch.no_grad():
+        m.final_layer.weight.mul_(1e-2)
+    m = m.to(DEV).train()
+    if how == "flat_adam":
+        opt = pkg.FlatAdam(m, lr=1e-3)
+
+        def step(x, t):
+            opt.zero_grad()
+            pkg.mse_loss(m(x), t).backward()
+            opt.step()
+    else:
+        step = pkg.GraphedModuleStep(m, torch.optim.Adam(m.parameters(), lr=1e-3, capturable=True), F.mse_loss,
+                                     frames[1], target)
+    m.eval()
+    y0 = m(frames[0])
+    m.train()
+    for x in frames[1:]:
+        step(x, target)
+    m.eval()
+    y1 = m(frames[0])
+    fresh = pkg.Model_3D(compute_dtype=dtype).to(DEV).eval()
+    fresh.load_state_dict(m.state_dict())
+    assert torch.equal(y1, fresh(frames[0]))
+    assert not torch.equal(y0, y1)                               # the two steps moved the weights
+
+
+def test_weights_changed_between_forward_and_backward_raise(pkg):
+    """The planes convolutions' backward reads the weight as it is at backward time: a weight changed in place after the
+    forward, or a FlatAdam step in between (raw-pointer writes that bump the parameters' version counters), makes backward
+    raise, as eager torch does for any tensor saved for backward (third finding).  Forward, backward, step
+    is unaffected."""
+    m = pkg.ResNet("resnet50")
+    m.load_state_dict(pkg.synth.seeded_state(m.state_dict(), 125))
+    m = m.to(DEV).train()
+    opt = pkg.FlatAdam(m, lr=1e-4)
+    x = pkg.synth.structured_frames(4, 126, size=128).to(DEV)
+    loss = m(x).square().mean()
+    with torch.no_grad():
+        m.layer1[0].conv1.weight.mul_(1.5)                      # a 1x1 convolution on the planes GEMM
+    with pytest.raises(RuntimeError, match="modified by an inplace operation"):
+        loss.backward()
+    for _ in range(2):
+        opt.zero_grad()
+        loss = m(x).square().mean()
+        loss.backward()
+        opt.step()
+        assert torch.isfinite(loss)
+    loss = m(x).square().mean()
+    opt.step()
+    with pytest.raises(RuntimeError, match="modified by an inplace operation"):
+        loss.backward()

@@ -399,7 +399,7 @@ def test_graphed_train_step_follows_or_refuses_host_side_counter_changes(pkg):
 def test_weight_planes_follow_small_batch_steps(graphed):
     """Training at the reference's batch of 64 (AdamW inside the backward launches: pl_lifter_train_step) never touches the
     persistent weight planes; an evaluation at a batch on the planes path afterwards must see the NEW weights -- eager steps
-    and replayed ones (a replay bumps no tensor version: GraphedTrainStep says so itself)."""
+    and replayed ones (a replay writes through raw pointers: GraphedTrainStep bumps the parameters' versions itself)."""
     import __graft_entry__ as ge
     pkg = ge.build()
     torch.manual_seed(0)
@@ -421,3 +421,48 @@ def test_weight_planes_follow_small_batch_steps(graphed):
         y2 = m(xe).clone()
     assert torch.equal(y1, y2)
     assert (y1 - y0).abs().max().item() > 1e-3  # the three steps moved the weights
+
+
+def test_weight_planes_stay_current_through_optimizer_launches(pkg, monkeypatch):
+    """The separate AdamW launch (pl_adamw_flat_planes) refreshes the persistent weight planes while it writes the
+    parameters: after FlatAdamW.step() -- fused train_step or the autograd route -- and after a GraphedTrainStep replay
+    they are marked current, so no step adds a pl_wplanes_refresh launch.  At B = 64 (AdamW inside the step's own
+    launches, planes untouched) the next evaluation on the planes path equals a fresh model's bit for bit."""
+    L = pkg.lib()
+    calls = []
+    real = L.pl_wplanes_refresh
+
+    def counted(*a):
+        calls.append(a)
+        return real(*a)
+    monkeypatch.setattr(L, "pl_wplanes_refresh", counted)
+    torch.manual_seed(8)
+    m = pkg.LinearModel(34, 51, p_dropout=0.5, compute_dtype="f16x3").to(DEV).train()
+    opt = pkg.FlatAdamW(m, lr=1e-3)
+    B = 256
+    batches = [pkg.synth.synthetic_batch(B, 70 + i, DEV) for i in range(3)]
+    assert not m.step_carries_adamw(B) and m.step_carries_adamw(64)
+    pkg.train_step(m, opt, *batches[0])                     # (the first forward writes the planes)
+    n = len(calls)
+    for x, y in batches[1:]:
+        pkg.train_step(m, opt, x, y)
+        assert m._wplanes_ver == m._planes_key()
+    opt.zero_grad()
+    pkg.mse_loss(m(x).reshape(B, 17, 3), y).backward()
+    opt.step()
+    assert m._wplanes_ver == m._planes_key()
+    assert len(calls) == n
+    step = pkg.GraphedTrainStep(m, opt, *batches[0])       # (restoring its snapshot: one refresh)
+    n = len(calls)
+    for x, y in batches:
+        step(x, y)
+        assert m._wplanes_ver == m._planes_key()
+    assert len(calls) == n
+    xs, ys = pkg.synth.synthetic_batch(64, 80, DEV)
+    for _ in range(2):
+        pkg.train_step(m, opt, xs, ys)
+    m.eval()
+    fresh = pkg.LinearModel(34, 51, p_dropout=0.5, compute_dtype="f16x3").to(DEV).eval()
+    fresh.load_state_dict(m.state_dict())
+    with torch.no_grad():
+        assert torch.equal(m(batches[0][0]), fresh(batches[0][0]))
