@@ -213,6 +213,17 @@ SIGNATURES = {
     "pl_vit_head_bwd": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int, _P, _c.c_int, _P, _P, _P, _P]),
     "pl_vit_planes_scratch_bytes": (_c.c_size_t, []),
     "pl_vit_planes_dyn": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _c.c_int64, _P, _P, _P, _P, _P]),
+    "pl_vit_ln_fwd_bf16": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int, _c.c_int, _P, _P, _P, _P, _c.c_float, _P, _P, _P,
+                                      _c.c_int64, _P, _P]),
+    "pl_vit_ln_bwd_bf16": (_c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_int, _c.c_int, _P, _P, _P, _P, _P, _c.c_int64, _P,
+                                      _P, _P]),
+    "pl_vit_attn_fwd_bf16": (_c.c_int, [_P, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _c.c_float, _P, _P, _c.c_int64, _P,
+                                        _P]),
+    "pl_vit_attn_bwd_bf16": (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _c.c_float, _P, _P,
+                                        _c.c_int64, _P]),
+    "pl_vit_gelu_fwd_bf16": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _c.c_int64, _P, _P, _P]),
+    "pl_vit_gelu_bwd_bf16": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _c.c_int64, _P, _P, _P]),
+    "pl_vit_bf16_pack": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _c.c_int64, _P, _P]),
     "pl_prof_enable": (_c.c_int, [_c.c_int]),
     "pl_prof_read": (_c.c_int, [_c.c_double, _c.c_double, _c.POINTER(_c.c_double), _c.POINTER(_c.c_int64),
                                 _c.POINTER(_c.c_double)]),

@@ -7,6 +7,12 @@
 //   vit_head_fwd / _bwd      ReLU + the last Linear of the token head (H/2 -> out_d, out_d <= 4)
 //   vit_amax / vit_split     fp16 operand planes of an activation or gradient with a power-of-two scale chosen
 //                            on the device from its max |x| (PL_F16X3 mode)
+//   vit_bf16_pack            fp32 -> bf16 carrier (the one "bf16p" operand no producer here writes: the head's dx)
+// "bf16p" mode: the producers of the block GEMMs' operands (LayerNorm forward / backward, attention forward / backward,
+// GELU forward / backward) also take a bf16 CARRIER of their output, [rows_pad][cols] row-major with the rows past T
+// zero (the padded contraction of the TN weight gradients).  Each carrier element is the kernel's own fp32 result
+// rounded once at the store (__bf16 cast: v_cvt_pk_bf16_f32, round to nearest even, NaN stays NaN).  The kernels take
+// it as a template flag: the <false> instantiations are the fp32 kernels, launched as before.
 // Every parameter gradient is reduced in a fixed order: per-chunk partial sums, then one ordered pass over the
 // chunks (vit_reduce_chunks).  No float atomics anywhere: a repeated step is bitwise equal.
 #include <math.h>
@@ -42,6 +48,26 @@ __device__ __forceinline__ float wave_max(float v) {
 
 inline int blocks_for(int64_t n, int per) { return (int)((n + per - 1) / per); }
 inline int64_t chunks_of(int64_t T) { return (T + kChunkRows - 1) / kChunkRows; }
+
+typedef __bf16 vb4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ unsigned short bf16_bits(float v) {
+  const __bf16 q = (__bf16)v;
+  return __builtin_bit_cast(unsigned short, q);
+}
+
+// 4 consecutive carrier elements (8-byte aligned)
+__device__ __forceinline__ void st_bf16x4(unsigned short* p, float4 v) {
+  vb4 q;
+  q[0] = (__bf16)v.x; q[1] = (__bf16)v.y; q[2] = (__bf16)v.z; q[3] = (__bf16)v.w;
+  *reinterpret_cast<vb4*>(p) = q;
+}
+
+// rows T .. rows_pad-1 of a [rows_pad][cols] carrier (cols % 4 == 0) to zero, by every thread of the calling workgroup
+__device__ __forceinline__ void zero_pad_rows(unsigned short* c, int64_t T, int64_t rows_pad, int64_t cols) {
+  const int64_t e1 = rows_pad * cols / 4;
+  for (int64_t e = T * cols / 4 + threadIdx.x; e < e1; e += NT) reinterpret_cast<uint2*>(c)[e] = make_uint2(0u, 0u);
+}
 
 // out[c] = sum over k = 0 .. nchunks-1 of part[k][c], in that order per quarter (k = q mod 4), quarters summed 0..3
 __global__ void __launch_bounds__(NT) vit_reduce_chunks(const float* __restrict__ part, int nchunks, int ncols,
@@ -158,13 +184,20 @@ __device__ __forceinline__ float4 ln_apply4(float4 x, float shift, float mean, f
 }
 
 // x_out = x + add (add optional); y = LN_nnorm(... LN_1(x_out)); stats [nnorm][2][T] = mean, rstd of each LayerNorm
+// kBf: y also (or only: y may be NULL) as the bf16 carrier yb [rows_pad][H]; the grid covers rows_pad rows
+template <bool kBf>
 __global__ void __launch_bounds__(NT) vit_ln_fwd(const float* __restrict__ x, const float* __restrict__ add, int T, int H,
                                                  int nnorm, const float* __restrict__ g1, const float* __restrict__ b1,
                                                  const float* __restrict__ g2, const float* __restrict__ b2, float eps,
-                                                 float* __restrict__ x_out, float* __restrict__ y, float* __restrict__ stats) {
+                                                 float* __restrict__ x_out, float* __restrict__ y, float* __restrict__ stats,
+                                                 unsigned short* __restrict__ yb, int rows_pad) {
   const int t = blockIdx.x * (NT / kWave) + threadIdx.x / kWave, lane = threadIdx.x % kWave;
-  if (t >= T) return;
   const int nv4 = H / 4;
+  if (kBf && t >= T && t < rows_pad) {
+    for (int c = lane; c < nv4; c += kWave) reinterpret_cast<uint2*>(yb + (size_t)t * H)[c] = make_uint2(0u, 0u);
+    return;
+  }
+  if (t >= T) return;
   const float4* xr = reinterpret_cast<const float4*>(x + (size_t)t * H);
   const float4* ar = add ? reinterpret_cast<const float4*>(add + (size_t)t * H) : nullptr;
   LnRow r;
@@ -201,7 +234,14 @@ __global__ void __launch_bounds__(NT) vit_ln_fwd(const float* __restrict__ x, co
 #pragma unroll
     for (int k = 0; k < kLnMaxV; ++k) {
       const int c = lane + k * kWave;
-      if (c < nv4) reinterpret_cast<float4*>(y + (size_t)t * H)[c] = r.v[k];
+      if (c < nv4) {
+        if (kBf) {
+          st_bf16x4(yb + (size_t)t * H + 4 * c, r.v[k]);
+          if (y) reinterpret_cast<float4*>(y + (size_t)t * H)[c] = r.v[k];
+        } else {
+          reinterpret_cast<float4*>(y + (size_t)t * H)[c] = r.v[k];
+        }
+      }
     }
   }
 }
@@ -238,11 +278,13 @@ __device__ __forceinline__ void ln_row_bwd(LnRow& xh, LnRow& dy, const float4* g
 }
 
 // dx = dres + LN_1'( ... LN_nnorm'(dy)); x is the first LayerNorm's input; partial[chunk][nnorm][2][H] = dgamma, dbeta
+// kBf: dx also (or only: dx may be NULL) as the bf16 carrier dxb [rows_pad][H]; the last workgroup zeroes its padding
+template <bool kBf>
 __global__ void __launch_bounds__(NT) vit_ln_bwd(const float* __restrict__ dy, const float* __restrict__ dres,
                                                  const float* __restrict__ x, const float* __restrict__ stats, int T, int H,
                                                  int nnorm, const float* __restrict__ g1, const float* __restrict__ b1,
                                                  const float* __restrict__ g2, float* __restrict__ dx,
-                                                 float* __restrict__ part) {
+                                                 float* __restrict__ part, unsigned short* __restrict__ dxb, int rows_pad) {
   extern __shared__ float4 red4[];              // [NT / kWave][2 * nnorm * H]
   float* red = reinterpret_cast<float*>(red4);
   const int w = threadIdx.x / kWave, lane = threadIdx.x % kWave, nv4 = H / 4, ncols = 2 * nnorm * H;
@@ -295,10 +337,16 @@ __global__ void __launch_bounds__(NT) vit_ln_bwd(const float* __restrict__ dy, c
           const float4 q = rr[c];
           v = make_float4(v.x + q.x, v.y + q.y, v.z + q.z, v.w + q.w);
         }
-        reinterpret_cast<float4*>(dx + (size_t)t * H)[c] = v;
+        if (kBf) {
+          st_bf16x4(dxb + (size_t)t * H + 4 * c, v);
+          if (dx) reinterpret_cast<float4*>(dx + (size_t)t * H)[c] = v;
+        } else {
+          reinterpret_cast<float4*>(dx + (size_t)t * H)[c] = v;
+        }
       }
     }
   }
+  if (kBf && blockIdx.x == gridDim.x - 1) zero_pad_rows(dxb, T, rows_pad, H);
   // waves -> LDS -> one ordered sum per column
   for (int n = 0; n < nnorm; ++n)
 #pragma unroll
@@ -318,8 +366,11 @@ __global__ void __launch_bounds__(NT) vit_ln_bwd(const float* __restrict__ dy, c
 // ---------------------------------------------------------------------------------------------- attention
 // qkv [B*seq][3*HD] (HD = heads * 64; q | k | v, head h at columns h*64 .. h*64+63 of each); one workgroup per sample.
 // LDS: the sample's qkv with rows padded by one float (the score loop's consecutive threads read consecutive key rows).
+// kBf: o only as the bf16 carrier ob [rows_pad][HD] (o may be NULL then); the last workgroup zeroes its padding
+template <bool kBf>
 __global__ void __launch_bounds__(NT) vit_attn_fwd(const float* __restrict__ qkv, int seq, int heads, float scale,
-                                                   float* __restrict__ o, float* __restrict__ lse) {
+                                                   float* __restrict__ o, float* __restrict__ lse,
+                                                   unsigned short* __restrict__ ob, int rows_pad) {
   extern __shared__ float lds[];
   const int HD = heads * kDimHead, ld = 3 * HD + 1;
   float* sq = lds;                          // [seq][ld]
@@ -363,15 +414,23 @@ __global__ void __launch_bounds__(NT) vit_attn_fwd(const float* __restrict__ qkv
     const float* p = sc + (h * seq + i) * kMaxSeq;
     float acc = 0.f;
     for (int j = 0; j < seq; ++j) acc = fmaf(p[j], sq[j * ld + 2 * HD + c], acc);
-    o[((size_t)b * seq + i) * HD + c] = acc;
+    if (kBf) {
+      ob[((size_t)b * seq + i) * HD + c] = bf16_bits(acc);
+      if (o) o[((size_t)b * seq + i) * HD + c] = acc;
+    } else {
+      o[((size_t)b * seq + i) * HD + c] = acc;
+    }
   }
+  if (kBf && b == (int)gridDim.x - 1) zero_pad_rows(ob, (int64_t)gridDim.x * seq, rows_pad, HD);
 }
 
 // P = exp(scale q k^T - lse) recomputed; dP = dO V^T; D = rowsum(P * dP) (= rowsum(dO * O): O = P V);
 // dS = P (dP - D) scale; dQ = dS K, dK = dS^T Q, dV = P^T dO -> dqkv [B*seq][3*HD]
+// kBf: dqkv also (or only: dqkv may be NULL) as the bf16 carrier dqb [rows_pad][3*HD]
+template <bool kBf>
 __global__ void __launch_bounds__(NT) vit_attn_bwd(const float* __restrict__ qkv, const float* __restrict__ lse,
                                                    const float* __restrict__ dout, int seq, int heads, float scale,
-                                                   float* __restrict__ dqkv) {
+                                                   float* __restrict__ dqkv, unsigned short* __restrict__ dqb, int rows_pad) {
   extern __shared__ float lds[];
   const int HD = heads * kDimHead, ld = 3 * HD + 1, ldo = HD + 1;
   float* sq = lds;                                   // [seq][ld]
@@ -430,8 +489,14 @@ __global__ void __launch_bounds__(NT) vit_attn_bwd(const float* __restrict__ qkv
     } else {                    // dv_i = sum_q P_qi dO_q
       for (int r = 0; r < seq; ++r) acc = fmaf(sp[(h * seq + r) * kMaxSeq + i], sd[r * ldo + cc], acc);
     }
-    dqkv[((size_t)b * seq + i) * 3 * HD + c] = acc;
+    if (kBf) {
+      dqb[((size_t)b * seq + i) * 3 * HD + c] = bf16_bits(acc);
+      if (dqkv) dqkv[((size_t)b * seq + i) * 3 * HD + c] = acc;
+    } else {
+      dqkv[((size_t)b * seq + i) * 3 * HD + c] = acc;
+    }
   }
+  if (kBf && b == (int)gridDim.x - 1) zero_pad_rows(dqb, (int64_t)gridDim.x * seq, rows_pad, 3 * HD);
 }
 
 size_t attn_fwd_lds(int seq, int heads) {
@@ -443,20 +508,58 @@ size_t attn_bwd_lds(int seq, int heads) {
 }
 
 // ---------------------------------------------------------------------------------------------- GELU (exact)
-__global__ void __launch_bounds__(NT) vit_gelu_fwd(const float* __restrict__ u, int64_t n, float* __restrict__ y) {
-  for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * NT) {
-    const float v = u[i];
-    y[i] = 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
+__device__ __forceinline__ float gelu_of(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f)); }
+
+__device__ __forceinline__ float gelu_grad_of(float v, float g) {
+  const float cdf = 0.5f * (1.0f + erff(v * 0.70710678118654752f));
+  const float pdf = 0.39894228040143268f * expf(-0.5f * v * v);
+  return g * (cdf + v * pdf);
+}
+
+// kBf: the result also (or only: y may be NULL) as the bf16 carrier yb of n_pad elements, zero past n
+template <bool kBf>
+__global__ void __launch_bounds__(NT) vit_gelu_fwd(const float* __restrict__ u, int64_t n, float* __restrict__ y,
+                                                   unsigned short* __restrict__ yb, int64_t n_pad) {
+  for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < (kBf ? n_pad : n); i += (int64_t)gridDim.x * NT) {
+    if (kBf) {
+      if (i >= n) {
+        yb[i] = 0;
+        continue;
+      }
+      const float r = gelu_of(u[i]);
+      yb[i] = bf16_bits(r);
+      if (y) y[i] = r;
+    } else {
+      y[i] = gelu_of(u[i]);
+    }
   }
 }
 
+template <bool kBf>
 __global__ void __launch_bounds__(NT) vit_gelu_bwd(const float* __restrict__ u, const float* __restrict__ dy, int64_t n,
-                                                   float* __restrict__ du) {
-  for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * NT) {
-    const float v = u[i];
-    const float cdf = 0.5f * (1.0f + erff(v * 0.70710678118654752f));
-    const float pdf = 0.39894228040143268f * expf(-0.5f * v * v);
-    du[i] = dy[i] * (cdf + v * pdf);
+                                                   float* __restrict__ du, unsigned short* __restrict__ dub, int64_t n_pad) {
+  for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < (kBf ? n_pad : n); i += (int64_t)gridDim.x * NT) {
+    if (kBf) {
+      if (i >= n) {
+        dub[i] = 0;
+        continue;
+      }
+      const float r = gelu_grad_of(u[i], dy[i]);
+      dub[i] = bf16_bits(r);
+      if (du) du[i] = r;
+    } else {
+      du[i] = gelu_grad_of(u[i], dy[i]);
+    }
+  }
+}
+
+// fp32 [n] (n % 4 == 0) -> bf16 carrier [n_pad], zero past n
+__global__ void __launch_bounds__(NT) vit_bf16_pack(const float* __restrict__ x, int64_t n, int64_t n_pad,
+                                                    unsigned short* __restrict__ out) {
+  for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n_pad / 4; e += (int64_t)gridDim.x * NT) {
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (4 * e < n) v = reinterpret_cast<const float4*>(x)[e];
+    st_bf16x4(out + 4 * e, v);
   }
 }
 
@@ -646,8 +749,8 @@ extern "C" int pl_vit_ln_fwd(const float* x, const float* add, int64_t T, int H,
   if (!aligned16(x) || (add && (!aligned16(add) || !aligned16(x_out))) || (y && !aligned16(y)) ||
       (g1 && !aligned16(g1)) || (b1 && !aligned16(b1)) || (g2 && !aligned16(g2)) || (b2 && !aligned16(b2)))
     PL_FAIL(PL_EINVAL, "pl_vit_ln_fwd: pointers must be 16-byte aligned");
-  hipLaunchKernelGGL(vit_ln_fwd, dim3(blocks_for(T, NT / kWave)), dim3(NT), 0, (hipStream_t)stream, x, add, (int)T, H, nnorm,
-                     g1, b1, g2, b2, eps, x_out, y, stats);
+  hipLaunchKernelGGL(vit_ln_fwd<false>, dim3(blocks_for(T, NT / kWave)), dim3(NT), 0, (hipStream_t)stream, x, add, (int)T, H,
+                     nnorm, g1, b1, g2, b2, eps, x_out, y, stats, nullptr, (int)T);
   PL_CHECK_LAUNCH("vit_ln_fwd");
   return PL_OK;
 }
@@ -669,8 +772,8 @@ extern "C" int pl_vit_ln_bwd(const float* dy, const float* dres, const float* x,
     PL_FAIL(PL_EINVAL, "pl_vit_ln_bwd: pointers must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   const int64_t nch = chunks_of(T);
-  hipLaunchKernelGGL(vit_ln_bwd, dim3((unsigned)nch), dim3(NT), sizeof(float) * (NT / kWave) * 2 * nnorm * H, s, dy, dres, x, stats, (int)T, H, nnorm, g1, b1, g2, dx,
-                     static_cast<float*>(scratch));
+  hipLaunchKernelGGL(vit_ln_bwd<false>, dim3((unsigned)nch), dim3(NT), sizeof(float) * (NT / kWave) * 2 * nnorm * H, s, dy, dres, x, stats, (int)T, H, nnorm, g1, b1, g2, dx,
+                     static_cast<float*>(scratch), nullptr, (int)T);
   PL_CHECK_LAUNCH("vit_ln_bwd");
   return launch_reduce(static_cast<const float*>(scratch), nch, 2 * nnorm * H, dgb, s);
 }
@@ -692,7 +795,8 @@ extern "C" int pl_vit_attn_fwd(const float* qkv, int64_t B, int seq, int heads, 
   const size_t lds = attn_fwd_lds(seq, heads);
   PL_TRY(attn_check(B, seq, heads, dim_head, lds, "pl_vit_attn_fwd"));
   if (!aligned16(qkv)) PL_FAIL(PL_EINVAL, "pl_vit_attn_fwd: qkv must be 16-byte aligned");
-  hipLaunchKernelGGL(vit_attn_fwd, dim3((unsigned)B), dim3(NT), lds, (hipStream_t)stream, qkv, seq, heads, scale, o, lse);
+  hipLaunchKernelGGL(vit_attn_fwd<false>, dim3((unsigned)B), dim3(NT), lds, (hipStream_t)stream, qkv, seq, heads, scale, o, lse,
+                     nullptr, 0);
   PL_CHECK_LAUNCH("vit_attn_fwd");
   return PL_OK;
 }
@@ -703,8 +807,8 @@ extern "C" int pl_vit_attn_bwd(const float* qkv, const float* lse, const float* 
   const size_t lds = attn_bwd_lds(seq, heads);
   PL_TRY(attn_check(B, seq, heads, dim_head, lds, "pl_vit_attn_bwd"));
   if (!aligned16(qkv) || !aligned16(dout)) PL_FAIL(PL_EINVAL, "pl_vit_attn_bwd: qkv / dout must be 16-byte aligned");
-  hipLaunchKernelGGL(vit_attn_bwd, dim3((unsigned)B), dim3(NT), lds, (hipStream_t)stream, qkv, lse, dout, seq, heads, scale,
-                     dqkv);
+  hipLaunchKernelGGL(vit_attn_bwd<false>, dim3((unsigned)B), dim3(NT), lds, (hipStream_t)stream, qkv, lse, dout, seq, heads, scale,
+                     dqkv, nullptr, 0);
   PL_CHECK_LAUNCH("vit_attn_bwd");
   return PL_OK;
 }
@@ -716,7 +820,7 @@ static unsigned grid_stride_blocks(int64_t n) {
 extern "C" int pl_vit_gelu_fwd(const float* u, int64_t n, float* y, void* stream) {
   if (!u || !y) PL_FAIL(PL_EINVAL, "pl_vit_gelu_fwd: null pointer");
   if (n <= 0) PL_FAIL(PL_ESHAPE, "pl_vit_gelu_fwd: n=%lld", (long long)n);
-  hipLaunchKernelGGL(vit_gelu_fwd, dim3(grid_stride_blocks(n)), dim3(NT), 0, (hipStream_t)stream, u, n, y);
+  hipLaunchKernelGGL(vit_gelu_fwd<false>, dim3(grid_stride_blocks(n)), dim3(NT), 0, (hipStream_t)stream, u, n, y, nullptr, n);
   PL_CHECK_LAUNCH("vit_gelu_fwd");
   return PL_OK;
 }
@@ -724,7 +828,8 @@ extern "C" int pl_vit_gelu_fwd(const float* u, int64_t n, float* y, void* stream
 extern "C" int pl_vit_gelu_bwd(const float* u, const float* dy, int64_t n, float* du, void* stream) {
   if (!u || !dy || !du) PL_FAIL(PL_EINVAL, "pl_vit_gelu_bwd: null pointer");
   if (n <= 0) PL_FAIL(PL_ESHAPE, "pl_vit_gelu_bwd: n=%lld", (long long)n);
-  hipLaunchKernelGGL(vit_gelu_bwd, dim3(grid_stride_blocks(n)), dim3(NT), 0, (hipStream_t)stream, u, dy, n, du);
+  hipLaunchKernelGGL(vit_gelu_bwd<false>, dim3(grid_stride_blocks(n)), dim3(NT), 0, (hipStream_t)stream, u, dy, n, du, nullptr,
+                     n);
   PL_CHECK_LAUNCH("vit_gelu_bwd");
   return PL_OK;
 }
@@ -778,5 +883,147 @@ extern "C" int pl_vit_planes_dyn(const float* x, int64_t rows, int64_t cols, int
   hipLaunchKernelGGL(vit_split, dim3(grid_stride_blocks(rows_pad * cols / 4)), dim3(NT), 0, s, x, rows, cols, rows_pad,
                      static_cast<const float*>(scratch), nb, other_scale, scale, static_cast<unsigned short*>(planes));
   PL_CHECK_LAUNCH("vit_split");
+  return PL_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- "bf16p" carriers
+// The same kernels with the bf16 carrier of their output ([rows_pad][cols], rows past T zero).  A NULL carrier runs the
+// fp32 kernel; with a carrier the fp32 output may be NULL.  Everything is checked before any HIP call.
+static int carrier_check(const void* c, int64_t T, int64_t rows_pad, int64_t cols, const char* who) {
+  if (!c) return PL_OK;
+  if (rows_pad < T || rows_pad % 32 || rows_pad > INT32_MAX / 1024 || cols % 4 || rows_pad * cols > ((int64_t)1 << 40))
+    PL_FAIL(PL_ESHAPE, "%s: carrier rows_pad=%lld for T=%lld rows of %lld (rows_pad >= T, rows_pad %% 32 == 0, cols %% 4 == 0)",
+            who, (long long)rows_pad, (long long)T, (long long)cols);
+  if (!aligned16(c)) PL_FAIL(PL_EINVAL, "%s: the bf16 carrier must be 16-byte aligned", who);
+  return PL_OK;
+}
+
+extern "C" int pl_vit_ln_fwd_bf16(const float* x, const float* add, int64_t T, int H, int nnorm, const float* g1,
+                                  const float* b1, const float* g2, const float* b2, float eps, float* x_out, float* y,
+                                  void* y_bf16, int64_t rows_pad, float* stats, void* stream) {
+  if (!ln_shape_ok(T, H, nnorm)) PL_FAIL(PL_ESHAPE, "pl_vit_ln_fwd_bf16: T=%lld H=%d nnorm=%d", (long long)T, H, nnorm);
+  if (!x || (add && !x_out) || (nnorm >= 1 && (!g1 || !b1 || !(y || y_bf16) || !stats)) || (nnorm == 2 && (!g2 || !b2)) ||
+      (nnorm == 0 && (!add || y_bf16)))
+    PL_FAIL(PL_EINVAL, "pl_vit_ln_fwd_bf16: null pointer");
+  if (!aligned16(x) || (add && (!aligned16(add) || !aligned16(x_out))) || (y && !aligned16(y)) ||
+      (g1 && !aligned16(g1)) || (b1 && !aligned16(b1)) || (g2 && !aligned16(g2)) || (b2 && !aligned16(b2)))
+    PL_FAIL(PL_EINVAL, "pl_vit_ln_fwd_bf16: pointers must be 16-byte aligned");
+  PL_TRY(carrier_check(y_bf16, T, rows_pad, H, "pl_vit_ln_fwd_bf16"));
+  hipStream_t s = (hipStream_t)stream;
+  if (!y_bf16) {
+    hipLaunchKernelGGL(vit_ln_fwd<false>, dim3(blocks_for(T, NT / kWave)), dim3(NT), 0, s, x, add, (int)T, H, nnorm, g1, b1,
+                       g2, b2, eps, x_out, y, stats, nullptr, (int)T);
+  } else {
+    hipLaunchKernelGGL(vit_ln_fwd<true>, dim3(blocks_for(rows_pad, NT / kWave)), dim3(NT), 0, s, x, add, (int)T, H, nnorm, g1,
+                       b1, g2, b2, eps, x_out, y, stats, static_cast<unsigned short*>(y_bf16), (int)rows_pad);
+  }
+  PL_CHECK_LAUNCH("vit_ln_fwd");
+  return PL_OK;
+}
+
+extern "C" int pl_vit_ln_bwd_bf16(const float* dy, const float* dres, const float* x, const float* stats, int64_t T, int H,
+                                  int nnorm, const float* g1, const float* b1, const float* g2, float* dx, void* dx_bf16,
+                                  int64_t rows_pad, float* dgb, void* scratch, void* stream) {
+  if (!ln_shape_ok(T, H, nnorm) || nnorm < 1)
+    PL_FAIL(PL_ESHAPE, "pl_vit_ln_bwd_bf16: T=%lld H=%d nnorm=%d", (long long)T, H, nnorm);
+  if (!dy || !x || !stats || !g1 || !(dx || dx_bf16) || !dgb || !scratch || (nnorm == 2 && (!b1 || !g2)))
+    PL_FAIL(PL_EINVAL, "pl_vit_ln_bwd_bf16: null pointer");
+  if (!aligned16(dy) || !aligned16(x) || (dx && !aligned16(dx)) || (dres && !aligned16(dres)) || !aligned16(g1) ||
+      (b1 && !aligned16(b1)) || (g2 && !aligned16(g2)))
+    PL_FAIL(PL_EINVAL, "pl_vit_ln_bwd_bf16: pointers must be 16-byte aligned");
+  PL_TRY(carrier_check(dx_bf16, T, rows_pad, H, "pl_vit_ln_bwd_bf16"));
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t nch = chunks_of(T);
+  const size_t lds = sizeof(float) * (NT / kWave) * 2 * nnorm * H;
+  if (!dx_bf16) {
+    hipLaunchKernelGGL(vit_ln_bwd<false>, dim3((unsigned)nch), dim3(NT), lds, s, dy, dres, x, stats, (int)T, H, nnorm, g1, b1,
+                       g2, dx, static_cast<float*>(scratch), nullptr, (int)T);
+  } else {
+    hipLaunchKernelGGL(vit_ln_bwd<true>, dim3((unsigned)nch), dim3(NT), lds, s, dy, dres, x, stats, (int)T, H, nnorm, g1, b1,
+                       g2, dx, static_cast<float*>(scratch), static_cast<unsigned short*>(dx_bf16), (int)rows_pad);
+  }
+  PL_CHECK_LAUNCH("vit_ln_bwd");
+  return launch_reduce(static_cast<const float*>(scratch), nch, 2 * nnorm * H, dgb, s);
+}
+
+extern "C" int pl_vit_attn_fwd_bf16(const float* qkv, int64_t B, int seq, int heads, int dim_head, float scale, float* o,
+                                    void* o_bf16, int64_t rows_pad, float* lse, void* stream) {
+  if (!qkv || !(o || o_bf16) || !lse) PL_FAIL(PL_EINVAL, "pl_vit_attn_fwd_bf16: null pointer");
+  const size_t lds = attn_fwd_lds(seq, heads);
+  PL_TRY(attn_check(B, seq, heads, dim_head, lds, "pl_vit_attn_fwd_bf16"));
+  if (!aligned16(qkv)) PL_FAIL(PL_EINVAL, "pl_vit_attn_fwd_bf16: qkv must be 16-byte aligned");
+  PL_TRY(carrier_check(o_bf16, B * seq, rows_pad, (int64_t)heads * kDimHead, "pl_vit_attn_fwd_bf16"));
+  hipStream_t s = (hipStream_t)stream;
+  if (!o_bf16)
+    hipLaunchKernelGGL(vit_attn_fwd<false>, dim3((unsigned)B), dim3(NT), lds, s, qkv, seq, heads, scale, o, lse, nullptr, 0);
+  else
+    hipLaunchKernelGGL(vit_attn_fwd<true>, dim3((unsigned)B), dim3(NT), lds, s, qkv, seq, heads, scale, o, lse,
+                       static_cast<unsigned short*>(o_bf16), (int)rows_pad);
+  PL_CHECK_LAUNCH("vit_attn_fwd");
+  return PL_OK;
+}
+
+extern "C" int pl_vit_attn_bwd_bf16(const float* qkv, const float* lse, const float* dout, int64_t B, int seq, int heads,
+                                    int dim_head, float scale, float* dqkv, void* dqkv_bf16, int64_t rows_pad, void* stream) {
+  if (!qkv || !lse || !dout || !(dqkv || dqkv_bf16)) PL_FAIL(PL_EINVAL, "pl_vit_attn_bwd_bf16: null pointer");
+  const size_t lds = attn_bwd_lds(seq, heads);
+  PL_TRY(attn_check(B, seq, heads, dim_head, lds, "pl_vit_attn_bwd_bf16"));
+  if (!aligned16(qkv) || !aligned16(dout)) PL_FAIL(PL_EINVAL, "pl_vit_attn_bwd_bf16: qkv / dout must be 16-byte aligned");
+  PL_TRY(carrier_check(dqkv_bf16, B * seq, rows_pad, 3 * (int64_t)heads * kDimHead, "pl_vit_attn_bwd_bf16"));
+  hipStream_t s = (hipStream_t)stream;
+  if (!dqkv_bf16)
+    hipLaunchKernelGGL(vit_attn_bwd<false>, dim3((unsigned)B), dim3(NT), lds, s, qkv, lse, dout, seq, heads, scale, dqkv,
+                       nullptr, 0);
+  else
+    hipLaunchKernelGGL(vit_attn_bwd<true>, dim3((unsigned)B), dim3(NT), lds, s, qkv, lse, dout, seq, heads, scale, dqkv,
+                       static_cast<unsigned short*>(dqkv_bf16), (int)rows_pad);
+  PL_CHECK_LAUNCH("vit_attn_bwd");
+  return PL_OK;
+}
+
+static int rows_cols_ok(int64_t rows, int64_t cols) {
+  return rows > 0 && cols > 0 && cols % 4 == 0 && rows <= INT32_MAX / 1024 && rows * cols <= ((int64_t)1 << 40);
+}
+
+extern "C" int pl_vit_gelu_fwd_bf16(const float* u, int64_t rows, int64_t cols, int64_t rows_pad, float* y, void* y_bf16,
+                                    void* stream) {
+  if (!u || !(y || y_bf16)) PL_FAIL(PL_EINVAL, "pl_vit_gelu_fwd_bf16: null pointer");
+  if (!rows_cols_ok(rows, cols)) PL_FAIL(PL_ESHAPE, "pl_vit_gelu_fwd_bf16: rows=%lld cols=%lld", (long long)rows, (long long)cols);
+  PL_TRY(carrier_check(y_bf16, rows, rows_pad, cols, "pl_vit_gelu_fwd_bf16"));
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t n = rows * cols, n_pad = y_bf16 ? rows_pad * cols : n;
+  if (!y_bf16)
+    hipLaunchKernelGGL(vit_gelu_fwd<false>, dim3(grid_stride_blocks(n)), dim3(NT), 0, s, u, n, y, nullptr, n);
+  else
+    hipLaunchKernelGGL(vit_gelu_fwd<true>, dim3(grid_stride_blocks(n_pad)), dim3(NT), 0, s, u, n, y,
+                       static_cast<unsigned short*>(y_bf16), n_pad);
+  PL_CHECK_LAUNCH("vit_gelu_fwd");
+  return PL_OK;
+}
+
+extern "C" int pl_vit_gelu_bwd_bf16(const float* u, const float* dy, int64_t rows, int64_t cols, int64_t rows_pad, float* du,
+                                    void* du_bf16, void* stream) {
+  if (!u || !dy || !(du || du_bf16)) PL_FAIL(PL_EINVAL, "pl_vit_gelu_bwd_bf16: null pointer");
+  if (!rows_cols_ok(rows, cols)) PL_FAIL(PL_ESHAPE, "pl_vit_gelu_bwd_bf16: rows=%lld cols=%lld", (long long)rows, (long long)cols);
+  PL_TRY(carrier_check(du_bf16, rows, rows_pad, cols, "pl_vit_gelu_bwd_bf16"));
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t n = rows * cols, n_pad = du_bf16 ? rows_pad * cols : n;
+  if (!du_bf16)
+    hipLaunchKernelGGL(vit_gelu_bwd<false>, dim3(grid_stride_blocks(n)), dim3(NT), 0, s, u, dy, n, du, nullptr, n);
+  else
+    hipLaunchKernelGGL(vit_gelu_bwd<true>, dim3(grid_stride_blocks(n_pad)), dim3(NT), 0, s, u, dy, n, du,
+                       static_cast<unsigned short*>(du_bf16), n_pad);
+  PL_CHECK_LAUNCH("vit_gelu_bwd");
+  return PL_OK;
+}
+
+extern "C" int pl_vit_bf16_pack(const float* x, int64_t rows, int64_t cols, int64_t rows_pad, void* out, void* stream) {
+  if (!x || !out) PL_FAIL(PL_EINVAL, "pl_vit_bf16_pack: null pointer");
+  if (!rows_cols_ok(rows, cols)) PL_FAIL(PL_ESHAPE, "pl_vit_bf16_pack: rows=%lld cols=%lld", (long long)rows, (long long)cols);
+  PL_TRY(carrier_check(out, rows, rows_pad, cols, "pl_vit_bf16_pack"));
+  if (!aligned16(x)) PL_FAIL(PL_EINVAL, "pl_vit_bf16_pack: x must be 16-byte aligned");
+  hipLaunchKernelGGL(vit_bf16_pack, dim3(grid_stride_blocks(rows_pad * cols / 4)), dim3(NT), 0, (hipStream_t)stream, x,
+                     rows * cols, rows_pad * cols, static_cast<unsigned short*>(out));
+  PL_CHECK_LAUNCH("vit_bf16_pack");
   return PL_OK;
 }

@@ -17,6 +17,16 @@ compute_dtype
            scale; the weights with the static weight-plane scale, cached until the parameter's _version moves (an
            in-place change or a FlatAdam step).  The token head's Linears stay fp32 (the residual stream they read is not
            normalised).
+  "bf16p"  the same four block Linears with bf16 operands: one bf16 plane per operand, one MFMA per product, fp32
+           accumulate (pl_gemm_planes_raw, PL_BF16).  No scale and no max |x| pass: each operand is written once, as a
+           bf16 carrier [pad32(T)][cols] with zero padding rows, by the kernel that produces it (the LayerNorm forward /
+           backward, attention forward / backward, GELU forward / backward; the last block's output gradient, which the
+           head's fp32 GEMM produces, by pl_vit_bf16_pack), rounded once from the fp32 value the fp32 mode computes.  The
+           backward keeps those carriers instead of fp32 copies of a, o, n2 and GELU(h).  The weights are unscaled bf16
+           carriers of W and W^T, cached like the f16x3 planes.  Everything else is the fp32 mode's arithmetic: the
+           residual stream, the LayerNorm statistics, attention (scores, softmax, P V and their backward), the embedding,
+           the token head's Linears and every parameter-gradient reduction (biases, gamma / beta, embedding).  Accuracy
+           is bf16-storage grade, not fp32 grade: DESIGN.md 3b has the measured error against the fp64 twin.
 """
 import numpy as np
 import torch
@@ -25,7 +35,7 @@ from torch import nn
 from . import _lib, conv
 
 DIM_HEAD = 64
-_DTYPES = ("f16x3", "fp32")
+_DTYPES = ("f16x3", "fp32", "bf16p")
 
 
 def positional_embeddings(seq, d):
@@ -108,14 +118,17 @@ class MyViT(nn.Module):
         return ps
 
     def _wplanes(self, w):
-        """(planes of W [N][K], planes of W^T [K][N]) with the weight-plane scale; rebuilt after a FlatAdam step or any
-        in-place change of the parameter."""
-        key = (w._version, w.data_ptr())
+        """(planes of W [N][K], planes of W^T [K][N]) with the weight-plane scale ("bf16p": unscaled bf16 carriers);
+        rebuilt after a FlatAdam step or any in-place change of the parameter."""
+        key = (w._version, w.data_ptr(), self.compute_dtype)
         hit = self._wcache.get(id(w))
         if hit is not None and hit[0] == key:
             return hit[1]
         wd = w.detach()
-        planes = (conv._planes_of(wd, conv.WEIGHT_PLANE_SCALE), conv._planes_of(wd.t(), conv.WEIGHT_PLANE_SCALE))
+        if self.compute_dtype == "bf16p":
+            planes = (conv._planes_of(wd, 1.0, _lib.PL_BF16), conv._planes_of(wd.t(), 1.0, _lib.PL_BF16))
+        else:
+            planes = (conv._planes_of(wd, conv.WEIGHT_PLANE_SCALE), conv._planes_of(wd.t(), conv.WEIGHT_PLANE_SCALE))
         self._wcache[id(w)] = (key, planes)
         return planes
 
@@ -198,6 +211,105 @@ def _pgemm_dgrad(gp, wtp, K_in):
                                  1.0 / conv.WEIGHT_PLANE_SCALE, gp.scale[1:2])
 
 
+def _carrier(rows_pad, cols, dev):
+    """A bf16 carrier [rows_pad][cols]: the producing kernel writes every row, the padding rows as zeros."""
+    return torch.empty(rows_pad, cols, dtype=torch.bfloat16, device=dev)
+
+
+def _bgemm_fwd(ac, M, wc, N, bias=None):
+    """y [M][N] = a W^T (+ bias): a as a bf16 carrier [rows_pad][K], W [N][K] as a bf16 weight carrier."""
+    L, K = _lib.lib(), ac.shape[1]
+    C = torch.empty(M, N, device=ac.device)
+    splits = L.pl_gemm_planes_splits(M, N, K)
+    slabs = torch.empty(splits * M * N, device=C.device) if splits > 1 else None
+    _run("pl_gemm_planes_raw", 0, _lib.PL_BF16, ac.data_ptr(), ac.numel(), K, wc.data_ptr(), N * K, K, C.data_ptr(), M, N, K,
+         _ptr(bias if splits == 1 else None), 1.0, None, _ptr(slabs), None)
+    if bias is not None and splits > 1:
+        C.add_(bias)
+    return C
+
+
+def _bgemm_wgrad(gc, ac):
+    """dW [g cols][a cols] = g^T a over the carriers' (zero-padded) rows."""
+    return conv._gemm_planes_raw(2, gc, tuple(gc.shape), ac, tuple(ac.shape), gc.shape[1], ac.shape[1], gc.shape[0], 1.0,
+                                 mode=_lib.PL_BF16)
+
+
+def _bgemm_dgrad(gc, wtc, M):
+    """dx [M][K_in] = g W: g as a carrier [rows_pad][N], W^T [K_in][N] as a bf16 weight carrier (NT)."""
+    K_in, N = wtc.shape
+    return conv._gemm_planes_raw(0, gc, tuple(gc.shape), wtc, (K_in, N), M, K_in, N, 1.0, mode=_lib.PL_BF16)
+
+
+def _block_fwd_bf16p(model, x, add, blk, B, seq, T, Tp, eps):
+    """One block in "bf16p" mode: (xa, m, what the backward keeps).  x (+ add: the previous block's mlp output) is the
+    residual stream."""
+    (g1, b1, g2, b2, wqkv, wout, g3, b3, w0, b0, w2, b2m) = blk
+    H, heads, dev = model.hidden_d, model.n_heads, x.device
+    xb = torch.empty(T, H, device=dev) if add is not None else x
+    a_c = _carrier(Tp, H, dev)
+    st12 = torch.empty(4, T, device=dev)
+    _run("pl_vit_ln_fwd_bf16", x.data_ptr(), _ptr(add), T, H, 2, g1.data_ptr(), b1.data_ptr(), g2.data_ptr(), b2.data_ptr(),
+         eps, _ptr(xb if add is not None else None), None, a_c.data_ptr(), Tp, st12.data_ptr())
+    qkv = _bgemm_fwd(a_c, T, model._wplanes(wqkv)[0], 3 * H)
+    o_c = _carrier(Tp, H, dev)
+    lse = torch.empty(B, heads, seq, device=dev)
+    _run("pl_vit_attn_fwd_bf16", qkv.data_ptr(), B, seq, heads, DIM_HEAD, DIM_HEAD ** -0.5, None, o_c.data_ptr(), Tp,
+         lse.data_ptr())
+    u = _bgemm_fwd(o_c, T, model._wplanes(wout)[0], H)
+    xa = torch.empty(T, H, device=dev)
+    n2_c = _carrier(Tp, H, dev)
+    st3 = torch.empty(2, T, device=dev)
+    _run("pl_vit_ln_fwd_bf16", xb.data_ptr(), u.data_ptr(), T, H, 1, g3.data_ptr(), b3.data_ptr(), None, None, eps,
+         xa.data_ptr(), None, n2_c.data_ptr(), Tp, st3.data_ptr())
+    h = _bgemm_fwd(n2_c, T, model._wplanes(w0)[0], 4 * H, b0)
+    g_c = _carrier(Tp, 4 * H, dev)
+    _run("pl_vit_gelu_fwd_bf16", h.data_ptr(), T, 4 * H, Tp, None, g_c.data_ptr())
+    m = _bgemm_fwd(g_c, T, model._wplanes(w2)[0], H, b2m)
+    return xa, m, dict(xb=xb, st12=st12, a_c=a_c, qkv=qkv, lse=lse, o_c=o_c, xa=xa, st3=st3, n2_c=n2_c, h=h, g_c=g_c)
+
+
+def _block_bwd_bf16p(model, s, blk, grads, base, dx, dm_c, B, seq, T, Tp, lnscratch, want_carrier):
+    """The backward of one "bf16p" block: dx is the gradient of its output (fp32: the residual stream), dm_c its carrier.
+    Fills grads[base:base + 12]; returns (dx of the block input, its carrier when want_carrier)."""
+    (g1, b1, g2, b2, wqkv, wout, g3, b3, w0, b0, w2, b2m) = blk
+    H, heads, dev = model.hidden_d, model.n_heads, dx.device
+    # mlp: m = mlp.2(GELU(mlp.0(n2)))
+    grads[base + 10] = _bgemm_wgrad(dm_c, s["g_c"])
+    dg = _bgemm_dgrad(dm_c, model._wplanes(w2)[1], T)
+    grads[base + 11] = _colsum(dx)
+    dh_c = _carrier(Tp, 4 * H, dev)
+    _run("pl_vit_gelu_bwd_bf16", s["h"].data_ptr(), dg.data_ptr(), T, 4 * H, Tp, dg.data_ptr(), dh_c.data_ptr())
+    grads[base + 8] = _bgemm_wgrad(dh_c, s["n2_c"])
+    dn2 = _bgemm_dgrad(dh_c, model._wplanes(w0)[1], T)
+    grads[base + 9] = _colsum(dg)                           # (dg now holds dh in fp32)
+    del dg, dh_c
+    # norm2 with the residual: dxa = dx + LN3'(dn2)
+    dxa = torch.empty(T, H, device=dev)
+    dxa_c = _carrier(Tp, H, dev)
+    dgb3 = torch.empty(2 * H, device=dev)
+    _run("pl_vit_ln_bwd_bf16", dn2.data_ptr(), dx.data_ptr(), s["xa"].data_ptr(), s["st3"].data_ptr(), T, H, 1, g3.data_ptr(),
+         None, None, dxa.data_ptr(), dxa_c.data_ptr(), Tp, dgb3.data_ptr(), lnscratch.data_ptr())
+    grads[base + 6], grads[base + 7] = dgb3[:H], dgb3[H:]
+    # attention: u = to_out(o)
+    grads[base + 5] = _bgemm_wgrad(dxa_c, s["o_c"])
+    do = _bgemm_dgrad(dxa_c, model._wplanes(wout)[1], T)
+    dq_c = _carrier(Tp, 3 * H, dev)
+    _run("pl_vit_attn_bwd_bf16", s["qkv"].data_ptr(), s["lse"].data_ptr(), do.data_ptr(), B, seq, heads, DIM_HEAD,
+         DIM_HEAD ** -0.5, None, dq_c.data_ptr(), Tp)
+    grads[base + 4] = _bgemm_wgrad(dq_c, s["a_c"])
+    da = _bgemm_dgrad(dq_c, model._wplanes(wqkv)[1], T)
+    # norm1 -> mhsa.norm with the residual: dx = dxa + LN1'(LN2'(da))
+    dxb = torch.empty(T, H, device=dev)
+    dxb_c = _carrier(Tp, H, dev) if want_carrier else None
+    dgb12 = torch.empty(4 * H, device=dev)
+    _run("pl_vit_ln_bwd_bf16", da.data_ptr(), dxa.data_ptr(), s["xb"].data_ptr(), s["st12"].data_ptr(), T, H, 2,
+         g1.data_ptr(), b1.data_ptr(), g2.data_ptr(), dxb.data_ptr(), _ptr(dxb_c), Tp, dgb12.data_ptr(), lnscratch.data_ptr())
+    grads[base + 0], grads[base + 1] = dgb12[:H], dgb12[H:2 * H]
+    grads[base + 2], grads[base + 3] = dgb12[2 * H:3 * H], dgb12[3 * H:]
+    return dxb, dxb_c
+
+
 def _colsum(x):
     rows, cols = x.shape
     out = torch.empty(cols, device=x.device)
@@ -221,7 +333,7 @@ class _ViTFn(torch.autograd.Function):
     def forward(ctx, model, want, x2d, *ps):
         B, seq, in_d = x2d.shape
         H, heads, out_d = model.hidden_d, model.n_heads, model.out_d
-        T, dev, f16 = B * seq, x2d.device, model.compute_dtype == "f16x3"
+        T, dev, f16, bf = B * seq, x2d.device, model.compute_dtype == "f16x3", model.compute_dtype == "bf16p"
         Tp = _pad32(T)
         eps = 1e-5
         Wm, bm, pos = ps[0], ps[1], ps[2]
@@ -231,6 +343,11 @@ class _ViTFn(torch.autograd.Function):
             _run("pl_vit_embed_fwd", x2d.data_ptr(), T, in_d, seq, Wm.data_ptr(), bm.data_ptr(), pos.data_ptr(), H, x.data_ptr())
             add = None
             for bi in range(model.n_block):
+                if bf:
+                    x, add, s = _block_fwd_bf16p(model, x, add, ps[3 + 12 * bi: 15 + 12 * bi], B, seq, T, Tp, eps)
+                    if want:
+                        saved.append(s)
+                    continue
                 (g1, b1, g2, b2, wqkv, wout, g3, b3, w0, b0, w2, b2m) = ps[3 + 12 * bi: 15 + 12 * bi]
                 xb = torch.empty(T, H, device=dev) if add is not None else x
                 a = torch.empty(T, H, device=dev)
@@ -281,7 +398,7 @@ class _ViTFn(torch.autograd.Function):
             _run("pl_vit_head_fwd", z.data_ptr(), T, H // 2, wl.data_ptr(), bl.data_ptr(), out_d, y.data_ptr())
         if want:
             ctx.model, ctx.saved, ctx.x2d, ctx.xf, ctx.z, ctx.ps = model, saved, x2d, xf, z, ps
-            ctx.dims = (B, seq, in_d, T, Tp, f16)
+            ctx.dims = (B, seq, in_d, T, Tp, f16, bf)
             ctx.versions = tuple(p._version for p in ps)     # (a FlatAdam step bumps them too)
         return y
 
@@ -289,7 +406,7 @@ class _ViTFn(torch.autograd.Function):
     def backward(ctx, dy):
         model, saved, ps = ctx.model, ctx.saved, ctx.ps
         _check_versions(model, ps, ctx.versions)
-        B, seq, in_d, T, Tp, f16 = ctx.dims
+        B, seq, in_d, T, Tp, f16, bf = ctx.dims
         H, heads, out_d = model.hidden_d, model.n_heads, model.out_d
         dev = dy.device
         dy = dy.float().contiguous()
@@ -307,10 +424,17 @@ class _ViTFn(torch.autograd.Function):
             grads[-3] = _colsum(dz)
             dx = _gemm_f32(1, dz, wh, T, H, H // 2)              # d(block output) = d(x_final)
             lnscratch = torch.empty(max(L.pl_vit_ln_bwd_scratch_bytes(T, H, 2), 4), dtype=torch.uint8, device=dev)
+            if bf:                                              # the head's fp32 dx: the last block's output gradient
+                dm_c = _carrier(Tp, H, dev)
+                _run("pl_vit_bf16_pack", dx.data_ptr(), T, H, Tp, dm_c.data_ptr())
             for bi in reversed(range(model.n_block)):
-                (g1, b1, g2, b2, wqkv, wout, g3, b3, w0, b0, w2, b2m) = ps[3 + 12 * bi: 15 + 12 * bi]
                 s = saved[bi]
                 base = 3 + 12 * bi
+                if bf:
+                    dx, dm_c = _block_bwd_bf16p(model, s, ps[base: base + 12], grads, base, dx, dm_c, B, seq, T, Tp,
+                                                lnscratch, bi > 0)
+                    continue
+                (g1, b1, g2, b2, wqkv, wout, g3, b3, w0, b0, w2, b2m) = ps[3 + 12 * bi: 15 + 12 * bi]
                 # mlp: m = mlp.2(GELU(mlp.0(n2)));  dm = dx
                 if f16:
                     dmp = _Planes(dx, Tp, other=s["gp"])

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define PL_VERSION 110 /* 0.1.10: + pl_vit_* (the MyViT transformer lifter); 0.1.9: + pl_conv2d_planes_fwd_hw, pl_conv2d_planes_wgrad_hw (the stem on the planes GEMM); 0.1.8: + pl_lifter_train_step, pl_lifter_step_carries_adamw; 0.1.7: + pl_workspace_bitmap_format (small-batch layer kernels); 0.1.6: + pl_counter_add; 0.1.5: + pl_flip_pose_ex, pl_flip_w_nhwc (phase5 Flip branch); 0.1.4: + pl_planes_split_strided; 0.1.3: + pl_bn_join_bwd (0.1.2: operand-plane outputs of the BatchNorm / join kernels, pl_gemm_planes_raw) */
+#define PL_VERSION 111 /* 0.1.11: + pl_vit_*_bf16, pl_vit_bf16_pack (MyViT "bf16p": bf16 operand carriers written by their producers); 0.1.10: + pl_vit_* (the MyViT transformer lifter); 0.1.9: + pl_conv2d_planes_fwd_hw, pl_conv2d_planes_wgrad_hw (the stem on the planes GEMM); 0.1.8: + pl_lifter_train_step, pl_lifter_step_carries_adamw; 0.1.7: + pl_workspace_bitmap_format (small-batch layer kernels); 0.1.6: + pl_counter_add; 0.1.5: + pl_flip_pose_ex, pl_flip_w_nhwc (phase5 Flip branch); 0.1.4: + pl_planes_split_strided; 0.1.3: + pl_bn_join_bwd (0.1.2: operand-plane outputs of the BatchNorm / join kernels, pl_gemm_planes_raw) */
 
 typedef enum PLStatus {
   PL_OK = 0,
@@ -633,6 +633,32 @@ int pl_vit_head_bwd(const float* dy, const float* z, int64_t T, int K, const flo
 size_t pl_vit_planes_scratch_bytes(void);
 int pl_vit_planes_dyn(const float* x, int64_t rows, int64_t cols, int64_t rows_pad, const float* other_scale, float* scale,
                       void* planes, void* scratch, void* stream);
+/* MyViT "bf16p" mode: the producers of the block Linears' operands also write a bf16 CARRIER of their output -- row-major
+ * [rows_pad][cols] bf16 (cols: H, heads*64, 3*heads*64 or 4*H), rows_pad >= T, rows_pad % 32 == 0, the rows past T zero (the
+ * padded contraction of the TN weight gradients), 16-byte aligned: a PL_BF16 operand of pl_gemm_planes_raw.  Every carrier
+ * element is the fp32 value the plain entry point computes, rounded once to nearest even (a NaN stays a NaN).
+ * Arguments as the plain entry points; a NULL carrier runs exactly the plain entry point's kernel; with a carrier, the
+ * fp32 output (y, dx, o, dqkv, du) may be NULL (not written).
+ *   pl_vit_ln_fwd_bf16   : y_bf16 = carrier of y (nnorm >= 1)
+ *   pl_vit_ln_bwd_bf16   : dx_bf16 = carrier of dx
+ *   pl_vit_attn_fwd_bf16 : o_bf16 [rows_pad][heads*64], T = B * seq
+ *   pl_vit_attn_bwd_bf16 : dqkv_bf16 [rows_pad][3*heads*64]
+ *   pl_vit_gelu_*_bf16   : u, dy, y, du as [rows][cols] (cols % 4 == 0); y_bf16 / du_bf16 their carriers
+ *   pl_vit_bf16_pack     : out = carrier of x [rows][cols] (cols % 4 == 0, x 16-byte aligned) */
+int pl_vit_ln_fwd_bf16(const float* x, const float* add, int64_t T, int H, int nnorm, const float* g1, const float* b1,
+                       const float* g2, const float* b2, float eps, float* x_out, float* y, void* y_bf16, int64_t rows_pad,
+                       float* stats, void* stream);
+int pl_vit_ln_bwd_bf16(const float* dy, const float* dres, const float* x, const float* stats, int64_t T, int H, int nnorm,
+                       const float* g1, const float* b1, const float* g2, float* dx, void* dx_bf16, int64_t rows_pad,
+                       float* dgb, void* scratch, void* stream);
+int pl_vit_attn_fwd_bf16(const float* qkv, int64_t B, int seq, int heads, int dim_head, float scale, float* o, void* o_bf16,
+                         int64_t rows_pad, float* lse, void* stream);
+int pl_vit_attn_bwd_bf16(const float* qkv, const float* lse, const float* dout, int64_t B, int seq, int heads, int dim_head,
+                         float scale, float* dqkv, void* dqkv_bf16, int64_t rows_pad, void* stream);
+int pl_vit_gelu_fwd_bf16(const float* u, int64_t rows, int64_t cols, int64_t rows_pad, float* y, void* y_bf16, void* stream);
+int pl_vit_gelu_bwd_bf16(const float* u, const float* dy, int64_t rows, int64_t cols, int64_t rows_pad, float* du,
+                         void* du_bf16, void* stream);
+int pl_vit_bf16_pack(const float* x, int64_t rows, int64_t cols, int64_t rows_pad, void* out, void* stream);
 
 /* ---- measurement hook (bench.py; not part of the reference interface) ------------------ */
 /* While enabled (on = n > 0), every n-th GEMM launch (n = 1: every one) is bracketed by two HIP events

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""MyViT training step on one MI355X: ms/step and poses/s of pl.MyViT (f16x3, fp32) and of an equivalent stock-torch
+"""MyViT training step on one MI355X: ms/step and poses/s of pl.MyViT (f16x3, fp32, bf16p) and of an equivalent stock-torch
 module (eager fp32, eager bf16 autocast), timed the same way (HIP events around `steps` steps after `warmup`; MSE + AdamW
 step included).  Prints one JSON line.
 
@@ -77,7 +77,7 @@ def main():
         t = (0.2 * torch.randn(B, 17, 3, generator=g)).to(DEV)
         fwd, step_flops = flops(B)
         row = {"gflop_forward": fwd / 1e9, "gflop_step": step_flops / 1e9}
-        for mode in ("f16x3", "fp32"):
+        for mode in ("f16x3", "fp32", "bf16p"):
             torch.manual_seed(0)
             m = pl.MyViT(compute_dtype=mode).to(DEV).train()
             opt = pl.FlatAdam(m, lr=1e-4, weight_decay=0.01, decoupled_weight_decay=True)
@@ -99,6 +99,8 @@ def main():
             row[name] = {"ms": ms, "poses_per_s": B / ms * 1e3}
         row["f16x3_over_eager_fp32"] = row["f16x3"]["ms"] / row["eager_fp32"]["ms"]
         row["fp32_over_eager_fp32"] = row["fp32"]["ms"] / row["eager_fp32"]["ms"]
+        row["bf16p_over_eager_bf16_autocast"] = row["bf16p"]["ms"] / row["eager_bf16_autocast"]["ms"]
+        row["bf16p_over_f16x3"] = row["bf16p"]["ms"] / row["f16x3"]["ms"]
         res["runs"][str(B)] = row
     res["bound"] = ("GEMM share of peak against the fp32 MFMA peak; the non-GEMM kernels are HBM-bound "
                     "(per-kernel times: rocprofv3 --kernel-trace --stats, profiles/vit_*)")
