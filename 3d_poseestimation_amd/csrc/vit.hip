@@ -735,24 +735,54 @@ extern "C" int pl_vit_embed_bwd(const float* dx, const float* x2d, int64_t T, in
   return PL_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- the carrier kernels
+// LayerNorm, attention and GELU, forward and backward: ONE checked launcher per kernel.  It takes the optional bf16 carrier
+// of the kernel's output ([rows_pad][cols], rows past T zero; "bf16p") and the name of the entry point for its messages.
+// Both exported forms are calls of it: the plain form passes no carrier, the _bf16 form its own arguments.  Without a
+// carrier the <false> kernel runs and the fp32 output is required; with one it may be NULL.  Everything is checked before
+// any HIP call.
+static int carrier_check(const void* c, int64_t T, int64_t rows_pad, int64_t cols, const char* who) {
+  if (!c) return PL_OK;
+  if (rows_pad < T || rows_pad % 32 || rows_pad > INT32_MAX / 1024 || cols % 4 || rows_pad * cols > ((int64_t)1 << 40))
+    PL_FAIL(PL_ESHAPE, "%s: carrier rows_pad=%lld for T=%lld rows of %lld (rows_pad >= T, rows_pad %% 32 == 0, cols %% 4 == 0)",
+            who, (long long)rows_pad, (long long)T, (long long)cols);
+  if (!aligned16(c)) PL_FAIL(PL_EINVAL, "%s: the bf16 carrier must be 16-byte aligned", who);
+  return PL_OK;
+}
+
 static int ln_shape_ok(int64_t T, int H, int nnorm) {
   return T > 0 && T <= INT32_MAX / 1024 && H > 0 && H % 4 == 0 && H <= 4 * kLnMaxV * kWave && nnorm >= 0 && nnorm <= 2;
+}
+
+static int ln_fwd(const char* who, const float* x, const float* add, int64_t T, int H, int nnorm, const float* g1,
+                  const float* b1, const float* g2, const float* b2, float eps, float* x_out, float* y, void* y_bf16,
+                  int64_t rows_pad, float* stats, void* stream) {
+  if (!ln_shape_ok(T, H, nnorm)) PL_FAIL(PL_ESHAPE, "%s: T=%lld H=%d nnorm=%d", who, (long long)T, H, nnorm);
+  if (!x || (add && !x_out) || (nnorm >= 1 && (!g1 || !b1 || !(y || y_bf16) || !stats)) || (nnorm == 2 && (!g2 || !b2)) ||
+      (nnorm == 0 && (!add || y_bf16)))
+    PL_FAIL(PL_EINVAL, "%s: null pointer", who);
+  if (!aligned16(x) || (add && (!aligned16(add) || !aligned16(x_out))) || (y && !aligned16(y)) ||
+      (g1 && !aligned16(g1)) || (b1 && !aligned16(b1)) || (g2 && !aligned16(g2)) || (b2 && !aligned16(b2)))
+    PL_FAIL(PL_EINVAL, "%s: pointers must be 16-byte aligned", who);
+  PL_TRY(carrier_check(y_bf16, T, rows_pad, H, who));
+  const int64_t rows = y_bf16 ? rows_pad : T;      // (the carrier kernel also zeroes the padding rows)
+  hipLaunchKernelGGL(y_bf16 ? vit_ln_fwd<true> : vit_ln_fwd<false>, dim3(blocks_for(rows, NT / kWave)), dim3(NT), 0,
+                     (hipStream_t)stream, x, add, (int)T, H, nnorm, g1, b1, g2, b2, eps, x_out, y, stats,
+                     static_cast<unsigned short*>(y_bf16), (int)rows);
+  PL_CHECK_LAUNCH("vit_ln_fwd");
+  return PL_OK;
 }
 
 extern "C" int pl_vit_ln_fwd(const float* x, const float* add, int64_t T, int H, int nnorm, const float* g1,
                              const float* b1, const float* g2, const float* b2, float eps, float* x_out, float* y,
                              float* stats, void* stream) {
-  if (!ln_shape_ok(T, H, nnorm)) PL_FAIL(PL_ESHAPE, "pl_vit_ln_fwd: T=%lld H=%d nnorm=%d", (long long)T, H, nnorm);
-  if (!x || (add && !x_out) || (nnorm >= 1 && (!g1 || !b1 || !y || !stats)) || (nnorm == 2 && (!g2 || !b2)) ||
-      (nnorm == 0 && !add))
-    PL_FAIL(PL_EINVAL, "pl_vit_ln_fwd: null pointer");
-  if (!aligned16(x) || (add && (!aligned16(add) || !aligned16(x_out))) || (y && !aligned16(y)) ||
-      (g1 && !aligned16(g1)) || (b1 && !aligned16(b1)) || (g2 && !aligned16(g2)) || (b2 && !aligned16(b2)))
-    PL_FAIL(PL_EINVAL, "pl_vit_ln_fwd: pointers must be 16-byte aligned");
-  hipLaunchKernelGGL(vit_ln_fwd<false>, dim3(blocks_for(T, NT / kWave)), dim3(NT), 0, (hipStream_t)stream, x, add, (int)T, H,
-                     nnorm, g1, b1, g2, b2, eps, x_out, y, stats, nullptr, (int)T);
-  PL_CHECK_LAUNCH("vit_ln_fwd");
-  return PL_OK;
+  return ln_fwd("pl_vit_ln_fwd", x, add, T, H, nnorm, g1, b1, g2, b2, eps, x_out, y, nullptr, 0, stats, stream);
+}
+
+extern "C" int pl_vit_ln_fwd_bf16(const float* x, const float* add, int64_t T, int H, int nnorm, const float* g1,
+                                  const float* b1, const float* g2, const float* b2, float eps, float* x_out, float* y,
+                                  void* y_bf16, int64_t rows_pad, float* stats, void* stream) {
+  return ln_fwd("pl_vit_ln_fwd_bf16", x, add, T, H, nnorm, g1, b1, g2, b2, eps, x_out, y, y_bf16, rows_pad, stats, stream);
 }
 
 extern "C" size_t pl_vit_ln_bwd_scratch_bytes(int64_t T, int H, int nnorm) {
@@ -760,22 +790,36 @@ extern "C" size_t pl_vit_ln_bwd_scratch_bytes(int64_t T, int H, int nnorm) {
   return sizeof(float) * (size_t)chunks_of(T) * (size_t)(2 * nnorm * H);
 }
 
+static int ln_bwd(const char* who, const float* dy, const float* dres, const float* x, const float* stats, int64_t T, int H,
+                  int nnorm, const float* g1, const float* b1, const float* g2, float* dx, void* dx_bf16, int64_t rows_pad,
+                  float* dgb, void* scratch, void* stream) {
+  if (!ln_shape_ok(T, H, nnorm) || nnorm < 1) PL_FAIL(PL_ESHAPE, "%s: T=%lld H=%d nnorm=%d", who, (long long)T, H, nnorm);
+  if (!dy || !x || !stats || !g1 || !(dx || dx_bf16) || !dgb || !scratch || (nnorm == 2 && (!b1 || !g2)))
+    PL_FAIL(PL_EINVAL, "%s: null pointer", who);
+  if (!aligned16(dy) || !aligned16(x) || (dx && !aligned16(dx)) || (dres && !aligned16(dres)) || !aligned16(g1) ||
+      (b1 && !aligned16(b1)) || (g2 && !aligned16(g2)))
+    PL_FAIL(PL_EINVAL, "%s: pointers must be 16-byte aligned", who);
+  PL_TRY(carrier_check(dx_bf16, T, rows_pad, H, who));
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t nch = chunks_of(T);
+  hipLaunchKernelGGL(dx_bf16 ? vit_ln_bwd<true> : vit_ln_bwd<false>, dim3((unsigned)nch), dim3(NT),
+                     sizeof(float) * (NT / kWave) * 2 * nnorm * H, s, dy, dres, x, stats, (int)T, H, nnorm, g1, b1, g2, dx,
+                     static_cast<float*>(scratch), static_cast<unsigned short*>(dx_bf16), (int)(dx_bf16 ? rows_pad : T));
+  PL_CHECK_LAUNCH("vit_ln_bwd");
+  return launch_reduce(static_cast<const float*>(scratch), nch, 2 * nnorm * H, dgb, s);
+}
+
 extern "C" int pl_vit_ln_bwd(const float* dy, const float* dres, const float* x, const float* stats, int64_t T, int H,
                              int nnorm, const float* g1, const float* b1, const float* g2, float* dx, float* dgb,
                              void* scratch, void* stream) {
-  if (!ln_shape_ok(T, H, nnorm) || nnorm < 1)
-    PL_FAIL(PL_ESHAPE, "pl_vit_ln_bwd: T=%lld H=%d nnorm=%d", (long long)T, H, nnorm);
-  if (!dy || !x || !stats || !g1 || !dx || !dgb || !scratch || (nnorm == 2 && (!b1 || !g2)))
-    PL_FAIL(PL_EINVAL, "pl_vit_ln_bwd: null pointer");
-  if (!aligned16(dy) || !aligned16(x) || !aligned16(dx) || (dres && !aligned16(dres)) || !aligned16(g1) ||
-      (b1 && !aligned16(b1)) || (g2 && !aligned16(g2)))
-    PL_FAIL(PL_EINVAL, "pl_vit_ln_bwd: pointers must be 16-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t nch = chunks_of(T);
-  hipLaunchKernelGGL(vit_ln_bwd<false>, dim3((unsigned)nch), dim3(NT), sizeof(float) * (NT / kWave) * 2 * nnorm * H, s, dy, dres, x, stats, (int)T, H, nnorm, g1, b1, g2, dx,
-                     static_cast<float*>(scratch), nullptr, (int)T);
-  PL_CHECK_LAUNCH("vit_ln_bwd");
-  return launch_reduce(static_cast<const float*>(scratch), nch, 2 * nnorm * H, dgb, s);
+  return ln_bwd("pl_vit_ln_bwd", dy, dres, x, stats, T, H, nnorm, g1, b1, g2, dx, nullptr, 0, dgb, scratch, stream);
+}
+
+extern "C" int pl_vit_ln_bwd_bf16(const float* dy, const float* dres, const float* x, const float* stats, int64_t T, int H,
+                                  int nnorm, const float* g1, const float* b1, const float* g2, float* dx, void* dx_bf16,
+                                  int64_t rows_pad, float* dgb, void* scratch, void* stream) {
+  return ln_bwd("pl_vit_ln_bwd_bf16", dy, dres, x, stats, T, H, nnorm, g1, b1, g2, dx, dx_bf16, rows_pad, dgb, scratch,
+                stream);
 }
 
 static int attn_check(int64_t B, int seq, int heads, int dim_head, size_t lds, const char* what) {
@@ -789,49 +833,110 @@ extern "C" int pl_vit_attn_supported(int seq, int heads, int dim_head) {
   return seq >= 1 && seq <= kMaxSeq && heads >= 1 && dim_head == kDimHead && attn_bwd_lds(seq, heads) <= kLdsMax;
 }
 
+static int attn_fwd(const char* who, const float* qkv, int64_t B, int seq, int heads, int dim_head, float scale, float* o,
+                    void* o_bf16, int64_t rows_pad, float* lse, void* stream) {
+  if (!qkv || !(o || o_bf16) || !lse) PL_FAIL(PL_EINVAL, "%s: null pointer", who);
+  const size_t lds = attn_fwd_lds(seq, heads);
+  PL_TRY(attn_check(B, seq, heads, dim_head, lds, who));
+  if (!aligned16(qkv)) PL_FAIL(PL_EINVAL, "%s: qkv must be 16-byte aligned", who);
+  PL_TRY(carrier_check(o_bf16, B * seq, rows_pad, (int64_t)heads * kDimHead, who));
+  hipLaunchKernelGGL(o_bf16 ? vit_attn_fwd<true> : vit_attn_fwd<false>, dim3((unsigned)B), dim3(NT), lds,
+                     (hipStream_t)stream, qkv, seq, heads, scale, o, lse, static_cast<unsigned short*>(o_bf16),
+                     (int)(o_bf16 ? rows_pad : 0));
+  PL_CHECK_LAUNCH("vit_attn_fwd");
+  return PL_OK;
+}
+
 extern "C" int pl_vit_attn_fwd(const float* qkv, int64_t B, int seq, int heads, int dim_head, float scale, float* o,
                                float* lse, void* stream) {
-  if (!qkv || !o || !lse) PL_FAIL(PL_EINVAL, "pl_vit_attn_fwd: null pointer");
-  const size_t lds = attn_fwd_lds(seq, heads);
-  PL_TRY(attn_check(B, seq, heads, dim_head, lds, "pl_vit_attn_fwd"));
-  if (!aligned16(qkv)) PL_FAIL(PL_EINVAL, "pl_vit_attn_fwd: qkv must be 16-byte aligned");
-  hipLaunchKernelGGL(vit_attn_fwd<false>, dim3((unsigned)B), dim3(NT), lds, (hipStream_t)stream, qkv, seq, heads, scale, o, lse,
-                     nullptr, 0);
-  PL_CHECK_LAUNCH("vit_attn_fwd");
+  return attn_fwd("pl_vit_attn_fwd", qkv, B, seq, heads, dim_head, scale, o, nullptr, 0, lse, stream);
+}
+
+extern "C" int pl_vit_attn_fwd_bf16(const float* qkv, int64_t B, int seq, int heads, int dim_head, float scale, float* o,
+                                    void* o_bf16, int64_t rows_pad, float* lse, void* stream) {
+  return attn_fwd("pl_vit_attn_fwd_bf16", qkv, B, seq, heads, dim_head, scale, o, o_bf16, rows_pad, lse, stream);
+}
+
+static int attn_bwd(const char* who, const float* qkv, const float* lse, const float* dout, int64_t B, int seq, int heads,
+                    int dim_head, float scale, float* dqkv, void* dqkv_bf16, int64_t rows_pad, void* stream) {
+  if (!qkv || !lse || !dout || !(dqkv || dqkv_bf16)) PL_FAIL(PL_EINVAL, "%s: null pointer", who);
+  const size_t lds = attn_bwd_lds(seq, heads);
+  PL_TRY(attn_check(B, seq, heads, dim_head, lds, who));
+  if (!aligned16(qkv) || !aligned16(dout)) PL_FAIL(PL_EINVAL, "%s: qkv / dout must be 16-byte aligned", who);
+  PL_TRY(carrier_check(dqkv_bf16, B * seq, rows_pad, 3 * (int64_t)heads * kDimHead, who));
+  hipLaunchKernelGGL(dqkv_bf16 ? vit_attn_bwd<true> : vit_attn_bwd<false>, dim3((unsigned)B), dim3(NT), lds,
+                     (hipStream_t)stream, qkv, lse, dout, seq, heads, scale, dqkv, static_cast<unsigned short*>(dqkv_bf16),
+                     (int)(dqkv_bf16 ? rows_pad : 0));
+  PL_CHECK_LAUNCH("vit_attn_bwd");
   return PL_OK;
 }
 
 extern "C" int pl_vit_attn_bwd(const float* qkv, const float* lse, const float* dout, int64_t B, int seq, int heads,
                                int dim_head, float scale, float* dqkv, void* stream) {
-  if (!qkv || !lse || !dout || !dqkv) PL_FAIL(PL_EINVAL, "pl_vit_attn_bwd: null pointer");
-  const size_t lds = attn_bwd_lds(seq, heads);
-  PL_TRY(attn_check(B, seq, heads, dim_head, lds, "pl_vit_attn_bwd"));
-  if (!aligned16(qkv) || !aligned16(dout)) PL_FAIL(PL_EINVAL, "pl_vit_attn_bwd: qkv / dout must be 16-byte aligned");
-  hipLaunchKernelGGL(vit_attn_bwd<false>, dim3((unsigned)B), dim3(NT), lds, (hipStream_t)stream, qkv, lse, dout, seq, heads, scale,
-                     dqkv, nullptr, 0);
-  PL_CHECK_LAUNCH("vit_attn_bwd");
-  return PL_OK;
+  return attn_bwd("pl_vit_attn_bwd", qkv, lse, dout, B, seq, heads, dim_head, scale, dqkv, nullptr, 0, stream);
+}
+
+extern "C" int pl_vit_attn_bwd_bf16(const float* qkv, const float* lse, const float* dout, int64_t B, int seq, int heads,
+                                    int dim_head, float scale, float* dqkv, void* dqkv_bf16, int64_t rows_pad, void* stream) {
+  return attn_bwd("pl_vit_attn_bwd_bf16", qkv, lse, dout, B, seq, heads, dim_head, scale, dqkv, dqkv_bf16, rows_pad, stream);
 }
 
 static unsigned grid_stride_blocks(int64_t n) {
   return (unsigned)std::min<int64_t>(std::max<int64_t>(1, (n + NT - 1) / NT), 8192);
 }
 
-extern "C" int pl_vit_gelu_fwd(const float* u, int64_t n, float* y, void* stream) {
-  if (!u || !y) PL_FAIL(PL_EINVAL, "pl_vit_gelu_fwd: null pointer");
-  if (n <= 0) PL_FAIL(PL_ESHAPE, "pl_vit_gelu_fwd: n=%lld", (long long)n);
-  hipLaunchKernelGGL(vit_gelu_fwd<false>, dim3(grid_stride_blocks(n)), dim3(NT), 0, (hipStream_t)stream, u, n, y, nullptr, n);
+static int rows_cols_ok(int64_t rows, int64_t cols) {
+  return rows > 0 && cols > 0 && cols % 4 == 0 && rows <= INT32_MAX / 1024 && rows * cols <= ((int64_t)1 << 40);
+}
+
+// GELU is elementwise.  The plain forms take a count (plain: `rows` elements, any n > 0), the _bf16 forms [rows][cols]
+// with cols % 4 == 0, which a carrier needs.
+static int gelu_shape(const char* who, int64_t rows, int64_t cols, bool plain) {
+  if (plain && rows <= 0) PL_FAIL(PL_ESHAPE, "%s: n=%lld", who, (long long)rows);
+  if (!plain && !rows_cols_ok(rows, cols)) PL_FAIL(PL_ESHAPE, "%s: rows=%lld cols=%lld", who, (long long)rows, (long long)cols);
+  return PL_OK;
+}
+
+static int gelu_fwd(const char* who, bool plain, const float* u, int64_t rows, int64_t cols, int64_t rows_pad, float* y,
+                    void* y_bf16, void* stream) {
+  if (!u || !(y || y_bf16)) PL_FAIL(PL_EINVAL, "%s: null pointer", who);
+  PL_TRY(gelu_shape(who, rows, cols, plain));
+  PL_TRY(carrier_check(y_bf16, rows, rows_pad, cols, who));
+  const int64_t n = plain ? rows : rows * cols, n_pad = y_bf16 ? rows_pad * cols : n;
+  hipLaunchKernelGGL(y_bf16 ? vit_gelu_fwd<true> : vit_gelu_fwd<false>, dim3(grid_stride_blocks(n_pad)), dim3(NT), 0,
+                     (hipStream_t)stream, u, n, y, static_cast<unsigned short*>(y_bf16), n_pad);
   PL_CHECK_LAUNCH("vit_gelu_fwd");
   return PL_OK;
 }
 
-extern "C" int pl_vit_gelu_bwd(const float* u, const float* dy, int64_t n, float* du, void* stream) {
-  if (!u || !dy || !du) PL_FAIL(PL_EINVAL, "pl_vit_gelu_bwd: null pointer");
-  if (n <= 0) PL_FAIL(PL_ESHAPE, "pl_vit_gelu_bwd: n=%lld", (long long)n);
-  hipLaunchKernelGGL(vit_gelu_bwd<false>, dim3(grid_stride_blocks(n)), dim3(NT), 0, (hipStream_t)stream, u, dy, n, du, nullptr,
-                     n);
+extern "C" int pl_vit_gelu_fwd(const float* u, int64_t n, float* y, void* stream) {
+  return gelu_fwd("pl_vit_gelu_fwd", true, u, n, 0, 0, y, nullptr, stream);
+}
+
+extern "C" int pl_vit_gelu_fwd_bf16(const float* u, int64_t rows, int64_t cols, int64_t rows_pad, float* y, void* y_bf16,
+                                    void* stream) {
+  return gelu_fwd("pl_vit_gelu_fwd_bf16", false, u, rows, cols, rows_pad, y, y_bf16, stream);
+}
+
+static int gelu_bwd(const char* who, bool plain, const float* u, const float* dy, int64_t rows, int64_t cols,
+                    int64_t rows_pad, float* du, void* du_bf16, void* stream) {
+  if (!u || !dy || !(du || du_bf16)) PL_FAIL(PL_EINVAL, "%s: null pointer", who);
+  PL_TRY(gelu_shape(who, rows, cols, plain));
+  PL_TRY(carrier_check(du_bf16, rows, rows_pad, cols, who));
+  const int64_t n = plain ? rows : rows * cols, n_pad = du_bf16 ? rows_pad * cols : n;
+  hipLaunchKernelGGL(du_bf16 ? vit_gelu_bwd<true> : vit_gelu_bwd<false>, dim3(grid_stride_blocks(n_pad)), dim3(NT), 0,
+                     (hipStream_t)stream, u, dy, n, du, static_cast<unsigned short*>(du_bf16), n_pad);
   PL_CHECK_LAUNCH("vit_gelu_bwd");
   return PL_OK;
+}
+
+extern "C" int pl_vit_gelu_bwd(const float* u, const float* dy, int64_t n, float* du, void* stream) {
+  return gelu_bwd("pl_vit_gelu_bwd", true, u, dy, n, 0, 0, du, nullptr, stream);
+}
+
+extern "C" int pl_vit_gelu_bwd_bf16(const float* u, const float* dy, int64_t rows, int64_t cols, int64_t rows_pad, float* du,
+                                    void* du_bf16, void* stream) {
+  return gelu_bwd("pl_vit_gelu_bwd_bf16", false, u, dy, rows, cols, rows_pad, du, du_bf16, stream);
 }
 
 static int head_shape_ok(int64_t T, int K, int out_d) {
@@ -883,137 +988,6 @@ extern "C" int pl_vit_planes_dyn(const float* x, int64_t rows, int64_t cols, int
   hipLaunchKernelGGL(vit_split, dim3(grid_stride_blocks(rows_pad * cols / 4)), dim3(NT), 0, s, x, rows, cols, rows_pad,
                      static_cast<const float*>(scratch), nb, other_scale, scale, static_cast<unsigned short*>(planes));
   PL_CHECK_LAUNCH("vit_split");
-  return PL_OK;
-}
-
-// ---------------------------------------------------------------------------------------------- "bf16p" carriers
-// The same kernels with the bf16 carrier of their output ([rows_pad][cols], rows past T zero).  A NULL carrier runs the
-// fp32 kernel; with a carrier the fp32 output may be NULL.  Everything is checked before any HIP call.
-static int carrier_check(const void* c, int64_t T, int64_t rows_pad, int64_t cols, const char* who) {
-  if (!c) return PL_OK;
-  if (rows_pad < T || rows_pad % 32 || rows_pad > INT32_MAX / 1024 || cols % 4 || rows_pad * cols > ((int64_t)1 << 40))
-    PL_FAIL(PL_ESHAPE, "%s: carrier rows_pad=%lld for T=%lld rows of %lld (rows_pad >= T, rows_pad %% 32 == 0, cols %% 4 == 0)",
-            who, (long long)rows_pad, (long long)T, (long long)cols);
-  if (!aligned16(c)) PL_FAIL(PL_EINVAL, "%s: the bf16 carrier must be 16-byte aligned", who);
-  return PL_OK;
-}
-
-extern "C" int pl_vit_ln_fwd_bf16(const float* x, const float* add, int64_t T, int H, int nnorm, const float* g1,
-                                  const float* b1, const float* g2, const float* b2, float eps, float* x_out, float* y,
-                                  void* y_bf16, int64_t rows_pad, float* stats, void* stream) {
-  if (!ln_shape_ok(T, H, nnorm)) PL_FAIL(PL_ESHAPE, "pl_vit_ln_fwd_bf16: T=%lld H=%d nnorm=%d", (long long)T, H, nnorm);
-  if (!x || (add && !x_out) || (nnorm >= 1 && (!g1 || !b1 || !(y || y_bf16) || !stats)) || (nnorm == 2 && (!g2 || !b2)) ||
-      (nnorm == 0 && (!add || y_bf16)))
-    PL_FAIL(PL_EINVAL, "pl_vit_ln_fwd_bf16: null pointer");
-  if (!aligned16(x) || (add && (!aligned16(add) || !aligned16(x_out))) || (y && !aligned16(y)) ||
-      (g1 && !aligned16(g1)) || (b1 && !aligned16(b1)) || (g2 && !aligned16(g2)) || (b2 && !aligned16(b2)))
-    PL_FAIL(PL_EINVAL, "pl_vit_ln_fwd_bf16: pointers must be 16-byte aligned");
-  PL_TRY(carrier_check(y_bf16, T, rows_pad, H, "pl_vit_ln_fwd_bf16"));
-  hipStream_t s = (hipStream_t)stream;
-  if (!y_bf16) {
-    hipLaunchKernelGGL(vit_ln_fwd<false>, dim3(blocks_for(T, NT / kWave)), dim3(NT), 0, s, x, add, (int)T, H, nnorm, g1, b1,
-                       g2, b2, eps, x_out, y, stats, nullptr, (int)T);
-  } else {
-    hipLaunchKernelGGL(vit_ln_fwd<true>, dim3(blocks_for(rows_pad, NT / kWave)), dim3(NT), 0, s, x, add, (int)T, H, nnorm, g1,
-                       b1, g2, b2, eps, x_out, y, stats, static_cast<unsigned short*>(y_bf16), (int)rows_pad);
-  }
-  PL_CHECK_LAUNCH("vit_ln_fwd");
-  return PL_OK;
-}
-
-extern "C" int pl_vit_ln_bwd_bf16(const float* dy, const float* dres, const float* x, const float* stats, int64_t T, int H,
-                                  int nnorm, const float* g1, const float* b1, const float* g2, float* dx, void* dx_bf16,
-                                  int64_t rows_pad, float* dgb, void* scratch, void* stream) {
-  if (!ln_shape_ok(T, H, nnorm) || nnorm < 1)
-    PL_FAIL(PL_ESHAPE, "pl_vit_ln_bwd_bf16: T=%lld H=%d nnorm=%d", (long long)T, H, nnorm);
-  if (!dy || !x || !stats || !g1 || !(dx || dx_bf16) || !dgb || !scratch || (nnorm == 2 && (!b1 || !g2)))
-    PL_FAIL(PL_EINVAL, "pl_vit_ln_bwd_bf16: null pointer");
-  if (!aligned16(dy) || !aligned16(x) || (dx && !aligned16(dx)) || (dres && !aligned16(dres)) || !aligned16(g1) ||
-      (b1 && !aligned16(b1)) || (g2 && !aligned16(g2)))
-    PL_FAIL(PL_EINVAL, "pl_vit_ln_bwd_bf16: pointers must be 16-byte aligned");
-  PL_TRY(carrier_check(dx_bf16, T, rows_pad, H, "pl_vit_ln_bwd_bf16"));
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t nch = chunks_of(T);
-  const size_t lds = sizeof(float) * (NT / kWave) * 2 * nnorm * H;
-  if (!dx_bf16) {
-    hipLaunchKernelGGL(vit_ln_bwd<false>, dim3((unsigned)nch), dim3(NT), lds, s, dy, dres, x, stats, (int)T, H, nnorm, g1, b1,
-                       g2, dx, static_cast<float*>(scratch), nullptr, (int)T);
-  } else {
-    hipLaunchKernelGGL(vit_ln_bwd<true>, dim3((unsigned)nch), dim3(NT), lds, s, dy, dres, x, stats, (int)T, H, nnorm, g1, b1,
-                       g2, dx, static_cast<float*>(scratch), static_cast<unsigned short*>(dx_bf16), (int)rows_pad);
-  }
-  PL_CHECK_LAUNCH("vit_ln_bwd");
-  return launch_reduce(static_cast<const float*>(scratch), nch, 2 * nnorm * H, dgb, s);
-}
-
-extern "C" int pl_vit_attn_fwd_bf16(const float* qkv, int64_t B, int seq, int heads, int dim_head, float scale, float* o,
-                                    void* o_bf16, int64_t rows_pad, float* lse, void* stream) {
-  if (!qkv || !(o || o_bf16) || !lse) PL_FAIL(PL_EINVAL, "pl_vit_attn_fwd_bf16: null pointer");
-  const size_t lds = attn_fwd_lds(seq, heads);
-  PL_TRY(attn_check(B, seq, heads, dim_head, lds, "pl_vit_attn_fwd_bf16"));
-  if (!aligned16(qkv)) PL_FAIL(PL_EINVAL, "pl_vit_attn_fwd_bf16: qkv must be 16-byte aligned");
-  PL_TRY(carrier_check(o_bf16, B * seq, rows_pad, (int64_t)heads * kDimHead, "pl_vit_attn_fwd_bf16"));
-  hipStream_t s = (hipStream_t)stream;
-  if (!o_bf16)
-    hipLaunchKernelGGL(vit_attn_fwd<false>, dim3((unsigned)B), dim3(NT), lds, s, qkv, seq, heads, scale, o, lse, nullptr, 0);
-  else
-    hipLaunchKernelGGL(vit_attn_fwd<true>, dim3((unsigned)B), dim3(NT), lds, s, qkv, seq, heads, scale, o, lse,
-                       static_cast<unsigned short*>(o_bf16), (int)rows_pad);
-  PL_CHECK_LAUNCH("vit_attn_fwd");
-  return PL_OK;
-}
-
-extern "C" int pl_vit_attn_bwd_bf16(const float* qkv, const float* lse, const float* dout, int64_t B, int seq, int heads,
-                                    int dim_head, float scale, float* dqkv, void* dqkv_bf16, int64_t rows_pad, void* stream) {
-  if (!qkv || !lse || !dout || !(dqkv || dqkv_bf16)) PL_FAIL(PL_EINVAL, "pl_vit_attn_bwd_bf16: null pointer");
-  const size_t lds = attn_bwd_lds(seq, heads);
-  PL_TRY(attn_check(B, seq, heads, dim_head, lds, "pl_vit_attn_bwd_bf16"));
-  if (!aligned16(qkv) || !aligned16(dout)) PL_FAIL(PL_EINVAL, "pl_vit_attn_bwd_bf16: qkv / dout must be 16-byte aligned");
-  PL_TRY(carrier_check(dqkv_bf16, B * seq, rows_pad, 3 * (int64_t)heads * kDimHead, "pl_vit_attn_bwd_bf16"));
-  hipStream_t s = (hipStream_t)stream;
-  if (!dqkv_bf16)
-    hipLaunchKernelGGL(vit_attn_bwd<false>, dim3((unsigned)B), dim3(NT), lds, s, qkv, lse, dout, seq, heads, scale, dqkv,
-                       nullptr, 0);
-  else
-    hipLaunchKernelGGL(vit_attn_bwd<true>, dim3((unsigned)B), dim3(NT), lds, s, qkv, lse, dout, seq, heads, scale, dqkv,
-                       static_cast<unsigned short*>(dqkv_bf16), (int)rows_pad);
-  PL_CHECK_LAUNCH("vit_attn_bwd");
-  return PL_OK;
-}
-
-static int rows_cols_ok(int64_t rows, int64_t cols) {
-  return rows > 0 && cols > 0 && cols % 4 == 0 && rows <= INT32_MAX / 1024 && rows * cols <= ((int64_t)1 << 40);
-}
-
-extern "C" int pl_vit_gelu_fwd_bf16(const float* u, int64_t rows, int64_t cols, int64_t rows_pad, float* y, void* y_bf16,
-                                    void* stream) {
-  if (!u || !(y || y_bf16)) PL_FAIL(PL_EINVAL, "pl_vit_gelu_fwd_bf16: null pointer");
-  if (!rows_cols_ok(rows, cols)) PL_FAIL(PL_ESHAPE, "pl_vit_gelu_fwd_bf16: rows=%lld cols=%lld", (long long)rows, (long long)cols);
-  PL_TRY(carrier_check(y_bf16, rows, rows_pad, cols, "pl_vit_gelu_fwd_bf16"));
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t n = rows * cols, n_pad = y_bf16 ? rows_pad * cols : n;
-  if (!y_bf16)
-    hipLaunchKernelGGL(vit_gelu_fwd<false>, dim3(grid_stride_blocks(n)), dim3(NT), 0, s, u, n, y, nullptr, n);
-  else
-    hipLaunchKernelGGL(vit_gelu_fwd<true>, dim3(grid_stride_blocks(n_pad)), dim3(NT), 0, s, u, n, y,
-                       static_cast<unsigned short*>(y_bf16), n_pad);
-  PL_CHECK_LAUNCH("vit_gelu_fwd");
-  return PL_OK;
-}
-
-extern "C" int pl_vit_gelu_bwd_bf16(const float* u, const float* dy, int64_t rows, int64_t cols, int64_t rows_pad, float* du,
-                                    void* du_bf16, void* stream) {
-  if (!u || !dy || !(du || du_bf16)) PL_FAIL(PL_EINVAL, "pl_vit_gelu_bwd_bf16: null pointer");
-  if (!rows_cols_ok(rows, cols)) PL_FAIL(PL_ESHAPE, "pl_vit_gelu_bwd_bf16: rows=%lld cols=%lld", (long long)rows, (long long)cols);
-  PL_TRY(carrier_check(du_bf16, rows, rows_pad, cols, "pl_vit_gelu_bwd_bf16"));
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t n = rows * cols, n_pad = du_bf16 ? rows_pad * cols : n;
-  if (!du_bf16)
-    hipLaunchKernelGGL(vit_gelu_bwd<false>, dim3(grid_stride_blocks(n)), dim3(NT), 0, s, u, dy, n, du, nullptr, n);
-  else
-    hipLaunchKernelGGL(vit_gelu_bwd<true>, dim3(grid_stride_blocks(n_pad)), dim3(NT), 0, s, u, dy, n, du,
-                       static_cast<unsigned short*>(du_bf16), n_pad);
-  PL_CHECK_LAUNCH("vit_gelu_bwd");
   return PL_OK;
 }
 

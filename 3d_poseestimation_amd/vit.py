@@ -170,138 +170,179 @@ def _pad32(n):
     return (n + 31) // 32 * 32
 
 
+# ------------------------------------------------------------------------------------------------ the operand layer
+# An OPERAND is what a block GEMM reads: the fp32 tensor itself ("fp32") or a _Planes ("f16x3", "bf16p").  A mode object
+# says where a producing kernel writes (dest, carrier), how what it wrote becomes an operand, and computes the three
+# products; the block below is written once against it and never looks at compute_dtype.
 class _Planes:
-    """fp16 planes of an activation / gradient [rows][cols] in a [rows_pad][cols] carrier, and its device scale
-    {S, 1/S, 1/(S S_other)}."""
+    """A planes-GEMM operand [rows][cols] in the carrier p [rows_pad][cols] (padding rows zero): two fp16 planes and the
+    device scale {S, 1/S, 1/(S S_other)} ("f16x3"), or one bf16 plane and no scale ("bf16p")."""
     __slots__ = ("p", "scale", "rows", "cols", "rows_pad")
 
-    def __init__(self, x, rows_pad, other=None):
-        rows, cols = x.shape
-        self.rows, self.cols, self.rows_pad = rows, cols, rows_pad
-        self.p = torch.empty(rows_pad, cols, device=x.device)
-        self.scale = torch.empty(4, device=x.device)
-        scratch = torch.empty(_lib.lib().pl_vit_planes_scratch_bytes(), dtype=torch.uint8, device=x.device)
-        _run("pl_vit_planes_dyn", x.data_ptr(), rows, cols, rows_pad, _ptr(other.scale if other is not None else None),
-             self.scale.data_ptr(), self.p.data_ptr(), scratch.data_ptr())
+    def __init__(self, p, scale, rows):
+        self.p, self.scale, self.rows = p, scale, rows
+        self.rows_pad, self.cols = p.shape
+
+    def inv(self, i):
+        """scale[i] as the GEMM's device-side factor (None: no scale)."""
+        return self.scale[i:i + 1] if self.scale is not None else None
 
 
-def _pgemm_fwd(ap, wp, N, bias=None):
-    """y [rows][N] = a W^T (+ bias): a as dynamic planes, W [N][K] as weight planes."""
-    L, K, M = _lib.lib(), ap.cols, ap.rows
-    C = torch.empty(M, N, device=ap.p.device)
-    splits = L.pl_gemm_planes_splits(M, N, K)
-    slabs = torch.empty(splits * M * N, device=C.device) if splits > 1 else None
-    _run("pl_gemm_planes_raw", 0, _lib.PL_F16X3, ap.p.data_ptr(), ap.rows_pad * K, K, wp.data_ptr(), N * K, K, C.data_ptr(),
-         M, N, K, _ptr(bias if splits == 1 else None), 1.0 / conv.WEIGHT_PLANE_SCALE, ap.scale.data_ptr() + 4, _ptr(slabs), None)
-    if bias is not None and splits > 1:
-        C.add_(bias)
-    return C
+class _Fp32:
+    """Every block Linear on pl_gemm_f32."""
+
+    def __init__(self, model, T, dev):
+        self.model, self.T, self.Tp, self.dev = model, T, _pad32(T), dev
+
+    def carrier(self, cols):
+        """The bf16 carrier [Tp][cols] a producing kernel writes next to its fp32 output ("bf16p"; the others: None)."""
+        return None
+
+    def dest(self, cols):
+        """(fp32 output or None, carrier or None) for a value [T][cols] that only GEMMs read."""
+        return torch.empty(self.T, cols, device=self.dev), None
+
+    def operand(self, x, carrier, partner=None):
+        """The operand of x as its producer left it (x fp32 or None, carrier or None); partner: the operand x meets in the
+        weight gradient."""
+        return x
+
+    def linear(self, a, w, bias=None):
+        """y [T][N] = a W^T (+ bias), W [N][K]."""
+        return _gemm_f32(0, a, w, self.T, w.shape[0], w.shape[1], bias)
+
+    def wgrad(self, g, a):
+        """dW [g cols][a cols] = g^T a."""
+        return _gemm_f32(2, g, a, g.shape[1], a.shape[1], self.T)
+
+    def dgrad(self, g, w):
+        """dx [T][K] = g W."""
+        return _gemm_f32(1, g, w, self.T, w.shape[1], w.shape[0])
 
 
-def _pgemm_wgrad(gp, ap):
-    """dW [gp.cols][ap.cols] = g^T a over the (zero-padded) token rows, both operands as dynamic planes; gp was split with
-    other=ap, so gp.scale[2] = 1 / (S_g S_a)."""
-    return conv._gemm_planes_raw(2, gp.p, (gp.rows_pad, gp.cols), ap.p, (ap.rows_pad, ap.cols), gp.cols, ap.cols, gp.rows_pad,
-                                 1.0, gp.scale[2:3])
+class _F16x3(_Fp32):
+    """pl_gemm_planes_raw on fp16 planes: every operand split from its fp32 value by pl_vit_planes_dyn."""
+    mode, w_inv = _lib.PL_F16X3, 1.0 / conv.WEIGHT_PLANE_SCALE
+
+    def operand(self, x, carrier, partner=None):
+        p, scale = torch.empty(self.Tp, x.shape[1], device=self.dev), torch.empty(4, device=self.dev)
+        scratch = torch.empty(_lib.lib().pl_vit_planes_scratch_bytes(), dtype=torch.uint8, device=self.dev)
+        _run("pl_vit_planes_dyn", x.data_ptr(), self.T, x.shape[1], self.Tp, _ptr(partner.scale if partner is not None else None),
+             scale.data_ptr(), p.data_ptr(), scratch.data_ptr())
+        return _Planes(p, scale, self.T)
+
+    def linear(self, a, w, bias=None):
+        (N, K), M, wp = w.shape, a.rows, self.model._wplanes(w)[0]
+        C = torch.empty(M, N, device=self.dev)
+        splits = _lib.lib().pl_gemm_planes_splits(M, N, K)
+        slabs = torch.empty(splits * M * N, device=self.dev) if splits > 1 else None
+        _run("pl_gemm_planes_raw", 0, self.mode, a.p.data_ptr(), a.rows_pad * K, K, wp.data_ptr(), N * K, K, C.data_ptr(), M, N, K,
+             _ptr(bias if splits == 1 else None), self.w_inv, a.scale.data_ptr() + 4 if a.scale is not None else None,
+             _ptr(slabs), None)
+        if bias is not None and splits > 1:
+            C.add_(bias)
+        return C
+
+    def wgrad(self, g, a):
+        """Over the zero-padded rows; g was split with partner=a, so g.scale[2] = 1 / (S_g S_a)."""
+        return conv._gemm_planes_raw(2, g.p, (g.rows_pad, g.cols), a.p, (a.rows_pad, a.cols), g.cols, a.cols, g.rows_pad, 1.0,
+                                     g.inv(2), self.mode)
+
+    def dgrad(self, g, w):
+        """NT on the planes of W^T [K][N]."""
+        return conv._gemm_planes_raw(0, g.p, (g.rows_pad, g.cols), self.model._wplanes(w)[1], (w.shape[1], g.cols), g.rows,
+                                     w.shape[1], g.cols, self.w_inv, g.inv(1), self.mode)
 
 
-def _pgemm_dgrad(gp, wtp, K_in):
-    """dx [rows][K_in] = g W: g as dynamic planes, W^T [K_in][N] as weight planes (NT)."""
-    return conv._gemm_planes_raw(0, gp.p, (gp.rows_pad, gp.cols), wtp, (K_in, gp.cols), gp.rows, K_in, gp.cols,
-                                 1.0 / conv.WEIGHT_PLANE_SCALE, gp.scale[1:2])
+class _Bf16p(_F16x3):
+    """pl_gemm_planes_raw on bf16 carriers the producers write themselves: no fp32 copy of a GEMM-only value, no scale."""
+    mode, w_inv = _lib.PL_BF16, 1.0
+
+    def carrier(self, cols):
+        return torch.empty(self.Tp, cols, dtype=torch.bfloat16, device=self.dev)
+
+    def dest(self, cols):
+        return None, self.carrier(cols)
+
+    def operand(self, x, carrier, partner=None):
+        if carrier is None:                 # no producer wrote one: the head's fp32 GEMM made x
+            carrier = self.carrier(x.shape[1])
+            _run("pl_vit_bf16_pack", x.data_ptr(), self.T, x.shape[1], self.Tp, carrier.data_ptr())
+        return _Planes(carrier, None, self.T)
 
 
-def _carrier(rows_pad, cols, dev):
-    """A bf16 carrier [rows_pad][cols]: the producing kernel writes every row, the padding rows as zeros."""
-    return torch.empty(rows_pad, cols, dtype=torch.bfloat16, device=dev)
+_MODES = {"fp32": _Fp32, "f16x3": _F16x3, "bf16p": _Bf16p}
 
 
-def _bgemm_fwd(ac, M, wc, N, bias=None):
-    """y [M][N] = a W^T (+ bias): a as a bf16 carrier [rows_pad][K], W [N][K] as a bf16 weight carrier."""
-    L, K = _lib.lib(), ac.shape[1]
-    C = torch.empty(M, N, device=ac.device)
-    splits = L.pl_gemm_planes_splits(M, N, K)
-    slabs = torch.empty(splits * M * N, device=C.device) if splits > 1 else None
-    _run("pl_gemm_planes_raw", 0, _lib.PL_BF16, ac.data_ptr(), ac.numel(), K, wc.data_ptr(), N * K, K, C.data_ptr(), M, N, K,
-         _ptr(bias if splits == 1 else None), 1.0, None, _ptr(slabs), None)
-    if bias is not None and splits > 1:
-        C.add_(bias)
-    return C
-
-
-def _bgemm_wgrad(gc, ac):
-    """dW [g cols][a cols] = g^T a over the carriers' (zero-padded) rows."""
-    return conv._gemm_planes_raw(2, gc, tuple(gc.shape), ac, tuple(ac.shape), gc.shape[1], ac.shape[1], gc.shape[0], 1.0,
-                                 mode=_lib.PL_BF16)
-
-
-def _bgemm_dgrad(gc, wtc, M):
-    """dx [M][K_in] = g W: g as a carrier [rows_pad][N], W^T [K_in][N] as a bf16 weight carrier (NT)."""
-    K_in, N = wtc.shape
-    return conv._gemm_planes_raw(0, gc, tuple(gc.shape), wtc, (K_in, N), M, K_in, N, 1.0, mode=_lib.PL_BF16)
-
-
-def _block_fwd_bf16p(model, x, add, blk, B, seq, T, Tp, eps):
-    """One block in "bf16p" mode: (xa, m, what the backward keeps).  x (+ add: the previous block's mlp output) is the
-    residual stream."""
+def _block_fwd(ops, blk, x, add, B, seq, eps):
+    """One block: x (+ add: the previous block's mlp output) is the residual stream.  Returns (xa, m, what the backward
+    keeps): the next block's x and add."""
     (g1, b1, g2, b2, wqkv, wout, g3, b3, w0, b0, w2, b2m) = blk
-    H, heads, dev = model.hidden_d, model.n_heads, x.device
+    T, Tp, dev, H, heads = ops.T, ops.Tp, ops.dev, ops.model.hidden_d, ops.model.n_heads
     xb = torch.empty(T, H, device=dev) if add is not None else x
-    a_c = _carrier(Tp, H, dev)
+    a, a_c = ops.dest(H)
     st12 = torch.empty(4, T, device=dev)
     _run("pl_vit_ln_fwd_bf16", x.data_ptr(), _ptr(add), T, H, 2, g1.data_ptr(), b1.data_ptr(), g2.data_ptr(), b2.data_ptr(),
-         eps, _ptr(xb if add is not None else None), None, a_c.data_ptr(), Tp, st12.data_ptr())
-    qkv = _bgemm_fwd(a_c, T, model._wplanes(wqkv)[0], 3 * H)
-    o_c = _carrier(Tp, H, dev)
+         eps, _ptr(xb if add is not None else None), _ptr(a), _ptr(a_c), Tp, st12.data_ptr())
+    a = ops.operand(a, a_c)
+    qkv = ops.linear(a, wqkv)
+    o, o_c = ops.dest(H)
     lse = torch.empty(B, heads, seq, device=dev)
-    _run("pl_vit_attn_fwd_bf16", qkv.data_ptr(), B, seq, heads, DIM_HEAD, DIM_HEAD ** -0.5, None, o_c.data_ptr(), Tp,
+    _run("pl_vit_attn_fwd_bf16", qkv.data_ptr(), B, seq, heads, DIM_HEAD, DIM_HEAD ** -0.5, _ptr(o), _ptr(o_c), Tp,
          lse.data_ptr())
-    u = _bgemm_fwd(o_c, T, model._wplanes(wout)[0], H)
+    o = ops.operand(o, o_c)
+    u = ops.linear(o, wout)
     xa = torch.empty(T, H, device=dev)
-    n2_c = _carrier(Tp, H, dev)
+    n2, n2_c = ops.dest(H)
     st3 = torch.empty(2, T, device=dev)
     _run("pl_vit_ln_fwd_bf16", xb.data_ptr(), u.data_ptr(), T, H, 1, g3.data_ptr(), b3.data_ptr(), None, None, eps,
-         xa.data_ptr(), None, n2_c.data_ptr(), Tp, st3.data_ptr())
-    h = _bgemm_fwd(n2_c, T, model._wplanes(w0)[0], 4 * H, b0)
-    g_c = _carrier(Tp, 4 * H, dev)
-    _run("pl_vit_gelu_fwd_bf16", h.data_ptr(), T, 4 * H, Tp, None, g_c.data_ptr())
-    m = _bgemm_fwd(g_c, T, model._wplanes(w2)[0], H, b2m)
-    return xa, m, dict(xb=xb, st12=st12, a_c=a_c, qkv=qkv, lse=lse, o_c=o_c, xa=xa, st3=st3, n2_c=n2_c, h=h, g_c=g_c)
+         xa.data_ptr(), _ptr(n2), _ptr(n2_c), Tp, st3.data_ptr())
+    n2 = ops.operand(n2, n2_c)
+    h = ops.linear(n2, w0, b0)
+    g, g_c = ops.dest(4 * H)
+    _run("pl_vit_gelu_fwd_bf16", h.data_ptr(), T, 4 * H, Tp, _ptr(g), _ptr(g_c))
+    g = ops.operand(g, g_c)
+    m = ops.linear(g, w2, b2m)
+    return xa, m, dict(xb=xb, st12=st12, a=a, qkv=qkv, lse=lse, o=o, xa=xa, st3=st3, n2=n2, h=h, g=g)
 
 
-def _block_bwd_bf16p(model, s, blk, grads, base, dx, dm_c, B, seq, T, Tp, lnscratch, want_carrier):
-    """The backward of one "bf16p" block: dx is the gradient of its output (fp32: the residual stream), dm_c its carrier.
-    Fills grads[base:base + 12]; returns (dx of the block input, its carrier when want_carrier)."""
+def _block_bwd(ops, s, blk, grads, base, dx, dx_c, B, seq, lnscratch, want_carrier):
+    """The backward of one block: dx is the gradient of its output (the residual stream), dx_c its carrier if a producer
+    wrote one.  Fills grads[base:base + 12]; returns (dx of the block input, its carrier when want_carrier)."""
     (g1, b1, g2, b2, wqkv, wout, g3, b3, w0, b0, w2, b2m) = blk
-    H, heads, dev = model.hidden_d, model.n_heads, dx.device
-    # mlp: m = mlp.2(GELU(mlp.0(n2)))
-    grads[base + 10] = _bgemm_wgrad(dm_c, s["g_c"])
-    dg = _bgemm_dgrad(dm_c, model._wplanes(w2)[1], T)
+    T, Tp, dev, H, heads = ops.T, ops.Tp, ops.dev, ops.model.hidden_d, ops.model.n_heads
+    # mlp: m = mlp.2(GELU(mlp.0(n2)));  dm = dx
+    dm = ops.operand(dx, dx_c, s["g"])
+    grads[base + 10] = ops.wgrad(dm, s["g"])
+    dg = ops.dgrad(dm, w2)
     grads[base + 11] = _colsum(dx)
-    dh_c = _carrier(Tp, 4 * H, dev)
-    _run("pl_vit_gelu_bwd_bf16", s["h"].data_ptr(), dg.data_ptr(), T, 4 * H, Tp, dg.data_ptr(), dh_c.data_ptr())
-    grads[base + 8] = _bgemm_wgrad(dh_c, s["n2_c"])
-    dn2 = _bgemm_dgrad(dh_c, model._wplanes(w0)[1], T)
-    grads[base + 9] = _colsum(dg)                           # (dg now holds dh in fp32)
-    del dg, dh_c
+    dh_c = ops.carrier(4 * H)
+    _run("pl_vit_gelu_bwd_bf16", s["h"].data_ptr(), dg.data_ptr(), T, 4 * H, Tp, dg.data_ptr(), _ptr(dh_c))
+    dh = ops.operand(dg, dh_c, s["n2"])                    # (dg now holds dh in fp32)
+    grads[base + 8] = ops.wgrad(dh, s["n2"])
+    dn2 = ops.dgrad(dh, w0)
+    grads[base + 9] = _colsum(dg)
+    del dg, dh, dh_c
     # norm2 with the residual: dxa = dx + LN3'(dn2)
     dxa = torch.empty(T, H, device=dev)
-    dxa_c = _carrier(Tp, H, dev)
+    dxa_c = ops.carrier(H)
     dgb3 = torch.empty(2 * H, device=dev)
     _run("pl_vit_ln_bwd_bf16", dn2.data_ptr(), dx.data_ptr(), s["xa"].data_ptr(), s["st3"].data_ptr(), T, H, 1, g3.data_ptr(),
-         None, None, dxa.data_ptr(), dxa_c.data_ptr(), Tp, dgb3.data_ptr(), lnscratch.data_ptr())
+         None, None, dxa.data_ptr(), _ptr(dxa_c), Tp, dgb3.data_ptr(), lnscratch.data_ptr())
     grads[base + 6], grads[base + 7] = dgb3[:H], dgb3[H:]
     # attention: u = to_out(o)
-    grads[base + 5] = _bgemm_wgrad(dxa_c, s["o_c"])
-    do = _bgemm_dgrad(dxa_c, model._wplanes(wout)[1], T)
-    dq_c = _carrier(Tp, 3 * H, dev)
+    du = ops.operand(dxa, dxa_c, s["o"])
+    grads[base + 5] = ops.wgrad(du, s["o"])
+    do = ops.dgrad(du, wout)
+    dqkv, dq_c = ops.dest(3 * H)
     _run("pl_vit_attn_bwd_bf16", s["qkv"].data_ptr(), s["lse"].data_ptr(), do.data_ptr(), B, seq, heads, DIM_HEAD,
-         DIM_HEAD ** -0.5, None, dq_c.data_ptr(), Tp)
-    grads[base + 4] = _bgemm_wgrad(dq_c, s["a_c"])
-    da = _bgemm_dgrad(dq_c, model._wplanes(wqkv)[1], T)
+         DIM_HEAD ** -0.5, _ptr(dqkv), _ptr(dq_c), Tp)
+    dq = ops.operand(dqkv, dq_c, s["a"])
+    grads[base + 4] = ops.wgrad(dq, s["a"])
+    da = ops.dgrad(dq, wqkv)
     # norm1 -> mhsa.norm with the residual: dx = dxa + LN1'(LN2'(da))
     dxb = torch.empty(T, H, device=dev)
-    dxb_c = _carrier(Tp, H, dev) if want_carrier else None
+    dxb_c = ops.carrier(H) if want_carrier else None
     dgb12 = torch.empty(4 * H, device=dev)
     _run("pl_vit_ln_bwd_bf16", da.data_ptr(), dxa.data_ptr(), s["xb"].data_ptr(), s["st12"].data_ptr(), T, H, 2,
          g1.data_ptr(), b1.data_ptr(), g2.data_ptr(), dxb.data_ptr(), _ptr(dxb_c), Tp, dgb12.data_ptr(), lnscratch.data_ptr())
@@ -332,9 +373,9 @@ class _ViTFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, want, x2d, *ps):
         B, seq, in_d = x2d.shape
-        H, heads, out_d = model.hidden_d, model.n_heads, model.out_d
-        T, dev, f16, bf = B * seq, x2d.device, model.compute_dtype == "f16x3", model.compute_dtype == "bf16p"
-        Tp = _pad32(T)
+        H, out_d = model.hidden_d, model.out_d
+        T, dev = B * seq, x2d.device
+        ops = _MODES[model.compute_dtype](model, T, dev)
         eps = 1e-5
         Wm, bm, pos = ps[0], ps[1], ps[2]
         saved = []
@@ -343,71 +384,28 @@ class _ViTFn(torch.autograd.Function):
             _run("pl_vit_embed_fwd", x2d.data_ptr(), T, in_d, seq, Wm.data_ptr(), bm.data_ptr(), pos.data_ptr(), H, x.data_ptr())
             add = None
             for bi in range(model.n_block):
-                if bf:
-                    x, add, s = _block_fwd_bf16p(model, x, add, ps[3 + 12 * bi: 15 + 12 * bi], B, seq, T, Tp, eps)
-                    if want:
-                        saved.append(s)
-                    continue
-                (g1, b1, g2, b2, wqkv, wout, g3, b3, w0, b0, w2, b2m) = ps[3 + 12 * bi: 15 + 12 * bi]
-                xb = torch.empty(T, H, device=dev) if add is not None else x
-                a = torch.empty(T, H, device=dev)
-                st12 = torch.empty(4, T, device=dev)
-                _run("pl_vit_ln_fwd", x.data_ptr(), _ptr(add), T, H, 2, g1.data_ptr(), b1.data_ptr(), g2.data_ptr(), b2.data_ptr(),
-                     eps, _ptr(xb if add is not None else None), a.data_ptr(), st12.data_ptr())
-                if f16:
-                    ap = _Planes(a, Tp)
-                    qkv = _pgemm_fwd(ap, model._wplanes(wqkv)[0], 3 * H)
-                else:
-                    qkv = _gemm_f32(0, a, wqkv, T, 3 * H, H)
-                o = torch.empty(T, H, device=dev)
-                lse = torch.empty(B, heads, seq, device=dev)
-                _run("pl_vit_attn_fwd", qkv.data_ptr(), B, seq, heads, DIM_HEAD, DIM_HEAD ** -0.5, o.data_ptr(), lse.data_ptr())
-                if f16:
-                    op = _Planes(o, Tp)
-                    u = _pgemm_fwd(op, model._wplanes(wout)[0], H)
-                else:
-                    u = _gemm_f32(0, o, wout, T, H, H)
-                xa = torch.empty(T, H, device=dev)
-                n2 = torch.empty(T, H, device=dev)
-                st3 = torch.empty(2, T, device=dev)
-                _run("pl_vit_ln_fwd", xb.data_ptr(), u.data_ptr(), T, H, 1, g3.data_ptr(), b3.data_ptr(), None, None, eps,
-                     xa.data_ptr(), n2.data_ptr(), st3.data_ptr())
-                if f16:
-                    n2p = _Planes(n2, Tp)
-                    h = _pgemm_fwd(n2p, model._wplanes(w0)[0], 4 * H, b0)
-                else:
-                    h = _gemm_f32(0, n2, w0, T, 4 * H, H, b0)
-                g = torch.empty_like(h)
-                _run("pl_vit_gelu_fwd", h.data_ptr(), h.numel(), g.data_ptr())
-                if f16:
-                    gp = _Planes(g, Tp)
-                    m = _pgemm_fwd(gp, model._wplanes(w2)[0], H, b2m)
-                else:
-                    m = _gemm_f32(0, g, w2, T, H, 4 * H, b2m)
+                x, add, s = _block_fwd(ops, ps[3 + 12 * bi: 15 + 12 * bi], x, add, B, seq, eps)
                 if want:
-                    if f16:
-                        saved.append(dict(xb=xb, st12=st12, ap=ap, qkv=qkv, lse=lse, op=op, xa=xa, st3=st3, n2p=n2p, h=h, gp=gp))
-                    else:
-                        saved.append(dict(xb=xb, st12=st12, a=a, qkv=qkv, lse=lse, o=o, xa=xa, st3=st3, n2=n2, h=h, g=g))
-                x, add = xa, m
+                    saved.append(s)
             xf = torch.empty(T, H, device=dev)
-            _run("pl_vit_ln_fwd", x.data_ptr(), add.data_ptr(), T, H, 0, None, None, None, None, eps, xf.data_ptr(), None, None)
+            _run("pl_vit_ln_fwd_bf16", x.data_ptr(), add.data_ptr(), T, H, 0, None, None, None, None, eps, xf.data_ptr(), None,
+                 None, 0, None)
             wh, bh, wl, bl = ps[-4:]
             z = _gemm_f32(0, xf, wh, T, H // 2, H, bh)
             y = torch.empty(B, seq, out_d, device=dev)
             _run("pl_vit_head_fwd", z.data_ptr(), T, H // 2, wl.data_ptr(), bl.data_ptr(), out_d, y.data_ptr())
         if want:
             ctx.model, ctx.saved, ctx.x2d, ctx.xf, ctx.z, ctx.ps = model, saved, x2d, xf, z, ps
-            ctx.dims = (B, seq, in_d, T, Tp, f16, bf)
+            ctx.ops, ctx.dims = ops, (B, seq, in_d, T)
             ctx.versions = tuple(p._version for p in ps)     # (a FlatAdam step bumps them too)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        model, saved, ps = ctx.model, ctx.saved, ctx.ps
+        model, saved, ps, ops = ctx.model, ctx.saved, ctx.ps, ctx.ops
         _check_versions(model, ps, ctx.versions)
-        B, seq, in_d, T, Tp, f16, bf = ctx.dims
-        H, heads, out_d = model.hidden_d, model.n_heads, model.out_d
+        B, seq, in_d, T = ctx.dims
+        H, out_d = model.hidden_d, model.out_d
         dev = dy.device
         dy = dy.float().contiguous()
         grads = [None] * len(ps)
@@ -423,70 +421,11 @@ class _ViTFn(torch.autograd.Function):
             grads[-4] = _gemm_f32(2, dz, ctx.xf, H // 2, H, T)
             grads[-3] = _colsum(dz)
             dx = _gemm_f32(1, dz, wh, T, H, H // 2)              # d(block output) = d(x_final)
+            dx_c = None                                         # (the head's fp32 GEMM writes no carrier)
             lnscratch = torch.empty(max(L.pl_vit_ln_bwd_scratch_bytes(T, H, 2), 4), dtype=torch.uint8, device=dev)
-            if bf:                                              # the head's fp32 dx: the last block's output gradient
-                dm_c = _carrier(Tp, H, dev)
-                _run("pl_vit_bf16_pack", dx.data_ptr(), T, H, Tp, dm_c.data_ptr())
             for bi in reversed(range(model.n_block)):
-                s = saved[bi]
-                base = 3 + 12 * bi
-                if bf:
-                    dx, dm_c = _block_bwd_bf16p(model, s, ps[base: base + 12], grads, base, dx, dm_c, B, seq, T, Tp,
-                                                lnscratch, bi > 0)
-                    continue
-                (g1, b1, g2, b2, wqkv, wout, g3, b3, w0, b0, w2, b2m) = ps[3 + 12 * bi: 15 + 12 * bi]
-                # mlp: m = mlp.2(GELU(mlp.0(n2)));  dm = dx
-                if f16:
-                    dmp = _Planes(dx, Tp, other=s["gp"])
-                    grads[base + 10] = _pgemm_wgrad(dmp, s["gp"])
-                    dg = _pgemm_dgrad(dmp, model._wplanes(w2)[1], 4 * H)
-                else:
-                    grads[base + 10] = _gemm_f32(2, dx, s["g"], H, 4 * H, T)
-                    dg = _gemm_f32(1, dx, w2, T, 4 * H, H)
-                grads[base + 11] = _colsum(dx)
-                dh = dg
-                _run("pl_vit_gelu_bwd", s["h"].data_ptr(), dg.data_ptr(), dg.numel(), dh.data_ptr())
-                if f16:
-                    dhp = _Planes(dh, Tp, other=s["n2p"])
-                    grads[base + 8] = _pgemm_wgrad(dhp, s["n2p"])
-                    dn2 = _pgemm_dgrad(dhp, model._wplanes(w0)[1], H)
-                else:
-                    grads[base + 8] = _gemm_f32(2, dh, s["n2"], 4 * H, H, T)
-                    dn2 = _gemm_f32(1, dh, w0, T, H, 4 * H)
-                grads[base + 9] = _colsum(dh)
-                del dg, dh
-                # norm2 with the residual: dxa = dx + LN3'(dn2)
-                dxa = torch.empty(T, H, device=dev)
-                dgb3 = torch.empty(2 * H, device=dev)
-                _run("pl_vit_ln_bwd", dn2.data_ptr(), dx.data_ptr(), s["xa"].data_ptr(), s["st3"].data_ptr(), T, H, 1,
-                     g3.data_ptr(), None, None, dxa.data_ptr(), dgb3.data_ptr(), lnscratch.data_ptr())
-                grads[base + 6], grads[base + 7] = dgb3[:H], dgb3[H:]
-                # attention: u = to_out(o)
-                if f16:
-                    dup = _Planes(dxa, Tp, other=s["op"])
-                    grads[base + 5] = _pgemm_wgrad(dup, s["op"])
-                    do = _pgemm_dgrad(dup, model._wplanes(wout)[1], H)
-                else:
-                    grads[base + 5] = _gemm_f32(2, dxa, s["o"], H, H, T)
-                    do = _gemm_f32(1, dxa, wout, T, H, H)
-                dqkv = torch.empty(T, 3 * H, device=dev)
-                _run("pl_vit_attn_bwd", s["qkv"].data_ptr(), s["lse"].data_ptr(), do.data_ptr(), B, seq, heads, DIM_HEAD,
-                     DIM_HEAD ** -0.5, dqkv.data_ptr())
-                if f16:
-                    dqp = _Planes(dqkv, Tp, other=s["ap"])
-                    grads[base + 4] = _pgemm_wgrad(dqp, s["ap"])
-                    da = _pgemm_dgrad(dqp, model._wplanes(wqkv)[1], H)
-                else:
-                    grads[base + 4] = _gemm_f32(2, dqkv, s["a"], 3 * H, H, T)
-                    da = _gemm_f32(1, dqkv, wqkv, T, H, 3 * H)
-                # norm1 -> mhsa.norm with the residual: dx = dxa + LN1'(LN2'(da))
-                dxb = torch.empty(T, H, device=dev)
-                dgb12 = torch.empty(4 * H, device=dev)
-                _run("pl_vit_ln_bwd", da.data_ptr(), dxa.data_ptr(), s["xb"].data_ptr(), s["st12"].data_ptr(), T, H, 2,
-                     g1.data_ptr(), b1.data_ptr(), g2.data_ptr(), dxb.data_ptr(), dgb12.data_ptr(), lnscratch.data_ptr())
-                grads[base + 0], grads[base + 1] = dgb12[:H], dgb12[H:2 * H]
-                grads[base + 2], grads[base + 3] = dgb12[2 * H:3 * H], dgb12[3 * H:]
-                dx = dxb
+                base = 3 + 12 * bi                              # (block 0's input gradient meets no GEMM: no carrier)
+                dx, dx_c = _block_bwd(ops, saved[bi], ps[base: base + 12], grads, base, dx, dx_c, B, seq, lnscratch, bi > 0)
             Wm, pos = ps[0], ps[2]
             dwb = torch.empty(H * in_d + H, device=dev)
             dpos = torch.empty(seq, H, device=dev) if ctx.needs_input_grad[5] else None

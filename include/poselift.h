@@ -637,8 +637,10 @@ int pl_vit_planes_dyn(const float* x, int64_t rows, int64_t cols, int64_t rows_p
  * [rows_pad][cols] bf16 (cols: H, heads*64, 3*heads*64 or 4*H), rows_pad >= T, rows_pad % 32 == 0, the rows past T zero (the
  * padded contraction of the TN weight gradients), 16-byte aligned: a PL_BF16 operand of pl_gemm_planes_raw.  Every carrier
  * element is the fp32 value the plain entry point computes, rounded once to nearest even (a NaN stays a NaN).
- * Arguments as the plain entry points; a NULL carrier runs exactly the plain entry point's kernel; with a carrier, the
- * fp32 output (y, dx, o, dqkv, du) may be NULL (not written).
+ * Each pair of entry points (plain, _bf16) is one checked launcher in vit.hip, and the plain form is the _bf16 form without
+ * a carrier: the same argument rules (but pl_vit_gelu_* take any element count n, the _bf16 forms rows and cols), and a NULL
+ * carrier launches exactly the plain form's kernel.  Without a carrier the fp32 output (y, dx, o, dqkv, du) is required;
+ * with one it may be NULL (not written).
  *   pl_vit_ln_fwd_bf16   : y_bf16 = carrier of y (nnorm >= 1)
  *   pl_vit_ln_bwd_bf16   : dx_bf16 = carrier of dx
  *   pl_vit_attn_fwd_bf16 : o_bf16 [rows_pad][heads*64], T = B * seq

@@ -74,3 +74,56 @@ def test_carrier_entry_points_reject_bad_arguments(pkg):
     assert L.pl_vit_bf16_pack(one, T, 254, 64, one, None) != 0
     assert L.pl_vit_bf16_pack(None, T, 256, 64, one, None) != 0 and b"null" in L.pl_last_error()
     assert L.pl_vit_bf16_pack(odd, T, 256, 64, one, None) != 0 and b"aligned" in L.pl_last_error()
+
+
+def test_plain_and_null_carrier_forms_refuse_the_same_calls_with_the_same_code(pkg):
+    """Each of the six carrier kernels has one checked launcher behind both of its names: a bad call is refused with the same
+    return code through the plain form and through the _bf16 form with a NULL carrier, and neither accepts a NULL fp32
+    output when there is no carrier to write instead."""
+    L = pkg.lib()
+    one, odd = ctypes.c_void_p(16), ctypes.c_void_p(24)
+    T, H, Tp = 17 * 3, 256, 64
+
+    def both(name, plain_args, carrier_args):          # (return codes; each message names the entry point that was called)
+        rp, mp = getattr(L, name)(*plain_args, None), L.pl_last_error()
+        rc, mc = getattr(L, name + "_bf16")(*carrier_args, None), L.pl_last_error()
+        assert mp.startswith(name.encode() + b":") and mc.startswith(name.encode() + b"_bf16:"), (mp, mc)
+        return rp, rc
+
+    def ln_fwd(x=one, add=None, T=T, H=H, nn=2, g1=one, b1=one, g2=one, b2=one, x_out=None, y=one, stats=one):
+        return both("pl_vit_ln_fwd", (x, add, T, H, nn, g1, b1, g2, b2, 1e-5, x_out, y, stats),
+                    (x, add, T, H, nn, g1, b1, g2, b2, 1e-5, x_out, y, None, Tp, stats))
+
+    def ln_bwd(dy=one, dres=None, x=one, stats=one, T=T, H=H, nn=2, g1=one, b1=one, g2=one, dx=one, dgb=one, scratch=one):
+        return both("pl_vit_ln_bwd", (dy, dres, x, stats, T, H, nn, g1, b1, g2, dx, dgb, scratch),
+                    (dy, dres, x, stats, T, H, nn, g1, b1, g2, dx, None, Tp, dgb, scratch))
+
+    def attn_fwd(qkv=one, B=3, seq=17, heads=4, dh=64, o=one, lse=one):
+        return both("pl_vit_attn_fwd", (qkv, B, seq, heads, dh, 0.125, o, lse), (qkv, B, seq, heads, dh, 0.125, o, None, Tp, lse))
+
+    def attn_bwd(qkv=one, lse=one, dout=one, B=3, seq=17, heads=4, dh=64, dqkv=one):
+        return both("pl_vit_attn_bwd", (qkv, lse, dout, B, seq, heads, dh, 0.125, dqkv),
+                    (qkv, lse, dout, B, seq, heads, dh, 0.125, dqkv, None, Tp))
+
+    def gelu_fwd(u=one, rows=T, y=one):          # the plain form takes the element count
+        return both("pl_vit_gelu_fwd", (u, rows * 1024, y), (u, rows, 1024, Tp, y, None))
+
+    def gelu_bwd(u=one, dy=one, rows=T, du=one):
+        return both("pl_vit_gelu_bwd", (u, dy, rows * 1024, du), (u, dy, rows, 1024, Tp, du, None))
+
+    bad = {
+        "ln_fwd": [ln_fwd(y=None), ln_fwd(x=None), ln_fwd(T=0), ln_fwd(H=1028), ln_fwd(H=258), ln_fwd(nn=3), ln_fwd(g2=None),
+                   ln_fwd(stats=None), ln_fwd(add=one), ln_fwd(nn=0), ln_fwd(x=odd), ln_fwd(y=odd), ln_fwd(b1=odd),
+                   ln_fwd(add=odd, x_out=one)],
+        "ln_bwd": [ln_bwd(dx=None), ln_bwd(dy=None), ln_bwd(nn=0), ln_bwd(H=1028), ln_bwd(T=-1), ln_bwd(b1=None), ln_bwd(g2=None),
+                   ln_bwd(dgb=None), ln_bwd(scratch=None), ln_bwd(dx=odd), ln_bwd(dres=odd), ln_bwd(g1=odd)],
+        "attn_fwd": [attn_fwd(o=None), attn_fwd(qkv=None), attn_fwd(lse=None), attn_fwd(seq=33), attn_fwd(dh=32), attn_fwd(B=0),
+                     attn_fwd(heads=0), attn_fwd(qkv=odd)],
+        "attn_bwd": [attn_bwd(dqkv=None), attn_bwd(qkv=None), attn_bwd(lse=None), attn_bwd(dout=None), attn_bwd(seq=33),
+                     attn_bwd(seq=32, heads=4), attn_bwd(dh=32), attn_bwd(dout=odd)],
+        "gelu_fwd": [gelu_fwd(y=None), gelu_fwd(u=None), gelu_fwd(rows=0), gelu_fwd(rows=-3)],
+        "gelu_bwd": [gelu_bwd(du=None), gelu_bwd(u=None), gelu_bwd(dy=None), gelu_bwd(rows=0)],
+    }
+    for kernel, calls in bad.items():
+        for i, (plain, null_carrier) in enumerate(calls):       # (the first of each list: no fp32 output and no carrier)
+            assert plain != 0 and null_carrier == plain, (kernel, i, plain, null_carrier)
