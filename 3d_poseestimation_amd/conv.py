@@ -1,17 +1,28 @@
-"""Convolution-path ops on the HIP library, NHWC throughout: forward ops and their autograd forms.
+"""Convolution-path ops on the HIP library, NHWC throughout: forward ops and their autograd forms, in two generations.
 
+Direct kernels (csrc/conv.hip; compute_dtype "bf16x6" / "bf16", and maps too small for the planes GEMM):
     conv2d_nhwc          nn.Conv2d forward with the Bottleneck's eval-mode epilogue folded in
-                         (/root/reference/phase4_joined/Resnet.py:51-95, :112-118, :151-158; Model.py:66-69)
+                         (reference: phase4_joined/Resnet.py:51-95, :112-118, :151-158; Model.py:66-69)
     maxpool3x3s2_nhwc    nn.MaxPool2d(3, 2, 1)                               (Resnet.py:119)
     deconv4x4s2_nhwc     nn.ConvTranspose2d(4, 2, 1, bias=False) + BN + ReLU (Model.py:47-63)
     nhwc_to_nchw         layout change for heads that want NCHW (Model_2D)
-    *_autograd, batchnorm_relu_train, add_relu   the differentiable forms used in training mode
-    to_ohwi / deconv_subkernels / fold_bn   weight-layout helpers (host side, once per model)
+    *_autograd           their differentiable forms (dgrad / wgrad on the same kernels)
+    to_ohwi / deconv_subkernels / fold_bn   weight-layout helpers (host side, once per set of weights)
 
-The phase4 model permutes its NHWC input to NCHW for cuDNN/MIOpen (Model.py:88); here activations stay NHWC
+Planes GEMM (csrc/gemm_planes16.h; compute_dtype "f16x3" / "bf16p"): every convolution of a training step and of eval
+mode as a GEMM on 16-bit operand planes that the producer of each tensor writes (second half of this file):
+    conv1x1[_bias]_planes, conv_planes, stem_planes, deconv4x4s2_planes     training, with autograd
+    conv2d_planes_eval, deconv_planes_eval                                  eval, folded epilogue, planes in and out
+
+Shared by both: batchnorm_relu_train[_planes] / bn_join_planes (training-mode BatchNorm, optionally reading a GEMM
+epilogue's statistics, adding the residual and writing planes) and add_relu[_planes] (the residual join).
+
+The reference model permutes its NHWC input to NCHW for cuDNN/MIOpen (Model.py:88); here activations stay NHWC
 end to end: a feature map IS the [B*H*W][C] matrix the MFMA GEMM wants, a 1x1 convolution is a GEMM, a KxK
 convolution is the same GEMM with a gathering A loader (implicit GEMM, no im2col buffer).
 """
+import ctypes
+
 import torch
 from torch.autograd.graph import increment_version
 
@@ -103,8 +114,14 @@ def _opt(t, name, n):
     return t
 
 
-# "f16x3": the 1x1 convolutions of a TRAINING step run on the planes GEMM (bottom of this file); everything else -- the
-# 3x3 / 7x7 / transposed convolutions, eval mode -- keeps the fp32-grade bf16x6 kernels
+def _bits(rows, C, dev):
+    """The ReLU bitmap of a [rows][C] map: one bit per element, four 64-bit words per row and 256-column strip."""
+    return torch.empty(rows, 4 * ((C + 255) // 256), dtype=torch.int64, device=dev)
+
+
+# The direct kernels' arithmetic per compute_dtype.  "f16x3" / "bf16p" run on the planes GEMM (second half of this file);
+# what reaches a direct kernel under them -- maps too small for the planes path -- keeps the same grade: fp32-grade
+# bf16x6 next to two fp16 planes, bf16 operands next to one bf16 plane.
 ARITH = {"bf16x6": _lib.PL_BF16X6, "bf16": _lib.PL_BF16, "f16x3": _lib.PL_BF16X6, "bf16p": _lib.PL_BF16}
 
 
@@ -237,17 +254,29 @@ def nhwc_to_nchw(x):
 
 
 # ---------------------------------------------------------------------------------------------
-# Training-mode building blocks (autograd), NHWC.  The assembly of a trainable ResNet from them -- and the
-# transposed-convolution / max-pool backward it also needs -- is the next slice of SURVEY 8f row N2.
+# Training-mode building blocks (autograd), NHWC.  backbone.py assembles the trainable ResNet and head from them.
+# The convolutions here run on the direct kernels; BatchNorm and the residual join serve the planes path as well
+# (operand planes and PlaneLink: second half of this file).
 # ---------------------------------------------------------------------------------------------
+def _colsum(x, rows, C):
+    """Column sums [C] of the fp32 map x [rows][C] (a bias gradient)."""
+    L = _lib.lib()
+    out = torch.empty(C, dtype=torch.float32, device=x.device)
+    scratch = torch.empty(L.pl_colsum_scratch_bytes(rows, C), dtype=torch.uint8, device=x.device)
+    with _lib.on_device(x.device):
+        rc = L.pl_colsum(x.data_ptr(), rows, C, out.data_ptr(), scratch.data_ptr(), _lib.current_stream_ptr())
+    _lib.check(rc, "pl_colsum")
+    return out
+
+
 class _Conv2dFn(torch.autograd.Function):
-    """conv2d_nhwc with autograd: dgrad and wgrad run on the library too (conv2d_nhwc_dgrad / _wgrad)."""
+    """conv2d_nhwc (+ bias, or None) with autograd: dgrad and wgrad run on the library too (conv2d_nhwc_dgrad / _wgrad)."""
 
     @staticmethod
-    def forward(ctx, x, w_ohwi, stride, padding, arith):
+    def forward(ctx, x, w_ohwi, bias, stride, padding, arith):
         ctx.save_for_backward(x, w_ohwi)
         ctx.geom = (stride, padding, arith)
-        return conv2d_nhwc(x, w_ohwi, stride, padding, arith=arith)
+        return conv2d_nhwc(x, w_ohwi, stride, padding, bias=bias, arith=arith)
 
     @staticmethod
     def backward(ctx, dy):
@@ -256,74 +285,175 @@ class _Conv2dFn(torch.autograd.Function):
         dy = dy.contiguous()
         dx = conv2d_nhwc_dgrad(dy, w, x.shape[1:3], stride, padding, arith) if ctx.needs_input_grad[0] else None
         dw = conv2d_nhwc_wgrad(x, dy, w.shape[1], stride, padding, arith) if ctx.needs_input_grad[1] else None
-        return dx, dw, None, None, None
+        db = None
+        if ctx.needs_input_grad[2]:
+            C = dy.shape[-1]
+            db = _colsum(dy, dy.numel() // C, C)
+        return dx, dw, db, None, None, None
 
 
 def conv2d_nhwc_autograd(x, w_ohwi, stride=1, padding=0, arith="bf16x6"):
     """Differentiable conv2d_nhwc (no folded epilogue: in training mode BatchNorm needs batch statistics).
     arith "bf16": forward, dgrad and wgrad round their operands to bf16 while staging (fp32 accumulate/storage)."""
-    return _Conv2dFn.apply(x, w_ohwi, stride, padding, arith)
+    return _Conv2dFn.apply(x, w_ohwi, None, stride, padding, arith)
 
 
-class _BNReLUFn(torch.autograd.Function):
+def conv2d_bias_nhwc_autograd(x, w_ohwi, bias, stride=1, padding=0, arith="bf16x6"):
+    return _Conv2dFn.apply(x, w_ohwi, bias, stride, padding, arith)
+
+
+def _bn_fwd(ctx, z, identity, gamma, beta, running_mean, running_var, batches, eps, momentum, *, relu, f32, planes, link, mode):
+    """Training-mode BatchNorm of z [..., C] over every leading dimension (+ identity, when given) (+ ReLU): the output as
+    fp32 (f32), as a carrier of its operand planes in `mode` (planes), or both -- returns (y, yp), [rows][C] or None.  With
+    link, the planes convolution that produced z has left its epilogue statistics there (or None: one more pass over z).
+    Saves what _bn_bwd needs on ctx.  (Here and in _bn_bwd the library is handed mode 0 next to a NULL planes pointer.)"""
+    shape = z.shape
+    C = shape[-1]
+    z2 = z.contiguous().reshape(-1, C)
+    id2 = identity.contiguous().reshape(-1, C) if identity is not None else None
+    rows = z2.shape[0]
+    dev, L = z2.device, _lib.lib()
+    y = torch.empty_like(z2) if f32 else None
+    yp = torch.empty_like(z2) if planes else None
+    bits = _bits(rows, C, dev)
+    mean, rstd = torch.empty(C, device=dev), torch.empty(C, device=dev)
+    scratch = torch.empty(L.pl_bn_train_scratch_bytes(rows, C), dtype=torch.uint8, device=dev)
+    gstat = None
+    if link is not None:
+        gstat, link.stat = link.stat, None
+    with _lib.on_device(dev):
+        rc = L.pl_bn_train_fwd_ex(z2.data_ptr(), rows, C, gamma.data_ptr(), beta.data_ptr(), eps, momentum,
+                                  running_mean.data_ptr(), running_var.data_ptr(), batches.data_ptr(), int(relu),
+                                  y.data_ptr() if f32 else None, bits.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                                  scratch.data_ptr(), yp.data_ptr() if planes else None, mode if planes else 0,
+                                  gstat.data_ptr() if gstat is not None else None,
+                                  id2.data_ptr() if id2 is not None else None, _lib.current_stream_ptr())
+    _lib.check(rc, "pl_bn_train_fwd_ex")
+    ctx.save_for_backward(z2, bits, mean, rstd, gamma, beta)
+    ctx.shape, ctx.link = shape, link
+    return y, yp
+
+
+def _bn_bwd(ctx, g2, gp2=None, join=False):
+    """Backward of _bn_fwd from dy = g2 [rows][C] -- join: from dy = the sum of g2 and gp2 (or None) where the join's ReLU
+    passed, which is also the identity's gradient dx.  dz is fp32 or, with a link, a carrier of its planes, range-scaled on
+    the device (link.dz_scale).  Returns (dz, dx or None, dgamma, dbeta), the last two as _pgrad2 hands them to autograd."""
+    z2, bits, mean, rstd, gamma, beta = ctx.saved_tensors
+    rows, C = z2.shape
+    dev, L, link = z2.device, _lib.lib(), ctx.link
+    dx = torch.empty_like(g2) if join else None
+    dz = torch.empty_like(z2)
+    scratch = torch.empty(L.pl_bn_train_scratch_bytes(rows, C), dtype=torch.uint8, device=dev)
+    if link is not None:
+        link.dz_scale = torch.empty(2, device=dev)
+        dzf, dzp, mode, scale = None, dz.data_ptr(), link.mode, link.dz_scale.data_ptr()
+    else:
+        dzf, dzp, mode, scale = dz.data_ptr(), None, 0, None
+    gp = gp2.data_ptr() if gp2 is not None else None
+
+    def run(dgamma, dbeta):
+        with _lib.on_device(dev):
+            if join and C >= 256:
+                # one pass writes the masked sum and takes BatchNorm-backward's column sums of it (pl_bn_join_bwd)
+                rc = L.pl_bn_join_bwd(g2.data_ptr(), gp, bits.data_ptr(), z2.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                                      gamma.data_ptr(), rows, C, dx.data_ptr(), dzf, dgamma.data_ptr(), dbeta.data_ptr(),
+                                      scratch.data_ptr(), dzp, mode, scale, _lib.current_stream_ptr())
+                _lib.check(rc, "pl_bn_join_bwd")
+                return
+            dy = g2
+            if join:
+                rc = L.pl_mask_add_by_bits(g2.data_ptr(), gp, bits.data_ptr(), rows, C, dx.data_ptr(), _lib.current_stream_ptr())
+                _lib.check(rc, "pl_mask_add_by_bits")
+                dy = dx     # (dy = dx where the join's bitmap is set: masking the masked sum again changes nothing)
+            rc = L.pl_bn_train_bwd_ex(dy.data_ptr(), bits.data_ptr(), z2.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                                      gamma.data_ptr(), rows, C, dzf, dgamma.data_ptr(), dbeta.data_ptr(), scratch.data_ptr(),
+                                      dzp, mode, scale, _lib.current_stream_ptr())
+            _lib.check(rc, "pl_bn_train_bwd_ex")
+    dgamma, dbeta = _pgrad2(gamma, beta, C, dev, run)
+    return dz, dx, dgamma, dbeta
+
+
+class _BNFn(torch.autograd.Function):
+    """BatchNorm (+ ReLU) with the output as fp32 (out_planes False) or ONLY as a carrier of its planes (True: the next op
+    is a planes convolution), and -- link given: the convolution that produced z is a planes convolution -- dz returned as a
+    carrier of its planes (PlaneLink)."""
+
     @staticmethod
-    def forward(ctx, z, gamma, beta, running_mean, running_var, batches, eps, momentum, relu):
-        shape = z.shape
-        C = shape[-1]
-        z2 = z.contiguous().reshape(-1, C)
-        rows = z2.shape[0]
-        for name, t in (("z", z2), ("gamma", gamma), ("beta", beta), ("running_mean", running_mean),
-                        ("running_var", running_var)):
+    def forward(ctx, z, gamma, beta, running_mean, running_var, batches, eps, momentum, relu, out_planes, link, mode):
+        z = z.contiguous()
+        # (callers hand this node tensors of their own making; the join below only ever sees this file's outputs)
+        for name, t in (("z", z), ("gamma", gamma), ("beta", beta), ("running_mean", running_mean), ("running_var", running_var)):
             _lib.require_device_tensor(t, name)
         _lib.require_device_tensor(batches, "num_batches_tracked", torch.int64)
-        dev, L = z2.device, _lib.lib()
-        y = torch.empty_like(z2)
-        bits = torch.empty(rows, 4 * ((C + 255) // 256), dtype=torch.int64, device=dev)
-        mean, rstd = torch.empty(C, device=dev), torch.empty(C, device=dev)
-        scratch = torch.empty(L.pl_bn_train_scratch_bytes(rows, C), dtype=torch.uint8, device=dev)
-        with _lib.on_device(dev):
-            rc = L.pl_bn_train_fwd(z2.data_ptr(), rows, C, gamma.data_ptr(), beta.data_ptr(), eps, momentum,
-                                   running_mean.data_ptr(), running_var.data_ptr(), batches.data_ptr(), int(relu),
-                                   y.data_ptr(), bits.data_ptr(), mean.data_ptr(), rstd.data_ptr(), scratch.data_ptr(),
-                                   _lib.current_stream_ptr())
-        _lib.check(rc, "pl_bn_train_fwd")
-        ctx.save_for_backward(z2, bits, mean, rstd, gamma, beta)
-        ctx.shape = shape
-        return y.reshape(shape)
+        y, yp = _bn_fwd(ctx, z, None, gamma, beta, running_mean, running_var, batches, eps, momentum, relu=relu,
+                        f32=not out_planes, planes=out_planes, link=link, mode=mode)
+        return (yp if out_planes else y).reshape(z.shape)
 
     @staticmethod
     def backward(ctx, dy):
-        z2, bits, mean, rstd, gamma, beta = ctx.saved_tensors
-        rows, C = z2.shape
-        dy2 = dy.contiguous().reshape(rows, C)
-        dev, L = z2.device, _lib.lib()
-        dz = torch.empty_like(z2)
-        scratch = torch.empty(L.pl_bn_train_scratch_bytes(rows, C), dtype=torch.uint8, device=dev)
-
-        def run(dgamma, dbeta):
-            with _lib.on_device(dev):
-                rc = L.pl_bn_train_bwd(dy2.data_ptr(), bits.data_ptr(), z2.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                       gamma.data_ptr(), rows, C, dz.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
-                                       scratch.data_ptr(), _lib.current_stream_ptr())
-            _lib.check(rc, "pl_bn_train_bwd")
-        dgamma, dbeta = _pgrad2(gamma, beta, C, dev, run)
-        return dz.reshape(ctx.shape), dgamma, dbeta, None, None, None, None, None, None
+        dz, _, dgamma, dbeta = _bn_bwd(ctx, dy.contiguous().reshape(-1, ctx.shape[-1]))
+        return dz.reshape(ctx.shape), dgamma, dbeta, None, None, None, None, None, None, None, None, None
 
 
-def batchnorm_relu_train(z, bn, relu=True):
-    """Training-mode nn.BatchNorm2d `bn` (+ ReLU) applied to an NHWC feature map z [..., C] (batch statistics over
-    every leading dimension); updates bn.running_mean / running_var / num_batches_tracked in place."""
+class _BNJoinFn(torch.autograd.Function):
+    """bn3 and the residual join of a Bottleneck in ONE pass: x = relu(bn(z) + identity) as fp32 (the next join's identity) AND
+    as a carrier of its planes (the next block's convolutions) -- bn3's output is never materialised.  backward: the masked
+    sum of the two incoming gradients IS both the identity's gradient and bn3's dy; dz leaves as a carrier of its planes
+    (link).  Resnet.py:81-91."""
+
+    @staticmethod
+    def forward(ctx, z, identity, gamma, beta, running_mean, running_var, batches, eps, momentum, link):
+        x, xp = _bn_fwd(ctx, z, identity, gamma, beta, running_mean, running_var, batches, eps, momentum, relu=True, f32=True,
+                        planes=True, link=link, mode=link.mode)
+        ctx.set_materialize_grads(False)
+        return x.reshape(z.shape), xp.reshape(z.shape)
+
+    @staticmethod
+    def backward(ctx, g, gp):
+        if g is None:
+            g, gp = gp, None
+        if g is None:
+            return (None,) * 10
+        C = ctx.shape[-1]
+        dz, dx, dgamma, dbeta = _bn_bwd(ctx, g.contiguous().reshape(-1, C),
+                                        gp.contiguous().reshape(-1, C) if gp is not None else None, join=True)
+        return dz.reshape(ctx.shape), dx.reshape(ctx.shape), dgamma, dbeta, None, None, None, None, None, None
+
+
+def _bn_state(bn):
     if bn.momentum is None:
         raise NotImplementedError("cumulative moving average (momentum=None)")
-    y = _BNReLUFn.apply(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
-                        float(bn.eps), float(bn.momentum), bool(relu))
+    return (bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, float(bn.eps), float(bn.momentum))
+
+
+def batchnorm_relu_train_planes(z, bn, relu=True, out_planes=False, link=None, mode=_lib.PL_F16X3):
+    """Training-mode nn.BatchNorm2d `bn` (+ ReLU) applied to an NHWC feature map z [..., C] (batch statistics over
+    every leading dimension); updates bn.running_mean / running_var / num_batches_tracked in place.  out_planes: the
+    output is a carrier of its operand planes (`mode`, or the link's); link: z came from a planes convolution (PlaneLink)."""
+    y = _BNFn.apply(z, *_bn_state(bn), bool(relu), bool(out_planes), link, link.mode if link is not None else mode)
     increment_version((bn.running_mean, bn.running_var, bn.num_batches_tracked))
     return y
 
 
+def batchnorm_relu_train(z, bn, relu=True):
+    """The same, fp32 in and out."""
+    return batchnorm_relu_train_planes(z, bn, relu)
+
+
+def bn_join_planes(z, identity, bn, link):
+    """relu(bn(z) + identity) -> (fp32, carrier of its planes); z came from a planes convolution (link)."""
+    x, xp = _BNJoinFn.apply(z, identity, *_bn_state(bn), link)
+    increment_version((bn.running_mean, bn.running_var, bn.num_batches_tracked))
+    return x, xp
+
+
 class _AddReLUFn(torch.autograd.Function):
+    """relu(a + b), the residual join of a Bottleneck (Resnet.py:90-91), as fp32 and -- mode given -- ALSO as a carrier of
+    its planes (the next block's 1x1 convolutions); backward: one masked pass over the SUM of the two gradients (no
+    separate add)."""
+
     @staticmethod
-    def forward(ctx, a, b):
+    def forward(ctx, a, b, mode):
         if a.shape != b.shape:
             raise ValueError("add_relu: shapes differ")
         C = a.shape[-1]
@@ -332,32 +462,45 @@ class _AddReLUFn(torch.autograd.Function):
         _lib.require_device_tensor(b2, "b")
         rows = a2.shape[0]
         out = torch.empty_like(a2)
-        bits = torch.empty(rows, 4 * ((C + 255) // 256), dtype=torch.int64, device=a2.device)
+        outp = torch.empty_like(a2) if mode is not None else None
+        bits = _bits(rows, C, a2.device)
         with _lib.on_device(a2.device):
-            rc = _lib.lib().pl_add_relu_fwd(a2.data_ptr(), b2.data_ptr(), rows, C, out.data_ptr(), bits.data_ptr(),
-                                            _lib.current_stream_ptr())
-        _lib.check(rc, "pl_add_relu_fwd")
+            rc = _lib.lib().pl_add_relu_fwd_ex(a2.data_ptr(), b2.data_ptr(), rows, C, out.data_ptr(), bits.data_ptr(),
+                                               outp.data_ptr() if outp is not None else None, mode or 0,
+                                               _lib.current_stream_ptr())
+        _lib.check(rc, "pl_add_relu_fwd_ex")
         ctx.save_for_backward(bits)
         ctx.shape = a.shape
-        return out.reshape(a.shape)
+        ctx.set_materialize_grads(False)       # an unused output's gradient arrives as None, not as a zero map
+        return out.reshape(a.shape), outp.reshape(a.shape) if outp is not None else None
 
     @staticmethod
-    def backward(ctx, g):
+    def backward(ctx, g, gp):
         (bits,) = ctx.saved_tensors
         C = ctx.shape[-1]
+        if g is None:
+            g, gp = gp, None
+        if g is None:
+            return None, None, None
         g2 = g.contiguous().reshape(-1, C)
+        gp2 = gp.contiguous().reshape(-1, C) if gp is not None else None
         dx = torch.empty_like(g2)
         with _lib.on_device(g2.device):
-            rc = _lib.lib().pl_mask_by_bits(g2.data_ptr(), bits.data_ptr(), g2.shape[0], C, dx.data_ptr(),
-                                            _lib.current_stream_ptr())
-        _lib.check(rc, "pl_mask_by_bits")
+            rc = _lib.lib().pl_mask_add_by_bits(g2.data_ptr(), gp2.data_ptr() if gp2 is not None else None, bits.data_ptr(),
+                                                g2.shape[0], C, dx.data_ptr(), _lib.current_stream_ptr())
+        _lib.check(rc, "pl_mask_add_by_bits")
         dx = dx.reshape(ctx.shape)
-        return dx, dx
+        return dx, dx, None
 
 
 def add_relu(a, b):
-    """relu(a + b), differentiable: the residual join of a Bottleneck (Resnet.py:90-91)."""
-    return _AddReLUFn.apply(a, b)
+    """relu(a + b), differentiable."""
+    return _AddReLUFn.apply(a, b, None)[0]
+
+
+def add_relu_planes(a, b, mode=_lib.PL_F16X3):
+    """(relu(a + b), carrier of its planes)."""
+    return _AddReLUFn.apply(a, b, mode)
 
 
 class _MaxPoolFn(torch.autograd.Function):
@@ -422,37 +565,6 @@ def deconv4x4s2_nhwc_autograd(x, weight_iohw, arith="bf16x6"):
     return _DeconvFn.apply(x.contiguous(), weight_iohw, arith)
 
 
-class _ConvBiasFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, w_ohwi, bias, stride, padding, arith):
-        ctx.save_for_backward(x, w_ohwi)
-        ctx.geom = (stride, padding, arith)
-        return conv2d_nhwc(x, w_ohwi, stride, padding, bias=bias, arith=arith)
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, w = ctx.saved_tensors
-        stride, padding, arith = ctx.geom
-        dy = dy.contiguous()
-        dx = conv2d_nhwc_dgrad(dy, w, x.shape[1:3], stride, padding, arith) if ctx.needs_input_grad[0] else None
-        dw = conv2d_nhwc_wgrad(x, dy, w.shape[1], stride, padding, arith) if ctx.needs_input_grad[1] else None
-        db = None
-        if ctx.needs_input_grad[2]:
-            C = dy.shape[-1]
-            rows = dy.numel() // C
-            db = torch.empty(C, dtype=torch.float32, device=dy.device)
-            L = _lib.lib()
-            scratch = torch.empty(L.pl_colsum_scratch_bytes(rows, C), dtype=torch.uint8, device=dy.device)
-            with _lib.on_device(dy.device):
-                rc = L.pl_colsum(dy.data_ptr(), rows, C, db.data_ptr(), scratch.data_ptr(), _lib.current_stream_ptr())
-            _lib.check(rc, "pl_colsum")
-        return dx, dw, db, None, None, None
-
-
-def conv2d_bias_nhwc_autograd(x, w_ohwi, bias, stride=1, padding=0, arith="bf16x6"):
-    return _ConvBiasFn.apply(x, w_ohwi, bias, stride, padding, arith)
-
-
 class _ToNCHWFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
@@ -474,7 +586,7 @@ def nhwc_to_nchw_autograd(x):
 
 
 # ---------------------------------------------------------------------------------------------
-# 1x1 convolutions on the planes GEMM (compute_dtype "f16x3"): the lifter's round-2 design on the conv path.
+# Convolutions on the planes GEMM (compute_dtype "f16x3" / "bf16p"): the lifter's round-2 design on the conv path.
 #
 # A 1x1 convolution over an NHWC map IS the GEMM [pixels][Cin] x [Cout][Cin]^T.  Its operands travel as 16-bit operand
 # planes written by the kernel that produces the tensor (BatchNorm apply, the residual join, BatchNorm backward), and the
@@ -482,7 +594,7 @@ def nhwc_to_nchw_autograd(x):
 # work in the loop.  Between autograd nodes a tensor that exists ONLY as planes travels in a float32-typed "carrier" of
 # the logical shape: two fp16 planes are exactly four bytes per element, so the carrier has the size autograd expects of
 # the tensor (or of its gradient) while its bytes are [2][n] fp16.  Carriers are only ever handed to the functions below
-# (ResNet._forward_train wires producer to consumer directly); every gradient that reaches torch code is real fp32.
+# (backbone.py wires producer to consumer directly); every gradient that reaches torch code is real fp32.
 #   reference: phase4_joined/Resnet.py:56-63, 65-93 (the Bottleneck's conv1 / conv3 / downsample and their autograd)
 # ---------------------------------------------------------------------------------------------
 ACT_PLANE_SCALE = 1.0 / 64   # csrc/pl_internal.h kConvActPlaneScale (pl_conv_act_plane_scale(): checked by the host-logic test)
@@ -503,7 +615,6 @@ class PlaneLink:
 def _planes_of_strided(base, dims, strides, offset, scale, mode):
     """Planes of the strided view (dims, signed element strides, element offset) of `base` -- pl_planes_split_strided: the layout
     change and the split in one launch."""
-    import ctypes
     nd = len(dims)
     d4 = (ctypes.c_int64 * 4)(*((1,) * (4 - nd) + tuple(int(v) for v in dims)))
     s4 = (ctypes.c_int64 * 4)(*((0,) * (4 - nd) + tuple(int(v) for v in strides)))
@@ -546,17 +657,19 @@ def _stat_buffer(rows, cols, dev):
 
 
 def _gemm_planes_raw(layout, a, a_rows_cols, b, b_rows_cols, M, N, K, out_scale, dyn_inv=None, mode=_lib.PL_F16X3, stat=None,
-                     out=None):
-    """C [M][N] fp32 from two carriers (planes of row-major matrices a_rows_cols / b_rows_cols); out: where to put it."""
+                     out=None, bias=None):
+    """C [M][N] fp32 from two carriers (planes of row-major matrices a_rows_cols / b_rows_cols); out: where to put it.
+    With a bias the launch is never split over K (no slabs: a problem the library would split is its error to report)."""
     L = _lib.lib()
     dev = a.device
     C = torch.empty(M, N, device=dev) if out is None else out
-    splits = L.pl_gemm_planes_splits(M, N, K)
+    splits = L.pl_gemm_planes_splits(M, N, K) if bias is None else 1
     slabs = torch.empty(splits * M * N, device=dev) if splits > 1 else None
     with _lib.on_device(dev):
         rc = L.pl_gemm_planes_raw(layout, mode, a.data_ptr(), a_rows_cols[0] * a_rows_cols[1], a_rows_cols[1],
                                   b.data_ptr(), b_rows_cols[0] * b_rows_cols[1], b_rows_cols[1], C.data_ptr(), M, N, K,
-                                  None, float(out_scale), dyn_inv.data_ptr() if dyn_inv is not None else None,
+                                  bias.data_ptr() if bias is not None else None, float(out_scale),
+                                  dyn_inv.data_ptr() if dyn_inv is not None else None,
                                   slabs.data_ptr() if slabs is not None else None,
                                   stat.data_ptr() if stat is not None else None, _lib.current_stream_ptr())
     _lib.check(rc, "pl_gemm_planes_raw")
@@ -570,37 +683,41 @@ def planes_conv_supported(rows, cin, cout):
 
 
 class _Conv1x1PlanesFn(torch.autograd.Function):
-    """z = x W^T for a 1x1 convolution: xp = carrier of x's planes [rows][Cin], w [Cout][Cin] fp32 -> z [rows][Cout] fp32.
-    backward takes dz as a carrier (written by the BatchNorm behind this convolution, see PlaneLink)."""
+    """z = x W^T (+ bias, or None) for a 1x1 convolution: xp = carrier of x's planes [rows][Cin], w [Cout][Cin] fp32 ->
+    z [rows][Cout] fp32, and the epilogue's BatchNorm statistics of z or None.  backward takes dz as a carrier (PlaneLink:
+    written by the BatchNorm behind this convolution or, for the head's final convolution with its bias -- Model.py:66-69 --
+    by the soft-argmax backward, heads.py): data gradient NT on W^T, weight gradient TN over the pixels, bias gradient =
+    column sums of the planes."""
 
     @staticmethod
-    def forward(ctx, xp, wparam, link):
+    def forward(ctx, xp, wparam, bias, link):
         rows, cin = xp.shape
         cout = wparam.shape[0]
         w = wparam.float().reshape(cout, cin)
         wp = _planes_of(w, WEIGHT_PLANE_SCALE, link.mode)
         # the BatchNorm behind this convolution reads the epilogue's statistics (no pass over z) -- unless the GEMM is split over K
-        stat = (_stat_buffer(rows, cout, xp.device) if _lib.lib().pl_gemm_planes_splits(rows, cout, cin) == 1
-                else torch.empty(0, device=xp.device))
+        stat = None
+        if bias is None and _lib.lib().pl_gemm_planes_splits(rows, cout, cin) == 1:
+            stat = _stat_buffer(rows, cout, xp.device)
+            ctx.mark_non_differentiable(stat)
         z = _gemm_planes_raw(0, xp, (rows, cin), wp, (cout, cin), rows, cout, cin,
-                             1.0 / (ACT_PLANE_SCALE * WEIGHT_PLANE_SCALE), None, link.mode, stat if stat.numel() else None)
-        ctx.save_for_backward(xp, wparam)
+                             1.0 / (ACT_PLANE_SCALE * WEIGHT_PLANE_SCALE), None, link.mode, stat, bias=bias)
+        ctx.save_for_backward(xp, wparam, bias)
         ctx.link = link
-        ctx.mark_non_differentiable(stat)
         ctx.set_materialize_grads(False)       # (no zero tensor the size of `stat` per backward)
         return z, stat
 
     @staticmethod
     def backward(ctx, dzp, _gstat):
         if dzp is None:
-            return None, None, None
-        xp, wparam = ctx.saved_tensors
+            return None, None, None, None
+        xp, wparam, bparam = ctx.saved_tensors
         rows, cin = xp.shape
         cout = wparam.shape[0]
         w = wparam.detach().float().reshape(cout, cin)
         dzp = dzp.contiguous()
         inv, mode = ctx.link.dz_scale[1:], ctx.link.mode   # 1 / S of the dz planes (device scalar; fp16 planes only)
-        dx = dw = None
+        dx = dw = db = None
         if ctx.needs_input_grad[0]:
             wtp = _planes_of(w.t(), WEIGHT_PLANE_SCALE, mode)  # [Cin][Cout]: the data gradient is NT on W^T
             dx = _gemm_planes_raw(0, dzp, (rows, cout), wtp, (cin, cout), rows, cin, cout, 1.0 / WEIGHT_PLANE_SCALE, inv, mode)
@@ -610,132 +727,31 @@ class _Conv1x1PlanesFn(torch.autograd.Function):
                 r = _gemm_planes_raw(2, dzp, (rows, cout), xp, (rows, cin), cout, cin, rows, 1.0 / ACT_PLANE_SCALE, inv, mode, out=o2)
                 return r.reshape(wparam.shape)
             dw = _pgrad(wparam, make)
-        return dx, dw, None
+        if ctx.needs_input_grad[2]:
+            L = _lib.lib()
+
+            def make_b(out):
+                b = torch.empty(cout, device=dzp.device) if out is None else out
+                scratch = torch.empty(L.pl_colsum_scratch_bytes(rows, cout), dtype=torch.uint8, device=dzp.device)
+                with _lib.on_device(dzp.device):
+                    rc = L.pl_colsum_planes(dzp.data_ptr(), mode, rows, cout, inv.data_ptr(), b.data_ptr(), scratch.data_ptr(),
+                                            _lib.current_stream_ptr())
+                _lib.check(rc, "pl_colsum_planes")
+                return b
+            db = _pgrad(bparam, make_b)
+        return dx, dw, db, None
 
 
-def conv1x1_planes(xp, weight_oihw, link):
-    """xp: carrier [B, H, W, Cin] of the input's planes; weight: the nn.Conv2d parameter [Cout][Cin][1][1]."""
+def conv1x1_bias_planes(xp, weight_oihw, bias, link):
+    """xp: carrier [B, H, W, Cin] of the input's planes; weight, bias: the nn.Conv2d parameters [Cout][Cin][1][1], [Cout]."""
     shape = xp.shape
     cout, cin = weight_oihw.shape[0], weight_oihw.shape[1]
-    z, stat = _Conv1x1PlanesFn.apply(xp.reshape(-1, cin), weight_oihw, link)
-    link.stat = stat if stat.numel() else None
+    z, link.stat = _Conv1x1PlanesFn.apply(xp.reshape(-1, cin), weight_oihw, bias, link)
     return z.reshape(*shape[:-1], cout)
 
 
-class _BNPlanesFn(torch.autograd.Function):
-    """_BNReLUFn with the output as fp32 (out_planes False) or ONLY as a carrier of its planes (True: the next op is a
-    planes convolution), and -- link given: the convolution that produced z is a planes convolution -- dz returned as a
-    carrier of its planes, range-scaled on the device (link.dz_scale)."""
-
-    @staticmethod
-    def forward(ctx, z, gamma, beta, running_mean, running_var, batches, eps, momentum, relu, out_planes, link, mode):
-        shape = z.shape
-        C = shape[-1]
-        z2 = z.contiguous().reshape(-1, C)
-        rows = z2.shape[0]
-        for name, t in (("z", z2), ("gamma", gamma), ("beta", beta), ("running_mean", running_mean),
-                        ("running_var", running_var)):
-            _lib.require_device_tensor(t, name)
-        _lib.require_device_tensor(batches, "num_batches_tracked", torch.int64)
-        dev, L = z2.device, _lib.lib()
-        y = torch.empty_like(z2)                      # fp32 values, or the carrier
-        bits = torch.empty(rows, 4 * ((C + 255) // 256), dtype=torch.int64, device=dev)
-        mean, rstd = torch.empty(C, device=dev), torch.empty(C, device=dev)
-        scratch = torch.empty(L.pl_bn_train_scratch_bytes(rows, C), dtype=torch.uint8, device=dev)
-        gstat = link.stat if link is not None else None
-        if link is not None:
-            link.stat = None
-        with _lib.on_device(dev):
-            rc = L.pl_bn_train_fwd_ex(z2.data_ptr(), rows, C, gamma.data_ptr(), beta.data_ptr(), eps, momentum,
-                                      running_mean.data_ptr(), running_var.data_ptr(), batches.data_ptr(), int(relu),
-                                      None if out_planes else y.data_ptr(), bits.data_ptr(), mean.data_ptr(),
-                                      rstd.data_ptr(), scratch.data_ptr(), y.data_ptr() if out_planes else None,
-                                      mode, gstat.data_ptr() if gstat is not None else None, None, _lib.current_stream_ptr())
-        _lib.check(rc, "pl_bn_train_fwd_ex")
-        ctx.save_for_backward(z2, bits, mean, rstd, gamma, beta)
-        ctx.shape, ctx.link = shape, link
-        return y.reshape(shape)
-
-    @staticmethod
-    def backward(ctx, dy):
-        z2, bits, mean, rstd, gamma, beta = ctx.saved_tensors
-        rows, C = z2.shape
-        dy2 = dy.contiguous().reshape(rows, C)
-        dev, L = z2.device, _lib.lib()
-        dz = torch.empty_like(z2)
-        scratch = torch.empty(L.pl_bn_train_scratch_bytes(rows, C), dtype=torch.uint8, device=dev)
-        link = ctx.link
-        if link is not None:
-            link.dz_scale = torch.empty(2, device=dev)
-
-        def run(dgamma, dbeta):
-            with _lib.on_device(dev):
-                rc = L.pl_bn_train_bwd_ex(dy2.data_ptr(), bits.data_ptr(), z2.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                          gamma.data_ptr(), rows, C, None if link is not None else dz.data_ptr(),
-                                          dgamma.data_ptr(), dbeta.data_ptr(), scratch.data_ptr(),
-                                          dz.data_ptr() if link is not None else None,
-                                          link.mode if link is not None else _lib.PL_F16X3,
-                                          link.dz_scale.data_ptr() if link is not None else None, _lib.current_stream_ptr())
-            _lib.check(rc, "pl_bn_train_bwd_ex")
-        dgamma, dbeta = _pgrad2(gamma, beta, C, dev, run)
-        return dz.reshape(ctx.shape), dgamma, dbeta, None, None, None, None, None, None, None, None, None
-
-
-def batchnorm_relu_train_planes(z, bn, relu=True, out_planes=False, link=None, mode=_lib.PL_F16X3):
-    if bn.momentum is None:
-        raise NotImplementedError("cumulative moving average (momentum=None)")
-    y = _BNPlanesFn.apply(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
-                          float(bn.eps), float(bn.momentum), bool(relu), bool(out_planes), link,
-                          link.mode if link is not None else mode)
-    increment_version((bn.running_mean, bn.running_var, bn.num_batches_tracked))
-    return y
-
-
-class _AddReLUPlanesFn(torch.autograd.Function):
-    """relu(a + b) as fp32 (the next join's identity) AND as a carrier of its planes (the next block's 1x1
-    convolutions); backward: one masked pass over the SUM of the two gradients (no separate add)."""
-
-    @staticmethod
-    def forward(ctx, a, b, mode):
-        if a.shape != b.shape:
-            raise ValueError("add_relu: shapes differ")
-        C = a.shape[-1]
-        a2, b2 = a.contiguous().reshape(-1, C), b.contiguous().reshape(-1, C)
-        _lib.require_device_tensor(a2, "a")
-        _lib.require_device_tensor(b2, "b")
-        rows = a2.shape[0]
-        out, outp = torch.empty_like(a2), torch.empty_like(a2)
-        bits = torch.empty(rows, 4 * ((C + 255) // 256), dtype=torch.int64, device=a2.device)
-        with _lib.on_device(a2.device):
-            rc = _lib.lib().pl_add_relu_fwd_ex(a2.data_ptr(), b2.data_ptr(), rows, C, out.data_ptr(), bits.data_ptr(),
-                                               outp.data_ptr(), mode, _lib.current_stream_ptr())
-        _lib.check(rc, "pl_add_relu_fwd_ex")
-        ctx.save_for_backward(bits)
-        ctx.shape = a.shape
-        ctx.set_materialize_grads(False)       # an unused output's gradient arrives as None, not as a zero map
-        return out.reshape(a.shape), outp.reshape(a.shape)
-
-    @staticmethod
-    def backward(ctx, g, gp):
-        (bits,) = ctx.saved_tensors
-        C = ctx.shape[-1]
-        if g is None:
-            g, gp = gp, None
-        if g is None:
-            return None, None, None
-        g2 = g.contiguous().reshape(-1, C)
-        gp2 = gp.contiguous().reshape(-1, C) if gp is not None else None
-        dx = torch.empty_like(g2)
-        with _lib.on_device(g2.device):
-            rc = _lib.lib().pl_mask_add_by_bits(g2.data_ptr(), gp2.data_ptr() if gp2 is not None else None, bits.data_ptr(),
-                                                g2.shape[0], C, dx.data_ptr(), _lib.current_stream_ptr())
-        _lib.check(rc, "pl_mask_add_by_bits")
-        dx = dx.reshape(ctx.shape)
-        return dx, dx, None
-
-
-def add_relu_planes(a, b, mode=_lib.PL_F16X3):
-    return _AddReLUPlanesFn.apply(a, b, mode)
+def conv1x1_planes(xp, weight_oihw, link):
+    return conv1x1_bias_planes(xp, weight_oihw, None, link)
 
 
 class _ToPlanesFn(torch.autograd.Function):
@@ -754,13 +770,18 @@ def to_planes(x, mode=_lib.PL_F16X3):
     return _ToPlanesFn.apply(x, mode)
 
 
+def _conv_geom(H, W, kh, kw, stride, pad):
+    """stride: s or (sh, sw); pad: p or (above = below, left, right) -> (sh, sw, ph, pw, pwr, Ho, Wo)."""
+    sh, sw = stride if isinstance(stride, tuple) else (stride, stride)
+    ph, pw, pwr = pad if isinstance(pad, tuple) else (pad, pad, pad)
+    return sh, sw, ph, pw, pwr, (H + 2 * ph - kh) // sh + 1, (W + pw + pwr - kw) // sw + 1
+
+
 def _conv_planes_fwd(xp, x_shape, wp, w_shape, stride, pad, out_scale, dyn_inv=None, mode=_lib.PL_F16X3, stat=None):
     """pl_conv2d_planes_fwd on carriers: xp planes of x [B][H][W][Cin], wp planes of the OHWI kernel w_shape."""
     B, H, W, cin = x_shape
     cout, kh, kw, _ = w_shape
-    sh, sw = stride if isinstance(stride, tuple) else (stride, stride)
-    ph, pw, pwr = pad if isinstance(pad, tuple) else (pad, pad, pad)          # (above = below, left, right)
-    ho, wo = (H + 2 * ph - kh) // sh + 1, (W + pw + pwr - kw) // sw + 1
+    sh, sw, ph, pw, pwr, ho, wo = _conv_geom(H, W, kh, kw, stride, pad)
     y = torch.empty(B, ho, wo, cout, device=xp.device)
     with _lib.on_device(xp.device):
         rc = _lib.lib().pl_conv2d_planes_fwd_hw(mode, xp.data_ptr(), B * H * W * cin, B, H, W, cin, wp.data_ptr(),
@@ -769,6 +790,23 @@ def _conv_planes_fwd(xp, x_shape, wp, w_shape, stride, pad, out_scale, dyn_inv=N
                                                 stat.data_ptr() if stat is not None else None, _lib.current_stream_ptr())
     _lib.check(rc, "pl_conv2d_planes_fwd")
     return y
+
+
+def _planes_wgrad(dzp, xp, x_shape, cout, kh, kw, stride, pad, inv, mode):
+    """Weight gradient [cout][kh][kw][cin] (OHWI, fp32) of a planes convolution: the TN GEMM over the output pixels of the dz
+    planes [B][Ho][Wo][cout] with the planes of x (x_shape) gathered; split over K into slabs where the library says so."""
+    B, H, W, cin = x_shape
+    sh, sw, ph, pw, pwr, ho, wo = _conv_geom(H, W, kh, kw, stride, pad)
+    L = _lib.lib()
+    splits = L.pl_gemm_planes_splits(cout, kh * kw * cin, B * ho * wo)
+    slabs = torch.empty(splits * cout * kh * kw * cin, device=dzp.device) if splits > 1 else None
+    dw = torch.empty(cout, kh, kw, cin, device=dzp.device)
+    with _lib.on_device(dzp.device):
+        rc = L.pl_conv2d_planes_wgrad_hw(mode, dzp.data_ptr(), B * ho * wo * cout, xp.data_ptr(), B * H * W * cin, B, H, W, cin,
+                                         cout, kh, kw, sh, sw, ph, pw, pwr, dw.data_ptr(), 1.0 / ACT_PLANE_SCALE, inv.data_ptr(),
+                                         slabs.data_ptr() if slabs is not None else None, _lib.current_stream_ptr())
+    _lib.check(rc, "pl_conv2d_planes_wgrad_hw")
+    return dw
 
 
 class _PlanesTwinFn(torch.autograd.Function):
@@ -804,8 +842,8 @@ class _ConvKxKPlanesFn(torch.autograd.Function):
         wp = _planes_of(w, WEIGHT_PLANE_SCALE, link.mode)
         B, H, W, _ = xp.shape
         cout, kh, kw, _ = w.shape
-        rows = B * ((H + 2 * pad - kh) // stride + 1) * ((W + 2 * pad - kw) // stride + 1)
-        stat = _stat_buffer(rows, cout, xp.device)
+        ho, wo = _conv_geom(H, W, kh, kw, stride, pad)[5:]
+        stat = _stat_buffer(B * ho * wo, cout, xp.device)
         z = _conv_planes_fwd(xp, xp.shape, wp, w.shape, stride, pad, 1.0 / (ACT_PLANE_SCALE * WEIGHT_PLANE_SCALE), None, link.mode,
                              stat)
         ctx.save_for_backward(xp, wparam)
@@ -865,18 +903,7 @@ class _ConvKxKPlanesFn(torch.autograd.Function):
                 src, shape = up.reshape(-1).view(torch.float32).reshape(B, hu, wu, cout), (B, hu, wu, cout)
                 dx = _conv_planes_fwd(src, shape, wf, (cin, kh, kw, cout), 1, kh - 1 - pad, 1.0 / WEIGHT_PLANE_SCALE, inv, mode)
         if ctx.needs_input_grad[1]:
-            L = _lib.lib()
-            n = cout * kh * kw * cin
-            splits = L.pl_gemm_planes_splits(cout, kh * kw * cin, B * ho * wo)
-            slabs = torch.empty(splits * n, device=dzp.device) if splits > 1 else None
-            dw = torch.empty(cout, kh, kw, cin, device=dzp.device)
-            with _lib.on_device(dzp.device):
-                rc = L.pl_conv2d_planes_wgrad(mode, dzp.data_ptr(), B * ho * wo * cout, xp.data_ptr(), B * H * W * cin,
-                                              B, H, W, cin, cout, kh, kw, stride, pad, dw.data_ptr(), 1.0 / ACT_PLANE_SCALE,
-                                              inv.data_ptr(), slabs.data_ptr() if slabs is not None else None,
-                                              _lib.current_stream_ptr())
-            _lib.check(rc, "pl_conv2d_planes_wgrad")
-            dw_ohwi = dw
+            dw_ohwi = _planes_wgrad(dzp, xp, xp.shape, cout, kh, kw, stride, pad, inv, mode)
             dw = _pgrad(wparam, lambda out: _oihw_from_ohwi(dw_ohwi, out))
         return dx, dw, None, None, None
 
@@ -934,20 +961,10 @@ class _StemPlanesFn(torch.autograd.Function):
         if dzp is None or not ctx.needs_input_grad[1]:
             return None, None, None
         xp, wparam = ctx.saved_tensors
-        B, H, W2, _ = xp.shape
-        _, ho, wo, cout = dzp.shape
+        cout = dzp.shape[3]
         dzp = dzp.contiguous()
         inv, mode = ctx.link.dz_scale[1:], ctx.link.mode
-        L = _lib.lib()
-        n = cout * 7 * 4 * 8
-        splits = L.pl_gemm_planes_splits(cout, 7 * 4 * 8, B * ho * wo)
-        slabs = torch.empty(splits * n, device=dzp.device) if splits > 1 else None
-        dwp = torch.empty(cout, 7, 8, 4, device=dzp.device)
-        with _lib.on_device(dzp.device):
-            rc = L.pl_conv2d_planes_wgrad_hw(mode, dzp.data_ptr(), B * ho * wo * cout, xp.data_ptr(), B * H * W2 * 8, B, H, W2, 8,
-                                             cout, 7, 4, 2, 1, 3, 2, 1, dwp.data_ptr(), 1.0 / ACT_PLANE_SCALE, inv.data_ptr(),
-                                             slabs.data_ptr() if slabs is not None else None, _lib.current_stream_ptr())
-        _lib.check(rc, "pl_conv2d_planes_wgrad_hw")
+        dwp = _planes_wgrad(dzp, xp, xp.shape, cout, 7, 4, (2, 1), (3, 2, 1), inv, mode).reshape(cout, 7, 8, 4)
 
         def make(out):
             g = dwp[:, :, 1:, :3].permute(0, 3, 1, 2)              # the 147 real taps, as OIHW
@@ -1018,16 +1035,7 @@ class _DeconvPlanesFn(torch.autograd.Function):
             wc = _planes_of(weight.float().permute(0, 2, 3, 1), WEIGHT_PLANE_SCALE, mode)
             dx = _conv_planes_fwd(dyp, (B, 2 * H, 2 * W, cout), wc, (cin, 4, 4, cout), 2, 1, 1.0 / WEIGHT_PLANE_SCALE, inv, mode)
         if ctx.needs_input_grad[1]:       # wgrad of C: "output gradient" x [B][H][W][Cin], gathered input dy -> [Cin][4][4][Cout]
-            L = _lib.lib()
-            n = cin * 16 * cout
-            splits = L.pl_gemm_planes_splits(cin, 16 * cout, B * H * W)
-            slabs = torch.empty(splits * n, device=dyp.device) if splits > 1 else None
-            dwc = torch.empty(cin, 4, 4, cout, device=dyp.device)
-            with _lib.on_device(dyp.device):
-                rc = L.pl_conv2d_planes_wgrad(mode, xp.data_ptr(), xp.numel(), dyp.data_ptr(), dyp.numel(), B, 2 * H, 2 * W,
-                                              cout, cin, 4, 4, 2, 1, dwc.data_ptr(), 1.0 / ACT_PLANE_SCALE, inv.data_ptr(),
-                                              slabs.data_ptr() if slabs is not None else None, _lib.current_stream_ptr())
-            _lib.check(rc, "pl_conv2d_planes_wgrad")
+            dwc = _planes_wgrad(xp, dyp, (B, 2 * H, 2 * W, cout), cin, 4, 4, 2, 1, inv, mode)
             dw = _pgrad(weight, lambda out: _oihw_from_ohwi(dwc, out))      # [Cin][4][4][Cout] -> [Cin][Cout][4][4]
         return dx, dw, None
 
@@ -1039,70 +1047,6 @@ def deconv4x4s2_planes(xp, weight_iohw, link):
 def planes_deconv_supported(B, H, W, cin, cout):
     return (cin % 32 == 0 and cout % 32 == 0 and (B * H * W) % 32 == 0 and
             max(B * H * W * cin, B * 4 * H * W * cout) * 4 < (1 << 31))
-
-
-class _ConvBiasPlanesFn(torch.autograd.Function):
-    """The head's final 1x1 convolution with bias (Model.py:66-69) on the planes GEMM: xp carrier [rows][Cin], w [Cout][Cin],
-    bias [Cout] -> logits [rows][Cout] fp32.  backward takes dlogits as a carrier written by the soft-argmax backward
-    (heads.py, PlaneLink): data gradient NT on W^T, weight gradient TN over the pixels, bias gradient = column sums of the
-    planes."""
-
-    @staticmethod
-    def forward(ctx, xp, wparam, bias, link):
-        rows, cin = xp.shape
-        cout = wparam.shape[0]
-        w = wparam.float().reshape(cout, cin)
-        mode = link.mode
-        wp = _planes_of(w, WEIGHT_PLANE_SCALE, mode)
-        L = _lib.lib()
-        y = torch.empty(rows, cout, device=xp.device)
-        with _lib.on_device(xp.device):
-            rc = L.pl_gemm_planes_raw(0, mode, xp.data_ptr(), rows * cin, cin, wp.data_ptr(), cout * cin, cin, y.data_ptr(), rows,
-                                      cout, cin, bias.data_ptr(), 1.0 / (ACT_PLANE_SCALE * WEIGHT_PLANE_SCALE), None, None, None,
-                                      _lib.current_stream_ptr())
-        _lib.check(rc, "pl_gemm_planes_raw")
-        ctx.save_for_backward(xp, wparam, bias)
-        ctx.link = link
-        return y
-
-    @staticmethod
-    def backward(ctx, dyp):
-        xp, wparam, bparam = ctx.saved_tensors
-        rows, cin = xp.shape
-        cout = wparam.shape[0]
-        w = wparam.detach().float().reshape(cout, cin)
-        dyp = dyp.contiguous()
-        inv, mode = ctx.link.dz_scale[1:], ctx.link.mode
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            wtp = _planes_of(w.t(), WEIGHT_PLANE_SCALE, mode)
-            dx = _gemm_planes_raw(0, dyp, (rows, cout), wtp, (cin, cout), rows, cin, cout, 1.0 / WEIGHT_PLANE_SCALE, inv, mode)
-        if ctx.needs_input_grad[1]:
-            def make_w(out):
-                o2 = out.reshape(cout, cin) if out is not None else None
-                r = _gemm_planes_raw(2, dyp, (rows, cout), xp, (rows, cin), cout, cin, rows, 1.0 / ACT_PLANE_SCALE, inv, mode, out=o2)
-                return r.reshape(wparam.shape)
-            dw = _pgrad(wparam, make_w)
-        if ctx.needs_input_grad[2]:
-            L = _lib.lib()
-
-            def make_b(out):
-                b = torch.empty(cout, device=dyp.device) if out is None else out
-                scratch = torch.empty(L.pl_colsum_scratch_bytes(rows, cout), dtype=torch.uint8, device=dyp.device)
-                with _lib.on_device(dyp.device):
-                    rc = L.pl_colsum_planes(dyp.data_ptr(), mode, rows, cout, inv.data_ptr(), b.data_ptr(), scratch.data_ptr(),
-                                            _lib.current_stream_ptr())
-                _lib.check(rc, "pl_colsum_planes")
-                return b
-            db = _pgrad(bparam, make_b)
-        return dx, dw, db, None
-
-
-def conv1x1_bias_planes(xp, weight_oihw, bias, link):
-    shape = xp.shape
-    cout, cin = weight_oihw.shape[0], weight_oihw.shape[1]
-    y = _ConvBiasPlanesFn.apply(xp.reshape(-1, cin), weight_oihw, bias, link)
-    return y.reshape(*shape[:-1], cout)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1123,12 +1067,9 @@ def conv2d_planes_eval(xp, wp, w_shape, stride=1, padding=0, scale=None, shift=N
                        want_f32=True, want_planes=False, mode=_lib.PL_F16X3):
     """conv2d_nhwc with the input as a carrier of its planes [B,H,W,Cin] and the OHWI kernel's planes wp (w_shape):
     returns (y fp32 or None, carrier of y's planes or None)."""
-    import ctypes
     B, H, W, cin = xp.shape
     cout, kh, kw, _ = w_shape
-    sh, sw = stride if isinstance(stride, tuple) else (stride, stride)
-    ph, pw, pwr = padding if isinstance(padding, tuple) else (padding, padding, padding)     # (above = below, left, right)
-    ho, wo = (H + 2 * ph - kh) // sh + 1, (W + pw + pwr - kw) // sw + 1
+    sh, sw, ph, pw, pwr, ho, wo = _conv_geom(H, W, kh, kw, stride, padding)
     y = torch.empty(B, ho, wo, cout, device=xp.device) if want_f32 else None
     yp = torch.empty(B, ho, wo, cout, device=xp.device) if want_planes else None
     opt = [_opt(scale, "scale", cout), _opt(shift, "shift", cout), _opt(bias, "bias", cout),
@@ -1146,7 +1087,6 @@ def conv2d_planes_eval(xp, wp, w_shape, stride=1, padding=0, scale=None, shift=N
 
 def deconv_planes_eval(xp, wsubp, cout, scale=None, shift=None, relu=0, want_f32=True, want_planes=False, mode=_lib.PL_F16X3):
     """deconv4x4s2_nhwc the same way: wsubp = planes of deconv_subkernels(weight)."""
-    import ctypes
     B, H, W, cin = xp.shape
     y = torch.empty(B, 2 * H, 2 * W, cout, device=xp.device) if want_f32 else None
     yp = torch.empty(B, 2 * H, 2 * W, cout, device=xp.device) if want_planes else None
@@ -1158,81 +1098,3 @@ def deconv_planes_eval(xp, wsubp, cout, scale=None, shift=None, relu=0, want_f32
                                                      _lib.current_stream_ptr())
     _lib.check(rc, "pl_deconv4x4s2_planes_fwd_ep")
     return y, yp
-
-
-
-class _BNJoinPlanesFn(torch.autograd.Function):
-    """bn3 and the residual join of a Bottleneck in ONE pass: x = relu(bn(z) + identity) as fp32 (the next join's identity) AND
-    as a carrier of its planes (the next block's convolutions) -- bn3's output is never materialised.  backward: the masked
-    sum of the two incoming gradients (pl_mask_add_by_bits) IS both the identity's gradient and bn3's dy; dz leaves as a
-    carrier of its planes (link).  Resnet.py:81-91."""
-
-    @staticmethod
-    def forward(ctx, z, identity, gamma, beta, running_mean, running_var, batches, eps, momentum, link):
-        shape = z.shape
-        C = shape[-1]
-        z2, id2 = z.contiguous().reshape(-1, C), identity.contiguous().reshape(-1, C)
-        rows = z2.shape[0]
-        dev, L = z2.device, _lib.lib()
-        x, xp = torch.empty_like(z2), torch.empty_like(z2)
-        bits = torch.empty(rows, 4 * ((C + 255) // 256), dtype=torch.int64, device=dev)
-        mean, rstd = torch.empty(C, device=dev), torch.empty(C, device=dev)
-        scratch = torch.empty(L.pl_bn_train_scratch_bytes(rows, C), dtype=torch.uint8, device=dev)
-        gstat, link.stat = link.stat, None
-        with _lib.on_device(dev):
-            rc = L.pl_bn_train_fwd_ex(z2.data_ptr(), rows, C, gamma.data_ptr(), beta.data_ptr(), eps, momentum,
-                                      running_mean.data_ptr(), running_var.data_ptr(), batches.data_ptr(), 1, x.data_ptr(),
-                                      bits.data_ptr(), mean.data_ptr(), rstd.data_ptr(), scratch.data_ptr(), xp.data_ptr(),
-                                      link.mode, gstat.data_ptr() if gstat is not None else None, id2.data_ptr(),
-                                      _lib.current_stream_ptr())
-        _lib.check(rc, "pl_bn_train_fwd_ex")
-        ctx.save_for_backward(z2, bits, mean, rstd, gamma, beta)
-        ctx.shape, ctx.link = shape, link
-        ctx.set_materialize_grads(False)
-        return x.reshape(shape), xp.reshape(shape)
-
-    @staticmethod
-    def backward(ctx, g, gp):
-        z2, bits, mean, rstd, gamma, beta = ctx.saved_tensors
-        rows, C = z2.shape
-        dev, L, link = z2.device, _lib.lib(), ctx.link
-        if g is None:
-            g, gp = gp, None
-        if g is None:
-            return (None,) * 10
-        g2 = g.contiguous().reshape(rows, C)
-        gp2 = gp.contiguous().reshape(rows, C) if gp is not None else None
-        dx = torch.empty_like(g2)                    # masked sum: the identity's gradient and bn3's dy
-        dz = torch.empty_like(z2)
-        scratch = torch.empty(L.pl_bn_train_scratch_bytes(rows, C), dtype=torch.uint8, device=dev)
-        link.dz_scale = torch.empty(2, device=dev)
-
-        def run(dgamma, dbeta):
-            with _lib.on_device(dev):
-                if C >= 256:
-                    # one pass writes the masked sum and takes BatchNorm-backward's column sums of it (pl_bn_join_bwd)
-                    rc = L.pl_bn_join_bwd(g2.data_ptr(), gp2.data_ptr() if gp2 is not None else None, bits.data_ptr(), z2.data_ptr(),
-                                          mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), rows, C, dx.data_ptr(), None,
-                                          dgamma.data_ptr(), dbeta.data_ptr(), scratch.data_ptr(), dz.data_ptr(), link.mode,
-                                          link.dz_scale.data_ptr(), _lib.current_stream_ptr())
-                    _lib.check(rc, "pl_bn_join_bwd")
-                else:
-                    rc = L.pl_mask_add_by_bits(g2.data_ptr(), gp2.data_ptr() if gp2 is not None else None, bits.data_ptr(), rows, C,
-                                               dx.data_ptr(), _lib.current_stream_ptr())
-                    _lib.check(rc, "pl_mask_add_by_bits")
-                    # (dy = dx where the join's bitmap is set: masking the masked sum again changes nothing)
-                    rc = L.pl_bn_train_bwd_ex(dx.data_ptr(), bits.data_ptr(), z2.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                              gamma.data_ptr(), rows, C, None, dgamma.data_ptr(), dbeta.data_ptr(), scratch.data_ptr(),
-                                              dz.data_ptr(), link.mode, link.dz_scale.data_ptr(), _lib.current_stream_ptr())
-                    _lib.check(rc, "pl_bn_train_bwd_ex")
-        dgamma, dbeta = _pgrad2(gamma, beta, C, dev, run)
-        return dz.reshape(ctx.shape), dx.reshape(ctx.shape), dgamma, dbeta, None, None, None, None, None, None
-
-
-def bn_join_planes(z, identity, bn, link):
-    if bn.momentum is None:
-        raise NotImplementedError("cumulative moving average (momentum=None)")
-    x, xp = _BNJoinPlanesFn.apply(z, identity, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
-                                  float(bn.eps), float(bn.momentum), link)
-    increment_version((bn.running_mean, bn.running_var, bn.num_batches_tracked))
-    return x, xp

@@ -1018,6 +1018,14 @@ extern "C" int pl_gemm_arith(int layout, int arith, const float* A, const float*
   return launch_gemm_f32((GemmLayout)layout, g, s);
 }
 
+// What `mode` means to the planes GEMM: PL_F16X3 is two fp16 planes per operand, whose products carry the caller's static
+// (out_scale) and device-side (dyn_inv = {1 / S}) scales; PL_BF16 is one unscaled bf16 plane.
+static void set_planes_mode(PlanesGemmArgs& g, int mode, float out_scale, const float* dyn_inv) {
+  g.mode = mode == PL_F16X3 ? 2 : 0;
+  g.out_scale = mode == PL_F16X3 ? out_scale : 1.0f;
+  g.dyn_inv = mode == PL_F16X3 ? dyn_inv : nullptr;
+}
+
 // C = op(A) op(B) on 16-bit operand planes: the fp32 operands are split into planes in `scratch` first (the lifter's
 // own producers write planes directly), then the planes GEMM of gemm_planes.hip runs.  mode: PL_F16X3 or PL_BF16.
 extern "C" size_t pl_gemm_planes_scratch_bytes(int64_t M, int64_t N, int64_t K) {
@@ -1043,8 +1051,7 @@ extern "C" int pl_gemm_planes(int layout, int mode, const float* A, const float*
   g.A = pa; g.B = pb; g.a_plane = M * K; g.b_plane = N * K;
   g.lda = layout == kTN ? (int)M : (int)K;
   g.ldb = layout == kNT ? (int)K : (int)N;
-  g.mode = mode == PL_F16X3 ? 2 : 0;
-  g.out_scale = mode == PL_F16X3 ? 1.0f / (scale_a * scale_b) : 1.0f;
+  set_planes_mode(g, mode, 1.0f / (scale_a * scale_b), nullptr);
   g.e.C = C; g.e.M = (int)M; g.e.N = (int)N; g.e.K = (int)K; g.e.ldc = (int)N; g.e.split_k = 1; g.e.bias = bias;
   return launch_gemm_planes((GemmLayout)layout, g, s);
 }
@@ -1061,6 +1068,21 @@ extern "C" int pl_gemm_planes_splits(int64_t M, int64_t N, int64_t K) {
   return s;
 }
 
+// The launch of a planes GEMM into C [M][N], over pl_gemm_planes_splits(M, N, K) K slices: more than one go to `slabs` and are
+// summed into C by a second launch (no bias or epilogue statistics then).  g.e holds M, N, K, ldc and any bias / statistics.
+static int launch_planes_split_k(const char* who, GemmLayout layout, PlanesGemmArgs& g, float* C, float* slabs, hipStream_t s) {
+  const int splits = pl_gemm_planes_splits(g.e.M, g.e.N, g.e.K);
+  if (splits > 1) {
+    if (!slabs) PL_FAIL(PL_EWORKSPACE, "%s: %d K slices need slabs", who, splits);
+    if (g.e.bias || g.e.stat_sum) PL_FAIL(PL_EINVAL, "%s: no bias / statistics on a split-K problem", who);
+    g.e.C = slabs; g.e.split_k = splits;
+    PL_TRY(launch_gemm_planes(layout, g, s));
+    return launch_reduce_slabs(slabs, splits, (int64_t)g.e.M * g.e.N, C, s);
+  }
+  g.e.C = C; g.e.split_k = 1;
+  return launch_gemm_planes(layout, g, s);
+}
+
 extern "C" int pl_gemm_planes_raw(int layout, int mode, const void* A, int64_t a_plane, int64_t lda, const void* Bm,
                                   int64_t b_plane, int64_t ldb, float* C, int64_t M, int64_t N, int64_t K, const float* bias,
                                   float out_scale, const float* dyn_inv, float* slabs, float* stat, void* stream) {
@@ -1069,25 +1091,13 @@ extern "C" int pl_gemm_planes_raw(int layout, int mode, const void* A, int64_t a
   if (!A || !Bm || !C) PL_FAIL(PL_EINVAL, "pl_gemm_planes_raw: null pointer");
   if (M <= 0 || N <= 0 || K <= 0 || M > INT32_MAX || N > INT32_MAX || K > INT32_MAX || lda > INT32_MAX || ldb > INT32_MAX)
     PL_FAIL(PL_ESHAPE, "pl_gemm_planes_raw: bad shape");
-  hipStream_t s = (hipStream_t)stream;
   PlanesGemmArgs g = {};
   g.A = static_cast<const unsigned short*>(A); g.B = static_cast<const unsigned short*>(Bm);
   g.a_plane = a_plane; g.b_plane = b_plane; g.lda = (int)lda; g.ldb = (int)ldb;
-  g.mode = mode == PL_F16X3 ? 2 : 0;
-  g.out_scale = mode == PL_F16X3 ? out_scale : 1.0f;
-  g.dyn_inv = mode == PL_F16X3 ? dyn_inv : nullptr;
-  g.e.M = (int)M; g.e.N = (int)N; g.e.K = (int)K; g.e.ldc = (int)N;
-  const int splits = pl_gemm_planes_splits(M, N, K);
-  if (splits > 1) {
-    if (!slabs) PL_FAIL(PL_EWORKSPACE, "pl_gemm_planes_raw: %d K slices need slabs", splits);
-    if (bias || stat) PL_FAIL(PL_EINVAL, "pl_gemm_planes_raw: no bias / statistics on a split-K problem");
-    g.e.C = slabs; g.e.split_k = splits;
-    PL_TRY(launch_gemm_planes((GemmLayout)layout, g, s));
-    return launch_reduce_slabs(slabs, splits, M * N, C, s);
-  }
-  g.e.C = C; g.e.split_k = 1; g.e.bias = bias;
+  set_planes_mode(g, mode, out_scale, dyn_inv);
+  g.e.M = (int)M; g.e.N = (int)N; g.e.K = (int)K; g.e.ldc = (int)N; g.e.bias = bias;
   if (stat) { g.e.stat_sum = stat; g.e.stat_m2 = stat + (size_t)gemm_stat_groups((int)M) * N; }
-  return launch_gemm_planes((GemmLayout)layout, g, s);
+  return launch_planes_split_k("pl_gemm_planes_raw", (GemmLayout)layout, g, C, slabs, (hipStream_t)stream);
 }
 
 extern "C" int pl_gemm_stat_groups(int64_t M) { return M > 0 && M <= INT32_MAX ? gemm_stat_groups((int)M) : 0; }
@@ -1108,33 +1118,6 @@ static int conv_planes_geom(GemmArgs& e, int64_t B, int64_t H, int64_t W, int64_
   return PL_OK;
 }
 
-extern "C" int pl_conv2d_planes_fwd(int mode, const void* x_planes, int64_t x_plane, int64_t B, int64_t H, int64_t W, int64_t Cin,
-                                    const void* w_planes, int64_t w_plane, int64_t Cout, int KH, int KW, int stride, int pad,
-                                    float* y, float out_scale, const float* dyn_inv, float* stat, void* stream) {
-  return pl_conv2d_planes_fwd_hw(mode, x_planes, x_plane, B, H, W, Cin, w_planes, w_plane, Cout, KH, KW, stride, stride, pad, pad,
-                                 pad, y, out_scale, dyn_inv, stat, stream);
-}
-
-extern "C" int pl_conv2d_planes_fwd_hw(int mode, const void* x_planes, int64_t x_plane, int64_t B, int64_t H, int64_t W,
-                                       int64_t Cin, const void* w_planes, int64_t w_plane, int64_t Cout, int KH, int KW,
-                                       int stride_h, int stride_w, int pad_h, int pad_w, int pad_w_right, float* y,
-                                       float out_scale, const float* dyn_inv, float* stat, void* stream) {
-  if (mode != PL_F16X3 && mode != PL_BF16) PL_FAIL(PL_EDTYPE, "pl_conv2d_planes_fwd: mode %d", mode);
-  if (!x_planes || !w_planes || !y || Cout <= 0) PL_FAIL(PL_EINVAL, "pl_conv2d_planes_fwd: null pointer");
-  PlanesGemmArgs g = {};
-  int64_t Ho, Wo;
-  PL_TRY(conv_planes_geom(g.e, B, H, W, Cin, KH, KW, stride_h, pad_h, &Ho, &Wo, "pl_conv2d_planes_fwd", stride_w, pad_w, pad_w_right));
-  const int64_t K = (int64_t)KH * KW * Cin;
-  g.A = static_cast<const unsigned short*>(x_planes); g.B = static_cast<const unsigned short*>(w_planes);
-  g.a_plane = x_plane; g.b_plane = w_plane; g.lda = 0; g.ldb = (int)K;
-  g.mode = mode == PL_F16X3 ? 2 : 0;
-  g.out_scale = mode == PL_F16X3 ? out_scale : 1.0f;
-  g.dyn_inv = mode == PL_F16X3 ? dyn_inv : nullptr;
-  g.e.C = y; g.e.M = (int)(B * Ho * Wo); g.e.N = (int)Cout; g.e.K = (int)K; g.e.ldc = (int)Cout; g.e.split_k = 1;
-  if (stat) { g.e.stat_sum = stat; g.e.stat_m2 = stat + (size_t)gemm_stat_groups(g.e.M) * Cout; }
-  return launch_gemm_planes(kNT, g, (hipStream_t)stream);
-}
-
 // the folded eval-mode epilogue and the planes output of a planes convolution (PLPlanesEpilogue)
 static int apply_planes_epilogue(GemmArgs& e, int mode, const PLPlanesEpilogue* ep, int64_t n_out, const char* who) {
   if (!ep) return PL_OK;
@@ -1151,68 +1134,68 @@ static int apply_planes_epilogue(GemmArgs& e, int mode, const PLPlanesEpilogue* 
   return PL_OK;
 }
 
+// The gathered forward behind pl_conv2d_planes_fwd[_ep][_hw] (`who`: the name the caller's errors carry).  The training
+// forms pass dyn_inv / stat and no epilogue, the eval forms an epilogue (with which y may be NULL: planes output only).
+static int conv_planes_fwd(const char* who, int mode, const void* x_planes, int64_t x_plane, int64_t B, int64_t H, int64_t W,
+                           int64_t Cin, const void* w_planes, int64_t w_plane, int64_t Cout, int KH, int KW, int stride_h,
+                           int stride_w, int pad_h, int pad_w, int pad_w_right, float* y, float out_scale, const float* dyn_inv,
+                           float* stat, const PLPlanesEpilogue* ep, void* stream) {
+  if (mode != PL_F16X3 && mode != PL_BF16) PL_FAIL(PL_EDTYPE, "%s: mode %d", who, mode);
+  if (!x_planes || !w_planes || (!y && !(ep && ep->y_planes)) || Cout <= 0) PL_FAIL(PL_EINVAL, "%s: null pointer", who);
+  PlanesGemmArgs g = {};
+  int64_t Ho, Wo;
+  PL_TRY(conv_planes_geom(g.e, B, H, W, Cin, KH, KW, stride_h, pad_h, &Ho, &Wo, who, stride_w, pad_w, pad_w_right));
+  const int64_t K = (int64_t)KH * KW * Cin;
+  g.A = static_cast<const unsigned short*>(x_planes); g.B = static_cast<const unsigned short*>(w_planes);
+  g.a_plane = x_plane; g.b_plane = w_plane; g.lda = 0; g.ldb = (int)K;
+  set_planes_mode(g, mode, out_scale, dyn_inv);
+  g.e.C = y; g.e.M = (int)(B * Ho * Wo); g.e.N = (int)Cout; g.e.K = (int)K; g.e.ldc = (int)Cout; g.e.split_k = 1;
+  if (stat) { g.e.stat_sum = stat; g.e.stat_m2 = stat + (size_t)gemm_stat_groups(g.e.M) * Cout; }
+  PL_TRY(apply_planes_epilogue(g.e, mode, ep, B * Ho * Wo * Cout, who));
+  return launch_gemm_planes(kNT, g, (hipStream_t)stream);
+}
+
+extern "C" int pl_conv2d_planes_fwd(int mode, const void* x_planes, int64_t x_plane, int64_t B, int64_t H, int64_t W, int64_t Cin,
+                                    const void* w_planes, int64_t w_plane, int64_t Cout, int KH, int KW, int stride, int pad,
+                                    float* y, float out_scale, const float* dyn_inv, float* stat, void* stream) {
+  return conv_planes_fwd("pl_conv2d_planes_fwd", mode, x_planes, x_plane, B, H, W, Cin, w_planes, w_plane, Cout, KH, KW, stride,
+                         stride, pad, pad, pad, y, out_scale, dyn_inv, stat, nullptr, stream);
+}
+
+extern "C" int pl_conv2d_planes_fwd_hw(int mode, const void* x_planes, int64_t x_plane, int64_t B, int64_t H, int64_t W,
+                                       int64_t Cin, const void* w_planes, int64_t w_plane, int64_t Cout, int KH, int KW,
+                                       int stride_h, int stride_w, int pad_h, int pad_w, int pad_w_right, float* y,
+                                       float out_scale, const float* dyn_inv, float* stat, void* stream) {
+  return conv_planes_fwd("pl_conv2d_planes_fwd", mode, x_planes, x_plane, B, H, W, Cin, w_planes, w_plane, Cout, KH, KW, stride_h,
+                         stride_w, pad_h, pad_w, pad_w_right, y, out_scale, dyn_inv, stat, nullptr, stream);
+}
+
 extern "C" int pl_conv2d_planes_fwd_ep(int mode, const void* x_planes, int64_t x_plane, int64_t B, int64_t H, int64_t W,
                                        int64_t Cin, const void* w_planes, int64_t w_plane, int64_t Cout, int KH, int KW,
                                        int stride, int pad, float* y, float out_scale, const PLPlanesEpilogue* ep, void* stream) {
-  return pl_conv2d_planes_fwd_ep_hw(mode, x_planes, x_plane, B, H, W, Cin, w_planes, w_plane, Cout, KH, KW, stride, stride, pad,
-                                    pad, pad, y, out_scale, ep, stream);
+  return conv_planes_fwd("pl_conv2d_planes_fwd_ep", mode, x_planes, x_plane, B, H, W, Cin, w_planes, w_plane, Cout, KH, KW, stride,
+                         stride, pad, pad, pad, y, out_scale, nullptr, nullptr, ep, stream);
 }
 
 extern "C" int pl_conv2d_planes_fwd_ep_hw(int mode, const void* x_planes, int64_t x_plane, int64_t B, int64_t H, int64_t W,
                                           int64_t Cin, const void* w_planes, int64_t w_plane, int64_t Cout, int KH, int KW,
                                           int stride_h, int stride_w, int pad_h, int pad_w, int pad_w_right, float* y,
                                           float out_scale, const PLPlanesEpilogue* ep, void* stream) {
-  if (mode != PL_F16X3 && mode != PL_BF16) PL_FAIL(PL_EDTYPE, "pl_conv2d_planes_fwd_ep: mode %d", mode);
-  if (!x_planes || !w_planes || (!y && !(ep && ep->y_planes)) || Cout <= 0) PL_FAIL(PL_EINVAL, "pl_conv2d_planes_fwd_ep: null pointer");
-  PlanesGemmArgs g = {};
-  int64_t Ho, Wo;
-  PL_TRY(conv_planes_geom(g.e, B, H, W, Cin, KH, KW, stride_h, pad_h, &Ho, &Wo, "pl_conv2d_planes_fwd_ep", stride_w, pad_w, pad_w_right));
-  const int64_t K = (int64_t)KH * KW * Cin;
-  g.A = static_cast<const unsigned short*>(x_planes); g.B = static_cast<const unsigned short*>(w_planes);
-  g.a_plane = x_plane; g.b_plane = w_plane; g.lda = 0; g.ldb = (int)K;
-  g.mode = mode == PL_F16X3 ? 2 : 0;
-  g.out_scale = mode == PL_F16X3 ? out_scale : 1.0f;
-  g.e.C = y; g.e.M = (int)(B * Ho * Wo); g.e.N = (int)Cout; g.e.K = (int)K; g.e.ldc = (int)Cout; g.e.split_k = 1;
-  PL_TRY(apply_planes_epilogue(g.e, mode, ep, B * Ho * Wo * Cout, "pl_conv2d_planes_fwd_ep"));
-  return launch_gemm_planes(kNT, g, (hipStream_t)stream);
-}
-
-extern "C" int pl_deconv4x4s2_planes_fwd_ep(int mode, const void* x_planes, int64_t x_plane, int64_t B, int64_t H, int64_t W,
-                                            int64_t Cin, const void* wsub_planes, int64_t wsub_plane, int64_t Cout, float* y,
-                                            float out_scale, const PLPlanesEpilogue* ep, void* stream) {
-  if (mode != PL_F16X3 && mode != PL_BF16) PL_FAIL(PL_EDTYPE, "pl_deconv4x4s2_planes_fwd_ep: mode %d", mode);
-  if (!x_planes || !wsub_planes || (!y && !(ep && ep->y_planes)) || Cout <= 0) PL_FAIL(PL_EINVAL, "pl_deconv4x4s2_planes_fwd_ep: null pointer");
-  if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || B * H * W > INT32_MAX) PL_FAIL(PL_ESHAPE, "pl_deconv4x4s2_planes_fwd_ep: bad geometry");
-  if (ep && ep->resid) PL_FAIL(PL_EINVAL, "pl_deconv4x4s2_planes_fwd_ep: no residual on a transposed convolution");
-  const int64_t K = 4 * Cin, nsub = Cout * K;
-  for (int ph = 0; ph < 2; ++ph)
-    for (int pw = 0; pw < 2; ++pw) {
-      PlanesGemmArgs g = {};
-      g.e.conv_cin = (int)Cin; g.e.conv_h = (int)H; g.e.conv_w = (int)W; g.e.conv_ho = (int)H; g.e.conv_wo = (int)W;
-      g.e.conv_kw = 2; g.e.conv_stride = 1;
-      g.e.conv_pad_h = ph ? 0 : 1; g.e.conv_pad_w = pw ? 0 : 1;
-      g.e.scat_on = 1; g.e.scat_ph = ph; g.e.scat_pw = pw;
-      g.A = static_cast<const unsigned short*>(x_planes);
-      g.B = static_cast<const unsigned short*>(wsub_planes) + (size_t)(ph * 2 + pw) * nsub;
-      g.a_plane = x_plane; g.b_plane = wsub_plane; g.lda = 0; g.ldb = (int)K;
-      g.mode = mode == PL_F16X3 ? 2 : 0;
-      g.out_scale = mode == PL_F16X3 ? out_scale : 1.0f;
-      g.e.C = y; g.e.M = (int)(B * H * W); g.e.N = (int)Cout; g.e.K = (int)K; g.e.ldc = (int)Cout; g.e.split_k = 1;
-      PL_TRY(apply_planes_epilogue(g.e, mode, ep, B * 4 * H * W * Cout, "pl_deconv4x4s2_planes_fwd_ep"));
-      PL_TRY(launch_gemm_planes(kNT, g, (hipStream_t)stream));
-    }
-  return PL_OK;
+  return conv_planes_fwd("pl_conv2d_planes_fwd_ep", mode, x_planes, x_plane, B, H, W, Cin, w_planes, w_plane, Cout, KH, KW,
+                         stride_h, stride_w, pad_h, pad_w, pad_w_right, y, out_scale, nullptr, nullptr, ep, stream);
 }
 
 // nn.ConvTranspose2d(4, 2, 1, bias=False) forward on the planes GEMM: four 2x2-tap convolutions at the INPUT resolution,
 // one per output parity (no zero insertion), each storing straight into its pixels of y [B][2H][2W][Cout].
 // wsub_planes: planes of conv.deconv_subkernels(weight) = [4 parities][Cout][2][2][Cin].
-extern "C" int pl_deconv4x4s2_planes_fwd(int mode, const void* x_planes, int64_t x_plane, int64_t B, int64_t H, int64_t W,
-                                         int64_t Cin, const void* wsub_planes, int64_t wsub_plane, int64_t Cout, float* y,
-                                         float out_scale, const float* dyn_inv, void* stream) {
-  if (mode != PL_F16X3 && mode != PL_BF16) PL_FAIL(PL_EDTYPE, "pl_deconv4x4s2_planes_fwd: mode %d", mode);
-  if (!x_planes || !wsub_planes || !y || Cout <= 0) PL_FAIL(PL_EINVAL, "pl_deconv4x4s2_planes_fwd: null pointer");
-  if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || B * H * W > INT32_MAX) PL_FAIL(PL_ESHAPE, "pl_deconv4x4s2_planes_fwd: bad geometry");
+// The launcher behind pl_deconv4x4s2_planes_fwd (dyn_inv, no epilogue) and _fwd_ep (an epilogue; y may then be NULL).
+static int deconv_planes_fwd(const char* who, int mode, const void* x_planes, int64_t x_plane, int64_t B, int64_t H, int64_t W,
+                             int64_t Cin, const void* wsub_planes, int64_t wsub_plane, int64_t Cout, float* y, float out_scale,
+                             const float* dyn_inv, const PLPlanesEpilogue* ep, void* stream) {
+  if (mode != PL_F16X3 && mode != PL_BF16) PL_FAIL(PL_EDTYPE, "%s: mode %d", who, mode);
+  if (!x_planes || !wsub_planes || (!y && !(ep && ep->y_planes)) || Cout <= 0) PL_FAIL(PL_EINVAL, "%s: null pointer", who);
+  if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || B * H * W > INT32_MAX) PL_FAIL(PL_ESHAPE, "%s: bad geometry", who);
+  if (ep && ep->resid) PL_FAIL(PL_EINVAL, "%s: no residual on a transposed convolution", who);
   const int64_t K = 4 * Cin, nsub = Cout * K;
   for (int ph = 0; ph < 2; ++ph)
     for (int pw = 0; pw < 2; ++pw) {
@@ -1224,13 +1207,26 @@ extern "C" int pl_deconv4x4s2_planes_fwd(int mode, const void* x_planes, int64_t
       g.A = static_cast<const unsigned short*>(x_planes);
       g.B = static_cast<const unsigned short*>(wsub_planes) + (size_t)(ph * 2 + pw) * nsub;
       g.a_plane = x_plane; g.b_plane = wsub_plane; g.lda = 0; g.ldb = (int)K;
-      g.mode = mode == PL_F16X3 ? 2 : 0;
-      g.out_scale = mode == PL_F16X3 ? out_scale : 1.0f;
-      g.dyn_inv = mode == PL_F16X3 ? dyn_inv : nullptr;
+      set_planes_mode(g, mode, out_scale, dyn_inv);
       g.e.C = y; g.e.M = (int)(B * H * W); g.e.N = (int)Cout; g.e.K = (int)K; g.e.ldc = (int)Cout; g.e.split_k = 1;
+      PL_TRY(apply_planes_epilogue(g.e, mode, ep, B * 4 * H * W * Cout, who));   // (its checks: before the first launch)
       PL_TRY(launch_gemm_planes(kNT, g, (hipStream_t)stream));
     }
   return PL_OK;
+}
+
+extern "C" int pl_deconv4x4s2_planes_fwd_ep(int mode, const void* x_planes, int64_t x_plane, int64_t B, int64_t H, int64_t W,
+                                            int64_t Cin, const void* wsub_planes, int64_t wsub_plane, int64_t Cout, float* y,
+                                            float out_scale, const PLPlanesEpilogue* ep, void* stream) {
+  return deconv_planes_fwd("pl_deconv4x4s2_planes_fwd_ep", mode, x_planes, x_plane, B, H, W, Cin, wsub_planes, wsub_plane, Cout, y,
+                           out_scale, nullptr, ep, stream);
+}
+
+extern "C" int pl_deconv4x4s2_planes_fwd(int mode, const void* x_planes, int64_t x_plane, int64_t B, int64_t H, int64_t W,
+                                         int64_t Cin, const void* wsub_planes, int64_t wsub_plane, int64_t Cout, float* y,
+                                         float out_scale, const float* dyn_inv, void* stream) {
+  return deconv_planes_fwd("pl_deconv4x4s2_planes_fwd", mode, x_planes, x_plane, B, H, W, Cin, wsub_planes, wsub_plane, Cout, y,
+                           out_scale, dyn_inv, nullptr, stream);
 }
 
 extern "C" int pl_conv2d_planes_wgrad(int mode, const void* dz_planes, int64_t dz_plane, const void* x_planes, int64_t x_plane,
@@ -1252,20 +1248,9 @@ extern "C" int pl_conv2d_planes_wgrad_hw(int mode, const void* dz_planes, int64_
   const int64_t N = (int64_t)KH * KW * Cin, K = B * Ho * Wo;
   g.A = static_cast<const unsigned short*>(dz_planes); g.B = static_cast<const unsigned short*>(x_planes);
   g.a_plane = dz_plane; g.b_plane = x_plane; g.lda = (int)Cout; g.ldb = 0;
-  g.mode = mode == PL_F16X3 ? 2 : 0;
-  g.out_scale = mode == PL_F16X3 ? out_scale : 1.0f;
-  g.dyn_inv = mode == PL_F16X3 ? dyn_inv : nullptr;
+  set_planes_mode(g, mode, out_scale, dyn_inv);
   g.e.M = (int)Cout; g.e.N = (int)N; g.e.K = (int)K; g.e.ldc = (int)N;
-  const int splits = pl_gemm_planes_splits(Cout, N, K);
-  hipStream_t s = (hipStream_t)stream;
-  if (splits > 1) {
-    if (!slabs) PL_FAIL(PL_EWORKSPACE, "pl_conv2d_planes_wgrad: %d K slices need slabs", splits);
-    g.e.C = slabs; g.e.split_k = splits;
-    PL_TRY(launch_gemm_planes(kTN, g, s));
-    return launch_reduce_slabs(slabs, splits, Cout * N, dw, s);
-  }
-  g.e.C = dw; g.e.split_k = 1;
-  return launch_gemm_planes(kTN, g, s);
+  return launch_planes_split_k("pl_conv2d_planes_wgrad", kTN, g, dw, slabs, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------
