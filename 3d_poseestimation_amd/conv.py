@@ -73,24 +73,32 @@ def _pgrad(param, make):
     return None
 
 
-def _pgrad2(pa, pb, C, dev, run):
-    """_pgrad for two parameters whose gradients ONE kernel writes (BatchNorm's dgamma, dbeta): run(out_a, out_b)."""
+def _pgrad2(pa, pb, C, dev, run, need=(True, True)):
+    """_pgrad for two parameters whose gradients ONE kernel writes (BatchNorm's dgamma, dbeta): run(out_a, out_b).
+    need: the node's needs_input_grad of the two.  A frozen parameter's half lands in scratch and stays there: no .grad is
+    attached (FlatAdam steps every arena range that holds a gradient) and autograd is handed None, as for any other
+    parameter with requires_grad=False."""
     va, vb = getattr(pa, "_pl_grad", None), getattr(pb, "_pl_grad", None)
-    if va is not None and vb is not None and pa.grad is None and pb.grad is None:
+    if all(need) and va is not None and vb is not None and pa.grad is None and pb.grad is None:
         run(va, vb)
         pa.grad, pb.grad = va, vb
         return None, None
     a, b = torch.empty(C, device=dev), torch.empty(C, device=dev)
     run(a, b)
-    if va is None or vb is None:
-        return a, b
-    for p, v, t in ((pa, va, a), (pb, vb, b)):
-        if p.grad is None:
-            v.copy_(t)
-            p.grad = v
+    out = []
+    for p, v, t, n in ((pa, va, a, need[0]), (pb, vb, b, need[1])):
+        if not n:
+            out.append(None)
+        elif v is None:
+            out.append(t)
         else:
-            p.grad.add_(t)
-    return None, None
+            if p.grad is None:
+                v.copy_(t)
+                p.grad = v
+            else:
+                p.grad.add_(t)
+            out.append(None)
+    return tuple(out)
 
 
 def _oihw_from_ohwi(dw_ohwi, out):
@@ -334,10 +342,11 @@ def _bn_fwd(ctx, z, identity, gamma, beta, running_mean, running_var, batches, e
     return y, yp
 
 
-def _bn_bwd(ctx, g2, gp2=None, join=False):
+def _bn_bwd(ctx, g2, need, gp2=None, join=False):
     """Backward of _bn_fwd from dy = g2 [rows][C] -- join: from dy = the sum of g2 and gp2 (or None) where the join's ReLU
     passed, which is also the identity's gradient dx.  dz is fp32 or, with a link, a carrier of its planes, range-scaled on
-    the device (link.dz_scale).  Returns (dz, dx or None, dgamma, dbeta), the last two as _pgrad2 hands them to autograd."""
+    the device (link.dz_scale).  need: needs_input_grad of (gamma, beta).  Returns (dz, dx or None, dgamma, dbeta), the last
+    two as _pgrad2 hands them to autograd."""
     z2, bits, mean, rstd, gamma, beta = ctx.saved_tensors
     rows, C = z2.shape
     dev, L, link = z2.device, _lib.lib(), ctx.link
@@ -369,7 +378,7 @@ def _bn_bwd(ctx, g2, gp2=None, join=False):
                                       gamma.data_ptr(), rows, C, dzf, dgamma.data_ptr(), dbeta.data_ptr(), scratch.data_ptr(),
                                       dzp, mode, scale, _lib.current_stream_ptr())
             _lib.check(rc, "pl_bn_train_bwd_ex")
-    dgamma, dbeta = _pgrad2(gamma, beta, C, dev, run)
+    dgamma, dbeta = _pgrad2(gamma, beta, C, dev, run, need)
     return dz, dx, dgamma, dbeta
 
 
@@ -391,7 +400,7 @@ class _BNFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        dz, _, dgamma, dbeta = _bn_bwd(ctx, dy.contiguous().reshape(-1, ctx.shape[-1]))
+        dz, _, dgamma, dbeta = _bn_bwd(ctx, dy.contiguous().reshape(-1, ctx.shape[-1]), ctx.needs_input_grad[1:3])
         return dz.reshape(ctx.shape), dgamma, dbeta, None, None, None, None, None, None, None, None, None
 
 
@@ -415,7 +424,7 @@ class _BNJoinFn(torch.autograd.Function):
         if g is None:
             return (None,) * 10
         C = ctx.shape[-1]
-        dz, dx, dgamma, dbeta = _bn_bwd(ctx, g.contiguous().reshape(-1, C),
+        dz, dx, dgamma, dbeta = _bn_bwd(ctx, g.contiguous().reshape(-1, C), ctx.needs_input_grad[2:4],
                                         gp.contiguous().reshape(-1, C) if gp is not None else None, join=True)
         return dz.reshape(ctx.shape), dx.reshape(ctx.shape), dgamma, dbeta, None, None, None, None, None, None
 

@@ -45,6 +45,7 @@ __global__ __launch_bounds__(NTHR) void softargmax_fwd_kernel(const float* __res
     const int wq = i % w4, hd = i / w4;
     const float w0 = (float)(wq * 4), hh = (float)(hd % H), dd = (float)(hd / H);
     const float mx = fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w));
+    if (mx == -INFINITY) continue;       // weight exactly 0 (and with a.m still -inf, v - a.m would be NaN)
     if (mx > a.m) {                      // rescale what this lane has so far
       const float f = (a.m == -INFINITY) ? 0.f : __expf(a.m - mx);
       a.s *= f; a.x *= f; a.y *= f; a.z *= f;
@@ -107,6 +108,7 @@ __global__ __launch_bounds__(NTHR) void softargmax_nhwc_fwd_kernel(const float* 
       v[q] = p < P ? src[(size_t)p * C] : -INFINITY;
     }
     const float mx = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
+    if (mx == -INFINITY) continue;             // as above
     if (mx > a.m) {
       const float f = (a.m == -INFINITY) ? 0.f : __expf(a.m - mx);
       a.s *= f; a.x *= f; a.y *= f; a.z *= f;

@@ -1064,6 +1064,63 @@ def test_flat_adam_accumulates_a_second_backward_of_the_same_step(pkg):
         assert float((p.grad - q.grad).abs().max()) <= 1e-5 * den, (k, float((p.grad - q.grad).abs().max()), den)
 
 
+@pytest.mark.parametrize("frozen", [("bn2.weight", "bn2.bias", "conv2.weight"),      # a BatchNorm + ReLU node (conv._BNFn)
+                                    ("bn3.weight", "bn3.bias", "conv1.weight"),      # bn3 inside the residual join (_BNJoinFn)
+                                    ("bn1.weight", "conv3.weight")])                 # one half of a pair: beta still trains
+def test_flat_adam_leaves_frozen_parameters_alone(pkg, frozen):
+    """requires_grad=False under arena.FlatAdam on the conv path: a Bottleneck(256, 64) on the f16x3 planes route, B = 2,
+    8 x 8 pixels, two steps, against the stock modules under torch autograd + torch.optim.Adam on the CPU in fp64.  Frozen
+    parameters keep their bits and get no .grad (FlatAdam steps every arena range that holds one); the others track the
+    torch run within the bound of test_flat_adam_three_steps_of_model3d_vs_torch_adam (1e-3 lr).
+    The loss is a SUM of squares: under a mean over the 32768 outputs the weight gradients are ~1e-5 and their small
+    elements sit at Adam's eps = 1e-8, where the update g / (|g| + eps) turns fp32-sized gradient differences into 1e-2 lr
+    (seen: one element of conv2.weight at 1.8e-2 lr, every other tensor <= 2e-4 lr) -- a property of Adam, not of a kernel."""
+    import copy
+    torch.manual_seed(11)
+    blk = pkg.backbone.Bottleneck(256, 64, stride=1).train()
+    with torch.no_grad():
+        for bn in (blk.bn1, blk.bn2, blk.bn3):
+            bn.weight.uniform_(0.5, 1.5)
+            bn.bias.uniform_(-0.3, 0.3)
+    for k, p in blk.named_parameters():
+        p.requires_grad_(k not in frozen)
+    xs = [torch.randn(2, 8, 8, 256) for _ in range(2)]
+    target = torch.randn(2, 8, 8, 256)
+    lr = 1e-3
+    ref = copy.deepcopy(blk).double()
+    oref = torch.optim.Adam([p for p in ref.parameters() if p.requires_grad], lr=lr)
+    for x in xs:
+        oref.zero_grad()
+        xr = x.permute(0, 3, 1, 2).double()
+        o = torch.relu(ref.bn1(ref.conv1(xr)))
+        o = torch.relu(ref.bn2(ref.conv2(o)))
+        o = torch.relu(ref.bn3(ref.conv3(o)) + xr)
+        (0.5 * (o - target.permute(0, 3, 1, 2).double()).square().sum()).backward()
+        oref.step()
+    b = copy.deepcopy(blk).to(DEV)
+    init = {k: p.detach().clone() for k, p in b.named_parameters()}
+    opt = pkg.FlatAdam(b, lr=lr)
+    mode = pkg.conv._lib.PL_F16X3
+    assert pkg.backbone._bottleneck_planes_ok(b, (2, 8, 8, 256))
+    for x in xs:
+        opt.zero_grad()
+        xd = x.to(DEV)
+        out, _ = pkg.backbone._bottleneck_train_planes(b, xd, pkg.conv.to_planes(xd, mode), mode)
+        (0.5 * (out - target.to(DEV)).square().sum()).backward()
+        for k, p in b.named_parameters():
+            assert (p.grad is None) == (k in frozen), k
+        opt.step()
+    worst = {}
+    for (k, p), (_, r) in zip(b.named_parameters(), ref.named_parameters()):
+        if k in frozen:
+            assert torch.equal(p.detach(), init[k]) and p.grad is None, k
+        else:
+            assert not torch.equal(p.detach(), init[k]), k
+            worst[k] = float((p.detach().cpu().double() - r.detach()).abs().max()) / lr
+    print("max |p - p_torch| / lr:", worst)
+    assert max(worst.values()) <= 1e-3, worst
+
+
 @pytest.mark.parametrize("dtype", ["f16x3", "bf16x6"])
 @pytest.mark.parametrize("how", ["flat_adam", "graphed"])
 def test_eval_after_training_steps_uses_the_trained_weights(pkg, dtype, how):

@@ -119,3 +119,90 @@ def test_soft_argmax_3d_nhwc_backward_vs_torch_autograd(pkg):
     xc = x.to(DEV).requires_grad_(True)
     (pkg.soft_argmax_3d(xc) * g.to(DEV)).sum().backward()
     assert float((xn.grad.permute(0, 3, 1, 2) - xc.grad).abs().max()) < 2e-6 * scale
+
+
+# ---------------------------------------------------------------------------- -inf logits, maps smaller than the workgroup
+NEG = float("-inf")
+
+
+def _check_nchw(pkg, out, J, D, centred, seed):
+    """Forward (2e-5, oracle) and backward (1e-5 of the largest gradient, torch autograd in fp64; exactly 0 where the
+    logit is -inf) of the NCHW kernels on `out` (B, J*D, H, W)."""
+    B = out.shape[0]
+    nc = 3 if centred else 2
+    x = out.to(DEV).requires_grad_(True)
+    c = pkg.soft_argmax_3d(x, J, D) if centred else pkg.soft_argmax_2d(x, J)
+    got_c = c.detach().cpu().numpy()
+    assert np.isfinite(got_c).all()
+    np.testing.assert_allclose(got_c, ho.soft_argmax(out.numpy(), J, D, centred), rtol=0, atol=2e-5)
+    g = torch.randn(B, J * nc, generator=torch.Generator().manual_seed(seed))
+    c.backward(g.to(DEV))
+    xr = out.double().requires_grad_(True)
+    cr = _torch_ref(xr, J, D, centred)
+    np.testing.assert_allclose(got_c, cr.detach().numpy(), rtol=0, atol=2e-5)
+    cr.backward(g.double())
+    ref, got = xr.grad.numpy(), x.grad.cpu().numpy()
+    assert np.isfinite(got).all()
+    assert np.abs(got - ref).max() <= 1e-5 * np.abs(ref).max() + 1e-12
+    dead = np.isneginf(out.numpy())
+    assert (got[dead] == 0).all() and (ref[dead] == 0).all()
+    return got_c
+
+
+def _check_nhwc(pkg, out, J, seed):
+    """The same for the NHWC kernels (depth 64): `out` is the (B, J*64, H, W) view of the logits."""
+    B = out.shape[0]
+    xn = out.permute(0, 2, 3, 1).contiguous().to(DEV).requires_grad_(True)
+    c = pkg.soft_argmax_3d_nhwc(xn, J)
+    got_c = c.detach().cpu().numpy()
+    assert np.isfinite(got_c).all()
+    np.testing.assert_allclose(got_c, ho.soft_argmax(out.numpy(), J, 64, True), rtol=0, atol=2e-5)
+    g = torch.randn(B, J * 3, generator=torch.Generator().manual_seed(seed))
+    c.backward(g.to(DEV))
+    xr = out.double().requires_grad_(True)
+    cr = _torch_ref(xr, J, 64, True)
+    np.testing.assert_allclose(got_c, cr.detach().numpy(), rtol=0, atol=2e-5)
+    cr.backward(g.double())
+    ref, got = xr.grad.numpy(), xn.grad.permute(0, 3, 1, 2).cpu().numpy()
+    assert np.isfinite(got).all()
+    assert np.abs(got - ref).max() <= 1e-5 * np.abs(ref).max() + 1e-12
+    dead = np.isneginf(out.numpy())
+    assert (got[dead] == 0).all() and (ref[dead] == 0).all()
+
+
+def test_soft_argmax_3d_with_minus_infinity_logits(pkg):
+    """A true -inf logit has softmax weight exactly 0 (torch.softmax, the oracle).  Row h = 0 of depth 0 -- the first float4
+    lanes 0..7 visit -- is all -inf for two joints; a third joint is -inf everywhere but one voxel, where the expectation
+    then sits exactly."""
+    J, D, H, W = 17, 8, 16, 32
+    out = torch.randn(1, J * D, H, W, generator=torch.Generator().manual_seed(21)) * 3
+    for j in (3, 9):
+        out[0, j * D, 0, :] = NEG
+    out[0, 12 * D:13 * D] = NEG
+    out[0, 12 * D + 5, 7, 21] = 1.5
+    c = _check_nchw(pkg, out, J, D, True, 22).reshape(J, 3)
+    np.testing.assert_allclose(c[12], [(21 / 32 - 0.5) * 2, (7 / 16 - 0.5) * 2, (5 / 8 - 0.5) * 2], rtol=0, atol=1e-6)
+
+
+def test_soft_argmax_3d_nhwc_with_minus_infinity_logits(pkg):
+    """NHWC: the first 16 pixels of one joint -- what the four wavefronts read in their first pass, every depth -- are -inf."""
+    J, H, W = 17, 4, 8
+    out = torch.randn(1, J * 64, H, W, generator=torch.Generator().manual_seed(23)) * 3
+    out[0, 6 * 64:7 * 64, 0:2, :] = NEG
+    _check_nhwc(pkg, out, J, 24)
+
+
+@pytest.mark.parametrize("D,H,W", [(1, 1, 4), (1, 3, 4), (1, 4, 8), (2, 2, 4)])
+def test_soft_argmax_maps_smaller_than_the_workgroup(pkg, D, H, W):
+    """1, 3, 4 and 8 float4 groups per map: whole wavefronts of the 256-thread workgroup see no element."""
+    J = 17
+    out = torch.randn(2, J * D, H, W, generator=torch.Generator().manual_seed(D * 100 + H * 10 + W)) * 4
+    _check_nchw(pkg, out, J, D, D > 1, 31)
+
+
+@pytest.mark.parametrize("H,W", [(1, 1), (3, 5)])
+def test_soft_argmax_3d_nhwc_small_maps(pkg, H, W):
+    """1 and 15 pixels: fewer than the 16 a pass of the four wavefronts covers."""
+    J = 17
+    out = torch.randn(2, J * 64, H, W, generator=torch.Generator().manual_seed(H * 10 + W)) * 4
+    _check_nhwc(pkg, out, J, 32)

@@ -207,6 +207,45 @@ def test_g1_eval_forward_vs_reference(pkg, dtype):
     assert orc.mpjpe_mm(y, g["y_fp64"]) < 1e-3       # and against the reference run in fp64
 
 
+# Largest |BatchNorm output| at which the HIP path's ReLU decision may differ from D_ref in the g2 "full" f16x3 gate.
+# Measured: flips per layer [0, 0, 1, 0, 0], |BN output| 2.4e-7 at that one -- under 1e-4, so 1e-4 and not the 1e-3 that
+# test_ragged_shapes_vs_oracle uses for this shape and arithmetic.
+FLIP_BN_BOUND = 1e-4
+
+
+def _g64_on(st, g, decisions):
+    """Every gradient and dx of the g2 "full" step evaluated in fp64 with the ReLU decisions forced; also the cache."""
+    pred, cache = orc.forward(st, g["x"], num_stage=2, train=True, p_dropout=0.0, dtype=np.float64, update_running=False,
+                              on_masks=decisions)
+    _, dpred = orc.mse_loss(pred, g["t"].reshape(pred.shape), np.float64)
+    grads, dx = orc.backward(st, cache, dpred)
+    return grads, dx, cache
+
+
+def _without_flip_effect(pkg, m, st, g, got, got_dx):
+    """got - (G64(D_gpu) - G64(D_ref)): the HIP path's gradients with the effect of its own flipped ReLU decisions taken out.
+    D_ref, the fp32 oracle's decisions, stands in for the reference's (the golden file does not hold them):
+    tests/test_oracle_golden.py::test_g2_train_nodrop_full_fp64_on_fp32_decisions pins that an fp64 evaluation on D_ref meets
+    the golden outputs at 5e-4.  D_gpu: the bitmaps of the training forward (p = 0: they are the ReLU decisions).
+    Few flips (1e-4 of a layer + 2, the rule of _assert_decisions_consistent), each on a round-off-sized BatchNorm output
+    (below FLIP_BN_BOUND, taken from the fp64 run on D_ref)."""
+    _, c32 = orc.forward(st, g["x"], num_stage=2, train=True, p_dropout=0.0, update_running=False)
+    d_ref = [c["rmask"] for c in c32["layers"]]
+    d_gpu = _gpu_decisions(pkg, m, 5, 1024)
+    g_ref, dx_ref, cache = _g64_on(st, g, d_ref)
+    n_flip, worst = [], 0.0
+    for (lin, bnp), c, a, b in zip(orc.hidden_layer_names(2), cache["layers"], d_gpu, d_ref):
+        flipped = a != b
+        y = np.abs(c["zhat"] * st[bnp + ".weight"].astype(np.float64) + st[bnp + ".bias"].astype(np.float64))
+        n_flip.append(int(flipped.sum()))
+        worst = max(worst, float(y[flipped].max()) if flipped.any() else 0.0)
+        assert n_flip[-1] <= 1e-4 * flipped.size + 2, (lin, n_flip[-1])
+    print(f"g2 full-f16x3: flipped decisions per layer {n_flip}, largest |BN output| at a flip {worst:.3e}")
+    assert worst < FLIP_BN_BOUND, worst
+    g_gpu, dx_gpu, _ = _g64_on(st, g, d_gpu)
+    return {k: got[k].astype(np.float64) - (g_gpu[k] - g_ref[k]) for k in g_ref}, got_dx - (dx_gpu - dx_ref)
+
+
 @pytest.mark.parametrize("tag", ["small", "nobn", "s3", "full", "full-f16x3"])
 def test_g2_train_nodrop_vs_reference(pkg, tag):
     dtype = "fp32"
@@ -228,7 +267,14 @@ def test_g2_train_nodrop_vs_reference(pkg, tag):
     _assert_train_fwd(pred.detach().cpu().numpy(), g["pred"], p64)
     _close(loss.item(), g["loss"], 2e-5, 0)
     got = _grads(m)
+    got_dx = x.grad.cpu().numpy().reshape(g["x"].shape[0], -1).astype(np.float64)
     if tag == "full":
+        if dtype == "f16x3":
+            # B = 128 on the operand-planes path: the forward Linears run on the layer kernels' contraction, another summation
+            # order than the reference's, and a ReLU decision that flips on a round-off-sized pre-activation moves the
+            # gradients by 1 / B of the rows it touches.  That effect is accounted for, not tolerated: the flips are counted
+            # and located, their effect on every gradient is computed in fp64, and what is left meets the fp32 tag's 5e-4.
+            got, got_dx = _without_flip_effect(pkg, m, st, g, got, got_dx)
         for k in orc.param_names(2):
             flat = got[k].reshape(-1)
             pre_bn_bias = k.endswith(".bias") and "batch_norm" not in k and k != "w2.bias"
@@ -237,26 +283,14 @@ def test_g2_train_nodrop_vs_reference(pkg, tag):
             else:
                 scale = np.abs(g["gval:" + k]).max()
                 _close(np.linalg.norm(flat.astype(np.float64)), float(g["gnorm:" + k]), 1e-3, 0)
-            if dtype == "f16x3":
-                # B = 128 on the operand-planes path: the forward Linears run on the layer kernels' contraction (another
-                # summation order than the tile GEMM's and the reference's), and a ReLU decision that flips on a
-                # round-off-sized pre-activation moves the samples of the rows it touches by 1 / B of their size.  With the
-                # decisions forced (a one-off script, in git history; same shape) every gradient tensor is within 7e-7 of the fp64
-                # oracle in relative L2 -- the fp32 oracle itself: 1.3e-6; the tile GEMM: 8e-7 -- and
-                # test_ragged_shapes_vs_oracle[128-1024-2-...-f16x3] holds that in the suite.  Here, against the reference's own
-                # decisions: the typical sample within 1e-3 of the scale, none beyond 2 %.
-                dv = np.abs(flat[g["gidx:" + k]].astype(np.float64) - g["gval:" + k]) / scale
-                assert np.median(dv) < 1e-3 and np.mean(dv > 2e-3) < 0.2 and dv.max() < 2e-2, (k, np.median(dv), dv.max())
-            else:
-                _close(flat[g["gidx:" + k]] / scale, g["gval:" + k] / scale, 0, 5e-4)
+            _close(flat[g["gidx:" + k]] / scale, g["gval:" + k] / scale, 0, 5e-4)
     else:
         want = golden_state(g, "grad:")
         _check_grads(got, want, bn)
         if not bn:
             assert m.batch_norm1.weight.grad is None      # unused parameters keep grad None (as in torch)
     sdx = np.abs(g["dx"]).max()
-    _close(x.grad.cpu().numpy().reshape(g["dx"].shape) / sdx, g["dx"] / sdx, 0,
-           (2e-2 if dtype == "f16x3" else 5e-4) if tag == "full" else 2e-5)
+    _close(got_dx.reshape(g["dx"].shape) / sdx, g["dx"] / sdx, 0, 5e-4 if tag == "full" else 2e-5)
     sd = {k: v.cpu().numpy() for k, v in m.state_dict().items()}
     for k, v in golden_state(g, "after:").items():
         if "num_batches" in k:
