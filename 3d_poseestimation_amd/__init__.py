@@ -14,4 +14,5 @@ from .losses import TriangleLoss, l1_loss, l1_terms  # noqa: F401
 from .backbone import Model_2D, Model_3D, ResNet  # noqa: F401
 from .data import PoseFeeder, epoch_indices  # noqa: F401
 from .vit import MyViT  # noqa: F401
-from . import arena, backbone, conv, data, dp, layout, synth, vit  # noqa: F401
+from .range_guard import PoseliftRangeError  # noqa: F401
+from . import arena, backbone, conv, data, dp, layout, range_guard, synth, vit  # noqa: F401

@@ -112,6 +112,7 @@ SIGNATURES = {
     "pl_wplanes_layer_bytes": (_c.c_size_t, [_D]),
     "pl_weight_plane_scale": (_c.c_float, []),
     "pl_wplanes_refresh": (_c.c_int, [_D, _P]),
+    "pl_range_monitor": (_c.c_int, [_P]),
     "pl_flip_pose": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _c.c_int64, _P]),
     "pl_counter_add": (_c.c_int, [_P, _c.c_int64, _P]),
     "pl_flip_pose_ex": (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_float, _c.c_float, _P]),
@@ -259,14 +260,26 @@ def check(rc, what):
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+# range_guard._bind once the guard was ever enabled: the library keeps the record pointer per calling thread, and every call
+# that launches asks current_stream_ptr() for its stream on the thread and device it runs on -- the one place to hand it over
+_range_bind = None
 _cur_device = getattr(torch._C, "_cuda_getDevice", None)
 
 
 def current_stream_ptr():
     """hipStream_t of torch's current stream on the current device.  (torch.cuda.current_stream().cuda_stream builds a Stream
-    object per call: 9 us, 170 times per conv training step.)"""
+    object per call: 9 us, 170 times per conv training step.)
+    Every wrapper that launches must take its stream from here, on the thread that makes the call and right before it: once
+    the range guard was enabled this is also where the calling thread's library state is handed the device's record
+    (range_guard._bind; the library keeps that pointer per thread).  A wrapper that cached a stream pointer, or passed a
+    user's, would launch with another device's record or none."""
     if _raw_stream is not None and _cur_device is not None:
-        return _raw_stream(_cur_device())
+        dev = _cur_device()
+        if _range_bind is not None:
+            _range_bind(dev)
+        return _raw_stream(dev)
+    if _range_bind is not None:
+        _range_bind(torch.cuda.current_device())
     return torch.cuda.current_stream().cuda_stream
 
 

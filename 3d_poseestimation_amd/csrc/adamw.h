@@ -32,6 +32,7 @@ struct AdamWIn {
   int64_t seg_off[PL_ADAMW_MAX_SEGS], seg_n[PL_ADAMW_MAX_SEGS];
   unsigned short* seg_h[PL_ADAMW_MAX_SEGS];
   unsigned short* seg_l[PL_ADAMW_MAX_SEGS];
+  uint32_t* range;   // the range guard's record or NULL (fp16 planes at pscale: the weight slot)
 };
 
 // a slice [p, p + n) of the step carried by another kernel's spare workgroups (small_layer.hip): same fields, same constants

@@ -402,6 +402,7 @@ int split_weight_planes(const PLDesc* d, const ParamLayout& P, const Ws& w, void
   for (int l = 1; l < w.L; ++l) {
     unsigned short* q = wplane(d, w, ws, l);
     PlaneOut po = {q, q + n, kWeightPlaneScale, nullptr, w.pkind};
+    range_watch(po, PL_RANGE_SITE_LIFTER_WEIGHT);
     PL_TRY(launch_split_planes(d->params + P.off[4 * l], n, po, s));
   }
   return PL_OK;
@@ -456,6 +457,15 @@ using namespace pl;
 
 extern "C" int pl_version(void) { return PL_VERSION; }
 extern "C" const char* pl_last_error(void) { return g_err; }
+
+// the range guard's record (pl_internal.h range_record): per calling thread, like the error message
+static thread_local uint32_t* g_range = nullptr;
+uint32_t* pl::range_record() { return g_range; }
+extern "C" int pl_range_monitor(void* record_or_null) {
+  if (reinterpret_cast<uintptr_t>(record_or_null) & 3) PL_FAIL(PL_EINVAL, "pl_range_monitor: record not 4-byte aligned");
+  g_range = static_cast<uint32_t*>(record_or_null);
+  return PL_OK;
+}
 
 extern "C" int64_t pl_num_hidden(const PLDesc* d) { return d ? 1 + 2 * (int64_t)d->num_stage : PL_EINVAL; }
 extern "C" int64_t pl_param_tensors(const PLDesc* d) { return d ? 4 * (1 + 2 * (int64_t)d->num_stage) + 2 : PL_EINVAL; }
@@ -555,7 +565,7 @@ extern "C" int pl_lifter_fwd_eval(const PLDesc* d, const float* x, float* y, int
       float* out = w.act_f32[l] ? f32(ws, w.act[l]) : f32(ws, w.z[l]);
       PL_TRY(launch_small_layer_eval(a_in, ly.W, ly.b, ly.gamma, ly.beta, d->bn_eps, ly.rm, ly.rv, resid, out,
                                      (int)B, H, ly.K, s, l == 0, last ? d->params + P.off[4 * w.L] : nullptr,
-                                     last ? f32(ws, w.slabs) : nullptr, d->out_dim, sact_in(w, ws, l), sact_out(w, ws, l)));
+                                     last ? f32(ws, w.slabs) : nullptr, d->out_dim, sact_in(w, ws, l), sact_out(w, ws, l), l));
       a_in = out;
     }
     return launch_small_out(f32(ws, w.slabs), H / 16, (int)B, d->out_dim, d->params + P.off[4 * w.L + 1], y, s);
@@ -591,6 +601,7 @@ extern "C" int pl_lifter_fwd_eval(const PLDesc* d, const float* x, float* y, int
     }
     if (w.planes && l + 1 < w.L) {
       PlaneOut po = {u16(ws, w.actp[l]), u16(ws, w.actp[l]) + BH, kActPlaneScale, nullptr, w.pkind};
+      range_watch(po, range_site_act(l));
       PL_TRY(launch_split_planes(out, BH, po, s));
     }
     a_in = out;
@@ -704,7 +715,7 @@ static int fwd_saved_impl(const PLDesc* d, const float* x, float* y, int64_t B, 
       continue;
     }
     PlaneOut po = {nullptr, nullptr, kActPlaneScale, nullptr, 0};
-    if (w.planes && l + 1 < w.L) { po.h = u16(ws, w.actp[l]); po.l = po.h + BH; po.kind = w.pkind; }
+    if (w.planes && l + 1 < w.L) { po.h = u16(ws, w.actp[l]); po.l = po.h + BH; po.kind = w.pkind; range_watch(po, range_site_act(l)); }
     float* act = w.act_f32[l] ? f32(ws, w.act[l]) : nullptr;
     PL_TRY(launch_bn_apply(g.C, scale, shift, resid, act, u64(ws, w.bits[l]), (int)B, H,
                            eval_bn ? 0.f : d->p_dropout, seed, step, l,
@@ -1045,6 +1056,7 @@ extern "C" int pl_gemm_planes(int layout, int mode, const float* A, const float*
   unsigned short* pb = reinterpret_cast<unsigned short*>(static_cast<char*>(scratch) + align_up(M * K * 4, 256));
   const int kind = mode == PL_F16X3 ? 2 : 1;
   PlaneOut oa = {pa, pa + M * K, scale_a, nullptr, kind}, ob = {pb, pb + N * K, scale_b, nullptr, kind};
+  range_watch(oa, PL_RANGE_SITE_SPLIT); range_watch(ob, PL_RANGE_SITE_SPLIT);
   PL_TRY(launch_split_planes(A, M * K, oa, s));
   PL_TRY(launch_split_planes(Bm, N * K, ob, s));
   PlanesGemmArgs g = {};
@@ -1130,6 +1142,7 @@ static int apply_planes_epilogue(GemmArgs& e, int mode, const PLPlanesEpilogue* 
     e.cpl_l = e.cpl_h + n_out;
     e.cpl_scale = kConvActPlaneScale;
     e.cpl_kind = mode == PL_F16X3 ? 2 : 1;
+    e.cpl_range = e.cpl_kind == 2 ? range_record() : nullptr; e.cpl_site = PL_RANGE_SITE_CONV_ACT;
   }
   return PL_OK;
 }

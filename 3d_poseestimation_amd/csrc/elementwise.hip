@@ -1374,7 +1374,7 @@ __global__ __launch_bounds__(NTHR) void adamw_kernel(float* __restrict__ p, cons
         for (int q = 0; q < in.nseg; ++q) {
           const int64_t r = e - in.seg_off[q];
           if (r >= 0 && r < in.seg_n[q]) {
-            const PlaneDst d = {in.seg_h[q], in.seg_l[q], in.pscale, in.kind};
+            const PlaneDst d = {in.seg_h[q], in.seg_l[q], in.pscale, in.kind, 0, in.range, PL_RANGE_SITE_LIFTER_WEIGHT};
             store_planes4(d, (size_t)r, pv);
             break;
           }
@@ -1819,6 +1819,7 @@ extern "C" int pl_adamw_flat_planes(float* p, const float* g, float* m, float* v
     if (!(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v)) || (n & 3))
       PL_FAIL(PL_EINVAL, "pl_adamw_flat_planes: arenas must be 16-byte aligned, n %% 4 == 0");
     in.nseg = planes->nseg; in.kind = planes->kind; in.pscale = planes->scale;
+    in.range = planes->kind == 2 ? range_record() : nullptr;
     for (int q = 0; q < planes->nseg; ++q) {
       const PLAdamWSeg& sg = planes->seg[q];
       if (sg.offset < 0 || sg.numel <= 0 || (sg.offset & 3) || (sg.numel & 3) || sg.offset + sg.numel > n || !sg.h ||
@@ -1972,10 +1973,16 @@ int pl::plane_out_of(int mode, void* planes, int64_t n, float scale, const float
 
 extern "C" float pl_conv_act_plane_scale(void) { return kConvActPlaneScale; }
 
+// the range guard's slot of a caller-scaled split: the conv path's two scales are named, anything else is "a split"
+static int split_site(float scale) {
+  return scale == kConvActPlaneScale ? PL_RANGE_SITE_CONV_ACT : scale == kWeightPlaneScale ? PL_RANGE_SITE_CONV_WEIGHT : PL_RANGE_SITE_SPLIT;
+}
+
 extern "C" int pl_planes_split(const float* x, int64_t n, int mode, float scale, void* planes, void* stream) {
   if (!x || !planes || n <= 0 || !(scale > 0.f)) PL_FAIL(PL_EINVAL, "pl_planes_split: bad arguments");
   PlaneOut po;
   PL_TRY(plane_out_of(mode, planes, n, scale, nullptr, &po, "pl_planes_split"));
+  range_watch(po, split_site(scale));
   return launch_split_planes(x, n, po, (hipStream_t)stream);
 }
 
@@ -1990,6 +1997,7 @@ extern "C" int pl_planes_split_strided(const float* x, const int64_t* dims, cons
   const int64_t n = dims[0] * dims[1] * dims[2] * dims[3];
   PlaneOut po;
   PL_TRY(plane_out_of(mode, planes, n, scale, nullptr, &po, "pl_planes_split_strided"));
+  range_watch(po, split_site(scale));
   const Strided4 v = {(int)dims[1], (int)dims[2], (int)dims[3], strides[0], strides[1], strides[2], strides[3]};
   const int64_t n4 = n >> 2;
   int blocks = (int)((n4 + 255) / 256);
@@ -2015,6 +2023,7 @@ extern "C" int pl_bn_train_fwd_ex(const float* z, int64_t rows, int64_t C, const
   if (!z || !gamma || !beta || (!y && !y_planes) || !bits || !mean || !rstd || !scratch) PL_FAIL(PL_EINVAL, "pl_bn_train_fwd: null pointer");
   PlaneOut ypo;
   PL_TRY(plane_out_of(planes_mode, y_planes, rows * C, kConvActPlaneScale, nullptr, &ypo, "pl_bn_train_fwd_ex"));
+  range_watch(ypo, PL_RANGE_SITE_CONV_ACT);
   if (rows < 2 || rows > INT32_MAX || C <= 0 || (C & 3)) PL_FAIL(rows < 2 ? PL_EBATCH : PL_ESHAPE, "pl_bn_train_fwd: rows=%lld C=%lld (C %% 4 == 0, rows >= 2)", (long long)rows, (long long)C);
   hipStream_t s = (hipStream_t)stream;
   const int R = bn_replicas(rows, C);
@@ -2132,6 +2141,7 @@ extern "C" int pl_add_relu_fwd_ex(const float* a, const float* b, int64_t rows, 
   if (rows <= 0 || rows > INT32_MAX || C <= 0 || (C & 3)) PL_FAIL(PL_ESHAPE, "pl_add_relu_fwd: rows=%lld C=%lld", (long long)rows, (long long)C);
   PlaneOut po;
   PL_TRY(plane_out_of(planes_mode, out_planes, rows * C, kConvActPlaneScale, nullptr, &po, "pl_add_relu_fwd_ex"));
+  range_watch(po, PL_RANGE_SITE_CONV_ACT);
   const int strips = ((int)C + 255) / 256;
   dim3 grid(strips, stream_rows_grid((int)rows, strips));
   hipLaunchKernelGGL(add_relu_kernel, grid, dim3(NTHR), 0, (hipStream_t)stream, a, b, out, bits, (int)rows, (int)C, po);

@@ -98,7 +98,9 @@ __device__ __forceinline__ void staged_epilogue(const PlanesKern& k, float* __re
       }
     }
   }
-  const PlaneDst cpd = {e.cpl_h, e.cpl_l, e.cpl_scale, plain ? 0 : e.cpl_kind, k.nt_store};      // the result as the next GEMM's operand planes
+  // the result as the next GEMM's operand planes
+  const PlaneDst cpd = {e.cpl_h, e.cpl_l, e.cpl_scale, plain ? 0 : e.cpl_kind, k.nt_store, e.cpl_range, e.cpl_site};
+  float cpl_over = 0.f;                          // range guard of those planes: one flush behind the stores (plane_store.h)
   if (EDGE && e.scat_on) {                       // one output parity of a transposed convolution (GemmArgs::scat_*)
 #pragma unroll
     for (int it = 0; it < 16; ++it) {
@@ -108,8 +110,9 @@ __device__ __forceinline__ void staged_epilogue(const PlanesKern& k, float* __re
       const int a = t % e.conv_ho, b = t / e.conv_ho;
       const size_t orow = ((size_t)b * 2 * e.conv_ho + 2 * a + e.scat_ph) * 2 * e.conv_wo + 2 * c + e.scat_pw;
       if (C) *reinterpret_cast<float4*>(C + orow * e.ldc + col0) = v[it];
-      if (cpd.kind) store_planes4(cpd, orow * e.ldc + col0, v[it]);
+      if (cpd.kind) store_planes4(cpd, orow * e.ldc + col0, v[it], &cpl_over);
     }
+    if (cpd.kind == 2 && cpd.range) range_flush(cpd.range, cpd.site, cpl_over);
     return;
   }
   if (k.nt_store && C) {
@@ -119,16 +122,17 @@ __device__ __forceinline__ void staged_epilogue(const PlanesKern& k, float* __re
       if (ok(it)) {
         const f4v q = {v[it].x, v[it].y, v[it].z, v[it].w};
         __builtin_nontemporal_store(q, reinterpret_cast<f4v*>(C + o0 + (size_t)it * 4 * e.ldc));
-        if (cpd.kind) store_planes4(cpd, o0 + (size_t)it * 4 * e.ldc, v[it]);
+        if (cpd.kind) store_planes4(cpd, o0 + (size_t)it * 4 * e.ldc, v[it], &cpl_over);
       }
   } else {
 #pragma unroll
   for (int it = 0; it < 16; ++it)
     if (ok(it)) {
       if (C) *reinterpret_cast<float4*>(C + o0 + (size_t)it * 4 * e.ldc) = v[it];
-      if (cpd.kind) store_planes4(cpd, o0 + (size_t)it * 4 * e.ldc, v[it]);
+      if (cpd.kind) store_planes4(cpd, o0 + (size_t)it * 4 * e.ldc, v[it], &cpl_over);
     }
   }
+  if (cpd.kind == 2 && cpd.range) range_flush(cpd.range, cpd.site, cpl_over);
   if (plain) return;
   if (e.stat_sum) {
     // training-mode BatchNorm partial statistics of this 64-row block (sum and M2 about the block's own mean); lanes l,

@@ -76,6 +76,7 @@ struct GemmArgs {
   // planes GEMM (staged epilogue): the result ALSO (C != NULL) or ONLY (C == NULL) as operand planes of the next GEMM --
   // cpl_kind 0 none, 1 one bf16 plane, 2 fp16 pair (h, l) of cpl_scale * value; addressed like C (row * ldc + col)
   unsigned short* cpl_h; unsigned short* cpl_l; float cpl_scale; int cpl_kind;
+  uint32_t* cpl_range; int cpl_site;      // range guard of those planes (PlaneOut::range / site)
   // planes convolution launches only: row m = (b, a, c) of a conv_ho x conv_wo grid is stored at pixel
   // (b, 2a + scat_ph, 2c + scat_pw) of a [B][2 conv_ho][2 conv_wo][ldc] map (one output parity of a 4x4 stride-2
   // transposed convolution); plain stores only
@@ -107,7 +108,16 @@ struct PlaneOut {
   const float* dyn;
   int kind;
   int nt;             // the tensor (planes and its fp32 twin) leaves with nontemporal stores: far larger than the caches
+  uint32_t* range;    // range guard (static scales, kind 2): the caller's record or NULL, and this writer's slot in it
+  int site;
 };
+// The range guard's record for launches enqueued by this thread (pl_range_monitor; NULL = none), and a static-scale PlaneOut
+// joined to it: fp16 planes only, and never planes scaled on the device.
+uint32_t* range_record();
+inline int range_site_act(int layer) { return PL_RANGE_SITE_LIFTER_ACT + (layer < 7 ? layer : 7); }
+inline void range_watch(PlaneOut& po, int site) {
+  if (po.kind == 2 && !po.dyn) { po.range = range_record(); po.site = site; }
+}
 // outputs at least this large are streamed past the caches (their consumer reads them from HBM whatever the store policy)
 constexpr long long kNontemporalBytes = 64ll << 20;
 constexpr float kActPlaneScale = 1.0f;      // activations: fp16 covers 6e-5 .. 65504 in h, the remainder in l
@@ -237,7 +247,7 @@ int launch_small_layer_fwd(const float* a, const float* W, const float* bias, co
 int launch_small_layer_eval(const float* a, const float* W, const float* bias, const float* gamma, const float* beta, float eps,
                             const float* rm, const float* rv, const float* resid, float* act, int M, int H, int K, hipStream_t s,
                             bool first = false, const float* W2 = nullptr, float* ypart = nullptr, int O = 0,
-                            const unsigned short* a_planes = nullptr, unsigned short* out_planes = nullptr);
+                            const unsigned short* a_planes = nullptr, unsigned short* out_planes = nullptr, int layer = 0);
 int launch_small_out(const float* ypart, int NS, int M, int O, const float* bias, float* y, hipStream_t s);
 // the Linear alone with the statistics partials of a tile GEMM's epilogue, for TRAINING batches of 65 ... 512 rows: the tile
 // GEMMs have 8 ... 32 tiles for 256 CUs there (22 us per forward GEMM at any of these sizes; this form: 9-17 us)

@@ -144,7 +144,7 @@ typedef _Float16 f16x4h __attribute__((ext_vector_type(4)));
 template <int STEPS>
 __device__ __forceinline__ void contract_f16(const unsigned short* __restrict__ Ah, size_t a_plane, int lda, int M,
                                              const float* __restrict__ Bm, int ldb, int c0, float w_scale, float out_scale,
-                                             float* __restrict__ part, float* __restrict__ stage) {
+                                             float* __restrict__ part, float* __restrict__ stage, uint32_t* range) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int i = lane & 15, kq = lane >> 4;
   const int kb = wave * STEPS * 32;
@@ -174,6 +174,7 @@ __device__ __forceinline__ void contract_f16(const unsigned short* __restrict__ 
   f32x4 acc0[4], acc1[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t) { acc0[t] = f32x4{0.f, 0.f, 0.f, 0.f}; acc1[t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+  float w_over = 0.f;                       // range guard of the weight split below: flushed once behind the loop
 #pragma unroll
   for (int s = 0; s < STEPS; ++s) {
     {
@@ -186,6 +187,7 @@ __device__ __forceinline__ void contract_f16(const unsigned short* __restrict__ 
       }
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
+        if (range) w_over = range_over4(w_over, gb[s][j], w_scale);
         const float a[4] = {gb[s][j].x * w_scale, gb[s][j].y * w_scale, gb[s][j].z * w_scale, gb[s][j].w * w_scale};
         f16x4h hh, ll;
 #pragma unroll
@@ -218,6 +220,7 @@ __device__ __forceinline__ void contract_f16(const unsigned short* __restrict__ 
 #pragma unroll
     for (int v = 0; v < 4; ++v)
       mine[(16 * t + 4 * kq + v) * COLS + i] = fmaf(acc1[t][v], 1.0f / 2048.0f, acc0[t][v]) * out_scale;
+  if (range) range_flush(range, PL_RANGE_SITE_LIFTER_WEIGHT, w_over);
 }
 
 // the epilogue's element of thread tid < 256: row tid >> 2 (= 16 wave + (lane >> 2)), columns c0 + 4 (tid & 3) .. + 3
@@ -302,6 +305,10 @@ struct FwdArgs {
   const unsigned short* ap;
   unsigned short* outp;
   size_t a_plane, o_plane;
+  // the range guard's record or NULL (pl_internal.h range_record): outp is noted at slot `site`, the weight split of the
+  // planes contraction at the weight slot
+  uint32_t* range;
+  int site;
   // the Linear alone, for training batches of 65 ... 512 rows (stats = 1): z = a W^T + b and the partial BatchNorm statistics a
   // tile GEMM's epilogue emits (per 64-row group: column sums, and sums of squares about the group mean -- stat_sum / stat_m2
   // [groups][H], zeros for groups past the last row; NULL: none); the grid runs over the groups like an evaluation's
@@ -353,7 +360,7 @@ __device__ __forceinline__ float4 eval_tail(const FwdArgs& p, float4 z, const Fw
   y.z = fmaxf(fmaf(z.z, sz, fmaf(q.bias.z - q.rmean.z, sz, q.be.z)), 0.f) + q.rv.z;
   y.w = fmaxf(fmaf(z.w, sw, fmaf(q.bias.w - q.rmean.w, sw, q.be.w)), 0.f) + q.rv.w;
   st4(p.act + (size_t)r * p.H + c, y);
-  if (p.outp) store_planes4(PlaneDst{p.outp, p.outp + p.o_plane, kActPlaneScale, 2, 0}, (size_t)r * p.H + c, y);
+  if (p.outp) store_planes4(PlaneDst{p.outp, p.outp + p.o_plane, kActPlaneScale, 2, 0, p.range, p.site}, (size_t)r * p.H + c, y);
   return y;
 }
 // Returns the thread's four outputs (zeros outside the batch and for threads >= 256).
@@ -442,7 +449,7 @@ __device__ __forceinline__ float4 fwd_tail(const FwdArgs& p, float4 z, const Fwd
   const float4 out = make_float4(o[0] + rv.x, o[1] + rv.y, o[2] + rv.z, o[3] + rv.w);
   if (live) {
     st4(p.act + (size_t)r * p.H + c, out);
-    if (p.outp) store_planes4(PlaneDst{p.outp, p.outp + p.o_plane, kActPlaneScale, 2, 0}, (size_t)r * p.H + c, out);
+    if (p.outp) store_planes4(PlaneDst{p.outp, p.outp + p.o_plane, kActPlaneScale, 2, 0, p.range, p.site}, (size_t)r * p.H + c, out);
   }
   return live ? out : zero;
 }
@@ -523,7 +530,7 @@ __global__ __launch_bounds__(NTHR) void small_fwd_kernel(FwdArgs p_in) {
   const FwdPre pre = fwd_prefetch(p, c);
   if (p.ap)
     contract_f16<STEPS>(p.ap, p.a_plane, p.K, p.B, p.W, p.K, c0, kWeightPlaneScale, 1.0f / (kActPlaneScale * kWeightPlaneScale), part,
-                        stage);
+                        stage, p.range);
   else contract<STEPS, false>(p.a, p.K, p.B, p.W, p.K, c0, part, stage);
   __syncthreads();
   float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -931,7 +938,7 @@ int launch_small_out(const float* ypart, int NS, int M, int O, const float* bias
 int launch_small_layer_eval(const float* a, const float* W, const float* bias, const float* gamma, const float* beta, float eps,
                             const float* rm, const float* rv, const float* resid, float* act, int M, int H, int K, hipStream_t s,
                             bool first, const float* W2, float* ypart, int O, const unsigned short* a_planes,
-                            unsigned short* out_planes) {
+                            unsigned short* out_planes, int layer) {
   if (first ? !(small_layer_ok(2, H, H) && small_first_ok(K)) : !small_layer_ok(2, H, K))
     PL_FAIL(PL_ESHAPE, "small_layer_eval: H=%d K=%d first=%d", H, K, (int)first);
   if (!a || !W || !bias || !gamma || !beta || !rm || !rv || !act || M < 1) PL_FAIL(PL_EINVAL, "small_layer_eval: bad arguments");
@@ -948,6 +955,7 @@ int launch_small_layer_eval(const float* a, const float* W, const float* bias, c
   }
   if ((a_planes && (first || !al16(a_planes))) || !al16(out_planes)) PL_FAIL(PL_EINVAL, "small_layer_eval: operand planes");
   p.ap = a_planes; p.a_plane = (size_t)M * K; p.outp = out_planes; p.o_plane = (size_t)M * H;
+  p.range = range_record(); p.site = range_site_act(layer);
   const dim3 grid(H / COLS, (M + ROWS - 1) / ROWS), block(NTHR);
   void* prof = prof_begin_flops(2.0 * M * H * K, s);
   if (first) hipLaunchKernelGGL(small_first_fwd_kernel, grid, block, 0, s, p);
@@ -975,7 +983,7 @@ int launch_small_linear_stats(const float* a, const unsigned short* a_planes, co
   FwdArgs p = {};
   p.a = a; p.W = W; p.bias = bias; p.z = z; p.B = ROWS; p.H = H; p.K = K; p.Mtot = M; p.stats = 1;
   p.stat_sum = stat_sum; p.stat_m2 = stat_m2;
-  p.ap = a_planes; p.a_plane = (size_t)M * K;
+  p.ap = a_planes; p.a_plane = (size_t)M * K; p.range = range_record();
   if (!a) p.a = reinterpret_cast<const float*>(a_planes);     // (never read: the planes form is taken)
   const dim3 grid(H / COLS, stat_sum ? groups : (M + ROWS - 1) / ROWS), block(NTHR);
   void* prof = prof_begin_flops(2.0 * M * H * K, s);
@@ -1019,6 +1027,7 @@ int launch_small_layer_fwd(const float* a, const float* W, const float* bias, co
   }
   if ((a_planes && (first || !al16(a_planes))) || !al16(out_planes)) PL_FAIL(PL_EINVAL, "small_layer_fwd: operand planes");
   p.ap = a_planes; p.a_plane = (size_t)B * K; p.outp = out_planes; p.o_plane = (size_t)B * H;
+  p.range = range_record(); p.site = range_site_act(layer);
   const dim3 grid(H / COLS), block(NTHR);
   void* prof = prof_begin_flops(2.0 * B * H * K, s);
   if (first) {

@@ -138,9 +138,13 @@ class LinearModel(nn.Module):
     """compute_dtype: "fp32" (exact fp32 MFMA), "bf16x6" and "f16x3" (fp32-grade: meet the 1e-3 mm gate), "bf16" (bf16 operand
     storage, ~1 mm).  Range contract of "f16x3": the 1024-wide layers' activations are stored as fp16 planes at scale 1, so a
     hidden activation must stay below 65504 in magnitude (the conv path stores at 1/64: 4.2e6).  A training-mode BatchNorm
-    output is at most gamma * sqrt(B) + |beta| and the block adds two of them, so only weights in the thousands can get there;
-    nothing checks it at run time (an overflowing value becomes inf where "fp32" / "bf16x6" stay finite) -- use one of those
-    for models outside the contract.  Gradients have no such limit: dz is range-scaled on the device per layer and step."""
+    output is at most gamma * sqrt(B) + |beta| and the block adds two of them, so only weights in the thousands can get there.
+    An overflowing value becomes inf where "fp32" / "bf16x6" stay finite; the range guard (range_guard.py) records it on the
+    device, per site and with its magnitude, and `range_guard.check()` -- one small read, wherever the loop already
+    synchronises -- raises PoseliftRangeError naming the layer and the remedy: use "bf16x6" or "fp32" for models outside the
+    contract.  The guard is OFF by default, `range_guard.enable()` turns it on: enabled, the bench step at B = 4096 measured
+    0.627 ms against 0.617 (three interleaved runs each, the parent's own spread 0.005) and the phase5 cycle step 92.3 ms
+    against 91.7 (spread 0.3).  Gradients have no such limit: dz is range-scaled on the device per layer and step."""
 
     def __init__(self, i_dim, o_dim, linear_size=1024, num_stage=2, p_dropout=0.5, BN=True,
                  compute_dtype="fp32"):

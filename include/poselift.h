@@ -468,6 +468,23 @@ size_t pl_wplanes_layer_bytes(const PLDesc* d);
 float pl_weight_plane_scale(void);
 int pl_wplanes_refresh(const PLDesc* d, void* stream);   /* planes <- current parameters (wplanes_valid is ignored) */
 
+/* ---- PL_F16X3 range guard ---------------------------------------------------------- */
+/* PL_F16X3 stores activations, weights and conv-path feature maps as fp16 planes at STATIC scales (activations 1, weights
+ * 16, conv-path maps 1/64): a finite fp32 value v with |S v| > 65504 becomes inf in its plane and NaN in the next GEMM.
+ * With a record set, every kernel that writes such a plane also notes that it saw one: record[site] (the caller's
+ * PL_RANGE_SITES device words, zeroed by the caller) takes, by an atomic maximum, the fp32 bit pattern of the largest
+ * UNSCALED |v| that left the range at that site; 0 = clean.  inf / NaN sources are not recorded, planes with a scale
+ * chosen on the device (dz, dlogits) cannot leave the range, and the planes themselves are written exactly as without a
+ * record.  pl_range_monitor sets the record of the CALLING THREAD's later calls (NULL, the initial state: none); the pointer
+ * is read when a call enqueues its launches, so it is part of a captured graph and must outlive it.  Returns PL_OK. */
+#define PL_RANGE_SITES 16
+#define PL_RANGE_SITE_LIFTER_ACT 0     /* .. 7: output of the lifter's hidden layer l at min(l, 7) (scale 1)       */
+#define PL_RANGE_SITE_LIFTER_WEIGHT 8  /* the lifter's 1024-wide weight planes (scale 16)                          */
+#define PL_RANGE_SITE_CONV_ACT 9       /* conv-path feature maps (scale pl_conv_act_plane_scale())                 */
+#define PL_RANGE_SITE_CONV_WEIGHT 10   /* pl_planes_split* at scale 16: the conv path's weights                     */
+#define PL_RANGE_SITE_SPLIT 11         /* pl_planes_split*, pl_gemm_planes at any other scale                       */
+int pl_range_monitor(void* record_or_null);
+
 /* ---- building blocks exported for tests ------------------------------------------ */
 /* C[M][N] = op(A) op(B) on the fp32 MFMA path.
  * layout 0 (NT): A [M][K], B [N][K]   (forward  z = a W^T)
