@@ -1,6 +1,7 @@
-// Register epilogue shared by the fp32-operand GEMM (gemm_f32.hip) and the planes GEMM (gemm_planes.hip): same
-// accumulator layout (4 wavefronts 2x2, 64x64 each as 2x2 MFMA tiles of 32x32), same bias / eval-BN fold / ReLU /
-// residual / training-mode BatchNorm partial statistics, so the two main loops are interchangeable bit for bit.
+// Register epilogue shared by the main loops of the fp32-operand GEMM (gemm_f32.hip): one accumulator layout (4 wavefronts
+// 2x2, 64x64 each as 2x2 MFMA tiles of 32x32), one bias / eval-BN fold / ReLU / residual / training-mode BatchNorm partial
+// statistics, so those main loops are interchangeable bit for bit.  (The planes GEMM, gemm_planes.hip, has its own staged
+// epilogue: the same element order, float4 stores.)
 #pragma once
 #include "pl_internal.h"
 

@@ -2,9 +2,10 @@
 // PL_F16X3 (fp32-grade, three fp16 MFMAs per product term) and PL_BF16 (bf16 storage) modes.
 //
 // Replaces the ATen addmm calls behind nn.Linear forward / backward (reference phase1_lifting/baselineModel.py:33,39
-// and their autograd), like gemm_f32.hip; same 128x128 tile per workgroup, same register epilogue (gemm_epilogue.h:
-// bias, training-mode BatchNorm partial statistics, eval-mode BN fold + ReLU + skip, residual-gradient addend, split-K
-// slabs).  512 threads: wavefronts 0-3 compute, wavefronts 4-7 drive the LDS-DMA.
+// and their autograd), like gemm_f32.hip; same 128x128 tile per workgroup, the element order of its register epilogue
+// (gemm_epilogue.h) in an epilogue of its own (staged_epilogue below: bias, training-mode BatchNorm partial statistics,
+// eval-mode BN fold + ReLU + skip, residual-gradient addend, split-K slabs).  512 threads: wavefronts 0-3 compute,
+// wavefronts 4-7 drive the LDS-DMA.
 #include "gemm_planes16.h"
 #include "pl_internal.h"
 #include "plane_store.h"
@@ -149,14 +150,24 @@ __device__ __forceinline__ void staged_epilogue(const PlanesKern& k, float* __re
     const int cnt = EDGE ? max(0, min(64, nrows)) : 64;
     const float inv = cnt > 0 ? 1.0f / (float)cnt : 0.f;
     const float4 mean = make_float4(s.x * inv, s.y * inv, s.z * inv, s.w * inv);
-    float4 m2 = make_float4(0.f, 0.f, 0.f, 0.f);
+    // corrected two-pass form (Chan, Golub, LeVeque): the fp32 mean misses the true one by a rounding d0, which adds
+    // cnt d0^2 to the plain sum of squares -- all there is on a constant column; (sum d)^2 / cnt takes it out again.
+    // Only here: pl_gemm_planes_raw hands these partials to its caller, and they are held to an M2 floor of their own
+    // (K 2^-24 n s^2 u, tests/test_gpu_bn_conditioning.py c.).  The fp32 routes' partials (gemm_epilogue.h, gemm_thin.hip,
+    // skinny.hip, small_layer.hip) keep the plain sum about the group mean: they only feed the finalize, where cnt d0^2 is
+    // second order -- d0 <~ 2^-24 |mean| rounding units, so d0^2 / s^2 ~ u^2 against the stated u for mean, rstd and zhat.
+    float4 m2 = make_float4(0.f, 0.f, 0.f, 0.f), sd = m2;
 #pragma unroll
     for (int it = 0; it < 16; ++it) {
       if (EDGE && !ok(it)) continue;
       const float dx = v[it].x - mean.x, dy = v[it].y - mean.y, dz = v[it].z - mean.z, dw = v[it].w - mean.w;
       m2.x = fmaf(dx, dx, m2.x); m2.y = fmaf(dy, dy, m2.y); m2.z = fmaf(dz, dz, m2.z); m2.w = fmaf(dw, dw, m2.w);
+      sd.x += dx; sd.y += dy; sd.z += dz; sd.w += dw;
     }
     m2 = xadd_rows(m2);
+    sd = xadd_rows(sd);
+    m2.x = fmaxf(fmaf(-sd.x * inv, sd.x, m2.x), 0.f); m2.y = fmaxf(fmaf(-sd.y * inv, sd.y, m2.y), 0.f);
+    m2.z = fmaxf(fmaf(-sd.z * inv, sd.z, m2.z), 0.f); m2.w = fmaxf(fmaf(-sd.w * inv, sd.w, m2.w), 0.f);
     // (the consumers walk 2 ceil(M / 128) groups, empty ones included -- gemm_stat_groups; a wave block of a 256-row tile
     //  below that has no group)
     if (lr == 0 && cok && (!EDGE || (m0 >> 6) + wm < 2 * ((e.M + 127) >> 7))) {

@@ -309,8 +309,8 @@ struct FwdArgs {
   // planes contraction at the weight slot
   uint32_t* range;
   int site;
-  // the Linear alone, for training batches of 65 ... 512 rows (stats = 1): z = a W^T + b and the partial BatchNorm statistics a
-  // tile GEMM's epilogue emits (per 64-row group: column sums, and sums of squares about the group mean -- stat_sum / stat_m2
+  // the Linear alone, for training batches of 65 ... 512 rows (stats = 1): z = a W^T + b and partial BatchNorm statistics in the
+  // layout of a tile GEMM's epilogue (per 64-row group: column sums, and plain sums of squares about the group mean -- stat_sum / stat_m2
   // [groups][H], zeros for groups past the last row; NULL: none); the grid runs over the groups like an evaluation's
   int stats;
   float *stat_sum, *stat_m2;
