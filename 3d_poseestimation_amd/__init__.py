@@ -11,8 +11,9 @@ from .train import (cycle_step, epoch_mpjpe_mm, eval_step, flip_average, flip_fr
                     predict_flip_tta, train_step, GraphedTrainStep, GraphedModuleStep)
 from .heads import soft_argmax_2d, soft_argmax_3d, soft_argmax_3d_nhwc  # noqa: F401
 from .losses import TriangleLoss, l1_loss, l1_terms  # noqa: F401
+from .metrics import AUC_THRESHOLDS, PoseMetrics, pose_errors, procrustes_align  # noqa: F401
 from .backbone import Model_2D, Model_3D, ResNet  # noqa: F401
 from .data import PoseFeeder, epoch_indices  # noqa: F401
 from .vit import MyViT  # noqa: F401
 from .range_guard import PoseliftRangeError  # noqa: F401
-from . import arena, backbone, conv, data, dp, layout, range_guard, synth, vit  # noqa: F401
+from . import arena, backbone, conv, data, dp, layout, metrics, range_guard, synth, vit  # noqa: F401

@@ -388,13 +388,17 @@ def predict_flip_tta(model, y1, out_dims=3):
 
 
 @torch.no_grad()
-def eval_step(model, y1, y2, metric_out=None, flip=False):
+def eval_step(model, y1, y2, metric_out=None, flip=False, meter=None, group_ids=None):
     """train_1.py:112-145 body (model must be in eval mode): forward, MSE, loss_MPJPE.
-    flip=True: flip test-time augmentation (predict_flip_tta)."""
+    flip=True: flip test-time augmentation (predict_flip_tta).
+    meter: a metrics.PoseMetrics that also takes this batch (P-MPJPE, N-MPJPE, PCK; group_ids (B,) = e.g. the action of
+    each pose); like everything here it only enqueues work."""
     y1, y2 = y1.float(), y2.float()
     y2_hat = predict_flip_tta(model, y1, y2.shape[-1]).reshape(y2.shape) if flip else model(y1).reshape(y2.shape)
     loss = mse_loss(y2_hat, y2)
     metric = loss_MPJPE(y2_hat, y2, out=metric_out)
+    if meter is not None:
+        meter.update(y2_hat, y2, group_ids)
     return loss, metric, y2_hat
 
 

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define PL_VERSION 111 /* 0.1.11: + pl_vit_*_bf16, pl_vit_bf16_pack (MyViT "bf16p": bf16 operand carriers written by their producers); 0.1.10: + pl_vit_* (the MyViT transformer lifter); 0.1.9: + pl_conv2d_planes_fwd_hw, pl_conv2d_planes_wgrad_hw (the stem on the planes GEMM); 0.1.8: + pl_lifter_train_step, pl_lifter_step_carries_adamw; 0.1.7: + pl_workspace_bitmap_format (small-batch layer kernels); 0.1.6: + pl_counter_add; 0.1.5: + pl_flip_pose_ex, pl_flip_w_nhwc (phase5 Flip branch); 0.1.4: + pl_planes_split_strided; 0.1.3: + pl_bn_join_bwd (0.1.2: operand-plane outputs of the BatchNorm / join kernels, pl_gemm_planes_raw) */
+#define PL_VERSION 112 /* 0.1.12: + pl_pose_errors, pl_pose_errors_host, pl_pose_metrics_scratch_bytes, pl_pose_metrics_accum (evaluation: MPJPE / N-MPJPE / P-MPJPE, PCK counts, per group); 0.1.11: + pl_vit_*_bf16, pl_vit_bf16_pack (MyViT "bf16p": bf16 operand carriers written by their producers); 0.1.10: + pl_vit_* (the MyViT transformer lifter); 0.1.9: + pl_conv2d_planes_fwd_hw, pl_conv2d_planes_wgrad_hw (the stem on the planes GEMM); 0.1.8: + pl_lifter_train_step, pl_lifter_step_carries_adamw; 0.1.7: + pl_workspace_bitmap_format (small-batch layer kernels); 0.1.6: + pl_counter_add; 0.1.5: + pl_flip_pose_ex, pl_flip_w_nhwc (phase5 Flip branch); 0.1.4: + pl_planes_split_strided; 0.1.3: + pl_bn_join_bwd (0.1.2: operand-plane outputs of the BatchNorm / join kernels, pl_gemm_planes_raw) */
 
 typedef enum PLStatus {
   PL_OK = 0,
@@ -395,6 +395,35 @@ int pl_l1_terms_fwd_bwd(const PLL1Term* terms, int nterms, float grad_scale, flo
 size_t pl_mpjpe_scratch_bytes(int64_t B, int64_t joints);
 int pl_mpjpe_accum(const float* pred, const float* tgt, int64_t B, int64_t joints,
                    float* metric, void* scratch, void* stream);
+
+/* ---- evaluation: MPJPE, N-MPJPE, P-MPJPE per pose and joint; sums and PCK counts per group --------------------------
+ * The reference reports protocol-1 MPJPE only (train_1.py:19-23,100-104); these are the other columns of the usual
+ * Human3.6M table.  pred / tgt [B][J][3] fp32, 3 <= J <= 32, 16-byte aligned.  Per pose, with rows P_j, T_j:
+ *   err[0][b][j] = ||P_j - T_j||                                             MPJPE
+ *   err[1][b][j] = ||s P_j - T_j||,  s = sum P.T / sum P.P (0 if sum P.P = 0; no centring)            N-MPJPE
+ *   err[2][b][j] = ||a R (P_j - muP) + muT - T_j||                           P-MPJPE
+ * where R is the best PROPER rotation of the centred prediction P0 onto the centred target T0 (a reflected prediction is
+ * not flipped back: the SVD recipe with the determinant fix) and a = tr(R P0^T T0) / ||P0||^2 the best scale (0 if
+ * ||P0||^2 = 0: a collapsed prediction is scored against the target's centroid, a collapsed target scores 0).  A NaN in a
+ * pose makes that pose's N-MPJPE, P-MPJPE and aligned outputs NaN (MPJPE: at the joints that hold one) and touches no
+ * other pose.  aligned_or_null [B][J][3]: a R (P_j - muP) + muT.
+ * One launch, one lane per pose, no atomics: the same inputs give the same bits.
+ * pl_pose_errors_host: the same inline arithmetic compiled for the CPU, on host pointers (a test hook). */
+int pl_pose_errors(const float* pred, const float* tgt, int64_t B, int64_t J, float* err /* [3][B][J] */,
+                   float* aligned_or_null, void* stream);
+int pl_pose_errors_host(const float* pred, const float* tgt, int64_t B, int64_t J, float* err, float* aligned_or_null);
+/* Accumulate err [3][B][J] (pl_pose_errors) into per-group totals, in place:
+ *   sums   [G][3][J]     fp32   += sum of errors of the poses of group g
+ *   counts [G][3][T][J]  int64  += number of those errors <= thr[t] (inclusive)        (may be NULL when n_thr = 0)
+ *   n_poses [G + 1]      int64  += poses of group g; cell G counts the poses whose id is outside [0, G), which add to
+ *                                  nothing else (the host reports them; nothing traps on the device)
+ * group_or_null [B] int32 (NULL: every pose is group 0); 1 <= groups <= 32; thr_or_null [n_thr] fp32, 0 <= n_thr <= 32.
+ * Two launches (per-chunk partials into scratch >= pl_pose_metrics_scratch_bytes(B, J, groups, n_thr), then one thread
+ * per cell), no atomics, a fixed order of every sum. */
+size_t pl_pose_metrics_scratch_bytes(int64_t B, int64_t J, int groups, int n_thr);
+int pl_pose_metrics_accum(const float* err, int64_t B, int64_t J, const int32_t* group_or_null, int groups,
+                          const float* thr_or_null, int n_thr, float* sums, int64_t* counts, int64_t* n_poses,
+                          void* scratch, void* stream);
 
 /* *counter += delta on the stream (one thread).  The optimizer of a step replayed from a hipGraph keeps its step count on
  * the device: pl_adamw_flat_dev reads t = t_base + *t_dev, this call ticks it behind the update (arena.FlatAdam for the
