@@ -9,8 +9,9 @@ from .optim import FlatAdamW  # noqa: F401
 from .arena import FlatAdam, ModuleArena  # noqa: F401
 from .train import (cycle_step, epoch_mpjpe_mm, eval_step, flip_average, flip_frames_nhwc, flip_pose, loss_MPJPE, mse_loss,  # noqa: F401
                     predict_flip_tta, train_step, GraphedTrainStep, GraphedModuleStep)
-from .heads import soft_argmax_2d, soft_argmax_3d, soft_argmax_3d_nhwc  # noqa: F401
-from .losses import TriangleLoss, l1_loss, l1_terms  # noqa: F401
+from .heads import (gaussian_heatmap, heatmap_law, soft_argmax_2d, soft_argmax_2d_hm, soft_argmax_3d,  # noqa: F401
+                    soft_argmax_3d_hm, soft_argmax_3d_nhwc, soft_argmax_3d_nhwc_hm)
+from .losses import TriangleLoss, heatmap_mse, l1_loss, l1_terms  # noqa: F401
 from .metrics import AUC_THRESHOLDS, PoseMetrics, pose_errors, procrustes_align  # noqa: F401
 from .backbone import Model_2D, Model_3D, ResNet  # noqa: F401
 from .data import PoseFeeder, epoch_indices  # noqa: F401

@@ -168,6 +168,17 @@ SIGNATURES = {
     "pl_softargmax_fwd": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int, _P, _P, _P]),
     "pl_softargmax_bwd": (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int,
                                      _P, _P]),
+    "pl_heatmap_gaussian": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int, _c.c_float, _P, _P, _P]),
+    "pl_heatmap_gaussian_host": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int, _c.c_float, _P, _P]),
+    "pl_softargmax_hm_fwd": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int, _c.c_float,
+                                        _P, _P, _P, _P, _P]),
+    "pl_softargmax3d_nhwc_hm_fwd": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_float, _P, _P, _P,
+                                               _P, _P]),
+    "pl_softargmax_hm_bwd": (_c.c_int, [_P, _P, _P, _P, _P, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int,
+                                        _c.c_float, _P, _P, _P]),
+    "pl_softargmax3d_nhwc_hm_bwd_ex": (_c.c_int, [_P, _P, _P, _P, _P, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_float,
+                                                  _P, _P, _P, _c.c_int, _P, _P]),
+    "pl_softargmax_hm_dl_scale": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int, _P, _P]),
     "pl_gemm_f32": (_c.c_int, [_c.c_int, _P, _P, _P, _c.c_int64, _c.c_int64, _c.c_int64, _P,
                                _c.c_int, _P, _P]),
     "pl_gemm_arith": (_c.c_int, [_c.c_int, _c.c_int, _P, _P, _P, _c.c_int64, _c.c_int64, _c.c_int64, _P,

@@ -24,7 +24,8 @@ import torch
 import torch.nn as nn
 
 from . import conv
-from .heads import soft_argmax_2d, soft_argmax_3d, soft_argmax_3d_nhwc
+from .heads import (soft_argmax_2d, soft_argmax_2d_hm, soft_argmax_3d, soft_argmax_3d_hm, soft_argmax_3d_nhwc,
+                    soft_argmax_3d_nhwc_hm)
 
 # compute_dtype -> (operand planes of the planes route, or None: the direct route; arithmetic of the direct kernels).
 # "f16x3": two fp16 planes per operand, fp32-grade like "bf16x6"; "bf16p": ONE bf16 plane -- bf16 storage of the GEMM
@@ -342,45 +343,62 @@ class _HeatmapNet(nn.Module):
         out = conv.conv2d_bias_nhwc_autograd(out, conv.to_ohwi(self.final_layer.weight.float()), self.final_layer.bias, arith=ar)
         return out if nhwc else conv.nhwc_to_nchw_autograd(out)
 
-    def _coords(self, logits_nchw):
+    def _coords(self, logits_nchw, hm=None):
+        """hm: None, or (heatmap_target, sigma, centre) -> (coords, sq)."""
         if self.depth_dim > 1:
+            if hm is not None:
+                return soft_argmax_3d_hm(logits_nchw, hm[0], hm[1], hm[2], self.num_joints, self.depth_dim)
             return soft_argmax_3d(logits_nchw, self.num_joints, self.depth_dim)
+        if hm is not None:
+            return soft_argmax_2d_hm(logits_nchw, hm[0], hm[1], hm[2], self.num_joints)
         return soft_argmax_2d(logits_nchw, self.num_joints)
 
-    def predict_nhwc(self, x_nhwc):
+    def predict_nhwc(self, x_nhwc, heatmap_target=None, sigma=0.5, centre="head"):
         """Coordinates from NHWC frames, in whichever mode the module is in (phase5's cycle step feeds BOTH networks
-        the same frames; their reference forwards disagree about the input layout, this entry point does not)."""
+        the same frames; their reference forwards disagree about the input layout, this entry point does not).
+        heatmap_target: the joints' target coordinates in the head's own order and range, (B, J*3) or (B, J*2); the return
+        value is then (coords, sq) with sq (B, J) the heat-map's squared error against the Gaussian target (heads.py
+        soft_argmax_3d_hm; losses.heatmap_mse turns it into the reference's MSELoss) -- on every route, from the same pass
+        over the logits that yields the coordinates."""
+        hm = None if heatmap_target is None else (heatmap_target, sigma, centre)
         if self.depth_dim == 64:           # the head that reads the NHWC logits in place
             if self.training:
                 # every route offers the link; where the final convolution ran on the planes GEMM it comes back with that
                 # convolution's mode and its gradient arrives as planes written by the soft-argmax backward, else with None
                 lk = conv.PlaneLink()
                 logits = self._heatmap_logits_train(x_nhwc, nhwc=True, final_link=lk)
+                if hm is not None:
+                    return soft_argmax_3d_nhwc_hm(logits, heatmap_target, sigma, centre, self.num_joints,
+                                                  lk if lk.mode is not None else None)
                 return soft_argmax_3d_nhwc(logits, self.num_joints, lk if lk.mode is not None else None)
             with torch.no_grad():
+                if hm is not None:
+                    return soft_argmax_3d_nhwc_hm(self.heatmap_logits_nhwc(x_nhwc), heatmap_target, sigma, centre,
+                                                  self.num_joints)
                 return soft_argmax_3d_nhwc(self.heatmap_logits_nhwc(x_nhwc), self.num_joints)
         if self.training:
-            return self._coords(self._heatmap_logits_train(x_nhwc))
+            return self._coords(self._heatmap_logits_train(x_nhwc), hm)
         with torch.no_grad():
-            return self._coords(self.heatmap_logits(x_nhwc))
+            return self._coords(self.heatmap_logits(x_nhwc), hm)
 
 
 class Model_3D(_HeatmapNet):
     def __init__(self, architecture="resnet50", compute_dtype="f16x3"):
         super().__init__(64, architecture, compute_dtype)
 
-    def forward(self, x):
-        """x [B, 256, 256, 3] NHWC frames -> [B, 51] (x, y, z) per joint in (-1, 1)  (Model.py:83-137)."""
-        return self.predict_nhwc(x)
+    def forward(self, x, heatmap_target=None, sigma=0.5, centre="head"):
+        """x [B, 256, 256, 3] NHWC frames -> [B, 51] (x, y, z) per joint in (-1, 1)  (Model.py:83-137); with
+        heatmap_target [B, 51] also the heat-map's squared error per joint: (coords, sq [B, 17])  (predict_nhwc)."""
+        return self.predict_nhwc(x, heatmap_target, sigma, centre)
 
 
 class Model_2D(_HeatmapNet):
     def __init__(self, architecture="resnet50", compute_dtype="f16x3"):
         super().__init__(1, architecture, compute_dtype)
 
-    def forward(self, x):
+    def forward(self, x, heatmap_target=None, sigma=0.5, centre="head"):
         """x [B, 3, 256, 256] NCHW frames (Model_2d.py:91 leaves the permute commented out) -> [B, 34]
-        (x, y) per joint in (0, 1)  (Model_2d.py:87-136)."""
+        (x, y) per joint in (0, 1)  (Model_2d.py:87-136); with heatmap_target [B, 34]: (coords, sq [B, 17])."""
         if x.dim() != 4 or x.shape[1] != 3:
             raise ValueError(f"Model_2D expects NCHW frames [B, 3, H, W], got {tuple(x.shape)}")
-        return self.predict_nhwc(x.permute(0, 2, 3, 1).contiguous())
+        return self.predict_nhwc(x.permute(0, 2, 3, 1).contiguous(), heatmap_target, sigma, centre)

@@ -4,6 +4,8 @@
   TriangleLoss   /root/reference/phase5_loop/losses.py:10-62            (era="model2d")
                  /root/reference/phase5_loop/train_5 copy.py:34-86      (era="lifter", the LinearModel-era
                  copy: |y2d^ - y2d| + |y3d^ - y3d| + |lift(y2d) - y3d| + |lift(y2d^) - lift(y2d)|)
+  heatmap_mse    torch.nn.MSELoss(reduction="mean")(heatmap_hat, hm) of phase5_loop/train_5.py:130-142, from the per-joint
+                 squared errors the heat-map heads return (heads.soft_argmax_3d_hm): no heat-map is ever stored
 All L1 terms of one TriangleLoss call -- value and gradient -- are ONE pl_l1_terms_fwd_bwd launch pair.
 The reference reads four scalars back to the host in every call (`.cpu().item()`, losses.py:50-53);
 here the per-term values stay on the device until report_losses() asks for them.
@@ -69,6 +71,12 @@ def l1_terms(*pairs):
 def l1_loss(pred, tgt):
     """torch.nn.L1Loss(reduction="mean")(pred, tgt)."""
     return l1_terms((pred, tgt))[0]
+
+
+def heatmap_mse(sq, voxels):
+    """MSELoss(reduction="mean") of the normalised heat-maps against their Gaussian targets: sq (B, J) holds each map's
+    summed squared error, `voxels` is the size of one map (64**3 for Model_3D, 64**2 for Model_2D)."""
+    return sq.sum() / (sq.numel() * voxels)
 
 
 def _centre_on_first(t):

@@ -631,6 +631,37 @@ int pl_softargmax_bwd(const float* logits, const float* stats, const float* gcoo
                       int64_t D, int64_t H, int64_t W, int ncoord, int centred, float* dlogits,
                       void* stream);
 
+/* ---- heat-map supervision in the soft-argmax heads (csrc/heatmap_target.h) ------------------------------------------
+ * The reference's other loss, MSELoss(heatmap_hat, hm) (phase5_loop/train_5.py:130-142,188) against the dataset's Gaussian
+ * target (phase3_direct/my_HybrIK/H36_dataset.py:148-202), with neither the normalised heat-map nor the target stored:
+ *   target[BJ][ncoord]  the joints' target coordinates in the head's (x, y[, z]) <-> (W, H[, D]) order
+ *   law[6]              HOST floats {alpha x, y, z, gamma x, y, z}: centre index mu_a = alpha_a * (t_a + gamma_a)
+ *   sigma               window half = (ceil(6 sigma) made odd) / 2 <= 8, else PL_ESHAPE
+ *   g                   exp(-sum_a (idx_a - mu_a)^2 / (2 sigma^2)) where |idx_a - rint(mu_a)| <= half on every axis, else 0
+ * A non-finite centre makes that (b, j)'s sq, its stats[5..7] and its dlogits NaN and touches no other pair.
+ * pl_heatmap_gaussian(_host): the dense target out[BJ][D][H][W] on the device / on the host (test hook, same arithmetic). */
+int pl_heatmap_gaussian(const float* target, int64_t BJ, int64_t D, int64_t H, int64_t W, int ncoord, float sigma,
+                        const float* law, float* out, void* stream);
+int pl_heatmap_gaussian_host(const float* target, int64_t BJ, int64_t D, int64_t H, int64_t W, int ncoord, float sigma,
+                             const float* law, float* out);
+/* pl_softargmax_fwd / pl_softargmax3d_nhwc_fwd + sq[BJ] = sum_v (p_v - g_v)^2 in the same single read of the logits; coords
+ * are bitwise the plain entry point's.  stats [BJ][8] = {max, sum exp, Ex, Ey, Ez, sum p^2, sum_win p g, sum_win g^2}. */
+int pl_softargmax_hm_fwd(const float* logits, const float* target, int64_t BJ, int64_t D, int64_t H, int64_t W, int ncoord,
+                         int centred, float sigma, const float* law, float* coords, float* sq, float* stats, void* stream);
+int pl_softargmax3d_nhwc_hm_fwd(const float* logits, const float* target, int64_t B, int64_t J, int64_t H, int64_t W,
+                                float sigma, const float* law, float* coords, float* sq, float* stats, void* stream);
+/* The backward passes with the heat-map term: gsq[BJ] is the upstream gradient of sq (masks and per-joint weights are the
+ * caller's multiplication), dlogit_v += 2 gsq p_v (p_v - g_v - (sum p^2 - sum_win p g)).  gsq == 0 gives the plain
+ * backward's values.  The _ex form writes fp32, planes or both like pl_softargmax3d_nhwc_bwd_ex; its fp16 dl_scale comes
+ * from pl_softargmax_hm_dl_scale: the bound 2 max_rows (sum_c |gcoords| + 2 |gsq|). */
+int pl_softargmax_hm_bwd(const float* logits, const float* target, const float* stats, const float* gcoords, const float* gsq,
+                         int64_t BJ, int64_t D, int64_t H, int64_t W, int ncoord, int centred, float sigma, const float* law,
+                         float* dlogits, void* stream);
+int pl_softargmax3d_nhwc_hm_bwd_ex(const float* logits, const float* target, const float* stats, const float* gcoords,
+                                   const float* gsq, int64_t B, int64_t J, int64_t H, int64_t W, float sigma, const float* law,
+                                   float* dlogits, void* dl_planes, int planes_mode, const float* dl_scale, void* stream);
+int pl_softargmax_hm_dl_scale(const float* gcoords, const float* gsq, int64_t rows, int ncoord, float* scale2, void* stream);
+
 /* ---- MyViT, the transformer lifter (phase1_lifting/baselineModel.py:220-362) ------------ */
 /* The non-GEMM parts of its forward and backward (vit.hip); its Linears run on pl_gemm_f32 / pl_gemm_planes_raw.
  * T = B * seq token rows of H features, row-major.  Parameter gradients are reduced in a fixed order (per-256-row

@@ -1,0 +1,526 @@
+"""GPU tests of the heat-map supervision in the soft-argmax heads: the dense target kernel against the reference's function
+(fixture g14) and the host entry; the fused forward (coordinates bitwise the plain kernel's, sq against the fp64 oracle of
+heatmap_oracle.py) and backward (against fp64 autograd) on both layouts; the planes forms of the NHWC backward and the scale
+kernel's bound; Model_3D / Model_2D with a heat-map target on every route.
+
+Units of the gates (measured on the MI355X over every case of this file, gated at 4x the worst case; DESIGN.md N1b has the
+table):
+  sq       eps32 * (sum p^2 + sum g^2), the scale of the three-sum expansion: worst 4.61 (64^3, N(0, 9) logits) -> 18.5
+  dlogits  eps32 * max |dlogits| of the map (fp64 autograd), per kind of logits: N(0, 9) 16.6 (NHWC 64 x 64 x 17), some -inf
+           16.4, all equal 1.01 -> 66.4 / 65.6 / 4.1.  On a SATURATED map (one logit +25; log of the target) this unit says
+           nothing: the true gradient cancels to 1e-9 of the upstream gradient (p -> 1 at the peak, every term vanishes)
+           while fp32 holds eps32 of it -- in the coordinate term of the plain kernel just as in the heat-map term -- and
+           the figure is 8.4e6 (= the whole of a gradient that is itself rounding noise) up to 1.6e8.  Those kinds are
+           gated at 4x that all the same, and every case is also gated on the scale that is meaningful there:
+  dlogits  eps32 * (2 sum_c |g_c| + 4 |gsq|), the map's bound: worst 0.43 -> 1.72
+"""
+import math
+import ctypes
+import importlib
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import heatmap_oracle as orc
+from conftest import ROOT, load_golden
+from test_heatmap_target_host import check_against_g14, g14_maps
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+EPS = float(np.finfo(np.float32).eps)
+SQ_GATE = 18.5
+# per kind of logits (_logit_kinds; "normal3" also gates the NHWC and model tests, whose logits are of that kind)
+DL_GATE_KIND = {"normal3": 66.4, "equal": 4.1, "some_minus_inf": 65.6}
+DL_GATE = DL_GATE_KIND["normal3"]
+DL_ABS_GATE = 1.72
+# NOT a check of accuracy.  The two saturated kinds in the same relative unit, 4x the measured figure like the others, kept
+# only because that unit is asked of every kind: the numbers exceed the whole gradient by orders of magnitude (see the
+# docstring).  DL_ABS_GATE is the gate that binds these kinds.
+DL_RECORD_SATURATED = {"peak25": 6.6e8, "log_target": 3.4e7}
+# device target against the host entry: the same text, but the two expf differ (each within 1 ulp of exp by its
+# documentation, the tail factor rounds once more on each side): 4 ulps of the value
+TARGET_DEVICE_HOST_ULPS = 4.0
+
+
+@pytest.fixture(scope="module")
+def pkg():
+    sys.path.insert(0, ROOT)
+    import __graft_entry__ as ge
+    return ge.build()
+
+
+@pytest.fixture(scope="module")
+def heads(pkg):
+    return importlib.import_module("3d_poseestimation_amd.heads")
+
+
+def _law(law):
+    return (ctypes.c_float * 6)(*law)
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+# ------------------------------------------------------------------------------------------------------------ the target
+@pytest.mark.parametrize("si", [0, 1])
+def test_device_target_matches_the_reference_function_and_the_host_entry(pkg, si):
+    g14 = load_golden("g14_heatmap_targets.npz")
+    sigma = float(g14["sigmas"][si])
+    kp = np.stack([k for k, _, _, _ in g14_maps(g14, si)])
+    dev = pkg.gaussian_heatmap(torch.from_numpy(kp).to(DEV), (64, 64, 64), sigma, centre="reference").cpu().numpy()
+    check_against_g14(dev, g14, si)
+    host = np.empty_like(dev)
+    law = pkg.heatmap_law(64, 64, 64, True, "reference")
+    assert pkg.lib().pl_heatmap_gaussian_host(kp.ctypes.data, len(kp), 64, 64, 64, 3, sigma, _law(law), host.ctypes.data) == 0
+    assert np.array_equal(dev != 0, host != 0)
+    nz = host != 0
+    ulps = np.abs(dev[nz].astype(np.float64) - host[nz]) / np.spacing(host[nz]).astype(np.float64)
+    print(f"sigma {sigma}: device vs host target, worst {ulps.max():.2f} ulps")
+    assert ulps.max() <= TARGET_DEVICE_HOST_ULPS
+
+
+def test_device_target_edge_cases_and_the_2d_law(pkg):
+    t = torch.tensor([[0.0, 0.0, 0.0], [5.0, 0.0, 0.0], [0.0, float("nan"), 0.0], [0.0, 0.0, float("-inf")], [1e30, -1e30, 1e20]])
+    got = pkg.gaussian_heatmap(t.to(DEV), (16, 16, 16), 0.5).cpu()
+    assert int((got[0] != 0).sum()) == 27 and float(got[0, 8, 8, 8]) == 1.0
+    assert not got[1].any() and not got[4].any()
+    assert got[2].isnan().all() and got[3].isnan().all()
+    t2 = torch.tensor([[0.5, 0.25], [0.29166667, 0.9375]])
+    got2 = pkg.gaussian_heatmap(t2.to(DEV), (8, 12), 0.5).cpu().numpy()
+    want2 = orc.dense_target(t2.numpy(), 1, 8, 12, 0.5, pkg.heatmap_law(12, 8, 1, False, "head"))
+    assert got2.shape == (2, 1, 8, 12) and np.array_equal(got2 != 0, want2 != 0)
+    assert np.abs(got2 - want2).max() <= 8 * EPS
+    with pytest.raises(ValueError, match="centred heads only"):
+        pkg.gaussian_heatmap(t2.to(DEV), (8, 12), 0.5, centre="reference")
+
+
+# ------------------------------------------------------------------------------------------------- NCHW forward + backward
+def _targets(BJ, centred, dims, pick):
+    """BJ target rows (x, y[, z]) chosen from: both corners, the .5 rounding tie, off the map, random."""
+    W, H, D = dims
+    rng = np.random.default_rng(7 + BJ + W)
+    if centred:
+        tie = lambda dim: (2 * (dim // 2 - 1) + 1) / dim - 1.0           # mu = dim/2 - 0.5, rounds to even
+        kinds = {"lo": [-1.0, -1.0, -1.0], "hi": [1.0, 1.0, 1.0], "tie": [tie(W), tie(H), tie(D)], "off": [3.0, 0.1, -0.2],
+                 "rnd": list(rng.uniform(-0.9, 0.9, 3))}
+    else:
+        tie = lambda dim: (dim // 2 - 0.5) / dim
+        kinds = {"lo": [0.0, 0.0], "hi": [1.0, 1.0], "tie": [tie(W), tie(H)], "off": [2.5, 0.3], "rnd": list(rng.uniform(0.05, 0.95, 2))}
+    return np.asarray([kinds[pick[i % len(pick)]] for i in range(BJ)], dtype=np.float32)
+
+
+def _logit_kinds(BJ, D, H, W, g):
+    """name -> (BJ, D, H, W) fp32 logits; g the dense fp64 target (for the two kinds built from it)."""
+    rng = np.random.default_rng(11 * D + W)
+    n = D * H * W
+    out = {}
+    out["normal3"] = (rng.standard_normal((BJ, D, H, W)) * 3).astype(np.float32)
+    peak = np.zeros((BJ, n), np.float32)
+    for b in range(BJ):                                    # +25 at the target's largest voxel (voxel 0 for an all-zero target)
+        peak[b, int(np.argmax(g[b]))] = 25.0
+    out["peak25"] = peak.reshape(BJ, D, H, W)
+    with np.errstate(divide="ignore"):
+        out["log_target"] = np.where(g > 0, np.log(np.where(g > 0, g, 1.0)), -40.0).astype(np.float32)
+    out["equal"] = np.full((BJ, D, H, W), 1.5, np.float32)
+    x = (rng.standard_normal((BJ, n)) * 3).astype(np.float32)
+    x[rng.random((BJ, n)) < 0.3] = -np.inf
+    x[:, : n // 4] = -np.inf                               # whole float4s, whole rows, a lane's first loads: the skip path
+    x[0, :] = np.where(g[0].reshape(-1) > 0, -np.inf, x[0, :])          # the window itself at weight 0: sum g^2 still counts
+    x[:, n - 1] = 2.0
+    out["some_minus_inf"] = x.reshape(BJ, D, H, W)
+    return out
+
+
+def _run_nchw(pkg, logits, target, sigma, law, ncoord, centred, gc=None, gsq=None):
+    L = pkg.lib()
+    BJ, D, H, W = logits.shape
+    x = torch.from_numpy(logits).to(DEV)
+    t = torch.from_numpy(target).to(DEV)
+    coords = torch.empty(BJ, ncoord, device=DEV); sq = torch.empty(BJ, device=DEV); stats = torch.empty(BJ, 8, device=DEV)
+    rc = L.pl_softargmax_hm_fwd(x.data_ptr(), t.data_ptr(), BJ, D, H, W, ncoord, centred, sigma, _law(law), coords.data_ptr(),
+                                sq.data_ptr(), stats.data_ptr(), _stream())
+    assert rc == 0, L.pl_last_error()
+    c0 = torch.empty(BJ, ncoord, device=DEV); s0 = torch.empty(BJ, 5, device=DEV)
+    assert L.pl_softargmax_fwd(x.data_ptr(), BJ, D, H, W, ncoord, centred, c0.data_ptr(), s0.data_ptr(), _stream()) == 0
+    out = {"coords": coords, "sq": sq, "stats": stats, "coords_plain": c0, "stats_plain": s0}
+    if gc is not None:
+        gct, gst = torch.from_numpy(gc).to(DEV), torch.from_numpy(gsq).to(DEV)
+        def bwd(gs):
+            dl = torch.empty_like(x)
+            rc = L.pl_softargmax_hm_bwd(x.data_ptr(), t.data_ptr(), stats.data_ptr(), gct.data_ptr(), gs.data_ptr(), BJ, D, H, W,
+                                        ncoord, centred, sigma, _law(law), dl.data_ptr(), _stream())
+            assert rc == 0, L.pl_last_error()
+            return dl
+        out["dl"], out["dl_again"], out["dl_w0"] = bwd(gst), bwd(gst), bwd(torch.zeros_like(gst))
+        dp = torch.empty_like(x)
+        assert L.pl_softargmax_bwd(x.data_ptr(), s0.data_ptr(), gct.data_ptr(), BJ, D, H, W, ncoord, centred, dp.data_ptr(),
+                                   _stream()) == 0
+        out["dl_plain"] = dp
+    return out
+
+
+def _figures(name, got, want, gc, gsq):
+    """(sq, dlogits, dlogits-absolute) errors in their units: eps32 (sum p^2 + sum g^2); eps32 max |dlogits| of the map; eps32
+    times the map's bound 2 sum_c |g_c| + 4 |gsq| (the scale kernel's), which is what fp32 can hold where the true gradient
+    of a saturated map cancels to nothing."""
+    sq = got["sq"].cpu().numpy().astype(np.float64)
+    unit = EPS * (want["p2"] + want["g2"])
+    u_sq = float((np.abs(sq - want["sq"]) / unit).max())
+    dl = got["dl"].cpu().numpy().astype(np.float64)
+    BJ = dl.shape[0]
+    top = np.abs(want["dlogits"]).reshape(BJ, -1).max(axis=1)
+    err = np.abs(dl - want["dlogits"]).reshape(BJ, -1).max(axis=1)
+    ok = top > 0
+    u_dl = float((err[ok] / (EPS * top[ok])).max()) if ok.any() else 0.0
+    assert (err[~ok] == 0).all()
+    bound = 2 * np.abs(np.asarray(gc, dtype=np.float64)).sum(axis=1) + 4 * np.abs(np.asarray(gsq, dtype=np.float64))
+    u_abs = float((err / (EPS * bound)).max())
+    assert (np.abs(dl).reshape(BJ, -1).max(axis=1) <= bound).all()           # the bound the fp16 planes' scale relies on
+    print(f"  {name}: sq {u_sq:.3f} units, dlogits {u_dl:.3f} units of the map's largest, {u_abs:.4f} units of its bound")
+    return u_sq, u_dl, u_abs
+
+
+NCHW_SHAPES = {"4x8x8": (5, 4, 8, 8), "2d_64x64": (4, 1, 64, 64), "64x64x64": (3, 64, 64, 64), "below_one_workgroup": (2, 2, 4, 8)}
+
+
+@pytest.mark.parametrize("sigma", [0.5, 1.75])
+@pytest.mark.parametrize("shape", list(NCHW_SHAPES))
+def test_nchw_forward_and_backward_against_the_fp64_oracle(pkg, shape, sigma):
+    BJ, D, H, W = NCHW_SHAPES[shape]
+    centred = D > 1
+    ncoord = 3 if centred else 2
+    law = pkg.heatmap_law(W, H, D, centred, "head")
+    pick = ["lo", "tie", "off", "hi", "rnd"] if sigma == 0.5 else ["hi", "rnd", "tie", "off", "lo"]
+    target = _targets(BJ, centred, (W, H, D), pick)
+    g = orc.dense_target(target, D, H, W, sigma, law, ncoord)
+    rng = np.random.default_rng(5)
+    gc = rng.standard_normal((BJ, ncoord)).astype(np.float32)
+    gsq = rng.standard_normal(BJ).astype(np.float32)
+    gsq[0], gsq[1] = 0.0, -abs(gsq[1]) - 0.5                      # a zero row and a negative row
+    fig = {}
+    for name, logits in _logit_kinds(BJ, D, H, W, g).items():
+        want = orc.loss_and_grad(logits, target, sigma, law, centred, gc, gsq)
+        got = _run_nchw(pkg, logits, target, sigma, law, ncoord, int(centred), gc, gsq)
+        assert torch.equal(got["coords"], got["coords_plain"]), name          # bitwise the plain kernel's
+        assert torch.equal(got["stats"][:, :5], got["stats_plain"]), name
+        assert np.abs(got["coords"].cpu().numpy() - want["coords"]).max() < 1e-4, name
+        assert torch.equal(got["dl"], got["dl_again"]), name                  # a repeated call is bitwise equal
+        assert torch.equal(got["dl_w0"], got["dl_plain"]), name               # gsq == 0: the plain backward
+        assert np.abs(got["stats"][:, 7].cpu().numpy() - want["g2"]).max() <= 16 * EPS * max(1.0, want["g2"].max()), name
+        fig[name] = _figures(f"{shape} sigma {sigma} {name}", got, want, gc, gsq)
+    for name, (u_sq, u_dl, u_abs) in fig.items():
+        assert u_sq <= SQ_GATE, (name, u_sq)
+        assert u_abs <= DL_ABS_GATE, (name, u_abs)                            # every kind: eps32 of the map's bound
+        assert u_dl <= {**DL_GATE_KIND, **DL_RECORD_SATURATED}[name], (name, u_dl)
+
+
+def test_a_nan_target_poisons_its_own_pair_only(pkg):
+    BJ, D, H, W = 4, 4, 8, 8
+    law = pkg.heatmap_law(W, H, D, True, "head")
+    rng = np.random.default_rng(3)
+    logits = rng.standard_normal((BJ, D, H, W)).astype(np.float32)
+    target = rng.uniform(-0.8, 0.8, (BJ, 3)).astype(np.float32)
+    clean = _run_nchw(pkg, logits, target, 0.5, law, 3, 1, np.ones((BJ, 3), np.float32), np.ones(BJ, np.float32))
+    target[1, 2], target[2, 0] = np.nan, np.inf
+    got = _run_nchw(pkg, logits, target, 0.5, law, 3, 1, np.ones((BJ, 3), np.float32), np.ones(BJ, np.float32))
+    assert torch.equal(got["coords"], clean["coords"])
+    for b in (1, 2):
+        assert got["sq"][b].isnan() and got["dl"][b].isnan().all()
+    for b in (0, 3):
+        assert torch.equal(got["sq"][b], clean["sq"][b]) and torch.equal(got["dl"][b], clean["dl"][b])
+
+
+# ------------------------------------------------------------------------------------------------------------------ NHWC
+def _run_nhwc(pkg, x, t, sigma, law, gct=None, gst=None, planes_mode=0, both=False):
+    """x (B, H, W, J*64), t (B*J, 3) device tensors -> dict; planes_mode: 0 fp32 dlogits, else the carrier of the planes."""
+    L = pkg.lib()
+    B, H, W, C = x.shape
+    J = C // 64
+    coords = torch.empty(B * J, 3, device=DEV); sq = torch.empty(B * J, device=DEV); stats = torch.empty(B * J, 8, device=DEV)
+    rc = L.pl_softargmax3d_nhwc_hm_fwd(x.data_ptr(), t.data_ptr(), B, J, H, W, sigma, _law(law), coords.data_ptr(), sq.data_ptr(),
+                                       stats.data_ptr(), _stream())
+    assert rc == 0, L.pl_last_error()
+    out = {"coords": coords, "sq": sq, "stats": stats}
+    if gct is not None:
+        dl = torch.empty_like(x) if (planes_mode == 0 or both) else None
+        carrier = torch.empty_like(x) if planes_mode else None
+        scale = torch.empty(2, device=DEV)
+        assert L.pl_softargmax_hm_dl_scale(gct.data_ptr(), gst.data_ptr(), B * J, 3, scale.data_ptr(), _stream()) == 0
+        rc = L.pl_softargmax3d_nhwc_hm_bwd_ex(x.data_ptr(), t.data_ptr(), stats.data_ptr(), gct.data_ptr(), gst.data_ptr(), B, J, H, W,
+                                              sigma, _law(law), dl.data_ptr() if dl is not None else None,
+                                              carrier.data_ptr() if carrier is not None else None, planes_mode, scale.data_ptr(),
+                                              _stream())
+        assert rc == 0, L.pl_last_error()
+        out.update(dl=dl, carrier=carrier, scale=scale)
+    return out
+
+
+@pytest.mark.parametrize("shape", [(2, 8, 8, 3), (1, 64, 64, 17)])
+def test_nhwc_forward_and_backward_against_nchw_and_the_oracle(pkg, shape):
+    B, H, W, J = shape
+    L = pkg.lib()
+    sigma = 0.5 if J == 3 else 1.75
+    law = pkg.heatmap_law(W, H, 64, True, "head")
+    g = torch.Generator().manual_seed(9)
+    x = (torch.randn(B, H, W, J * 64, generator=g) * 3)
+    x[0, :, :, 70:90] = float("-inf")                                       # part of joint 1's depths at weight 0
+    target = _targets(B * J, True, (W, H, 64), ["rnd", "lo", "tie", "hi", "off", "rnd", "rnd"])
+    gc = torch.randn(B * J, 3, generator=g)
+    gsq = torch.randn(B * J, generator=g)
+    gsq[0], gsq[1] = 0.0, -1.25
+    xd, td, gcd, gsd = x.to(DEV), torch.from_numpy(target).to(DEV), gc.to(DEV), gsq.to(DEV)
+    got = _run_nhwc(pkg, xd, td, sigma, law, gcd, gsd)
+    # coordinates: bitwise the plain NHWC entry point's
+    c0 = torch.empty(B * J, 3, device=DEV); s0 = torch.empty(B * J, 5, device=DEV)
+    assert L.pl_softargmax3d_nhwc_fwd(xd.data_ptr(), B, J, H, W, c0.data_ptr(), s0.data_ptr(), _stream()) == 0
+    assert torch.equal(got["coords"], c0) and torch.equal(got["stats"][:, :5], s0)
+    # gsq == 0 is the plain backward; a repeated call is bitwise equal
+    zero = _run_nhwc(pkg, xd, td, sigma, law, gcd, torch.zeros_like(gsd))
+    dp = torch.empty_like(xd)
+    assert L.pl_softargmax3d_nhwc_bwd(xd.data_ptr(), s0.data_ptr(), gcd.data_ptr(), B, J, H, W, dp.data_ptr(), _stream()) == 0
+    assert torch.equal(zero["dl"], dp)
+    assert torch.equal(_run_nhwc(pkg, xd, td, sigma, law, gcd, gsd)["dl"], got["dl"])
+    # the oracle, on the NCHW view of the same logits: [B][H][W][J][64] -> [B*J][64][H][W]
+    to_nchw = lambda v: v.reshape(B, H, W, J, 64).permute(0, 3, 4, 1, 2).reshape(B * J, 64, H, W).contiguous()
+    want = orc.loss_and_grad(to_nchw(x).numpy(), target, sigma, law, True, gc.numpy(), gsq.numpy())
+    as_nchw = {"sq": got["sq"], "dl": to_nchw(got["dl"])}
+    u_sq, u_dl, u_abs = _figures(f"nhwc {shape}", as_nchw, want, gc.numpy(), gsq.numpy())
+    assert u_sq <= SQ_GATE and u_dl <= DL_GATE and u_abs <= DL_ABS_GATE, (u_sq, u_dl, u_abs)
+    # ... and the NCHW kernels on it: both within the gate of the oracle, so within twice the gate of each other
+    nchw = _run_nchw(pkg, to_nchw(x).numpy(), target, sigma, law, 3, 1, gc.numpy(), gsq.numpy())
+    unit = EPS * (want["p2"] + want["g2"])
+    assert (np.abs((got["sq"] - nchw["sq"]).cpu().numpy()) <= 2 * SQ_GATE * unit).all()
+    top = torch.from_numpy(np.abs(want["dlogits"]).reshape(B * J, -1).max(axis=1)).to(DEV).float()
+    diff = (as_nchw["dl"] - nchw["dl"]).abs().reshape(B * J, -1).amax(dim=1)
+    assert bool((diff <= 2 * DL_GATE * EPS * top).all())
+    assert np.abs(got["coords"].cpu().numpy() - want["coords"]).max() < 1e-4
+
+
+def test_nhwc_backward_planes_match_the_fp32_form_and_the_scale_kernel_bounds_them(pkg, heads):
+    """As test_softargmax_bwd_planes_and_colsum_planes_match_the_fp32_forms for the plain kernel: the fp16 planes (scaled by
+    the power of two of the NEW bound 2 max (sum_c |g_c| + 2 |gsq|)) carry the fp32 gradient to 2^-21 of the bound, the bf16
+    plane is the rounded fp32 gradient, writing both changes neither."""
+    B, J, H, W = 3, 17, 8, 8
+    law = pkg.heatmap_law(W, H, 64, True, "head")
+    g = torch.Generator().manual_seed(5)
+    x = (torch.randn(B, H, W, J * 64, generator=g) * 2).to(DEV)
+    # the gradient is bounded whatever the logits: put a near-one-hot map on its target, where the heat-map term peaks
+    t = torch.from_numpy(_targets(B * J, True, (W, H, 64), ["rnd", "tie", "lo"])).to(DEV)
+    gc = (torch.randn(B * J, 3, generator=g) * 1e-3).to(DEV)
+    gsq = (torch.randn(B * J, generator=g) * 5e-3).to(DEV)
+    x[0, 3, 4, 64 + 20] = 30.0
+    f32 = _run_nhwc(pkg, x, t, 0.5, law, gc, gsq)
+    bound = float(2.0 * (gc.abs().sum(1) + 2.0 * gsq.abs()).max())
+    assert float(f32["scale"][0]) == 2.0 ** (14 - math.frexp(bound)[1])
+    assert 2 ** 13 <= bound * float(f32["scale"][0]) < 2 ** 14 and float(f32["scale"][0] * f32["scale"][1]) == 1.0
+    assert float(f32["dl"].abs().max()) <= bound
+    n = x.numel()
+    for both in (False, True):
+        p16 = _run_nhwc(pkg, x, t, 0.5, law, gc, gsq, planes_mode=3, both=both)
+        pl16 = p16["carrier"].reshape(-1).view(torch.float16)
+        back = (pl16[:n].float() + pl16[n:].float() / 2048.0) * p16["scale"][1]
+        assert float((back - f32["dl"].reshape(-1)).abs().max()) <= bound * 2.0 ** -21
+        pb = _run_nhwc(pkg, x, t, 0.5, law, gc, gsq, planes_mode=1, both=both)
+        assert torch.equal(pb["carrier"].reshape(-1).view(torch.bfloat16)[:n], f32["dl"].reshape(-1).bfloat16())
+        if both:
+            assert torch.equal(p16["dl"], f32["dl"]) and torch.equal(pb["dl"], f32["dl"])
+    # a non-finite upstream gradient: scale 1, as the plain scale kernel answers
+    gsq[4] = float("inf")
+    s = torch.empty(2, device=DEV)
+    assert pkg.lib().pl_softargmax_hm_dl_scale(gc.data_ptr(), gsq.data_ptr(), B * J, 3, s.data_ptr(), _stream()) == 0
+    assert s.tolist() == [1.0, 1.0]
+
+
+# ---------------------------------------------------------------------------------------------------------------- models
+def _model3d(pkg, dtype, seed=51):
+    m = pkg.Model_3D(compute_dtype=dtype)
+    m.load_state_dict(pkg.synth.seeded_state(m.state_dict(), seed))
+    with torch.no_grad():
+        m.final_layer.weight.mul_(1e-3)
+    return m.to(DEV)
+
+
+def test_python_heads_autograd_and_heatmap_mse(pkg):
+    """soft_argmax_3d_hm / soft_argmax_2d_hm / soft_argmax_3d_nhwc_hm under autograd against the fp64 oracle, and
+    heatmap_mse = MSELoss(mean) of the dense maps."""
+    g = torch.Generator().manual_seed(21)
+    B, J, H, W = 2, 3, 8, 8
+    x = (torch.randn(B, H, W, J * 64, generator=g) * 2).to(DEV).requires_grad_()
+    y = (torch.rand(B, J * 3, generator=g) * 1.6 - 0.8).to(DEV)
+    coords, sq = pkg.soft_argmax_3d_nhwc_hm(x, y, num_joints=J)
+    assert coords.shape == (B, J * 3) and sq.shape == (B, J)
+    loss = ((coords - y) ** 2).mean() + 1000 * pkg.heatmap_mse(sq, 64 * H * W)
+    loss.backward()
+    law = pkg.heatmap_law(W, H, 64, True, "head")
+    to_nchw = lambda v: v.reshape(B, H, W, J, 64).permute(0, 3, 4, 1, 2).reshape(B * J, 64, H, W)
+    xo = to_nchw(x.detach().cpu()).double().requires_grad_()
+    go = torch.from_numpy(orc.dense_target(y.cpu().numpy().reshape(-1, 3), 64, H, W, 0.5, law))
+    co, so, po = orc.head_outputs(xo, go, True)
+    lo = ((co.reshape(B, J * 3) - y.cpu().double()) ** 2).mean() + 1000 * ((po - go) ** 2).mean()
+    lo.backward()
+    assert abs(float(loss.detach()) - float(lo.detach())) <= 1e-5 * abs(float(lo.detach()))
+    err = (to_nchw(x.grad.cpu()).double() - xo.grad).abs().max() / xo.grad.abs().max()
+    assert float(err) <= DL_GATE * EPS
+    # the NCHW heads: the same numbers through the other layout, and the 2-D head on its own law
+    xn = to_nchw(x.detach()).reshape(B, J * 64, H, W).contiguous().requires_grad_()
+    c2, s2 = pkg.soft_argmax_3d_hm(xn, y, num_joints=J)
+    assert torch.equal(c2, pkg.soft_argmax_3d(xn, J)) and float((s2 - sq).detach().abs().max()) <= 2 * SQ_GATE * EPS * 4.0
+    x2 = torch.randn(B, J, 16, 16, generator=g).to(DEV).requires_grad_()
+    y2 = torch.rand(B, J * 2, generator=g).to(DEV)
+    c3, s3 = pkg.soft_argmax_2d_hm(x2, y2, num_joints=J)
+    pkg.heatmap_mse(s3, 256).backward()
+    w2 = orc.loss_and_grad(x2.detach().cpu().numpy().reshape(B * J, 1, 16, 16), y2.cpu().numpy().reshape(-1, 2), 0.5,
+                           pkg.heatmap_law(16, 16, 1, False, "head"), False, np.zeros((B * J, 2)), np.full(B * J, 1 / (B * J * 256)))
+    assert torch.equal(c3, pkg.soft_argmax_2d(x2, J))
+    assert (np.abs(s3.detach().cpu().numpy().reshape(-1) - w2["sq"]) <= SQ_GATE * EPS * (w2["p2"] + w2["g2"])).all()   # per map
+    e2 = np.abs(x2.grad.cpu().numpy().reshape(B * J, 1, 16, 16) - w2["dlogits"]).max() / np.abs(w2["dlogits"]).max()
+    assert e2 <= DL_GATE * EPS
+    assert y.grad is None and not y.requires_grad
+
+
+def test_error_paths(pkg):
+    x = torch.zeros(2, 8, 8, 3 * 64, device=DEV)
+    y = torch.zeros(2, 9, device=DEV)
+    with pytest.raises(ValueError, match="heat-map target has"):
+        pkg.soft_argmax_3d_nhwc_hm(x, y[:, :6], num_joints=3)
+    with pytest.raises(pkg._lib.PoseliftError, match="half-width 9"):
+        pkg.soft_argmax_3d_nhwc_hm(x, y, sigma=3.0, num_joints=3)
+    with pytest.raises(pkg._lib.PoseliftError, match="half-width"):
+        pkg.soft_argmax_3d_hm(torch.zeros(2, 3 * 64, 8, 8, device=DEV), y, sigma=4.0, num_joints=3)
+    with pytest.raises(ValueError, match="centred heads only"):
+        pkg.soft_argmax_2d_hm(torch.zeros(2, 3, 8, 8, device=DEV), torch.zeros(2, 6, device=DEV), centre="reference", num_joints=3)
+    with pytest.raises(ValueError, match="channels"):
+        pkg.soft_argmax_3d_nhwc_hm(x, y, num_joints=4)
+    c, s = pkg.soft_argmax_3d_nhwc_hm(x, y, centre="reference", num_joints=3)          # defined for the centred head
+    assert c.shape == (2, 9) and s.shape == (2, 3)
+
+
+def test_model3d_eval_with_a_heatmap_target(pkg):
+    m = _model3d(pkg, "f16x3", 31).eval()
+    frames = pkg.synth.seeded_frames(2, 32).to(DEV)
+    y = (torch.rand(2, 51, generator=torch.Generator().manual_seed(1)) * 1.8 - 0.9).to(DEV)
+    coords, sq = m(frames, heatmap_target=y)
+    c2, s2 = pkg.soft_argmax_3d_nhwc_hm(m.heatmap_logits_nhwc(frames), y)
+    assert torch.equal(coords, c2) and torch.equal(sq, s2)
+    assert torch.equal(coords, m(frames))
+    assert sq.shape == (2, 17) and bool(sq.isfinite().all()) and not coords.requires_grad and not sq.requires_grad
+    c3, s3 = m(frames, heatmap_target=y, sigma=1.75, centre="reference")
+    assert torch.equal(c3, coords) and not torch.equal(s3, sq)
+
+
+def _train_step(pkg, m, frames, y, lam, capture=None, sigma=0.5):
+    """One forward + backward of MSE(coords) + lam * 1000 * heatmap_mse (lam None: the coordinate loss alone, plain forward);
+    capture: a list that receives (logits, link) of the head call."""
+    backbone = importlib.import_module("3d_poseestimation_amd.backbone")
+    m.train()
+    m.zero_grad(set_to_none=True)
+    orig = backbone.soft_argmax_3d_nhwc_hm
+
+    def spy(out, *a, **k):
+        if capture is not None:
+            capture.append((out.detach().clone(), a[4] if len(a) > 4 else k.get("link")))
+        return orig(out, *a, **k)
+
+    backbone.soft_argmax_3d_nhwc_hm = spy
+    try:
+        if lam is None:
+            loss = ((m(frames) - y) ** 2).mean()
+        else:
+            coords, sq = m(frames, heatmap_target=y, sigma=sigma)
+            H = W = frames.shape[1] // 4
+            loss = ((coords - y) ** 2).mean() + lam * 1000 * pkg.heatmap_mse(sq, 64 * H * W)
+        loss.backward()
+    finally:
+        backbone.soft_argmax_3d_nhwc_hm = orig
+    return loss.detach()
+
+
+def test_model3d_training_bias_gradient_is_the_oracles_column_sums(pkg):
+    """Model_3D in training mode at B = 2 on the fp32-grade direct route (compute_dtype "bf16x6": fp32 dlogits): the final
+    convolution's bias gradient is the column sum of d loss / d logits, and that is the fp64 oracle's on the very logits the
+    head saw."""
+    lam = 10.0
+    m = _model3d(pkg, "bf16x6")
+    frames = pkg.synth.seeded_frames(2, 52, size=64).to(DEV)
+    y = (torch.rand(2, 51, generator=torch.Generator().manual_seed(2)) * 1.6 - 0.8).to(DEV)
+    seen = []
+    _train_step(pkg, m, frames, y, lam, seen)
+    (logits, link), = seen
+    assert link is None                                            # this route takes the gradient in fp32
+    B, H, W, C = logits.shape
+    J = 17
+    to_nchw = lambda v: v.reshape(B, H, W, J, 64).permute(0, 3, 4, 1, 2).reshape(B * J, 64, H, W)
+    law = pkg.heatmap_law(W, H, 64, True, "head")
+    yn = y.cpu().numpy().reshape(-1, 3)
+    co = orc.loss_and_grad(to_nchw(logits.cpu()).numpy(), yn, 0.5, law, True)["coords"]
+    gc = 2.0 * (co - yn) / (B * 51)
+    gsq = np.full(B * J, lam * 1000.0 / (B * J * 64 * H * W))
+    want = orc.loss_and_grad(to_nchw(logits.cpu()).numpy(), yn, 0.5, law, True, gc, gsq)["dlogits"]
+    plain = orc.loss_and_grad(to_nchw(logits.cpu()).numpy(), yn, 0.5, law, True, gc, np.zeros(B * J))["dlogits"]
+    cols = lambda d: d.reshape(B, J, 64, H * W).sum(axis=(0, 3)).reshape(-1)              # column (j, depth) of the NHWC logits
+    db = m.final_layer.bias.grad.cpu().numpy().astype(np.float64)
+    # every dlogit is within DL_GATE units of its map's largest; a column adds H W of them per batch entry, in fp32
+    top = np.abs(want).reshape(B, J, -1).max(axis=2)
+    tol = EPS * (DL_GATE * H * W * np.repeat(top.sum(axis=0), 64) + 16 * cols(np.abs(want)))
+    err = np.abs(db - cols(want))
+    print(f"bias gradient: worst error / tolerance {float((err / tol).max()):.3f}; heat-map part of it / tolerance "
+          f"{float((np.abs(cols(want) - cols(plain)) / tol).max()):.1f}")
+    # tol lets every voxel of a column err by the whole gate with one sign; rounding errors do not line up so, and the
+    # measured worst is 0.012 of it (MI355X, the same figure on two machines): gated at 4x that
+    assert (err <= 0.05 * tol).all()
+    assert (np.abs(cols(want) - cols(plain)) / tol).max() > 100          # the test sees the heat-map term
+
+
+def test_model3d_training_plane_link_against_the_fp32_route(pkg):
+    """The f16x3 route (dlogits leave the head as fp16 planes under the NEW scale bound) against the fp32-grade direct route,
+    same weights and frames: the distance of the two routes' gradients is measured for the coordinate loss alone, and the
+    step with the heat-map term may be twice as far."""
+    frames = pkg.synth.seeded_frames(2, 52, size=256).to(DEV)
+    y = (torch.rand(2, 51, generator=torch.Generator().manual_seed(2)) * 1.6 - 0.8).to(DEV)
+    names = ["final_layer.bias", "final_layer.weight", "deconv_layers.6.weight"]
+    LAM = 1000.0        # with near-uniform heat-maps (final weights scaled down) this makes the two terms' gradients comparable
+    grads = {}
+    for dtype in ("bf16x6", "f16x3"):
+        m = _model3d(pkg, dtype)
+        for lam in (None, LAM):
+            seen = []
+            loss = _train_step(pkg, m, frames, y, lam, seen, sigma=1.75)
+            if lam is not None:
+                assert (seen[0][1] is not None) == (dtype == "f16x3")       # the plane link is what this test is about
+                if dtype == "f16x3":
+                    assert seen[0][1].mode == pkg._lib.PL_F16X3
+            grads[dtype, lam] = ({k: dict(m.named_parameters())[k].grad.double().clone() for k in names}, float(loss))
+    fig = {}
+    for lam in (None, LAM):
+        a, b = grads["bf16x6", lam], grads["f16x3", lam]
+        fig[lam] = max(float((a[0][k] - b[0][k]).norm() / a[0][k].norm()) for k in names)
+        assert abs(a[1] - b[1]) <= 1e-4 * abs(a[1])
+    print(f"f16x3 vs fp32-grade route, relative L2 distance of the head's gradients: coordinate loss {fig[None]:.3e}, "
+          f"with the heat-map term {fig[LAM]:.3e}")
+    assert fig[LAM] <= 2 * fig[None]
+    # and the heat-map term is in those gradients
+    a0, a1 = grads["bf16x6", None][0], grads["bf16x6", LAM][0]
+    part = float((a0["final_layer.bias"] - a1["final_layer.bias"]).norm() / a0["final_layer.bias"].norm())
+    print(f"the heat-map term's share of the bias gradient: {part:.3e} of the coordinate term's norm")
+    assert part > 5 * fig[None]
+
+
+def test_model2d_through_the_2d_head(pkg):
+    m = pkg.Model_2D(compute_dtype="bf16x6")
+    m.load_state_dict(pkg.synth.seeded_state(m.state_dict(), 41))
+    m = m.to(DEV).train()
+    frames = pkg.synth.seeded_frames(2, 42, size=64).permute(0, 3, 1, 2).contiguous().to(DEV)
+    y = torch.rand(2, 34, generator=torch.Generator().manual_seed(3)).to(DEV)
+    coords, sq = m(frames, heatmap_target=y)
+    assert coords.shape == (2, 34) and sq.shape == (2, 17) and bool(sq.isfinite().all())
+    (((coords - y) ** 2).mean() + pkg.heatmap_mse(sq, 16 * 16) * 1000).backward()
+    gb = m.final_layer.bias.grad
+    assert gb is not None and bool(gb.isfinite().all()) and float(gb.abs().max()) > 0
+    with pytest.raises(ValueError, match="centred heads only"):
+        m(frames, heatmap_target=y, centre="reference")
+    m.eval()
+    ce, se = m(frames, heatmap_target=y)
+    assert torch.equal(ce, m(frames)) and se.shape == (2, 17)

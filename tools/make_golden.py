@@ -159,6 +159,47 @@ def golden_g11():
     np.savez_compressed(os.path.join(OUT, "g11_resnet50_train.npz"), **rec)
 
 
+def golden_g14():
+    """G14: the reference's Gaussian heat-map target, phase3_direct/my_HybrIK/H36_dataset.py imported as-is (its `cv2` and
+    `utils` imports are not installed here and are not needed by the function: stand-in modules take their names) and
+    _keypoint_to_heatmap_3D called on float32 keypoints at both sigmas the file mentions.  Stored sparsely per map: flat
+    indices of the non-zeros in the function's own (u, v, w) order, their values, the count, sum g^2 in fp64."""
+    import importlib.util
+    import types
+    for name, attrs in (("cv2", ()), ("utils", ("camera_parameters", "qv_mult", "flip_pose", "h36m_cameras_intrinsic_params"))):
+        if name not in sys.modules:
+            mod = types.ModuleType(name)
+            for a in attrs:
+                setattr(mod, a, None)
+            sys.modules[name] = mod
+    spec = importlib.util.spec_from_file_location("ref_h36_dataset", "/root/reference/phase3_direct/my_HybrIK/H36_dataset.py")
+    ds = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ds)
+    rng = np.random.default_rng(1401)
+    kps = [(-1, -1, -1), (1, 1, 1), (0, 0, 0),                      # 8-voxel clipped windows; the rounding tie 31.5 -> 32
+           (-1, 1, 0.3), (1, -1, -0.7), (0.96, -0.97, 1),           # mixed faces and edges
+           (1 / 63, -1 / 63, 3 / 63),                               # centres on voxels: mu = 32, 31, 33
+           (2 / 63, 0.5, -0.5)]                                     # another tie: mu = 32.5 -> 32
+    kps += [tuple(r) for r in rng.uniform(-1, 1, size=(16, 3))]
+    kps = np.asarray(kps, dtype=np.float32)
+    rec = {"keypoints": kps, "sigmas": np.array([0.5, 1.75], dtype=np.float64)}
+    for si, sigma in enumerate((0.5, 1.75)):
+        idx, val, cnt, ss = [], [], [], []
+        for kp in kps:
+            im = ds.H36_dataset._keypoint_to_heatmap_3D(None, kp, sigma=sigma)
+            assert im.dtype == np.float32 and im.shape == (64, 64, 64)
+            nz = np.flatnonzero(im)
+            idx.append(nz.astype(np.int32))
+            val.append(im.reshape(-1)[nz])
+            cnt.append(nz.size)
+            ss.append((im.astype(np.float64) ** 2).sum())
+        rec[f"s{si}:index"] = np.concatenate(idx)
+        rec[f"s{si}:value"] = np.concatenate(val)
+        rec[f"s{si}:count"] = np.asarray(cnt, dtype=np.int64)
+        rec[f"s{si}:sumsq"] = np.asarray(ss, dtype=np.float64)
+    np.savez_compressed(os.path.join(OUT, "g14_heatmap_targets.npz"), **rec)
+
+
 def main():
     only = None
     if "--only" in sys.argv:
@@ -171,6 +212,8 @@ def main():
             golden_g10()
         if "g11" in only:
             golden_g11()
+        if "g14" in only:
+            golden_g14()
         for f in sorted(os.listdir(OUT)):
             print(f, os.path.getsize(os.path.join(OUT, f)))
         return
@@ -333,6 +376,7 @@ def main():
                         abs_max=np.float64(feat.abs().max().item()), mean=np.float64(feat.double().mean().item()),
                         sq_mean=np.float64((feat.double() ** 2).mean().item()))
     golden_g11()
+    golden_g14()
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))
 
