@@ -17,4 +17,4 @@ from .backbone import Model_2D, Model_3D, ResNet  # noqa: F401
 from .data import PoseFeeder, epoch_indices  # noqa: F401
 from .vit import MyViT  # noqa: F401
 from .range_guard import PoseliftRangeError  # noqa: F401
-from . import arena, backbone, conv, data, dp, layout, metrics, range_guard, synth, vit  # noqa: F401
+from . import arena, backbone, conv, data, dp, gradclip, layout, metrics, range_guard, synth, vit  # noqa: F401

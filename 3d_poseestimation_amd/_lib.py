@@ -63,6 +63,18 @@ class PLAdamWStep(ctypes.Structure):
                 ("t", ctypes.c_int64), ("t_dev", ctypes.c_void_p)]
 
 
+class PLClipRecord(ctypes.Structure):
+    _fields_ = [("norm", ctypes.c_float), ("coef", ctypes.c_float), ("finite", ctypes.c_uint32), ("skip", ctypes.c_uint32),
+                ("skipped", ctypes.c_uint64)]
+
+
+class PLGradRange(ctypes.Structure):
+    _fields_ = [("lo", ctypes.c_int64), ("hi", ctypes.c_int64)]
+
+
+GRAD_NORM_MAX_RANGES = 1024
+
+
 class PLPlanesEpilogue(ctypes.Structure):
     _fields_ = [("bias", ctypes.c_void_p), ("scale", ctypes.c_void_p), ("shift", ctypes.c_void_p), ("resid", ctypes.c_void_p),
                 ("relu", ctypes.c_int32), ("reserved", ctypes.c_int32), ("y_planes", ctypes.c_void_p)]
@@ -112,6 +124,15 @@ SIGNATURES = {
                                      _c.c_float, _c.c_int64, _P, _c.c_float, _P]),
     "pl_adamw_flat_planes": (_c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_float, _P, _c.c_float, _c.c_float, _c.c_float,
                                         _c.c_float, _c.c_int64, _P, _c.c_float, _c.POINTER(PLAdamWPlanes), _P]),
+    "pl_grad_norm_scratch_bytes": (_c.c_size_t, [_c.c_int]),
+    "pl_grad_norm_clip": (_c.c_int, [_P, _c.c_int64, _c.POINTER(PLGradRange), _c.c_int, _c.c_float, _c.c_int, _c.c_float, _P,
+                                     _c.c_int, _P, _P, _P]),
+    "pl_adamw_flat_clip": (_c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_float, _c.c_float, _c.c_float,
+                                      _c.c_float, _c.c_float, _c.c_int64, _c.c_float, _P, _P]),
+    "pl_adamw_flat_dev_clip": (_c.c_int, [_P, _P, _P, _P, _c.c_int64, _P, _c.c_float, _c.c_float, _c.c_float,
+                                          _c.c_float, _c.c_int64, _P, _c.c_float, _P, _P]),
+    "pl_adamw_flat_planes_clip": (_c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_float, _P, _c.c_float, _c.c_float, _c.c_float,
+                                             _c.c_float, _c.c_int64, _P, _c.c_float, _c.POINTER(PLAdamWPlanes), _P, _P]),
     "pl_wplanes_bytes": (_c.c_size_t, [_D]),
     "pl_wplanes_layer_bytes": (_c.c_size_t, [_D]),
     "pl_weight_plane_scale": (_c.c_float, []),

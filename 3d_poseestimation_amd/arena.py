@@ -22,7 +22,7 @@ Every host call that writes a parameter or buffer through a raw pointer bumps th
 import torch
 from torch.autograd.graph import increment_version
 
-from . import _lib
+from . import _lib, gradclip
 
 
 class ModuleArena:
@@ -85,17 +85,21 @@ class FlatAdam(torch.optim.Optimizer):
     """torch.optim.Adam(module.parameters(), lr, betas, eps) as one library launch over the module's flat arenas."""
 
     def __init__(self, module, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable=False,
-                 decoupled_weight_decay=False):
+                 decoupled_weight_decay=False, max_grad_norm=None, skip_nonfinite=False):
+        max_grad_norm, skip_nonfinite = gradclip.check_options(max_grad_norm, skip_nonfinite)
         if weight_decay != 0.0 and not decoupled_weight_decay:
             raise NotImplementedError("FlatAdam: Adam's coupled L2 weight decay is not implemented (the reference uses 0); "
                                       "decoupled_weight_decay=True is AdamW")
         self.arena = arena_of(module)
         super().__init__(self.arena.params, dict(lr=lr, betas=betas, eps=eps, weight_decay=float(weight_decay),
                                                  capturable=bool(capturable),
-                                                 decoupled_weight_decay=bool(decoupled_weight_decay)))
+                                                 decoupled_weight_decay=bool(decoupled_weight_decay),
+                                                 max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite))
         a = self.arena
         self._m, self._v = torch.zeros_like(a.flat), torch.zeros_like(a.flat)
-        self._t = 0
+        self._t = 0                      # ATTEMPTED steps (as _t_dev); taken = attempted - the clip record's skipped count
+        self._clip = None                # gradclip.GradClip, created by the first step that clips or skips
+        self._skipped_seen = 0
         dev = a.flat.device
         self._t_dev = torch.zeros(1, dtype=torch.int64, device=dev)           # completed steps (capturable)
         self._lr_dev = torch.full((1,), float(lr) if not torch.is_tensor(lr) else float(lr), dtype=torch.float32, device=dev)
@@ -119,6 +123,43 @@ class FlatAdam(torch.optim.Optimizer):
             st["exp_avg"], st["exp_avg_sq"], st["step"] = mv, vv, self._step_tensor
         self._t = t
         self._step_tensor.fill_(t)
+        if self._clip is not None:        # the loaded step counts taken steps: nothing skipped against it
+            self._clip.reset_skipped()
+        self._skipped_seen = 0
+
+    # ---- gradient clipping / non-finite skip (gradclip.py; the gradient arena is not rewritten) -------------------
+    def _clip_state(self):
+        if self._clip is None:
+            self._clip = gradclip.GradClip(self.arena.flat.device)
+        return self._clip
+
+    @property
+    def grad_norm(self):
+        """Device scalar: |grad_scale| * ||g||_2 of the last step that clipped or skipped (no sync)."""
+        return self._clip_state().norm
+
+    @property
+    def clip_coef(self):
+        """Device scalar: the coefficient the last step multiplied its gradient by (no sync)."""
+        return self._clip_state().coef
+
+    def skipped_steps(self):
+        """Steps not taken because their gradient norm was not finite, since construction / load_state_dict (one host read)."""
+        if self._clip is None:
+            return 0
+        self._skipped_seen = self._clip.skipped()
+        return self._skipped_seen
+
+    def state_dict(self):
+        """'step' reports TAKEN steps (attempted - skipped); the live state keeps counting attempts (capturable: on the
+        device, ticking inside the graph)."""
+        sd = super().state_dict()
+        k = self.skipped_steps()
+        if k:
+            taken = self._step_tensor - k
+            for st in sd["state"].values():
+                st["step"] = taken
+        return sd
 
     @torch.no_grad()
     def step(self, closure=None, grad_scale=1.0):
@@ -134,6 +175,9 @@ class FlatAdam(torch.optim.Optimizer):
         L, lr = _lib.lib(), g["lr"]
         wd = float(g["weight_decay"]) if g.get("decoupled_weight_decay", False) else 0.0
         cap = bool(g.get("capturable", False))
+        max_norm, skip = gradclip.check_options(g.get("max_grad_norm"), g.get("skip_nonfinite", False))
+        if (max_norm is not None or skip) and runs:
+            return self._step_clipped(runs, lr, wd, cap, grad_scale, max_norm, skip, loss)
         with _lib.on_device(a.flat.device):
             if cap:
                 if torch.is_tensor(lr):
@@ -155,6 +199,40 @@ class FlatAdam(torch.optim.Optimizer):
                                                self._v.data_ptr() + 4 * lo, hi - lo, float(lr), float(g["betas"][0]),
                                                float(g["betas"][1]), float(g["eps"]), wd, self._t, float(grad_scale),
                                                _lib.current_stream_ptr()), "pl_adamw_flat")
+                self._step_tensor.fill_(float(self._t))
+        increment_version(a.params)
+        return loss
+
+    def _lr_ptr(self, lr):
+        if torch.is_tensor(lr):
+            return lr.data_ptr()                            # (a device scalar the caller changes between replays)
+        if self._lr_host != float(lr) and not torch.cuda.is_current_stream_capturing():
+            self._lr_dev.fill_(float(lr)); self._lr_host = float(lr)
+        return self._lr_dev.data_ptr()
+
+    def _step_clipped(self, runs, lr, wd, cap, grad_scale, max_norm, skip, loss):
+        """step() with max_grad_norm / skip_nonfinite: the norm pass over the runs that hold a gradient, then the same
+        launches with its record.  The counters tick every attempt; the kernels subtract the record's skipped count."""
+        a, g, L = self.arena, self.param_groups[0], _lib.lib()
+        b1, b2, eps = float(g["betas"][0]), float(g["betas"][1]), float(g["eps"])
+        with _lib.on_device(a.flat.device):
+            clip = self._clip_state()
+            clip.launch(a.grad, runs, grad_scale, max_norm, skip, from_device=cap)
+            if cap:
+                lr_ptr = self._lr_ptr(lr)
+                for lo, hi in runs:
+                    _lib.check(L.pl_adamw_flat_dev_clip(a.flat.data_ptr() + 4 * lo, a.grad.data_ptr() + 4 * lo,
+                                                        self._m.data_ptr() + 4 * lo, self._v.data_ptr() + 4 * lo, hi - lo, lr_ptr,
+                                                        b1, b2, eps, wd, 1, self._t_dev.data_ptr(), float(grad_scale), clip.ptr,
+                                                        _lib.current_stream_ptr()), "pl_adamw_flat_dev_clip")
+                _lib.check(L.pl_counter_add(self._t_dev.data_ptr(), 1, _lib.current_stream_ptr()), "pl_counter_add")
+            else:
+                self._t += 1
+                for lo, hi in runs:
+                    _lib.check(L.pl_adamw_flat_clip(a.flat.data_ptr() + 4 * lo, a.grad.data_ptr() + 4 * lo,
+                                                    self._m.data_ptr() + 4 * lo, self._v.data_ptr() + 4 * lo, hi - lo, float(lr),
+                                                    b1, b2, eps, wd, self._t, float(grad_scale), clip.ptr,
+                                                    _lib.current_stream_ptr()), "pl_adamw_flat_clip")
                 self._step_tensor.fill_(float(self._t))
         increment_version(a.params)
         return loss

@@ -33,6 +33,8 @@ struct AdamWIn {
   unsigned short* seg_h[PL_ADAMW_MAX_SEGS];
   unsigned short* seg_l[PL_ADAMW_MAX_SEGS];
   uint32_t* range;   // the range guard's record or NULL (fp16 planes at pscale: the weight slot)
+  // pl_grad_norm_clip's record or NULL (gradnorm.hip): gscale *= coef, t -= skipped, no update when skip
+  const PLClipRecord* clip;
 };
 
 // a slice [p, p + n) of the step carried by another kernel's spare workgroups (small_layer.hip): same fields, same constants
@@ -61,6 +63,27 @@ __device__ __forceinline__ AdamWK adamw_consts(const A& a) {
   k.bc2_sqrt = (float)sqrt(bc2);
   k.eps = a.eps;
   k.gscale = a.gscale;
+  return k;
+}
+
+// The same constants behind pl_grad_norm_clip's record (the clipping forms of the optimizer kernel): a skipped step does not
+// count in the bias corrections (t - skipped: what a loop that does not call optimizer.step() gives), and the clipping
+// coefficient folds into the gradient scale as ONE fp32 product.  (Its own copy rather than a parameter of adamw_consts:
+// the constants of the step without a record compile to the code they always did.)
+__device__ __forceinline__ AdamWK adamw_consts_clip(const AdamWIn& a, const PLClipRecord* clip) {
+  const double lr = a.lr_dev ? (double)a.lr_dev[0] : (double)a.lr;
+  const double t = (double)(a.t + (a.t_dev ? (int64_t)a.t_dev[0] : 0) - (int64_t)clip->skipped);
+  const double bc1 = 1.0 - pow((double)a.beta1, t);
+  const double bc2 = 1.0 - pow((double)a.beta2, t);
+  AdamWK k;
+  k.decay = (float)(1.0 - lr * (double)a.wd);
+  k.one_m_b1 = (float)(1.0 - (double)a.beta1);
+  k.b2 = a.beta2;
+  k.one_m_b2 = (float)(1.0 - (double)a.beta2);
+  k.step_size = (float)(lr / bc1);
+  k.bc2_sqrt = (float)sqrt(bc2);
+  k.eps = a.eps;
+  k.gscale = a.gscale * clip->coef;
   return k;
 }
 

@@ -1352,10 +1352,33 @@ __global__ void gather_rows2_kernel(const float* __restrict__ a, int wa, const f
 }
 
 // ---- flat AdamW (torch single-tensor update order): AdamWIn, adamw_consts, adamw_one in adamw.h ---------
+// CLIP: the step behind pl_grad_norm_clip (in.clip set).  A skipped step writes no p, m, v; it still writes the operand
+// planes, from the unchanged parameters -- the host marks them current after every launch (optim.FlatAdamW._launch), and
+// they may have been stale before it (load_state_dict).  CLIP = false is the kernel as it was.
+template <bool CLIP>
 __global__ __launch_bounds__(NTHR) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                      float* __restrict__ m, float* __restrict__ v,
                                                      int64_t n, AdamWIn in, int vec) {
-  const AdamWK k = adamw_consts(in);
+  if constexpr (CLIP) {
+    if (in.clip->skip) {
+      if (!in.nseg) return;
+      const int64_t stride = (int64_t)gridDim.x * blockDim.x, n4 = n >> 2;
+      for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        const int64_t e = 4 * i;
+#pragma unroll 1
+        for (int q = 0; q < in.nseg; ++q) {
+          const int64_t r = e - in.seg_off[q];
+          if (r >= 0 && r < in.seg_n[q]) {
+            const PlaneDst d = {in.seg_h[q], in.seg_l[q], in.pscale, in.kind, 0, in.range, PL_RANGE_SITE_LIFTER_WEIGHT};
+            store_planes4(d, (size_t)r, ld4(p + e));
+            break;
+          }
+        }
+      }
+      return;
+    }
+  }
+  const AdamWK k = [&] { if constexpr (CLIP) return adamw_consts_clip(in, in.clip); else return adamw_consts(in); }();
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (vec) {
@@ -1777,12 +1800,14 @@ constexpr int kAdamBlocks = 512;
 static int adamw_launch(float* p, const float* g, float* m, float* v, int64_t n, const AdamWIn& in, void* stream) {
   if (!p || !g || !m || !v) PL_FAIL(PL_EINVAL, "pl_adamw_flat: null pointer");
   if (n <= 0 || in.t < (in.t_dev ? 0 : 1)) PL_FAIL(PL_ESHAPE, "pl_adamw_flat: n=%lld t=%lld", (long long)n, (long long)in.t);
+  if (reinterpret_cast<uintptr_t>(in.clip) & 7) PL_FAIL(PL_EINVAL, "pl_adamw_flat: clip record must be 8-byte aligned");
   const int vec = aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v);
   int64_t work = vec ? (n >> 2) : n;
   int blocks = (int)((work + NTHR - 1) / NTHR);
   if (blocks > kAdamBlocks) blocks = kAdamBlocks;
   if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(adamw_kernel, dim3(blocks), dim3(NTHR), 0, (hipStream_t)stream, p, g, m, v, n, in, vec);
+  if (in.clip) hipLaunchKernelGGL(adamw_kernel<true>, dim3(blocks), dim3(NTHR), 0, (hipStream_t)stream, p, g, m, v, n, in, vec);
+  else hipLaunchKernelGGL(adamw_kernel<false>, dim3(blocks), dim3(NTHR), 0, (hipStream_t)stream, p, g, m, v, n, in, vec);
   PL_CHECK_LAUNCH("adamw");
   return PL_OK;
 }
@@ -1795,24 +1820,50 @@ static AdamWIn adamw_in(float lr, float beta1, float beta2, float eps, float wd,
   return in;
 }
 
+extern "C" int pl_adamw_flat_clip(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
+                                  float beta2, float eps, float weight_decay, int64_t t, float grad_scale,
+                                  const PLClipRecord* clip, void* stream) {
+  AdamWIn in = adamw_in(lr, beta1, beta2, eps, weight_decay, grad_scale, t, nullptr, nullptr);
+  in.clip = clip;
+  return adamw_launch(p, g, m, v, n, in, stream);
+}
+
 extern "C" int pl_adamw_flat(float* p, const float* g, float* m, float* v, int64_t n, float lr,
                              float beta1, float beta2, float eps, float weight_decay, int64_t t,
                              float grad_scale, void* stream) {
-  return adamw_launch(p, g, m, v, n, adamw_in(lr, beta1, beta2, eps, weight_decay, grad_scale, t, nullptr, nullptr), stream);
+  return pl_adamw_flat_clip(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, t, grad_scale, nullptr, stream);
+}
+
+extern "C" int pl_adamw_flat_dev_clip(float* p, const float* g, float* m, float* v, int64_t n, const float* lr_dev,
+                                      float beta1, float beta2, float eps, float weight_decay, int64_t t_base,
+                                      const uint64_t* t_dev, float grad_scale, const PLClipRecord* clip, void* stream) {
+  if (!lr_dev || !t_dev) PL_FAIL(PL_EINVAL, "pl_adamw_flat_dev: null lr / t pointer");
+  AdamWIn in = adamw_in(0.f, beta1, beta2, eps, weight_decay, grad_scale, t_base, lr_dev, t_dev);
+  in.clip = clip;
+  return adamw_launch(p, g, m, v, n, in, stream);
 }
 
 extern "C" int pl_adamw_flat_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* lr_dev,
                                  float beta1, float beta2, float eps, float weight_decay, int64_t t_base,
                                  const uint64_t* t_dev, float grad_scale, void* stream) {
-  if (!lr_dev || !t_dev) PL_FAIL(PL_EINVAL, "pl_adamw_flat_dev: null lr / t pointer");
-  return adamw_launch(p, g, m, v, n, adamw_in(0.f, beta1, beta2, eps, weight_decay, grad_scale, t_base, lr_dev, t_dev), stream);
+  return pl_adamw_flat_dev_clip(p, g, m, v, n, lr_dev, beta1, beta2, eps, weight_decay, t_base, t_dev, grad_scale, nullptr,
+                                stream);
 }
 
 extern "C" int pl_adamw_flat_planes(float* p, const float* g, float* m, float* v, int64_t n, float lr, const float* lr_dev,
                                     float beta1, float beta2, float eps, float weight_decay, int64_t t,
                                     const uint64_t* t_dev, float grad_scale, const PLAdamWPlanes* planes, void* stream) {
+  return pl_adamw_flat_planes_clip(p, g, m, v, n, lr, lr_dev, beta1, beta2, eps, weight_decay, t, t_dev, grad_scale, planes,
+                                   nullptr, stream);
+}
+
+extern "C" int pl_adamw_flat_planes_clip(float* p, const float* g, float* m, float* v, int64_t n, float lr,
+                                         const float* lr_dev, float beta1, float beta2, float eps, float weight_decay,
+                                         int64_t t, const uint64_t* t_dev, float grad_scale, const PLAdamWPlanes* planes,
+                                         const PLClipRecord* clip, void* stream) {
   if ((lr_dev != nullptr) != (t_dev != nullptr)) PL_FAIL(PL_EINVAL, "pl_adamw_flat_planes: lr_dev and t_dev go together");
   AdamWIn in = adamw_in(lr, beta1, beta2, eps, weight_decay, grad_scale, t, lr_dev, t_dev);
+  in.clip = clip;
   if (planes && planes->nseg > 0) {
     if (planes->nseg > PL_ADAMW_MAX_SEGS || (planes->kind != 1 && planes->kind != 2) || !(planes->scale > 0.f))
       PL_FAIL(PL_EINVAL, "pl_adamw_flat_planes: bad plane description");

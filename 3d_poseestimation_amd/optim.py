@@ -7,21 +7,32 @@ order.  It is a torch.optim.Optimizer subclass (LR schedulers such as the refere
 ReduceLROnPlateau, train_1.py:41, work unchanged) and its state_dict() has the stock
 AdamW structure (per-parameter 'step', 'exp_avg', 'exp_avg_sq'), so the reference's
 checkpoint envelope {'epoch','batch_size','model','optimizer'} (train_1.py:186) round-trips.
+
+max_grad_norm / skip_nonfinite (gradclip.py): `nn.utils.clip_grad_norm(model.parameters(), max_norm=1)` of the reference's
+lifter script (phase1_lifting/main.py:465-470, MaxNormConctraint) and "do not step on a non-finite gradient", both decided
+on the device: a norm pass over the active ranges of the gradient arena writes a record, the AdamW launch reads it.  The
+gradient arena is not rewritten -- unlike clip_grad_norm_, `p.grad` keeps the UNCLIPPED gradient.  A non-finite gradient
+without skip_nonfinite follows torch's error_if_nonfinite=False: inf norm -> coefficient 0 -> inf * 0 = NaN parameters.
 """
 import torch
 from torch.autograd.graph import increment_version
 
-from . import _lib
+from . import _lib, gradclip
 
 
 class FlatAdamW(torch.optim.Optimizer):
-    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None,
+                 skip_nonfinite=False):
         if not hasattr(model, "flat_params"):
             raise TypeError("FlatAdamW drives a 3d_poseestimation_amd LinearModel")
         self._model = model
-        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        max_grad_norm, skip_nonfinite = gradclip.check_options(max_grad_norm, skip_nonfinite)
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
+                        skip_nonfinite=skip_nonfinite)
         super().__init__(list(model._param_list), defaults)
-        self._t = 0
+        self._t = 0                      # ATTEMPTED steps; taken = _t - (the record's skipped count, on the device)
+        self._clip = None                # gradclip.GradClip, created by the first step that clips or skips
+        self._skipped_seen = 0           # the device's skipped count at the last host read
         self._m = self._v = None
         self._bound_arena = None
 
@@ -44,7 +55,7 @@ class FlatAdamW(torch.optim.Optimizer):
                 self._t = max(self._t, int(st["step"]))
             st["exp_avg"], st["exp_avg_sq"] = mv, vv
             st["step"] = self._step_tensor
-        self._step_tensor.fill_(float(self._t))
+        self._step_tensor_fill()
         self._m, self._v, self._bound_arena = m, v, flat
 
     def _active_ranges(self):
@@ -68,10 +79,56 @@ class FlatAdamW(torch.optim.Optimizer):
                 runs.append((s.offset, end))
         return runs
 
+    # ---- gradient clipping / non-finite skip (gradclip.py) ---------------------------------------------------
+    def _clip_options(self):
+        """(max_grad_norm or None, skip_nonfinite) of this step: param_groups[0], changeable between steps like lr."""
+        g = self.param_groups[0]
+        return gradclip.check_options(g.get("max_grad_norm"), g.get("skip_nonfinite", False))
+
+    def _clipping(self):
+        m, skip = self._clip_options()
+        return m is not None or skip
+
+    def _clip_state(self):
+        if self._clip is None or self._clip.device != self._model.flat_params.device:
+            self._clip = gradclip.GradClip(self._model.flat_params.device)
+            self._skipped_seen = 0
+        return self._clip
+
+    @property
+    def grad_norm(self):
+        """Device scalar: |grad_scale| * ||g||_2 of the last step that clipped or skipped (no sync)."""
+        return self._clip_state().norm
+
+    @property
+    def clip_coef(self):
+        """Device scalar: the coefficient the last step multiplied its gradient by (no sync)."""
+        return self._clip_state().coef
+
+    def skipped_steps(self):
+        """Steps not taken because their gradient norm was not finite, since construction / load_state_dict (one host read)."""
+        if self._clip is None:
+            return 0
+        self._skipped_seen = self._clip.skipped()
+        self._step_tensor_fill()
+        return self._skipped_seen
+
+    def _step_tensor_fill(self):
+        if getattr(self, "_step_tensor", None) is not None:
+            self._step_tensor.fill_(float(self._t - self._skipped_seen))
+
+    def state_dict(self):
+        """'step' reports TAKEN steps (attempted - skipped): one host read of the record when a step was ever clipped."""
+        self.skipped_steps()
+        return super().state_dict()
+
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
         self._bound_arena = None          # loaded tensors are copies: re-bind into the arenas
         self._t = 0
+        if self._clip is not None:        # the loaded step counts taken steps: nothing skipped against it
+            self._clip.reset_skipped()
+        self._skipped_seen = 0
         self._bind()
 
     @torch.no_grad()
@@ -87,27 +144,42 @@ class FlatAdamW(torch.optim.Optimizer):
         g = self.param_groups[0]
         self._t += 1
         self._launch(float(g["lr"]), None, self._t, None, grad_scale)
-        self._step_tensor.fill_(float(self._t))
+        self._step_tensor_fill()
         return loss
 
     def _launch(self, lr, lr_dev, t, t_dev, grad_scale):
         """One pl_adamw_flat_planes launch per run of active tensors.  With the whole arena active (the normal case)
         the same launch refreshes the model's persistent GEMM weight planes while the new parameters are in registers.
-        Returns whether it did."""
+        Returns whether it did.  With max_grad_norm / skip_nonfinite the norm pass over the same runs goes first and every
+        launch takes its record (a skipped step still writes the planes, from the unchanged parameters: marking them
+        current below stays right)."""
         model = self._model
         flat, grads = model.flat_params, model.flat_grads
         g = self.param_groups[0]
         ranges = self._active_ranges()
         planes = model.adamw_plane_segments() if ranges == [(0, flat.numel())] else None
+        max_norm, skip = self._clip_options()
         with _lib.on_device(flat.device):
-            for lo, hi in ranges:
-                rc = _lib.lib().pl_adamw_flat_planes(
-                    flat.data_ptr() + 4 * lo, grads.data_ptr() + 4 * lo, self._m.data_ptr() + 4 * lo,
-                    self._v.data_ptr() + 4 * lo, hi - lo, float(lr), lr_dev.data_ptr() if lr_dev is not None else None,
-                    float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), int(t),
-                    t_dev.data_ptr() if t_dev is not None else None, float(grad_scale),
-                    _lib.ctypes.byref(planes) if planes is not None else None, _lib.current_stream_ptr())
-                _lib.check(rc, "pl_adamw_flat_planes")
+            if max_norm is None and not skip:
+                for lo, hi in ranges:
+                    rc = _lib.lib().pl_adamw_flat_planes(
+                        flat.data_ptr() + 4 * lo, grads.data_ptr() + 4 * lo, self._m.data_ptr() + 4 * lo,
+                        self._v.data_ptr() + 4 * lo, hi - lo, float(lr), lr_dev.data_ptr() if lr_dev is not None else None,
+                        float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), int(t),
+                        t_dev.data_ptr() if t_dev is not None else None, float(grad_scale),
+                        _lib.ctypes.byref(planes) if planes is not None else None, _lib.current_stream_ptr())
+                    _lib.check(rc, "pl_adamw_flat_planes")
+            else:
+                clip = self._clip_state()
+                clip.launch(grads, ranges, grad_scale, max_norm, skip, from_device=lr_dev is not None)
+                for lo, hi in ranges:
+                    rc = _lib.lib().pl_adamw_flat_planes_clip(
+                        flat.data_ptr() + 4 * lo, grads.data_ptr() + 4 * lo, self._m.data_ptr() + 4 * lo,
+                        self._v.data_ptr() + 4 * lo, hi - lo, float(lr), lr_dev.data_ptr() if lr_dev is not None else None,
+                        float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), int(t),
+                        t_dev.data_ptr() if t_dev is not None else None, float(grad_scale),
+                        _lib.ctypes.byref(planes) if planes is not None else None, clip.ptr, _lib.current_stream_ptr())
+                    _lib.check(rc, "pl_adamw_flat_planes_clip")
         increment_version(model._param_list)
         if planes is not None:                # the planes are those of the parameters just written
             model._wplanes_ver = model._planes_key()
@@ -136,4 +208,4 @@ class FlatAdamW(torch.optim.Optimizer):
 
     def _advance_host(self, n=1):
         self._t += n
-        self._step_tensor.fill_(float(self._t))
+        self._step_tensor_fill()

@@ -162,8 +162,10 @@ def train_step(model, optimizer, y1, y2, grad_sync=None):
         # same results as the autograd route below; `zero_grad` is implicit (gradients are overwritten)
         with _lib.on_device(y1.device):
             x2, t2 = y1.reshape(y1.shape[0], -1).contiguous(), y2.reshape(y2.shape[0], -1).contiguous()
-            if grad_sync is None and model._grad_sync is None and model.step_carries_adamw(x2.shape[0]):
+            if (grad_sync is None and model._grad_sync is None and model.step_carries_adamw(x2.shape[0])
+                    and not optimizer._clipping()):
                 # small batches: AdamW rides in the backward launches (pl_lifter_train_step) -- one library call per step
+                # (not with max_grad_norm / skip_nonfinite: the norm of the whole gradient has to exist before any update)
                 adamw = optimizer._step_struct(float(optimizer.param_groups[0]["lr"]), None, optimizer._t + 1, None)
                 if adamw is not None:
                     loss, y2_hat = model.fused_train_fwd_bwd(x2, t2, None, adamw=adamw)
@@ -211,21 +213,31 @@ class GraphedTrainStep:
         self._lr = float(optimizer.param_groups[0]["lr"])
         self._lr_dev = torch.full((1,), self._lr, dtype=torch.float32, device=dev)
         optimizer._bind()
+        # max_grad_norm / skip_nonfinite: the captured sequence is fwd+bwd, the norm pass, one AdamW launch; max_norm is read
+        # from a device scalar refreshed like the learning rate, the skipped count from the optimizer's record
+        max_norm, skip = optimizer._clip_options()
+        self._clip_mode = (max_norm is not None, skip)
         with _lib.on_device(dev):
             # one eager step on a snapshot: every kernel is loaded and the workspace sits in the model's pool before
             # anything is captured; the snapshot is then restored (the step must not count)
-            snap = [t.clone() for t in (model.flat_params, model._bn_running, model._bn_batches, optimizer._m, optimizer._v)]
+            state = [model.flat_params, model._bn_running, model._bn_batches, optimizer._m, optimizer._v]
+            if optimizer._clipping():
+                state.append(optimizer._clip_state().record)
+            snap = [t.clone() for t in state]
             step0, t0 = model._step, optimizer._t
             train_step(model, optimizer, self._x, self._y.reshape(self._out_shape))
-            for dst, src in zip((model.flat_params, model._bn_running, model._bn_batches, optimizer._m, optimizer._v), snap):
+            for dst, src in zip(state, snap):
                 dst.copy_(src)
             model._step, optimizer._t = step0, t0
-            optimizer._step_tensor.fill_(float(t0))
+            optimizer._step_tensor_fill()
             increment_version(model._arena_tensors)      # (the copies above wrote the arenas, not these views)
             model._ensure_wplanes()          # restoring the snapshot made the persistent weight planes stale
+            if self._clip_mode[0] and not torch.is_tensor(optimizer.param_groups[0]["max_grad_norm"]):
+                optimizer._clip_state().refresh_max_norm(optimizer.param_groups[0]["max_grad_norm"])
             torch.cuda.synchronize(dev)
             self.graph = torch.cuda.CUDAGraph()
-            adamw = optimizer._step_struct(0.0, self._lr_dev, t0, self._tick) if model.step_carries_adamw(B) else None
+            adamw = (optimizer._step_struct(0.0, self._lr_dev, t0, self._tick)
+                     if model.step_carries_adamw(B) and not optimizer._clipping() else None)
             self._in_call = adamw is not None
             with torch.cuda.graph(self.graph):
                 if adamw is not None:        # small batches: the optimizer step is inside the same call's launches
@@ -256,6 +268,12 @@ class GraphedTrainStep:
         if lr != self._lr:                                                   # ReduceLROnPlateau et al. (train_1.py:106)
             self._lr = lr
             self._lr_dev.fill_(lr)
+        max_norm, skip = self.opt._clip_options()
+        if (max_norm is not None, skip) != self._clip_mode:
+            raise _lib.PoseliftError("GraphedTrainStep: max_grad_norm / skip_nonfinite were switched on or off after capture "
+                                     "(their value may change, not whether the step has a norm pass): capture a new one")
+        if max_norm is not None and not torch.is_tensor(max_norm):
+            self.opt._clip_state().refresh_max_norm(max_norm)
         # an eager train_step / optimizer.step() / load_state_dict() between replays moves the host-side counters but
         # not the device counter the captured launches read: re-seed it when both moved together, refuse otherwise
         ds, dt = self.model._step - self._step0, self.opt._t - self._t0

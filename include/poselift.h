@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define PL_VERSION 112 /* 0.1.12: + pl_pose_errors, pl_pose_errors_host, pl_pose_metrics_scratch_bytes, pl_pose_metrics_accum (evaluation: MPJPE / N-MPJPE / P-MPJPE, PCK counts, per group); 0.1.11: + pl_vit_*_bf16, pl_vit_bf16_pack (MyViT "bf16p": bf16 operand carriers written by their producers); 0.1.10: + pl_vit_* (the MyViT transformer lifter); 0.1.9: + pl_conv2d_planes_fwd_hw, pl_conv2d_planes_wgrad_hw (the stem on the planes GEMM); 0.1.8: + pl_lifter_train_step, pl_lifter_step_carries_adamw; 0.1.7: + pl_workspace_bitmap_format (small-batch layer kernels); 0.1.6: + pl_counter_add; 0.1.5: + pl_flip_pose_ex, pl_flip_w_nhwc (phase5 Flip branch); 0.1.4: + pl_planes_split_strided; 0.1.3: + pl_bn_join_bwd (0.1.2: operand-plane outputs of the BatchNorm / join kernels, pl_gemm_planes_raw) */
+#define PL_VERSION 113 /* 0.1.13: + PLClipRecord, pl_grad_norm_scratch_bytes, pl_grad_norm_clip, pl_adamw_flat_clip, pl_adamw_flat_dev_clip, pl_adamw_flat_planes_clip (gradient-norm clipping and non-finite skip on the device); 0.1.12: + pl_pose_errors, pl_pose_errors_host, pl_pose_metrics_scratch_bytes, pl_pose_metrics_accum (evaluation: MPJPE / N-MPJPE / P-MPJPE, PCK counts, per group); 0.1.11: + pl_vit_*_bf16, pl_vit_bf16_pack (MyViT "bf16p": bf16 operand carriers written by their producers); 0.1.10: + pl_vit_* (the MyViT transformer lifter); 0.1.9: + pl_conv2d_planes_fwd_hw, pl_conv2d_planes_wgrad_hw (the stem on the planes GEMM); 0.1.8: + pl_lifter_train_step, pl_lifter_step_carries_adamw; 0.1.7: + pl_workspace_bitmap_format (small-batch layer kernels); 0.1.6: + pl_counter_add; 0.1.5: + pl_flip_pose_ex, pl_flip_w_nhwc (phase5 Flip branch); 0.1.4: + pl_planes_split_strided; 0.1.3: + pl_bn_join_bwd (0.1.2: operand-plane outputs of the BatchNorm / join kernels, pl_gemm_planes_raw) */
 
 typedef enum PLStatus {
   PL_OK = 0,
@@ -489,6 +489,52 @@ typedef struct PLAdamWPlanes {
 int pl_adamw_flat_planes(float* p, const float* g, float* m, float* v, int64_t n, float lr, const float* lr_dev,
                          float beta1, float beta2, float eps, float weight_decay, int64_t t, const uint64_t* t_dev,
                          float grad_scale, const PLAdamWPlanes* planes, void* stream);
+/* ---- gradient-norm clipping and non-finite skip over a flat gradient arena --------------------
+ * nn.utils.clip_grad_norm(model.parameters(), max_norm=1) between loss.backward() and optimizer.step()
+ * (phase1_lifting/main.py:465-470, MaxNormConctraint), without a host decision: pl_grad_norm_clip writes a small device
+ * record, the *_clip forms of the flat AdamW step read it.  The gradient arena itself is never rewritten.
+ *   norm    = |grad_scale| * sqrt(sum of g^2 over the ranges), the sum in fp64 (a product of two fp32 values is exact
+ *             there: no square overflows or underflows), rounded to fp32 once
+ *   coef    = min(1, max_norm / (norm + 1e-6f)) in fp32, torch's formula (NaN stays NaN); 1 when clip == 0
+ *   finite  = isfinite(norm)
+ *   skip    = skip_nonfinite && !finite: the AdamW launches behind this record leave p, m, v bitwise untouched (and still
+ *             write the operand planes, from the unchanged parameters)
+ *   skipped = number of steps skipped so far (this call adds 1 when skip); AdamW's bias corrections use t - skipped,
+ *             which is what a loop that does not call optimizer.step() on such a step gives
+ * The caller zeroes the record once and keeps it for the life of the optimizer (it is baked into captured graphs). */
+typedef struct PLClipRecord {
+  float norm;
+  float coef;
+  uint32_t finite;
+  uint32_t skip;
+  uint64_t skipped;
+} PLClipRecord;
+/* [lo, hi) in floats of the arena; lo a multiple of 4, hi arbitrary; ascending and disjoint.  Nothing outside the ranges
+ * is read: a NaN in an inactive slot (BN=False, a frozen parameter, no gradient) does not matter. */
+typedef struct PLGradRange {
+  int64_t lo, hi;
+} PLGradRange;
+#define PL_GRAD_NORM_MAX_RANGES 1024
+size_t pl_grad_norm_scratch_bytes(int nranges);
+/* g: the gradient arena of n floats, 16-byte aligned.  clip != 0: max_norm (>= 0) by value, or *max_norm_dev when that
+ * pointer is set (captured graphs, as lr / lr_dev).  record and scratch (>= pl_grad_norm_scratch_bytes(nranges)) 8-byte
+ * aligned.  Per-workgroup fp64 partials, then one workgroup sums them in a fixed order: no atomics, a repeated call gives
+ * the same bits. */
+int pl_grad_norm_clip(const float* g, int64_t n, const PLGradRange* ranges, int nranges, float grad_scale, int clip,
+                      float max_norm, const float* max_norm_dev, int skip_nonfinite, PLClipRecord* record, void* scratch,
+                      void* stream);
+/* pl_adamw_flat / pl_adamw_flat_dev / pl_adamw_flat_planes with the record of the pl_grad_norm_clip launched before them on
+ * the stream: the gradient is multiplied by grad_scale * clip->coef (one fp32 product), t is t - clip->skipped, and nothing
+ * is updated when clip->skip.  clip == NULL: exactly the call without the suffix. */
+int pl_adamw_flat_clip(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                       float weight_decay, int64_t t, float grad_scale, const PLClipRecord* clip, void* stream);
+int pl_adamw_flat_dev_clip(float* p, const float* g, float* m, float* v, int64_t n, const float* lr_dev, float beta1,
+                           float beta2, float eps, float weight_decay, int64_t t_base, const uint64_t* t_dev,
+                           float grad_scale, const PLClipRecord* clip, void* stream);
+int pl_adamw_flat_planes_clip(float* p, const float* g, float* m, float* v, int64_t n, float lr, const float* lr_dev,
+                              float beta1, float beta2, float eps, float weight_decay, int64_t t, const uint64_t* t_dev,
+                              float grad_scale, const PLAdamWPlanes* planes, const PLClipRecord* clip, void* stream);
+
 /* Layout of the caller-owned weight-plane buffer PLDesc.wplanes: pl_wplanes_bytes() bytes (0: this descriptor has no
  * planes path); the planes of hidden layer l (1 <= l < n_hidden) start at byte (l - 1) * pl_wplanes_layer_bytes(d):
  * plane h, then (PL_F16X3) plane l, hidden*hidden 16-bit elements each, row-major like the weight. */
