@@ -146,7 +146,7 @@ enum class Stats : uint8_t {   // BatchNorm statistics of a training forward
   None,
   InLayer,                     // small batches: Linear, statistics, finalize, apply in one small_layer.hip launch (tile bitmap)
   Small,                       // small batches: the Linear, then the rest in one launch (bn_small_fwd_kernel, row bitmap)
-  // The statistics finalize inside the apply launch (bn_apply_kernel, BnFin): local statistics, <= 4 groups (256
+  // The statistics finalize inside the apply launch (bn_apply_kernel, BnApplyArgs::fin): local statistics, <= 4 groups (256
   // rows).  Measured same-box, step in ms with / without: B = 96 0.312 / 0.319, 128 0.295 / 0.300,
   // 256 0.298 / 0.304 -- and, when tried up to 16 groups, 512 0.353 / 0.351, 1,024 0.419 / 0.391: the dependent prologue in
   // every workgroup costs what the 4.9 us launch did as soon as there are more than a few groups (round 2 saw the same at 64).
@@ -344,10 +344,9 @@ BnrSlab bnr_slab(const PLDesc* d, const Ws& w, void* ws, int rc, int n_amax, boo
 }
 
 struct Layer {
-  const float *W, *b, *gamma, *beta;
+  const float *W, *b;
+  BnParams bn;
   float *gW, *gb, *ggamma, *gbeta;
-  float *rm, *rv;
-  int64_t* nbt;
   int K;
 };
 
@@ -357,20 +356,27 @@ Layer layer_of(const PLDesc* d, const ParamLayout& pl_, float* grads, int l) {
   y.K = l == 0 ? d->in_dim : H;
   y.W = d->params + pl_.off[4 * l];
   y.b = d->params + pl_.off[4 * l + 1];
-  y.gamma = d->params + pl_.off[4 * l + 2];
-  y.beta = d->params + pl_.off[4 * l + 3];
+  y.bn.gamma = d->params + pl_.off[4 * l + 2];
+  y.bn.beta = d->params + pl_.off[4 * l + 3];
+  y.bn.eps = d->bn_eps;
+  y.bn.momentum = d->bn_momentum;
+  y.bn.running_mean = d->bn_running ? d->bn_running + (size_t)l * 2 * H : nullptr;
+  y.bn.running_var = d->bn_running ? d->bn_running + (size_t)l * 2 * H + H : nullptr;
+  y.bn.batches = d->bn_batches ? d->bn_batches + l : nullptr;
   y.gW = grads ? grads + pl_.off[4 * l] : nullptr;
   y.gb = grads ? grads + pl_.off[4 * l + 1] : nullptr;
   y.ggamma = grads ? grads + pl_.off[4 * l + 2] : nullptr;
   y.gbeta = grads ? grads + pl_.off[4 * l + 3] : nullptr;
-  y.rm = d->bn_running ? d->bn_running + (size_t)l * 2 * H : nullptr;
-  y.rv = d->bn_running ? d->bn_running + (size_t)l * 2 * H + H : nullptr;
-  y.nbt = d->bn_batches ? d->bn_batches + l : nullptr;
   return y;
 }
 
 inline float* f32(void* ws, size_t off) { return reinterpret_cast<float*>(static_cast<char*>(ws) + off); }
 inline uint64_t* u64(void* ws, size_t off) { return reinterpret_cast<uint64_t*>(static_cast<char*>(ws) + off); }
+
+// what hidden layer l's forward saves in the workspace for its backward
+inline BnSaved saved_of(const Ws& w, void* ws, int l) {
+  return BnSaved{f32(ws, w.z[l]), u64(ws, w.bits[l]), f32(ws, w.mean[l]), f32(ws, w.rstd[l]), w.layer[l].stats == Stats::InLayer};
+}
 
 int check_ws(const Ws& w, void* ws, size_t bytes) {
   if (!ws) PL_FAIL(PL_EWORKSPACE, "workspace is NULL");
@@ -563,17 +569,22 @@ extern "C" int pl_lifter_fwd_eval(const PLDesc* d, const float* x, float* y, int
       const bool last = l == w.L - 1;
       // (a whole-tile batch's plan keeps no fp32 activation for the odd layers: their output goes through the z buffer)
       float* out = w.act_f32[l] ? f32(ws, w.act[l]) : f32(ws, w.z[l]);
-      PL_TRY(launch_small_layer_eval(a_in, ly.W, ly.b, ly.gamma, ly.beta, d->bn_eps, ly.rm, ly.rv, resid, out,
-                                     (int)B, H, ly.K, s, l == 0, last ? d->params + P.off[4 * w.L] : nullptr,
-                                     last ? f32(ws, w.slabs) : nullptr, d->out_dim, sact_in(w, ws, l), sact_out(w, ws, l), l));
+      SmallLayerFwdArgs a = {};
+      a.a = a_in; a.W = ly.W; a.bias = ly.b; a.bn = ly.bn; a.resid = resid; a.act = out;
+      a.B = (int)B; a.H = H; a.K = ly.K; a.layer = l; a.first = l == 0;
+      if (last) { a.W2 = d->params + P.off[4 * w.L]; a.ypart = f32(ws, w.slabs); a.O = d->out_dim; }
+      a.a_planes = sact_in(w, ws, l); a.out_planes = sact_out(w, ws, l);
+      PL_TRY(launch_small_layer_eval(a, s));
       a_in = out;
     }
-    return launch_small_out(f32(ws, w.slabs), H / 16, (int)B, d->out_dim, d->params + P.off[4 * w.L + 1], y, s);
+    SmallHeadArgs h = {};
+    h.ypart = f32(ws, w.slabs); h.NS = H / 16; h.B = (int)B; h.O = d->out_dim; h.bias = d->params + P.off[4 * w.L + 1]; h.y = y;
+    return launch_small_out(h, s);
   }
   for (int l = 0; l < w.L; ++l) {
     const Layer ly = layer_of(d, P, nullptr, l);
-    PL_TRY(launch_bn_fold_eval(ly.b, ly.gamma, ly.beta, ly.rm, ly.rv, d->bn_eps, d->bn, H,
-                               f32(ws, w.scale) + (size_t)l * H, f32(ws, w.shift) + (size_t)l * H, s));
+    PL_TRY(launch_bn_fold_eval(ly.b, d->bn ? &ly.bn : nullptr, H, f32(ws, w.scale) + (size_t)l * H,
+                               f32(ws, w.shift) + (size_t)l * H, s));
   }
   const float* a_in = x;
   if (w.planes) PL_TRY(split_weight_planes(d, P, w, ws, s));
@@ -661,15 +672,17 @@ static int fwd_saved_impl(const PLDesc* d, const float* x, float* y, int64_t B, 
     g.thin_scratch = f32(ws, w.slabs); g.thin_scratch_floats = w.slab_floats;
     float* stat = f32(ws, w.stat);
     const float* resid = (l >= 2 && (l % 2) == 0) ? f32(ws, w.act[l - 2]) : nullptr;
+    const BnSaved sv = saved_of(w, ws, l);
+    const DropKey drop = dropout_key(eval_bn ? 0.f : d->p_dropout, seed, step, l,
+                                     inject_keep ? inject_keep + (size_t)l * inj_stride : nullptr, eval_bn ? nullptr : d->step_dev);
     if (st == Stats::InLayer) {
-      const bool slabs_here = head_slabs && l == w.L - 1;
-      PL_TRY(launch_small_layer_fwd(a_in, ly.W, ly.b, ly.gamma, ly.beta, d->bn_eps, d->bn_momentum, ly.rm, ly.rv, ly.nbt,
-                                    f32(ws, w.mean[l]), f32(ws, w.rstd[l]), resid, g.C, f32(ws, w.act[l]), u64(ws, w.bits[l]),
-                                    (int)B, H, ly.K, d->p_dropout, seed, step, l,
-                                    inject_keep ? inject_keep + (size_t)l * inj_stride : nullptr, s, d->step_dev, l == 0,
-                                    slabs_here ? d->params + P.off[4 * w.L] : nullptr, slabs_here ? f32(ws, w.slabs) : nullptr,
-                                    d->out_dim, sact_in(w, ws, l), sact_out(w, ws, l)));
-      a_in = f32(ws, w.act[l]);
+      SmallLayerFwdArgs a = {};
+      a.a = a_in; a.W = ly.W; a.bias = ly.b; a.bn = ly.bn; a.saved = sv; a.resid = resid; a.act = f32(ws, w.act[l]);
+      a.B = (int)B; a.H = H; a.K = ly.K; a.layer = l; a.drop = drop; a.first = l == 0;
+      if (head_slabs && l == w.L - 1) { a.W2 = d->params + P.off[4 * w.L]; a.ypart = f32(ws, w.slabs); a.O = d->out_dim; }
+      a.a_planes = sact_in(w, ws, l); a.out_planes = sact_out(w, ws, l);
+      PL_TRY(launch_small_layer_fwd(a, s));
+      a_in = a.act;
       continue;
     }
     if (st == Stats::InApply || st == Stats::Finalize) {
@@ -678,50 +691,52 @@ static int fwd_saved_impl(const PLDesc* d, const float* x, float* y, int64_t B, 
     }
     if (r.lin == Lin::Skinny) {
       PL_TRY(launch_skinny_wide_out(a_in, ly.W, ly.b, g.C, (int)B, ly.K, H, false, g.stat_sum, g.stat_m2, s));
-    } else if (r.lin == Lin::PlanesMid) {
-      PL_TRY(launch_small_linear_stats(nullptr, u16(ws, w.actp[l - 1]), ly.W, ly.b, g.C, (int)B, H, H, g.stat_sum, g.stat_m2, r.groups, s));
+    } else if (r.lin == Lin::PlanesMid || r.lin == Lin::F32Mid) {
+      SmallLinearStatsArgs q = {};
+      if (r.lin == Lin::PlanesMid) q.a_planes = u16(ws, w.actp[l - 1]); else q.a = a_in;
+      q.W = ly.W; q.bias = ly.b; q.z = sv.z; q.M = (int)B; q.H = H; q.K = H;
+      q.stat_sum = g.stat_sum; q.stat_m2 = g.stat_m2; q.groups = r.groups;
+      PL_TRY(launch_small_linear_stats(q, s));
     } else if (r.lin == Lin::Planes) {
       PlanesGemmArgs pg = planes_args(w.pkind, u16(ws, w.actp[l - 1]), BH, H, wplane(d, w, ws, l), (int64_t)H * H, H, g.C, (int)B, H, H,
                                       1.0f / (kActPlaneScale * kWeightPlaneScale), nullptr);
       pg.e.bias = ly.b; pg.e.stat_sum = g.stat_sum; pg.e.stat_m2 = g.stat_m2;
       PL_TRY(launch_gemm_planes(kNT, pg, s));
-    } else if (r.lin == Lin::F32Mid) {
-      PL_TRY(launch_small_linear_stats(a_in, nullptr, ly.W, ly.b, g.C, (int)B, H, H, g.stat_sum, g.stat_m2, r.groups, s));
     } else {
       PL_TRY(launch_gemm_f32(kNT, g, s));
     }
-    const float *scale = nullptr, *shift = nullptr;
+    BnApplyArgs ap = {};
     BnFinalizeArgs fin = {};
-    float* sc = f32(ws, w.scale) + (size_t)l * H;
-    float* sh = f32(ws, w.shift) + (size_t)l * H;
+    fin.G = r.groups; fin.group_rows = 64; fin.world = sync_world(d); fin.B = (int)B; fin.H = H;
+    fin.bn = ly.bn; fin.mean = sv.mean; fin.rstd = sv.rstd;
+    fin.scale = f32(ws, w.scale) + (size_t)l * H; fin.shift = f32(ws, w.shift) + (size_t)l * H;
     if (d->bn && eval_bn) {
-      PL_TRY(launch_bn_eval_stats(ly.gamma, ly.beta, ly.rm, ly.rv, d->bn_eps, H, f32(ws, w.mean[l]), f32(ws, w.rstd[l]),
-                                  sc, sh, s));
-      scale = sc; shift = sh;
+      PL_TRY(launch_bn_eval_stats(fin, s));
+      ap.scale = fin.scale; ap.shift = fin.shift;
     } else if (st == Stats::InApply) {
-      fin = BnFinalizeArgs{stat, r.groups, 64, ly.gamma, ly.beta, d->bn_eps, d->bn_momentum, ly.rm, ly.rv, ly.nbt,
-                           f32(ws, w.mean[l]), f32(ws, w.rstd[l])};
+      fin.stat = stat;
+      ap.fin = fin;
     } else if (st == Stats::Finalize) {
       PL_TRY(sync_gather(d, stat, (int64_t)2 * r.groups * H, s));
-      PL_TRY(launch_bn_finalize(stat, r.groups, sync_world(d), (int)B, H, ly.gamma, ly.beta, d->bn_eps,
-                                d->bn_momentum, ly.rm, ly.rv, ly.nbt, f32(ws, w.mean[l]),
-                                f32(ws, w.rstd[l]), sc, sh, s));
-      scale = sc; shift = sh;
+      fin.stat = stat;
+      PL_TRY(launch_bn_finalize(fin, s));
+      ap.scale = fin.scale; ap.shift = fin.shift;
     } else if (st == Stats::Small) {
-      PL_TRY(launch_bn_small_fwd(g.C, ly.gamma, ly.beta, d->bn_eps, d->bn_momentum, ly.rm, ly.rv, ly.nbt, f32(ws, w.mean[l]),
-                                 f32(ws, w.rstd[l]), resid, f32(ws, w.act[l]), u64(ws, w.bits[l]), (int)B, H, d->p_dropout, seed,
-                                 step, l, inject_keep ? inject_keep + (size_t)l * inj_stride : nullptr, s, d->step_dev));
-      a_in = f32(ws, w.act[l]);
+      BnSmallFwdArgs a = {};
+      a.saved = sv; a.bn = ly.bn; a.resid = resid; a.act = f32(ws, w.act[l]); a.B = (int)B; a.H = H; a.drop = drop;
+      PL_TRY(launch_bn_small_fwd(a, s));
+      a_in = a.act;
       continue;
     }
-    PlaneOut po = {nullptr, nullptr, kActPlaneScale, nullptr, 0};
-    if (w.planes && l + 1 < w.L) { po.h = u16(ws, w.actp[l]); po.l = po.h + BH; po.kind = w.pkind; range_watch(po, range_site_act(l)); }
-    float* act = w.act_f32[l] ? f32(ws, w.act[l]) : nullptr;
-    PL_TRY(launch_bn_apply(g.C, scale, shift, resid, act, u64(ws, w.bits[l]), (int)B, H,
-                           eval_bn ? 0.f : d->p_dropout, seed, step, l,
-                           inject_keep ? inject_keep + (size_t)l * inj_stride : nullptr, s, &po,
-                           eval_bn ? nullptr : d->step_dev, st == Stats::InApply ? &fin : nullptr));
-    a_in = act;
+    ap.z = sv.z; ap.resid = resid; ap.act = w.act_f32[l] ? f32(ws, w.act[l]) : nullptr; ap.bits = sv.bits;
+    ap.B = (int)B; ap.H = H; ap.drop = drop;
+    ap.planes.scale = kActPlaneScale;
+    if (w.planes && l + 1 < w.L) {
+      ap.planes.h = u16(ws, w.actp[l]); ap.planes.l = ap.planes.h + BH; ap.planes.kind = w.pkind;
+      range_watch(ap.planes, range_site_act(l));
+    }
+    PL_TRY(launch_bn_apply(ap, s));
+    a_in = ap.act;
   }
   if (head_slabs) return PL_OK;
   if (defer_out_reduce)   // (the fused train step: y = bias + slabs is formed by the MSE pass, mse_partial_from_slabs)
@@ -734,6 +749,260 @@ static int fwd_saved_impl(const PLDesc* d, const float* x, float* y, int64_t B, 
 // ---------------------------------------------------------------------------------------
 // backward
 // ---------------------------------------------------------------------------------------
+namespace pl {
+namespace {
+
+// What the parts of one backward range share.
+struct BwdCtx {
+  const PLDesc* d;
+  const Ws& w;
+  const ParamLayout& P;
+  void* ws;
+  hipStream_t s;
+  const float *x, *dy;
+  float *dx, *grads;
+  int B, H, O;
+  int l_hi, l_lo;
+  float kscale;                 // 1 / (1 - p) of the dropout the forward applied
+  bool eval_bn;
+  bool small, sl;               // small batches: every BatchNorm in one launch; layers 1.. on the layer kernels (small_layer.hip)
+  bool top_fused;               // the output layer and the top hidden layer's BatchNorm backward in one launch (dz of that layer: DZ)
+  float* loss_out;              // the fused train step: the loss is finalised by a launch of this range
+  int n_loss_part;              //   ... from this many partial sums in w.mse
+  // the AdamW step carried by the backward launches (pl_lifter_train_step) or run behind them
+  const PLAdamWStep* adam;
+  bool adam_rides;
+  // bias gradients and split-K slabs = column sums of partials; all of them are reduced by ONE launch at the end
+  std::vector<RowJob> jobs;
+
+  float* buf(size_t off) const { return f32(ws, off); }
+  float* GA() const { return buf(w.ga); }
+  float* GB() const { return buf(w.gb); }
+  float* DZ() const { return buf(w.dz); }
+  int64_t BH() const { return (int64_t)B * H; }
+  // gradient w.r.t. layer l's activation: GA for layer 0 and even layers, GB for odd ones
+  const float* gin(int l) const { return (l % 2 == 1) ? GB() : GA(); }
+  // where dz of layer l lives (layer kernels: alternating -- a launch reads dz_l and writes dz_{l-1})
+  float* dzbuf(int l) const { return (sl && (l & 1)) ? GB() : DZ(); }
+  bool planes_pair(int l) const { return w.layer[l].bwd == Bwd::PlanesPair; }      // layer l's dz feeds the planes GEMM pair
+  // fp16 planes of dz are range-scaled: {S, 1/S} of layer l on the device, or NULL
+  float* dzs(int l) const { return (planes_pair(l) && w.pkind == 2) ? buf(w.dzscale) + 2 * l : nullptr; }
+  void job(const float* part, float* out, int R, int Hj, int kind, int transK) { jobs.push_back(RowJob{part, out, R, Hj, kind, transK}); }
+  // small batches (small_layer.hip): what describes a layer's BatchNorm -- and its bitmap's format
+  SmallBnLayer bn_layer(int l) const {
+    const Layer y = layer_of(d, P, grads, l);
+    return SmallBnLayer{saved_of(w, ws, l), y.bn.gamma, y.ggamma, y.gbeta, y.gb};
+  }
+  // which slice of the arena rides with a launch
+  AdamWRide ride(int64_t lo, int64_t hi) const {
+    AdamWRide r = {};
+    r.p = const_cast<float*>(d->params) + lo; r.g = grads + lo; r.m = adam->m + lo; r.v = adam->v + lo; r.n = hi - lo;
+    r.lr = adam->lr; r.beta1 = adam->beta1; r.beta2 = adam->beta2; r.eps = adam->eps; r.wd = adam->weight_decay; r.gscale = 1.0f;
+    r.t = adam->t; r.lr_dev = adam->lr_dev; r.t_dev = adam->t_dev;
+    return r;
+  }
+};
+
+// BatchNorm-backward pass 1 of layer l inside the epilogue of the GEMM that produces its incoming gradient
+// (LayerRoute::bnr_fused): partial sums per 64-row block, and -- where the layer's dz leaves as fp16 planes (PL_F16X3, not the
+// first layer) -- the range maxima per (64-row block, 64-column strip); the top layer's gradient comes from the skinny
+// kernel, whose strips are 32 columns wide.
+int bnr_amax_pairs(const BwdCtx& c, int l) { return (c.B / 64) * (c.H / (l == c.w.L - 1 ? 32 : 64)); }
+void fill_bnr(const BwdCtx& c, int l, GemmArgs& e) {
+  const BnSaved sv = saved_of(c.w, c.ws, l);
+  const bool scaled = c.w.pkind == 2 && l > 0;
+  const BnrSlab slab = bnr_slab(c.d, c.w, c.ws, c.B / 64, scaled ? bnr_amax_pairs(c, l) : 0, c.eval_bn);
+  e.bnr_z = sv.z; e.bnr_bits = sv.bits; e.bnr_mean = sv.mean; e.bnr_rstd = sv.rstd; e.bnr_kscale = c.kscale;
+  e.bnr_part_dy = slab.mine; e.bnr_part_dyz = slab.mine + (size_t)(c.B / 64) * c.H;
+  e.bnr_amax = scaled ? slab.amax_mine : nullptr;
+}
+
+// The output layer (LinearModel.w2): dW = dy^T h, db = sum dy, g = dy W -> GA.  Three routes.
+int bwd_output(BwdCtx& c) {
+  const Ws& w = c.w;
+  const int Bi = c.B, H = c.H, O = c.O;
+  const float* W2 = c.d->params + c.P.off[4 * w.L];
+  float* gW2 = c.grads + c.P.off[4 * w.L];
+  float* gb2 = c.grads + c.P.off[4 * w.L + 1];
+  const float* h = c.buf(w.act[w.L - 1]);
+  if (c.top_fused) {
+    SmallTopBwdArgs a = {};
+    a.dy = c.dy; a.W2 = W2; a.h = h; a.B = Bi; a.H = H; a.O = O; a.gout = c.GA(); a.dW2 = gW2; a.db2 = gb2;
+    a.top = c.bn_layer(w.L - 1); a.kscale = c.kscale; a.dz_top = c.DZ();
+    a.mpart = c.buf(w.mse); a.np = c.n_loss_part; a.inv_n = 1.0f / (float)((int64_t)Bi * O); a.loss = c.loss_out;
+    a.tick = const_cast<uint64_t*>(c.d->step_dev);
+    return launch_small_top_bwd(a, c.s);
+  }
+  if (w.out_skinny) {
+    // dW5 partials, and -- the kernel holds every row of dy in its A fragments -- the bias gradient's partial column sums
+    // (Round 3 tried this launch on a side stream -- nothing reads its output before the closing reduce, and it and the head of
+    //  the chain below are both latency-bound -- forked and joined with events: 0.627 -> 0.660 ms per step eager, 0.644 -> 0.663
+    //  replayed from a graph, same box: the two cross-stream dependencies cost more than the 13 us launch they hide.)
+    PL_TRY(launch_skinny_wide_in(c.dy, h, gW2, Bi, O, H, false, c.buf(w.skp_out), c.s, false, c.buf(w.outpart)));
+    c.job(c.buf(w.skp_out), gW2, skinny_in_chunks(Bi), O * H, 0, 0);
+    c.job(c.buf(w.outpart), gb2, skinny_in_chunks(Bi), O, 0, 0);
+    GemmArgs be = {};
+    if (!c.eval_bn && w.layer[w.L - 1].bnr_fused) fill_bnr(c, w.L - 1, be);   // pass 1 of the top hidden layer, on the block just produced
+    return launch_skinny_wide_out(c.dy, W2, nullptr, c.GA(), Bi, O, H, true, nullptr, nullptr, c.s, &be);
+  }
+  PL_TRY(gemm_tn_reduced(c.dy, O, h, H, gW2, O, H, Bi, c.buf(w.slabs), c.s));
+  PL_TRY(launch_colsum_partial(c.dy, Bi, O, c.buf(w.outpart), c.s));
+  c.job(c.buf(w.outpart), gb2, colsum_chunks(Bi), O, 0, 0);
+  GemmArgs g = {};
+  g.A = c.dy; g.B = W2; g.C = c.GA(); g.M = Bi; g.N = H; g.K = O; g.lda = O; g.ldb = H; g.ldc = H;
+  g.split_k = 1;
+  return launch_gemm_f32(kNN, g, c.s);
+}
+
+// Hidden layer l: from the gradient of its activation (gin) to dz, dgamma, dbeta and the bias gradient.  Four routes.
+int bwd_layer_bn(BwdCtx& c, int l) {
+  // small batches, layer kernels (small_layer.hip): the dX launch of layer l + 1 (launch_small_layer_bwd) or launch_small_top_bwd
+  // already ran this layer's BatchNorm backward (dz_l sits in dzbuf(l)) unless this layer heads the range
+  if (c.sl && (l < c.l_hi || c.top_fused)) return PL_OK;
+  const Ws& w = c.w;
+  const PLDesc* d = c.d;
+  const int Bi = c.B, H = c.H;
+  if (c.small) {
+    // pass 1, the coefficients, dz, the bias gradient and dgamma / dbeta of this layer in one launch (small batches)
+    BnSmallBwdArgs a = {};
+    a.g = c.gin(l); a.layer = c.bn_layer(l); a.keep_scale = c.kscale; a.B = Bi; a.H = H; a.dz = c.dzbuf(l);
+    return launch_bn_small_bwd(a, c.s);
+  }
+  const Layer ly = layer_of(d, c.P, c.grads, l);
+  const LayerRoute& r = w.layer[l];
+  const BnSaved sv = saved_of(w, c.ws, l);
+  float* dzs = c.dzs(l);
+  if (d->bn) {
+    // pass 1 (column sums of dy and dy*zhat): a streaming kernel of its own, or -- round 2 -- already done by the
+    // LDS-staged epilogue of the planes GEMM that produced `gin` (round 1 tried it in the dword-per-lane epilogue of
+    // the fp32-operand GEMM: +17 us per GEMM for the 7.5 us kernel it removed)
+    const bool fr = !c.eval_bn && r.bnr_fused;
+    const int rc_l = fr ? Bi / 64 : w.RC;
+    const int n_amax_l = fr ? bnr_amax_pairs(c, l) : ((H + 255) / 256) * w.RC;
+    const BnrSlab slab = bnr_slab(d, w, c.ws, rc_l, dzs ? n_amax_l : 0, c.eval_bn);
+    float* stat = c.buf(w.stat);
+    if (!fr) {
+      BnBwdReduceArgs a = {};
+      a.g = c.gin(l); a.saved = sv; a.keep_scale = c.kscale; a.B = Bi; a.H = H; a.rc = rc_l;
+      a.part_dy = slab.mine; a.part_dyz = slab.mine + (size_t)rc_l * H; a.part_amax = dzs ? slab.amax_mine : nullptr;
+      PL_TRY(launch_bn_bwd_reduce(a, c.s));
+    }
+    // (fused: the partials were written by the GEMM / skinny epilogue that produced `gin`, into this rank's slab)
+    if (!c.eval_bn) PL_TRY(sync_gather(d, stat, slab.floats_per_rank, c.s));
+    BnBwdFinalizeArgs f = {};
+    f.part = stat; f.RC = rc_l; f.world = c.eval_bn ? 1 : sync_world(d); f.rank = c.eval_bn ? 0 : sync_rank(d); f.B = Bi; f.H = H;
+    f.gamma = ly.bn.gamma; f.rstd = sv.rstd; f.coef = c.buf(w.coef); f.dgamma = ly.ggamma; f.dbeta = ly.gbeta;
+    f.part_amax = dzs ? slab.amax0 : nullptr; f.n_amax = n_amax_l; f.dz_scale = dzs; f.eval_mode = c.eval_bn ? 1 : 0;
+    f.rstride = slab.floats_per_rank; f.amax_world = slab.world;
+    PL_TRY(launch_bn_bwd_finalize(f, c.s));
+  } else {
+    PL_TRY(launch_fill(ly.ggamma, H, 0.f, c.s));
+    PL_TRY(launch_fill(ly.gbeta, H, 0.f, c.s));
+  }
+  BnBwdDzArgs a = {};
+  a.g = c.gin(l); a.saved = sv; a.coef = c.buf(w.coef); a.keep_scale = c.kscale; a.bn = d->bn; a.B = Bi; a.H = H; a.rc = w.RC;
+  a.dz = c.planes_pair(l) ? nullptr : c.DZ(); a.part_db = c.buf(w.dbpart[l]);
+  a.planes.scale = 1.0f; a.planes.dyn = dzs;
+  if (c.planes_pair(l)) { a.planes.h = u16(c.ws, w.dzp); a.planes.l = a.planes.h + c.BH(); a.planes.kind = w.pkind; }
+  PL_TRY(launch_bn_bwd_dz(a, c.s));
+  c.job(c.buf(w.dbpart[l]), ly.gb, w.RC, H, 0, 0);
+  return PL_OK;
+}
+
+// Hidden layer l: from dz to the gradient of the activation below (GA / GB; dx for layer 0) and the weight gradient.
+// Six routes.
+int bwd_layer_linear(BwdCtx& c, int l) {
+  const Ws& w = c.w;
+  const PLDesc* d = c.d;
+  const int Bi = c.B, H = c.H;
+  hipStream_t s = c.s;
+  const Layer ly = layer_of(d, c.P, c.grads, l);
+  const LayerRoute& r = w.layer[l];
+  float* const GA = c.GA();
+  float* const GB = c.GB();
+  float* const DZ = c.DZ();
+  float* const DZl = c.dzbuf(l);
+  float* slabs = c.buf(w.slabs);
+  const float* a_in = l == 0 ? c.x : (w.planes ? nullptr : c.buf(w.act[l - 1]));
+  if (c.planes_pair(l)) {
+    // dX = dz W (NN) and dW = dz^T a (TN, split-K slabs) on the planes: one launch
+    float* dzs = c.dzs(l);
+    const int64_t BH = c.BH();
+    const int splits = tn_splits(H, H, Bi);
+    PlanesGemmArgs nn = planes_args(w.pkind, u16(c.ws, w.dzp), BH, H, wplane(d, w, c.ws, l), (int64_t)H * H, H,
+                                    (l % 2 == 1) ? GA : GB, Bi, H, H, 1.0f / kWeightPlaneScale, dzs ? dzs + 1 : nullptr);
+    if (l % 2 == 1) nn.e.addend = GA;
+    if (!c.eval_bn && w.layer[l - 1].bnr_fused) fill_bnr(c, l - 1, nn.e);      // pass 1 of the layer below, on the block just produced
+    float* wsl = c.buf(w.wslab[l]);                  // this layer's own slabs: combined by the range's one reduce launch
+    PlanesGemmArgs tn = planes_args(w.pkind, u16(c.ws, w.dzp), BH, H, u16(c.ws, w.actp[l - 1]), BH, H,
+                                    splits > 1 ? wsl : ly.gW, H, H, Bi, 1.0f / kActPlaneScale, dzs ? dzs + 1 : nullptr);
+    tn.e.split_k = splits;
+    PL_TRY(launch_gemm_planes_pair(nn, tn, s));
+    if (splits > 1) c.job(wsl, ly.gW, splits, H * H, 1, 0);
+  } else if (l > 0) {
+    // off the planes path: dX = dz W (+ the skip gradient a residual block's first Linear receives in GA, added in the
+    // epilogue) and dW = dz^T a_in
+    GemmArgs g = {};
+    g.A = DZl; g.B = ly.W; g.M = Bi; g.N = H; g.K = H; g.lda = H; g.ldb = H; g.ldc = H; g.split_k = 1;
+    if (l % 2 == 1) { g.C = GA; g.addend = GA; } else { g.C = GB; }
+    g.arith = arith_of(d);
+    g.thin_scratch = slabs; g.thin_scratch_floats = w.slab_floats;   // (the pair runs as two launches off the tile grid)
+    GemmArgs t = {};
+    t.arith = g.arith;
+    t.A = DZl; t.B = a_in; t.M = H; t.N = H; t.K = Bi; t.lda = H; t.ldb = H; t.ldc = H; t.split_k = 1; t.C = ly.gW;
+    if (c.sl && (r.bwd == Bwd::SmallLayer || r.bwd == Bwd::SmallLayerDw)) {
+      // small batches: dX and the BatchNorm backward of the layer below in one launch when that layer belongs to this
+      // range; the weight gradient is one whole-K launch (K = B <= 64) or extra workgroups of the same launch
+      const bool dw_rides = r.bwd == Bwd::SmallLayerDw;
+      if (l - 1 < c.l_lo) {
+        PL_TRY(launch_gemm_f32(kNN, g, s));
+        return launch_gemm_f32(kTN, t, s);
+      }
+      const bool w1 = l == 1 && w.layer[0].bwd == Bwd::InAbove;
+      // AdamW on this launch's spare workgroups: this layer's bias and BatchNorm parameters (their gradients came with the
+      // launch before) and everything above them up to where the launch before started -- the weight matrix of layer
+      // l + 1 (its gradient, too), or the output layer behind the top hidden layer
+      AdamWRide ar = {};
+      if (c.adam_rides) ar = c.ride(c.P.off[4 * l + 1], l == w.L - 1 ? c.P.total : c.P.off[4 * (l + 1) + 1]);
+      SmallLayerBwdArgs a = {};
+      a.dz = DZl; a.W = ly.W; a.B = Bi; a.H = H; a.K = H;
+      if (l % 2 == 1) { a.addend = GA; a.gout = GA; }
+      a.below = c.bn_layer(l - 1); a.kscale = c.kscale; a.dz_lo = c.dzbuf(l - 1);
+      if (dw_rides) { a.a_in = a_in; a.dW = ly.gW; }
+      if (w1) { a.x1 = c.x; a.dW1 = c.grads + c.P.off[0]; }
+      a.K1 = d->in_dim;
+      if (c.adam_rides) a.adam = &ar;
+      PL_TRY(launch_small_layer_bwd(a, s));
+      return dw_rides ? PL_OK : launch_gemm_f32(kTN, t, s);
+    }
+    // dX and dW share dz and are independent: ONE launch.
+    // (Tried: dW on a side stream so that the next layer's BatchNorm-backward kernels overlap it --
+    //  -2 % per step only: two single-GEMM workgroups do not fit one CU together, so dX and dW
+    //  time-slice the CUs and the dual launch's co-residency is lost.  Same-box A/B, tools/ab_env.py.)
+    const int splits = tn_splits(H, H, Bi);
+    t.split_k = splits; t.C = splits > 1 ? slabs : ly.gW;
+    PL_TRY(launch_gemm_f32_pair(g, t, s));
+    if (splits > 1) PL_TRY(launch_reduce_slabs(slabs, splits, (int64_t)H * H, ly.gW, s));
+  } else if (r.bwd == Bwd::InAbove && c.sl && c.l_hi > 0) {
+    // (layer 0's weight gradient came with its BatchNorm backward, small_layer.hip)
+  } else if (r.lin == Lin::Skinny) {
+    PL_TRY(launch_skinny_wide_in(a_in, DZ, ly.gW, Bi, ly.K, H, true, c.buf(w.skp_in), s, false));
+    c.job(c.buf(w.skp_in), ly.gW, skinny_in_chunks(Bi), ly.K * H, 0, ly.K);
+  } else {
+    PL_TRY(gemm_tn_reduced(DZ, H, a_in, ly.K, ly.gW, H, ly.K, Bi, slabs, s));
+  }
+  if (l == 0 && c.dx) {
+    GemmArgs g = {};
+    g.A = DZ; g.B = ly.W; g.C = c.dx; g.M = Bi; g.N = d->in_dim; g.K = H; g.lda = H; g.ldb = d->in_dim;
+    g.ldc = d->in_dim; g.split_k = 1;
+    PL_TRY(launch_gemm_f32(kNN, g, s));
+  }
+  return PL_OK;
+}
+
+}  // namespace
+}  // namespace pl
+
 // Backward over the output layer (if do_output) and hidden layers l_hi .. l_lo (descending).
 // The gradient flowing between two calls lives in the workspace (GA/GB), so the pass can be cut
 // at any layer boundary: the data-parallel driver all-reduces the first half's gradients while
@@ -749,217 +1018,32 @@ static int bwd_impl(const PLDesc* d, const float* x, const float* dy, int64_t B,
   const Ws w = plan(d, B);
   PL_TRY(check_ws(w, ws, ws_bytes));
   const ParamLayout P = param_layout(d);
-  hipStream_t s = (hipStream_t)stream;
-  const int H = d->hidden, O = d->out_dim, Bi = (int)B;
-  const float kscale = (!eval_bn && d->p_dropout > 0.f && d->p_dropout < 1.f) ? 1.0f / (1.0f - d->p_dropout) : 1.0f;
-  float* slabs = f32(ws, w.slabs);
-  float* GA = f32(ws, w.ga);
-  float* GB = f32(ws, w.gb);
-  float* DZ = f32(ws, w.dz);
-  const int64_t BH = B * H;
-  const int n_amax = ((H + 255) / 256) * w.RC;
-  // bias gradients = column sums of partials; all of them are reduced by ONE launch at the end
-  std::vector<const float*> jpart; std::vector<float*> jout; std::vector<int> jR, jH, jkind, jtrans;
-  auto job = [&](const float* part, float* out, int R, int Hj, int kind, int transK) {
-    jpart.push_back(part); jout.push_back(out); jR.push_back(R); jH.push_back(Hj); jkind.push_back(kind); jtrans.push_back(transK);
-  };
-
-  // small batches (small_layer.hip): what describes a layer's BatchNorm -- and its bitmap's format
-  const bool small = !eval_bn && w.bn_small, sl = !eval_bn && w.small_layer;
-  auto bn_layer = [&](int l) {
-    const Layer y = layer_of(d, P, grads, l);
-    SmallBnLayer b = {f32(ws, w.z[l]), f32(ws, w.mean[l]), f32(ws, w.rstd[l]), y.gamma, u64(ws, w.bits[l]),
-                      w.layer[l].stats != Stats::InLayer, y.ggamma, y.gbeta, y.gb};
-    return b;
-  };
-  // the output layer and the BatchNorm backward of the top hidden layer in one launch (dz of that layer: DZ)
-  const int n_loss_part = loss_partials > 0 ? loss_partials : mse_partials(B * O);   // partial sums of the loss in w.mse
-  const bool top_fused = do_output && !eval_bn && w.top_fused && l_hi == w.L - 1 && l_hi >= l_lo;
-  // the AdamW step carried by the backward launches (pl_lifter_train_step): which slice of the arena rides with layer l
-  const bool adam_rides = adam && top_fused && l_lo == 0 && w.adam_rides;
-  auto ride = [&](int64_t lo, int64_t hi) {
-    AdamWRide r = {};
-    r.p = const_cast<float*>(d->params) + lo; r.g = grads + lo; r.m = adam->m + lo; r.v = adam->v + lo; r.n = hi - lo;
-    r.lr = adam->lr; r.beta1 = adam->beta1; r.beta2 = adam->beta2; r.eps = adam->eps; r.wd = adam->weight_decay; r.gscale = 1.0f;
-    r.t = adam->t; r.lr_dev = adam->lr_dev; r.t_dev = adam->t_dev;
-    return r;
-  };
-  if (top_fused) {
-    PL_TRY(launch_small_top_bwd(dy, d->params + P.off[4 * w.L], f32(ws, w.act[w.L - 1]), Bi, H, O, GA, grads + P.off[4 * w.L],
-                                grads + P.off[4 * w.L + 1], bn_layer(w.L - 1), kscale, DZ, s, f32(ws, w.mse),
-                                n_loss_part, 1.0f / (float)(B * O), loss_out, const_cast<uint64_t*>(d->step_dev)));
-  } else if (do_output && w.out_skinny) {
-    // final Linear (LinearModel.w2): dW = dy^T h, db = sum dy, g = dy W
-    // dW5 partials, and -- the kernel holds every row of dy in its A fragments -- the bias gradient's partial column sums
-    // (Round 3 tried this launch on a side stream -- nothing reads its output before the closing reduce, and it and the head of
-    //  the chain below are both latency-bound -- forked and joined with events: 0.627 -> 0.660 ms per step eager, 0.644 -> 0.663
-    //  replayed from a graph, same box: the two cross-stream dependencies cost more than the 13 us launch they hide.)
-    PL_TRY(launch_skinny_wide_in(dy, f32(ws, w.act[w.L - 1]), grads + P.off[4 * w.L], Bi, O, H, false, f32(ws, w.skp_out), s,
-                                 false, f32(ws, w.outpart)));
-    job(f32(ws, w.skp_out), grads + P.off[4 * w.L], skinny_in_chunks(Bi), O * H, 0, 0);
-    job(f32(ws, w.outpart), grads + P.off[4 * w.L + 1], skinny_in_chunks(Bi), O, 0, 0);
-    GemmArgs be = {};
-    const int lt = w.L - 1;
-    if (!eval_bn && w.layer[lt].bnr_fused) {      // pass 1 of the top hidden layer, on the block just produced
-      const BnrSlab sl = bnr_slab(d, w, ws, Bi / 64, (w.pkind == 2 && lt > 0) ? (Bi / 64) * (H / 32) : 0, eval_bn);
-      be.bnr_z = f32(ws, w.z[lt]); be.bnr_bits = u64(ws, w.bits[lt]);
-      be.bnr_mean = f32(ws, w.mean[lt]); be.bnr_rstd = f32(ws, w.rstd[lt]); be.bnr_kscale = kscale;
-      be.bnr_part_dy = sl.mine; be.bnr_part_dyz = sl.mine + (size_t)(Bi / 64) * H;
-      be.bnr_amax = (w.pkind == 2 && lt > 0) ? sl.amax_mine : nullptr;
-    }
-    PL_TRY(launch_skinny_wide_out(dy, d->params + P.off[4 * w.L], nullptr, GA, Bi, O, H, true, nullptr, nullptr, s, &be));
-  } else if (do_output) {
-    PL_TRY(gemm_tn_reduced(dy, O, f32(ws, w.act[w.L - 1]), H, grads + P.off[4 * w.L], O, H, Bi, slabs, s));
-    PL_TRY(launch_colsum_partial(dy, Bi, O, f32(ws, w.outpart), s));
-    job(f32(ws, w.outpart), grads + P.off[4 * w.L + 1], colsum_chunks(Bi), O, 0, 0);
-    GemmArgs g = {};
-    g.A = dy; g.B = d->params + P.off[4 * w.L]; g.C = GA; g.M = Bi; g.N = H; g.K = O; g.lda = O; g.ldb = H; g.ldc = H;
-    g.split_k = 1;
-    PL_TRY(launch_gemm_f32(kNN, g, s));
-  }
-
+  BwdCtx c = {d, w, P, ws, (hipStream_t)stream, x, dy, dx, grads, (int)B, d->hidden, d->out_dim, l_hi, l_lo};
+  c.kscale = eval_bn ? 1.0f : dropout_key(d->p_dropout, 0, 0, 0, nullptr, nullptr).kscale;
+  c.eval_bn = eval_bn;
+  c.small = !eval_bn && w.bn_small;
+  c.sl = !eval_bn && w.small_layer;
+  c.top_fused = do_output && !eval_bn && w.top_fused && l_hi == w.L - 1 && l_hi >= l_lo;
+  c.loss_out = loss_out;
+  c.n_loss_part = loss_partials > 0 ? loss_partials : mse_partials(B * c.O);   // partial sums of the loss in w.mse
+  c.adam = adam;
+  c.adam_rides = adam && c.top_fused && l_lo == 0 && w.adam_rides;
+  if (do_output) PL_TRY(bwd_output(c));
   for (int l = l_hi; l >= l_lo; --l) {
-    const Layer ly = layer_of(d, P, grads, l);
-    const LayerRoute& r = w.layer[l];
-    // gradient w.r.t. this layer's activation: GA for layer 0 and even layers, GB for odd ones
-    const float* gin = (l % 2 == 1) ? GB : GA;
-    const uint64_t* bits = u64(ws, w.bits[l]);
-    const float* z = f32(ws, w.z[l]);
-    const bool pl_layer = r.bwd == Bwd::PlanesPair;       // this layer's dz feeds the planes GEMM pair
-    float* dzs = (pl_layer && w.pkind == 2) ? f32(ws, w.dzscale) + 2 * l : nullptr;   // fp16 planes of dz are range-scaled
-    PlaneOut dzo = {nullptr, nullptr, 1.0f, dzs, 0};
-    if (pl_layer) { dzo.h = u16(ws, w.dzp); dzo.l = dzo.h + BH; dzo.kind = w.pkind; }
-    // small batches, layer kernels (small_layer.hip): the dX launch of layer l + 1 already ran this layer's BatchNorm backward
-    // (dz_l sits in dzbuf(l)) unless this layer heads the range
-    auto dzbuf = [&](int layer) { return (sl && (layer & 1)) ? GB : DZ; };   // (alternating: a launch reads dz_l and writes dz_{l-1})
-    float* DZl = dzbuf(l);
-    if (sl && (l < l_hi || top_fused)) {
-      // (nothing: done by launch_small_layer_bwd of layer l + 1 / by launch_small_top_bwd)
-    } else if (small) {
-      // pass 1, the coefficients, dz, the bias gradient and dgamma / dbeta of this layer in one launch (small batches)
-      PL_TRY(launch_bn_small_bwd(gin, bits, z, f32(ws, w.mean[l]), f32(ws, w.rstd[l]), ly.gamma, kscale, Bi, H, DZl, ly.ggamma,
-                                 ly.gbeta, ly.gb, s, r.stats == Stats::InLayer));
-    } else if (d->bn) {
-      // pass 1 (column sums of dy and dy*zhat): a streaming kernel of its own, or -- round 2 -- already done by the
-      // LDS-staged epilogue of the planes GEMM that produced `gin` (round 1 tried it in the dword-per-lane epilogue of
-      // the fp32-operand GEMM: +17 us per GEMM for the 7.5 us kernel it removed)
-      const bool fr = !eval_bn && r.bnr_fused;
-      const int rc_l = fr ? Bi / 64 : w.RC;
-      const int n_amax_l = fr ? (Bi / 64) * (l == w.L - 1 ? H / 32 : H / 64) : n_amax;   // (top layer: skinny epilogue, 32-column strips)
-      const BnrSlab sl = bnr_slab(d, w, ws, rc_l, dzs ? n_amax_l : 0, eval_bn);
-      float* stat = f32(ws, w.stat);
-      if (!fr)
-        PL_TRY(launch_bn_bwd_reduce(gin, bits, z, f32(ws, w.mean[l]), f32(ws, w.rstd[l]), kscale, Bi, H,
-                                    sl.mine, sl.mine + (size_t)rc_l * H, s, 0, dzs ? sl.amax_mine : nullptr, rc_l));
-      // (fused: the partials were written by the GEMM / skinny epilogue that produced `gin`, into this rank's slab)
-      if (!eval_bn) PL_TRY(sync_gather(d, stat, sl.floats_per_rank, s));
-      PL_TRY(launch_bn_bwd_finalize(stat, rc_l, eval_bn ? 1 : sync_world(d), eval_bn ? 0 : sync_rank(d), Bi, H, ly.gamma,
-                                    f32(ws, w.rstd[l]), f32(ws, w.coef), ly.ggamma, ly.gbeta, s,
-                                    dzs ? sl.amax0 : nullptr, n_amax_l, dzs, eval_bn ? 1 : 0, sl.floats_per_rank, sl.world));
-    } else {
-      PL_TRY(launch_fill(ly.ggamma, H, 0.f, s));
-      PL_TRY(launch_fill(ly.gbeta, H, 0.f, s));
-    }
-    if (!small) {
-      PL_TRY(launch_bn_bwd_dz(gin, bits, z, f32(ws, w.mean[l]), f32(ws, w.rstd[l]), f32(ws, w.coef), kscale,
-                              d->bn, Bi, H, pl_layer ? nullptr : DZ, f32(ws, w.dbpart[l]), s, 0, &dzo, w.RC));
-      job(f32(ws, w.dbpart[l]), ly.gb, w.RC, H, 0, 0);
-    }
-    const float* a_in = l == 0 ? x : (w.planes ? nullptr : f32(ws, w.act[l - 1]));
-    if (pl_layer) {
-      // dX = dz W (NN) and dW = dz^T a (TN, split-K slabs) on the planes: one launch
-      const int splits = tn_splits(H, H, Bi);
-      PlanesGemmArgs nn = planes_args(w.pkind, u16(ws, w.dzp), BH, H, wplane(d, w, ws, l), (int64_t)H * H, H,
-                                      (l % 2 == 1) ? GA : GB, Bi, H, H, 1.0f / kWeightPlaneScale, dzs ? dzs + 1 : nullptr);
-      if (l % 2 == 1) nn.e.addend = GA;
-      if (!eval_bn && w.layer[l - 1].bnr_fused) {      // pass 1 of the layer below, on the block just produced
-        const bool lower_scaled = w.pkind == 2 && l - 1 > 0;       // its dz planes (fp16) want the range maxima too
-        const BnrSlab sl = bnr_slab(d, w, ws, Bi / 64, lower_scaled ? (Bi / 64) * (H / 64) : 0, eval_bn);
-        nn.e.bnr_z = f32(ws, w.z[l - 1]);
-        nn.e.bnr_bits = u64(ws, w.bits[l - 1]);
-        nn.e.bnr_mean = f32(ws, w.mean[l - 1]);
-        nn.e.bnr_rstd = f32(ws, w.rstd[l - 1]);
-        nn.e.bnr_kscale = kscale;
-        nn.e.bnr_part_dy = sl.mine;
-        nn.e.bnr_part_dyz = sl.mine + (size_t)(Bi / 64) * H;
-        nn.e.bnr_amax = lower_scaled ? sl.amax_mine : nullptr;
-      }
-      float* wsl = f32(ws, w.wslab[l]);                // this layer's own slabs: combined by the range's one reduce launch
-      PlanesGemmArgs tn = planes_args(w.pkind, u16(ws, w.dzp), BH, H, u16(ws, w.actp[l - 1]), BH, H,
-                                      splits > 1 ? wsl : ly.gW, H, H, Bi, 1.0f / kActPlaneScale, dzs ? dzs + 1 : nullptr);
-      tn.e.split_k = splits;
-      PL_TRY(launch_gemm_planes_pair(nn, tn, s));
-      if (splits > 1) job(wsl, ly.gW, splits, H * H, 1, 0);
-    } else if (l > 0) {
-      // off the planes path: dX = dz W (+ the skip gradient a residual block's first Linear receives in GA, added in the
-      // epilogue) and dW = dz^T a_in
-      GemmArgs g = {};
-      g.A = DZl; g.B = ly.W; g.M = Bi; g.N = H; g.K = H; g.lda = H; g.ldb = H; g.ldc = H; g.split_k = 1;
-      if (l % 2 == 1) { g.C = GA; g.addend = GA; } else { g.C = GB; }
-      g.arith = arith_of(d);
-      g.thin_scratch = slabs; g.thin_scratch_floats = w.slab_floats;   // (the pair runs as two launches off the tile grid)
-      GemmArgs t = {};
-      t.arith = g.arith;
-      t.A = DZl; t.B = a_in; t.M = H; t.N = H; t.K = Bi; t.lda = H; t.ldb = H; t.ldc = H; t.split_k = 1; t.C = ly.gW;
-      if (sl && (r.bwd == Bwd::SmallLayer || r.bwd == Bwd::SmallLayerDw)) {
-        // small batches: dX and the BatchNorm backward of the layer below in one launch when that layer belongs to this
-        // range; the weight gradient is one whole-K launch (K = B <= 64) or extra workgroups of the same launch
-        const bool dw_rides = r.bwd == Bwd::SmallLayerDw;
-        if (l - 1 >= l_lo) {
-          const bool w1 = l == 1 && w.layer[0].bwd == Bwd::InAbove;
-          // AdamW on this launch's spare workgroups: this layer's bias and BatchNorm parameters (their gradients came with the
-          // launch before) and everything above them up to where the launch before started -- the weight matrix of layer
-          // l + 1 (its gradient, too), or the output layer behind the top hidden layer
-          AdamWRide ar = {};
-          if (adam_rides) ar = ride(P.off[4 * l + 1], l == w.L - 1 ? P.total : P.off[4 * (l + 1) + 1]);
-          PL_TRY(launch_small_layer_bwd(DZl, ly.W, (l % 2 == 1) ? GA : nullptr, (l % 2 == 1) ? GA : nullptr, Bi, H, H,
-                                        bn_layer(l - 1), kscale, dzbuf(l - 1), s, dw_rides ? a_in : nullptr,
-                                        dw_rides ? ly.gW : nullptr, w1 ? x : nullptr, w1 ? grads + P.off[0] : nullptr, d->in_dim,
-                                        adam_rides ? &ar : nullptr));
-          if (dw_rides) continue;
-        } else {
-          PL_TRY(launch_gemm_f32(kNN, g, s));
-        }
-        PL_TRY(launch_gemm_f32(kTN, t, s));
-        continue;
-      }
-      // dX and dW share dz and are independent: ONE launch.
-      // (Tried: dW on a side stream so that the next layer's BatchNorm-backward kernels overlap it --
-      //  -2 % per step only: two single-GEMM workgroups do not fit one CU together, so dX and dW
-      //  time-slice the CUs and the dual launch's co-residency is lost.  Same-box A/B, tools/ab_env.py.)
-      const int splits = tn_splits(H, H, Bi);
-      t.split_k = splits; t.C = splits > 1 ? slabs : ly.gW;
-      PL_TRY(launch_gemm_f32_pair(g, t, s));
-      if (splits > 1) PL_TRY(launch_reduce_slabs(slabs, splits, (int64_t)H * H, ly.gW, s));
-    } else if (r.bwd == Bwd::InAbove && sl && l_hi > 0) {
-      // (layer 0's weight gradient came with its BatchNorm backward, small_layer.hip)
-    } else if (r.lin == Lin::Skinny) {
-      PL_TRY(launch_skinny_wide_in(a_in, DZ, ly.gW, Bi, ly.K, H, true, f32(ws, w.skp_in), s, false));
-      job(f32(ws, w.skp_in), ly.gW, skinny_in_chunks(Bi), ly.K * H, 0, ly.K);
-    } else {
-      PL_TRY(gemm_tn_reduced(DZ, H, a_in, ly.K, ly.gW, H, ly.K, Bi, slabs, s));
-    }
-    if (l == 0 && dx) {
-      GemmArgs g = {};
-      g.A = DZ; g.B = ly.W; g.C = dx; g.M = Bi; g.N = d->in_dim; g.K = H; g.lda = H; g.ldb = d->in_dim;
-      g.ldc = d->in_dim; g.split_k = 1;
-      PL_TRY(launch_gemm_f32(kNN, g, s));
-    }
+    PL_TRY(bwd_layer_bn(c, l));
+    PL_TRY(bwd_layer_linear(c, l));
   }
   float inv_n = 0.f;
   uint64_t* tick = nullptr;
-  if (loss_out && !top_fused) {
-    const int64_t n = B * O;
-    job(f32(ws, w.mse), loss_out, n_loss_part, 1, 2, 0);
-    inv_n = 1.0f / (float)n;
+  if (loss_out && !c.top_fused) {
+    c.job(f32(ws, w.mse), loss_out, c.n_loss_part, 1, 2, 0);
+    inv_n = 1.0f / (float)(B * c.O);
     tick = const_cast<uint64_t*>(d->step_dev);
   }
-  if (!jpart.empty())
-    PL_TRY(launch_reduce_rows_multi(jpart.data(), jR.data(), jH.data(), jout.data(), (int)jpart.size(), s, jkind.data(),
-                                    jtrans.data(), inv_n, tick));
+  if (!c.jobs.empty()) PL_TRY(launch_reduce_rows_multi(c.jobs.data(), (int)c.jobs.size(), inv_n, tick, c.s));
   if (adam) {
     // what no backward launch carried: the bottom of the arena (first layer and the first residual Linear) -- or all of it
-    const int64_t n = adam_rides ? (w.L > 1 ? P.off[4 * 1 + 1] : P.total) : P.total;
+    const int64_t n = c.adam_rides ? (w.L > 1 ? P.off[4 * 1 + 1] : P.total) : P.total;
     float* p = const_cast<float*>(d->params);
     if (adam->lr_dev)
       PL_TRY(pl_adamw_flat_dev(p, grads, adam->m, adam->v, n, adam->lr_dev, adam->beta1, adam->beta2, adam->eps,
@@ -1322,9 +1406,12 @@ static int train_fwd_bwd_impl(const PLDesc* d, const float* x, const float* targ
     const int H = d->hidden, O = d->out_dim;
     PL_TRY(fwd_saved_impl(d, x, y, B, ws, ws_bytes, seed, step, nullptr, stream, false, true));
     const float* bias = d->params + param_layout(d).off[4 * L + 1];
-    if (w.loss == Loss::SmallMse)
-      PL_TRY(launch_small_mse(f32(ws, w.slabs), H / 16, (int)B, O, bias, target, 1.0f, y, dy, f32(ws, w.mse), (hipStream_t)stream));
-    else
+    if (w.loss == Loss::SmallMse) {
+      SmallHeadArgs h = {};
+      h.ypart = f32(ws, w.slabs); h.NS = H / 16; h.B = (int)B; h.O = O; h.bias = bias; h.y = y;
+      h.tgt = target; h.grad_scale = 1.0f; h.dpred = dy; h.mpart = f32(ws, w.mse);
+      PL_TRY(launch_small_mse(h, (hipStream_t)stream));
+    } else
       PL_TRY(mse_partial_from_slabs(f32(ws, w.slabs), skinny_narrow_out_splits((int)B, H), (int)B, O, bias, target, 1.0f, y, dy,
                                     f32(ws, w.mse), stream));
   }

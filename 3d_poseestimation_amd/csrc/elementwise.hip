@@ -15,6 +15,8 @@
 #include "philox.h"
 #include <stdlib.h>
 
+#include <algorithm>
+
 #include "pl_internal.h"
 #include "plane_store.h"
 
@@ -416,12 +418,14 @@ __device__ __forceinline__ void bn_apply_rows(
   }
 }
 
-// The statistics finalize inside the apply launch (BnFin::stat != NULL; local statistics, at most 4 groups = 256 rows):
-// every workgroup re-derives mean / rstd / scale / shift of its four columns per lane from the partials -- with <= 16 groups
-// bn_finalize_kernel's part p holds group p alone, so its result is the sum over the groups in order, which is what is done
-// here, bit for bit -- and the workgroups with blockIdx.y == 0 write mean, rstd and the running statistics.  At B = 4096 (64
-// groups, 128 KB of partials per workgroup) this cost more than the launch it removes (round 2); at 128 ... 512 rows the
-// prologue is 2 ... 8 float4 pairs per lane and the 4.9 us finalize launch is a twentieth of the step.
+// The statistics finalize inside the apply launch (BnFin::stat != NULL; local statistics, at most 16 groups -- BnApplyArgs::fin
+// in pl_internal.h says what is routed here): every workgroup re-derives mean / rstd / scale / shift of its four columns per
+// lane from the partials -- with <= 16 groups bn_finalize_kernel's part p holds group p alone, so its result is the sum over
+// the groups in order, which is what is done here, bit for bit -- and the workgroups with blockIdx.y == 0 write mean, rstd and
+// the running statistics.  At B = 4096 (64 groups, 128 KB of partials per workgroup) this cost more than the launch it
+// removes (round 2); at 128 ... 256 rows the prologue is 2 ... 4 float4 pairs per lane and the 4.9 us finalize launch is a
+// twentieth of the step.
+// (the kernel's own copy of BnFinalizeArgs: only what it reads, so that the kernel's argument block stays as small as it was)
 struct BnFin {
   const float* stat;            // [2][G][H]
   const float *gamma, *beta;
@@ -438,12 +442,7 @@ __global__ __launch_bounds__(NTHR) void bn_apply_kernel(
     const uint64_t* __restrict__ inject, int Hc, PlaneOut po, const uint64_t* __restrict__ step_dev,
     uint32_t seed_hi, BnFin fin) {
   const PlaneDst pd = plane_dst(po);
-  if (step_dev) {
-    // graph replay: the step number is base (baked into c3 / k1's slot as the low / high word) + the device counter
-    const uint64_t step = (((uint64_t)k1 << 32) | c3) + step_dev[0];
-    c3 = (uint32_t)step;
-    k1 = seed_hi ^ (uint32_t)(step >> 32);
-  }
+  dropout_replay_step(c3, k1, seed_hi, step_dev);
   // Hc: real columns behind the H virtual ones (bn_colstats_kernel); Hc == H for the lifter
   // mode: 0 keep all, 1 philox, 2 injected bitmap, 3 drop all; + 8: no ReLU (BatchNorm alone; bitmap all ones)
   const bool norelu = (mode & 8) != 0, resid_first = (mode & 32) != 0;      // + 32: the residual joins before the ReLU
@@ -539,11 +538,7 @@ __global__ __launch_bounds__(kSmallThreads) void bn_small_fwd_kernel(
     uint32_t k0, uint32_t k1, uint32_t c3, uint32_t layer, const uint64_t* __restrict__ inject,
     const uint64_t* __restrict__ step_dev, uint32_t seed_hi) {
   __shared__ float4 sm[8][64];
-  if (step_dev) {
-    const uint64_t step = (((uint64_t)k1 << 32) | c3) + step_dev[0];
-    c3 = (uint32_t)step;
-    k1 = seed_hi ^ (uint32_t)(step >> 32);
-  }
+  dropout_replay_step(c3, k1, seed_hi, step_dev);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int c = blockIdx.x * 256 + lane * 4;
   const bool active = c < H;
@@ -1455,90 +1450,71 @@ __global__ __launch_bounds__(NTHR) void bn_merge_groups_kernel(const float* __re
   out[(size_t)Gp * H + (size_t)gp * H + c] = Q;
 }
 
-int launch_bn_finalize(const float* stat, int G, int world, int B, int H,
-                       const float* gamma, const float* beta, float eps, float momentum,
-                       float* running_mean, float* running_var, int64_t* batches, float* mean,
-                       float* rstd, float* scale, float* shift, hipStream_t s, int group_rows) {
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3((H + RCOLS - 1) / RCOLS), dim3(NTHR), 0, s, stat, G, world, B,
-                     H, group_rows, gamma, beta, eps, momentum, running_mean, running_var, batches, mean, rstd,
-                     scale, shift);
+int launch_bn_finalize(const BnFinalizeArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(bn_finalize_kernel, dim3((a.H + RCOLS - 1) / RCOLS), dim3(NTHR), 0, s, a.stat, a.G, a.world, a.B,
+                     a.H, a.group_rows, a.bn.gamma, a.bn.beta, a.bn.eps, a.bn.momentum, a.bn.running_mean, a.bn.running_var,
+                     a.bn.batches, a.mean, a.rstd, a.scale, a.shift);
   PL_CHECK_LAUNCH("bn_finalize");
   return PL_OK;
 }
 
-int launch_bn_apply(const float* z, const float* scale, const float* shift, const float* resid,
-                    float* act, uint64_t* bits, int B, int H, float p, uint64_t seed, uint64_t step,
-                    int layer, const uint64_t* inject_keep, hipStream_t s, const PlaneOut* planes,
-                    const uint64_t* step_dev, const BnFinalizeArgs* finalize) {
-  int mode = 0;
-  PlaneOut po = planes ? *planes : PlaneOut{nullptr, nullptr, 1.f, nullptr, 0};
+int launch_bn_apply(const BnApplyArgs& a, hipStream_t s) {
+  const int B = a.B, H = a.H;
+  PlaneOut po = a.planes;
   po.nt = (int64_t)B * H * 4 >= kNontemporalBytes ? 1 : 0;
-  if (!act && !po.kind) PL_FAIL(PL_EINVAL, "bn_apply: nothing to write");
-  float kscale = 1.f;
-  if (p >= 1.f) mode = 3;
-  else if (p > 0.f) {
-    mode = inject_keep ? 2 : 1;
-    kscale = 1.0f / (1.0f - p);
-  }
-  const uint32_t thr = dropout_threshold(p);
-  // step_dev: the kernel forms the key itself from (step + *step_dev); it receives the step's two words instead
-  const uint32_t k0 = (uint32_t)seed, seed_hi = (uint32_t)(seed >> 32);
-  const uint32_t k1 = step_dev ? (uint32_t)(step >> 32) : seed_hi ^ (uint32_t)(step >> 32);
+  if (!a.act && !po.kind) PL_FAIL(PL_EINVAL, "bn_apply: nothing to write");
+  // the kernel's mode word: the dropout mode (0 .. 3) + 8: no ReLU + 32: the residual joins before the ReLU
+  const int mode = a.drop.mode | (a.no_relu ? 8 : 0) | (a.resid_before_relu ? 32 : 0);
   const int strips = (H + 255) / 256;
   dim3 grid(strips, stream_rows_grid(B, strips));
   BnFin fin = {};
-  if (finalize) {
-    const BnFinalizeArgs& f = *finalize;
-    if (!f.stat || !f.gamma || !f.beta || !f.mean || !f.rstd || f.G < 1 || f.G > 16 || (H & 3) ||
-        (f.running_mean != nullptr) != (f.running_var != nullptr))
+  if (a.fin.stat) {
+    const BnFinalizeArgs& f = a.fin;
+    if (!f.bn.gamma || !f.bn.beta || !f.mean || !f.rstd || f.G < 1 || f.G > 16 || (H & 3) ||
+        (f.bn.running_mean != nullptr) != (f.bn.running_var != nullptr))
       PL_FAIL(PL_EINVAL, "bn_apply: statistics finalize (G=%d)", f.G);
-    fin.stat = f.stat; fin.gamma = f.gamma; fin.beta = f.beta; fin.running_mean = f.running_mean; fin.running_var = f.running_var;
-    fin.mean_out = f.mean; fin.rstd_out = f.rstd; fin.batches = f.batches; fin.eps = f.eps; fin.momentum = f.momentum;
-    fin.G = f.G; fin.Br = B; fin.gs = f.group_rows;
+    fin = BnFin{f.stat, f.bn.gamma, f.bn.beta, f.bn.running_mean, f.bn.running_var, f.mean, f.rstd, f.bn.batches, f.bn.eps,
+                f.bn.momentum, f.G, B, f.group_rows};
   }
-  hipLaunchKernelGGL(bn_apply_kernel, grid, dim3(NTHR), 0, s, z, scale, shift, resid, act, bits, B, H,
-                     mode, thr, kscale, k0, k1, (uint32_t)step, (uint32_t)layer, inject_keep, H, po, step_dev, seed_hi, fin);
+  const DropKey& k = a.drop;
+  hipLaunchKernelGGL(bn_apply_kernel, grid, dim3(NTHR), 0, s, a.z, a.scale, a.shift, a.resid, a.act, a.bits, B, H,
+                     mode, k.thr, k.kscale, k.k0, k.k1, k.c3, k.layer, k.inject, a.Hc > 0 ? a.Hc : H, po, k.step_dev, k.seed_hi,
+                     fin);
   PL_CHECK_LAUNCH("bn_apply");
   return PL_OK;
 }
 
-int launch_bn_small_fwd(const float* z, const float* gamma, const float* beta, float eps, float momentum, float* rm, float* rv,
-                        int64_t* nbt, float* mean, float* rstd, const float* resid, float* act, uint64_t* bits, int B, int H,
-                        float p, uint64_t seed, uint64_t step, int layer, const uint64_t* inject_keep, hipStream_t s,
-                        const uint64_t* step_dev) {
-  if (!z || !act || !bits || !mean || !rstd || B < 2 || (H & 3)) PL_FAIL(PL_EINVAL, "bn_small_fwd: bad arguments");
-  int mode = 0;
-  float kscale = 1.f;
-  if (p >= 1.f) mode = 3;
-  else if (p > 0.f) { mode = inject_keep ? 2 : 1; kscale = 1.0f / (1.0f - p); }
-  const uint32_t thr = dropout_threshold(p);
-  const uint32_t k0 = (uint32_t)seed, seed_hi = (uint32_t)(seed >> 32);
-  const uint32_t k1 = step_dev ? (uint32_t)(step >> 32) : seed_hi ^ (uint32_t)(step >> 32);
+int launch_bn_small_fwd(const BnSmallFwdArgs& a, hipStream_t s) {
+  const int B = a.B, H = a.H;
+  if (!a.saved.z || !a.act || !a.saved.bits || !a.saved.mean || !a.saved.rstd || B < 2 || (H & 3))
+    PL_FAIL(PL_EINVAL, "bn_small_fwd: bad arguments");
   if (B > kBnSmallRows) PL_FAIL(PL_ESHAPE, "bn_small_fwd: B=%d", B);
   const dim3 grid((H + 255) / 256), block(kSmallThreads);
-#define PL_SMALL_FWD(RU, RES)                                                                                               \
-  hipLaunchKernelGGL((bn_small_fwd_kernel<RU, RES>), grid, block, 0, s, z, gamma, beta, eps, momentum, rm, rv, nbt, mean, rstd,   \
-                     resid, act, bits, B, H, mode, thr, kscale, k0, k1, (uint32_t)step, (uint32_t)layer, inject_keep, step_dev, \
-                     seed_hi)
-  if (resid) PL_SMALL_FWD(8, true); else PL_SMALL_FWD(8, false);
+  const DropKey& k = a.drop;
+#define PL_SMALL_FWD(RU, RES)                                                                                              \
+  hipLaunchKernelGGL((bn_small_fwd_kernel<RU, RES>), grid, block, 0, s, a.saved.z, a.bn.gamma, a.bn.beta, a.bn.eps,        \
+                     a.bn.momentum, a.bn.running_mean, a.bn.running_var, a.bn.batches, a.saved.mean, a.saved.rstd, a.resid, \
+                     a.act, a.saved.bits, B, H, k.mode, k.thr, k.kscale, k.k0, k.k1, k.c3, k.layer, k.inject, k.step_dev,   \
+                     k.seed_hi)
+  if (a.resid) PL_SMALL_FWD(8, true); else PL_SMALL_FWD(8, false);
 #undef PL_SMALL_FWD
   PL_CHECK_LAUNCH("bn_small_fwd");
   return PL_OK;
 }
 
-int launch_bn_small_bwd(const float* g, const uint64_t* bits, const float* z, const float* mean, const float* rstd,
-                        const float* gamma, float keep_scale, int B, int H, float* dz, float* dgamma, float* dbeta, float* dbias,
-                        hipStream_t s, bool tile_bits) {
-  if (!g || !bits || !z || !dz || !dgamma || !dbeta || !dbias || B < 1 || (H & 3)) PL_FAIL(PL_EINVAL, "bn_small_bwd: bad arguments");
+int launch_bn_small_bwd(const BnSmallBwdArgs& a, hipStream_t s) {
+  const SmallBnLayer& l = a.layer;
+  const int B = a.B, H = a.H;
+  if (!a.g || !l.saved.bits || !l.saved.z || !a.dz || !l.dgamma || !l.dbeta || !l.dbias || B < 1 || (H & 3))
+    PL_FAIL(PL_EINVAL, "bn_small_bwd: bad arguments");
   if (B > kBnSmallRows) PL_FAIL(PL_ESHAPE, "bn_small_bwd: B=%d", B);
   const dim3 grid((H + 255) / 256), block(kSmallThreads);
-  if (tile_bits && (H & 255)) PL_FAIL(PL_ESHAPE, "bn_small_bwd: tile-format bitmap with H=%d", H);
-  if (tile_bits)
-    hipLaunchKernelGGL((bn_small_bwd_kernel<8, true>), grid, block, 0, s, g, bits, z, mean, rstd, gamma, keep_scale, B, H, dz,
-                       dgamma, dbeta, dbias);
-  else
-    hipLaunchKernelGGL((bn_small_bwd_kernel<8, false>), grid, block, 0, s, g, bits, z, mean, rstd, gamma, keep_scale, B, H, dz,
-                       dgamma, dbeta, dbias);
+  if (l.saved.tile_bits && (H & 255)) PL_FAIL(PL_ESHAPE, "bn_small_bwd: tile-format bitmap with H=%d", H);
+#define PL_SMALL_BWD(TILE)                                                                                              \
+  hipLaunchKernelGGL((bn_small_bwd_kernel<8, TILE>), grid, block, 0, s, a.g, l.saved.bits, l.saved.z, l.saved.mean,     \
+                     l.saved.rstd, l.gamma, a.keep_scale, B, H, a.dz, l.dgamma, l.dbeta, l.dbias)
+  if (l.saved.tile_bits) PL_SMALL_BWD(true); else PL_SMALL_BWD(false);
+#undef PL_SMALL_BWD
   PL_CHECK_LAUNCH("bn_small_bwd");
   return PL_OK;
 }
@@ -1556,37 +1532,29 @@ int bwd_row_chunks(int B, int H) {
   return rc < 1 ? 1 : rc;
 }
 
-int launch_bn_bwd_reduce(const float* g, const uint64_t* bits, const float* z, const float* mean,
-                         const float* rstd, float keep_scale, int B, int H, float* part_dy,
-                         float* part_dyz, hipStream_t s, int Hc, float* part_amax, int rc, const float* join_g2,
-                         float* join_dx) {
-  dim3 grid((H + 255) / 256, rc > 0 ? rc : bwd_row_chunks(B, H));
-  hipLaunchKernelGGL(bn_bwd_reduce_kernel, grid, dim3(NTHR), 0, s, g, bits, z, mean, rstd, keep_scale, B,
-                     H, part_dy, part_dyz, Hc > 0 ? Hc : H, part_amax, join_g2, join_dx);
+int launch_bn_bwd_reduce(const BnBwdReduceArgs& a, hipStream_t s) {
+  dim3 grid((a.H + 255) / 256, a.rc > 0 ? a.rc : bwd_row_chunks(a.B, a.H));
+  hipLaunchKernelGGL(bn_bwd_reduce_kernel, grid, dim3(NTHR), 0, s, a.g, a.saved.bits, a.saved.z, a.saved.mean, a.saved.rstd,
+                     a.keep_scale, a.B, a.H, a.part_dy, a.part_dyz, a.Hc > 0 ? a.Hc : a.H, a.part_amax, a.join_g2, a.join_dx);
   PL_CHECK_LAUNCH("bn_bwd_reduce");
   return PL_OK;
 }
 
-int launch_bn_bwd_finalize(const float* part, int RC, int world, int rank, int B, int H,
-                           const float* gamma, const float* rstd, float* coef, float* dgamma,
-                           float* dbeta, hipStream_t s, const float* part_amax, int n_amax, float* dz_scale,
-                           int eval_mode, int64_t rstride, int amax_world) {
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((H + RCOLS - 1) / RCOLS + (dz_scale ? 1 : 0)), dim3(NTHR), 0, s, part,
-                     RC, world, rank, B, H, gamma, rstd, coef, dgamma, dbeta, part_amax, n_amax, dz_scale, eval_mode,
-                     (long long)rstride, amax_world);
+int launch_bn_bwd_finalize(const BnBwdFinalizeArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((a.H + RCOLS - 1) / RCOLS + (a.dz_scale ? 1 : 0)), dim3(NTHR), 0, s, a.part,
+                     a.RC, a.world, a.rank, a.B, a.H, a.gamma, a.rstd, a.coef, a.dgamma, a.dbeta, a.part_amax, a.n_amax,
+                     a.dz_scale, a.eval_mode, (long long)a.rstride, a.amax_world > 0 ? a.amax_world : 1);
   PL_CHECK_LAUNCH("bn_bwd_finalize");
   return PL_OK;
 }
 
-int launch_bn_bwd_dz(const float* g, const uint64_t* bits, const float* z, const float* mean,
-                     const float* rstd, const float* coef, float keep_scale, int bn, int B, int H,
-                     float* dz, float* part_db, hipStream_t s, int Hc, const PlaneOut* planes, int rc) {
-  dim3 grid((H + 255) / 256, rc > 0 ? rc : bwd_row_chunks(B, H));
-  PlaneOut po = planes ? *planes : PlaneOut{nullptr, nullptr, 1.f, nullptr, 0};
-  po.nt = (int64_t)B * H * 4 >= kNontemporalBytes ? 1 : 0;
-  if (!dz && !po.kind) PL_FAIL(PL_EINVAL, "bn_bwd_dz: nothing to write");
-  hipLaunchKernelGGL(bn_bwd_dz_kernel, grid, dim3(NTHR), 0, s, g, bits, z, mean, rstd, coef, keep_scale,
-                     bn, B, H, dz, part_db, Hc > 0 ? Hc : H, po);
+int launch_bn_bwd_dz(const BnBwdDzArgs& a, hipStream_t s) {
+  dim3 grid((a.H + 255) / 256, a.rc > 0 ? a.rc : bwd_row_chunks(a.B, a.H));
+  PlaneOut po = a.planes;
+  po.nt = (int64_t)a.B * a.H * 4 >= kNontemporalBytes ? 1 : 0;
+  if (!a.dz && !po.kind) PL_FAIL(PL_EINVAL, "bn_bwd_dz: nothing to write");
+  hipLaunchKernelGGL(bn_bwd_dz_kernel, grid, dim3(NTHR), 0, s, a.g, a.saved.bits, a.saved.z, a.saved.mean, a.saved.rstd, a.coef,
+                     a.keep_scale, a.bn, a.B, a.H, a.dz, a.part_db, a.Hc > 0 ? a.Hc : a.H, po);
   PL_CHECK_LAUNCH("bn_bwd_dz");
   return PL_OK;
 }
@@ -1630,26 +1598,24 @@ int launch_reduce_slabs_bias(const float* slabs, int nslab, int rows, int cols, 
   return PL_OK;
 }
 
-int launch_reduce_rows_multi(const float* const* part, const int* R, const int* H, float* const* out, int njobs,
-                             hipStream_t s, const int* kind, const int* transK, float loss_inv_n, uint64_t* loss_tick) {
+int launch_reduce_rows_multi(const RowJob* jobs, int njobs, float loss_inv_n, uint64_t* loss_tick, hipStream_t s) {
   for (int base = 0; base < njobs; base += kMaxRowJobs) {
     RowJobs j = {};
     j.inv_n = loss_inv_n; j.tick = loss_tick;
     const int n = njobs - base < kMaxRowJobs ? njobs - base : kMaxRowJobs;
     int gx = 1;
     for (int k = 0; k < n; ++k) {
-      j.part[k] = part[base + k]; j.out[k] = out[base + k]; j.R[k] = R[base + k]; j.H[k] = H[base + k];
-      j.kind[k] = kind ? kind[base + k] : 0;
-      j.transK[k] = transK ? transK[base + k] : 0;
+      const RowJob& q = jobs[base + k];
+      j.part[k] = q.part; j.out[k] = q.out; j.R[k] = q.R; j.H[k] = q.H; j.kind[k] = q.kind; j.transK[k] = q.transK;
       int need;
-      if (j.kind[k] == 1) {
-        if ((j.H[k] & 3) || !aligned16(j.part[k]) || !aligned16(j.out[k])) PL_FAIL(PL_EINVAL, "reduce_rows_multi: slab job alignment");
-        need = ((j.H[k] >> 2) + NTHR - 1) / NTHR;
+      if (q.kind == 1) {
+        if ((q.H & 3) || !aligned16(q.part) || !aligned16(q.out)) PL_FAIL(PL_EINVAL, "reduce_rows_multi: slab job alignment");
+        need = ((q.H >> 2) + NTHR - 1) / NTHR;
         if (need > 1024) need = 1024;
-      } else if (j.kind[k] == 2) {
+      } else if (q.kind == 2) {
         need = 1;
       } else {
-        need = (j.H[k] + RCOLS - 1) / RCOLS;
+        need = (q.H + RCOLS - 1) / RCOLS;
       }
       if (need > gx) gx = need;
     }
@@ -1673,19 +1639,18 @@ int launch_colsum_partial(const float* X, int rows, int cols, float* part, hipSt
   return PL_OK;
 }
 
-int launch_bn_fold_eval(const float* bias, const float* gamma, const float* beta, const float* rm,
-                        const float* rv, float eps, int bn, int H, float* scale, float* shift,
-                        hipStream_t s) {
-  hipLaunchKernelGGL(bn_fold_eval_kernel, dim3((H + NTHR - 1) / NTHR), dim3(NTHR), 0, s, bias, gamma, beta,
-                     rm, rv, eps, bn, H, scale, shift);
+int launch_bn_fold_eval(const float* bias, const BnParams* bn, int H, float* scale, float* shift, hipStream_t s) {
+  const BnParams b = bn ? *bn : BnParams{};
+  hipLaunchKernelGGL(bn_fold_eval_kernel, dim3((H + NTHR - 1) / NTHR), dim3(NTHR), 0, s, bias, b.gamma, b.beta,
+                     (const float*)b.running_mean, (const float*)b.running_var, b.eps, bn ? 1 : 0, H, scale, shift);
   PL_CHECK_LAUNCH("bn_fold_eval");
   return PL_OK;
 }
 
-int launch_bn_eval_stats(const float* gamma, const float* beta, const float* rm, const float* rv, float eps, int H,
-                         float* mean, float* rstd, float* scale, float* shift, hipStream_t s) {
-  hipLaunchKernelGGL(bn_eval_stats_kernel, dim3((H + NTHR - 1) / NTHR), dim3(NTHR), 0, s, gamma, beta, rm, rv, eps, H,
-                     mean, rstd, scale, shift);
+int launch_bn_eval_stats(const BnFinalizeArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(bn_eval_stats_kernel, dim3((a.H + NTHR - 1) / NTHR), dim3(NTHR), 0, s, a.bn.gamma, a.bn.beta,
+                     (const float*)a.bn.running_mean, (const float*)a.bn.running_var, a.bn.eps, a.H, a.mean, a.rstd, a.scale,
+                     a.shift);
   PL_CHECK_LAUNCH("bn_eval_stats");
   return PL_OK;
 }
@@ -1998,16 +1963,39 @@ static int bn_replicas(int64_t rows, int64_t C) {
   return r;
 }
 
+// The view the streaming kernels take of a [rows][C] map -- [B = rows / R][H = R C], Hc = C real columns -- and where
+// the conv-path entry points keep what in their scratch buffer (float offsets; pl_bn_train_scratch_bytes sizes it for both
+// directions).
+//   forward:  stat [2][R G][Hc] | scale [Hc] | shift [Hc]        (a GEMM's statistics merged first: [2][<= 512][Hc] | ...)
+//   backward: part [2][R RC][Hc] | coef [3][Hc] | part_db [RC R][Hc] | amax [strips RC][2] (the dz range maxima)
+struct BnScratch {
+  int R, B, H, Hc;
+  int G, gs;                     // forward: statistics groups of gs rows
+  int RC, n_amax;                // backward: row chunks; workgroups of pass 1
+  size_t scale;                  // forward: scale at this offset, shift Hc behind it
+  size_t coef, part_db, amax;    // backward
+  size_t fwd_floats, bwd_floats;
+};
+static BnScratch bn_scratch(int64_t rows, int64_t C) {
+  BnScratch q = {};
+  q.R = bn_replicas(rows, C);
+  q.B = (int)(rows / q.R); q.H = (int)C * q.R; q.Hc = (int)C;
+  q.G = bn_groups(q.B); q.gs = bn_group_rows(q.B);
+  q.RC = bwd_row_chunks(q.B, q.H);
+  q.n_amax = ((q.H + 255) / 256) * q.RC;
+  q.scale = (size_t)2 * q.R * q.G * q.Hc;
+  q.fwd_floats = std::max(q.scale, (size_t)2 * 512 * q.Hc) + 2 * (size_t)q.Hc;
+  q.coef = (size_t)2 * q.R * q.RC * q.Hc;
+  q.part_db = q.coef + 3 * (size_t)q.Hc;
+  q.amax = q.part_db + (size_t)q.RC * q.R * q.Hc;
+  q.bwd_floats = q.amax + (size_t)2 * q.n_amax + 16;
+  return q;
+}
+
 extern "C" size_t pl_bn_train_scratch_bytes(int64_t rows, int64_t C) {
   if (rows <= 0 || C <= 0) return 0;
-  const int R = bn_replicas(rows, C);
-  const int64_t rv = rows / R;                      // rows of the reshaped view
-  size_t fwd = ((size_t)2 * R * bn_groups(rv) * C + 2 * (size_t)C) * sizeof(float);
-  if (fwd < ((size_t)2 * 512 * C + 2 * (size_t)C) * sizeof(float)) fwd = ((size_t)2 * 512 * C + 2 * (size_t)C) * sizeof(float);
-  const int rc = bwd_row_chunks((int)rv, (int)C * R);
-  const size_t bwd = ((size_t)2 * R * rc * C + 3 * (size_t)C + (size_t)rc * R * C +
-                      (size_t)2 * ((C * R + 255) / 256) * rc + 16) * sizeof(float);     // ... + the dz range maxima
-  return fwd > bwd ? fwd : bwd;
+  const BnScratch q = bn_scratch(rows, C);
+  return std::max(q.fwd_floats, q.bwd_floats) * sizeof(float);
 }
 
 // operand planes of a [n]-element tensor for the planes GEMM: mode PL_F16X3 -> [2][n] fp16 (h, l), PL_BF16 -> [n] bf16
@@ -2077,45 +2065,80 @@ extern "C" int pl_bn_train_fwd_ex(const float* z, int64_t rows, int64_t C, const
   range_watch(ypo, PL_RANGE_SITE_CONV_ACT);
   if (rows < 2 || rows > INT32_MAX || C <= 0 || (C & 3)) PL_FAIL(rows < 2 ? PL_EBATCH : PL_ESHAPE, "pl_bn_train_fwd: rows=%lld C=%lld (C %% 4 == 0, rows >= 2)", (long long)rows, (long long)C);
   hipStream_t s = (hipStream_t)stream;
-  const int R = bn_replicas(rows, C);
-  const int B = (int)(rows / R), H = (int)C * R, Hc = (int)C;       // the view the streaming kernels work on
-  const int G = bn_groups(B), gs = bn_group_rows(B);
+  const BnScratch q = bn_scratch(rows, C);
   float* stat = static_cast<float*>(scratch);
-  float* scale = stat + (size_t)2 * R * G * Hc;
-  float* shift = scale + Hc;
+  BnFinalizeArgs f = {};
+  f.bn = BnParams{gamma, beta, eps, momentum, running_mean, running_var, batches};
+  f.H = q.Hc; f.mean = mean; f.rstd = rstd;
   if (gemm_stat) {
     // the convolution's GEMM epilogue already left (sum, M2) per 64-row group and column: [2][gemm_stat_groups(rows)][C]
     // -- no pass over z for the statistics; more than 512 groups are merged F at a time first
     const int G64 = gemm_stat_groups((int)rows);
-    const float* st = gemm_stat;
-    int Gf = G64, gsf = 64;
+    f.stat = gemm_stat; f.G = G64; f.group_rows = 64; f.world = 1; f.B = (int)rows;
+    f.scale = stat + q.scale;
     if (G64 > 512) {
       const int F = (G64 + 511) / 512;
-      Gf = (G64 + F - 1) / F; gsf = 64 * F;
-      float* merged = stat;                              // (scratch >= 2 * 512 * C floats: pl_bn_train_scratch_bytes)
-      scale = merged + (size_t)2 * Gf * Hc; shift = scale + Hc;
-      hipLaunchKernelGGL(bn_merge_groups_kernel, dim3((Hc + NTHR - 1) / NTHR, Gf), dim3(NTHR), 0, s, gemm_stat, G64, (int)rows,
-                         Hc, F, merged, Gf);
+      f.G = (G64 + F - 1) / F; f.group_rows = 64 * F;
+      f.stat = stat;                                     // (the merged partials: scratch >= 2 * 512 * C floats)
+      f.scale = stat + (size_t)2 * f.G * q.Hc;
+      hipLaunchKernelGGL(bn_merge_groups_kernel, dim3((q.Hc + NTHR - 1) / NTHR, f.G), dim3(NTHR), 0, s, gemm_stat, G64, (int)rows,
+                         q.Hc, F, stat, f.G);
       PL_CHECK_LAUNCH("bn_merge_groups");
-      st = merged;
     }
-    PL_TRY(launch_bn_finalize(st, Gf, 1, (int)rows, Hc, gamma, beta, eps, momentum, running_mean, running_var, batches, mean,
-                              rstd, scale, shift, s, gsf));
   } else {
-    hipLaunchKernelGGL(bn_colstats_kernel, dim3((H + 255) / 256, G), dim3(NTHR), 0, s, z, B, H, gs, Hc, stat);
+    hipLaunchKernelGGL(bn_colstats_kernel, dim3((q.H + 255) / 256, q.G), dim3(NTHR), 0, s, z, q.B, q.H, q.gs, q.Hc, stat);
     PL_CHECK_LAUNCH("bn_colstats");
-    PL_TRY(launch_bn_finalize(stat, G, R, B, Hc, gamma, beta, eps, momentum, running_mean, running_var, batches, mean, rstd,
-                              scale, shift, s, gs));
+    f.stat = stat; f.G = q.G; f.group_rows = q.gs; f.world = q.R; f.B = q.B;
+    f.scale = stat + q.scale;
   }
-  const int strips = (H + 255) / 256;
-  dim3 grid(strips, stream_rows_grid(B, strips));
+  f.shift = f.scale + q.Hc;
+  PL_TRY(launch_bn_finalize(f, s));
   // join (optional): y = relu(bn(z) + join) in this one pass -- the Bottleneck's bn3 and residual join (needs relu != 0)
   if (join && !relu) PL_FAIL(PL_EINVAL, "pl_bn_train_fwd_ex: a join without its ReLU");
-  hipLaunchKernelGGL(bn_apply_kernel, grid, dim3(NTHR), 0, s, z, scale, shift, join, y, bits, B, H,
-                     (relu ? 0 : 8) | (join ? 32 : 0), 0u, 1.0f, 0u, 0u, 0u, 0u, (const uint64_t*)nullptr, Hc, ypo,
-                     (const uint64_t*)nullptr, 0u, BnFin{});
-  PL_CHECK_LAUNCH("bn_apply");
-  return PL_OK;
+  BnApplyArgs ap = {};
+  ap.z = z; ap.scale = f.scale; ap.shift = f.shift; ap.resid = join; ap.act = y; ap.bits = bits;
+  ap.B = q.B; ap.H = q.H; ap.Hc = q.Hc;
+  ap.no_relu = !relu; ap.resid_before_relu = join != nullptr;
+  ap.drop = dropout_key(0.f, 0, 0, 0, nullptr, nullptr);
+  ap.planes = ypo;
+  return launch_bn_apply(ap, s);
+}
+
+// BatchNorm backward of a [rows][C] map in three launches -- pass 1, the finalize, dz -- on the scratch layout above.
+// join_dx != NULL (pl_bn_join_bwd): pass 1 first forms the incoming gradient, (g + join_g2) where the bitmap is set, and
+// writes it to join_dx; dz then reads it from there.
+struct ConvBnBwd {
+  const float* g;
+  const float* join_g2;
+  float* join_dx;
+  BnSaved saved;
+  const float* gamma;
+  float *dz, *dgamma, *dbeta;
+  PlaneOut planes;              // dz also / only (dz == NULL) as operand planes
+  float* dz_scale;              // fp16 planes: receives {S, 1/S} (bn_bwd_finalize_kernel)
+};
+// (BnSaved is written by a forward and read here: the C ABI hands the backward const pointers)
+static BnSaved conv_saved(const float* z, const uint64_t* bits, const float* mean, const float* rstd) {
+  return BnSaved{const_cast<float*>(z), const_cast<uint64_t*>(bits), const_cast<float*>(mean), const_cast<float*>(rstd), false};
+}
+static int conv_bn_bwd(const ConvBnBwd& a, int64_t rows, int64_t C, void* scratch, hipStream_t s) {
+  const BnScratch q = bn_scratch(rows, C);
+  float* part = static_cast<float*>(scratch);
+  float* amax = a.dz_scale ? part + q.amax : nullptr;
+  BnBwdReduceArgs r = {};
+  r.g = a.g; r.saved = a.saved; r.keep_scale = 1.0f; r.B = q.B; r.H = q.H; r.Hc = q.Hc;
+  r.part_dy = part; r.part_dyz = part + (size_t)q.RC * q.Hc; r.part_amax = amax;
+  r.join_g2 = a.join_g2; r.join_dx = a.join_dx;
+  PL_TRY(launch_bn_bwd_reduce(r, s));
+  BnBwdFinalizeArgs f = {};
+  f.part = part; f.RC = q.RC; f.world = q.R; f.rank = q.R > 1 ? -1 : 0; f.B = q.B; f.H = q.Hc;
+  f.gamma = a.gamma; f.rstd = a.saved.rstd; f.coef = part + q.coef; f.dgamma = a.dgamma; f.dbeta = a.dbeta;
+  f.part_amax = amax; f.n_amax = q.n_amax; f.dz_scale = a.dz_scale;
+  PL_TRY(launch_bn_bwd_finalize(f, s));
+  BnBwdDzArgs d = {};
+  d.g = a.join_dx ? a.join_dx : a.g; d.saved = a.saved; d.coef = f.coef; d.keep_scale = 1.0f; d.bn = 1;
+  d.B = q.B; d.H = q.H; d.Hc = q.Hc; d.dz = a.dz; d.part_db = part + q.part_db; d.planes = a.planes;
+  return launch_bn_bwd_dz(d, s);
 }
 
 extern "C" int pl_bn_train_bwd(const float* dy, const uint64_t* bits, const float* z, const float* mean, const float* rstd,
@@ -2136,20 +2159,11 @@ extern "C" int pl_bn_train_bwd_ex(const float* dy, const uint64_t* bits, const f
   if (rows < 2 || rows > INT32_MAX || C <= 0 || (C & 3)) PL_FAIL(PL_ESHAPE, "pl_bn_train_bwd: rows=%lld C=%lld", (long long)rows, (long long)C);
   const bool scaled = dz_planes && planes_mode == PL_F16X3;
   if (scaled && !dz_scale) PL_FAIL(PL_EINVAL, "pl_bn_train_bwd_ex: fp16 planes of dz need dz_scale");
-  PlaneOut po;
-  PL_TRY(plane_out_of(planes_mode, dz_planes, rows * C, 1.0f, scaled ? dz_scale : nullptr, &po, "pl_bn_train_bwd_ex"));
-  hipStream_t s = (hipStream_t)stream;
-  const int R = bn_replicas(rows, C);
-  const int B = (int)(rows / R), H = (int)C * R, Hc = (int)C, RC = bwd_row_chunks(B, H);
-  float* part = static_cast<float*>(scratch);
-  float* coef = part + (size_t)2 * R * RC * Hc;
-  float* part_db = coef + 3 * (size_t)Hc;
-  float* amax = part_db + (size_t)RC * R * Hc;                      // [strips * RC][2] (pl_bn_train_scratch_bytes)
-  const int n_amax = ((H + 255) / 256) * RC;
-  PL_TRY(launch_bn_bwd_reduce(dy, bits, z, mean, rstd, 1.0f, B, H, part, part + (size_t)RC * Hc, s, Hc, scaled ? amax : nullptr));
-  PL_TRY(launch_bn_bwd_finalize(part, RC, R, R > 1 ? -1 : 0, B, Hc, gamma, rstd, coef, dgamma, dbeta, s,
-                                scaled ? amax : nullptr, n_amax, scaled ? dz_scale : nullptr));
-  return launch_bn_bwd_dz(dy, bits, z, mean, rstd, coef, 1.0f, 1, B, H, dz, part_db, s, Hc, dz_planes ? &po : nullptr);
+  ConvBnBwd a = {};
+  PL_TRY(plane_out_of(planes_mode, dz_planes, rows * C, 1.0f, scaled ? dz_scale : nullptr, &a.planes, "pl_bn_train_bwd_ex"));
+  a.g = dy; a.saved = conv_saved(z, bits, mean, rstd); a.gamma = gamma; a.dz = dz; a.dgamma = dgamma; a.dbeta = dbeta;
+  a.dz_scale = scaled ? dz_scale : nullptr;
+  return conv_bn_bwd(a, rows, C, scratch, (hipStream_t)stream);
 }
 
 // Backward of the Bottleneck's bn3 + residual join (pl_bn_train_fwd_ex with `join`; Resnet.py:81-91) in three launches: dx = (g + g2)
@@ -2165,19 +2179,12 @@ extern "C" int pl_bn_join_bwd(const float* g, const float* g2, const uint64_t* b
   if (bn_replicas(rows, C) != 1) PL_FAIL(PL_ESHAPE, "pl_bn_join_bwd: C=%lld is narrower than one 256-column strip", (long long)C);
   const bool scaled = dz_planes && planes_mode == PL_F16X3;
   if (scaled && !dz_scale) PL_FAIL(PL_EINVAL, "pl_bn_join_bwd: fp16 planes of dz need dz_scale");
-  PlaneOut po;
-  PL_TRY(plane_out_of(planes_mode, dz_planes, rows * C, 1.0f, scaled ? dz_scale : nullptr, &po, "pl_bn_join_bwd"));
-  hipStream_t s = (hipStream_t)stream;
-  const int B = (int)rows, H = (int)C, RC = bwd_row_chunks(B, H);
-  float* part = static_cast<float*>(scratch);
-  float* coef = part + (size_t)2 * RC * H;
-  float* part_db = coef + 3 * (size_t)H;
-  float* amax = part_db + (size_t)RC * H;
-  const int n_amax = ((H + 255) / 256) * RC;
-  PL_TRY(launch_bn_bwd_reduce(g, bits, z, mean, rstd, 1.0f, B, H, part, part + (size_t)RC * H, s, H, scaled ? amax : nullptr, 0, g2, dx));
-  PL_TRY(launch_bn_bwd_finalize(part, RC, 1, 0, B, H, gamma, rstd, coef, dgamma, dbeta, s, scaled ? amax : nullptr, n_amax,
-                                scaled ? dz_scale : nullptr));
-  return launch_bn_bwd_dz(dx, bits, z, mean, rstd, coef, 1.0f, 1, B, H, dz, part_db, s, H, dz_planes ? &po : nullptr);
+  ConvBnBwd a = {};
+  PL_TRY(plane_out_of(planes_mode, dz_planes, rows * C, 1.0f, scaled ? dz_scale : nullptr, &a.planes, "pl_bn_join_bwd"));
+  a.g = g; a.join_g2 = g2; a.join_dx = dx;
+  a.saved = conv_saved(z, bits, mean, rstd); a.gamma = gamma; a.dz = dz; a.dgamma = dgamma; a.dbeta = dbeta;
+  a.dz_scale = scaled ? dz_scale : nullptr;
+  return conv_bn_bwd(a, rows, C, scratch, (hipStream_t)stream);
 }
 
 extern "C" int pl_add_relu_fwd(const float* a, const float* b, int64_t rows, int64_t C, float* out, uint64_t* bits,

@@ -44,4 +44,40 @@ inline uint32_t dropout_threshold(float p) {
   return (uint32_t)t;   // floor
 }
 
+// Everything a kernel needs to decide "keep" for one hidden layer's dropout.
+// mode: 0 keep all, 1 philox, 2 injected bitmap, 3 drop all; kscale = 1 / (1 - p) where something is kept and dropped.
+// step_dev != NULL (graph replay): the step number is the host's step + the device counter; c3 / k1 then carry the host step's low /
+// high word and the kernel forms the counter and key words itself (dropout_replay_step).
+struct DropKey {
+  int mode;
+  uint32_t thr;
+  float kscale;
+  uint32_t k0, k1, c3, layer, seed_hi;
+  const uint64_t* inject;
+  const uint64_t* step_dev;
+};
+
+inline DropKey dropout_key(float p, uint64_t seed, uint64_t step, int layer, const uint64_t* inject_keep,
+                           const uint64_t* step_dev) {
+  DropKey k = {};
+  k.kscale = 1.f;
+  if (p >= 1.f) k.mode = 3;
+  else if (p > 0.f) { k.mode = inject_keep ? 2 : 1; k.kscale = 1.0f / (1.0f - p); }
+  k.thr = dropout_threshold(p);
+  k.k0 = (uint32_t)seed; k.seed_hi = (uint32_t)(seed >> 32);
+  k.k1 = step_dev ? (uint32_t)(step >> 32) : k.seed_hi ^ (uint32_t)(step >> 32);
+  k.c3 = (uint32_t)step; k.layer = (uint32_t)layer;
+  k.inject = inject_keep; k.step_dev = step_dev;
+  return k;
+}
+
+// graph replay: c3 / k1 arrive as the low / high word of the step baked in at capture; the step of this replay is that plus
+// the device counter
+__device__ __forceinline__ void dropout_replay_step(uint32_t& c3, uint32_t& k1, uint32_t seed_hi, const uint64_t* step_dev) {
+  if (!step_dev) return;
+  const uint64_t step = (((uint64_t)k1 << 32) | c3) + step_dev[0];
+  c3 = (uint32_t)step;
+  k1 = seed_hi ^ (uint32_t)(step >> 32);
+}
+
 }  // namespace pl

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/poselift.h"
+#include "philox.h"
 
 namespace pl {
 
@@ -165,61 +166,116 @@ int prof_read(double min_flops, double max_flops, double* ms_total, int64_t* lau
 // ---------------------------------------------------------------------------------
 inline int bitmap_words_per_row(int H) { return ((H + 255) / 256) * 4; }
 
-// BN statistics: merge per-group (sum, M2) partials -> mean/rstd/scale/shift, update running
-// (stat = [world][2][G][H]: per rank G rows of sums then G rows of M2; B = rows per rank)
-int launch_bn_finalize(const float* stat, int G, int world, int B, int H,
-                       const float* gamma, const float* beta, float eps, float momentum,
-                       float* running_mean, float* running_var, int64_t* batches,
-                       float* mean, float* rstd, float* scale, float* shift, hipStream_t s, int group_rows = 64);
-
-// act = [resid +] dropout(relu(z*scale + shift)); bits = keep&positive bitmap
-// planes: also (act == NULL: only) write the activation as GEMM operand planes
-// finalize != NULL: the statistics finalize (launch_bn_finalize's job: local statistics, at most 4 groups) inside this launch;
-// scale / shift are then not read
-struct BnFinalizeArgs {
-  const float* stat;            // [2][G][H] partials of this process
-  int G, group_rows;
+// A BatchNorm layer's parameters and running statistics (built once per layer: layer_of() in api.hip, the C ABI's
+// arguments on the conv path).  running_mean / running_var / batches may be NULL (nothing to update).
+struct BnParams {
   const float *gamma, *beta;
   float eps, momentum;
   float *running_mean, *running_var;
   int64_t* batches;
-  float *mean, *rstd;
 };
-int launch_bn_apply(const float* z, const float* scale, const float* shift, const float* resid,
-                    float* act, uint64_t* bits, int B, int H, float p, uint64_t seed,
-                    uint64_t step, int layer, const uint64_t* inject_keep, hipStream_t s,
-                    const PlaneOut* planes = nullptr, const uint64_t* step_dev = nullptr,
-                    const BnFinalizeArgs* finalize = nullptr);
+// What a layer's forward saves for its backward: the pre-activation, the ReLU & keep bitmap and the batch statistics.
+// tile_bits: the bitmap is in the tile format of small_layer.hip (the layer's forward ran there) instead of the row format
+// of bn_apply_row.
+struct BnSaved {
+  float* z;
+  uint64_t* bits;
+  float *mean, *rstd;
+  bool tile_bits;
+};
+
+// BN statistics: merge per-group (sum, M2) partials -> mean/rstd/scale/shift, update running
+// (stat = [world][2][G][H]: per rank G rows of sums then G rows of M2 over group_rows rows each; B = rows per rank)
+struct BnFinalizeArgs {
+  const float* stat;
+  int G, group_rows, world, B, H;
+  BnParams bn;
+  float *mean, *rstd, *scale, *shift;
+};
+int launch_bn_finalize(const BnFinalizeArgs& a, hipStream_t s);
+
+// act = [resid +] dropout(relu(z*scale + shift)); bits = keep&positive bitmap
+struct BnApplyArgs {
+  const float* z;
+  const float *scale, *shift;   // [Hc]; NULL: identity (no BatchNorm); not read when fin.stat is set
+  const float* resid;           // optional
+  float* act;                   // NULL: planes only
+  uint64_t* bits;
+  int B, H;
+  int Hc;                       // real columns behind the H virtual ones (conv path, bn_colstats_kernel); 0: H
+  bool no_relu;                 // BatchNorm alone; the bitmap is all ones
+  bool resid_before_relu;       // relu(bn(z) + resid), the Bottleneck's join, instead of resid + relu(bn(z))
+  DropKey drop;                 // dropout_key(); dropout_key(0, ...) where there is no dropout
+  PlaneOut planes;              // kind != 0: also (act == NULL: only) write the activation as GEMM operand planes
+  // fin.stat != NULL: the statistics finalize (launch_bn_finalize's job) inside this launch.  The kernel takes local
+  // statistics (world, scale and shift are not read; B and H are this launch's) of at most 16 groups; plan() routes
+  // single-process layers of at most 4 groups (256 rows) here (Stats::InApply).
+  BnFinalizeArgs fin;
+};
+int launch_bn_apply(const BnApplyArgs& a, hipStream_t s);
 // pl_mse_fwd_bwd + (tick != NULL) tick[0] += 1 once the loss is written (PLDesc.step_dev, graph replay)
 int mse_fwd_bwd_tick(const float* pred, const float* tgt, int64_t n, float grad_scale, float* dpred, float* loss_out,
                      void* scratch, uint64_t* tick, void* stream);
 
 int bwd_row_chunks(int B, int H);
 // pass 1: partial column sums of dy and dy*zhat, dy = g * bits * keep_scale
-// part_amax (optional): [strips * RC][2] per-workgroup maxima of |dy| and |zhat| (the dz range bound, below)
-int launch_bn_bwd_reduce(const float* g, const uint64_t* bits, const float* z, const float* mean,
-                         const float* rstd, float keep_scale, int B, int H, float* part_dy,
-                         float* part_dyz, hipStream_t s, int Hc = 0, float* part_amax = nullptr, int rc = 0,
-                         const float* join_g2 = nullptr, float* join_dx = nullptr);
+struct BnBwdReduceArgs {
+  const float* g;
+  BnSaved saved;
+  float keep_scale;
+  int B, H;
+  int Hc;                       // 0: H
+  int rc;                       // row chunks (grid.y); 0: bwd_row_chunks(B, H)
+  float *part_dy, *part_dyz;
+  float* part_amax;             // optional: [strips * rc][2] per-workgroup maxima of |dy| and |zhat| (the dz range bound, below)
+  const float* join_g2;         // the residual join's backward: g := (g + join_g2 (or 0)) where the bitmap is set, written
+  float* join_dx;               //   to join_dx by this pass (NULL: none)
+};
+int launch_bn_bwd_reduce(const BnBwdReduceArgs& a, hipStream_t s);
 
 // dz_scale (optional, with part_amax of n_amax workgroups): {S, 1/S}, S the power of two that maps the bound
 // max|c0| max|dy| (2 + max|zhat|) >= max|dz| to at most 2^14 (fp16 planes of dz, PL_F16X3)
-int launch_bn_bwd_finalize(const float* part, int RC, int world, int rank, int B, int H,
-                           const float* gamma, const float* rstd, float* coef, float* dgamma,
-                           float* dbeta, hipStream_t s, const float* part_amax = nullptr, int n_amax = 0,
-                           float* dz_scale = nullptr, int eval_mode = 0, int64_t rstride = 0, int amax_world = 1);
+struct BnBwdFinalizeArgs {
+  const float* part;
+  int RC, world, rank, B, H;
+  const float *gamma, *rstd;
+  float *coef, *dgamma, *dbeta;
+  const float* part_amax;
+  int n_amax;
+  float* dz_scale;
+  int eval_mode;
+  int64_t rstride;
+  int amax_world;               // 0: 1
+};
+int launch_bn_bwd_finalize(const BnBwdFinalizeArgs& a, hipStream_t s);
 // Small batches (B <= kBnSmallRows, local statistics, fp32 outputs): statistics + finalize + apply of a hidden layer in ONE
 // launch (a workgroup owns a 256-column strip for all rows, held in registers), and pass 1 + finalize + dz + bias gradient
 // of its backward.  Measured same-box (bench.py --batch B): B = 64 0.305 -> 0.280 ms per step; B = 100 / 127 with sixteen
 // rows per wave 0.42 / 0.45 -> 0.47 / 0.52 ms (slower: kept to 64 rows).
 constexpr int kBnSmallRows = 64;
-int launch_bn_small_fwd(const float* z, const float* gamma, const float* beta, float eps, float momentum, float* rm, float* rv,
-                        int64_t* nbt, float* mean, float* rstd, const float* resid, float* act, uint64_t* bits, int B, int H,
-                        float p, uint64_t seed, uint64_t step, int layer, const uint64_t* inject_keep, hipStream_t s,
-                        const uint64_t* step_dev);
-int launch_bn_small_bwd(const float* g, const uint64_t* bits, const float* z, const float* mean, const float* rstd,
-                        const float* gamma, float keep_scale, int B, int H, float* dz, float* dgamma, float* dbeta, float* dbias,
-                        hipStream_t s, bool tile_bits = false);
+struct BnSmallFwdArgs {
+  BnSaved saved;                // z read; bits, mean, rstd written (row-format bitmap)
+  BnParams bn;
+  const float* resid;           // optional
+  float* act;
+  int B, H;
+  DropKey drop;
+};
+int launch_bn_small_fwd(const BnSmallFwdArgs& a, hipStream_t s);
+// what the BatchNorm backward of a small-batch layer reads and writes (besides its incoming gradient and dz)
+struct SmallBnLayer {
+  BnSaved saved;
+  const float* gamma;
+  float *dgamma, *dbeta, *dbias;
+};
+struct BnSmallBwdArgs {
+  const float* g;
+  SmallBnLayer layer;
+  float keep_scale;
+  int B, H;
+  float* dz;
+};
+int launch_bn_small_bwd(const BnSmallBwdArgs& a, hipStream_t s);
 // Small batches, hidden layers behind the first (small_layer.hip): a workgroup owns 16 columns for all B <= 64 rows, so one
 // launch is Linear + BatchNorm1d (batch statistics) + ReLU + Dropout (+ skip) forward, and one launch is dX = dz W (+ skip
 // gradient) followed by the BatchNorm backward of the layer below.  Their ReLU & keep bitmap is in the "tile format" of
@@ -230,65 +286,121 @@ bool small_layer_ok(int B, int H, int K);
 // dW2, db2; out_dim <= 64) as one launch.
 bool small_first_ok(int K);
 bool small_top_ok(int O);
-int launch_small_layer_fwd(const float* a, const float* W, const float* bias, const float* gamma, const float* beta, float eps,
-                           float momentum, float* rm, float* rv, int64_t* nbt, float* mean, float* rstd, const float* resid,
-                           float* z, float* act, uint64_t* bits, int B, int H, int K, float pdrop, uint64_t seed, uint64_t step,
-                           int layer, const uint64_t* inject_keep, hipStream_t s, const uint64_t* step_dev, bool first = false,
-                           const float* W2 = nullptr, float* ypart = nullptr, int O = 0,
-                           const unsigned short* a_planes = nullptr, unsigned short* out_planes = nullptr);
-// a_planes (PL_F16X3 descriptors, not the first layer): the input as two fp16 planes [B][K] (h, l) -- the contraction then
-// runs as three fp16 MFMAs per product (fp32-grade, a fifth of the MFMA time of the exact fp32 form); out_planes: the output
-// also as planes [B][H], for the next layer's launch
-// ypart != NULL (the last hidden layer of a fused train step): the launch also leaves its share of the output Linear,
-// ypart [H / 16][B][64] (columns < O); launch_small_mse adds the slabs up: y, dpred = grad_scale * 2 (y - t) / (B O) and
-// small_mse_partials(B, O) partial sums of (y - t)^2 -- no launch for the output layer, none for its slab reduce
+// One hidden layer of a small batch, forward.  launch_small_layer_fwd (training: B <= 64 rows, batch statistics) reads every
+// field; launch_small_layer_eval (any B; running statistics, Dropout the identity, nothing saved) ignores saved and drop.
+struct SmallLayerFwdArgs {
+  const float *a, *W, *bias;
+  BnParams bn;
+  BnSaved saved;                // z, bits (tile format), mean, rstd: written
+  const float* resid;           // optional
+  float* act;
+  int B, H, K, layer;
+  DropKey drop;
+  bool first;                   // the first layer (K = in_dim <= 256 inputs: contraction on the vector unit)
+  // ypart != NULL (the last hidden layer of a fused train step / of an evaluation): the launch also leaves its share of the
+  // output Linear, ypart [H / 16][B][64] (columns < O); launch_small_mse adds the slabs up: y, dpred = grad_scale * 2 (y - t)
+  // / (B O) and small_mse_partials(B, O) partial sums of (y - t)^2 -- no launch for the output layer, none for its slab
+  // reduce; an evaluation hands them to launch_small_out
+  const float* W2;
+  float* ypart;
+  int O;
+  // a_planes (PL_F16X3 descriptors, not the first layer): the input as two fp16 planes [B][K] (h, l) -- the contraction then
+  // runs as three fp16 MFMAs per product (fp32-grade, a fifth of the MFMA time of the exact fp32 form); out_planes: the output
+  // also as planes [B][H], for the next layer's launch
+  const unsigned short* a_planes;
+  unsigned short* out_planes;
+};
+int launch_small_layer_fwd(const SmallLayerFwdArgs& a, hipStream_t s);
 // evaluation forward (model.eval()): the same layer kernels with the BatchNorm fold on the running statistics as tail, the
-// grid also over 64-row blocks (any M; every row the same bits whatever the batch), and launch_small_out for the output layer
-int launch_small_layer_eval(const float* a, const float* W, const float* bias, const float* gamma, const float* beta, float eps,
-                            const float* rm, const float* rv, const float* resid, float* act, int M, int H, int K, hipStream_t s,
-                            bool first = false, const float* W2 = nullptr, float* ypart = nullptr, int O = 0,
-                            const unsigned short* a_planes = nullptr, unsigned short* out_planes = nullptr, int layer = 0);
-int launch_small_out(const float* ypart, int NS, int M, int O, const float* bias, float* y, hipStream_t s);
+// grid also over 64-row blocks (any B; every row the same bits whatever the batch), and launch_small_out for the output layer
+int launch_small_layer_eval(const SmallLayerFwdArgs& a, hipStream_t s);
+// the output Linear from the NS slabs the last hidden layer's launch left: y = bias + their sum (launch_small_out reads
+// these fields alone) and, launch_small_mse, dpred = grad_scale * 2 (y - tgt) / (B O) and the MSE partials in mpart
+struct SmallHeadArgs {
+  const float* ypart;
+  int NS, B, O;
+  const float* bias;
+  float* y;
+  const float* tgt;
+  float grad_scale;
+  float *dpred, *mpart;
+};
+int launch_small_out(const SmallHeadArgs& a, hipStream_t s);
 // the Linear alone with the statistics partials of a tile GEMM's epilogue, for TRAINING batches of 65 ... 512 rows: the tile
 // GEMMs have 8 ... 32 tiles for 256 CUs there (22 us per forward GEMM at any of these sizes; this form: 9-17 us)
-int launch_small_linear_stats(const float* a, const unsigned short* a_planes, const float* W, const float* bias, float* z, int M,
-                              int H, int K, float* stat_sum, float* stat_m2, int groups, hipStream_t s);
-int small_mse_partials(int B, int O);     // partial sums launch_small_mse leaves in mpart (<= 64)
-int launch_small_mse(const float* ypart, int NS, int B, int O, const float* bias, const float* tgt, float grad_scale, float* y,
-                     float* dpred, float* mpart, hipStream_t s);
-// what the BatchNorm backward of a layer reads and writes (besides its incoming gradient and dz)
-struct SmallBnLayer {
-  const float *z, *mean, *rstd, *gamma;
-  const uint64_t* bits;
-  bool rowbits;                           // bitmap in the row format (the layer's forward was bn_small_fwd_kernel)
-  float *dgamma, *dbeta, *dbias;
+// (a_planes != NULL: the input as fp16 planes [M][K] (h, l) instead of a; stat_sum / stat_m2 [groups][H], optional)
+struct SmallLinearStatsArgs {
+  const float* a;
+  const unsigned short* a_planes;
+  const float *W, *bias;
+  float* z;
+  int M, H, K;
+  float *stat_sum, *stat_m2;
+  int groups;
 };
-// g = dz W (+ addend) -> gout (or NULL), then the BatchNorm backward of the layer below -> dz_lo;
-// dW != NULL: + dW = dz^T a_in (extra workgroups); dW1 != NULL: the layer below is the first one, + dW1 = dz_lo^T x1
-int launch_small_layer_bwd(const float* dz, const float* W, const float* addend, float* gout, int B, int H, int K,
-                           const SmallBnLayer& below, float kscale, float* dz_lo, hipStream_t s, const float* a_in = nullptr,
-                           float* dW = nullptr, const float* x1 = nullptr, float* dW1 = nullptr, int K1 = 0,
-                           const struct AdamWRide* adam = nullptr);   // adam: a slice of the AdamW step on spare workgroups (adamw.h)
-int launch_small_top_bwd(const float* dy, const float* W2, const float* h, int B, int H, int O, float* gout, float* dW2,
-                         float* db2, const SmallBnLayer& top, float kscale, float* dz_top, hipStream_t s,
-                         const float* mpart = nullptr, int np = 0, float inv_n = 0.f, float* loss = nullptr,
-                         uint64_t* tick = nullptr);   // loss != NULL: + loss = inv_n * sum of the np partials, tick += 1
+int launch_small_linear_stats(const SmallLinearStatsArgs& a, hipStream_t s);
+int small_mse_partials(int B, int O);     // partial sums launch_small_mse leaves in mpart (<= 64)
+int launch_small_mse(const SmallHeadArgs& a, hipStream_t s);
+// g = dz W (+ addend) -> gout (or NULL), then the BatchNorm backward of the layer below -> dz_lo
+struct SmallLayerBwdArgs {
+  const float *dz, *W;
+  const float* addend;          // optional
+  float* gout;                  // optional
+  int B, H, K;
+  SmallBnLayer below;
+  float kscale;
+  float* dz_lo;
+  const float* a_in;            // dW != NULL: + dW = dz^T a_in (extra workgroups)
+  float* dW;
+  const float* x1;              // dW1 != NULL: the layer below is the first one, + dW1 = dz_lo^T x1 (K1 inputs)
+  float* dW1;
+  int K1;
+  const struct AdamWRide* adam; // optional: a slice of the AdamW step on spare workgroups (adamw.h)
+};
+int launch_small_layer_bwd(const SmallLayerBwdArgs& a, hipStream_t s);
+// the whole top of the backward pass: g = dy W2 -> gout, the BatchNorm backward of the last hidden layer -> dz_top, dW2, db2
+struct SmallTopBwdArgs {
+  const float *dy, *W2, *h;
+  int B, H, O;
+  float *gout, *dW2, *db2;
+  SmallBnLayer top;
+  float kscale;
+  float* dz_top;
+  const float* mpart;           // loss != NULL: + loss = inv_n * sum of the np partials in mpart, tick[0] += 1
+  int np;
+  float inv_n;
+  float* loss;
+  uint64_t* tick;
+};
+int launch_small_top_bwd(const SmallTopBwdArgs& a, hipStream_t s);
 // eval-mode BatchNorm for the saved-state forward: mean := running mean, rstd := rsqrt(running var + eps), scale, shift
-int launch_bn_eval_stats(const float* gamma, const float* beta, const float* rm, const float* rv, float eps, int H,
-                         float* mean, float* rstd, float* scale, float* shift, hipStream_t s);
+// (reads a.bn, a.H and the four outputs)
+int launch_bn_eval_stats(const BnFinalizeArgs& a, hipStream_t s);
 // pass 2: dz = c0*(dy - c1 - zhat*c2)  (bn) or dz = dy (no bn); partial column sums of dz
-// planes: also (dz == NULL: only) write dz as GEMM operand planes
-int launch_bn_bwd_dz(const float* g, const uint64_t* bits, const float* z, const float* mean,
-                     const float* rstd, const float* coef, float keep_scale, int bn, int B, int H,
-                     float* dz, float* part_db, hipStream_t s, int Hc = 0, const PlaneOut* planes = nullptr, int rc = 0);
+struct BnBwdDzArgs {
+  const float* g;
+  BnSaved saved;
+  const float* coef;
+  float keep_scale;
+  int bn, B, H;
+  int Hc;                       // 0: H
+  int rc;                       // row chunks (grid.y); 0: bwd_row_chunks(B, H)
+  float* dz;                    // NULL: planes only
+  float* part_db;
+  PlaneOut planes;              // kind != 0: also write dz as GEMM operand planes
+};
+int launch_bn_bwd_dz(const BnBwdDzArgs& a, hipStream_t s);
 
 // out[i] = sum_s slabs[s*n + i]
 int launch_reduce_slabs(const float* slabs, int nslab, int64_t n, float* out, hipStream_t s);
 // njobs independent out[c] = sum_r part[r][c] reductions in one launch
 // kind 2 (at most one job): out[0] = (sum of the R MSE partials) * loss_inv_n, then loss_tick[0] += 1 -- mse_final_kernel
-int launch_reduce_rows_multi(const float* const* part, const int* R, const int* H, float* const* out, int njobs,
-                             hipStream_t s, const int* kind = nullptr, const int* transK = nullptr, float loss_inv_n = 0.f,
-                             uint64_t* loss_tick = nullptr);
+struct RowJob {
+  const float* part;
+  float* out;
+  int R, H, kind, transK;
+};
+int launch_reduce_rows_multi(const RowJob* jobs, int njobs, float loss_inv_n, uint64_t* loss_tick, hipStream_t s);
 int mse_partial_only(const float* pred, const float* tgt, int64_t n, float grad_scale, float* dpred, void* scratch, void* stream);
 int mse_partials(int64_t n);
 // the output Linear's slab reduce folded into the MSE partial pass (fused train step; bit-identical to the two launches)
@@ -302,9 +414,7 @@ int launch_reduce_slabs_bias(const float* slabs, int nslab, int rows, int cols, 
 int colsum_chunks(int rows);
 int launch_colsum_partial(const float* X, int rows, int cols, float* part, hipStream_t s);
 // eval-mode fold: scale = gamma*rsqrt(rv+eps), shift = (bias - rm)*scale + beta  (bn) or 1, bias
-int launch_bn_fold_eval(const float* bias, const float* gamma, const float* beta, const float* rm,
-                        const float* rv, float eps, int bn, int H, float* scale, float* shift,
-                        hipStream_t s);
+int launch_bn_fold_eval(const float* bias, const BnParams* bn, int H, float* scale, float* shift, hipStream_t s);
 int launch_fill(float* p, int64_t n, float v, hipStream_t s);
 
 // ---------------------------------------------------------------------------------

@@ -409,11 +409,7 @@ __device__ __forceinline__ float4 fwd_tail(const FwdArgs& p, float4 z, const Fwd
   if (p.nbt && blockIdx.x == 0 && tid == 0) p.nbt[0] += 1;
   // ReLU, dropout, bitmap, residual (element order of bn_apply_row, elementwise.hip)
   uint32_t c3 = p.c3, k1 = p.k1;
-  if (p.step_dev) {
-    const uint64_t step = (((uint64_t)k1 << 32) | c3) + p.step_dev[0];
-    c3 = (uint32_t)step;
-    k1 = p.seed_hi ^ (uint32_t)(step >> 32);
-  }
+  dropout_replay_step(c3, k1, p.seed_hi, p.step_dev);
   const int mode = p.mode & 7;
   const bool norelu = (p.mode & 8) != 0;
   const float zv[4] = {z.x, z.y, z.z, z.w};
@@ -925,170 +921,150 @@ bool small_top_ok(int O) {
 }
 
 // the output Linear of an evaluation forward from the slabs the last hidden layer's launch left: y = bias + sum of slabs
-int launch_small_out(const float* ypart, int NS, int M, int O, const float* bias, float* y, hipStream_t s) {
-  if (!ypart || !y || NS < 1 || M < 1 || !small_top_ok(O)) PL_FAIL(PL_EINVAL, "small_out: bad arguments");
-  hipLaunchKernelGGL(small_mse_kernel, dim3((M * O + kMseElems - 1) / kMseElems), dim3(256), 0, s, ypart, NS, M, O, bias,
-                     (const float*)nullptr, 0.f, y, (float*)nullptr, (float*)nullptr);
+int launch_small_out(const SmallHeadArgs& a, hipStream_t s) {
+  if (!a.ypart || !a.y || a.NS < 1 || a.B < 1 || !small_top_ok(a.O)) PL_FAIL(PL_EINVAL, "small_out: bad arguments");
+  hipLaunchKernelGGL(small_mse_kernel, dim3((a.B * a.O + kMseElems - 1) / kMseElems), dim3(256), 0, s, a.ypart, a.NS, a.B, a.O,
+                     a.bias, (const float*)nullptr, 0.f, a.y, (float*)nullptr, (float*)nullptr);
   PL_CHECK_LAUNCH("small_out");
   return PL_OK;
 }
 
-// hidden layer l of an evaluation forward of M rows (any M: the grid runs over 64-row blocks): act = relu(bn_eval(a W^T + b))
-// (+ resid); first: the K-input first layer; ypart != NULL: + the output Linear's slabs [H / 16][M][64]
-int launch_small_layer_eval(const float* a, const float* W, const float* bias, const float* gamma, const float* beta, float eps,
-                            const float* rm, const float* rv, const float* resid, float* act, int M, int H, int K, hipStream_t s,
-                            bool first, const float* W2, float* ypart, int O, const unsigned short* a_planes,
-                            unsigned short* out_planes, int layer) {
-  if (first ? !(small_layer_ok(2, H, H) && small_first_ok(K)) : !small_layer_ok(2, H, K))
-    PL_FAIL(PL_ESHAPE, "small_layer_eval: H=%d K=%d first=%d", H, K, (int)first);
-  if (!a || !W || !bias || !gamma || !beta || !rm || !rv || !act || M < 1) PL_FAIL(PL_EINVAL, "small_layer_eval: bad arguments");
-  if ((!first && (!al16(a) || !al16(W))) || !al16(bias) || !al16(gamma) || !al16(beta) || !al16(rm) || !al16(rv) || !al16(act) ||
-      !al16(resid))
-    PL_FAIL(PL_EINVAL, "small_layer_eval: 16-byte alignment");
-  FwdArgs p = {};
-  p.a = a; p.W = W; p.bias = bias; p.gamma = gamma; p.beta = beta; p.resid = resid;
-  p.rm = const_cast<float*>(rm); p.rv = const_cast<float*>(rv); p.act = act; p.eps = eps;
-  p.B = ROWS; p.H = H; p.K = K; p.eval = 1; p.Mtot = M;
-  if (ypart) {
-    if (!W2 || !small_top_ok(O)) PL_FAIL(PL_EINVAL, "small_layer_eval: output-layer slabs (O=%d)", O);
-    p.W2 = W2; p.ypart = ypart; p.O = O;
+namespace {
+// what launch_small_layer_fwd / _eval share: the kernel's arguments from the fields both read (rows: all rows of the
+// launch), and the launch itself (grid.y = row_blocks 64-row blocks)
+int fill_layer_fwd(FwdArgs& p, const SmallLayerFwdArgs& a, int rows, const char* who) {
+  p.a = a.a; p.W = a.W; p.bias = a.bias; p.resid = a.resid; p.act = a.act;
+  p.gamma = a.bn.gamma; p.beta = a.bn.beta; p.eps = a.bn.eps; p.rm = a.bn.running_mean; p.rv = a.bn.running_var;
+  p.H = a.H; p.K = a.K;
+  if (a.ypart) {
+    if (!a.W2 || !small_top_ok(a.O)) PL_FAIL(PL_EINVAL, "%s: output-layer slabs (O=%d)", who, a.O);
+    p.W2 = a.W2; p.ypart = a.ypart; p.O = a.O;
   }
-  if ((a_planes && (first || !al16(a_planes))) || !al16(out_planes)) PL_FAIL(PL_EINVAL, "small_layer_eval: operand planes");
-  p.ap = a_planes; p.a_plane = (size_t)M * K; p.outp = out_planes; p.o_plane = (size_t)M * H;
-  p.range = range_record(); p.site = range_site_act(layer);
-  const dim3 grid(H / COLS, (M + ROWS - 1) / ROWS), block(NTHR);
-  void* prof = prof_begin_flops(2.0 * M * H * K, s);
+  if ((a.a_planes && (a.first || !al16(a.a_planes))) || !al16(a.out_planes)) PL_FAIL(PL_EINVAL, "%s: operand planes", who);
+  p.ap = a.a_planes; p.a_plane = (size_t)rows * a.K; p.outp = a.out_planes; p.o_plane = (size_t)rows * a.H;
+  p.range = range_record(); p.site = range_site_act(a.layer);
+  return PL_OK;
+}
+int run_layer_fwd(const FwdArgs& p, bool first, int rows, int row_blocks, const char* who, hipStream_t s) {
+  const dim3 grid(p.H / COLS, row_blocks), block(NTHR);
+  void* prof = prof_begin_flops(2.0 * rows * p.H * p.K, s);
   if (first) hipLaunchKernelGGL(small_first_fwd_kernel, grid, block, 0, s, p);
-  else switch (K / (NWAVE * 32)) {
+  else switch (p.K / (NWAVE * 32)) {
     case 1: hipLaunchKernelGGL(small_fwd_kernel<1>, grid, block, 0, s, p); break;
     case 2: hipLaunchKernelGGL(small_fwd_kernel<2>, grid, block, 0, s, p); break;
     default: hipLaunchKernelGGL(small_fwd_kernel<4>, grid, block, 0, s, p); break;
   }
   prof_end(prof, s);
-  PL_CHECK_LAUNCH("small_layer_eval");
+  PL_CHECK_LAUNCH(who);
   return PL_OK;
+}
+}  // namespace
+
+// hidden layer l of an evaluation forward of a.B rows (any number: the grid runs over 64-row blocks): act = relu(bn_eval(a W^T
+// + b)) (+ resid); first: the K-input first layer; ypart != NULL: + the output Linear's slabs [H / 16][B][64]
+int launch_small_layer_eval(const SmallLayerFwdArgs& a, hipStream_t s) {
+  const int M = a.B;
+  if (a.first ? !(small_layer_ok(2, a.H, a.H) && small_first_ok(a.K)) : !small_layer_ok(2, a.H, a.K))
+    PL_FAIL(PL_ESHAPE, "small_layer_eval: H=%d K=%d first=%d", a.H, a.K, (int)a.first);
+  if (!a.a || !a.W || !a.bias || !a.bn.gamma || !a.bn.beta || !a.bn.running_mean || !a.bn.running_var || !a.act || M < 1)
+    PL_FAIL(PL_EINVAL, "small_layer_eval: bad arguments");
+  if ((!a.first && (!al16(a.a) || !al16(a.W))) || !al16(a.bias) || !al16(a.bn.gamma) || !al16(a.bn.beta) ||
+      !al16(a.bn.running_mean) || !al16(a.bn.running_var) || !al16(a.act) || !al16(a.resid))
+    PL_FAIL(PL_EINVAL, "small_layer_eval: 16-byte alignment");
+  FwdArgs p = {};
+  PL_TRY(fill_layer_fwd(p, a, M, "small_layer_eval"));
+  p.B = ROWS; p.eval = 1; p.Mtot = M;
+  return run_layer_fwd(p, a.first, M, (M + ROWS - 1) / ROWS, "small_layer_eval", s);
 }
 
 // z [M][H] = a W^T + bias for M <= 512 rows (any M; one 64-row block x 16 columns per workgroup) and, stat_sum != NULL, the
 // groups partial BatchNorm statistics of a tile GEMM's epilogue ([groups][H] each; groups >= ceil(M / 64): the rest zeros).
 // a_planes != NULL: the input as fp16 planes [M][K] (h, l), contraction as three fp16 MFMAs per product; else a fp32, exact.
-int launch_small_linear_stats(const float* a, const unsigned short* a_planes, const float* W, const float* bias, float* z, int M,
-                              int H, int K, float* stat_sum, float* stat_m2, int groups, hipStream_t s) {
-  if (!small_layer_ok(2, H, K) || M < 1 || groups < (M + ROWS - 1) / ROWS)
-    PL_FAIL(PL_ESHAPE, "small_linear_stats: M=%d H=%d K=%d groups=%d", M, H, K, groups);
-  if ((!a && !a_planes) || !W || !bias || !z || (stat_sum != nullptr) != (stat_m2 != nullptr))
+int launch_small_linear_stats(const SmallLinearStatsArgs& q, hipStream_t s) {
+  const int M = q.M, H = q.H, K = q.K;
+  if (!small_layer_ok(2, H, K) || M < 1 || q.groups < (M + ROWS - 1) / ROWS)
+    PL_FAIL(PL_ESHAPE, "small_linear_stats: M=%d H=%d K=%d groups=%d", M, H, K, q.groups);
+  if ((!q.a && !q.a_planes) || !q.W || !q.bias || !q.z || (q.stat_sum != nullptr) != (q.stat_m2 != nullptr))
     PL_FAIL(PL_EINVAL, "small_linear_stats: bad arguments");
-  if (!al16(a) || !al16(a_planes) || !al16(W) || !al16(bias) || !al16(z) || !al16(stat_sum) || !al16(stat_m2))
+  if (!al16(q.a) || !al16(q.a_planes) || !al16(q.W) || !al16(q.bias) || !al16(q.z) || !al16(q.stat_sum) || !al16(q.stat_m2))
     PL_FAIL(PL_EINVAL, "small_linear_stats: 16-byte alignment");
   FwdArgs p = {};
-  p.a = a; p.W = W; p.bias = bias; p.z = z; p.B = ROWS; p.H = H; p.K = K; p.Mtot = M; p.stats = 1;
-  p.stat_sum = stat_sum; p.stat_m2 = stat_m2;
-  p.ap = a_planes; p.a_plane = (size_t)M * K; p.range = range_record();
-  if (!a) p.a = reinterpret_cast<const float*>(a_planes);     // (never read: the planes form is taken)
-  const dim3 grid(H / COLS, stat_sum ? groups : (M + ROWS - 1) / ROWS), block(NTHR);
-  void* prof = prof_begin_flops(2.0 * M * H * K, s);
-  switch (K / (NWAVE * 32)) {
-    case 1: hipLaunchKernelGGL(small_fwd_kernel<1>, grid, block, 0, s, p); break;
-    case 2: hipLaunchKernelGGL(small_fwd_kernel<2>, grid, block, 0, s, p); break;
-    default: hipLaunchKernelGGL(small_fwd_kernel<4>, grid, block, 0, s, p); break;
-  }
-  prof_end(prof, s);
-  PL_CHECK_LAUNCH("small_linear_stats");
-  return PL_OK;
+  p.a = q.a; p.W = q.W; p.bias = q.bias; p.z = q.z; p.B = ROWS; p.H = H; p.K = K; p.Mtot = M; p.stats = 1;
+  p.stat_sum = q.stat_sum; p.stat_m2 = q.stat_m2;
+  p.ap = q.a_planes; p.a_plane = (size_t)M * K; p.range = range_record();
+  if (!q.a) p.a = reinterpret_cast<const float*>(q.a_planes);     // (never read: the planes form is taken)
+  return run_layer_fwd(p, false, M, q.stat_sum ? q.groups : (M + ROWS - 1) / ROWS, "small_linear_stats", s);
 }
 
-int launch_small_layer_fwd(const float* a, const float* W, const float* bias, const float* gamma, const float* beta, float eps,
-                           float momentum, float* rm, float* rv, int64_t* nbt, float* mean, float* rstd, const float* resid,
-                           float* z, float* act, uint64_t* bits, int B, int H, int K, float pdrop, uint64_t seed, uint64_t step,
-                           int layer, const uint64_t* inject_keep, hipStream_t s, const uint64_t* step_dev, bool first,
-                           const float* W2, float* ypart, int O, const unsigned short* a_planes, unsigned short* out_planes) {
-  if (first ? !(small_layer_ok(B, H, H) && small_first_ok(K)) : !small_layer_ok(B, H, K))
-    PL_FAIL(PL_ESHAPE, "small_layer_fwd: B=%d H=%d K=%d first=%d", B, H, K, (int)first);
-  if (!a || !W || !bias || !gamma || !beta || !mean || !rstd || !z || !act || !bits || (rm != nullptr) != (rv != nullptr))
+int launch_small_layer_fwd(const SmallLayerFwdArgs& a, hipStream_t s) {
+  const int B = a.B;
+  const BnSaved& sv = a.saved;
+  if (a.first ? !(small_layer_ok(B, a.H, a.H) && small_first_ok(a.K)) : !small_layer_ok(B, a.H, a.K))
+    PL_FAIL(PL_ESHAPE, "small_layer_fwd: B=%d H=%d K=%d first=%d", B, a.H, a.K, (int)a.first);
+  if (!a.a || !a.W || !a.bias || !a.bn.gamma || !a.bn.beta || !sv.mean || !sv.rstd || !sv.z || !a.act || !sv.bits ||
+      (a.bn.running_mean != nullptr) != (a.bn.running_var != nullptr))
     PL_FAIL(PL_EINVAL, "small_layer_fwd: bad arguments");
-  if ((!first && (!al16(a) || !al16(W))) || !al16(bias) || !al16(gamma) || !al16(beta) || !al16(mean) || !al16(rstd) || !al16(z) ||
-      !al16(act) || !al16(resid) || !al16(rm) || !al16(rv) || !al16(bits))
+  if ((!a.first && (!al16(a.a) || !al16(a.W))) || !al16(a.bias) || !al16(a.bn.gamma) || !al16(a.bn.beta) || !al16(sv.mean) ||
+      !al16(sv.rstd) || !al16(sv.z) || !al16(a.act) || !al16(a.resid) || !al16(a.bn.running_mean) || !al16(a.bn.running_var) ||
+      !al16(sv.bits))
     PL_FAIL(PL_EINVAL, "small_layer_fwd: 16-byte alignment");
   FwdArgs p = {};
-  p.a = a; p.W = W; p.bias = bias; p.gamma = gamma; p.beta = beta; p.resid = resid;
-  p.rm = rm; p.rv = rv; p.mean = mean; p.rstd = rstd; p.z = z; p.act = act; p.nbt = nbt; p.bits = bits;
-  p.inject = inject_keep; p.step_dev = step_dev; p.eps = eps; p.momentum = momentum;
-  p.B = B; p.H = H; p.K = K;
-  p.mode = 0; p.kscale = 1.f;
-  if (pdrop >= 1.f) p.mode = 3;
-  else if (pdrop > 0.f) { p.mode = inject_keep ? 2 : 1; p.kscale = 1.0f / (1.0f - pdrop); }
-  p.thr = dropout_threshold(pdrop);
-  p.k0 = (uint32_t)seed; p.seed_hi = (uint32_t)(seed >> 32);
-  p.k1 = step_dev ? (uint32_t)(step >> 32) : p.seed_hi ^ (uint32_t)(step >> 32);
-  p.c3 = (uint32_t)step; p.layer = (uint32_t)layer;
-  if (ypart) {
-    if (!W2 || !small_top_ok(O)) PL_FAIL(PL_EINVAL, "small_layer_fwd: output-layer slabs (O=%d)", O);
-    p.W2 = W2; p.ypart = ypart; p.O = O;
-  }
-  if ((a_planes && (first || !al16(a_planes))) || !al16(out_planes)) PL_FAIL(PL_EINVAL, "small_layer_fwd: operand planes");
-  p.ap = a_planes; p.a_plane = (size_t)B * K; p.outp = out_planes; p.o_plane = (size_t)B * H;
-  p.range = range_record(); p.site = range_site_act(layer);
-  const dim3 grid(H / COLS), block(NTHR);
-  void* prof = prof_begin_flops(2.0 * B * H * K, s);
-  if (first) {
-    hipLaunchKernelGGL(small_first_fwd_kernel, grid, block, 0, s, p);
-  } else {
-    switch (K / (NWAVE * 32)) {
-      case 1: hipLaunchKernelGGL(small_fwd_kernel<1>, grid, block, 0, s, p); break;
-      case 2: hipLaunchKernelGGL(small_fwd_kernel<2>, grid, block, 0, s, p); break;
-      default: hipLaunchKernelGGL(small_fwd_kernel<4>, grid, block, 0, s, p); break;
-    }
-  }
-  prof_end(prof, s);
-  PL_CHECK_LAUNCH("small_layer_fwd");
-  return PL_OK;
+  PL_TRY(fill_layer_fwd(p, a, B, "small_layer_fwd"));
+  const DropKey& k = a.drop;
+  p.momentum = a.bn.momentum; p.nbt = a.bn.batches; p.mean = sv.mean; p.rstd = sv.rstd; p.z = sv.z; p.bits = sv.bits; p.B = B;
+  p.mode = k.mode; p.thr = k.thr; p.kscale = k.kscale; p.k0 = k.k0; p.k1 = k.k1; p.c3 = k.c3; p.layer = k.layer;
+  p.seed_hi = k.seed_hi; p.inject = k.inject; p.step_dev = k.step_dev;
+  return run_layer_fwd(p, a.first, B, 1, "small_layer_fwd", s);
 }
 
 namespace {
+// the BatchNorm backward a launch ends with: every field of the layer checked in this one place
 int fill_lo(BnLo& lo, const SmallBnLayer& b, int B, int H, float kscale, float* dz_lo, const char* who) {
-  if (!b.z || !b.bits || !b.mean || !b.rstd || !b.gamma || !dz_lo || !b.dgamma || !b.dbeta || !b.dbias)
+  const BnSaved& v = b.saved;
+  if (!v.z || !v.bits || !v.mean || !v.rstd || !b.gamma || !dz_lo || !b.dgamma || !b.dbeta || !b.dbias)
     PL_FAIL(PL_EINVAL, "%s: bad arguments (layer below)", who);
-  if (!al16(b.z) || !al16(b.bits) || !al16(b.mean) || !al16(b.rstd) || !al16(b.gamma) || !al16(dz_lo) || !al16(b.dgamma) ||
+  if (!al16(v.z) || !al16(v.bits) || !al16(v.mean) || !al16(v.rstd) || !al16(b.gamma) || !al16(dz_lo) || !al16(b.dgamma) ||
       !al16(b.dbeta) || !al16(b.dbias))
     PL_FAIL(PL_EINVAL, "%s: 16-byte alignment (layer below)", who);
-  lo.z = b.z; lo.mean = b.mean; lo.rstd = b.rstd; lo.gamma = b.gamma; lo.bits = b.bits; lo.dz = dz_lo;
-  lo.dgamma = b.dgamma; lo.dbeta = b.dbeta; lo.dbias = b.dbias; lo.kscale = kscale; lo.B = B; lo.H = H; lo.rowbits = b.rowbits ? 1 : 0;
+  lo.z = v.z; lo.mean = v.mean; lo.rstd = v.rstd; lo.gamma = b.gamma; lo.bits = v.bits; lo.dz = dz_lo;
+  lo.dgamma = b.dgamma; lo.dbeta = b.dbeta; lo.dbias = b.dbias; lo.kscale = kscale; lo.B = B; lo.H = H; lo.rowbits = v.tile_bits ? 0 : 1;
   return PL_OK;
 }
 }  // namespace
 
-int launch_small_layer_bwd(const float* dz, const float* W, const float* addend, float* gout, int B, int H, int K,
-                           const SmallBnLayer& below, float kscale, float* dz_lo, hipStream_t s, const float* a_in, float* dW,
-                           const float* x1, float* dW1, int K1, const AdamWRide* adam) {
+int launch_small_layer_bwd(const SmallLayerBwdArgs& a, hipStream_t s) {
+  const int B = a.B, H = a.H, K = a.K;
   if (!small_layer_ok(B, H, K)) PL_FAIL(PL_ESHAPE, "small_layer_bwd: B=%d H=%d K=%d", B, H, K);
-  if (!dz || !W || dz_lo == dz) PL_FAIL(PL_EINVAL, "small_layer_bwd: bad arguments");
-  if (!al16(dz) || !al16(W) || !al16(addend) || !al16(gout)) PL_FAIL(PL_EINVAL, "small_layer_bwd: 16-byte alignment");
+  if (!a.dz || !a.W || a.dz_lo == a.dz) PL_FAIL(PL_EINVAL, "small_layer_bwd: bad arguments");
+  if (!al16(a.dz) || !al16(a.W) || !al16(a.addend) || !al16(a.gout)) PL_FAIL(PL_EINVAL, "small_layer_bwd: 16-byte alignment");
   BwdArgs p = {};
-  PL_TRY(fill_lo(p.lo, below, B, H, kscale, dz_lo, "small_layer_bwd"));
-  p.dz = dz; p.W = W; p.addend = addend; p.gout = gout;
+  PL_TRY(fill_lo(p.lo, a.below, B, H, a.kscale, a.dz_lo, "small_layer_bwd"));
+  p.dz = a.dz; p.W = a.W; p.addend = a.addend; p.gout = a.gout;
   p.B = B; p.H = H; p.K = K;
   p.nblk_dx = H / COLS;
   int extra = 0;
-  if (dW) {
-    if (!a_in || !al16(a_in) || !al16(dW) || (K & 127) || (H & 63)) PL_FAIL(PL_EINVAL, "small_layer_bwd: weight-gradient part (K=%d H=%d)", K, H);
-    p.a_in = a_in; p.dW = dW;
+  if (a.dW) {
+    if (!a.a_in || !al16(a.a_in) || !al16(a.dW) || (K & 127) || (H & 63))
+      PL_FAIL(PL_EINVAL, "small_layer_bwd: weight-gradient part (K=%d H=%d)", K, H);
+    p.a_in = a.a_in; p.dW = a.dW;
     extra = (K / 128) * (H / 64);
   }
-  if (dW1) {
-    if (!x1 || !small_first_ok(K1)) PL_FAIL(PL_EINVAL, "small_layer_bwd: first-layer weight gradient (K1=%d)", K1);
-    p.x1 = x1; p.dW1 = dW1; p.K1 = K1;
+  if (a.dW1) {
+    if (!a.x1 || !small_first_ok(a.K1)) PL_FAIL(PL_EINVAL, "small_layer_bwd: first-layer weight gradient (K1=%d)", a.K1);
+    p.x1 = a.x1; p.dW1 = a.dW1; p.K1 = a.K1;
   }
   p.nblk_dw = extra;
-  if (adam && adam->n > 0) {
-    if (!adam->p || !adam->g || !adam->m || !adam->v || (adam->n & 3) || !al16(adam->p) || !al16(adam->g) || !al16(adam->m) ||
-        !al16(adam->v) || (adam->lr_dev != nullptr) != (adam->t_dev != nullptr))
+  if (a.adam && a.adam->n > 0) {
+    const AdamWRide& r = *a.adam;
+    if (!r.p || !r.g || !r.m || !r.v || (r.n & 3) || !al16(r.p) || !al16(r.g) || !al16(r.m) || !al16(r.v) ||
+        (r.lr_dev != nullptr) != (r.t_dev != nullptr))
       PL_FAIL(PL_EINVAL, "small_layer_bwd: AdamW slice");
-    p.adam = *adam;
-    p.nblk_adam = (int)std::min<int64_t>(kSmallAdamBlocks, (adam->n / 4 + NTHR - 1) / NTHR);
+    p.adam = r;
+    p.nblk_adam = (int)std::min<int64_t>(kSmallAdamBlocks, (r.n / 4 + NTHR - 1) / NTHR);
     extra += p.nblk_adam;
   }
   const dim3 grid(H / COLS + extra), block(NTHR);
-  void* prof = prof_begin_flops(2.0 * B * H * K * (dW ? 2 : 1), s);
+  void* prof = prof_begin_flops(2.0 * B * H * K * (a.dW ? 2 : 1), s);
   switch (K / (NWAVE * 32)) {
     case 1: hipLaunchKernelGGL(small_bwd_kernel<1>, grid, block, 0, s, p); break;
     case 2: hipLaunchKernelGGL(small_bwd_kernel<2>, grid, block, 0, s, p); break;
@@ -1101,30 +1077,29 @@ int launch_small_layer_bwd(const float* dz, const float* W, const float* addend,
 
 int small_mse_partials(int B, int O) { return (B * O + kMseElems - 1) / kMseElems; }
 
-int launch_small_mse(const float* ypart, int NS, int B, int O, const float* bias, const float* tgt, float grad_scale, float* y,
-                     float* dpred, float* mpart, hipStream_t s) {
-  if (!ypart || !tgt || !y || !dpred || !mpart || NS < 1 || B < 1 || B > ROWS || !small_top_ok(O))
+int launch_small_mse(const SmallHeadArgs& a, hipStream_t s) {
+  if (!a.ypart || !a.tgt || !a.y || !a.dpred || !a.mpart || a.NS < 1 || a.B < 1 || a.B > ROWS || !small_top_ok(a.O))
     PL_FAIL(PL_EINVAL, "small_mse: bad arguments");
-  const int np = small_mse_partials(B, O);
-  const float coef = grad_scale * 2.0f / (float)(B * O);
-  hipLaunchKernelGGL(small_mse_kernel, dim3(np), dim3(256), 0, s, ypart, NS, B, O, bias, tgt, coef, y, dpred, mpart);
+  const int np = small_mse_partials(a.B, a.O);
+  const float coef = a.grad_scale * 2.0f / (float)(a.B * a.O);
+  hipLaunchKernelGGL(small_mse_kernel, dim3(np), dim3(256), 0, s, a.ypart, a.NS, a.B, a.O, a.bias, a.tgt, coef, a.y, a.dpred,
+                     a.mpart);
   PL_CHECK_LAUNCH("small_mse");
   return PL_OK;
 }
 
-int launch_small_top_bwd(const float* dy, const float* W2, const float* h, int B, int H, int O, float* gout, float* dW2,
-                         float* db2, const SmallBnLayer& top, float kscale, float* dz_top, hipStream_t s, const float* mpart,
-                         int np, float inv_n, float* loss, uint64_t* tick) {
-  if (!small_layer_ok(B, H, H) || !small_top_ok(O)) PL_FAIL(PL_ESHAPE, "small_top_bwd: B=%d H=%d O=%d", B, H, O);
-  if (!dy || !W2 || !h || !gout || !dW2 || !db2 || !al16(gout) || !al16(h)) PL_FAIL(PL_EINVAL, "small_top_bwd: bad arguments");
+int launch_small_top_bwd(const SmallTopBwdArgs& a, hipStream_t s) {
+  if (!small_layer_ok(a.B, a.H, a.H) || !small_top_ok(a.O)) PL_FAIL(PL_ESHAPE, "small_top_bwd: B=%d H=%d O=%d", a.B, a.H, a.O);
+  if (!a.dy || !a.W2 || !a.h || !a.gout || !a.dW2 || !a.db2 || !al16(a.gout) || !al16(a.h))
+    PL_FAIL(PL_EINVAL, "small_top_bwd: bad arguments");
   TopArgs p = {};
-  PL_TRY(fill_lo(p.lo, top, B, H, kscale, dz_top, "small_top_bwd"));
-  p.dy = dy; p.W2 = W2; p.h = h; p.gout = gout; p.dW2 = dW2; p.db2 = db2; p.B = B; p.H = H; p.O = O;
-  if (loss) {
-    if (!mpart || np < 1) PL_FAIL(PL_EINVAL, "small_top_bwd: loss partials");
-    p.mpart = mpart; p.np = np; p.inv_n = inv_n; p.loss = loss; p.tick = tick;
+  PL_TRY(fill_lo(p.lo, a.top, a.B, a.H, a.kscale, a.dz_top, "small_top_bwd"));
+  p.dy = a.dy; p.W2 = a.W2; p.h = a.h; p.gout = a.gout; p.dW2 = a.dW2; p.db2 = a.db2; p.B = a.B; p.H = a.H; p.O = a.O;
+  if (a.loss) {
+    if (!a.mpart || a.np < 1) PL_FAIL(PL_EINVAL, "small_top_bwd: loss partials");
+    p.mpart = a.mpart; p.np = a.np; p.inv_n = a.inv_n; p.loss = a.loss; p.tick = a.tick;
   }
-  hipLaunchKernelGGL(small_top_bwd_kernel, dim3(H / COLS), dim3(NTHR), 0, s, p);
+  hipLaunchKernelGGL(small_top_bwd_kernel, dim3(a.H / COLS), dim3(NTHR), 0, s, p);
   PL_CHECK_LAUNCH("small_top_bwd");
   return PL_OK;
 }
