@@ -11,7 +11,7 @@ ResNet, the way optim.FlatAdamW does for the lifter:
     their weight / BatchNorm gradient kernels the arena view as output and return None to autograd (`p._pl_grad`, conv._pgrad);
     the first backward of a step overwrites, a second one in the same step (two forward passes: the phase5 Flip branch)
     accumulates.  No `p.grad += dw` launches, no layout copies.
-  * FlatAdam.step(): ONE pl_adamw_flat launch over the whole arena (weight_decay 0 = torch.optim.Adam's default; Adam's
+  * FlatAdam.step(): ONE AdamW launch over the whole arena (weight_decay 0 = torch.optim.Adam's default; Adam's
     coupled L2 decay is not implemented; decoupled_weight_decay=True is torch.optim.AdamW), in torch's single-tensor update order; the 1/world average of a data-parallel sum
     folds into it (grad_scale).  zero_grad() sets .grad to None and launches nothing.
 A torch.optim.Optimizer subclass: LR schedulers and the stock Adam state_dict layout ('step', 'exp_avg', 'exp_avg_sq' per
@@ -23,6 +23,7 @@ import torch
 from torch.autograd.graph import increment_version
 
 from . import _lib, gradclip
+from .optim import FlatOptimizer
 
 
 class ModuleArena:
@@ -81,34 +82,31 @@ def arena_of(module):
     return a
 
 
-class FlatAdam(torch.optim.Optimizer):
+class FlatAdam(FlatOptimizer):
     """torch.optim.Adam(module.parameters(), lr, betas, eps) as one library launch over the module's flat arenas."""
 
     def __init__(self, module, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable=False,
                  decoupled_weight_decay=False, max_grad_norm=None, skip_nonfinite=False):
-        max_grad_norm, skip_nonfinite = gradclip.check_options(max_grad_norm, skip_nonfinite)
         if weight_decay != 0.0 and not decoupled_weight_decay:
             raise NotImplementedError("FlatAdam: Adam's coupled L2 weight decay is not implemented (the reference uses 0); "
                                       "decoupled_weight_decay=True is AdamW")
-        self.arena = arena_of(module)
-        super().__init__(self.arena.params, dict(lr=lr, betas=betas, eps=eps, weight_decay=float(weight_decay),
-                                                 capturable=bool(capturable),
-                                                 decoupled_weight_decay=bool(decoupled_weight_decay),
-                                                 max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite))
-        a = self.arena
+        self.arena = a = arena_of(module)
+        super().__init__(a.params, dict(lr=lr, betas=betas, eps=eps, weight_decay=float(weight_decay),
+                                        capturable=bool(capturable), decoupled_weight_decay=bool(decoupled_weight_decay),
+                                        max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite))
         self._m, self._v = torch.zeros_like(a.flat), torch.zeros_like(a.flat)
-        self._t = 0                      # ATTEMPTED steps (as _t_dev); taken = attempted - the clip record's skipped count
-        self._clip = None                # gradclip.GradClip, created by the first step that clips or skips
-        self._skipped_seen = 0
         dev = a.flat.device
+        # _t / _t_dev: ATTEMPTED steps, as in the base; taken = attempted - the clip record's skipped count
         self._t_dev = torch.zeros(1, dtype=torch.int64, device=dev)           # completed steps (capturable)
-        self._lr_dev = torch.full((1,), float(lr) if not torch.is_tensor(lr) else float(lr), dtype=torch.float32, device=dev)
-        self._lr_host = None
+        self._lr_dev = gradclip.DeviceScalar(dev, lr)                         # what a capturable step reads its lr from
         step = self._t_dev if capturable else torch.tensor(0.0)
         self._step_tensor = step
         for p, o in zip(a.params, a.offsets):
             n = p.numel()
             self.state[p] = {"step": step, "exp_avg": self._m[o:o + n].view(p.shape), "exp_avg_sq": self._v[o:o + n].view(p.shape)}
+
+    def _arenas(self):
+        return self.arena.flat, self.arena.grad
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
@@ -123,32 +121,7 @@ class FlatAdam(torch.optim.Optimizer):
             st["exp_avg"], st["exp_avg_sq"], st["step"] = mv, vv, self._step_tensor
         self._t = t
         self._step_tensor.fill_(t)
-        if self._clip is not None:        # the loaded step counts taken steps: nothing skipped against it
-            self._clip.reset_skipped()
-        self._skipped_seen = 0
-
-    # ---- gradient clipping / non-finite skip (gradclip.py; the gradient arena is not rewritten) -------------------
-    def _clip_state(self):
-        if self._clip is None:
-            self._clip = gradclip.GradClip(self.arena.flat.device)
-        return self._clip
-
-    @property
-    def grad_norm(self):
-        """Device scalar: |grad_scale| * ||g||_2 of the last step that clipped or skipped (no sync)."""
-        return self._clip_state().norm
-
-    @property
-    def clip_coef(self):
-        """Device scalar: the coefficient the last step multiplied its gradient by (no sync)."""
-        return self._clip_state().coef
-
-    def skipped_steps(self):
-        """Steps not taken because their gradient norm was not finite, since construction / load_state_dict (one host read)."""
-        if self._clip is None:
-            return 0
-        self._skipped_seen = self._clip.skipped()
-        return self._skipped_seen
+        self._forget_skipped()
 
     def state_dict(self):
         """'step' reports TAKEN steps (attempted - skipped); the live state keeps counting attempts (capturable: on the
@@ -163,6 +136,9 @@ class FlatAdam(torch.optim.Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None, grad_scale=1.0):
+        """The norm pass when max_grad_norm / skip_nonfinite are on, then one AdamW launch per run of parameters that hold a
+        gradient (none anywhere: no launch).  The counters tick every attempt; the kernels subtract the record's skipped
+        count.  capturable: t and lr are read on the device and the counter ticks behind the update."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -172,67 +148,17 @@ class FlatAdam(torch.optim.Optimizer):
             raise _lib.PoseliftError("FlatAdam: the module's parameters left their arena (.to() / .data reassigned): "
                                      "build the optimizer after moving the module")
         runs = a.gather_grads()
-        L, lr = _lib.lib(), g["lr"]
-        wd = float(g["weight_decay"]) if g.get("decoupled_weight_decay", False) else 0.0
-        cap = bool(g.get("capturable", False))
-        max_norm, skip = gradclip.check_options(g.get("max_grad_norm"), g.get("skip_nonfinite", False))
-        if (max_norm is not None or skip) and runs:
-            return self._step_clipped(runs, lr, wd, cap, grad_scale, max_norm, skip, loss)
-        with _lib.on_device(a.flat.device):
-            if cap:
-                if torch.is_tensor(lr):
-                    lr_ptr = lr.data_ptr()                  # (a device scalar the caller changes between replays)
-                else:
-                    if self._lr_host != float(lr) and not torch.cuda.is_current_stream_capturing():
-                        self._lr_dev.fill_(float(lr)); self._lr_host = float(lr)
-                    lr_ptr = self._lr_dev.data_ptr()
-                for lo, hi in runs:
-                    _lib.check(L.pl_adamw_flat_dev(a.flat.data_ptr() + 4 * lo, a.grad.data_ptr() + 4 * lo, self._m.data_ptr() + 4 * lo,
-                                                   self._v.data_ptr() + 4 * lo, hi - lo, lr_ptr, float(g["betas"][0]),
-                                                   float(g["betas"][1]), float(g["eps"]), wd, 1, self._t_dev.data_ptr(),
-                                                   float(grad_scale), _lib.current_stream_ptr()), "pl_adamw_flat_dev")
-                _lib.check(L.pl_counter_add(self._t_dev.data_ptr(), 1, _lib.current_stream_ptr()), "pl_counter_add")
-            else:
-                self._t += 1
-                for lo, hi in runs:
-                    _lib.check(L.pl_adamw_flat(a.flat.data_ptr() + 4 * lo, a.grad.data_ptr() + 4 * lo, self._m.data_ptr() + 4 * lo,
-                                               self._v.data_ptr() + 4 * lo, hi - lo, float(lr), float(g["betas"][0]),
-                                               float(g["betas"][1]), float(g["eps"]), wd, self._t, float(grad_scale),
-                                               _lib.current_stream_ptr()), "pl_adamw_flat")
-                self._step_tensor.fill_(float(self._t))
-        increment_version(a.params)
-        return loss
-
-    def _lr_ptr(self, lr):
-        if torch.is_tensor(lr):
-            return lr.data_ptr()                            # (a device scalar the caller changes between replays)
-        if self._lr_host != float(lr) and not torch.cuda.is_current_stream_capturing():
-            self._lr_dev.fill_(float(lr)); self._lr_host = float(lr)
-        return self._lr_dev.data_ptr()
-
-    def _step_clipped(self, runs, lr, wd, cap, grad_scale, max_norm, skip, loss):
-        """step() with max_grad_norm / skip_nonfinite: the norm pass over the runs that hold a gradient, then the same
-        launches with its record.  The counters tick every attempt; the kernels subtract the record's skipped count."""
-        a, g, L = self.arena, self.param_groups[0], _lib.lib()
-        b1, b2, eps = float(g["betas"][0]), float(g["betas"][1]), float(g["eps"])
-        with _lib.on_device(a.flat.device):
-            clip = self._clip_state()
-            clip.launch(a.grad, runs, grad_scale, max_norm, skip, from_device=cap)
-            if cap:
-                lr_ptr = self._lr_ptr(lr)
-                for lo, hi in runs:
-                    _lib.check(L.pl_adamw_flat_dev_clip(a.flat.data_ptr() + 4 * lo, a.grad.data_ptr() + 4 * lo,
-                                                        self._m.data_ptr() + 4 * lo, self._v.data_ptr() + 4 * lo, hi - lo, lr_ptr,
-                                                        b1, b2, eps, wd, 1, self._t_dev.data_ptr(), float(grad_scale), clip.ptr,
-                                                        _lib.current_stream_ptr()), "pl_adamw_flat_dev_clip")
-                _lib.check(L.pl_counter_add(self._t_dev.data_ptr(), 1, _lib.current_stream_ptr()), "pl_counter_add")
-            else:
-                self._t += 1
-                for lo, hi in runs:
-                    _lib.check(L.pl_adamw_flat_clip(a.flat.data_ptr() + 4 * lo, a.grad.data_ptr() + 4 * lo,
-                                                    self._m.data_ptr() + 4 * lo, self._v.data_ptr() + 4 * lo, hi - lo, float(lr),
-                                                    b1, b2, eps, wd, self._t, float(grad_scale), clip.ptr,
-                                                    _lib.current_stream_ptr()), "pl_adamw_flat_clip")
-                self._step_tensor.fill_(float(self._t))
+        lr = g["lr"]
+        wd = g["weight_decay"] if g.get("decoupled_weight_decay", False) else 0.0
+        if g.get("capturable", False):
+            # (a tensor lr: a device scalar the caller changes between replays)
+            lr_ptr = lr.data_ptr() if torch.is_tensor(lr) else self._lr_dev.refresh(lr)
+            self._launch_adamw(runs, 0.0, lr_ptr, 1, self._t_dev.data_ptr(), wd, grad_scale)
+            with _lib.on_device(a.flat.device):
+                _lib.check(_lib.lib().pl_counter_add(self._t_dev.data_ptr(), 1, _lib.current_stream_ptr()), "pl_counter_add")
+        else:
+            self._t += 1
+            self._launch_adamw(runs, lr, None, self._t, None, wd, grad_scale)
+            self._step_tensor.fill_(float(self._t))
         increment_version(a.params)
         return loss

@@ -1044,13 +1044,11 @@ static int bwd_impl(const PLDesc* d, const float* x, const float* dy, int64_t B,
   if (adam) {
     // what no backward launch carried: the bottom of the arena (first layer and the first residual Linear) -- or all of it
     const int64_t n = c.adam_rides ? (w.L > 1 ? P.off[4 * 1 + 1] : P.total) : P.total;
-    float* p = const_cast<float*>(d->params);
-    if (adam->lr_dev)
-      PL_TRY(pl_adamw_flat_dev(p, grads, adam->m, adam->v, n, adam->lr_dev, adam->beta1, adam->beta2, adam->eps,
-                               adam->weight_decay, adam->t, adam->t_dev, 1.0f, stream));
-    else
-      PL_TRY(pl_adamw_flat(p, grads, adam->m, adam->v, n, adam->lr, adam->beta1, adam->beta2, adam->eps, adam->weight_decay,
-                           adam->t, 1.0f, stream));
+    // (the same fields as ride(); pl_lifter_train_step checked that lr_dev and t_dev go together)
+    const AdamWArgs a = {const_cast<float*>(d->params), grads, adam->m, adam->v, n,
+                         {adam->lr, adam->beta1, adam->beta2, adam->eps, adam->weight_decay, 1.0f, adam->t, adam->lr_dev,
+                          adam->t_dev}};
+    PL_TRY(launch_adamw(a, c.s));
   }
   return PL_OK;
 }

@@ -1762,35 +1762,51 @@ extern "C" int pl_mpjpe_accum(const float* pred, const float* tgt, int64_t B, in
 // (same-box sweep, B = 64 step: 256 / 512 / 1024 / 2048 blocks -> 0.1297 / 0.1289 / 0.1295 / 0.1304 ms; B = 4096: no difference)
 constexpr int kAdamBlocks = 512;
 
-static int adamw_launch(float* p, const float* g, float* m, float* v, int64_t n, const AdamWIn& in, void* stream) {
-  if (!p || !g || !m || !v) PL_FAIL(PL_EINVAL, "pl_adamw_flat: null pointer");
-  if (n <= 0 || in.t < (in.t_dev ? 0 : 1)) PL_FAIL(PL_ESHAPE, "pl_adamw_flat: n=%lld t=%lld", (long long)n, (long long)in.t);
+int pl::launch_adamw(const AdamWArgs& a, hipStream_t s) {
+  const AdamWIn& in = a.in;
+  if (!a.p || !a.g || !a.m || !a.v) PL_FAIL(PL_EINVAL, "pl_adamw_flat: null pointer");
+  if (a.n <= 0 || in.t < (in.t_dev ? 0 : 1)) PL_FAIL(PL_ESHAPE, "pl_adamw_flat: n=%lld t=%lld", (long long)a.n, (long long)in.t);
   if (reinterpret_cast<uintptr_t>(in.clip) & 7) PL_FAIL(PL_EINVAL, "pl_adamw_flat: clip record must be 8-byte aligned");
-  const int vec = aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v);
-  int64_t work = vec ? (n >> 2) : n;
+  const int vec = aligned16(a.p) && aligned16(a.g) && aligned16(a.m) && aligned16(a.v);
+  int64_t work = vec ? (a.n >> 2) : a.n;
   int blocks = (int)((work + NTHR - 1) / NTHR);
   if (blocks > kAdamBlocks) blocks = kAdamBlocks;
   if (blocks < 1) blocks = 1;
-  if (in.clip) hipLaunchKernelGGL(adamw_kernel<true>, dim3(blocks), dim3(NTHR), 0, (hipStream_t)stream, p, g, m, v, n, in, vec);
-  else hipLaunchKernelGGL(adamw_kernel<false>, dim3(blocks), dim3(NTHR), 0, (hipStream_t)stream, p, g, m, v, n, in, vec);
+  if (in.clip) hipLaunchKernelGGL(adamw_kernel<true>, dim3(blocks), dim3(NTHR), 0, s, a.p, a.g, a.m, a.v, a.n, in, vec);
+  else hipLaunchKernelGGL(adamw_kernel<false>, dim3(blocks), dim3(NTHR), 0, s, a.p, a.g, a.m, a.v, a.n, in, vec);
   PL_CHECK_LAUNCH("adamw");
   return PL_OK;
 }
 
-static AdamWIn adamw_in(float lr, float beta1, float beta2, float eps, float wd, float gscale, int64_t t,
-                        const float* lr_dev, const uint64_t* t_dev) {
-  AdamWIn in = {};
-  in.lr = lr; in.beta1 = beta1; in.beta2 = beta2; in.eps = eps; in.wd = wd; in.gscale = gscale; in.t = t;
-  in.lr_dev = lr_dev; in.t_dev = t_dev;
-  return in;
+// PLAdamWPlanes (NULL or no segment: nothing) -> the plane fields of a.in, checked against a's arenas
+static int adamw_planes(const PLAdamWPlanes* planes, AdamWArgs& a) {
+  if (!planes || planes->nseg <= 0) return PL_OK;
+  AdamWIn& in = a.in;
+  if (planes->nseg > PL_ADAMW_MAX_SEGS || (planes->kind != 1 && planes->kind != 2) || !(planes->scale > 0.f))
+    PL_FAIL(PL_EINVAL, "pl_adamw_flat_planes: bad plane description");
+  if (!(aligned16(a.p) && aligned16(a.g) && aligned16(a.m) && aligned16(a.v)) || (a.n & 3))
+    PL_FAIL(PL_EINVAL, "pl_adamw_flat_planes: arenas must be 16-byte aligned, n %% 4 == 0");
+  in.nseg = planes->nseg; in.kind = planes->kind; in.pscale = planes->scale;
+  in.range = planes->kind == 2 ? range_record() : nullptr;
+  for (int q = 0; q < planes->nseg; ++q) {
+    const PLAdamWSeg& sg = planes->seg[q];
+    if (sg.offset < 0 || sg.numel <= 0 || (sg.offset & 3) || (sg.numel & 3) || sg.offset + sg.numel > a.n || !sg.h ||
+        (planes->kind == 2 && !sg.l) || (reinterpret_cast<uintptr_t>(sg.h) & 7) || (reinterpret_cast<uintptr_t>(sg.l) & 7))
+      PL_FAIL(PL_EINVAL, "pl_adamw_flat_planes: segment %d", q);
+    in.seg_off[q] = sg.offset; in.seg_n[q] = sg.numel;
+    in.seg_h[q] = static_cast<unsigned short*>(sg.h); in.seg_l[q] = static_cast<unsigned short*>(sg.l);
+  }
+  return PL_OK;
 }
 
+// The six entry points: the three _clip ones fill an AdamWArgs (the AdamWIn fields they do not name stay zero), the plain
+// ones are their _clip twin with no record.
 extern "C" int pl_adamw_flat_clip(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
                                   float beta2, float eps, float weight_decay, int64_t t, float grad_scale,
                                   const PLClipRecord* clip, void* stream) {
-  AdamWIn in = adamw_in(lr, beta1, beta2, eps, weight_decay, grad_scale, t, nullptr, nullptr);
-  in.clip = clip;
-  return adamw_launch(p, g, m, v, n, in, stream);
+  AdamWArgs a = {p, g, m, v, n, {lr, beta1, beta2, eps, weight_decay, grad_scale, t}};
+  a.in.clip = clip;
+  return launch_adamw(a, (hipStream_t)stream);
 }
 
 extern "C" int pl_adamw_flat(float* p, const float* g, float* m, float* v, int64_t n, float lr,
@@ -1803,9 +1819,9 @@ extern "C" int pl_adamw_flat_dev_clip(float* p, const float* g, float* m, float*
                                       float beta1, float beta2, float eps, float weight_decay, int64_t t_base,
                                       const uint64_t* t_dev, float grad_scale, const PLClipRecord* clip, void* stream) {
   if (!lr_dev || !t_dev) PL_FAIL(PL_EINVAL, "pl_adamw_flat_dev: null lr / t pointer");
-  AdamWIn in = adamw_in(0.f, beta1, beta2, eps, weight_decay, grad_scale, t_base, lr_dev, t_dev);
-  in.clip = clip;
-  return adamw_launch(p, g, m, v, n, in, stream);
+  AdamWArgs a = {p, g, m, v, n, {0.f, beta1, beta2, eps, weight_decay, grad_scale, t_base, lr_dev, t_dev}};
+  a.in.clip = clip;
+  return launch_adamw(a, (hipStream_t)stream);
 }
 
 extern "C" int pl_adamw_flat_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* lr_dev,
@@ -1815,37 +1831,22 @@ extern "C" int pl_adamw_flat_dev(float* p, const float* g, float* m, float* v, i
                                 stream);
 }
 
-extern "C" int pl_adamw_flat_planes(float* p, const float* g, float* m, float* v, int64_t n, float lr, const float* lr_dev,
-                                    float beta1, float beta2, float eps, float weight_decay, int64_t t,
-                                    const uint64_t* t_dev, float grad_scale, const PLAdamWPlanes* planes, void* stream) {
-  return pl_adamw_flat_planes_clip(p, g, m, v, n, lr, lr_dev, beta1, beta2, eps, weight_decay, t, t_dev, grad_scale, planes,
-                                   nullptr, stream);
-}
-
 extern "C" int pl_adamw_flat_planes_clip(float* p, const float* g, float* m, float* v, int64_t n, float lr,
                                          const float* lr_dev, float beta1, float beta2, float eps, float weight_decay,
                                          int64_t t, const uint64_t* t_dev, float grad_scale, const PLAdamWPlanes* planes,
                                          const PLClipRecord* clip, void* stream) {
   if ((lr_dev != nullptr) != (t_dev != nullptr)) PL_FAIL(PL_EINVAL, "pl_adamw_flat_planes: lr_dev and t_dev go together");
-  AdamWIn in = adamw_in(lr, beta1, beta2, eps, weight_decay, grad_scale, t, lr_dev, t_dev);
-  in.clip = clip;
-  if (planes && planes->nseg > 0) {
-    if (planes->nseg > PL_ADAMW_MAX_SEGS || (planes->kind != 1 && planes->kind != 2) || !(planes->scale > 0.f))
-      PL_FAIL(PL_EINVAL, "pl_adamw_flat_planes: bad plane description");
-    if (!(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v)) || (n & 3))
-      PL_FAIL(PL_EINVAL, "pl_adamw_flat_planes: arenas must be 16-byte aligned, n %% 4 == 0");
-    in.nseg = planes->nseg; in.kind = planes->kind; in.pscale = planes->scale;
-    in.range = planes->kind == 2 ? range_record() : nullptr;
-    for (int q = 0; q < planes->nseg; ++q) {
-      const PLAdamWSeg& sg = planes->seg[q];
-      if (sg.offset < 0 || sg.numel <= 0 || (sg.offset & 3) || (sg.numel & 3) || sg.offset + sg.numel > n || !sg.h ||
-          (planes->kind == 2 && !sg.l) || (reinterpret_cast<uintptr_t>(sg.h) & 7) || (reinterpret_cast<uintptr_t>(sg.l) & 7))
-        PL_FAIL(PL_EINVAL, "pl_adamw_flat_planes: segment %d", q);
-      in.seg_off[q] = sg.offset; in.seg_n[q] = sg.numel;
-      in.seg_h[q] = static_cast<unsigned short*>(sg.h); in.seg_l[q] = static_cast<unsigned short*>(sg.l);
-    }
-  }
-  return adamw_launch(p, g, m, v, n, in, stream);
+  AdamWArgs a = {p, g, m, v, n, {lr, beta1, beta2, eps, weight_decay, grad_scale, t, lr_dev, t_dev}};
+  a.in.clip = clip;
+  PL_TRY(adamw_planes(planes, a));
+  return launch_adamw(a, (hipStream_t)stream);
+}
+
+extern "C" int pl_adamw_flat_planes(float* p, const float* g, float* m, float* v, int64_t n, float lr, const float* lr_dev,
+                                    float beta1, float beta2, float eps, float weight_decay, int64_t t,
+                                    const uint64_t* t_dev, float grad_scale, const PLAdamWPlanes* planes, void* stream) {
+  return pl_adamw_flat_planes_clip(p, g, m, v, n, lr, lr_dev, beta1, beta2, eps, weight_decay, t, t_dev, grad_scale, planes,
+                                   nullptr, stream);
 }
 
 // *counter += delta, one thread: the step counter of an optimizer whose step is replayed from a hipGraph (pl_adamw_flat_dev

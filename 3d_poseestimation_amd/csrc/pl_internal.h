@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/poselift.h"
+#include "adamw.h"
 #include "philox.h"
 
 namespace pl {
@@ -416,6 +417,17 @@ int launch_colsum_partial(const float* X, int rows, int cols, float* part, hipSt
 // eval-mode fold: scale = gamma*rsqrt(rv+eps), shift = (bias - rm)*scale + beta  (bn) or 1, bias
 int launch_bn_fold_eval(const float* bias, const BnParams* bn, int H, float* scale, float* shift, hipStream_t s);
 int launch_fill(float* p, int64_t n, float v, hipStream_t s);
+// the flat AdamW step over p, g, m, v [n] (adamw_kernel's only launch site).  in: the kernel's own argument block (adamw.h);
+// lr_dev / t_dev, the plane fields (adamw_planes) and the clip record are the optional parts, zero when absent
+struct AdamWArgs {
+  float* p;
+  const float* g;
+  float* m;
+  float* v;
+  int64_t n;
+  AdamWIn in;
+};
+int launch_adamw(const AdamWArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------------------------
 // skinny layers (skinny.hip): 34 -> H and H -> 51, MFMA straight from registers

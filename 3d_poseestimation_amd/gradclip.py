@@ -8,7 +8,7 @@ steps and leaves p, m, v untouched on a skipped step.  Nothing synchronises, so 
 train.GraphedTrainStep / GraphedModuleStep.  The gradient arena is NOT rewritten: unlike clip_grad_norm_, `p.grad` keeps the
 unclipped gradient.
 
-GradClip is the state one optimizer keeps for this (optim.FlatAdamW, arena.FlatAdam)."""
+GradClip is the state one optimizer keeps for this (optim.FlatOptimizer: FlatAdamW, arena.FlatAdam)."""
 import torch
 
 from . import _lib
@@ -21,6 +21,23 @@ def check_options(max_grad_norm, skip_nonfinite):
     return max_grad_norm, bool(skip_nonfinite)
 
 
+class DeviceScalar:
+    """A float32 device scalar that captured launches read (lr, max_norm), with the value it holds cached on the host:
+    refresh(value) returns its address, refilling it only when the value changed and never while a capture is under way (the
+    captured launches then read what it already held)."""
+
+    def __init__(self, device, value=None):
+        self._host = None if value is None else float(value)
+        self.tensor = torch.full((1,), self._host or 0.0, dtype=torch.float32, device=device)
+
+    def refresh(self, value):
+        v = float(value)
+        if self._host != v and not torch.cuda.is_current_stream_capturing():
+            self.tensor.fill_(v)
+            self._host = v
+        return self.tensor.data_ptr()
+
+
 class GradClip:
     def __init__(self, device):
         self.device = device
@@ -29,8 +46,7 @@ class GradClip:
         self.norm, self.coef = f[0], f[1]
         self._skipped = self.record.view(torch.int64)[2]
         self._scratch = None
-        self._max_norm_dev = torch.zeros(1, dtype=torch.float32, device=device)
-        self._max_norm_host = None
+        self._max_norm_dev = DeviceScalar(device)       # what the captured norm pass reads
         self._ranges, self._ranges_key = None, None
 
     @property
@@ -65,20 +81,13 @@ class GradClip:
         clip = max_norm is not None
         dev_ptr = None
         if clip and from_device:
-            if torch.is_tensor(max_norm):
-                dev_ptr = max_norm.data_ptr()
-            else:
-                self.refresh_max_norm(max_norm)
-                dev_ptr = self._max_norm_dev.data_ptr()
+            dev_ptr = max_norm.data_ptr() if torch.is_tensor(max_norm) else self._max_norm_dev.refresh(max_norm)
         rc = L.pl_grad_norm_clip(grads.data_ptr(), grads.numel(), self._ranges, len(runs), float(grad_scale), int(clip),
                                  float(max_norm) if clip and dev_ptr is None else 0.0, dev_ptr, int(bool(skip_nonfinite)),
                                  self.ptr, self._scratch.data_ptr(), _lib.current_stream_ptr())
         _lib.check(rc, "pl_grad_norm_clip")
 
-    def refresh_max_norm(self, max_norm):
-        """The device scalar the captured norm pass reads, as _lr_dev for the learning rate."""
-        m = float(max_norm)
-        if self._max_norm_host != m and not torch.cuda.is_current_stream_capturing():
-            self._max_norm_dev.fill_(m)
-            self._max_norm_host = m
-
+    def refresh(self, max_norm):
+        """Before a graph replay: bring the device scalar its captured norm pass reads up to date."""
+        if max_norm is not None and not torch.is_tensor(max_norm):
+            self._max_norm_dev.refresh(max_norm)

@@ -256,7 +256,7 @@ class LinearModel(nn.Module):
             self._wplanes_ver = key
 
     def adamw_plane_segments(self):
-        """PLAdamWPlanes for pl_adamw_flat_planes, or None: where the weight planes of each 1024-wide Linear go."""
+        """PLAdamWPlanes for FlatAdamW._launch, or None: where the weight planes of each 1024-wide Linear go."""
         if self._wplanes is None:
             return None
         L = _lib.lib()

@@ -20,21 +20,114 @@ from torch.autograd.graph import increment_version
 from . import _lib, gradclip
 
 
-class FlatAdamW(torch.optim.Optimizer):
+class FlatOptimizer(torch.optim.Optimizer):
+    """What FlatAdamW (the lifter's arenas) and arena.FlatAdam (any module's) share: the max_grad_norm / skip_nonfinite options
+    and their device state, and the one place an AdamW launch is issued.  A subclass provides _arenas() -> (parameter arena,
+    gradient arena) and the moment arenas self._m / self._v beside them."""
+
+    def __init__(self, params, defaults):
+        defaults["max_grad_norm"], defaults["skip_nonfinite"] = gradclip.check_options(defaults["max_grad_norm"],
+                                                                                       defaults["skip_nonfinite"])
+        super().__init__(params, defaults)
+        self._t = 0                      # ATTEMPTED steps; taken = _t - (the record's skipped count, on the device)
+        self._clip = None                # gradclip.GradClip, created by the first step that clips or skips
+        self._skipped_seen = 0           # the device's skipped count at the last host read
+
+    def _clip_options(self):
+        """(max_grad_norm or None, skip_nonfinite) of this step: param_groups[0], changeable between steps like lr."""
+        g = self.param_groups[0]
+        return gradclip.check_options(g.get("max_grad_norm"), g.get("skip_nonfinite", False))
+
+    def _clipping(self):
+        m, skip = self._clip_options()
+        return m is not None or skip
+
+    def _clip_state(self):
+        dev = self._arenas()[0].device
+        if self._clip is None or self._clip.device != dev:
+            self._clip = gradclip.GradClip(dev)
+            self._skipped_seen = 0
+        return self._clip
+
+    @property
+    def grad_norm(self):
+        """Device scalar: |grad_scale| * ||g||_2 of the last step that clipped or skipped (no sync)."""
+        return self._clip_state().norm
+
+    @property
+    def clip_coef(self):
+        """Device scalar: the coefficient the last step multiplied its gradient by (no sync)."""
+        return self._clip_state().coef
+
+    def skipped_steps(self):
+        """Steps not taken because their gradient norm was not finite, since construction / load_state_dict (one host read)."""
+        if self._clip is None:
+            return 0
+        self._skipped_seen = self._clip.skipped()
+        self._step_tensor_fill()
+        return self._skipped_seen
+
+    def _step_tensor_fill(self):
+        """(FlatAdamW: its host step tensor reports taken steps, so it follows the skipped count)"""
+
+    def _forget_skipped(self):
+        """load_state_dict: the loaded step counts taken steps, nothing is skipped against it."""
+        if self._clip is not None:
+            self._clip.reset_skipped()
+        self._skipped_seen = 0
+
+    def _capture_state(self):
+        """The optimizer's tensors a captured step writes: what a capture that warms up with a real step snapshots and
+        restores (train.GraphedTrainStep)."""
+        return [self._m, self._v] + ([self._clip_state().record] if self._clipping() else [])
+
+    def _replay_refresh(self):
+        """Before a capture and before every replay: bring the device scalars the captured launches read (max_norm) up to date.
+        Returns (clips, skips): whether the step has a norm pass is baked into a capture, the values are not."""
+        g = self.param_groups[0]
+        max_norm, skip = g.get("max_grad_norm"), bool(g.get("skip_nonfinite", False))
+        if max_norm is not None:
+            self._clip_state().refresh(gradclip.check_options(max_norm, skip)[0])
+        return max_norm is not None, skip
+
+    def _launch_adamw(self, runs, lr, lr_ptr, t, t_ptr, weight_decay, grad_scale, planes=None):
+        """THE AdamW launch: one pl_adamw_flat_planes_clip per [lo, hi) run of the arenas, every optional part absent = NULL
+        (lr by value or *lr_ptr, t or t + *t_ptr, planes, the clip record).  With max_grad_norm / skip_nonfinite the norm pass
+        over the same runs goes first and every launch takes its record.  No run: nothing is launched."""
+        if not runs:
+            return
+        flat, grads = self._arenas()
+        g = self.param_groups[0]
+        b1, b2, eps = float(g["betas"][0]), float(g["betas"][1]), float(g["eps"])
+        max_norm, skip = self._clip_options()
+        with _lib.on_device(flat.device):
+            record = None
+            if max_norm is not None or skip:
+                clip = self._clip_state()
+                clip.launch(grads, runs, grad_scale, max_norm, skip, from_device=lr_ptr is not None)
+                record = clip.ptr
+            adamw = _lib.lib().pl_adamw_flat_planes_clip
+            planes = _lib.ctypes.byref(planes) if planes is not None else None
+            for lo, hi in runs:
+                rc = adamw(flat.data_ptr() + 4 * lo, grads.data_ptr() + 4 * lo, self._m.data_ptr() + 4 * lo,
+                           self._v.data_ptr() + 4 * lo, hi - lo, float(lr), lr_ptr, b1, b2, eps, float(weight_decay), int(t), t_ptr,
+                           float(grad_scale), planes, record, _lib.current_stream_ptr())
+                _lib.check(rc, "pl_adamw_flat_planes_clip")
+
+
+class FlatAdamW(FlatOptimizer):
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None,
                  skip_nonfinite=False):
         if not hasattr(model, "flat_params"):
             raise TypeError("FlatAdamW drives a 3d_poseestimation_amd LinearModel")
         self._model = model
-        max_grad_norm, skip_nonfinite = gradclip.check_options(max_grad_norm, skip_nonfinite)
-        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
-                        skip_nonfinite=skip_nonfinite)
-        super().__init__(list(model._param_list), defaults)
-        self._t = 0                      # ATTEMPTED steps; taken = _t - (the record's skipped count, on the device)
-        self._clip = None                # gradclip.GradClip, created by the first step that clips or skips
-        self._skipped_seen = 0           # the device's skipped count at the last host read
+        super().__init__(list(model._param_list), dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                                       max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite))
         self._m = self._v = None
         self._bound_arena = None
+
+    def _arenas(self):
+        return self._model.flat_params, self._model.flat_grads
 
     def _bind(self):
         """(Re)create flat moment arenas next to the model's parameter arena and expose them
@@ -79,40 +172,6 @@ class FlatAdamW(torch.optim.Optimizer):
                 runs.append((s.offset, end))
         return runs
 
-    # ---- gradient clipping / non-finite skip (gradclip.py) ---------------------------------------------------
-    def _clip_options(self):
-        """(max_grad_norm or None, skip_nonfinite) of this step: param_groups[0], changeable between steps like lr."""
-        g = self.param_groups[0]
-        return gradclip.check_options(g.get("max_grad_norm"), g.get("skip_nonfinite", False))
-
-    def _clipping(self):
-        m, skip = self._clip_options()
-        return m is not None or skip
-
-    def _clip_state(self):
-        if self._clip is None or self._clip.device != self._model.flat_params.device:
-            self._clip = gradclip.GradClip(self._model.flat_params.device)
-            self._skipped_seen = 0
-        return self._clip
-
-    @property
-    def grad_norm(self):
-        """Device scalar: |grad_scale| * ||g||_2 of the last step that clipped or skipped (no sync)."""
-        return self._clip_state().norm
-
-    @property
-    def clip_coef(self):
-        """Device scalar: the coefficient the last step multiplied its gradient by (no sync)."""
-        return self._clip_state().coef
-
-    def skipped_steps(self):
-        """Steps not taken because their gradient norm was not finite, since construction / load_state_dict (one host read)."""
-        if self._clip is None:
-            return 0
-        self._skipped_seen = self._clip.skipped()
-        self._step_tensor_fill()
-        return self._skipped_seen
-
     def _step_tensor_fill(self):
         if getattr(self, "_step_tensor", None) is not None:
             self._step_tensor.fill_(float(self._t - self._skipped_seen))
@@ -126,9 +185,7 @@ class FlatAdamW(torch.optim.Optimizer):
         super().load_state_dict(state_dict)
         self._bound_arena = None          # loaded tensors are copies: re-bind into the arenas
         self._t = 0
-        if self._clip is not None:        # the loaded step counts taken steps: nothing skipped against it
-            self._clip.reset_skipped()
-        self._skipped_seen = 0
+        self._forget_skipped()
         self._bind()
 
     @torch.no_grad()
@@ -138,48 +195,23 @@ class FlatAdamW(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         self._bind()
-        model = self._model
-        flat, grads = model.flat_params, model.flat_grads
-        _lib.require_device_tensor(flat, "parameters")
-        g = self.param_groups[0]
+        _lib.require_device_tensor(self._model.flat_params, "parameters")
         self._t += 1
-        self._launch(float(g["lr"]), None, self._t, None, grad_scale)
+        self._launch(float(self.param_groups[0]["lr"]), None, self._t, None, grad_scale)
         self._step_tensor_fill()
         return loss
 
     def _launch(self, lr, lr_dev, t, t_dev, grad_scale):
-        """One pl_adamw_flat_planes launch per run of active tensors.  With the whole arena active (the normal case)
-        the same launch refreshes the model's persistent GEMM weight planes while the new parameters are in registers.
-        Returns whether it did.  With max_grad_norm / skip_nonfinite the norm pass over the same runs goes first and every
-        launch takes its record (a skipped step still writes the planes, from the unchanged parameters: marking them
-        current below stays right)."""
+        """The step over the active ranges.  With the whole arena active (the normal case) the same launch refreshes the
+        model's persistent GEMM weight planes while the new parameters are in registers.  Returns whether it did.  (A step
+        skipped for a non-finite gradient still writes the planes, from the unchanged parameters: marking them current
+        below stays right.)"""
         model = self._model
-        flat, grads = model.flat_params, model.flat_grads
-        g = self.param_groups[0]
         ranges = self._active_ranges()
-        planes = model.adamw_plane_segments() if ranges == [(0, flat.numel())] else None
-        max_norm, skip = self._clip_options()
-        with _lib.on_device(flat.device):
-            if max_norm is None and not skip:
-                for lo, hi in ranges:
-                    rc = _lib.lib().pl_adamw_flat_planes(
-                        flat.data_ptr() + 4 * lo, grads.data_ptr() + 4 * lo, self._m.data_ptr() + 4 * lo,
-                        self._v.data_ptr() + 4 * lo, hi - lo, float(lr), lr_dev.data_ptr() if lr_dev is not None else None,
-                        float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), int(t),
-                        t_dev.data_ptr() if t_dev is not None else None, float(grad_scale),
-                        _lib.ctypes.byref(planes) if planes is not None else None, _lib.current_stream_ptr())
-                    _lib.check(rc, "pl_adamw_flat_planes")
-            else:
-                clip = self._clip_state()
-                clip.launch(grads, ranges, grad_scale, max_norm, skip, from_device=lr_dev is not None)
-                for lo, hi in ranges:
-                    rc = _lib.lib().pl_adamw_flat_planes_clip(
-                        flat.data_ptr() + 4 * lo, grads.data_ptr() + 4 * lo, self._m.data_ptr() + 4 * lo,
-                        self._v.data_ptr() + 4 * lo, hi - lo, float(lr), lr_dev.data_ptr() if lr_dev is not None else None,
-                        float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), int(t),
-                        t_dev.data_ptr() if t_dev is not None else None, float(grad_scale),
-                        _lib.ctypes.byref(planes) if planes is not None else None, clip.ptr, _lib.current_stream_ptr())
-                    _lib.check(rc, "pl_adamw_flat_planes_clip")
+        planes = model.adamw_plane_segments() if ranges == [(0, model.flat_params.numel())] else None
+        self._launch_adamw(ranges, lr, lr_dev.data_ptr() if lr_dev is not None else None, t,
+                           t_dev.data_ptr() if t_dev is not None else None, self.param_groups[0]["weight_decay"], grad_scale,
+                           planes)
         increment_version(model._param_list)
         if planes is not None:                # the planes are those of the parameters just written
             model._wplanes_ver = model._planes_key()
@@ -205,6 +237,10 @@ class FlatAdamW(torch.optim.Optimizer):
         caller's business (a captured launch runs many times).  Returns whether the launch refreshes the weight planes."""
         self._bind()
         return self._launch(0.0, lr_dev, t_base, t_dev, grad_scale)
+
+    def _capture_state(self):
+        self._bind()
+        return super()._capture_state()
 
     def _advance_host(self, n=1):
         self._t += n

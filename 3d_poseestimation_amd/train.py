@@ -10,7 +10,7 @@ All arithmetic is in libposelift.so; tensors must live on the ROCm device.
 import torch
 from torch.autograd.graph import increment_version
 
-from . import _lib
+from . import _lib, gradclip
 
 
 class _MSEFn(torch.autograd.Function):
@@ -194,7 +194,7 @@ class GraphedTrainStep:
         loss, y_hat = step(x, y)            # same results, bit for bit, as train_step(model, optimizer, x, y)
 
     What changes from step to step lives in device memory and is advanced INSIDE the graph: the dropout stream's
-    step number and AdamW's t come from one device counter (PLDesc.step_dev, pl_adamw_flat_dev), the learning rate
+    step number and AdamW's t come from one device counter (PLDesc.step_dev, the AdamW launch's t_dev), the learning rate
     from a device scalar the host refreshes when a scheduler changed it.  Single process (a captured RCCL
     all-reduce is not wired); LinearModel + FlatAdamW; fixed batch shape."""
 
@@ -210,33 +210,27 @@ class GraphedTrainStep:
         self._y = y2.reshape(B, -1).contiguous().clone()
         self._out_shape = tuple(y2.shape)
         self._tick = torch.zeros(1, dtype=torch.int64, device=dev)          # completed replays
-        self._lr = float(optimizer.param_groups[0]["lr"])
-        self._lr_dev = torch.full((1,), self._lr, dtype=torch.float32, device=dev)
-        optimizer._bind()
-        # max_grad_norm / skip_nonfinite: the captured sequence is fwd+bwd, the norm pass, one AdamW launch; max_norm is read
-        # from a device scalar refreshed like the learning rate, the skipped count from the optimizer's record
-        max_norm, skip = optimizer._clip_options()
-        self._clip_mode = (max_norm is not None, skip)
+        self._lr_dev = gradclip.DeviceScalar(dev, optimizer.param_groups[0]["lr"])
+        lr_dev = self._lr_dev.tensor
         with _lib.on_device(dev):
             # one eager step on a snapshot: every kernel is loaded and the workspace sits in the model's pool before
             # anything is captured; the snapshot is then restored (the step must not count)
-            state = [model.flat_params, model._bn_running, model._bn_batches, optimizer._m, optimizer._v]
-            if optimizer._clipping():
-                state.append(optimizer._clip_state().record)
+            state = [model.flat_params, model._bn_running, model._bn_batches] + optimizer._capture_state()
             snap = [t.clone() for t in state]
             step0, t0 = model._step, optimizer._t
             train_step(model, optimizer, self._x, self._y.reshape(self._out_shape))
             for dst, src in zip(state, snap):
                 dst.copy_(src)
-            model._step, optimizer._t = step0, t0
-            optimizer._step_tensor_fill()
+            model._step = step0
+            optimizer._advance_host(t0 - optimizer._t)
             increment_version(model._arena_tensors)      # (the copies above wrote the arenas, not these views)
             model._ensure_wplanes()          # restoring the snapshot made the persistent weight planes stale
-            if self._clip_mode[0] and not torch.is_tensor(optimizer.param_groups[0]["max_grad_norm"]):
-                optimizer._clip_state().refresh_max_norm(optimizer.param_groups[0]["max_grad_norm"])
+            # max_grad_norm / skip_nonfinite: the captured sequence is fwd+bwd, the norm pass, one AdamW launch; max_norm is
+            # read from a device scalar the optimizer refreshes like the learning rate here, the skipped count from its record
+            self._clip_mode = optimizer._replay_refresh()
             torch.cuda.synchronize(dev)
             self.graph = torch.cuda.CUDAGraph()
-            adamw = (optimizer._step_struct(0.0, self._lr_dev, t0, self._tick)
+            adamw = (optimizer._step_struct(0.0, lr_dev, t0, self._tick)
                      if model.step_carries_adamw(B) and not optimizer._clipping() else None)
             self._in_call = adamw is not None
             with torch.cuda.graph(self.graph):
@@ -245,7 +239,7 @@ class GraphedTrainStep:
                     self._refreshes_planes = False
                 else:
                     self.loss, y_hat = model.fused_train_fwd_bwd(self._x, self._y, None, step_dev=self._tick)
-                    self._refreshes_planes = optimizer._enqueue_dev(self._lr_dev, t0, self._tick)
+                    self._refreshes_planes = optimizer._enqueue_dev(lr_dev, t0, self._tick)
             self.y_hat = y_hat.reshape(self._out_shape)
             model._step = step0                                              # capturing ran nothing
         # the graph owns the dropout-stream step and AdamW's t (both = the capture-time base + the device counter):
@@ -264,16 +258,10 @@ class GraphedTrainStep:
                 self.opt._v.data_ptr() if self.opt._v is not None else 0)
 
     def __call__(self, y1, y2):
-        lr = float(self.opt.param_groups[0]["lr"])
-        if lr != self._lr:                                                   # ReduceLROnPlateau et al. (train_1.py:106)
-            self._lr = lr
-            self._lr_dev.fill_(lr)
-        max_norm, skip = self.opt._clip_options()
-        if (max_norm is not None, skip) != self._clip_mode:
+        self._lr_dev.refresh(self.opt.param_groups[0]["lr"])                     # ReduceLROnPlateau et al. (train_1.py:106)
+        if self.opt._replay_refresh() != self._clip_mode:
             raise _lib.PoseliftError("GraphedTrainStep: max_grad_norm / skip_nonfinite were switched on or off after capture "
                                      "(their value may change, not whether the step has a norm pass): capture a new one")
-        if max_norm is not None and not torch.is_tensor(max_norm):
-            self.opt._clip_state().refresh_max_norm(max_norm)
         # an eager train_step / optimizer.step() / load_state_dict() between replays moves the host-side counters but
         # not the device counter the captured launches read: re-seed it when both moved together, refuse otherwise
         ds, dt = self.model._step - self._step0, self.opt._t - self._t0

@@ -425,6 +425,42 @@ def test_weight_planes_behind_a_skipped_step(pkg, when):
         assert torch.equal(m(x), fresh(x))
 
 
+# ------------------------------------------------------------------------------------------------ six entry points, one kernel
+@pytest.mark.parametrize("t", [1, 7])
+@pytest.mark.parametrize("offset", [0, 1])
+def test_the_six_adamw_entry_points_are_one_kernel_bitwise(pkg, offset, t):
+    """The optimizers issue every step through pl_adamw_flat_planes_clip; with NULL planes and a NULL record it has to be the
+    launch pl_adamw_flat / pl_adamw_flat_dev make.  n = 1027 from a 16-byte aligned base (float4 body + scalar tail) and from
+    a base one float further (scalar path); by value, and with lr = *lr_dev, t = t_base + *t_dev."""
+    L, n = pkg.lib(), 1027
+    lr, hp, gs = float(np.float32(3e-4)), (0.9, 0.999, 1e-8, 0.02), 0.5
+    g0 = torch.Generator().manual_seed(100 * offset + t)
+    init = [torch.randn(n + 1, generator=g0) * s for s in (1.0, 1e-2, 1e-3)] + [torch.rand(n + 1, generator=g0) * 1e-4]
+    lr_dev = torch.tensor([lr], dtype=torch.float32, device=DEV)
+    t_dev = torch.tensor([t - 1], dtype=torch.int64, device=DEV)
+    lp, tp = lr_dev.data_ptr(), t_dev.data_ptr()
+
+    def run(name, *tail):
+        bufs = [x.to(DEV) for x in init]
+        p, g, m, v = (b[offset:offset + n] for b in bufs)
+        assert all((x.data_ptr() % 16 == 0) == (offset == 0) for x in (p, g, m, v))
+        rc = getattr(L, name)(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, *tail,
+                              torch.cuda.current_stream().cuda_stream)
+        assert rc == 0, (name, L.pl_last_error())
+        return torch.stack([bufs[0], bufs[2], bufs[3]])      # whole buffers: the float outside [offset, offset + n) too
+
+    want = run("pl_adamw_flat", lr, *hp, t, gs)
+    assert not torch.equal(want[0], init[0].to(DEV))
+    forms = {"flat_clip": run("pl_adamw_flat_clip", lr, *hp, t, gs, None),
+             "flat_planes": run("pl_adamw_flat_planes", lr, None, *hp, t, None, gs, None),
+             "flat_planes_clip": run("pl_adamw_flat_planes_clip", lr, None, *hp, t, None, gs, None, None),
+             "flat_dev": run("pl_adamw_flat_dev", lp, *hp, 1, tp, gs),
+             "flat_dev_clip": run("pl_adamw_flat_dev_clip", lp, *hp, 1, tp, gs, None),
+             "flat_planes_clip, lr and t read on the device": run("pl_adamw_flat_planes_clip", 0.0, lp, *hp, 1, tp, gs, None, None)}
+    for name, got in forms.items():
+        assert torch.equal(got, want), name
+
+
 # ------------------------------------------------------------------------------------------------ FlatAdam
 @pytest.mark.parametrize("capturable", [False, True])
 def test_flat_adam_small_module_vs_torch_adam_and_clip_grad_norm(pkg, capturable):

@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""sha256 of everything the lifter's and the conv path's BatchNorm launches write, one line per (case, buffer):
+"""sha256 of everything the lifter's and the conv path's BatchNorm launches and the flat optimizers write, one line per
+(case, buffer):
 
     python tools/route_hashes.py > hashes.txt          (POSELIFT_LIB=... picks another build of the library)
 
@@ -236,6 +237,82 @@ def conv_cases():
     case_conv_bn("conv-bn/C64/rows33792", 33792, 64)                                 # 256-row statistics groups
 
 
+# ------------------------------------------------------------------------------------------------ the flat optimizers
+def opt_state(m, opt):
+    rec = opt._clip.record if opt._clip is not None else None
+    return dict(params=m.flat_params, moments=[opt._m, opt._v], wplanes=m._wplanes, bn=[m._bn_running, m._bn_batches], clip=rec)
+
+
+def case_opt(name, B, graphed=False, freeze=None, poison=None, steps=3, bn=True, **kw):
+    """Three train steps of the 1024-wide f16x3 lifter (the AdamW launch writes its weight planes) with FlatAdamW(**kw);
+    freeze: a parameter without a gradient (several runs, no planes); poison: the step whose target holds an inf."""
+    m, x, t = make(B, 1024, 2, "f16x3", 0.5, bn=bn)
+    if m._wplanes is not None:
+        m._wplanes.zero_()                                # (not written yet: whatever no launch writes hashes as zero)
+    if freeze:
+        dict(m.named_parameters())[freeze].requires_grad_(False)
+    opt = pkg.FlatAdamW(m, lr=1e-3, weight_decay=0.02, **kw)
+    step = pkg.GraphedTrainStep(m, opt, x, t) if graphed else (lambda a, b: pkg.train_step(m, opt, a, b))
+    losses = []
+    for i in range(steps):
+        tt = t.clone()
+        if i == poison:
+            tt[3, 7] = float("inf")
+        losses.append(step(x, tt)[0].clone())
+        if i == 1:
+            opt.param_groups[0]["lr"] = 5e-4              # (a scheduler's change: the device scalar of a replay follows)
+    torch.cuda.synchronize()
+    emit(name, loss=losses, step=opt.state_dict()["state"][0]["step"].float(), **opt_state(m, opt))
+
+
+def case_flat_adam(name, capturable=False, graphed=False, **kw):
+    """arena.FlatAdam on a stock module (gradients arrive through gather_grads): all gradients, one parameter without,
+    none at all (the counter still ticks), all again; graphed: three GraphedModuleStep replays."""
+    torch.manual_seed(12)
+    mod = torch.nn.Sequential(torch.nn.Linear(7, 5), torch.nn.Tanh(), torch.nn.Linear(5, 3)).to(DEV)
+    x, t = torch.randn(6, 7, device=DEV), torch.randn(6, 3, device=DEV)
+    opt = pkg.FlatAdam(mod, lr=1e-2, capturable=capturable, **kw)
+    if graphed:
+        step = pkg.GraphedModuleStep(mod, opt, torch.nn.functional.mse_loss, x, t)
+        for i in range(3):
+            step(x + i, t)
+    else:
+        for what in ("all", "missing", "none", "all"):
+            opt.zero_grad()
+            if what != "none":
+                (mod(x) - t).pow(2).mean().backward()
+            if what == "missing":
+                mod[0].bias.grad = None
+            opt.step()
+    torch.cuda.synchronize()
+    rec = opt._clip.record if opt._clip is not None else None
+    emit(name, params=opt.arena.flat, moments=[opt._m, opt._v], clip=rec, step=opt.state_dict()["state"][0]["step"].float())
+
+
+def optimizer_cases():
+    CLIP = dict(max_grad_norm=0.05, skip_nonfinite=True)
+    case_opt("opt/B256/planes", 256)                                    # a launch of its own, planes refreshed
+    case_opt("opt/B256/planes/clip", 256, **CLIP)
+    case_opt("opt/B64/in-call", 64)                                     # AdamW inside the backward launches + the remainder
+    case_opt("opt/B64/clip", 64, **CLIP)                                # ... bypassed: norm pass + one launch
+    case_opt("opt/B256/frozen", 256, freeze="w1.bias")
+    case_opt("opt/B256/frozen/clip", 256, freeze="w1.bias", **CLIP)
+    case_opt("opt/B256/nobn", 256, bn=False)
+    case_opt("opt/B256/nobn/clip", 256, bn=False, **CLIP)
+    case_opt("opt/B64/graph", 64, graphed=True)
+    case_opt("opt/B64/graph/clip", 64, graphed=True, **CLIP)
+    case_opt("opt/B256/graph", 256, graphed=True)
+    case_opt("opt/B256/graph/clip", 256, graphed=True, **CLIP)
+    case_opt("opt/B256/nonfinite-skip", 256, poison=1, **CLIP)
+    case_opt("opt/B256/graph/nonfinite-skip", 256, graphed=True, poison=1, skip_nonfinite=True)
+    for cap in (False, True):
+        case_flat_adam(f"flat-adam/cap{int(cap)}", capturable=cap)
+        case_flat_adam(f"flat-adam/cap{int(cap)}/clip", capturable=cap, **CLIP)
+    case_flat_adam("flat-adam/graph", capturable=True, graphed=True)
+    case_flat_adam("flat-adam/graph/clip", capturable=True, graphed=True, **CLIP)
+
+
 if __name__ == "__main__":
     lifter_cases()
     conv_cases()
+    optimizer_cases()
