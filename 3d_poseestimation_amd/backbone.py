@@ -24,8 +24,7 @@ import torch
 import torch.nn as nn
 
 from . import conv
-from .heads import (soft_argmax_2d, soft_argmax_2d_hm, soft_argmax_3d, soft_argmax_3d_hm, soft_argmax_3d_nhwc,
-                    soft_argmax_3d_nhwc_hm)
+from .heads import head_nchw, head_nhwc
 
 # compute_dtype -> (operand planes of the planes route, or None: the direct route; arithmetic of the direct kernels).
 # "f16x3": two fp16 planes per operand, fp32-grade like "bf16x6"; "bf16p": ONE bf16 plane -- bf16 storage of the GEMM
@@ -345,13 +344,7 @@ class _HeatmapNet(nn.Module):
 
     def _coords(self, logits_nchw, hm=None):
         """hm: None, or (heatmap_target, sigma, centre) -> (coords, sq)."""
-        if self.depth_dim > 1:
-            if hm is not None:
-                return soft_argmax_3d_hm(logits_nchw, hm[0], hm[1], hm[2], self.num_joints, self.depth_dim)
-            return soft_argmax_3d(logits_nchw, self.num_joints, self.depth_dim)
-        if hm is not None:
-            return soft_argmax_2d_hm(logits_nchw, hm[0], hm[1], hm[2], self.num_joints)
-        return soft_argmax_2d(logits_nchw, self.num_joints)
+        return head_nchw(logits_nchw, self.num_joints, self.depth_dim, hm)
 
     def predict_nhwc(self, x_nhwc, heatmap_target=None, sigma=0.5, centre="head"):
         """Coordinates from NHWC frames, in whichever mode the module is in (phase5's cycle step feeds BOTH networks
@@ -367,15 +360,9 @@ class _HeatmapNet(nn.Module):
                 # convolution's mode and its gradient arrives as planes written by the soft-argmax backward, else with None
                 lk = conv.PlaneLink()
                 logits = self._heatmap_logits_train(x_nhwc, nhwc=True, final_link=lk)
-                if hm is not None:
-                    return soft_argmax_3d_nhwc_hm(logits, heatmap_target, sigma, centre, self.num_joints,
-                                                  lk if lk.mode is not None else None)
-                return soft_argmax_3d_nhwc(logits, self.num_joints, lk if lk.mode is not None else None)
+                return head_nhwc(logits, self.num_joints, hm, lk if lk.mode is not None else None)
             with torch.no_grad():
-                if hm is not None:
-                    return soft_argmax_3d_nhwc_hm(self.heatmap_logits_nhwc(x_nhwc), heatmap_target, sigma, centre,
-                                                  self.num_joints)
-                return soft_argmax_3d_nhwc(self.heatmap_logits_nhwc(x_nhwc), self.num_joints)
+                return head_nhwc(self.heatmap_logits_nhwc(x_nhwc), self.num_joints, hm)
         if self.training:
             return self._coords(self._heatmap_logits_train(x_nhwc), hm)
         with torch.no_grad():

@@ -395,10 +395,14 @@ __global__ __launch_bounds__(NTHR) void softargmax_nhwc_bwd_kernel(const float* 
   if (pd.kind) store_planes4(pd, (size_t)t * 4, o);        // the final convolution's gradient GEMMs read planes
 }
 
-int check_dims(int64_t BJ, int64_t D, int64_t H, int64_t W, int ncoord, const char* who) {
-  if (BJ <= 0 || D <= 0 || H <= 0 || W <= 0 || (W & 3) || D * H * W > (int64_t)1 << 30 || BJ > 65535 * 64)
-    PL_FAIL(PL_ESHAPE, "%s: bad dims BJ=%lld D=%lld H=%lld W=%lld (W %% 4 == 0)", who, (long long)BJ, (long long)D,
-            (long long)H, (long long)W);
+// ---- the host side: one launcher per kernel (its checks, its grid, both instantiations' launch); the extern "C" entry points
+// fill its argument struct and pass their own name, which every message starts with.
+// The dims of every NCHW entry point -- w4: the soft-argmax kernels read float4 rows, the dense target does not; max_bj: BJ is
+// grid.x (65535 * 64; the backward, where it is grid.y, then answers with a message of its own) or the target's grid.y
+int check_dims(const char* who, int64_t BJ, int64_t D, int64_t H, int64_t W, int ncoord, bool w4, int64_t max_bj) {
+  if (BJ <= 0 || BJ > max_bj || D <= 0 || H <= 0 || W <= 0 || (w4 && (W & 3)) || D * H * W > (int64_t)1 << 30)
+    PL_FAIL(PL_ESHAPE, "%s: bad dims BJ=%lld D=%lld H=%lld W=%lld%s", who, (long long)BJ, (long long)D, (long long)H,
+            (long long)W, w4 ? " (W % 4 == 0)" : "");
   if (ncoord != 2 && ncoord != 3) PL_FAIL(PL_ESHAPE, "%s: ncoord=%d", who, ncoord);
   if (ncoord == 2 && D != 1) PL_FAIL(PL_ESHAPE, "%s: 2 coordinates need depth 1", who);
   return PL_OK;
@@ -436,12 +440,117 @@ int heat_law_of(const char* who, float sigma, const float* law, plh::Law* L) {
   return PL_OK;
 }
 
-int check_dense_dims(int64_t BJ, int64_t D, int64_t H, int64_t W, int ncoord, const char* who) {
-  if (BJ <= 0 || BJ > 65535 || D <= 0 || H <= 0 || W <= 0 || D * H * W > (int64_t)1 << 30)
-    PL_FAIL(PL_ESHAPE, "%s: bad dims BJ=%lld D=%lld H=%lld W=%lld", who, (long long)BJ, (long long)D, (long long)H,
-            (long long)W);
-  if (ncoord != 2 && ncoord != 3) PL_FAIL(PL_ESHAPE, "%s: ncoord=%d", who, ncoord);
-  if (ncoord == 2 && D != 1) PL_FAIL(PL_ESHAPE, "%s: 2 coordinates need depth 1", who);
+// what an _hm entry point receives besides the plain arguments, unchecked: the launchers check it where the entry points
+// always did (target among the pointers, sigma and law after the dims), so a call that is wrong twice answers as it used to
+struct HmArgs { const float* target; float sigma; const float* law; };
+
+// the kernels' heat-map input; hm == NULL: the empty one that the <false> instantiations are launched with
+int hm_in_of(const char* who, const HmArgs* hm, HmIn* in) {
+  *in = HmIn{};
+  if (!hm) return PL_OK;
+  if (!hm->target) PL_FAIL(PL_EINVAL, "%s: null pointer", who);
+  in->target = hm->target;
+  return heat_law_of(who, hm->sigma, hm->law, &in->law);
+}
+
+struct FwdArgs {
+  const float* logits;
+  int64_t BJ, D, H, W;
+  int ncoord, centred;
+  float *coords, *stats, *sq;                       // sq: with hm
+};
+
+int launch_softargmax_fwd(const FwdArgs& a, const char* who, const HmArgs* hm, hipStream_t s) {
+  if (!a.logits || !a.coords || !a.stats || (hm && (!hm->target || !a.sq))) PL_FAIL(PL_EINVAL, "%s: null pointer", who);
+  if (reinterpret_cast<uintptr_t>(a.logits) & 15) PL_FAIL(PL_EINVAL, "%s: logits not 16-byte aligned", who);
+  PL_TRY(check_dims(who, a.BJ, a.D, a.H, a.W, a.ncoord, true, 65535 * 64));
+  HmIn in;
+  PL_TRY(hm_in_of(who, hm, &in));
+  hipLaunchKernelGGL((hm ? softargmax_fwd_kernel<true> : softargmax_fwd_kernel<false>), dim3((unsigned)a.BJ), dim3(NTHR), 0, s,
+                     a.logits, (int)a.D, (int)a.H, (int)a.W, a.centred, a.coords, a.ncoord, a.stats, in, hm ? a.sq : nullptr);
+  PL_CHECK_LAUNCH(who);
+  return PL_OK;
+}
+
+struct BwdArgs {
+  const float *logits, *stats, *gcoords, *gsq;      // gsq: with hm
+  int64_t BJ, D, H, W;
+  int ncoord, centred;
+  float* dlogits;
+};
+
+int launch_softargmax_bwd(const BwdArgs& a, const char* who, const HmArgs* hm, hipStream_t s) {
+  if (!a.logits || !a.stats || !a.gcoords || !a.dlogits || (hm && (!hm->target || !a.gsq)))
+    PL_FAIL(PL_EINVAL, "%s: null pointer", who);
+  if ((reinterpret_cast<uintptr_t>(a.logits) | reinterpret_cast<uintptr_t>(a.dlogits)) & 15)
+    PL_FAIL(PL_EINVAL, "%s: tensors not 16-byte aligned", who);
+  PL_TRY(check_dims(who, a.BJ, a.D, a.H, a.W, a.ncoord, true, 65535 * 64));
+  if (a.BJ > 65535) PL_FAIL(PL_ESHAPE, "%s: BJ=%lld > 65535 (split the batch)", who, (long long)a.BJ);
+  HmIn in;
+  PL_TRY(hm_in_of(who, hm, &in));
+  const int64_t n4 = (a.D * a.H * a.W) >> 2;
+  int chunks = (int)((n4 + NTHR * 8 - 1) / (NTHR * 8));      // 8 float4 per thread
+  if (chunks < 1) chunks = 1;
+  if (chunks > 64) chunks = 64;
+  hipLaunchKernelGGL((hm ? softargmax_bwd_kernel<true> : softargmax_bwd_kernel<false>), dim3(chunks, (unsigned)a.BJ), dim3(NTHR),
+                     0, s, a.logits, a.stats, a.gcoords, (int)a.D, (int)a.H, (int)a.W, a.centred, a.ncoord, a.dlogits, in,
+                     hm ? a.gsq : nullptr);
+  PL_CHECK_LAUNCH(who);
+  return PL_OK;
+}
+
+int check_nhwc_dims(const char* who, int64_t B, int64_t J, int64_t H, int64_t W) {
+  if (B <= 0 || J <= 0 || H <= 0 || W <= 0 || B * J > 0x7fffffff || H * W > (1 << 24)) PL_FAIL(PL_ESHAPE, "%s: bad dims", who);
+  return PL_OK;
+}
+
+struct NhwcFwdArgs {
+  const float* logits;
+  int64_t B, J, H, W;
+  float *coords, *stats, *sq;                       // sq: with hm
+};
+
+int launch_softargmax_nhwc_fwd(const NhwcFwdArgs& a, const char* who, const HmArgs* hm, hipStream_t s) {
+  if (!a.logits || !a.coords || !a.stats || (hm && (!hm->target || !a.sq))) PL_FAIL(PL_EINVAL, "%s: null pointer", who);
+  PL_TRY(check_nhwc_dims(who, a.B, a.J, a.H, a.W));
+  HmIn in;
+  PL_TRY(hm_in_of(who, hm, &in));
+  hipLaunchKernelGGL((hm ? softargmax_nhwc_fwd_kernel<true> : softargmax_nhwc_fwd_kernel<false>), dim3((unsigned)(a.B * a.J)),
+                     dim3(NTHR), 0, s, a.logits, (int)a.J, (int)a.H, (int)a.W, a.coords, a.stats, in, hm ? a.sq : nullptr);
+  PL_CHECK_LAUNCH(who);
+  return PL_OK;
+}
+
+// dl_planes (optional): dlogits also / only (dlogits == NULL) as operand planes for the final convolution's gradient GEMMs.
+// PL_F16X3: the planes hold dl_scale[0] * dlogits -- dl_scale = {S, 1/S} on the device, S a power of two that the CALLER
+// derives from the bound on |dlogit| (pl_softargmax_dl_scale; with hm pl_softargmax_hm_dl_scale, the bound grows by 4 |gsq|)
+struct NhwcBwdArgs {
+  const float *logits, *stats, *gcoords, *gsq;      // gsq [B*J], with hm: the upstream gradient of sq
+  int64_t B, J, H, W;
+  float* dlogits;
+  void* dl_planes;
+  int planes_mode;
+  const float* dl_scale;
+};
+
+int launch_softargmax_nhwc_bwd(const NhwcBwdArgs& a, const char* who, const HmArgs* hm, hipStream_t s) {
+  if (!a.logits || !a.stats || !a.gcoords || (!a.dlogits && !a.dl_planes) || (hm && (!hm->target || !a.gsq)))
+    PL_FAIL(PL_EINVAL, "%s: null pointer", who);
+  if ((reinterpret_cast<uintptr_t>(a.logits) | reinterpret_cast<uintptr_t>(a.dlogits)) & 15)
+    PL_FAIL(PL_EINVAL, "%s: tensors not 16-byte aligned", who);
+  PL_TRY(check_nhwc_dims(who, a.B, a.J, a.H, a.W));
+  const int64_t n4 = a.B * a.H * a.W * a.J * 16;
+  if (n4 > (int64_t)INT32_MAX * NTHR) PL_FAIL(PL_ESHAPE, "%s: too large", who);
+  const bool f16 = a.planes_mode == PL_F16X3;
+  if (a.dl_planes && f16 && !a.dl_scale) PL_FAIL(PL_EINVAL, "%s: fp16 planes need dl_scale", who);
+  HmIn in;
+  PL_TRY(hm_in_of(who, hm, &in));
+  PlaneOut po;
+  PL_TRY(plane_out_of(a.planes_mode, a.dl_planes, n4 * 4, 1.0f, f16 ? a.dl_scale : nullptr, &po, who));
+  hipLaunchKernelGGL((hm ? softargmax_nhwc_bwd_kernel<true> : softargmax_nhwc_bwd_kernel<false>),
+                     dim3((unsigned)((n4 + NTHR - 1) / NTHR)), dim3(NTHR), 0, s, a.logits, a.stats, a.gcoords, (int)a.J, (int)a.H,
+                     (int)a.W, n4, a.dlogits, po, in, hm ? a.gsq : nullptr);
+  PL_CHECK_LAUNCH(who);
   return PL_OK;
 }
 
@@ -452,37 +561,75 @@ using namespace pl;
 
 extern "C" int pl_softargmax_fwd(const float* logits, int64_t BJ, int64_t D, int64_t H, int64_t W, int ncoord,
                                  int centred, float* coords, float* stats, void* stream) {
-  if (!logits || !coords || !stats) PL_FAIL(PL_EINVAL, "pl_softargmax_fwd: null pointer");
-  if (reinterpret_cast<uintptr_t>(logits) & 15) PL_FAIL(PL_EINVAL, "pl_softargmax_fwd: logits not 16-byte aligned");
-  PL_TRY(check_dims(BJ, D, H, W, ncoord, "pl_softargmax_fwd"));
-  hipLaunchKernelGGL(softargmax_fwd_kernel<false>, dim3((unsigned)BJ), dim3(NTHR), 0, (hipStream_t)stream, logits, (int)D,
-                     (int)H, (int)W, centred, coords, ncoord, stats, HmIn{}, (float*)nullptr);
-  PL_CHECK_LAUNCH("softargmax_fwd");
-  return PL_OK;
+  return launch_softargmax_fwd({logits, BJ, D, H, W, ncoord, centred, coords, stats, nullptr}, "pl_softargmax_fwd", nullptr,
+                               (hipStream_t)stream);
+}
+
+extern "C" int pl_softargmax_hm_fwd(const float* logits, const float* target, int64_t BJ, int64_t D, int64_t H, int64_t W,
+                                    int ncoord, int centred, float sigma, const float* law, float* coords, float* sq,
+                                    float* stats, void* stream) {
+  const HmArgs hm = {target, sigma, law};
+  return launch_softargmax_fwd({logits, BJ, D, H, W, ncoord, centred, coords, stats, sq}, "pl_softargmax_hm_fwd", &hm,
+                               (hipStream_t)stream);
 }
 
 extern "C" int pl_softargmax_bwd(const float* logits, const float* stats, const float* gcoords, int64_t BJ,
                                  int64_t D, int64_t H, int64_t W, int ncoord, int centred, float* dlogits,
                                  void* stream) {
-  if (!logits || !stats || !gcoords || !dlogits) PL_FAIL(PL_EINVAL, "pl_softargmax_bwd: null pointer");
-  if ((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(dlogits)) & 15)
-    PL_FAIL(PL_EINVAL, "pl_softargmax_bwd: tensors not 16-byte aligned");
-  PL_TRY(check_dims(BJ, D, H, W, ncoord, "pl_softargmax_bwd"));
-  if (BJ > 65535) PL_FAIL(PL_ESHAPE, "pl_softargmax_bwd: BJ=%lld > 65535 (split the batch)", (long long)BJ);
-  const int64_t n4 = (D * H * W) >> 2;
-  int chunks = (int)((n4 + NTHR * 8 - 1) / (NTHR * 8));      // 8 float4 per thread
-  if (chunks < 1) chunks = 1;
-  if (chunks > 64) chunks = 64;
-  hipLaunchKernelGGL(softargmax_bwd_kernel<false>, dim3(chunks, (unsigned)BJ), dim3(NTHR), 0, (hipStream_t)stream, logits,
-                     stats, gcoords, (int)D, (int)H, (int)W, centred, ncoord, dlogits, HmIn{}, (const float*)nullptr);
-  PL_CHECK_LAUNCH("softargmax_bwd");
-  return PL_OK;
+  return launch_softargmax_bwd({logits, stats, gcoords, nullptr, BJ, D, H, W, ncoord, centred, dlogits}, "pl_softargmax_bwd",
+                               nullptr, (hipStream_t)stream);
+}
+
+extern "C" int pl_softargmax_hm_bwd(const float* logits, const float* target, const float* stats, const float* gcoords,
+                                    const float* gsq, int64_t BJ, int64_t D, int64_t H, int64_t W, int ncoord, int centred,
+                                    float sigma, const float* law, float* dlogits, void* stream) {
+  const HmArgs hm = {target, sigma, law};
+  return launch_softargmax_bwd({logits, stats, gcoords, gsq, BJ, D, H, W, ncoord, centred, dlogits}, "pl_softargmax_hm_bwd", &hm,
+                               (hipStream_t)stream);
+}
+
+extern "C" int pl_softargmax3d_nhwc_fwd(const float* logits, int64_t B, int64_t J, int64_t H, int64_t W,
+                                        float* coords, float* stats, void* stream) {
+  return launch_softargmax_nhwc_fwd({logits, B, J, H, W, coords, stats, nullptr}, "pl_softargmax3d_nhwc_fwd", nullptr,
+                                    (hipStream_t)stream);
+}
+
+extern "C" int pl_softargmax3d_nhwc_hm_fwd(const float* logits, const float* target, int64_t B, int64_t J, int64_t H,
+                                           int64_t W, float sigma, const float* law, float* coords, float* sq, float* stats,
+                                           void* stream) {
+  const HmArgs hm = {target, sigma, law};
+  return launch_softargmax_nhwc_fwd({logits, B, J, H, W, coords, stats, sq}, "pl_softargmax3d_nhwc_hm_fwd", &hm,
+                                    (hipStream_t)stream);
+}
+
+extern "C" int pl_softargmax3d_nhwc_bwd(const float* logits, const float* stats, const float* gcoords, int64_t B,
+                                        int64_t J, int64_t H, int64_t W, float* dlogits, void* stream) {
+  const char* who = "pl_softargmax3d_nhwc_bwd";
+  if (!dlogits) PL_FAIL(PL_EINVAL, "%s: null pointer", who);          // (no planes to write instead)
+  return launch_softargmax_nhwc_bwd({logits, stats, gcoords, nullptr, B, J, H, W, dlogits, nullptr, 0, nullptr}, who, nullptr,
+                                    (hipStream_t)stream);
+}
+
+extern "C" int pl_softargmax3d_nhwc_bwd_ex(const float* logits, const float* stats, const float* gcoords, int64_t B,
+                                           int64_t J, int64_t H, int64_t W, float* dlogits, void* dl_planes, int planes_mode,
+                                           const float* dl_scale, void* stream) {
+  return launch_softargmax_nhwc_bwd({logits, stats, gcoords, nullptr, B, J, H, W, dlogits, dl_planes, planes_mode, dl_scale},
+                                    "pl_softargmax3d_nhwc_bwd_ex", nullptr, (hipStream_t)stream);
+}
+
+extern "C" int pl_softargmax3d_nhwc_hm_bwd_ex(const float* logits, const float* target, const float* stats,
+                                              const float* gcoords, const float* gsq, int64_t B, int64_t J, int64_t H,
+                                              int64_t W, float sigma, const float* law, float* dlogits, void* dl_planes,
+                                              int planes_mode, const float* dl_scale, void* stream) {
+  const HmArgs hm = {target, sigma, law};
+  return launch_softargmax_nhwc_bwd({logits, stats, gcoords, gsq, B, J, H, W, dlogits, dl_planes, planes_mode, dl_scale},
+                                    "pl_softargmax3d_nhwc_hm_bwd_ex", &hm, (hipStream_t)stream);
 }
 
 extern "C" int pl_heatmap_gaussian(const float* target, int64_t BJ, int64_t D, int64_t H, int64_t W, int ncoord, float sigma,
                                    const float* law, float* out, void* stream) {
   if (!target || !out) PL_FAIL(PL_EINVAL, "pl_heatmap_gaussian: null pointer");
-  PL_TRY(check_dense_dims(BJ, D, H, W, ncoord, "pl_heatmap_gaussian"));
+  PL_TRY(check_dims("pl_heatmap_gaussian", BJ, D, H, W, ncoord, false, 65535));
   plh::Law L;
   PL_TRY(heat_law_of("pl_heatmap_gaussian", sigma, law, &L));
   const int64_t n = D * H * W;
@@ -497,7 +644,7 @@ extern "C" int pl_heatmap_gaussian(const float* target, int64_t BJ, int64_t D, i
 extern "C" int pl_heatmap_gaussian_host(const float* target, int64_t BJ, int64_t D, int64_t H, int64_t W, int ncoord,
                                         float sigma, const float* law, float* out) {
   if (!target || !out) PL_FAIL(PL_EINVAL, "pl_heatmap_gaussian_host: null pointer");
-  PL_TRY(check_dense_dims(BJ, D, H, W, ncoord, "pl_heatmap_gaussian_host"));
+  PL_TRY(check_dims("pl_heatmap_gaussian_host", BJ, D, H, W, ncoord, false, 65535));
   plh::Law L;
   PL_TRY(heat_law_of("pl_heatmap_gaussian_host", sigma, law, &L));
   for (int64_t bj = 0; bj < BJ; ++bj) {
@@ -509,68 +656,6 @@ extern "C" int pl_heatmap_gaussian_host(const float* target, int64_t BJ, int64_t
         for (int64_t w = 0; w < W; ++w)
           dst[(d * H + h) * W + w] = bad ? __builtin_nanf("") : plh::value_at(mp, L, (float)w, (float)h, (float)d);
   }
-  return PL_OK;
-}
-
-extern "C" int pl_softargmax_hm_fwd(const float* logits, const float* target, int64_t BJ, int64_t D, int64_t H, int64_t W,
-                                    int ncoord, int centred, float sigma, const float* law, float* coords, float* sq,
-                                    float* stats, void* stream) {
-  if (!logits || !target || !coords || !sq || !stats) PL_FAIL(PL_EINVAL, "pl_softargmax_hm_fwd: null pointer");
-  if (reinterpret_cast<uintptr_t>(logits) & 15) PL_FAIL(PL_EINVAL, "pl_softargmax_hm_fwd: logits not 16-byte aligned");
-  PL_TRY(check_dims(BJ, D, H, W, ncoord, "pl_softargmax_hm_fwd"));
-  HmIn hm;
-  hm.target = target;
-  PL_TRY(heat_law_of("pl_softargmax_hm_fwd", sigma, law, &hm.law));
-  hipLaunchKernelGGL(softargmax_fwd_kernel<true>, dim3((unsigned)BJ), dim3(NTHR), 0, (hipStream_t)stream, logits, (int)D, (int)H,
-                     (int)W, centred, coords, ncoord, stats, hm, sq);
-  PL_CHECK_LAUNCH("softargmax_hm_fwd");
-  return PL_OK;
-}
-
-extern "C" int pl_softargmax_hm_bwd(const float* logits, const float* target, const float* stats, const float* gcoords,
-                                    const float* gsq, int64_t BJ, int64_t D, int64_t H, int64_t W, int ncoord, int centred,
-                                    float sigma, const float* law, float* dlogits, void* stream) {
-  if (!logits || !target || !stats || !gcoords || !gsq || !dlogits) PL_FAIL(PL_EINVAL, "pl_softargmax_hm_bwd: null pointer");
-  if ((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(dlogits)) & 15)
-    PL_FAIL(PL_EINVAL, "pl_softargmax_hm_bwd: tensors not 16-byte aligned");
-  PL_TRY(check_dims(BJ, D, H, W, ncoord, "pl_softargmax_hm_bwd"));
-  if (BJ > 65535) PL_FAIL(PL_ESHAPE, "pl_softargmax_hm_bwd: BJ=%lld > 65535 (split the batch)", (long long)BJ);
-  HmIn hm;
-  hm.target = target;
-  PL_TRY(heat_law_of("pl_softargmax_hm_bwd", sigma, law, &hm.law));
-  const int64_t n4 = (D * H * W) >> 2;
-  int chunks = (int)((n4 + NTHR * 8 - 1) / (NTHR * 8));      // as pl_softargmax_bwd
-  if (chunks < 1) chunks = 1;
-  if (chunks > 64) chunks = 64;
-  hipLaunchKernelGGL(softargmax_bwd_kernel<true>, dim3(chunks, (unsigned)BJ), dim3(NTHR), 0, (hipStream_t)stream, logits, stats,
-                     gcoords, (int)D, (int)H, (int)W, centred, ncoord, dlogits, hm, gsq);
-  PL_CHECK_LAUNCH("softargmax_hm_bwd");
-  return PL_OK;
-}
-
-extern "C" int pl_softargmax3d_nhwc_hm_fwd(const float* logits, const float* target, int64_t B, int64_t J, int64_t H,
-                                           int64_t W, float sigma, const float* law, float* coords, float* sq, float* stats,
-                                           void* stream) {
-  if (!logits || !target || !coords || !sq || !stats) PL_FAIL(PL_EINVAL, "pl_softargmax3d_nhwc_hm_fwd: null pointer");
-  if (B <= 0 || J <= 0 || H <= 0 || W <= 0 || B * J > 0x7fffffff || H * W > (1 << 24))
-    PL_FAIL(PL_ESHAPE, "pl_softargmax3d_nhwc_hm_fwd: bad dims");
-  HmIn hm;
-  hm.target = target;
-  PL_TRY(heat_law_of("pl_softargmax3d_nhwc_hm_fwd", sigma, law, &hm.law));
-  hipLaunchKernelGGL(softargmax_nhwc_fwd_kernel<true>, dim3((unsigned)(B * J)), dim3(NTHR), 0, (hipStream_t)stream, logits,
-                     (int)J, (int)H, (int)W, coords, stats, hm, sq);
-  PL_CHECK_LAUNCH("softargmax_nhwc_hm_fwd");
-  return PL_OK;
-}
-
-extern "C" int pl_softargmax3d_nhwc_fwd(const float* logits, int64_t B, int64_t J, int64_t H, int64_t W,
-                                        float* coords, float* stats, void* stream) {
-  if (!logits || !coords || !stats) PL_FAIL(PL_EINVAL, "pl_softargmax3d_nhwc_fwd: null pointer");
-  if (B <= 0 || J <= 0 || H <= 0 || W <= 0 || B * J > 0x7fffffff || H * W > (1 << 24))
-    PL_FAIL(PL_ESHAPE, "pl_softargmax3d_nhwc_fwd: bad dims");
-  hipLaunchKernelGGL(softargmax_nhwc_fwd_kernel<false>, dim3((unsigned)(B * J)), dim3(NTHR), 0, (hipStream_t)stream, logits,
-                     (int)J, (int)H, (int)W, coords, stats, HmIn{}, (float*)nullptr);
-  PL_CHECK_LAUNCH("softargmax_nhwc_fwd");
   return PL_OK;
 }
 
@@ -619,75 +704,37 @@ __global__ __launch_bounds__(NTHR) void softargmax_hm_dl_scale_kernel(const floa
   softargmax_dl_scale_body<true>(g, gsq, rows, ncoord, out);
 }
 
-extern "C" int pl_softargmax_hm_dl_scale(const float* gcoords, const float* gsq, int64_t rows, int ncoord, float* scale2,
-                                         void* stream) {
-  if (!gcoords || !gsq || !scale2) PL_FAIL(PL_EINVAL, "pl_softargmax_hm_dl_scale: null pointer");
-  if (rows <= 0 || ncoord <= 0 || ncoord > 3) PL_FAIL(PL_ESHAPE, "pl_softargmax_hm_dl_scale: bad dims");
-  hipLaunchKernelGGL(softargmax_hm_dl_scale_kernel, dim3(1), dim3(NTHR), 0, (hipStream_t)stream, gcoords, gsq, rows, ncoord,
-                     scale2);
-  PL_CHECK_LAUNCH("softargmax_hm_dl_scale");
+namespace pl {
+namespace {
+
+struct DlScaleArgs {
+  const float *gcoords, *gsq;           // gsq: with the heat-map term
+  int64_t rows;
+  int ncoord;
+  float* scale2;
+};
+
+int launch_softargmax_dl_scale(const DlScaleArgs& a, const char* who, bool hm, hipStream_t s) {
+  if (!a.gcoords || !a.scale2 || (hm && !a.gsq)) PL_FAIL(PL_EINVAL, "%s: null pointer", who);
+  if (a.rows <= 0 || a.ncoord <= 0 || a.ncoord > 3) PL_FAIL(PL_ESHAPE, "%s: bad dims", who);
+  if (hm)
+    hipLaunchKernelGGL(softargmax_hm_dl_scale_kernel, dim3(1), dim3(NTHR), 0, s, a.gcoords, a.gsq, a.rows, a.ncoord, a.scale2);
+  else
+    hipLaunchKernelGGL(softargmax_dl_scale_kernel, dim3(1), dim3(NTHR), 0, s, a.gcoords, a.rows, a.ncoord, a.scale2);
+  PL_CHECK_LAUNCH(who);
   return PL_OK;
 }
+
+}  // namespace
+}  // namespace pl
 
 extern "C" int pl_softargmax_dl_scale(const float* gcoords, int64_t rows, int ncoord, float* scale2, void* stream) {
-  if (!gcoords || !scale2) PL_FAIL(PL_EINVAL, "pl_softargmax_dl_scale: null pointer");
-  if (rows <= 0 || ncoord <= 0 || ncoord > 3) PL_FAIL(PL_ESHAPE, "pl_softargmax_dl_scale: bad dims");
-  hipLaunchKernelGGL(softargmax_dl_scale_kernel, dim3(1), dim3(NTHR), 0, (hipStream_t)stream, gcoords, rows, ncoord, scale2);
-  PL_CHECK_LAUNCH("softargmax_dl_scale");
-  return PL_OK;
+  return launch_softargmax_dl_scale({gcoords, nullptr, rows, ncoord, scale2}, "pl_softargmax_dl_scale", false,
+                                    (hipStream_t)stream);
 }
 
-extern "C" int pl_softargmax3d_nhwc_bwd(const float* logits, const float* stats, const float* gcoords, int64_t B,
-                                        int64_t J, int64_t H, int64_t W, float* dlogits, void* stream) {
-  if (!dlogits) PL_FAIL(PL_EINVAL, "pl_softargmax3d_nhwc_bwd: null pointer");
-  return pl_softargmax3d_nhwc_bwd_ex(logits, stats, gcoords, B, J, H, W, dlogits, nullptr, 0, nullptr, stream);
-}
-
-// + dl_planes (optional): dlogits also / only (dlogits == NULL) as operand planes for the final convolution's gradient
-// GEMMs.  PL_F16X3: the planes hold dl_scale[0] * dlogits -- dl_scale = {S, 1/S} on the device, S a power of two the
-// CALLER derives from the bound |dlogit| <= 2 max_(b,j) sum_c |g_c| (softmax weights <= 1, index offsets < the map size).
-extern "C" int pl_softargmax3d_nhwc_bwd_ex(const float* logits, const float* stats, const float* gcoords, int64_t B,
-                                           int64_t J, int64_t H, int64_t W, float* dlogits, void* dl_planes, int planes_mode,
-                                           const float* dl_scale, void* stream) {
-  if (!logits || !stats || !gcoords || (!dlogits && !dl_planes)) PL_FAIL(PL_EINVAL, "pl_softargmax3d_nhwc_bwd: null pointer");
-  if ((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(dlogits)) & 15)
-    PL_FAIL(PL_EINVAL, "pl_softargmax3d_nhwc_bwd: tensors not 16-byte aligned");
-  if (B <= 0 || J <= 0 || H <= 0 || W <= 0 || B * J > 0x7fffffff || H * W > (1 << 24))
-    PL_FAIL(PL_ESHAPE, "pl_softargmax3d_nhwc_bwd: bad dims");
-  const int64_t n4 = B * H * W * J * 16;
-  if (n4 > (int64_t)INT32_MAX * NTHR) PL_FAIL(PL_ESHAPE, "pl_softargmax3d_nhwc_bwd: too large");
-  if (dl_planes && planes_mode == PL_F16X3 && !dl_scale) PL_FAIL(PL_EINVAL, "pl_softargmax3d_nhwc_bwd_ex: fp16 planes need dl_scale");
-  PlaneOut po;
-  PL_TRY(plane_out_of(planes_mode, dl_planes, n4 * 4, 1.0f, planes_mode == PL_F16X3 ? dl_scale : nullptr, &po,
-                      "pl_softargmax3d_nhwc_bwd_ex"));
-  hipLaunchKernelGGL(softargmax_nhwc_bwd_kernel<false>, dim3((unsigned)((n4 + NTHR - 1) / NTHR)), dim3(NTHR), 0,
-                     (hipStream_t)stream, logits, stats, gcoords, (int)J, (int)H, (int)W, n4, dlogits, po, HmIn{},
-                     (const float*)nullptr);
-  PL_CHECK_LAUNCH("softargmax_nhwc_bwd");
-  return PL_OK;
-}
-
-// pl_softargmax3d_nhwc_bwd_ex with the heat-map term: gsq [B*J] is the upstream gradient of sq; the fp16 planes' dl_scale
-// comes from pl_softargmax_hm_dl_scale (the bound grows by 4 |gsq|)
-extern "C" int pl_softargmax3d_nhwc_hm_bwd_ex(const float* logits, const float* target, const float* stats,
-                                              const float* gcoords, const float* gsq, int64_t B, int64_t J, int64_t H,
-                                              int64_t W, float sigma, const float* law, float* dlogits, void* dl_planes,
-                                              int planes_mode, const float* dl_scale, void* stream) {
-  const char* who = "pl_softargmax3d_nhwc_hm_bwd_ex";
-  if (!logits || !target || !stats || !gcoords || !gsq || (!dlogits && !dl_planes)) PL_FAIL(PL_EINVAL, "%s: null pointer", who);
-  if ((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(dlogits)) & 15)
-    PL_FAIL(PL_EINVAL, "%s: tensors not 16-byte aligned", who);
-  if (B <= 0 || J <= 0 || H <= 0 || W <= 0 || B * J > 0x7fffffff || H * W > (1 << 24)) PL_FAIL(PL_ESHAPE, "%s: bad dims", who);
-  const int64_t n4 = B * H * W * J * 16;
-  if (n4 > (int64_t)INT32_MAX * NTHR) PL_FAIL(PL_ESHAPE, "%s: too large", who);
-  if (dl_planes && planes_mode == PL_F16X3 && !dl_scale) PL_FAIL(PL_EINVAL, "%s: fp16 planes need dl_scale", who);
-  HmIn hm;
-  hm.target = target;
-  PL_TRY(heat_law_of(who, sigma, law, &hm.law));
-  PlaneOut po;
-  PL_TRY(plane_out_of(planes_mode, dl_planes, n4 * 4, 1.0f, planes_mode == PL_F16X3 ? dl_scale : nullptr, &po, who));
-  hipLaunchKernelGGL(softargmax_nhwc_bwd_kernel<true>, dim3((unsigned)((n4 + NTHR - 1) / NTHR)), dim3(NTHR), 0,
-                     (hipStream_t)stream, logits, stats, gcoords, (int)J, (int)H, (int)W, n4, dlogits, po, hm, gsq);
-  PL_CHECK_LAUNCH("softargmax_nhwc_hm_bwd");
-  return PL_OK;
+extern "C" int pl_softargmax_hm_dl_scale(const float* gcoords, const float* gsq, int64_t rows, int ncoord, float* scale2,
+                                         void* stream) {
+  return launch_softargmax_dl_scale({gcoords, gsq, rows, ncoord, scale2}, "pl_softargmax_hm_dl_scale", true,
+                                    (hipStream_t)stream);
 }

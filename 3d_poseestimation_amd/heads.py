@@ -12,111 +12,98 @@ import torch
 from . import _lib
 
 
+def _call(name, dev, *args):
+    """One launching entry point of the library on dev's current stream."""
+    with _lib.on_device(dev):
+        rc = getattr(_lib.lib(), name)(*args, _lib.current_stream_ptr())
+    _lib.check(rc, name)
+
+
+# The two autograd nodes, one per layout.  target: None, or the (BJ, ncoord) fp32 heat-map target with sigma and the law array
+# beside it -- then the _hm entry points run, the statistics are 8 wide instead of 5 and the node returns (coords, sq).
+# backward(ctx, *grads) takes either form; an output the loss does not use arrives as zeros.
+
 class _SoftArgmaxFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, BJ, D, H, W, ncoord, centred):
-        _lib.require_device_tensor(logits, "heat-map logits")
-        coords = torch.empty(BJ, ncoord, dtype=torch.float32, device=logits.device)
-        stats = torch.empty(BJ, 5, dtype=torch.float32, device=logits.device)
-        with _lib.on_device(logits.device):
-            rc = _lib.lib().pl_softargmax_fwd(logits.data_ptr(), BJ, D, H, W, ncoord, centred, coords.data_ptr(),
-                                              stats.data_ptr(), _lib.current_stream_ptr())
-        _lib.check(rc, "pl_softargmax_fwd")
-        ctx.save_for_backward(logits, stats)
-        ctx.dims = (BJ, D, H, W, ncoord, centred)
-        return coords
+    def forward(ctx, logits, dims, target, sigma, law):
+        BJ, D, H, W, ncoord, centred = dims
+        dev = logits.device
+        coords = torch.empty(BJ, ncoord, dtype=torch.float32, device=dev)
+        if target is None:
+            out, stats = coords, torch.empty(BJ, 5, dtype=torch.float32, device=dev)
+            _call("pl_softargmax_fwd", dev, logits.data_ptr(), BJ, D, H, W, ncoord, centred, coords.data_ptr(), stats.data_ptr())
+        else:
+            sq = torch.empty(BJ, dtype=torch.float32, device=dev)
+            out, stats = (coords, sq), torch.empty(BJ, 8, dtype=torch.float32, device=dev)
+            _call("pl_softargmax_hm_fwd", dev, logits.data_ptr(), target.data_ptr(), BJ, D, H, W, ncoord, centred, sigma, law,
+                  coords.data_ptr(), sq.data_ptr(), stats.data_ptr())
+        ctx.save_for_backward(logits, stats, target)
+        ctx.args = (dims, sigma, law)
+        return out
 
     @staticmethod
-    def backward(ctx, g):
-        logits, stats = ctx.saved_tensors
-        BJ, D, H, W, ncoord, centred = ctx.dims
-        g = g.contiguous()
-        dl = torch.empty_like(logits)
-        with _lib.on_device(logits.device):
-            rc = _lib.lib().pl_softargmax_bwd(logits.data_ptr(), stats.data_ptr(), g.data_ptr(), BJ, D, H, W, ncoord,
-                                              centred, dl.data_ptr(), _lib.current_stream_ptr())
-        _lib.check(rc, "pl_softargmax_bwd")
-        return dl, None, None, None, None, None, None
-
-
-def soft_argmax_3d(out, num_joints=17, depth_dim=64):
-    """(B, num_joints*depth_dim, H, W) logits -> (B, num_joints*3) coordinates in (-1, 1), (x, y, z) per joint."""
-    B, C, H, W = out.shape
-    if C != num_joints * depth_dim:
-        raise ValueError(f"expected {num_joints * depth_dim} channels, got {C}")
-    x = out.contiguous().float()
-    return _SoftArgmaxFn.apply(x, B * num_joints, depth_dim, H, W, 3, 1).reshape(B, num_joints * 3)
-
-
-def soft_argmax_2d(out, num_joints=17):
-    """(B, num_joints, H, W) logits -> (B, num_joints*2) coordinates in (0, 1), (x, y) per joint."""
-    B, C, H, W = out.shape
-    if C != num_joints:
-        raise ValueError(f"expected {num_joints} channels, got {C}")
-    x = out.contiguous().float()
-    return _SoftArgmaxFn.apply(x, B * num_joints, 1, H, W, 2, 0).reshape(B, num_joints * 2)
-
-
-def _pow2_scale_for_bound(bound):
-    """{S, 1/S} on the device: S the power of two that maps `bound` (a 0-d device tensor >= max |value|) into [2^13, 2^14)
-    -- the range scale of fp16 operand planes (conv.py PlaneLink); bound 0 / inf / nan -> 1."""
-    ok = torch.isfinite(bound) & (bound > 0)
-    e = torch.frexp(torch.where(ok, bound, torch.ones_like(bound))).exponent
-    S = torch.ldexp(torch.ones_like(bound), 14 - e)
-    S = torch.where(ok, S, torch.ones_like(bound))
-    return torch.stack([S, 1.0 / S]).float().contiguous()
+    def backward(ctx, *grads):
+        logits, stats, target = ctx.saved_tensors
+        (BJ, D, H, W, ncoord, centred), sigma, law = ctx.args
+        g = grads[0].contiguous()
+        if target is None:
+            dl = torch.empty_like(logits)
+            _call("pl_softargmax_bwd", logits.device, logits.data_ptr(), stats.data_ptr(), g.data_ptr(), BJ, D, H, W, ncoord,
+                  centred, dl.data_ptr())
+        else:
+            gsq = grads[1].contiguous()
+            dl = torch.empty_like(logits)
+            _call("pl_softargmax_hm_bwd", logits.device, logits.data_ptr(), target.data_ptr(), stats.data_ptr(), g.data_ptr(),
+                  gsq.data_ptr(), BJ, D, H, W, ncoord, centred, sigma, law, dl.data_ptr())
+        return dl, None, None, None, None
 
 
 class _SoftArgmax3dNHWCFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, num_joints, link=None):
-        ctx.link = link
+    def forward(ctx, x, num_joints, target, sigma, law, link):
         B, H, W, _ = x.shape
-        coords = torch.empty(B * num_joints, 3, dtype=torch.float32, device=x.device)
-        stats = torch.empty(B * num_joints, 5, dtype=torch.float32, device=x.device)
-        with _lib.on_device(x.device):
-            rc = _lib.lib().pl_softargmax3d_nhwc_fwd(x.data_ptr(), B, num_joints, H, W, coords.data_ptr(),
-                                                     stats.data_ptr(), _lib.current_stream_ptr())
-        _lib.check(rc, "pl_softargmax3d_nhwc_fwd")
-        ctx.save_for_backward(x, stats)
-        ctx.num_joints = num_joints
-        return coords
+        BJ, dev = B * num_joints, x.device
+        coords = torch.empty(BJ, 3, dtype=torch.float32, device=dev)
+        if target is None:
+            out, stats = coords, torch.empty(BJ, 5, dtype=torch.float32, device=dev)
+            _call("pl_softargmax3d_nhwc_fwd", dev, x.data_ptr(), B, num_joints, H, W, coords.data_ptr(), stats.data_ptr())
+        else:
+            sq = torch.empty(BJ, dtype=torch.float32, device=dev)
+            out, stats = (coords, sq), torch.empty(BJ, 8, dtype=torch.float32, device=dev)
+            _call("pl_softargmax3d_nhwc_hm_fwd", dev, x.data_ptr(), target.data_ptr(), B, num_joints, H, W, sigma, law,
+                  coords.data_ptr(), sq.data_ptr(), stats.data_ptr())
+        ctx.save_for_backward(x, stats, target)
+        ctx.args = (num_joints, sigma, law, link)
+        return out
 
     @staticmethod
-    def backward(ctx, g):
-        x, stats = ctx.saved_tensors
+    def backward(ctx, *grads):
+        x, stats, target = ctx.saved_tensors
+        num_joints, sigma, law, link = ctx.args
         B, H, W, _ = x.shape
-        g = g.contiguous()
+        dev = x.device
+        g = grads[0].contiguous()
+        gsq = None if target is None else grads[1].contiguous()
         dl = torch.empty_like(x)
-        link = ctx.link
+        f32, planes, mode, scale = dl.data_ptr(), None, 0, None
         if link is not None:
-            # the final convolution runs on the planes GEMM (conv.py): dlogits leave as a carrier of their planes, fp16 ones
-            # scaled by a power of two from the bound |dlogit| <= 2 max_(b,j) sum_c |g_c| (softmax weights <= 1)
-            link.dz_scale = torch.empty(2, dtype=torch.float32, device=x.device)
-            with _lib.on_device(x.device):
-                _lib.check(_lib.lib().pl_softargmax_dl_scale(g.data_ptr(), g.numel() // 3, 3, link.dz_scale.data_ptr(),
-                                                             _lib.current_stream_ptr()), "pl_softargmax_dl_scale")
-                rc = _lib.lib().pl_softargmax3d_nhwc_bwd_ex(x.data_ptr(), stats.data_ptr(), g.data_ptr(), B, ctx.num_joints, H, W,
-                                                            None, dl.data_ptr(), link.mode, link.dz_scale.data_ptr(),
-                                                            _lib.current_stream_ptr())
-            _lib.check(rc, "pl_softargmax3d_nhwc_bwd_ex")
-            return dl, None, None
-        with _lib.on_device(x.device):
-            rc = _lib.lib().pl_softargmax3d_nhwc_bwd(x.data_ptr(), stats.data_ptr(), g.data_ptr(), B, ctx.num_joints,
-                                                     H, W, dl.data_ptr(), _lib.current_stream_ptr())
-        _lib.check(rc, "pl_softargmax3d_nhwc_bwd")
-        return dl, None, None
-
-
-def soft_argmax_3d_nhwc(out, num_joints=17, link=None):
-    """(B, H, W, num_joints*64) NHWC logits (depth_dim 64) -> (B, num_joints*3), differentiable: what Model_3D's
-    final 1x1 convolution writes, read in place -- no NHWC <-> NCHW pass in either direction."""
-    x = out.contiguous()
-    _lib.require_device_tensor(x, "heat-map logits")
-    B, H, W, C = x.shape
-    if C != num_joints * 64:
-        raise ValueError(f"expected {num_joints * 64} channels (depth 64), got {C}")
-    return _SoftArgmax3dNHWCFn.apply(x, num_joints, link).reshape(B, num_joints * 3)
+            # the final convolution runs on the planes GEMM (conv.py): dlogits leave as a carrier of their planes only, fp16
+            # ones scaled by a power of two from the bound |dlogit| <= 2 max_(b,j) (sum_c |g_c| + 2 |gsq|) (softmax weights <= 1)
+            link.dz_scale = torch.empty(2, dtype=torch.float32, device=dev)
+            f32, planes, mode, scale = None, f32, link.mode, link.dz_scale.data_ptr()
+            if target is None:
+                _call("pl_softargmax_dl_scale", dev, g.data_ptr(), g.numel() // 3, 3, scale)
+            else:
+                _call("pl_softargmax_hm_dl_scale", dev, g.data_ptr(), gsq.data_ptr(), g.numel() // 3, 3, scale)
+        if target is not None:
+            _call("pl_softargmax3d_nhwc_hm_bwd_ex", dev, x.data_ptr(), target.data_ptr(), stats.data_ptr(), g.data_ptr(),
+                  gsq.data_ptr(), B, num_joints, H, W, sigma, law, f32, planes, mode, scale)
+        elif link is not None:
+            _call("pl_softargmax3d_nhwc_bwd_ex", dev, x.data_ptr(), stats.data_ptr(), g.data_ptr(), B, num_joints, H, W, f32,
+                  planes, mode, scale)
+        else:
+            _call("pl_softargmax3d_nhwc_bwd", dev, x.data_ptr(), stats.data_ptr(), g.data_ptr(), B, num_joints, H, W, f32)
+        return dl, None, None, None, None, None
 
 
 # ---- heat-map supervision: sq[b, j] = sum over voxels (softmax(logits) - Gaussian target)^2, neither tensor stored -------
@@ -151,8 +138,48 @@ def _hm_target(target, BJ, ncoord, device):
     t = target.detach()
     if t.numel() != BJ * ncoord:
         raise ValueError(f"heat-map target has {t.numel()} values, expected {BJ} x {ncoord} (one coordinate set per joint)")
-    t = t.to(device=device, dtype=torch.float32).reshape(BJ, ncoord).contiguous()
-    return t
+    return t.to(device=device, dtype=torch.float32).reshape(BJ, ncoord).contiguous()
+
+
+def _node_args(hm, dims, centred, BJ, ncoord, device):
+    """hm = None or (target, sigma, centre) -> the nodes' (target, sigma, law) for a map of dims = (W, H, D)."""
+    if hm is None:
+        return None, 0.0, None
+    target, sigma, centre = hm
+    law = _law_array(heatmap_law(*dims, centred, centre))
+    return _hm_target(target, BJ, ncoord, device), float(sigma), law
+
+
+def _shaped(out, B, num_joints, ncoord):
+    if isinstance(out, tuple):
+        return out[0].reshape(B, num_joints * ncoord), out[1].reshape(B, num_joints)
+    return out.reshape(B, num_joints * ncoord)
+
+
+def head_nchw(logits, num_joints, depth_dim, hm=None, centred=None):
+    """What the four NCHW functions below do.  hm: None, or (target, sigma, centre) -> (coords, sq).  centred: the 3-D
+    head's three coordinates in (-1, 1), or the 2-D head's two in (0, 1); None: by depth_dim (depth 1 is the 2-D head)."""
+    centred = depth_dim > 1 if centred is None else centred
+    ncoord = 3 if centred else 2
+    B, C, H, W = logits.shape
+    if C != num_joints * depth_dim:
+        raise ValueError(f"expected {num_joints * depth_dim} channels, got {C}")
+    x = logits.contiguous().float()
+    _lib.require_device_tensor(x, "heat-map logits")
+    BJ = B * num_joints
+    node_args = _node_args(hm, (W, H, depth_dim), centred, BJ, ncoord, x.device)
+    return _shaped(_SoftArgmaxFn.apply(x, (BJ, depth_dim, H, W, ncoord, int(centred)), *node_args), B, num_joints, ncoord)
+
+
+def head_nhwc(logits, num_joints, hm=None, link=None):
+    """What the two NHWC functions below do; hm as in head_nchw, link: conv.PlaneLink of the final convolution or None."""
+    x = logits.contiguous()
+    _lib.require_device_tensor(x, "heat-map logits")
+    B, H, W, C = x.shape
+    if C != num_joints * 64:
+        raise ValueError(f"expected {num_joints * 64} channels (depth 64), got {C}")
+    node_args = _node_args(hm, (W, H, 64), True, B * num_joints, 3, x.device)
+    return _shaped(_SoftArgmax3dNHWCFn.apply(x, num_joints, *node_args, link), B, num_joints, 3)
 
 
 def gaussian_heatmap(target, dims, sigma=0.5, centre="head"):
@@ -183,34 +210,20 @@ def gaussian_heatmap(target, dims, sigma=0.5, centre="head"):
     return out
 
 
-class _SoftArgmaxHmFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, target, BJ, D, H, W, ncoord, centred, sigma, law):
-        _lib.require_device_tensor(logits, "heat-map logits")
-        coords = torch.empty(BJ, ncoord, dtype=torch.float32, device=logits.device)
-        sq = torch.empty(BJ, dtype=torch.float32, device=logits.device)
-        stats = torch.empty(BJ, 8, dtype=torch.float32, device=logits.device)
-        with _lib.on_device(logits.device):
-            rc = _lib.lib().pl_softargmax_hm_fwd(logits.data_ptr(), target.data_ptr(), BJ, D, H, W, ncoord, centred, sigma,
-                                                 _law_array(law), coords.data_ptr(), sq.data_ptr(), stats.data_ptr(),
-                                                 _lib.current_stream_ptr())
-        _lib.check(rc, "pl_softargmax_hm_fwd")
-        ctx.save_for_backward(logits, target, stats)
-        ctx.dims = (BJ, D, H, W, ncoord, centred, sigma, law)
-        return coords, sq
+def soft_argmax_3d(out, num_joints=17, depth_dim=64):
+    """(B, num_joints*depth_dim, H, W) logits -> (B, num_joints*3) coordinates in (-1, 1), (x, y, z) per joint."""
+    return head_nchw(out, num_joints, depth_dim, None, True)
 
-    @staticmethod
-    def backward(ctx, g, gsq):
-        logits, target, stats = ctx.saved_tensors
-        BJ, D, H, W, ncoord, centred, sigma, law = ctx.dims
-        g, gsq = g.contiguous(), gsq.contiguous()
-        dl = torch.empty_like(logits)
-        with _lib.on_device(logits.device):
-            rc = _lib.lib().pl_softargmax_hm_bwd(logits.data_ptr(), target.data_ptr(), stats.data_ptr(), g.data_ptr(),
-                                                 gsq.data_ptr(), BJ, D, H, W, ncoord, centred, sigma, _law_array(law),
-                                                 dl.data_ptr(), _lib.current_stream_ptr())
-        _lib.check(rc, "pl_softargmax_hm_bwd")
-        return (dl,) + (None,) * 9
+
+def soft_argmax_2d(out, num_joints=17):
+    """(B, num_joints, H, W) logits -> (B, num_joints*2) coordinates in (0, 1), (x, y) per joint."""
+    return head_nchw(out, num_joints, 1)
+
+
+def soft_argmax_3d_nhwc(out, num_joints=17, link=None):
+    """(B, H, W, num_joints*64) NHWC logits (depth_dim 64) -> (B, num_joints*3), differentiable: what Model_3D's
+    final 1x1 convolution writes, read in place -- no NHWC <-> NCHW pass in either direction."""
+    return head_nhwc(out, num_joints, None, link)
 
 
 def soft_argmax_3d_hm(out, target, sigma=0.5, centre="head", num_joints=17, depth_dim=64):
@@ -218,80 +231,16 @@ def soft_argmax_3d_hm(out, target, sigma=0.5, centre="head", num_joints=17, dept
     in the head's own (x, y, z) order and range -> (coords (B, num_joints*3), sq (B, num_joints)); sq[b, j] is the squared
     error of joint j's normalised heat-map against the Gaussian target centred at its coordinate (gaussian_heatmap), summed
     over the voxels.  Both are differentiable in the logits; the target takes no gradient."""
-    B, C, H, W = out.shape
-    if C != num_joints * depth_dim:
-        raise ValueError(f"expected {num_joints * depth_dim} channels, got {C}")
-    x = out.contiguous().float()
-    law = heatmap_law(W, H, depth_dim, True, centre)
-    t = _hm_target(target, B * num_joints, 3, x.device)
-    coords, sq = _SoftArgmaxHmFn.apply(x, t, B * num_joints, depth_dim, H, W, 3, 1, float(sigma), law)
-    return coords.reshape(B, num_joints * 3), sq.reshape(B, num_joints)
+    return head_nchw(out, num_joints, depth_dim, (target, sigma, centre), True)
 
 
 def soft_argmax_2d_hm(out, target, sigma=0.5, centre="head", num_joints=17):
     """soft_argmax_2d + heat-map supervision: (B, num_joints, H, W) logits, target (B, num_joints*2) in (0, 1) ->
     (coords (B, num_joints*2), sq (B, num_joints)).  centre="reference" is not defined for this head."""
-    B, C, H, W = out.shape
-    if C != num_joints:
-        raise ValueError(f"expected {num_joints} channels, got {C}")
-    x = out.contiguous().float()
-    law = heatmap_law(W, H, 1, False, centre)
-    t = _hm_target(target, B * num_joints, 2, x.device)
-    coords, sq = _SoftArgmaxHmFn.apply(x, t, B * num_joints, 1, H, W, 2, 0, float(sigma), law)
-    return coords.reshape(B, num_joints * 2), sq.reshape(B, num_joints)
-
-
-class _SoftArgmax3dNHWCHmFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, target, num_joints, sigma, law, link=None):
-        ctx.link = link
-        B, H, W, _ = x.shape
-        coords = torch.empty(B * num_joints, 3, dtype=torch.float32, device=x.device)
-        sq = torch.empty(B * num_joints, dtype=torch.float32, device=x.device)
-        stats = torch.empty(B * num_joints, 8, dtype=torch.float32, device=x.device)
-        with _lib.on_device(x.device):
-            rc = _lib.lib().pl_softargmax3d_nhwc_hm_fwd(x.data_ptr(), target.data_ptr(), B, num_joints, H, W, sigma,
-                                                        _law_array(law), coords.data_ptr(), sq.data_ptr(), stats.data_ptr(),
-                                                        _lib.current_stream_ptr())
-        _lib.check(rc, "pl_softargmax3d_nhwc_hm_fwd")
-        ctx.save_for_backward(x, target, stats)
-        ctx.args = (num_joints, sigma, law)
-        return coords, sq
-
-    @staticmethod
-    def backward(ctx, g, gsq):
-        x, target, stats = ctx.saved_tensors
-        num_joints, sigma, law = ctx.args
-        B, H, W, _ = x.shape
-        g, gsq = g.contiguous(), gsq.contiguous()
-        dl = torch.empty_like(x)
-        link = ctx.link
-        scale, planes_mode, f32 = None, 0, dl.data_ptr()
-        with _lib.on_device(x.device):
-            if link is not None:
-                # as _SoftArgmax3dNHWCFn: dlogits leave as a carrier of their planes; the fp16 scale's bound grows by 4 |gsq|
-                link.dz_scale = torch.empty(2, dtype=torch.float32, device=x.device)
-                _lib.check(_lib.lib().pl_softargmax_hm_dl_scale(g.data_ptr(), gsq.data_ptr(), g.numel() // 3, 3,
-                                                                link.dz_scale.data_ptr(), _lib.current_stream_ptr()),
-                           "pl_softargmax_hm_dl_scale")
-                scale, planes_mode, f32 = link.dz_scale.data_ptr(), link.mode, None
-            rc = _lib.lib().pl_softargmax3d_nhwc_hm_bwd_ex(x.data_ptr(), target.data_ptr(), stats.data_ptr(), g.data_ptr(),
-                                                           gsq.data_ptr(), B, num_joints, H, W, sigma, _law_array(law), f32,
-                                                           dl.data_ptr() if link is not None else None, planes_mode, scale,
-                                                           _lib.current_stream_ptr())
-        _lib.check(rc, "pl_softargmax3d_nhwc_hm_bwd_ex")
-        return dl, None, None, None, None, None
+    return head_nchw(out, num_joints, 1, (target, sigma, centre))
 
 
 def soft_argmax_3d_nhwc_hm(out, target, sigma=0.5, centre="head", num_joints=17, link=None):
     """soft_argmax_3d_nhwc + heat-map supervision on the NHWC logits (B, H, W, num_joints*64), read in place:
     -> (coords (B, num_joints*3), sq (B, num_joints)); see soft_argmax_3d_hm."""
-    x = out.contiguous()
-    _lib.require_device_tensor(x, "heat-map logits")
-    B, H, W, C = x.shape
-    if C != num_joints * 64:
-        raise ValueError(f"expected {num_joints * 64} channels (depth 64), got {C}")
-    law = heatmap_law(W, H, 64, True, centre)
-    t = _hm_target(target, B * num_joints, 3, x.device)
-    coords, sq = _SoftArgmax3dNHWCHmFn.apply(x, t, num_joints, float(sigma), law, link)
-    return coords.reshape(B, num_joints * 3), sq.reshape(B, num_joints)
+    return head_nhwc(out, num_joints, (target, sigma, centre), link)

@@ -381,6 +381,43 @@ def test_python_heads_autograd_and_heatmap_mse(pkg):
     assert y.grad is None and not y.requires_grad
 
 
+@pytest.mark.parametrize("which", ["coords_only", "sq_only"])
+@pytest.mark.parametrize("layout", ["nchw_3d", "nchw_2d", "nhwc"])
+def test_a_loss_on_one_output_of_the_hm_heads(pkg, layout, which):
+    """The heads' autograd node serves the plain and the _hm functions, so a loss that uses one of its two outputs reaches
+    backward with zeros for the other.  Coordinates only: x.grad is bitwise the plain function's.  sq only: bitwise what the
+    _hm backward entry point writes for explicit zero gcoords."""
+    B, J = 2, 3
+    D, H, W = {"nchw_3d": (8, 4, 8), "nchw_2d": (1, 4, 8), "nhwc": (64, 3, 5)}[layout]
+    centred = layout != "nchw_2d"
+    nc = 3 if centred else 2
+    g = torch.Generator().manual_seed(41)
+    shape = (B, H, W, J * 64) if layout == "nhwc" else (B, J * D, H, W)
+    x = (torch.randn(shape, generator=g) * 2).to(DEV)
+    y = torch.from_numpy(_targets(B * J, centred, (W, H, D), ["rnd", "hi", "tie"])).to(DEV).reshape(B, J * nc)
+    gc, gs = torch.randn(B, J * nc, generator=g).to(DEV), torch.randn(B, J, generator=g).to(DEV)
+    plain, hm = {"nchw_3d": (lambda v: pkg.soft_argmax_3d(v, J, D), lambda v: pkg.soft_argmax_3d_hm(v, y, num_joints=J, depth_dim=D)),
+                 "nchw_2d": (lambda v: pkg.soft_argmax_2d(v, J), lambda v: pkg.soft_argmax_2d_hm(v, y, num_joints=J)),
+                 "nhwc": (lambda v: pkg.soft_argmax_3d_nhwc(v, J), lambda v: pkg.soft_argmax_3d_nhwc_hm(v, y, num_joints=J))}[layout]
+    xr = x.clone().requires_grad_()
+    coords, sq = hm(xr)
+    if which == "coords_only":
+        (coords * gc).sum().backward()
+        xp = x.clone().requires_grad_()
+        (plain(xp) * gc).sum().backward()
+        assert torch.equal(xr.grad, xp.grad)
+        return
+    (sq * gs).sum().backward()
+    law = pkg.heatmap_law(W, H, D, centred, "head")
+    zero, gst = torch.zeros(B * J, nc, device=DEV), gs.reshape(B * J).contiguous()
+    if layout == "nhwc":
+        want = _run_nhwc(pkg, x, y.reshape(B * J, nc), 0.5, law, zero, gst)["dl"]
+    else:
+        want = _run_nchw(pkg, x.reshape(B * J, D, H, W).cpu().numpy(), y.reshape(B * J, nc).cpu().numpy(), 0.5, law, nc,
+                         int(centred), zero.cpu().numpy(), gst.cpu().numpy())["dl"].reshape(shape)
+    assert bool(xr.grad.abs().max() > 0) and torch.equal(xr.grad, want)
+
+
 def test_error_paths(pkg):
     x = torch.zeros(2, 8, 8, 3 * 64, device=DEV)
     y = torch.zeros(2, 9, device=DEV)
@@ -417,14 +454,14 @@ def _train_step(pkg, m, frames, y, lam, capture=None, sigma=0.5):
     backbone = importlib.import_module("3d_poseestimation_amd.backbone")
     m.train()
     m.zero_grad(set_to_none=True)
-    orig = backbone.soft_argmax_3d_nhwc_hm
+    orig = backbone.head_nhwc
 
-    def spy(out, *a, **k):
-        if capture is not None:
-            capture.append((out.detach().clone(), a[4] if len(a) > 4 else k.get("link")))
-        return orig(out, *a, **k)
+    def spy(out, num_joints, hm=None, link=None):
+        if capture is not None and hm is not None:
+            capture.append((out.detach().clone(), link))
+        return orig(out, num_joints, hm, link)
 
-    backbone.soft_argmax_3d_nhwc_hm = spy
+    backbone.head_nhwc = spy
     try:
         if lam is None:
             loss = ((m(frames) - y) ** 2).mean()
@@ -434,7 +471,7 @@ def _train_step(pkg, m, frames, y, lam, capture=None, sigma=0.5):
             loss = ((coords - y) ** 2).mean() + lam * 1000 * pkg.heatmap_mse(sq, 64 * H * W)
         loss.backward()
     finally:
-        backbone.soft_argmax_3d_nhwc_hm = orig
+        backbone.head_nhwc = orig
     return loss.detach()
 
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""sha256 of everything the lifter's and the conv path's BatchNorm launches and the flat optimizers write, one line per
-(case, buffer):
+"""sha256 of everything the lifter's and the conv path's BatchNorm launches, the flat optimizers and the soft-argmax heads
+write, one line per (case, buffer):
 
     python tools/route_hashes.py > hashes.txt          (POSELIFT_LIB=... picks another build of the library)
 
@@ -312,7 +312,177 @@ def optimizer_cases():
     case_flat_adam("flat-adam/graph/clip", capturable=True, graphed=True, **CLIP)
 
 
+# ------------------------------------------------------------------------------------------------ the soft-argmax heads
+FILL = -7.0                                       # what no launch writes hashes as this
+
+
+def heads_inputs(BJ, n, ncoord, centred, seed):
+    """logits (BJ, n) with one -inf, targets with one at the map's edge and one NaN, upstream gradients of coords and sq"""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(BJ, n, generator=g) * 3
+    x[BJ - 1, n // 3] = float("-inf")
+    t = torch.rand(BJ, ncoord, generator=g) * (1.6 if centred else 0.8) + (-0.8 if centred else 0.1)
+    t[0] = 1.0                                    # mu = dim: the window hangs over the last index
+    t[1, 0] = float("nan")
+    gc, gs = torch.randn(BJ, ncoord, generator=g), torch.randn(BJ, generator=g)
+    gs[0] = 0.0
+    return [v.to(DEV) for v in (x, t, gc, gs)]
+
+
+def hm_variants(centred):
+    return (None, (0.5, "head"), (1.75, "reference" if centred else "head"))
+
+
+def law_of(W, H, D, centred, centre):
+    return (ctypes.c_float * 6)(*pkg.heatmap_law(W, H, D, centred, centre))
+
+
+def full(*shape):
+    return torch.full(shape, FILL, device=DEV)
+
+
+def case_heads_nchw(BJ, D, H, W, ncoord, centred):
+    L, s = _lib.lib(), _lib.current_stream_ptr()
+    x, t, gc, gs = heads_inputs(BJ, D * H * W, ncoord, centred, 7 * D + W)
+    for hm in hm_variants(centred):
+        name = f"heads/abi/nchw/{BJ}x{D}x{H}x{W}/" + ("plain" if hm is None else f"hm-s{hm[0]}-{hm[1]}")
+        coords, sq, stats, dl = full(BJ, ncoord), full(BJ), full(BJ, 5 if hm is None else 8), full(BJ, D * H * W)
+        if hm is None:
+            rc = L.pl_softargmax_fwd(x.data_ptr(), BJ, D, H, W, ncoord, centred, coords.data_ptr(), stats.data_ptr(), s)
+            _lib.check(rc, "pl_softargmax_fwd")
+            rc = L.pl_softargmax_bwd(x.data_ptr(), stats.data_ptr(), gc.data_ptr(), BJ, D, H, W, ncoord, centred, dl.data_ptr(), s)
+            _lib.check(rc, "pl_softargmax_bwd")
+        else:
+            law = law_of(W, H, D, centred, hm[1])
+            rc = L.pl_softargmax_hm_fwd(x.data_ptr(), t.data_ptr(), BJ, D, H, W, ncoord, centred, hm[0], law, coords.data_ptr(),
+                                        sq.data_ptr(), stats.data_ptr(), s)
+            _lib.check(rc, "pl_softargmax_hm_fwd")
+            rc = L.pl_softargmax_hm_bwd(x.data_ptr(), t.data_ptr(), stats.data_ptr(), gc.data_ptr(), gs.data_ptr(), BJ, D, H, W,
+                                        ncoord, centred, hm[0], law, dl.data_ptr(), s)
+            _lib.check(rc, "pl_softargmax_hm_bwd")
+        torch.cuda.synchronize()
+        emit(name, stats=stats, coords=coords, sq=sq, dlogits=dl)
+
+
+def case_heads_nhwc(B, H, W, J):
+    L, s = _lib.lib(), _lib.current_stream_ptr()
+    BJ, shape = B * J, (B, H, W, J * 64)
+    x, t, gc, gs = heads_inputs(BJ, H * W * 64, 3, True, 11 * H + W)
+    x = x.reshape(shape)                          # (the values' order does not matter: any layout of random logits)
+    for hm in hm_variants(True):
+        name = f"heads/abi/nhwc/{B}x{H}x{W}x{J}/" + ("plain" if hm is None else f"hm-s{hm[0]}-{hm[1]}")
+        coords, sq, stats, scale = full(BJ, 3), full(BJ), full(BJ, 5 if hm is None else 8), full(2)
+        law = None if hm is None else law_of(W, H, 64, True, hm[1])
+        if hm is None:
+            rc = L.pl_softargmax3d_nhwc_fwd(x.data_ptr(), B, J, H, W, coords.data_ptr(), stats.data_ptr(), s)
+            _lib.check(rc, "pl_softargmax3d_nhwc_fwd")
+            _lib.check(L.pl_softargmax_dl_scale(gc.data_ptr(), BJ, 3, scale.data_ptr(), s), "pl_softargmax_dl_scale")
+        else:
+            rc = L.pl_softargmax3d_nhwc_hm_fwd(x.data_ptr(), t.data_ptr(), B, J, H, W, hm[0], law, coords.data_ptr(),
+                                               sq.data_ptr(), stats.data_ptr(), s)
+            _lib.check(rc, "pl_softargmax3d_nhwc_hm_fwd")
+            rc = L.pl_softargmax_hm_dl_scale(gc.data_ptr(), gs.data_ptr(), BJ, 3, scale.data_ptr(), s)
+            _lib.check(rc, "pl_softargmax_hm_dl_scale")
+        torch.cuda.synchronize()
+        emit(name, stats=stats, coords=coords, sq=sq, scale=scale)
+        forms = [("f32", True, False, 0), ("planes-bf16", False, True, 1), ("planes-f16x3", False, True, 3), ("both-f16x3", True, True, 3)]
+        for form, want_f32, want_planes, mode in forms:
+            dl, carrier = full(*shape), full(*shape)
+            tail = (dl.data_ptr() if want_f32 else None, carrier.data_ptr() if want_planes else None, mode, scale.data_ptr(), s)
+            if hm is None:
+                rc = L.pl_softargmax3d_nhwc_bwd_ex(x.data_ptr(), stats.data_ptr(), gc.data_ptr(), B, J, H, W, *tail)
+                _lib.check(rc, "pl_softargmax3d_nhwc_bwd_ex")
+            else:
+                rc = L.pl_softargmax3d_nhwc_hm_bwd_ex(x.data_ptr(), t.data_ptr(), stats.data_ptr(), gc.data_ptr(), gs.data_ptr(), B, J,
+                                                      H, W, hm[0], law, *tail)
+                _lib.check(rc, "pl_softargmax3d_nhwc_hm_bwd_ex")
+            torch.cuda.synchronize()
+            emit(f"{name}/bwd-{form}", dlogits=dl, planes=carrier.view(torch.int32))
+        if hm is None:
+            dl = full(*shape)
+            rc = L.pl_softargmax3d_nhwc_bwd(x.data_ptr(), stats.data_ptr(), gc.data_ptr(), B, J, H, W, dl.data_ptr(), s)
+            _lib.check(rc, "pl_softargmax3d_nhwc_bwd")
+            torch.cuda.synchronize()
+            emit(f"{name}/bwd-plain-entry", dlogits=dl)
+    # the two scale kernels on a non-finite row
+    gc[BJ - 1, 1] = float("inf")
+    s1, s2 = full(2), full(2)
+    _lib.check(L.pl_softargmax_dl_scale(gc.data_ptr(), BJ, 3, s1.data_ptr(), s), "pl_softargmax_dl_scale")
+    _lib.check(L.pl_softargmax_hm_dl_scale(gc.data_ptr(), gs.data_ptr(), BJ, 3, s2.data_ptr(), s), "pl_softargmax_hm_dl_scale")
+    torch.cuda.synchronize()
+    emit(f"heads/abi/nhwc/{B}x{H}x{W}x{J}/scale-nonfinite", plain=s1, hm=s2)
+
+
+def case_heads_public(name, x, J, fn, fn_hm, ncoord, centred, **kw):
+    """coords, sq and x.grad of a public function and its _hm twin"""
+    B = x.shape[0]
+    _, t, gc, gs = heads_inputs(B * J, 1, ncoord, centred, 3 * J + ncoord)
+    t, gc, gs = t.reshape(B, J * ncoord), gc.reshape(B, J * ncoord), gs.reshape(B, J)
+    for hm in hm_variants(centred):
+        xr = x.clone().requires_grad_(True)
+        if hm is None:
+            coords, sq = fn(xr, num_joints=J, **kw), None
+            (coords * gc).sum().backward()
+        else:
+            coords, sq = fn_hm(xr, t, hm[0], hm[1], num_joints=J, **kw)
+            ((coords * gc).sum() + (sq * gs).sum()).backward()
+        torch.cuda.synchronize()
+        emit(f"heads/public/{name}/" + ("plain" if hm is None else f"hm-s{hm[0]}-{hm[1]}"), coords=coords, sq=sq, dx=xr.grad)
+
+
+def case_heads_model(dtype):
+    """one Model_3D training step (the NHWC head behind the final convolution, with its plane link where the route has one)"""
+    frames = pkg.synth.seeded_frames(2, 32).to(DEV)
+    y = (torch.rand(2, 51, generator=torch.Generator().manual_seed(1)) * 1.6 - 0.8).to(DEV)
+    for with_hm in (False, True):
+        m = pkg.Model_3D(compute_dtype=dtype)
+        m.load_state_dict(pkg.synth.seeded_state(m.state_dict(), 51))
+        m = m.to(DEV).train()
+        if with_hm:
+            coords, sq = m(frames, heatmap_target=y)
+            (((coords - y) ** 2).mean() + 1000 * pkg.heatmap_mse(sq, 64 * 64 * 64)).backward()
+        else:
+            coords, sq = m(frames), None
+            ((coords - y) ** 2).mean().backward()
+        torch.cuda.synchronize()
+        emit(f"heads/model3d/{dtype}/" + ("hm" if with_hm else "plain"), coords=coords, sq=sq,
+             final_grads=[m.final_layer.weight.grad, m.final_layer.bias.grad])
+
+
+def heads_cases():
+    # (BJ, D, H, W): one chunk; 16384 voxels = two chunks of the backward; a map smaller than the workgroup; the 2-D head
+    for BJ, D, H, W, ncoord, centred in ((6, 8, 4, 8, 3, 1), (6, 16, 16, 64, 3, 1), (2, 1, 3, 4, 3, 1), (6, 1, 12, 16, 2, 0)):
+        case_heads_nchw(BJ, D, H, W, ncoord, centred)
+    for B, H, W, J in ((2, 3, 5, 3), (2, 8, 8, 3)):          # 15 pixels: a ragged last pass of the four wavefronts
+        case_heads_nhwc(B, H, W, J)
+    for BJ, D, H, W in ((4, 8, 4, 8), (4, 1, 12, 16)):
+        ncoord = 3 if D > 1 else 2
+        _, t, _, _ = heads_inputs(BJ, 1, ncoord, D > 1, 5)
+        for sigma, centre in hm_variants(D > 1)[1:]:
+            out = full(BJ, D, H, W)
+            rc = _lib.lib().pl_heatmap_gaussian(t.data_ptr(), BJ, D, H, W, ncoord, sigma, law_of(W, H, D, D > 1, centre),
+                                                out.data_ptr(), _lib.current_stream_ptr())
+            _lib.check(rc, "pl_heatmap_gaussian")
+            torch.cuda.synchronize()
+            emit(f"heads/abi/gaussian/{BJ}x{D}x{H}x{W}/s{sigma}-{centre}", out=out)
+    g = torch.Generator().manual_seed(77)
+    for D, H, W in ((8, 4, 8), (16, 16, 64)):
+        x = (torch.randn(2, 3 * D, H, W, generator=g) * 3).to(DEV)
+        case_heads_public(f"3d/2x3x{D}x{H}x{W}", x, 3, pkg.soft_argmax_3d, pkg.soft_argmax_3d_hm, 3, True, depth_dim=D)
+    x = (torch.randn(1, 2, 3, 4, generator=g) * 3).to(DEV)
+    case_heads_public("3d/1x2x1x3x4", x, 2, pkg.soft_argmax_3d, pkg.soft_argmax_3d_hm, 3, True, depth_dim=1)
+    x = (torch.randn(2, 3, 12, 16, generator=g) * 3).to(DEV)
+    case_heads_public("2d/2x3x12x16", x, 3, pkg.soft_argmax_2d, pkg.soft_argmax_2d_hm, 2, False)
+    for H, W in ((3, 5), (8, 8)):
+        x = (torch.randn(2, H, W, 3 * 64, generator=g) * 3).to(DEV)
+        x[1, H - 1, W - 1, 70] = float("-inf")
+        case_heads_public(f"nhwc/2x{H}x{W}x3", x, 3, pkg.soft_argmax_3d_nhwc, pkg.soft_argmax_3d_nhwc_hm, 3, True)
+    for dtype in ("f16x3", "bf16x6"):                         # the plane link; the fp32-grade direct route
+        case_heads_model(dtype)
+
+
 if __name__ == "__main__":
     lifter_cases()
     conv_cases()
     optimizer_cases()
+    heads_cases()
