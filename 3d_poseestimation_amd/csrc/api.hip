@@ -428,7 +428,11 @@ PlanesGemmArgs planes_args(int pkind, const unsigned short* A, int64_t a_plane, 
 
 int gemm_out_layer(bool narrow, const float* h, const float* W, const float* bias, float* y, int M, int N, int K,
                    float* slabs, hipStream_t s) {
-  if (narrow) return launch_skinny_narrow_out(h, W, bias, y, M, K, N, slabs, s);
+  if (narrow) {
+    SkinnyNarrowOutArgs a = {};
+    a.h = h; a.W = W; a.B = M; a.H = K; a.N = N; a.part = slabs; a.reduce = true; a.bias = bias; a.y = y;
+    return launch_skinny_narrow_out(a, s);
+  }
   GemmArgs g = {};
   g.A = h; g.B = W; g.M = M; g.N = N; g.K = K; g.lda = K; g.ldb = K; g.ldc = N;
   const int splits = out_splits(M, N, K);
@@ -690,7 +694,10 @@ static int fwd_saved_impl(const PLDesc* d, const float* x, float* y, int64_t B, 
       g.stat_m2 = g.stat_sum + (size_t)r.groups * H;
     }
     if (r.lin == Lin::Skinny) {
-      PL_TRY(launch_skinny_wide_out(a_in, ly.W, ly.b, g.C, (int)B, ly.K, H, false, g.stat_sum, g.stat_m2, s));
+      SkinnyWideOutArgs a = {};
+      a.X = a_in; a.W = ly.W; a.bias = ly.b; a.out = g.C; a.B = (int)B; a.K = ly.K; a.H = H;
+      a.stat_sum = g.stat_sum; a.stat_m2 = g.stat_m2;
+      PL_TRY(launch_skinny_wide_out(a, s));
     } else if (r.lin == Lin::PlanesMid || r.lin == Lin::F32Mid) {
       SmallLinearStatsArgs q = {};
       if (r.lin == Lin::PlanesMid) q.a_planes = u16(ws, w.actp[l - 1]); else q.a = a_in;
@@ -739,9 +746,11 @@ static int fwd_saved_impl(const PLDesc* d, const float* x, float* y, int64_t B, 
     a_in = ap.act;
   }
   if (head_slabs) return PL_OK;
-  if (defer_out_reduce)   // (the fused train step: y = bias + slabs is formed by the MSE pass, mse_partial_from_slabs)
-    return launch_skinny_narrow_out(a_in, d->params + P.off[4 * w.L], d->params + P.off[4 * w.L + 1], y, (int)B, H, d->out_dim,
-                                    f32(ws, w.slabs), s, false);
+  if (defer_out_reduce) {   // (the fused train step: y = bias + slabs is formed by the MSE pass, mse_partial_from_slabs)
+    SkinnyNarrowOutArgs a = {};
+    a.h = a_in; a.W = d->params + P.off[4 * w.L]; a.B = (int)B; a.H = H; a.N = d->out_dim; a.part = f32(ws, w.slabs);
+    return launch_skinny_narrow_out(a, s);
+  }
   return gemm_out_layer(w.out_narrow, a_in, d->params + P.off[4 * w.L], d->params + P.off[4 * w.L + 1], y, (int)B,
                         d->out_dim, H, f32(ws, w.slabs), s);
 }
@@ -808,13 +817,19 @@ struct BwdCtx {
 // first layer) -- the range maxima per (64-row block, 64-column strip); the top layer's gradient comes from the skinny
 // kernel, whose strips are 32 columns wide.
 int bnr_amax_pairs(const BwdCtx& c, int l) { return (c.B / 64) * (c.H / (l == c.w.L - 1 ? 32 : 64)); }
-void fill_bnr(const BwdCtx& c, int l, GemmArgs& e) {
+BnrEpilogue bnr_of(const BwdCtx& c, int l) {
   const BnSaved sv = saved_of(c.w, c.ws, l);
   const bool scaled = c.w.pkind == 2 && l > 0;
   const BnrSlab slab = bnr_slab(c.d, c.w, c.ws, c.B / 64, scaled ? bnr_amax_pairs(c, l) : 0, c.eval_bn);
-  e.bnr_z = sv.z; e.bnr_bits = sv.bits; e.bnr_mean = sv.mean; e.bnr_rstd = sv.rstd; e.bnr_kscale = c.kscale;
-  e.bnr_part_dy = slab.mine; e.bnr_part_dyz = slab.mine + (size_t)(c.B / 64) * c.H;
-  e.bnr_amax = scaled ? slab.amax_mine : nullptr;
+  BnrEpilogue b = {};
+  b.z = sv.z; b.bits = sv.bits; b.mean = sv.mean; b.rstd = sv.rstd; b.kscale = c.kscale;
+  b.part_dy = slab.mine; b.part_dyz = slab.mine + (size_t)(c.B / 64) * c.H;
+  b.amax = scaled ? slab.amax_mine : nullptr;
+  return b;
+}
+void set_bnr(GemmArgs& e, const BnrEpilogue& b) {     // the planes GEMM carries it in its epilogue fields
+  e.bnr_z = b.z; e.bnr_bits = b.bits; e.bnr_mean = b.mean; e.bnr_rstd = b.rstd; e.bnr_kscale = b.kscale;
+  e.bnr_part_dy = b.part_dy; e.bnr_part_dyz = b.part_dyz; e.bnr_amax = b.amax;
 }
 
 // The output layer (LinearModel.w2): dW = dy^T h, db = sum dy, g = dy W -> GA.  Three routes.
@@ -838,12 +853,15 @@ int bwd_output(BwdCtx& c) {
     // (Round 3 tried this launch on a side stream -- nothing reads its output before the closing reduce, and it and the head of
     //  the chain below are both latency-bound -- forked and joined with events: 0.627 -> 0.660 ms per step eager, 0.644 -> 0.663
     //  replayed from a graph, same box: the two cross-stream dependencies cost more than the 13 us launch they hide.)
-    PL_TRY(launch_skinny_wide_in(c.dy, h, gW2, Bi, O, H, false, c.buf(w.skp_out), c.s, false, c.buf(w.outpart)));
+    SkinnyWideInArgs wi = {};
+    wi.X = c.dy; wi.D = h; wi.B = Bi; wi.K = O; wi.H = H; wi.part = c.buf(w.skp_out); wi.xsum = c.buf(w.outpart);
+    PL_TRY(launch_skinny_wide_in(wi, c.s));
     c.job(c.buf(w.skp_out), gW2, skinny_in_chunks(Bi), O * H, 0, 0);
     c.job(c.buf(w.outpart), gb2, skinny_in_chunks(Bi), O, 0, 0);
-    GemmArgs be = {};
-    if (!c.eval_bn && w.layer[w.L - 1].bnr_fused) fill_bnr(c, w.L - 1, be);   // pass 1 of the top hidden layer, on the block just produced
-    return launch_skinny_wide_out(c.dy, W2, nullptr, c.GA(), Bi, O, H, true, nullptr, nullptr, c.s, &be);
+    SkinnyWideOutArgs wo = {};
+    wo.X = c.dy; wo.W = W2; wo.out = c.GA(); wo.B = Bi; wo.K = O; wo.H = H; wo.w_transposed = true;
+    if (!c.eval_bn && w.layer[w.L - 1].bnr_fused) wo.bnr = bnr_of(c, w.L - 1);   // pass 1 of the top hidden layer, on the block just produced
+    return launch_skinny_wide_out(wo, c.s);
   }
   PL_TRY(gemm_tn_reduced(c.dy, O, h, H, gW2, O, H, Bi, c.buf(w.slabs), c.s));
   PL_TRY(launch_colsum_partial(c.dy, Bi, O, c.buf(w.outpart), c.s));
@@ -932,7 +950,7 @@ int bwd_layer_linear(BwdCtx& c, int l) {
     PlanesGemmArgs nn = planes_args(w.pkind, u16(c.ws, w.dzp), BH, H, wplane(d, w, c.ws, l), (int64_t)H * H, H,
                                     (l % 2 == 1) ? GA : GB, Bi, H, H, 1.0f / kWeightPlaneScale, dzs ? dzs + 1 : nullptr);
     if (l % 2 == 1) nn.e.addend = GA;
-    if (!c.eval_bn && w.layer[l - 1].bnr_fused) fill_bnr(c, l - 1, nn.e);      // pass 1 of the layer below, on the block just produced
+    if (!c.eval_bn && w.layer[l - 1].bnr_fused) set_bnr(nn.e, bnr_of(c, l - 1));      // pass 1 of the layer below, on the block just produced
     float* wsl = c.buf(w.wslab[l]);                  // this layer's own slabs: combined by the range's one reduce launch
     PlanesGemmArgs tn = planes_args(w.pkind, u16(c.ws, w.dzp), BH, H, u16(c.ws, w.actp[l - 1]), BH, H,
                                     splits > 1 ? wsl : ly.gW, H, H, Bi, 1.0f / kActPlaneScale, dzs ? dzs + 1 : nullptr);
@@ -986,7 +1004,9 @@ int bwd_layer_linear(BwdCtx& c, int l) {
   } else if (r.bwd == Bwd::InAbove && c.sl && c.l_hi > 0) {
     // (layer 0's weight gradient came with its BatchNorm backward, small_layer.hip)
   } else if (r.lin == Lin::Skinny) {
-    PL_TRY(launch_skinny_wide_in(a_in, DZ, ly.gW, Bi, ly.K, H, true, c.buf(w.skp_in), s, false));
+    SkinnyWideInArgs wi = {};
+    wi.X = a_in; wi.D = DZ; wi.B = Bi; wi.K = ly.K; wi.H = H; wi.part = c.buf(w.skp_in);
+    PL_TRY(launch_skinny_wide_in(wi, s));
     c.job(c.buf(w.skp_in), ly.gW, skinny_in_chunks(Bi), ly.K * H, 0, ly.K);
   } else {
     PL_TRY(gemm_tn_reduced(DZ, H, a_in, ly.K, ly.gW, H, ly.K, Bi, slabs, s));
@@ -1090,8 +1110,9 @@ extern "C" int pl_gemm_f32(int layout, const float* A, const float* Bm, float* C
 extern "C" int pl_gemm_arith(int layout, int arith, const float* A, const float* Bm, float* C, int64_t M,
                              int64_t N, int64_t K, const float* bias, int split_k, float* slabs, void* stream) {
   if (layout < 0 || layout > 2) PL_FAIL(PL_EINVAL, "pl_gemm_f32: layout %d", layout);
-  // 5 / 6: test hooks forcing the PL_BF16X6 planes / fragment-split main loop (2 = the library's choice)
-  if ((arith < 0 || arith > 2) && arith != 5 && arith != 6) PL_FAIL(PL_EDTYPE, "pl_gemm_arith: arith %d", arith);
+  // the PLDtype values and the two test hooks forcing the PL_BF16X6 planes / fragment-split main loop
+  if (arith != kArithF32 && arith != kArithBf16 && arith != kArithX6 && arith != kArithX6Planes && arith != kArithX6Frag)
+    PL_FAIL(PL_EDTYPE, "pl_gemm_arith: arith %d", arith);
   if (M <= 0 || N <= 0 || K <= 0 || M > INT32_MAX || N > INT32_MAX || K > INT32_MAX)
     PL_FAIL(PL_ESHAPE, "pl_gemm_f32: bad shape");
   GemmArgs g = {};

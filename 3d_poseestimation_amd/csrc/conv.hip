@@ -621,7 +621,7 @@ int conv_core(const float* x, int64_t B, int64_t H, int64_t W, int64_t Cin, cons
     PL_CHECK_LAUNCH("stem7x7_c3");
     return PL_OK;
   }
-  const int gemm_arith = arith == PL_BF16 ? 7 : arith;     // PL_BF16 on the planes pipeline (gemm_f32.hip)
+  const int gemm_arith = arith == PL_BF16 ? (int)kArithBf16Planes : arith;     // PL_BF16 on the planes pipeline (gemm_f32.hip)
   const bool one = KH == 1 && KW == 1 && stride == 1 && pad_h == 0 && pad_w == 0;
   const bool implicit = !one && implicit_ok(M, Cin, Cout, K);
   // split-K (whole 128 x 128 tiles only: the split kernels' plain store is the tile store)

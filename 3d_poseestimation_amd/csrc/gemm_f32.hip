@@ -1026,7 +1026,7 @@ int prof_read(double min_flops, double max_flops, double* ms_total, int64_t* lau
   return PL_OK;
 }
 
-static ProfRec* prof_begin(const GemmArgs& a, hipStream_t s) {
+static ProfRec* prof_begin(double flops, hipStream_t s) {
   if (!g_prof_on) return nullptr;
   if (g_prof_seen++ % (size_t)g_prof_on) return nullptr;
   if (g_prof_used == g_prof_pool.size()) {
@@ -1035,37 +1035,49 @@ static ProfRec* prof_begin(const GemmArgs& a, hipStream_t s) {
     g_prof_pool.push_back(r);
   }
   ProfRec* r = &g_prof_pool[g_prof_used++];
-  r->flops = 2.0 * a.M * a.N * a.K;
+  r->flops = flops;
   (void)hipEventRecord(r->e0, s);
   return r;
 }
 
-// the same hook for launches made elsewhere (gemm_planes.hip)
-void* prof_begin_flops(double flops, hipStream_t s) {
-  GemmArgs a = {};
-  a.M = 1; a.N = 1; a.K = 1;
-  ProfRec* r = prof_begin(a, s);
-  if (r) r->flops = flops;
-  return r;
-}
+// the same hook for launches made elsewhere (gemm_planes.hip, gemm_thin.hip)
+void* prof_begin_flops(double flops, hipStream_t s) { return prof_begin(flops, s); }
 void prof_end(void* rec, hipStream_t s) {
   if (rec) (void)hipEventRecord(static_cast<ProfRec*>(rec)->e1, s);
 }
 
-// hot path: whole 128x128x32 tiles in every split, 16-byte aligned rows
-static bool whole_tiles(const GemmArgs& a) {
-  const int splits = a.split_k > 1 ? a.split_k : 1;
-  const int kper = splits > 1 ? (((a.K + splits - 1) / splits) + BK - 1) / BK * BK : a.K;
-  return (a.M % BM == 0) && (a.N % BN == 0) && (a.K % BK == 0) && (kper * splits == a.K || splits == 1) &&
-         (a.lda % 4 == 0) && (a.ldb % 4 == 0) && ((reinterpret_cast<uintptr_t>(a.A) & 15) == 0) &&
-         ((reinterpret_cast<uintptr_t>(a.B) & 15) == 0);
+// One launch of this file between its two profiler events, then the launch check.  (A template on the callable: it inlines,
+// nothing is allocated -- these run 15-36 times per eager step.)
+template <class Launch>
+static int profiled_launch(const char* what, double flops, hipStream_t s, Launch&& launch) {
+  ProfRec* prof = prof_begin(flops, s);
+  launch();
+  if (prof) (void)hipEventRecord(prof->e1, s);
+  PL_CHECK_LAUNCH(what);
+  return PL_OK;
+}
+static double flops_of(const GemmArgs& a) { return 2.0 * a.M * a.N * a.K; }
+
+static int splits_of(const GemmArgs& a) { return a.split_k > 1 ? a.split_k : 1; }
+static int grid_of(const GemmArgs& a) { return ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN) * splits_of(a); }
+
+// what every main loop that fetches 16 bytes at a time asks of its operands: row strides % 4, both 16-byte aligned
+static bool operands_vec4(const GemmArgs& a) {
+  return a.lda % 4 == 0 && a.ldb % 4 == 0 && ((reinterpret_cast<uintptr_t>(a.A) | reinterpret_cast<uintptr_t>(a.B)) & 15) == 0;
 }
 
-// the planes pipeline additionally wants even row strides for its float2 loads and whole K slices
-static bool planes_ok(const GemmArgs& a) {
-  const int splits = a.split_k > 1 ? a.split_k : 1;
-  return a.K % (BK * splits) == 0 && (a.lda % 4 == 0) && (a.ldb % 4 == 0);
+// hot path: whole 128x128x32 tiles in every split, 16-byte aligned rows
+static bool whole_tiles(const GemmArgs& a) {
+  const int splits = splits_of(a);
+  const int kper = splits > 1 ? (((a.K + splits - 1) / splits) + BK - 1) / BK * BK : a.K;
+  return (a.M % BM == 0) && (a.N % BN == 0) && (a.K % BK == 0) && (kper * splits == a.K || splits == 1) && operands_vec4(a);
 }
+
+// the planes pipeline additionally wants whole K slices
+static bool planes_ok(const GemmArgs& a) { return a.K % (BK * splits_of(a)) == 0 && operands_vec4(a); }
+
+// one K slice, whole M and K tiles, N as it comes: the NT planes kernels with clamped B rows + guarded stores
+static bool whole_mk(const GemmArgs& a) { return a.split_k <= 1 && a.M % BM == 0 && a.K % BK == 0 && operands_vec4(a); }
 
 // PL_BF16X6 main loop of the single-GEMM launches: planes pipeline unless POSELIFT_X6_FRAG=1
 static bool x6_planes_default() {
@@ -1076,102 +1088,40 @@ static bool x6_planes_default() {
   return on;
 }
 
-static int grid_of(const GemmArgs& a) {
-  return ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN) * (a.split_k > 1 ? a.split_k : 1);
-}
-
-// da = dz W (NN) and dW = dz^T a (TN) in one launch; falls back to two launches off the hot path
-int launch_gemm_f32_pair(const GemmArgs& nn, const GemmArgs& tn, hipStream_t s) {
-  const int g0 = grid_of(nn), g1 = grid_of(tn);
-  if (!whole_tiles(nn) || !whole_tiles(tn) || (g0 & 7) || (g1 & 7)) {
-    PL_TRY(launch_gemm_f32(kNN, nn, s));
-    return launch_gemm_f32(kTN, tn, s);
+// What launch_gemm_f32 runs.  The first family whose conditions hold takes the problem.
+enum class F32Family { Thin, Bf16Planes, X6PlanesNedge, X6Planes, Tile };
+struct F32Route {
+  F32Family family;
+  bool edge;        // Bf16Planes: ragged N; Tile: not whole tiles (exact fp32 whatever a.arith says)
+  int ar;           // Tile, whole: gemm_body's AR -- 0 fp32, 1 bf16, 2 bf16x6 on fragments
+  int grid;
+};
+static F32Route f32_route(GemmLayout layout, const GemmArgs& a, bool x6_frag) {
+  const bool whole = whole_tiles(a);
+  F32Route r = {};
+  r.grid = grid_of(a);
+  r.edge = !whole;
+  if (a.thin_scratch && !whole && a.M <= kThinGemmMaxM && thin_gemm_ok(layout, a)) {
+    // small batch: a handful of tiles for 256 CUs -- the contraction split over the chip instead (gemm_thin.hip)
+    // (only off the tile grid: whole-tile batches keep one arithmetic whatever their size -- SyncBN shards of 128 rows are
+    //  bitwise the single-process batch, tests/test_gpu_dp.py)
+    r.family = F32Family::Thin;
+  } else if (layout == kNT && a.arith == kArithBf16Planes && whole_mk(a)) {
+    r.family = F32Family::Bf16Planes;           // conv path, PL_BF16 on the planes pipeline
+    r.edge = a.N % BN != 0;
+  } else if (layout == kNT && a.arith == kArithX6 && !x6_frag && !whole && whole_mk(a)) {
+    r.family = F32Family::X6PlanesNedge;        // PL_BF16X6, ragged N only
+  } else if (whole && planes_ok(a) && (a.arith == kArithX6Planes || (a.arith == kArithX6 && !x6_frag))) {
+    r.family = F32Family::X6Planes;
+  } else {
+    // Everything else, as it has always been: a whole problem in its arithmetic on the fragment loop, and every problem
+    // that is not whole tiles -- a kArithBf16Planes one that missed its conditions above included -- on the exact-fp32
+    // kernel (edge form, or whole form for kArithBf16Planes on whole tiles of another layout).
+    r.family = F32Family::Tile;
+    const bool x6 = a.arith == kArithX6 || a.arith == kArithX6Planes || a.arith == kArithX6Frag;
+    r.ar = !whole ? 0 : x6 ? 2 : a.arith == kArithBf16 ? 1 : 0;
   }
-  GemmArgs both = nn;                 // profiling record: one launch, the work of two
-  ProfRec* prof = prof_begin(both, s);
-  if (prof) prof->flops += 2.0 * tn.M * tn.N * tn.K;
-  if (nn.arith != tn.arith) PL_FAIL(PL_EINVAL, "gemm pair: mixed arithmetic");
-  if (nn.arith == 2 && x6_planes_default() && planes_ok(nn) && planes_ok(tn))
-    hipLaunchKernelGGL(gemm_x6_planes_dual_kernel, dim3(g0 + g1), dim3(NTHR), 0, s, nn, tn, g0);
-  else if (nn.arith == 2) hipLaunchKernelGGL((gemm_f32_dual_kernel<2, 4>), dim3(g0 + g1), dim3(NTHR), 0, s, nn, tn, g0);
-  else if (nn.arith == 1) hipLaunchKernelGGL((gemm_f32_dual_kernel<1, 4>), dim3(g0 + g1), dim3(NTHR), 0, s, nn, tn, g0);
-  else hipLaunchKernelGGL((gemm_f32_dual_kernel<0, 4>), dim3(g0 + g1), dim3(NTHR), 0, s, nn, tn, g0);
-  if (prof) (void)hipEventRecord(prof->e1, s);
-  PL_CHECK_LAUNCH("gemm_f32_dual");
-  return PL_OK;
-}
-
-int launch_conv_nhwc(const GemmArgs& a, hipStream_t s) {
-  if (!a.A || !a.B || !a.C) PL_FAIL(PL_EINVAL, "conv: null operand");
-  const int splits = a.split_k > 1 ? a.split_k : 1;         // > 1: a.C = slabs [splits][M][ldc], plain sums
-  if (a.conv_cin <= 0 || a.conv_cin % 32 || a.M < 1 || a.N < 1 || a.K % BK || a.K % a.conv_cin ||
-      (splits > 1 && (a.arith == 1 || (a.K / BK) % splits)))
-    PL_FAIL(PL_ESHAPE, "conv: needs Cin %% 32 == 0 and whole K slices (M=%d N=%d K=%d Cin=%d splits=%d)", a.M, a.N,
-            a.K, a.conv_cin, splits);
-  if ((reinterpret_cast<uintptr_t>(a.A) | reinterpret_cast<uintptr_t>(a.B)) & 15)
-    PL_FAIL(PL_EINVAL, "conv: operands not 16-byte aligned");
-  ProfRec* prof = prof_begin(a, s);
-  const dim3 grid(((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN) * splits);
-  const bool edge = a.N % BN || a.M % BM;
-  if (a.arith == 1) {
-    if (edge) hipLaunchKernelGGL(conv_bf16_planes_kernel<true>, grid, dim3(NTHR), 0, s, a);
-    else hipLaunchKernelGGL(conv_bf16_planes_kernel<false>, grid, dim3(NTHR), 0, s, a);
-  } else if (edge) hipLaunchKernelGGL(conv_x6_planes_kernel<true>, grid, dim3(NTHR), 0, s, a);
-  else hipLaunchKernelGGL(conv_x6_planes_kernel<false>, grid, dim3(NTHR), 0, s, a);
-  if (prof) (void)hipEventRecord(prof->e1, s);
-  PL_CHECK_LAUNCH("conv_x6_planes");
-  return PL_OK;
-}
-
-// dW = dy^T x_gathered: a.A = dy [pixels][Cout] (lda = Cout), a.B = x (NHWC), a.C = slabs when split_k > 1,
-// a.M = Cout, a.N = KH*KW*Cin, a.K = B*Ho*Wo; needs Cout and Cin even, Wo % 8 == 0 and pixels % 32 == 0; the K slices
-// are whole 32-pixel tiles, the last one possibly shorter.
-int launch_conv_wgrad(const GemmArgs& a, hipStream_t s) {
-  if (!a.A || !a.B || !a.C) PL_FAIL(PL_EINVAL, "conv wgrad: null operand");
-  const int splits = a.split_k > 1 ? a.split_k : 1;
-  if (a.conv_cin <= 0 || (a.conv_cin & 1) || a.M < 2 || (a.M & 1) || a.N < 2 || a.N % a.conv_cin || a.conv_wo % 8 ||
-      a.K % BK || a.K != (a.K / (a.conv_ho * a.conv_wo)) * a.conv_ho * a.conv_wo || (a.lda & 1))
-    PL_FAIL(PL_ESHAPE, "conv wgrad: needs even Cout and Cin, Wo %% 8 == 0, pixels %% 32 == 0 "
-                       "(M=%d N=%d K=%d Cin=%d Wo=%d splits=%d)", a.M, a.N, a.K, a.conv_cin, a.conv_wo, splits);
-  if ((reinterpret_cast<uintptr_t>(a.A) & 7) || (reinterpret_cast<uintptr_t>(a.B) & 7))
-    PL_FAIL(PL_EINVAL, "conv wgrad: operands misaligned");
-  ProfRec* prof = prof_begin(a, s);
-  const dim3 grid(((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN) * splits);
-  const bool edge = a.M % BM || a.N % BN, bf = a.arith == 1;
-  if (edge && bf) hipLaunchKernelGGL((conv_wgrad_x6_planes_kernel<true, 1>), grid, dim3(NTHR), 0, s, a);
-  else if (edge) hipLaunchKernelGGL((conv_wgrad_x6_planes_kernel<true, 3>), grid, dim3(NTHR), 0, s, a);
-  else if (bf) hipLaunchKernelGGL((conv_wgrad_x6_planes_kernel<false, 1>), grid, dim3(NTHR), 0, s, a);
-  else hipLaunchKernelGGL((conv_wgrad_x6_planes_kernel<false, 3>), grid, dim3(NTHR), 0, s, a);
-  if (prof) (void)hipEventRecord(prof->e1, s);
-  PL_CHECK_LAUNCH("conv_wgrad_x6_planes");
-  return PL_OK;
-}
-
-int launch_conv_nhwc_group4(const GemmArgs* a, hipStream_t s) {
-  GemmArgs4 P;
-  for (int g = 0; g < 4; ++g) {
-    const GemmArgs& q = a[g];
-    if (!q.A || !q.B || !q.C) PL_FAIL(PL_EINVAL, "conv group: null operand");
-    if (q.M != a[0].M || q.N != a[0].N || q.K != a[0].K || q.conv_cin != a[0].conv_cin)
-      PL_FAIL(PL_ESHAPE, "conv group: the four problems must have one shape");
-    if (q.conv_cin <= 0 || q.conv_cin % 32 || q.M < 1 || q.N < 1 || q.K % BK || q.K % q.conv_cin || q.split_k > 1)
-      PL_FAIL(PL_ESHAPE, "conv group: needs Cin %% 32 == 0");
-    if ((reinterpret_cast<uintptr_t>(q.A) | reinterpret_cast<uintptr_t>(q.B)) & 15)
-      PL_FAIL(PL_EINVAL, "conv group: operands not 16-byte aligned");
-    P.g[g] = q;
-  }
-  const int per = ((a[0].M + BM - 1) / BM) * ((a[0].N + BN - 1) / BN);
-  GemmArgs all = a[0];
-  ProfRec* prof = prof_begin(all, s);
-  if (prof) prof->flops *= 4.0;
-  const bool edge = a[0].N % BN || a[0].M % BM, bf = a[0].arith == 1;
-  if (edge && bf) hipLaunchKernelGGL((conv_x6_planes_group4_kernel<true, 1>), dim3(4 * per), dim3(NTHR), 0, s, P, per);
-  else if (edge) hipLaunchKernelGGL((conv_x6_planes_group4_kernel<true, 3>), dim3(4 * per), dim3(NTHR), 0, s, P, per);
-  else if (bf) hipLaunchKernelGGL((conv_x6_planes_group4_kernel<false, 1>), dim3(4 * per), dim3(NTHR), 0, s, P, per);
-  else hipLaunchKernelGGL((conv_x6_planes_group4_kernel<false, 3>), dim3(4 * per), dim3(NTHR), 0, s, P, per);
-  if (prof) (void)hipEventRecord(prof->e1, s);
-  PL_CHECK_LAUNCH("conv_x6_planes_group4");
-  return PL_OK;
+  return r;
 }
 
 int launch_gemm_f32(GemmLayout layout, const GemmArgs& a, hipStream_t s) {
@@ -1179,55 +1129,143 @@ int launch_gemm_f32(GemmLayout layout, const GemmArgs& a, hipStream_t s) {
   if (a.M <= 0 || a.N <= 0 || a.K <= 0) PL_FAIL(PL_ESHAPE, "gemm_f32: bad shape %dx%dx%d", a.M, a.N, a.K);
   if ((a.stat_sum != nullptr) != (a.stat_m2 != nullptr)) PL_FAIL(PL_EINVAL, "gemm_f32: stats need both buffers");
   if (a.col_scale && !a.col_shift) PL_FAIL(PL_EINVAL, "gemm_f32: scale without shift");
-  const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
-  const int splits = a.split_k > 1 ? a.split_k : 1;
-  dim3 grid(tiles * splits), block(NTHR);
-  const size_t lds_bytes = 0;   // LDS is static
-  // small batch: a handful of tiles for 256 CUs -- the contraction split over the chip instead (gemm_thin.hip)
-  // (only off the tile grid: whole-tile batches keep one arithmetic whatever their size -- SyncBN shards of 128 rows are
-  //  bitwise the single-process batch, tests/test_gpu_dp.py)
-  if (a.thin_scratch && !whole_tiles(a) && a.M <= kThinGemmMaxM && thin_gemm_ok(layout, a))
-    return launch_gemm_thin(layout, a, a.thin_scratch, a.thin_scratch_floats, s);
-  ProfRec* prof = prof_begin(a, s);
-  const bool whole = whole_tiles(a);
-#define PL_GEMM_LAUNCH(AKS, BKS)                                                                          \
-  do {                                                                                                    \
-    if (whole && planes_ok(a) && (a.arith == 5 || (a.arith == 2 && x6_planes_default())))                 \
-      hipLaunchKernelGGL((gemm_x6_planes_kernel<AKS, BKS>), grid, block, lds_bytes, s, a);                 \
-    else if (whole && (a.arith == 2 || a.arith == 5 || a.arith == 6)) hipLaunchKernelGGL((gemm_f32_kernel<AKS, BKS, false, 2>), grid, block, lds_bytes, s, a); \
-    else if (whole && a.arith == 1) hipLaunchKernelGGL((gemm_f32_kernel<AKS, BKS, false, 1>), grid, block, lds_bytes, s, a); \
-    else if (whole) hipLaunchKernelGGL((gemm_f32_kernel<AKS, BKS, false>), grid, block, lds_bytes, s, a);      \
-    else hipLaunchKernelGGL((gemm_f32_kernel<AKS, BKS, true>), grid, block, lds_bytes, s, a);             \
-  } while (0)
-  // conv path, PL_BF16 on the planes pipeline (GemmArgs::arith 7, NT only)
-  if (layout == kNT && a.arith == 7 && a.split_k <= 1 && a.M % BM == 0 && a.K % BK == 0 && a.lda % 4 == 0 &&
-      a.ldb % 4 == 0 && ((reinterpret_cast<uintptr_t>(a.A) | reinterpret_cast<uintptr_t>(a.B)) & 15) == 0) {
-    if (a.N % BN) hipLaunchKernelGGL(gemm_bf16_planes_kernel<true>, grid, block, lds_bytes, s, a);
-    else hipLaunchKernelGGL(gemm_bf16_planes_kernel<false>, grid, block, lds_bytes, s, a);
-    if (prof) (void)hipEventRecord(prof->e1, s);
-    PL_CHECK_LAUNCH("gemm_bf16_planes");
-    return PL_OK;
+  if (layout != kNT && layout != kNN && layout != kTN) PL_FAIL(PL_EINVAL, "gemm_f32: bad layout %d", (int)layout);
+  const F32Route r = f32_route(layout, a, !x6_planes_default());
+  if (r.family == F32Family::Thin) return launch_gemm_thin(layout, a, s);
+  const dim3 grid(r.grid), block(NTHR);     // LDS is static
+  auto by_layout = [&](auto launch) {        // (A_KS, B_KS)
+    if (layout == kNT) launch(Bool<false>{}, Bool<false>{});
+    else if (layout == kNN) launch(Bool<false>{}, Bool<true>{});
+    else launch(Bool<true>{}, Bool<true>{});
+  };
+  const char* what = r.family == F32Family::Bf16Planes ? "gemm_bf16_planes"
+                     : r.family == F32Family::X6PlanesNedge ? "gemm_x6_planes_nedge" : "gemm_f32";
+  return profiled_launch(what, flops_of(a), s, [&] {
+    if (r.family == F32Family::Bf16Planes) {
+      auto launch = [&](auto E) { hipLaunchKernelGGL(gemm_bf16_planes_kernel<decltype(E)::value>, grid, block, 0, s, a); };
+      if (r.edge) launch(Bool<true>{}); else launch(Bool<false>{});
+    } else if (r.family == F32Family::X6PlanesNedge) {
+      hipLaunchKernelGGL(gemm_x6_planes_nedge_kernel, grid, block, 0, s, a);
+    } else if (r.family == F32Family::X6Planes) {
+      by_layout([&](auto AKS, auto BKS) {
+        hipLaunchKernelGGL((gemm_x6_planes_kernel<decltype(AKS)::value, decltype(BKS)::value>), grid, block, 0, s, a);
+      });
+    } else {
+      by_layout([&](auto AKS, auto BKS) {
+        auto launch = [&](auto E, auto AR) {
+          hipLaunchKernelGGL((gemm_f32_kernel<decltype(AKS)::value, decltype(BKS)::value, decltype(E)::value, decltype(AR)::value>),
+                             grid, block, 0, s, a);
+        };
+        if (r.edge) launch(Bool<true>{}, Int<0>{});
+        else if (r.ar == 2) launch(Bool<false>{}, Int<2>{});
+        else if (r.ar == 1) launch(Bool<false>{}, Int<1>{});
+        else launch(Bool<false>{}, Int<0>{});
+      });
+    }
+  });
+}
+
+// da = dz W (NN) and dW = dz^T a (TN) in one launch; two launches off the hot path (not whole tiles, or a grid that does not
+// split over the XCDs).  In one launch: the planes pipeline for PL_BF16X6 unless the fragment loop is asked for, else
+// gemm_f32_dual_kernel in the pair's arithmetic (AR 2 / 1; anything else, the forcing test hooks included, exact fp32).
+enum class F32PairRoute { TwoLaunches, X6PlanesDual, TileDual };
+static F32PairRoute f32_pair_route(const GemmArgs& nn, const GemmArgs& tn, bool x6_frag) {
+  if (!whole_tiles(nn) || !whole_tiles(tn) || (grid_of(nn) & 7) || (grid_of(tn) & 7)) return F32PairRoute::TwoLaunches;
+  if (nn.arith == kArithX6 && !x6_frag && planes_ok(nn) && planes_ok(tn)) return F32PairRoute::X6PlanesDual;
+  return F32PairRoute::TileDual;
+}
+
+int launch_gemm_f32_pair(const GemmArgs& nn, const GemmArgs& tn, hipStream_t s) {
+  const F32PairRoute r = f32_pair_route(nn, tn, !x6_planes_default());
+  if (r == F32PairRoute::TwoLaunches) {
+    PL_TRY(launch_gemm_f32(kNN, nn, s));
+    return launch_gemm_f32(kTN, tn, s);
   }
-  // NT, PL_BF16X6, whole M and K tiles but a ragged N: the planes kernel with clamped B rows + guarded stores
-  const bool nt_ragged_n = layout == kNT && a.arith == 2 && x6_planes_default() && !whole && a.split_k <= 1 &&
-                           a.M % BM == 0 && a.K % BK == 0 && a.lda % 4 == 0 && a.ldb % 4 == 0 &&
-                           ((reinterpret_cast<uintptr_t>(a.A) | reinterpret_cast<uintptr_t>(a.B)) & 15) == 0;
-  if (nt_ragged_n) {
-    hipLaunchKernelGGL(gemm_x6_planes_nedge_kernel, grid, block, lds_bytes, s, a);
-    if (prof) (void)hipEventRecord(prof->e1, s);
-    PL_CHECK_LAUNCH("gemm_x6_planes_nedge");
-    return PL_OK;
-  }
-  switch (layout) {
-    case kNT: PL_GEMM_LAUNCH(false, false); break;
-    case kNN: PL_GEMM_LAUNCH(false, true); break;
-    case kTN: PL_GEMM_LAUNCH(true, true); break;
-    default: PL_FAIL(PL_EINVAL, "gemm_f32: bad layout %d", (int)layout);
-  }
-#undef PL_GEMM_LAUNCH
-  if (prof) (void)hipEventRecord(prof->e1, s);
-  PL_CHECK_LAUNCH("gemm_f32");
+  if (nn.arith != tn.arith) PL_FAIL(PL_EINVAL, "gemm pair: mixed arithmetic");
+  const int g0 = grid_of(nn), g1 = grid_of(tn);
+  const dim3 grid(g0 + g1), block(NTHR);
+  // profiling record: one launch, the work of two
+  return profiled_launch("gemm_f32_dual", flops_of(nn) + flops_of(tn), s, [&] {
+    auto tile = [&](auto AR) { hipLaunchKernelGGL((gemm_f32_dual_kernel<decltype(AR)::value, 4>), grid, block, 0, s, nn, tn, g0); };
+    if (r == F32PairRoute::X6PlanesDual) hipLaunchKernelGGL(gemm_x6_planes_dual_kernel, grid, block, 0, s, nn, tn, g0);
+    else if (nn.arith == kArithX6) tile(Int<2>{});
+    else if (nn.arith == kArithBf16) tile(Int<1>{});
+    else tile(Int<0>{});
+  });
+}
+
+// ---- implicit-GEMM convolutions on the planes pipeline
+// the (EDGE, NPL) form of a conv launch: overhanging tiles or not, PL_BF16 (one plane) or PL_BF16X6 (three)
+template <class Launch>
+static void conv_form(const GemmArgs& a, Launch&& launch) {
+  const bool edge = a.M % BM || a.N % BN, bf = a.arith == kArithBf16;
+  if (edge && bf) launch(Bool<true>{}, Int<1>{});
+  else if (edge) launch(Bool<true>{}, Int<3>{});
+  else if (bf) launch(Bool<false>{}, Int<1>{});
+  else launch(Bool<false>{}, Int<3>{});
+}
+
+// What the forward kernels ask of one problem (`who`: the caller's name in the messages).  first != NULL: a member of a
+// group launch -- the shape of the group's first problem, one K slice; else K slices are allowed (PL_BF16X6, whole ones:
+// a.C = slabs [splits][M][ldc], plain sums).
+static int conv_fwd_check(const GemmArgs& a, const char* who, const GemmArgs* first = nullptr) {
+  if (!a.A || !a.B || !a.C) PL_FAIL(PL_EINVAL, "%s: null operand", who);
+  if (first && (a.M != first->M || a.N != first->N || a.K != first->K || a.conv_cin != first->conv_cin))
+    PL_FAIL(PL_ESHAPE, "%s: the four problems must have one shape", who);
+  const int splits = splits_of(a);
+  const bool shape_ok = a.conv_cin > 0 && a.conv_cin % 32 == 0 && a.M >= 1 && a.N >= 1 && a.K % BK == 0 && a.K % a.conv_cin == 0;
+  if (first && (!shape_ok || a.split_k > 1)) PL_FAIL(PL_ESHAPE, "%s: needs Cin %% 32 == 0", who);
+  if (!shape_ok || (splits > 1 && (a.arith == kArithBf16 || (a.K / BK) % splits)))
+    PL_FAIL(PL_ESHAPE, "%s: needs Cin %% 32 == 0 and whole K slices (M=%d N=%d K=%d Cin=%d splits=%d)", who, a.M, a.N, a.K,
+            a.conv_cin, splits);
+  if ((reinterpret_cast<uintptr_t>(a.A) | reinterpret_cast<uintptr_t>(a.B)) & 15)
+    PL_FAIL(PL_EINVAL, "%s: operands not 16-byte aligned", who);
   return PL_OK;
+}
+
+int launch_conv_nhwc(const GemmArgs& a, hipStream_t s) {
+  PL_TRY(conv_fwd_check(a, "conv"));
+  const dim3 grid(grid_of(a)), block(NTHR);
+  return profiled_launch("conv_x6_planes", flops_of(a), s, [&] {
+    conv_form(a, [&](auto E, auto NPL) {
+      if constexpr (decltype(NPL)::value == 1) hipLaunchKernelGGL(conv_bf16_planes_kernel<decltype(E)::value>, grid, block, 0, s, a);
+      else hipLaunchKernelGGL(conv_x6_planes_kernel<decltype(E)::value>, grid, block, 0, s, a);
+    });
+  });
+}
+
+// dW = dy^T x_gathered: a.A = dy [pixels][Cout] (lda = Cout), a.B = x (NHWC), a.C = slabs when split_k > 1,
+// a.M = Cout, a.N = KH*KW*Cin, a.K = B*Ho*Wo; needs Cout and Cin even, Wo % 8 == 0 and pixels % 32 == 0; the K slices
+// are whole 32-pixel tiles, the last one possibly shorter.
+int launch_conv_wgrad(const GemmArgs& a, hipStream_t s) {
+  if (!a.A || !a.B || !a.C) PL_FAIL(PL_EINVAL, "conv wgrad: null operand");
+  if (a.conv_cin <= 0 || (a.conv_cin & 1) || a.M < 2 || (a.M & 1) || a.N < 2 || a.N % a.conv_cin || a.conv_wo % 8 ||
+      a.K % BK || a.K != (a.K / (a.conv_ho * a.conv_wo)) * a.conv_ho * a.conv_wo || (a.lda & 1))
+    PL_FAIL(PL_ESHAPE, "conv wgrad: needs even Cout and Cin, Wo %% 8 == 0, pixels %% 32 == 0 "
+                       "(M=%d N=%d K=%d Cin=%d Wo=%d splits=%d)", a.M, a.N, a.K, a.conv_cin, a.conv_wo, splits_of(a));
+  if ((reinterpret_cast<uintptr_t>(a.A) & 7) || (reinterpret_cast<uintptr_t>(a.B) & 7))
+    PL_FAIL(PL_EINVAL, "conv wgrad: operands misaligned");
+  const dim3 grid(grid_of(a)), block(NTHR);
+  return profiled_launch("conv_wgrad_x6_planes", flops_of(a), s, [&] {
+    conv_form(a, [&](auto E, auto NPL) {
+      hipLaunchKernelGGL((conv_wgrad_x6_planes_kernel<decltype(E)::value, decltype(NPL)::value>), grid, block, 0, s, a);
+    });
+  });
+}
+
+int launch_conv_nhwc_group4(const GemmArgs* a, hipStream_t s) {
+  GemmArgs4 P;
+  for (int g = 0; g < 4; ++g) {
+    PL_TRY(conv_fwd_check(a[g], "conv group", &a[0]));
+    P.g[g] = a[g];
+  }
+  const int per = grid_of(a[0]);
+  return profiled_launch("conv_x6_planes_group4", flops_of(a[0]) * 4.0, s, [&] {
+    conv_form(a[0], [&](auto E, auto NPL) {
+      hipLaunchKernelGGL((conv_x6_planes_group4_kernel<decltype(E)::value, decltype(NPL)::value>), dim3(4 * per), dim3(NTHR), 0, s,
+                         P, per);
+    });
+  });
 }
 
 }  // namespace pl

@@ -386,7 +386,7 @@ __global__ __launch_bounds__(512) void planes_gemm_dual_kernel(PlanesKern k0, Pl
     planes_body<true, true, MODE>(k1, b - n0, gridDim.x - n0, gridDim.x - n0, lds);
 }
 
-PlanesKern kern_of(GemmLayout layout, const PlanesGemmArgs& a) {
+PlanesKern kern_of(const PlanesGemmArgs& a) {
   PlanesKern k = {};
   k.p.A = reinterpret_cast<const __bf16*>(a.A);
   k.p.B = reinterpret_cast<const __bf16*>(a.B);
@@ -402,7 +402,6 @@ PlanesKern kern_of(GemmLayout layout, const PlanesGemmArgs& a) {
   k.out_scale = a.out_scale;
   k.dyn_inv = a.dyn_inv;
   k.nt_store = (int64_t)a.e.M * a.e.N * 4 >= kNontemporalBytes ? 1 : 0;
-  (void)layout;
   return k;
 }
 
@@ -419,24 +418,93 @@ int cu_count() {
   return cached[dev];
 }
 
-int grid_of(const PlanesGemmArgs& a) {
-  return ((a.e.M + 127) / 128) * ((a.e.N + 127) / 128) * (a.e.split_k > 1 ? a.e.split_k : 1);
-}
+int splits_of(const GemmArgs& e) { return e.split_k > 1 ? e.split_k : 1; }
+int grid_of(const PlanesGemmArgs& a) { return ((a.e.M + 127) / 128) * ((a.e.N + 127) / 128) * splits_of(a.e); }
 bool is_edge(const PlanesGemmArgs& a) { return (a.e.M % 128) != 0 || (a.e.N % 128) != 0; }
+
+// One planes GEMM as planes_route decided it: every kernel template is named here and nowhere else.
+template <int MODE>
+int launch_routed(GemmLayout layout, const PlanesRoute& r, const PlanesKern& k, hipStream_t s) {
+  const dim3 grid(r.grid), block(512);
+  // the (EDGE, CONV) forms of the NT families: whole <false, 0>, overhanging <true, 0>, gathered A <true, 1>
+  auto nt_form = [&](auto launch) {
+    if (r.conv) launch(Bool<true>{}, Int<1>{});
+    else if (r.edge) launch(Bool<true>{}, Int<0>{});
+    else launch(Bool<false>{}, Int<0>{});
+  };
+  auto persist_form = [&](auto launch) {
+    if (r.persist) launch(Bool<true>{}); else launch(Bool<false>{});
+  };
+  switch (r.family) {
+    case PlanesFamily::T64:
+      nt_form([&](auto E, auto C) {
+        persist_form([&](auto P) {
+          hipLaunchKernelGGL((planes_gemm_t64_kernel<MODE, decltype(E)::value, decltype(C)::value, decltype(P)::value>), grid, block,
+                             0, s, k, r.nwork);
+        });
+      });
+      return PL_OK;
+    case PlanesFamily::Wide:
+      nt_form([&](auto E, auto C) {
+        persist_form([&](auto P) {
+          hipLaunchKernelGGL((planes_gemm_wide_kernel<MODE, decltype(E)::value, decltype(C)::value, decltype(P)::value>), grid, block,
+                             0, s, k, r.nwork);
+        });
+      });
+      return PL_OK;
+    case PlanesFamily::Persistent:
+      nt_form([&](auto E, auto C) {
+        hipLaunchKernelGGL((planes_gemm_persistent_kernel<MODE, decltype(E)::value, decltype(C)::value>), grid, block, 0, s, k,
+                           r.nwork);
+      });
+      return PL_OK;
+    case PlanesFamily::OneItem: break;
+  }
+  // one item per workgroup, any layout: whole or overhanging, and the layout's gathered form GATHER (NT 1, TN 2, NN none)
+  auto one_item = [&](auto AKS, auto BKS, auto GATHER) {
+    auto launch = [&](auto E, auto C) {
+      hipLaunchKernelGGL((planes_gemm_kernel<decltype(AKS)::value, decltype(BKS)::value, MODE, decltype(E)::value, decltype(C)::value>),
+                         grid, block, 0, s, k);
+    };
+    if constexpr (decltype(GATHER)::value != 0) {
+      if (r.conv) return launch(Bool<true>{}, GATHER);
+    }
+    if (r.edge) launch(Bool<true>{}, Int<0>{}); else launch(Bool<false>{}, Int<0>{});
+  };
+  switch (layout) {
+    case kNT: one_item(Bool<false>{}, Bool<false>{}, Int<1>{}); break;
+    case kNN: one_item(Bool<false>{}, Bool<true>{}, Int<0>{}); break;
+    case kTN: one_item(Bool<true>{}, Bool<true>{}, Int<2>{}); break;
+    default: PL_FAIL(PL_EINVAL, "gemm_planes: bad layout %d", (int)layout);
+  }
+  return PL_OK;
+}
+
+// the backward pair: chained (one workgroup per dX tile that goes on to a dW item, operands streaming across) or side by side
+enum class PairRoute { Chain, Dual };
+PairRoute pair_route(const PlanesGemmArgs& nn, const PlanesGemmArgs& tn) {
+  const int ts = splits_of(tn.e);
+  const bool chain = grid_of(nn) == grid_of(tn) && nn.e.K % 32 == 0 && nn.e.K >= 64 && tn.e.K % (32 * ts) == 0 && tn.e.K >= 32 * ts;
+  return chain ? PairRoute::Chain : PairRoute::Dual;
+}
+template <int MODE>
+void launch_pair(PairRoute r, const PlanesKern& k0, const PlanesKern& k1, int g0, int g1, hipStream_t s) {
+  if (r == PairRoute::Chain) hipLaunchKernelGGL((planes_gemm_chain_kernel<MODE>), dim3(g0), dim3(512), 0, s, k0, k1);
+  else hipLaunchKernelGGL((planes_gemm_dual_kernel<MODE>), dim3(g0 + g1), dim3(512), 0, s, k0, k1, g0);
+}
 
 }  // namespace
 
 // whole 128x128 tiles, every K slice a whole number of 32-k tiles, 16-byte aligned plane rows, and every byte
 // offset the DMA's 32-bit scalar offset has to hold below 2^31
-static int splits_of(const GemmArgs& e) { return e.split_k > 1 ? e.split_k : 1; }
 bool planes_gemm_ok(GemmLayout layout, const PlanesGemmArgs& a) {
   const GemmArgs& e = a.e;
+  const int splits = splits_of(e);
   if (a.mode != plp::kBf16 && a.mode != plp::kF16x3) return false;
   if (!a.A || !a.B || (!e.C && !e.cpl_kind) || e.M <= 0 || e.N <= 0 || e.K <= 0) return false;
-  if (e.cpl_kind && (splits_of(e) > 1 || !e.cpl_h || (e.cpl_kind == 2 && !e.cpl_l) ||
+  if (e.cpl_kind && (splits > 1 || !e.cpl_h || (e.cpl_kind == 2 && !e.cpl_l) ||
                      ((reinterpret_cast<uintptr_t>(e.cpl_h) | reinterpret_cast<uintptr_t>(e.cpl_l)) & 7)))
     return false;
-  const int splits = e.split_k > 1 ? e.split_k : 1;
   if (e.K % (32 * splits)) return false;
   if (e.conv_cin) {
     // implicit-GEMM convolution: NT with A gathered (forward / data gradient) or TN with B gathered (weight gradient);
@@ -446,9 +514,7 @@ bool planes_gemm_ok(GemmLayout layout, const PlanesGemmArgs& a) {
     const int64_t pixels = layout == kNT ? e.M : e.K;
     if (pixels % ((int64_t)e.conv_ho * e.conv_wo)) return false;
     const int64_t xb = pixels / ((int64_t)e.conv_ho * e.conv_wo) * e.conv_h * e.conv_w * e.conv_cin * 2;
-    const int npl_ = a.mode == plp::kF16x3 ? 2 : 1;
     if (xb >= 0x7fffffe0ll) return false;
-    (void)npl_;
     // (8 channels: four taps of a kernel row per 32-k tile -- the stem on pixel pairs; one K slice, no pair staging)
     const bool cin8 = e.conv_cin == 8 && e.conv_kw % 4 == 0 && e.split_k <= 1;
     if (layout == kNT && !cin8 && ((e.conv_cin & 31) || e.K % e.conv_cin)) return false;
@@ -484,76 +550,45 @@ bool planes_gemm_ok(GemmLayout layout, const PlanesGemmArgs& a) {
   return true;
 }
 
+// Which kernel family runs a problem that planes_gemm_ok accepted, in which form and on what grid.  The first
+// family whose conditions hold takes it; a gathered operand (conv) implies the edge form in every family -- the gathered
+// kernels exist as <EDGE = true> only.
+PlanesRoute planes_route(GemmLayout layout, const PlanesGemmArgs& a, int ncu) {
+  const GemmArgs& e = a.e;
+  const bool nt = layout == kNT, one_slice = splits_of(e) == 1;
+  PlanesRoute r = {};
+  r.conv = !e.conv_cin ? 0 : nt ? 1 : 2;     // 1: A gathered as a convolution input (NT), 2: B gathered, weight gradient (TN)
+  r.nwork = grid_of(a);                      // 128 x 128 tiles x K slices
+  r.edge = is_edge(a) || r.conv;
+  if (nt && e.N <= 64 && one_slice && !e.scat_on) {
+    // 64-channel outputs: 256-row x 64-column tiles (half of a 128-wide tile would be padding)
+    r.family = PlanesFamily::T64;
+    r.nwork = ((e.M + 255) / 256) * ((e.N + 63) / 64);
+    r.edge = (e.M % 256) != 0 || (e.N % 64) != 0 || r.conv;
+  } else if (nt && one_slice && e.K % 64 == 0 && e.K >= 1024 && (e.conv_cin == 0 || e.conv_cin % 64 == 0)) {
+    // pair-staged k-tiles: every K slice a whole number of 64-k pairs, a gathered pair inside one filter tap -- and a long
+    // contraction: measured same-box (tools/bench_conv_gemm.py, bench.py) K = 1024 / 2048 take 4-6 % less time (the lifter's
+    // forward GEMM 33.2 -> 32.7 us in the step), K <= 512 0-3 % MORE (a pair is a coarser unit at an item boundary)
+    r.family = PlanesFamily::Wide;
+  } else if (nt && r.nwork >= 2 * ncu) {
+    // persistent form (round 3): NT problems with at least two work items per CU -- the conv path's 1x1 / 3x3 / transposed
+    // convolutions over 16K .. 1M pixels
+    r.family = PlanesFamily::Persistent;
+  } else {
+    r.family = PlanesFamily::OneItem;
+  }
+  // the NT families walk their items with one workgroup per CU from two items per CU on
+  r.persist = r.family != PlanesFamily::OneItem && r.nwork >= 2 * ncu;
+  r.grid = r.persist ? ncu : r.nwork;
+  return r;
+}
+
 int launch_gemm_planes(GemmLayout layout, const PlanesGemmArgs& a, hipStream_t s) {
   if (!planes_gemm_ok(layout, a)) PL_FAIL(PL_ESHAPE, "gemm_planes: unsupported problem %dx%dx%d (layout %d, mode %d)", a.e.M, a.e.N, a.e.K, (int)layout, a.mode);
-  const PlanesKern k = kern_of(layout, a);
-  const dim3 grid(grid_of(a)), block(512);
+  const PlanesKern k = kern_of(a);
+  const PlanesRoute r = planes_route(layout, a, cu_count());
   void* prof = prof_begin_flops(2.0 * a.e.M * a.e.N * a.e.K, s);
-#define PL_PLANES_LAUNCH(MODE, EDGE)                                                                             \
-  switch (layout) {                                                                                              \
-    case kNT: hipLaunchKernelGGL((planes_gemm_kernel<false, false, MODE, EDGE>), grid, block, 0, s, k); break;   \
-    case kNN: hipLaunchKernelGGL((planes_gemm_kernel<false, true, MODE, EDGE>), grid, block, 0, s, k); break;    \
-    case kTN: hipLaunchKernelGGL((planes_gemm_kernel<true, true, MODE, EDGE>), grid, block, 0, s, k); break;     \
-    default: PL_FAIL(PL_EINVAL, "gemm_planes: bad layout %d", (int)layout);                                     \
-  }
-  // persistent form (round 3): NT problems with at least two work items per CU -- the conv path's 1x1 / 3x3 / transposed
-  // convolutions over 16K .. 1M pixels
-  const int ncu = cu_count();
-  const bool persist = layout == kNT && (int)grid.x >= 2 * ncu;
-  // pair-staged k-tiles: NT, every K slice a whole number of 64-k pairs, a gathered pair inside one filter tap -- and a long
-  // contraction: measured same-box (tools/bench_conv_gemm.py, bench.py) K = 1024 / 2048 take 4-6 % less time (the lifter's
-  // forward GEMM 33.2 -> 32.7 us in the step), K <= 512 0-3 % MORE (a pair is a coarser unit at an item boundary)
-  const bool wide = layout == kNT && splits_of(a.e) == 1 && a.e.K % 64 == 0 && a.e.K >= 1024 &&
-                    (a.e.conv_cin == 0 || a.e.conv_cin % 64 == 0);
-  // 64-channel outputs: 256-row x 64-column tiles (half of a 128-wide tile would be padding)
-  const bool t64 = layout == kNT && a.e.N <= 64 && splits_of(a.e) == 1 && !a.e.scat_on;
-  if (t64) {
-    const int nwork = (int)(((a.e.M + 255) / 256) * ((a.e.N + 63) / 64));
-    const bool pers = nwork >= 2 * ncu;
-    const dim3 tg(pers ? ncu : nwork);
-    const bool edge = (a.e.M % 256) != 0 || (a.e.N % 64) != 0 || a.e.conv_cin;
-#define PL_T64(MODE, P)                                                                                                  \
-    if (a.e.conv_cin) hipLaunchKernelGGL((planes_gemm_t64_kernel<MODE, true, 1, P>), tg, block, 0, s, k, nwork);          \
-    else if (edge) hipLaunchKernelGGL((planes_gemm_t64_kernel<MODE, true, 0, P>), tg, block, 0, s, k, nwork);             \
-    else hipLaunchKernelGGL((planes_gemm_t64_kernel<MODE, false, 0, P>), tg, block, 0, s, k, nwork);
-    if (pers) { if (a.mode == plp::kF16x3) { PL_T64(plp::kF16x3, true) } else { PL_T64(plp::kBf16, true) } }
-    else { if (a.mode == plp::kF16x3) { PL_T64(plp::kF16x3, false) } else { PL_T64(plp::kBf16, false) } }
-#undef PL_T64
-  } else if (wide) {
-    const int nwork = (int)grid.x;
-    const dim3 wg(persist ? ncu : nwork);
-    const bool edge = is_edge(a) || a.e.conv_cin;
-#define PL_WIDE(MODE, P)                                                                                                  \
-    if (a.e.conv_cin) hipLaunchKernelGGL((planes_gemm_wide_kernel<MODE, true, 1, P>), wg, block, 0, s, k, nwork);          \
-    else if (edge) hipLaunchKernelGGL((planes_gemm_wide_kernel<MODE, true, 0, P>), wg, block, 0, s, k, nwork);             \
-    else hipLaunchKernelGGL((planes_gemm_wide_kernel<MODE, false, 0, P>), wg, block, 0, s, k, nwork);
-    if (persist) { if (a.mode == plp::kF16x3) { PL_WIDE(plp::kF16x3, true) } else { PL_WIDE(plp::kBf16, true) } }
-    else { if (a.mode == plp::kF16x3) { PL_WIDE(plp::kF16x3, false) } else { PL_WIDE(plp::kBf16, false) } }
-#undef PL_WIDE
-  } else if (persist) {
-    const dim3 pg(ncu);
-    const int nwork = (int)grid.x;
-    const bool edge = is_edge(a) || a.e.conv_cin;
-#define PL_PERSIST(MODE)                                                                                               \
-    if (a.e.conv_cin) hipLaunchKernelGGL((planes_gemm_persistent_kernel<MODE, true, 1>), pg, block, 0, s, k, nwork);   \
-    else if (edge) hipLaunchKernelGGL((planes_gemm_persistent_kernel<MODE, true, 0>), pg, block, 0, s, k, nwork);      \
-    else hipLaunchKernelGGL((planes_gemm_persistent_kernel<MODE, false, 0>), pg, block, 0, s, k, nwork);
-    if (a.mode == plp::kF16x3) { PL_PERSIST(plp::kF16x3) } else { PL_PERSIST(plp::kBf16) }
-#undef PL_PERSIST
-  } else if (a.e.conv_cin) {
-    if (layout == kNT) {
-      if (a.mode == plp::kF16x3) hipLaunchKernelGGL((planes_gemm_kernel<false, false, plp::kF16x3, true, 1>), grid, block, 0, s, k);
-      else hipLaunchKernelGGL((planes_gemm_kernel<false, false, plp::kBf16, true, 1>), grid, block, 0, s, k);
-    } else {
-      if (a.mode == plp::kF16x3) hipLaunchKernelGGL((planes_gemm_kernel<true, true, plp::kF16x3, true, 2>), grid, block, 0, s, k);
-      else hipLaunchKernelGGL((planes_gemm_kernel<true, true, plp::kBf16, true, 2>), grid, block, 0, s, k);
-    }
-  } else if (is_edge(a)) {
-    if (a.mode == plp::kF16x3) { PL_PLANES_LAUNCH(plp::kF16x3, true) } else { PL_PLANES_LAUNCH(plp::kBf16, true) }
-  } else {
-    if (a.mode == plp::kF16x3) { PL_PLANES_LAUNCH(plp::kF16x3, false) } else { PL_PLANES_LAUNCH(plp::kBf16, false) }
-  }
-#undef PL_PLANES_LAUNCH
+  PL_TRY(a.mode == plp::kF16x3 ? launch_routed<plp::kF16x3>(layout, r, k, s) : launch_routed<plp::kBf16>(layout, r, k, s));
   prof_end(prof, s);
   PL_CHECK_LAUNCH("gemm_planes");
   return PL_OK;
@@ -562,24 +597,13 @@ int launch_gemm_planes(GemmLayout layout, const PlanesGemmArgs& a, hipStream_t s
 int launch_gemm_planes_pair(const PlanesGemmArgs& nn, const PlanesGemmArgs& tn, hipStream_t s) {
   if (!planes_gemm_ok(kNN, nn) || !planes_gemm_ok(kTN, tn) || nn.mode != tn.mode || is_edge(nn) || is_edge(tn))
     PL_FAIL(PL_ESHAPE, "gemm_planes_pair: unsupported problems");
-  const PlanesKern k0 = kern_of(kNN, nn), k1 = kern_of(kTN, tn);
-  const int g0 = grid_of(nn), g1 = grid_of(tn);
+  const PlanesKern k0 = kern_of(nn), k1 = kern_of(tn);
+  const PairRoute r = pair_route(nn, tn);
   void* prof = prof_begin_flops(2.0 * nn.e.M * nn.e.N * nn.e.K + 2.0 * tn.e.M * tn.e.N * tn.e.K, s);
-  // chained form (round 3): one workgroup per dX tile that goes on to a dW item, operands streaming across
-  if (g0 == g1 && nn.e.K % 32 == 0 && nn.e.K >= 64 && tn.e.K % (32 * splits_of(tn.e)) == 0 &&
-      tn.e.K >= 32 * splits_of(tn.e)) {
-    const dim3 cg(g0), cb(512);
-    if (nn.mode == plp::kF16x3) hipLaunchKernelGGL((planes_gemm_chain_kernel<plp::kF16x3>), cg, cb, 0, s, k0, k1);
-    else hipLaunchKernelGGL((planes_gemm_chain_kernel<plp::kBf16>), cg, cb, 0, s, k0, k1);
-    prof_end(prof, s);
-    PL_CHECK_LAUNCH("gemm_planes_chain");
-    return PL_OK;
-  }
-  const dim3 grid(g0 + g1), block(512);
-  if (nn.mode == plp::kF16x3) hipLaunchKernelGGL((planes_gemm_dual_kernel<plp::kF16x3>), grid, block, 0, s, k0, k1, g0);
-  else hipLaunchKernelGGL((planes_gemm_dual_kernel<plp::kBf16>), grid, block, 0, s, k0, k1, g0);
+  if (nn.mode == plp::kF16x3) launch_pair<plp::kF16x3>(r, k0, k1, grid_of(nn), grid_of(tn), s);
+  else launch_pair<plp::kBf16>(r, k0, k1, grid_of(nn), grid_of(tn), s);
   prof_end(prof, s);
-  PL_CHECK_LAUNCH("gemm_planes_dual");
+  PL_CHECK_LAUNCH(r == PairRoute::Chain ? "gemm_planes_chain" : "gemm_planes_dual");
   return PL_OK;
 }
 

@@ -189,10 +189,11 @@ bool thin_gemm_ok(GemmLayout layout, const GemmArgs& a) {
   return (al & 15) == 0;
 }
 
-int launch_gemm_thin(GemmLayout layout, const GemmArgs& a, float* scratch, size_t scratch_floats, hipStream_t s) {
+int launch_gemm_thin(GemmLayout layout, const GemmArgs& a, hipStream_t s) {
+  float* const scratch = a.thin_scratch;
   if (!thin_gemm_ok(layout, a)) PL_FAIL(PL_ESHAPE, "gemm_thin: unsupported problem %dx%dx%d (layout %d)", a.M, a.N, a.K, (int)layout);
   const int splits = thin_gemm_splits(a.N, a.K);
-  if (!scratch || scratch_floats < (size_t)splits * a.M * a.N || (reinterpret_cast<uintptr_t>(scratch) & 15))
+  if (!scratch || a.thin_scratch_floats < (size_t)splits * a.M * a.N || (reinterpret_cast<uintptr_t>(scratch) & 15))
     PL_FAIL(PL_EWORKSPACE, "gemm_thin: scratch of %zu floats needed", (size_t)splits * a.M * a.N);
   const int tasks = ((a.M + 63) / 64) * ((a.N + 31) / 32) * splits;
   void* prof = prof_begin_flops(2.0 * a.M * a.N * a.K, s);

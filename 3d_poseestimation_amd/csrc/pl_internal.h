@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/poselift.h"
 #include "adamw.h"
 #include "philox.h"
@@ -12,6 +14,9 @@
 namespace pl {
 
 constexpr int kWave = 64;
+// template arguments chosen at run time travel to the one launch site of a kernel template as values of these types
+template <bool V> using Bool = std::integral_constant<bool, V>;
+template <int V> using Int = std::integral_constant<int, V>;
 
 void set_error(const char* fmt, ...);
 
@@ -55,9 +60,7 @@ struct GemmArgs {
   const float* col_shift;
   int relu;                 // 1: v = max(v, 0) before the resid add; 2: after it (Bottleneck order)
   const float* resid;       // [M][ldc] v += resid[row][col] after relu (may alias C)
-  int arith;                // 0 fp32 MFMA; 1 PL_BF16: operands rounded to bf16 on the way to the MFMA;
-                            // 2 PL_BF16X6: three-way bf16 split, six MFMAs, fp32-grade products
-                            // (whole-tile problems only; edge problems stay fp32)
+  int arith;                // a GemmArith value (below)
   // Implicit-GEMM convolution (launch_conv_nhwc only; conv_cin == 0 otherwise): A is not a matrix but the
   // NHWC input x [B][H][W][Cin]; row m = (b, oh, ow), k = (kh*KW + kw)*Cin + ci, element
   // x[b][oh*stride - pad + kh][ow*stride - pad + kw][ci] or 0 outside the image.  B = weights [N][K] (OHWI).
@@ -86,6 +89,17 @@ struct GemmArgs {
   // host side only: scratch for the small-batch split-K path (gemm_thin.hip); NULL = never take it
   float* thin_scratch;
   size_t thin_scratch_floats;
+};
+
+// GemmArgs::arith.  0-2 are the PLDtype values; launch_gemm_f32 runs every problem that is not whole tiles, and an
+// kArithBf16Planes problem that misses that pipeline's conditions, in exact fp32 (f32_route, gemm_f32.hip).
+enum GemmArith : int {
+  kArithF32 = 0,            // fp32 MFMA
+  kArithBf16 = 1,           // PL_BF16: operands rounded to bf16 on the way to the MFMA
+  kArithX6 = 2,             // PL_BF16X6: three-way bf16 split, six MFMAs, fp32-grade products; the library picks the main loop
+  kArithX6Planes = 5,       //   ... forced to the planes loop (test hook of pl_gemm_arith)
+  kArithX6Frag = 6,         //   ... forced to the fragment-split loop (test hook of pl_gemm_arith)
+  kArithBf16Planes = 7,     // PL_BF16 on the planes pipeline: the conv path's NT GEMMs (conv.hip)
 };
 
 // y = conv2d(x, w) as an implicit GEMM on the PL_BF16X6 planes pipeline; a.A = x, a.B = w [Cout][KH*KW*Cin],
@@ -140,6 +154,17 @@ struct PlanesGemmArgs {
   const float* dyn_inv;       // device scalar or NULL
 };
 bool planes_gemm_ok(GemmLayout layout, const PlanesGemmArgs& a);
+// What launch_gemm_planes runs for a problem planes_gemm_ok accepted on a device of ncu CUs (the table: DESIGN 3a): the
+// kernel family, its form and its grid.  A plain function of its arguments.
+enum class PlanesFamily { OneItem, Persistent, Wide, T64 };
+struct PlanesRoute {
+  PlanesFamily family;
+  bool persist;               // one workgroup per CU walks nwork items (else one item per workgroup)
+  bool edge;                  // overhanging tiles or a gathered operand: guarded loads and stores
+  int conv;                   // 0 none, 1 A gathered as a convolution input (NT), 2 B gathered, weight gradient (TN)
+  int grid, nwork;
+};
+PlanesRoute planes_route(GemmLayout layout, const PlanesGemmArgs& a, int ncu);
 int launch_gemm_planes(GemmLayout layout, const PlanesGemmArgs& a, hipStream_t s);
 // dX = dz W (NN) and dW = dz^T a (TN, split-K slabs) of one layer in ONE launch
 int launch_gemm_planes_pair(const PlanesGemmArgs& nn, const PlanesGemmArgs& tn, hipStream_t s);
@@ -150,11 +175,11 @@ int plane_out_of(int mode, void* planes, int64_t n, float scale, const float* dy
 
 int launch_gemm_f32(GemmLayout layout, const GemmArgs& a, hipStream_t s);
 // M <= kThinGemmMaxM rows (NT, NN): the contraction split over the chip, exact fp32 MFMA, slabs + one reduce/epilogue
-// launch (gemm_thin.hip); launch_gemm_f32 takes it for problems that are not whole tiles when a.thin_scratch is set
+// launch (gemm_thin.hip) on a.thin_scratch; launch_gemm_f32 takes it for problems that are not whole tiles when that is set
 constexpr int kThinGemmMaxM = 512;
 bool thin_gemm_ok(GemmLayout layout, const GemmArgs& a);
 size_t thin_gemm_scratch_floats(int M, int N, int K);
-int launch_gemm_thin(GemmLayout layout, const GemmArgs& a, float* scratch, size_t scratch_floats, hipStream_t s);
+int launch_gemm_thin(GemmLayout layout, const GemmArgs& a, hipStream_t s);
 int launch_gemm_f32_pair(const GemmArgs& nn, const GemmArgs& tn, hipStream_t s);
 int gemm_stat_groups(int M);  // number of 64-row groups the stats epilogue emits
 int prof_enable(int on);
@@ -435,23 +460,54 @@ int launch_adamw(const AdamWArgs& a, hipStream_t s);
 bool skinny_supported(int K, int H);           // narrow dimension specialised (34, 51), H % 128 == 0
 int skinny_chunks(int B);                      // row tasks (64 rows each)
 int skinny_stat_groups(int B);                 // 64-row BN statistics groups it emits
-// bnr (optional, w_transposed only): its bnr_* fields = BatchNorm-backward pass 1 of the layer that consumes `out` as its
-// incoming gradient, done on the block just produced (amax per (64-row group, 32-column strip): (B/64) * (H/32) pairs)
-int launch_skinny_wide_out(const float* X, const float* W, const float* bias, float* out, int B, int K,
-                           int H, bool w_transposed, float* stat_sum, float* stat_m2, hipStream_t s,
-                           const GemmArgs* bnr = nullptr);
-// reduce == false: only the partials are written (part: skinny_in_chunks(B) x K x H floats); the caller combines them
-// (launch_reduce_rows_multi: R = skinny_in_chunks(B), H = K*H, transK = K when out_transposed)
-// xsum (optional): skinny_in_chunks(B) x K partial column sums of X (the output layer's bias gradient: X = dy), to be combined
-// like any other partial (R = skinny_in_chunks(B), H = K)
-int launch_skinny_wide_in(const float* X, const float* D, float* out, int B, int K, int H,
-                          bool out_transposed, float* part, hipStream_t s, bool reduce = true, float* xsum = nullptr);
+// BatchNorm-backward pass 1 of the layer that consumes a kernel's output as its incoming gradient, done on the block just
+// produced (GemmArgs::bnr_* for the planes GEMM); z == NULL: none
+struct BnrEpilogue {
+  const float* z;
+  const uint64_t* bits;
+  const float *mean, *rstd;
+  float kscale;
+  float *part_dy, *part_dyz;  // [B/64][H]
+  float* amax;                // optional: per (64-row group, column strip) max |dy| and max |zhat|
+};
+// out [B][H] = X [B][K] W^T + bias (the input layer's forward: W [H][K], stat_sum / stat_m2 optional) or, w_transposed,
+// X W (g = dy W5: W [K][H], no bias; bnr: 32-column strips, whole groups only)
+struct SkinnyWideOutArgs {
+  const float *X, *W, *bias;
+  float* out;
+  int B, K, H;
+  bool w_transposed;
+  float *stat_sum, *stat_m2;
+  BnrEpilogue bnr;
+};
+int launch_skinny_wide_out(const SkinnyWideOutArgs& a, hipStream_t s);
+// X^T D, X [B][K], D [B][H]: partials in part (skinny_in_chunks(B) x K x H floats), then -- reduce -- their sum in out, [K][H]
+// or, out_transposed, [H][K].  Without reduce the caller combines them (launch_reduce_rows_multi: R = skinny_in_chunks(B),
+// H = K*H, transK = K for the transposed form) and out is not touched
+struct SkinnyWideInArgs {
+  const float *X, *D;
+  int B, K, H;
+  float* part;
+  bool reduce, out_transposed;
+  float* out;
+  float* xsum;                // optional: skinny_in_chunks(B) x K partial column sums of X (the output layer's bias gradient:
+                              // X = dy), to be combined like any other partial (R = skinny_in_chunks(B), H = K)
+};
+int launch_skinny_wide_in(const SkinnyWideInArgs& a, hipStream_t s);
 int skinny_in_chunks(int B);
 bool skinny_narrow_out_supported(int H, int N);
 size_t skinny_narrow_out_part_floats(int B, int H);
-// part: [splits][B][64] slabs; reduce == false: only the slabs are written (y = bias + their sum is left to the caller)
-int launch_skinny_narrow_out(const float* h, const float* W, const float* bias, float* y, int B, int H,
-                             int N, float* part, hipStream_t s, bool reduce = true);
+// part: [splits][B][64] slabs of h W^T, then -- reduce -- y = bias + their sum; without reduce that is left to the caller
+// (mse_partial_from_slabs)
+struct SkinnyNarrowOutArgs {
+  const float *h, *W;
+  int B, H, N;
+  float* part;
+  bool reduce;
+  const float* bias;
+  float* y;
+};
+int launch_skinny_narrow_out(const SkinnyNarrowOutArgs& a, hipStream_t s);
 int skinny_narrow_out_splits(int B, int H);
 
 }  // namespace pl

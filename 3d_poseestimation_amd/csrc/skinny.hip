@@ -429,46 +429,49 @@ int skinny_in_chunks(int B) { return (B + IN_CHUNK - 1) / IN_CHUNK; }
 int skinny_stat_groups(int B) { return (B + 63) / 64; }
 
 // forward of the input layer (+ BN statistics)  /  g = dy W5 (transposed weights, no bias)
-int launch_skinny_wide_out(const float* X, const float* W, const float* bias, float* out, int B, int K,
-                           int H, bool w_transposed, float* stat_sum, float* stat_m2, hipStream_t s, const GemmArgs* bnr) {
-  if (!skinny_supported(K, H)) PL_FAIL(PL_ESHAPE, "skinny_wide_out: K=%d H=%d not specialised", K, H);
-  dim3 grid(skinny_chunks(B) * (H / 128)), block(NTHR);
-  SkinnyBnr bn = {};
-  if (bnr && bnr->bnr_z) {
-    if (!w_transposed || stat_sum || (B & 63)) PL_FAIL(PL_EINVAL, "skinny_wide_out: BatchNorm-backward epilogue only on g = dy W, whole groups");
-    bn = SkinnyBnr{bnr->bnr_z, bnr->bnr_bits, bnr->bnr_mean, bnr->bnr_rstd, bnr->bnr_kscale, bnr->bnr_part_dy, bnr->bnr_part_dyz,
-                   bnr->bnr_amax};
-    if (K == 34) hipLaunchKernelGGL((skinny_wide_out_kernel<34, true, false, true>), grid, block, 0, s, X, W, bias, out, B, H, stat_sum, stat_m2, bn);
-    else hipLaunchKernelGGL((skinny_wide_out_kernel<51, true, false, true>), grid, block, 0, s, X, W, bias, out, B, H, stat_sum, stat_m2, bn);
-    PL_CHECK_LAUNCH("skinny_wide_out");
-    return PL_OK;
-  }
-#define PL_SK(KK, WT, ST) hipLaunchKernelGGL((skinny_wide_out_kernel<KK, WT, ST>), grid, block, 0, s, X, W, bias, out, B, H, stat_sum, stat_m2, bn)
-  const bool st = stat_sum != nullptr;
-  if (K == 34 && !w_transposed) { if (st) PL_SK(34, false, true); else PL_SK(34, false, false); }
-  else if (K == 34) { if (st) PL_SK(34, true, true); else PL_SK(34, true, false); }
-  else if (K == 51 && !w_transposed) { if (st) PL_SK(51, false, true); else PL_SK(51, false, false); }
-  else { if (st) PL_SK(51, true, true); else PL_SK(51, true, false); }
-#undef PL_SK
+namespace {
+template <int K>
+void launch_wide_out(const SkinnyWideOutArgs& a, const SkinnyBnr& bn, hipStream_t s) {
+  const dim3 grid(skinny_chunks(a.B) * (a.H / 128)), block(NTHR);
+  // (WT, STATS, BNR): the forward with or without statistics, g = dy W with or without the BatchNorm-backward epilogue
+  auto launch = [&](auto WT, auto ST, auto BNR) {
+    hipLaunchKernelGGL((skinny_wide_out_kernel<K, decltype(WT)::value, decltype(ST)::value, decltype(BNR)::value>), grid, block, 0, s,
+                       a.X, a.W, a.bias, a.out, a.B, a.H, a.stat_sum, a.stat_m2, bn);
+  };
+  using T = Bool<true>;
+  using F = Bool<false>;
+  if (bn.z) launch(T{}, F{}, T{});
+  else if (a.w_transposed) { if (a.stat_sum) launch(T{}, T{}, F{}); else launch(T{}, F{}, F{}); }
+  else if (a.stat_sum) launch(F{}, T{}, F{});
+  else launch(F{}, F{}, F{});
+}
+}  // namespace
+
+int launch_skinny_wide_out(const SkinnyWideOutArgs& a, hipStream_t s) {
+  if (!skinny_supported(a.K, a.H)) PL_FAIL(PL_ESHAPE, "skinny_wide_out: K=%d H=%d not specialised", a.K, a.H);
+  if (a.bnr.z && (!a.w_transposed || a.stat_sum || (a.B & 63)))
+    PL_FAIL(PL_EINVAL, "skinny_wide_out: BatchNorm-backward epilogue only on g = dy W, whole groups");
+  const BnrEpilogue& b = a.bnr;
+  const SkinnyBnr bn = {b.z, b.bits, b.mean, b.rstd, b.kscale, b.part_dy, b.part_dyz, b.amax};   // all zero without one
+  if (a.K == 34) launch_wide_out<34>(a, bn, s); else launch_wide_out<51>(a, bn, s);
   PL_CHECK_LAUNCH("skinny_wide_out");
   return PL_OK;
 }
 
-// out = X^T D, X [B][K], D [B][H]; out is [K][H] or, transposed, [H][K]; part: chunks*K*H floats
-int launch_skinny_wide_in(const float* X, const float* D, float* out, int B, int K, int H,
-                          bool out_transposed, float* part, hipStream_t s, bool reduce, float* xsum) {
-  if (!skinny_supported(K, H)) PL_FAIL(PL_ESHAPE, "skinny_wide_in: K=%d H=%d not specialised", K, H);
-  const int nc = skinny_in_chunks(B);
-  dim3 grid(nc * (H / 32)), block(NTHR);
-  if (K == 34) hipLaunchKernelGGL((skinny_wide_in_kernel<34>), grid, block, 0, s, X, D, B, H, part, xsum);
-  else hipLaunchKernelGGL((skinny_wide_in_kernel<51>), grid, block, 0, s, X, D, B, H, part, xsum);
+// X^T D (SkinnyWideInArgs)
+int launch_skinny_wide_in(const SkinnyWideInArgs& a, hipStream_t s) {
+  if (!skinny_supported(a.K, a.H)) PL_FAIL(PL_ESHAPE, "skinny_wide_in: K=%d H=%d not specialised", a.K, a.H);
+  const int nc = skinny_in_chunks(a.B);
+  dim3 grid(nc * (a.H / 32)), block(NTHR);
+  if (a.K == 34) hipLaunchKernelGGL((skinny_wide_in_kernel<34>), grid, block, 0, s, a.X, a.D, a.B, a.H, a.part, a.xsum);
+  else hipLaunchKernelGGL((skinny_wide_in_kernel<51>), grid, block, 0, s, a.X, a.D, a.B, a.H, a.part, a.xsum);
   PL_CHECK_LAUNCH("skinny_wide_in");
-  if (!reduce) return PL_OK;
-  const int n = K * H;
-  if (out_transposed)
-    hipLaunchKernelGGL((skinny_reduce_kernel<true>), dim3((n + 15) / 16), block, 0, s, part, nc, K, H, out);
+  if (!a.reduce) return PL_OK;
+  const int n = a.K * a.H;
+  if (a.out_transposed)
+    hipLaunchKernelGGL((skinny_reduce_kernel<true>), dim3((n + 15) / 16), block, 0, s, a.part, nc, a.K, a.H, a.out);
   else
-    hipLaunchKernelGGL((skinny_reduce_kernel<false>), dim3((n + 15) / 16), block, 0, s, part, nc, K, H, out);
+    hipLaunchKernelGGL((skinny_reduce_kernel<false>), dim3((n + 15) / 16), block, 0, s, a.part, nc, a.K, a.H, a.out);
   PL_CHECK_LAUNCH("skinny_reduce");
   return PL_OK;
 }
@@ -481,18 +484,17 @@ int skinny_narrow_out_splits(int B, int H) {
 bool skinny_narrow_out_supported(int H, int N) { return N <= 64 && H % 8 == 0; }
 size_t skinny_narrow_out_part_floats(int B, int H) { return (size_t)skinny_narrow_out_splits(B, H) * B * 64; }
 
-int launch_skinny_narrow_out(const float* h, const float* W, const float* bias, float* y, int B, int H,
-                             int N, float* part, hipStream_t s, bool reduce) {
-  if (!skinny_narrow_out_supported(H, N)) PL_FAIL(PL_ESHAPE, "skinny_narrow_out: H=%d N=%d", H, N);
-  const int splits = skinny_narrow_out_splits(B, H);
-  const int tasks = ((B + 31) / 32) * splits;
-  hipLaunchKernelGGL(skinny_narrow_out_kernel, dim3((tasks + 3) / 4), dim3(NTHR), 0, s, h, W, B, H, N, splits,
-                     part);
+int launch_skinny_narrow_out(const SkinnyNarrowOutArgs& a, hipStream_t s) {
+  if (!skinny_narrow_out_supported(a.H, a.N)) PL_FAIL(PL_ESHAPE, "skinny_narrow_out: H=%d N=%d", a.H, a.N);
+  const int splits = skinny_narrow_out_splits(a.B, a.H);
+  const int tasks = ((a.B + 31) / 32) * splits;
+  hipLaunchKernelGGL(skinny_narrow_out_kernel, dim3((tasks + 3) / 4), dim3(NTHR), 0, s, a.h, a.W, a.B, a.H, a.N, splits,
+                     a.part);
   PL_CHECK_LAUNCH("skinny_narrow_out");
-  if (!reduce) return PL_OK;                  // the caller combines the slabs (mse_partial_from_slabs)
-  const int64_t n = (int64_t)B * 64;
+  if (!a.reduce) return PL_OK;                  // the caller combines the slabs (mse_partial_from_slabs)
+  const int64_t n = (int64_t)a.B * 64;
   hipLaunchKernelGGL(skinny_narrow_out_reduce_kernel, dim3((unsigned)((n + NTHR - 1) / NTHR)), dim3(NTHR), 0, s,
-                     part, splits, B, N, bias, y);
+                     a.part, splits, a.B, a.N, a.bias, a.y);
   PL_CHECK_LAUNCH("skinny_narrow_out_reduce");
   return PL_OK;
 }

@@ -188,6 +188,92 @@ def test_bf16x6_planes_pipeline_is_bitwise_the_fragment_split(pkg, layout, M, N,
     assert torch.isfinite(outs[0]).all()
 
 
+def _gpu_kernel_names(fn):
+    """Names of the GPU kernels one call of fn() launches (torch.profiler; as in test_gpu_conv.py)."""
+    from torch.profiler import profile, ProfilerActivity
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+        fn()
+        torch.cuda.synchronize()
+    return [e.name for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA]
+
+
+F32_FAMILIES = ("gemm_f32_kernel", "gemm_x6_planes_kernel", "gemm_x6_planes_nedge_kernel", "gemm_bf16_planes_kernel",
+                "gemm_f32_dual_kernel", "gemm_x6_planes_dual_kernel", "thin_gemm_kernel")
+
+
+def _f32_families(names):
+    """The kernel templates of launch_gemm_f32 among launched kernel names: the function identifier, which a mangled
+    and a demangled name both contain (no identifier of F32_FAMILIES is a substring of another)."""
+    return {f for f in F32_FAMILIES for n in names if f in n}
+
+
+# pl_gemm_arith's arithmetics: 0 fp32, 2 PL_BF16X6 (the library's main loop), 6 PL_BF16X6 on the fragment loop -- all held to
+# the fp32 bound of test_gemm_layouts / test_gemm_bf16_arithmetic_modes
+@pytest.mark.parametrize("name,kernel,arith,layout,M,N,K,splits", [
+    ("fp32 whole NT", "gemm_f32_kernel", 0, 0, 128, 128, 32, 1),
+    ("fp32 whole NN", "gemm_f32_kernel", 0, 1, 128, 128, 32, 1),
+    ("fp32 whole TN", "gemm_f32_kernel", 0, 2, 128, 128, 32, 1),
+    ("fp32 edge", "gemm_f32_kernel", 0, 0, 130, 72, 40, 1),
+    ("x6 whole", "gemm_x6_planes_kernel", 2, 0, 128, 128, 32, 1),
+    ("x6 fragment loop", "gemm_f32_kernel", 6, 0, 128, 128, 32, 1),
+    ("x6 ragged N", "gemm_x6_planes_nedge_kernel", 2, 0, 128, 72, 32, 1),
+    ("fp32 TN split-K", "gemm_f32_kernel", 0, 2, 128, 128, 256, 2),
+    ("x6 TN split-K", "gemm_x6_planes_kernel", 2, 2, 128, 128, 256, 2),
+], ids=lambda v: v.replace(" ", "-") if isinstance(v, str) and " " in v else None)
+def test_gemm_arith_routes(pkg, name, kernel, arith, layout, M, N, K, splits):
+    """launch_gemm_f32's route table (f32_route) through pl_gemm_arith at the smallest shape that reaches each
+    branch: the kernel template that ran, by name, and the result against fp64."""
+    rng = np.random.default_rng(M + N + K + layout + arith)
+    a = rng.standard_normal((M, K)).astype(np.float32)
+    b = rng.standard_normal((K, N)).astype(np.float32)
+    A = _t(a if layout != 2 else a.T)
+    Bm = _t(b.T if layout == 0 else b)
+    C = torch.full((M, N), float("nan"), device=DEV)
+    slabs = torch.empty(splits, M, N, device=DEV) if splits > 1 else None
+
+    def run():
+        rc = pkg.lib().pl_gemm_arith(layout, arith, A.data_ptr(), Bm.data_ptr(), C.data_ptr(), M, N, K, None, splits,
+                                     slabs.data_ptr() if splits > 1 else None, torch.cuda.current_stream().cuda_stream)
+        assert rc == 0, pkg.lib().pl_last_error()
+    assert _f32_families(_gpu_kernel_names(run)) == {kernel}, name
+    want = a.astype(np.float64) @ b.astype(np.float64)
+    bound = 2e-6 * (np.abs(a).astype(np.float64) @ np.abs(b).astype(np.float64)) + 1e-6
+    err = np.abs(C.cpu().numpy() - want)
+    assert np.all(err <= bound), float((err / bound).max())
+
+
+@pytest.mark.parametrize("Cout", [128, 72])
+def test_conv1x1_bf16_takes_the_bf16_planes_gemm(pkg, Cout):
+    """A 1x1 convolution in PL_BF16 is launch_gemm_f32's bf16-planes route (whole and ragged N), which pl_gemm_arith
+    cannot select: the kernel by name, the result against fp64 with the bf16 bound of test_gemm_bf16_arithmetic_modes."""
+    rng = np.random.default_rng(Cout)
+    x = rng.standard_normal((2, 8, 8, 32)).astype(np.float32)             # B H W = 128 pixels
+    w = rng.standard_normal((Cout, 1, 1, 32)).astype(np.float32)
+    got = []
+    names = _gpu_kernel_names(lambda: got.append(pkg.conv.conv2d_nhwc(_t(x), _t(w), arith="bf16")))
+    assert _f32_families(names) == {"gemm_bf16_planes_kernel"}, names
+    a, b = x.reshape(128, 32).astype(np.float64), w.reshape(Cout, 32).T.astype(np.float64)
+    err = np.abs(got[0].cpu().numpy().reshape(128, Cout) - a @ b)
+    bound = 2e-2 * (np.abs(a) @ np.abs(b)) + 1e-6
+    assert np.all(err <= bound), float((err / bound).max())
+    assert err.max() > 1e-4                                               # really bf16
+
+
+def test_thin_gemm_runs_the_small_training_batch_off_the_tile_grid(pkg):
+    """65 rows of a 64-wide lifter in fp32: launch_gemm_f32 hands its Linears to the thin GEMM (by name); the training
+    forward is as close to the fp64 oracle as the fp32 oracle is (_assert_train_fwd)."""
+    st = orc.init_state(34, 51, 64, 2, rng=np.random.default_rng(3))
+    m = _model_from_state(pkg, st, 64, 2, 0.0, True).train()
+    x = np.random.default_rng(4).random((65, 34)).astype(np.float32)
+    got = []
+    names = _gpu_kernel_names(lambda: got.append(m(_t(x))))
+    assert "thin_gemm_kernel" in _f32_families(names), names
+    p32, _ = orc.forward({k: v.copy() for k, v in st.items()}, x, num_stage=2, train=True, p_dropout=0.0)
+    p64, _ = orc.forward({k: v.copy() for k, v in st.items()}, x, num_stage=2, train=True, p_dropout=0.0, dtype=np.float64)
+    _assert_train_fwd(got[0].detach().cpu().numpy(), p32, p64)
+
+
 # ---------------------------------------------------------------------------- golden vectors
 @pytest.mark.parametrize("dtype", ["fp32", "bf16x6", "f16x3"])
 def test_g1_eval_forward_vs_reference(pkg, dtype):

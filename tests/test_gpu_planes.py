@@ -71,6 +71,70 @@ def test_planes_gemm_vs_fp64(pkg, mode, tol, layout, M, N, K):
         assert err.max() > 1e-4                       # really one bf16 product
 
 
+def _gpu_kernel_names(fn):
+    """Names of the GPU kernels one call of fn() launches (torch.profiler; as in test_gpu_conv.py)."""
+    from torch.profiler import profile, ProfilerActivity
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+        fn()
+        torch.cuda.synchronize()
+    return [e.name for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA]
+
+
+PLANES_FAMILIES = ("planes_gemm_kernel", "planes_gemm_persistent_kernel", "planes_gemm_wide_kernel", "planes_gemm_t64_kernel",
+                   "planes_gemm_chain_kernel", "planes_gemm_dual_kernel")
+
+
+def _planes_families(names):
+    """The planes GEMM kernel templates among launched kernel names: the function identifier, which a mangled and a
+    demangled name both contain (no identifier of PLANES_FAMILIES is a substring of another)."""
+    return {f for f in PLANES_FAMILIES for n in names if f in n}
+
+
+def _ncu():
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+# (name, kernel family, layout, M as a function of the device's CU count, N, K)
+ROUTE_CASES = [
+    ("one-item NT", "planes_gemm_kernel", 0, lambda n: 128, 128, 32),
+    ("one-item NN", "planes_gemm_kernel", 1, lambda n: 128, 128, 32),
+    ("one-item TN", "planes_gemm_kernel", 2, lambda n: 128, 128, 32),
+    ("one-item edge", "planes_gemm_kernel", 0, lambda n: 200, 192, 64),
+    ("t64", "planes_gemm_t64_kernel", 0, lambda n: 256, 64, 32),
+    ("t64 edge", "planes_gemm_t64_kernel", 0, lambda n: 1, 8, 32),
+    ("t64 persistent", "planes_gemm_t64_kernel", 0, lambda n: 256 * 2 * n, 64, 32),
+    ("wide", "planes_gemm_wide_kernel", 0, lambda n: 128, 128, 1024),
+    ("wide edge", "planes_gemm_wide_kernel", 0, lambda n: 136, 128, 1024),
+    ("wide persistent", "planes_gemm_wide_kernel", 0, lambda n: 128 * 2 * n, 128, 1024),
+    ("persistent", "planes_gemm_persistent_kernel", 0, lambda n: 128 * 2 * n, 128, 32),
+    ("persistent edge", "planes_gemm_persistent_kernel", 0, lambda n: 128 * 2 * n + 8, 128, 32),
+    ("one tile below persistent", "planes_gemm_kernel", 0, lambda n: 128 * (2 * n - 1), 128, 32),
+]
+
+
+@pytest.mark.parametrize("mode,tol", [(PL_F16X3, 2e-6), (PL_BF16, 2e-2)])
+@pytest.mark.parametrize("name,kernel,layout,rows,N,K", ROUTE_CASES, ids=[c[0].replace(" ", "-") for c in ROUTE_CASES])
+def test_planes_gemm_routes(pkg, mode, tol, name, kernel, layout, rows, N, K):
+    """launch_gemm_planes' route table (planes_route) at the smallest shape that reaches each branch, the
+    thresholds that depend on the CU count taken from the device: the kernel family that ran, by name, and the result
+    against fp64 with the bounds of test_planes_gemm_vs_fp64 (reference and bound formed in fp64 on the device: the
+    persistent shapes have 2 ncu tiles)."""
+    M = rows(_ncu())
+    rng = np.random.default_rng(M + 3 * N + 7 * K + layout)
+    a = rng.standard_normal((M, K), dtype=np.float32)
+    b = rng.standard_normal((K, N), dtype=np.float32) * np.float32(0.05)
+    bias = rng.standard_normal(N, dtype=np.float32)
+    got = []
+    names = _gpu_kernel_names(lambda: got.append(_planes_gemm(pkg, layout, mode, a, b, bias, sa=1.0, sb=16.0)))
+    assert _planes_families(names) == {kernel}, (name, names)
+    a64, b64, bias64 = _t(a).double(), _t(b).double(), _t(bias).double()
+    want = a64 @ b64 + bias64
+    bound = tol * (a64.abs() @ b64.abs() + bias64.abs()) + 1e-7
+    err = (_t(got[0]).double() - want).abs()
+    assert bool((err <= bound).all()), (name, float((err / bound).max()))
+
+
 def test_planes_gemm_asymmetric_operands_catch_transposes(pkg):
     """A = I with an asymmetric B returns B itself: a swapped fragment or accumulator map cannot hide."""
     n = 256
@@ -230,6 +294,11 @@ def test_graphed_train_step_is_bitwise_the_eager_one(pkg, dtype, B, H):
     assert torch.equal(l1, l2)
 
 
+# the hidden layers' backward pair (dX and dW in one launch, launch_gemm_planes_pair) at B = 640 by linear_size: five dX tiles
+# and five dW items chain; ten tiles and twenty items run side by side
+PAIR_KERNEL = {128: "planes_gemm_chain_kernel", 256: "planes_gemm_dual_kernel"}
+
+
 @pytest.mark.parametrize("dtype,B,H", [("fp32", 96, 128), ("f16x3", 256, 256), ("bf16x6", 160, 256)])
 def test_eval_mode_backward_vs_torch_twin(pkg, dtype, B, H):
     """model.eval() inside an autograd graph -- phase5_loop/train_5.py:120 runs the lifter in eval mode with gradients
@@ -270,6 +339,11 @@ def test_eval_mode_backward_vs_torch_twin(pkg, dtype, B, H):
         if "running" in k or "num_batches" in k:
             assert torch.equal(after[k].cpu(), v), k
     assert m._live_graphs == 0
+    if dtype == "f16x3":                 # (once) one training backward per form of the pair launch: the kernel, by name
+        for Hp, kernel in PAIR_KERNEL.items():
+            mp = pkg.LinearModel(34, 51, linear_size=Hp, compute_dtype="f16x3").to(DEV).train()
+            loss = (mp(torch.rand(640, 34, device=DEV)) ** 2).mean()
+            assert _planes_families(_gpu_kernel_names(loss.backward)) & set(PAIR_KERNEL.values()) == {kernel}
 
 
 # ---------------------------------------------------------------------------- freshness of the persistent weight planes

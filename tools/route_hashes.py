@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""sha256 of everything the lifter's and the conv path's BatchNorm launches, the flat optimizers and the soft-argmax heads
-write, one line per (case, buffer):
+"""sha256 of everything the lifter's and the conv path's BatchNorm launches, the flat optimizers, the soft-argmax heads and
+the GEMM launchers (every branch of their route tables) write, one line per (case, buffer):
 
     python tools/route_hashes.py > hashes.txt          (POSELIFT_LIB=... picks another build of the library)
 
@@ -481,8 +481,137 @@ def heads_cases():
         case_heads_model(dtype)
 
 
+# ------------------------------------------------------------------------------------------------ GEMM launchers
+def gemm_planes_case(name, layout, mode, M, N, K):
+    """pl_gemm_planes (launch_gemm_planes behind two plane splits)"""
+    g = torch.Generator().manual_seed(M + 3 * N + 7 * K + layout)
+    A = torch.randn((K, M) if layout == 2 else (M, K), generator=g).to(DEV)
+    Bm = (torch.randn((N, K) if layout == 0 else (K, N), generator=g) * 0.05).to(DEV)
+    bias = torch.randn(N, generator=g).to(DEV)
+    C = full(M, N)
+    L = _lib.lib()
+    scratch = torch.zeros(L.pl_gemm_planes_scratch_bytes(M, N, K), dtype=torch.uint8, device=DEV)
+    rc = L.pl_gemm_planes(layout, mode, A.data_ptr(), Bm.data_ptr(), C.data_ptr(), M, N, K, bias.data_ptr(), 1.0, 16.0,
+                          scratch.data_ptr(), _lib.current_stream_ptr())
+    _lib.check(rc, "pl_gemm_planes")
+    torch.cuda.synchronize()
+    emit(f"gemm/planes/{name}/mode{mode}/l{layout}-{M}x{N}x{K}", C=C, scratch=scratch.view(torch.int32))
+
+
+def gemm_arith_case(arith, layout, M, N, K, splits=1):
+    """pl_gemm_arith (launch_gemm_f32), slabs included"""
+    g = torch.Generator().manual_seed(M + N + K + layout)
+    A = torch.randn((K, M) if layout == 2 else (M, K), generator=g).to(DEV)
+    Bm = torch.randn((N, K) if layout == 0 else (K, N), generator=g).to(DEV)
+    bias = torch.randn(N, generator=g).to(DEV) if splits == 1 else None
+    C, slabs = full(M, N), full(splits, M, N) if splits > 1 else None
+    rc = _lib.lib().pl_gemm_arith(layout, arith, A.data_ptr(), Bm.data_ptr(), C.data_ptr(), M, N, K,
+                                  bias.data_ptr() if bias is not None else None, splits,
+                                  slabs.data_ptr() if slabs is not None else None, _lib.current_stream_ptr())
+    _lib.check(rc, "pl_gemm_arith")
+    torch.cuda.synchronize()
+    emit(f"gemm/arith{arith}/l{layout}-{M}x{N}x{K}-s{splits}", C=C, slabs=slabs)
+
+
+def conv_planes_case(mode, B, H, W, Cin, Cout, K, stride, pad):
+    """pl_conv2d_planes_fwd (with the epilogue's statistics) and pl_conv2d_planes_wgrad (slabs included)"""
+    cv, L, s = pkg.conv, _lib.lib(), _lib.current_stream_ptr()
+    g = torch.Generator().manual_seed(B * 131 + H * 17 + Cin + Cout + K)
+    x = torch.randn(B, H, W, Cin, generator=g).to(DEV)
+    w = (torch.randn(Cout, K, K, Cin, generator=g) * 0.05).to(DEV)
+    Ho, Wo = (H + 2 * pad - K) // stride + 1, (W + 2 * pad - K) // stride + 1
+    dz = torch.randn(B, Ho, Wo, Cout, generator=g).to(DEV)
+    xp, wp, dzp = cv._planes_of(x, 1.0, mode), cv._planes_of(w, 16.0, mode), cv._planes_of(dz, 1.0, mode)
+    y, stat = full(B, Ho, Wo, Cout), full(2, L.pl_gemm_stat_groups(B * Ho * Wo), Cout)
+    rc = L.pl_conv2d_planes_fwd(mode, xp.data_ptr(), x.numel(), B, H, W, Cin, wp.data_ptr(), w.numel(), Cout, K, K, stride, pad,
+                                y.data_ptr(), 1.0 / 16.0, None, stat.data_ptr(), s)
+    _lib.check(rc, "pl_conv2d_planes_fwd")
+    name = f"gemm/conv-planes/mode{mode}/{B}x{H}x{W}x{Cin}-{Cout}-k{K}s{stride}"
+    torch.cuda.synchronize()
+    emit(name, y=y, stat=stat)
+    if (B * Ho * Wo) % 32 == 0:
+        splits = L.pl_gemm_planes_splits(Cout, K * K * Cin, B * Ho * Wo)
+        slabs = full(splits, Cout * K * K * Cin) if splits > 1 else None
+        dw = full(Cout, K, K, Cin)
+        rc = L.pl_conv2d_planes_wgrad(mode, dzp.data_ptr(), dz.numel(), xp.data_ptr(), x.numel(), B, H, W, Cin, Cout, K, K, stride,
+                                      pad, dw.data_ptr(), 1.0, None, slabs.data_ptr() if slabs is not None else None, s)
+        _lib.check(rc, "pl_conv2d_planes_wgrad")
+        torch.cuda.synchronize()
+        emit(name + f"/wgrad-s{splits}", dw=dw, slabs=slabs)
+
+
+def deconv_planes_case(mode, B, H, W, Cin, Cout):
+    cv, L = pkg.conv, _lib.lib()
+    g = torch.Generator().manual_seed(B + 7 * H + Cin + 3 * Cout)
+    x = torch.randn(B, H, W, Cin, generator=g).to(DEV)
+    w = (torch.randn(Cin, Cout, 4, 4, generator=g) * 0.05).to(DEV)
+    xp, wsub = cv._planes_of(x, 1.0, mode), cv._planes_of(cv.deconv_subkernels(w), 16.0, mode)
+    y = full(B, 2 * H, 2 * W, Cout)
+    rc = L.pl_deconv4x4s2_planes_fwd(mode, xp.data_ptr(), x.numel(), B, H, W, Cin, wsub.data_ptr(), wsub.numel(), Cout, y.data_ptr(),
+                                     1.0 / 16.0, None, _lib.current_stream_ptr())
+    _lib.check(rc, "pl_deconv4x4s2_planes_fwd")
+    torch.cuda.synchronize()
+    emit(f"gemm/deconv-planes/mode{mode}/{B}x{H}x{W}x{Cin}-{Cout}", y=y)
+
+
+def conv_nhwc_case(arith, B, H, Cin, Cout, K, stride, pad):
+    """pl_conv2d_nhwc_fwd / _wgrad (launch_conv_nhwc, launch_conv_wgrad; 1x1: launch_gemm_f32) through the package"""
+    g = torch.Generator().manual_seed(B + H + Cin + Cout + K)
+    x = torch.randn(B, H, H, Cin, generator=g).to(DEV)
+    w = (torch.randn(Cout, K, K, Cin, generator=g) * 0.05).to(DEV)
+    y = pkg.conv.conv2d_nhwc(x, w, stride, pad, arith=arith)
+    dw = pkg.conv.conv2d_nhwc_wgrad(x, torch.randn(y.shape, generator=g).to(DEV), K, stride, pad, arith=arith)
+    torch.cuda.synchronize()
+    emit(f"gemm/conv-nhwc/{arith}/{B}x{H}x{H}x{Cin}-{Cout}-k{K}s{stride}", y=y, dw=dw)
+
+
+def gemm_cases():
+    ncu = torch.cuda.get_device_properties(0).multi_processor_count
+    # every branch of planes_route (DESIGN 3a; tests/test_gpu_planes.py test_planes_gemm_routes), both modes
+    for mode in (3, 1):
+        for name, layout, M, N, K in (("one-item", 0, 128, 128, 32), ("one-item", 1, 128, 128, 32), ("one-item", 2, 128, 128, 32),
+                                      ("one-item-edge", 0, 200, 192, 64), ("t64", 0, 256, 64, 32), ("t64-edge", 0, 1, 8, 32),
+                                      ("t64-persistent", 0, 256 * 2 * ncu, 64, 32), ("wide", 0, 128, 128, 1024),
+                                      ("wide-edge", 0, 136, 128, 1024), ("wide-persistent", 0, 128 * 2 * ncu, 128, 1024),
+                                      ("persistent", 0, 128 * 2 * ncu, 128, 32), ("persistent-edge", 0, 128 * 2 * ncu + 8, 128, 32),
+                                      ("below-persistent", 0, 128 * (2 * ncu - 1), 128, 32)):
+            gemm_planes_case(name, layout, mode, M, N, K)
+    # every branch of f32_route that pl_gemm_arith reaches (tests/test_gpu_parity.py test_gemm_arith_routes)
+    for arith, layout, M, N, K, splits in ((0, 0, 128, 128, 32, 1), (0, 1, 128, 128, 32, 1), (0, 2, 128, 128, 32, 1),
+                                           (0, 0, 130, 72, 40, 1), (1, 0, 128, 128, 32, 1), (2, 0, 128, 128, 32, 1),
+                                           (5, 1, 128, 128, 32, 1), (6, 0, 128, 128, 32, 1), (2, 0, 128, 72, 32, 1),
+                                           (0, 2, 128, 128, 256, 2), (2, 2, 128, 128, 256, 2)):
+        gemm_arith_case(arith, layout, M, N, K, splits)
+    # ... the bf16-planes GEMM (a 1x1 convolution in PL_BF16, whole and ragged N) and the implicit-GEMM launchers: 3x3 whole,
+    # ragged (Cout = 72 / 189 pixels) and split-K (128 pixels of 1152 k), weight gradients
+    for arith in ("bf16", "bf16x6"):
+        for B, H, Cin, Cout, K, stride, pad in ((2, 8, 32, 128, 1, 1, 0), (2, 8, 32, 72, 1, 1, 0), (2, 8, 128, 128, 3, 1, 1),
+                                                (2, 16, 64, 72, 3, 2, 1), (2, 32, 128, 128, 3, 1, 1)):
+            conv_nhwc_case(arith, B, H, Cin, Cout, K, stride, pad)
+        g = torch.Generator().manual_seed(8)
+        x = torch.randn(2, 8, 8, 64, generator=g).to(DEV)
+        for cout in (128, 72):                                  # launch_conv_nhwc_group4, whole and ragged
+            wsub = pkg.conv.deconv_subkernels((torch.randn(64, cout, 4, 4, generator=g) * 0.05).to(DEV))
+            y = pkg.conv.deconv4x4s2_nhwc(x, wsub, arith=arith)
+            torch.cuda.synchronize()
+            emit(f"gemm/deconv-nhwc/{arith}/2x8x8x64-{cout}", y=y)
+    # the planes convolutions (tests/test_gpu_conv.py's smallest shapes: t64 / edge / row gather / ragged M / split-K wgrad)
+    for mode in (3, 1):
+        for shape in ((2, 16, 16, 64, 64, 3, 1, 1), (2, 16, 24, 32, 128, 3, 2, 1), (2, 8, 8, 128, 72, 1, 2, 0),
+                      (3, 9, 7, 64, 96, 3, 1, 1), (1, 32, 32, 96, 256, 3, 1, 1)):
+            conv_planes_case(mode, *shape)
+        for shape in ((2, 8, 8, 64, 128), (1, 6, 10, 96, 64), (3, 4, 4, 256, 256)):
+            deconv_planes_case(mode, *shape)
+    # the thin GEMM (65 rows of a 64-wide fp32 lifter) and the backward pair, chained (five dX tiles, five dW items) and dual
+    case_autograd("gemm/thin/fp32/B65/H64", 65, 64, 2, "fp32", 0.0)
+    for dtype in ("f16x3", "bf16", "fp32", "bf16x6"):
+        for H in (128, 256):
+            case_autograd(f"gemm/pair/{dtype}/B640/H{H}", 640, H, 2, dtype, 0.5)
+
+
 if __name__ == "__main__":
     lifter_cases()
     conv_cases()
     optimizer_cases()
     heads_cases()
+    gemm_cases()
