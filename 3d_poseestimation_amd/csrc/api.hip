@@ -153,7 +153,7 @@ enum class Stats : uint8_t {   // BatchNorm statistics of a training forward
   InApply,
   Finalize,                    // a finalize launch of its own
 };
-enum class Bwd : uint8_t {     // backward of a hidden layer's Linear in training (eval_bn: F32Pair, or First)
+enum class Bwd : uint8_t {     // backward of a hidden layer's Linear in training (eval_bn: PlanesPair or F32Pair, or First)
   PlanesPair, F32Pair,         // dX = dz W and dW = dz^T a in one launch, on the operand planes / on fp32
   SmallLayer, SmallLayerDw,    // dX and the layer below's BatchNorm backward in one small_layer.hip launch; dW a GEMM / in it
   InAbove,                     // first layer: dW1 follows its BatchNorm backward in layer 1's launch (when in the range) ...

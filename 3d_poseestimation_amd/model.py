@@ -436,8 +436,11 @@ class LinearModel(nn.Module):
         if token is None or ws["busy"] == token:
             ws["busy"] = None
 
-    def workspace_view(self, ws, which, layer):
-        """Debug/test: a saved tensor of the last training forward (pl_workspace_view)."""
+    def workspace_view(self, ws, which, layer, row_bitmap=False):
+        """Debug/test: a saved tensor of the last training forward (pl_workspace_view).
+        row_bitmap: the bitmap (which = 2) is in the row format whatever pl_workspace_bitmap_format says of a training
+        forward at this batch -- the eval-mode saved forward (_LifterEvalFn) takes none of the small-batch launches and
+        writes the row format at every batch size."""
         off, size = ctypes.c_size_t(), ctypes.c_size_t()
         _lib.check(_lib.lib().pl_workspace_view(ctypes.byref(self._desc), ws["B"], which, layer,
                                                 ctypes.byref(off), ctypes.byref(size)), "pl_workspace_view")
@@ -447,7 +450,7 @@ class LinearModel(nn.Module):
             return raw.view(torch.float32).view(ws["B"], H)
         if which == 2:
             # always handed out in the row format (layout.unpack_bitmap); small batches keep a tile format on the device
-            fmt = _lib.lib().pl_workspace_bitmap_format(ctypes.byref(self._desc), ws["B"], layer)
+            fmt = 0 if row_bitmap else _lib.lib().pl_workspace_bitmap_format(ctypes.byref(self._desc), ws["B"], layer)
             _lib.check(min(fmt, 0), "pl_workspace_bitmap_format")
             words = raw.view(torch.int64)
             if fmt == 1:
@@ -511,6 +514,8 @@ class LinearModel(nn.Module):
             self._guarded(ws, lambda: _lib.lib().pl_lifter_bwd(*args, _lib.current_stream_ptr()), "pl_lifter_bwd")
         if accumulate:
             for s, p in zip(self._slots, self._param_list):
+                if not self.BN and "batch_norm" in s.name:
+                    continue                  # unused parameters have no gradient, on this path as on the one below
                 gview = target[s.offset:s.offset + s.numel].view(s.shape)
                 if p.grad is None:
                     p.grad = gview.clone()

@@ -132,7 +132,8 @@ int pl_workspace_view(const PLDesc* d, int64_t B, int which, int64_t layer,
  *   0  row format: [B][4*ceil(H/256)] words; row r, 256-column strip q, word j: bit l <-> column 256 q + 4 l + j;
  *   1  tile format (batches of <= 64 rows whose hidden layers run as ONE launch each, csrc/small_layer.hip): H words;
  *      element (r, c) is bit (r & 15) * 4 + ((c >> 2) & 3) of word (c >> 4) * 16 + (r >> 4) * 4 + (c & 3).
- * Negative = error code.  (Debug / test only: the backward pass knows by itself.) */
+ * Negative = error code.  (Debug / test only: the backward pass knows by itself.)
+ * pl_lifter_fwd_eval_saved takes none of the small-batch launches: it writes format 0 at every B, whatever this returns. */
 int pl_workspace_bitmap_format(const PLDesc* d, int64_t B, int64_t layer);
 
 /* ---- forward ------------------------------------------------------------------- */
