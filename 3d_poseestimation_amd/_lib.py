@@ -80,6 +80,12 @@ class PLPlanesEpilogue(ctypes.Structure):
                 ("relu", ctypes.c_int32), ("reserved", ctypes.c_int32), ("y_planes", ctypes.c_void_p)]
 
 
+class PLPoseAug(ctypes.Structure):
+    _fields_ = [("p_flip", ctypes.c_float), ("flip_offset", ctypes.c_float), ("max_rot", ctypes.c_float),
+                ("scale_range", ctypes.c_float), ("max_shift", ctypes.c_float), ("jitter_sigma", ctypes.c_float),
+                ("cx", ctypes.c_float), ("cy", ctypes.c_float), ("seed", ctypes.c_uint64)]
+
+
 _c = ctypes
 _P = ctypes.c_void_p
 _D = ctypes.POINTER(PLDesc)
@@ -183,6 +189,8 @@ SIGNATURES = {
                                            _c.c_int, _P, _c.c_int, _P, _c.c_size_t, _P]),
     "pl_nhwc_to_nchw": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _c.c_int64, _P, _P]),
     "pl_gather_rows2": (_c.c_int, [_P, _c.c_int64, _P, _c.c_int64, _P, _c.c_int64, _c.c_int64, _P, _P, _P]),
+    "pl_pose_augment_gather": (_c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_int64, _P, _P, _c.POINTER(PLPoseAug), _c.c_uint64, _P]),
+    "pl_pose_augment_host": (_c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_int64, _P, _P, _c.POINTER(PLPoseAug), _c.c_uint64]),
     "pl_flip_tta_pack": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _c.c_int64, _P]),
     "pl_flip_tta_merge": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _c.c_int64, _P]),
     "pl_softargmax_dl_scale": (_c.c_int, [_P, _c.c_int64, _c.c_int, _P, _P]),

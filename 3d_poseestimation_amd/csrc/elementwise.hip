@@ -13,6 +13,7 @@
 #include "adamw.h"
 #include "bn_pieces.h"
 #include "philox.h"
+#include "pose_augment.h"
 #include <stdlib.h>
 
 #include <algorithm>
@@ -1346,6 +1347,83 @@ __global__ void gather_rows2_kernel(const float* __restrict__ a, int wa, const f
   else ob[i * wb + (c - wa)] = b[r * wb + (c - wa)];
 }
 
+// ---- augmented batch gather (data.py PoseFeeder(augment=...), augment_poses): pose_augment.h applied where the row is read ----
+// 32 lanes share a pose (two poses per wave, eight per workgroup).  The pose's Philox calls are spread over the group, one
+// call per lane: lane 0 turns c2 = 0 into the flip bit, sin / cos and the scale, lane 1 c2 = 1 into the shift, lanes 2..10
+// one call each into four noise values; the group then reads them with shuffles of width 32, so no draw, sincosf or logf is
+// made twice for a pose.  Output element e = lane, lane + 32, lane + 64 (< 85; the first 34 are a's, the rest b's):
+// consecutive lanes store consecutive floats, and load them too unless the pose is flipped (then joints swap inside the
+// 340-byte row).  Every stage test is on a kernel argument, the same in all lanes; with all stages off the kernel is
+// gather_rows2's copy.  A source index outside [0, table_rows) reads nothing and yields a NaN pose.
+constexpr int PA_LANES = 32;
+__global__ __launch_bounds__(NTHR) void pose_augment_gather_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                                   const int64_t* __restrict__ src_idx,
+                                                                   const int64_t* __restrict__ row_id, int64_t n,
+                                                                   int64_t table_rows, float* __restrict__ oa,
+                                                                   float* __restrict__ ob, pa::Plan p) {
+  const int gl = threadIdx.x & (PA_LANES - 1);
+  const int64_t k = (int64_t)blockIdx.x * (NTHR / PA_LANES) + (threadIdx.x / PA_LANES);
+  if (k >= n) return;                                   // a whole group leaves; no shuffle below crosses a group
+  const int64_t src = src_idx ? src_idx[k] : k;
+  const uint64_t row = (uint64_t)row_id[k];
+  const bool ok = src >= 0 && src < table_rows;
+  const float* ar = a + (ok ? src : 0) * pa::kWA;
+  const float* br = b + (ok ? src : 0) * pa::kWB;
+
+  const bool any0 = pa::needs_call(p, 0), any1 = pa::needs_call(p, 1), any2 = pa::needs_call(p, 2);
+  pa::Pose q = {p.flip_mode == 2, 1.f, 0.f, 1.f, 0.f, 0.f};
+  float nz[4] = {0.f, 0.f, 0.f, 0.f};
+  if (gl < pa::kCalls && pa::needs_call(p, gl)) {
+    uint32_t w[4];
+    pa::draw(p, row, gl, w);
+    if (gl == 0) pa::decide0(p, w, q);
+    else if (gl == 1) pa::decide1(p, w, q);
+    else pa::noise4(p, w, nz);
+  }
+  if (any0) {
+    q.flip = __shfl(q.flip, 0, PA_LANES);
+    q.cs = __shfl(q.cs, 0, PA_LANES);
+    q.sn = __shfl(q.sn, 0, PA_LANES);
+    q.sc = __shfl(q.sc, 0, PA_LANES);
+  }
+  if (any1) {
+    q.tx = __shfl(q.tx, 1, PA_LANES);
+    q.ty = __shfl(q.ty, 1, PA_LANES);
+  }
+  float nz_lo = 0.f, nz_hi = 0.f;                       // noise of a's elements gl and gl + 32 (the latter: lanes 0, 1)
+  if (any2) {
+    const int from = 2 + (gl >> 2);
+    const float t0 = __shfl(nz[0], from, PA_LANES), t1 = __shfl(nz[1], from, PA_LANES);
+    const float t2 = __shfl(nz[2], from, PA_LANES), t3 = __shfl(nz[3], from, PA_LANES);
+    nz_lo = (gl & 2) ? ((gl & 1) ? t3 : t2) : ((gl & 1) ? t1 : t0);
+    const float u0 = __shfl(nz[0], 2 + (32 >> 2), PA_LANES), u1 = __shfl(nz[1], 2 + (32 >> 2), PA_LANES);
+    nz_hi = (gl & 1) ? u1 : u0;
+  }
+
+  const bool rot = p.max_rot != 0.f;
+  const float bad = __int_as_float(0x7fc00000);
+  float* oar = oa + k * pa::kWA;
+  float* obr = ob + k * pa::kWB;
+#pragma unroll
+  for (int it = 0; it < 3; ++it) {
+    const int e = gl + PA_LANES * it;
+    if (e < pa::kWA) {
+      const int j = e >> 1, d = e & 1, sj = q.flip ? pa::flip_src_joint(j) : j;
+      float v = bad;
+      if (ok) v = pa::elem2d(p, q, d, ar[sj * 2 + d], rot ? ar[sj * 2 + (d ^ 1)] : 0.f, it == 0 ? nz_lo : nz_hi);
+      oar[e] = v;
+    } else if (e < pa::kRow) {
+      const int c = e - pa::kWA, j = c / 3, d = c - 3 * j, sj = q.flip ? pa::flip_src_joint(j) : j;
+      float v = bad;
+      if (ok) {
+        v = br[sj * 3 + d];
+        if (d != 2) v = pa::elem3d(p, q, d, v, rot ? br[sj * 3 + (d ^ 1)] : 0.f);
+      }
+      obr[c] = v;
+    }
+  }
+}
+
 // ---- flat AdamW (torch single-tensor update order): AdamWIn, adamw_consts, adamw_one in adamw.h ---------
 // CLIP: the step behind pl_grad_norm_clip (in.clip set).  A skipped step writes no p, m, v; it still writes the operand
 // planes, from the unchanged parameters -- the host marks them current after every launch (optim.FlatAdamW._launch), and
@@ -1922,6 +2000,66 @@ extern "C" int pl_gather_rows2(const float* a, int64_t wa, const float* b, int64
   hipLaunchKernelGGL(gather_rows2_kernel, dim3((unsigned)((total + NTHR - 1) / NTHR)), dim3(NTHR), 0,
                      (hipStream_t)stream, a, (int)wa, b, (int)wb, idx, n, oa, ob);
   PL_CHECK_LAUNCH("gather_rows2");
+  return PL_OK;
+}
+
+// Argument checks shared by pl_pose_augment_gather and pl_pose_augment_host; on success *plan is what the transform reads.
+static bool pa_overlap(const float* x, int64_t nx, const float* y, int64_t ny) {
+  const uintptr_t x0 = (uintptr_t)x, x1 = x0 + (uintptr_t)nx * sizeof(float);
+  const uintptr_t y0 = (uintptr_t)y, y1 = y0 + (uintptr_t)ny * sizeof(float);
+  return x0 < y1 && y0 < x1;
+}
+static int pose_augment_args(const char* fn, const float* a, const float* b, const int64_t* src_idx, const int64_t* row_id,
+                             int64_t n, int64_t table_rows, float* oa, float* ob, const PLPoseAug* aug, uint64_t epoch,
+                             pa::Plan* plan) {
+  if (!a || !b || !row_id || !oa || !ob || !aug) PL_FAIL(PL_EINVAL, "%s: null pointer", fn);
+  if (n <= 0 || table_rows <= 0 || n > (int64_t)INT32_MAX * (NTHR / PA_LANES) || table_rows > INT64_MAX / (4 * pa::kRow))
+    PL_FAIL(PL_ESHAPE, "%s: n=%lld rows=%lld", fn, (long long)n, (long long)table_rows);
+  if (!src_idx && n > table_rows)
+    PL_FAIL(PL_ESHAPE, "%s: n=%lld exceeds the %lld rows of an ungathered batch", fn, (long long)n, (long long)table_rows);
+  if (pa_overlap(oa, n * pa::kWA, ob, n * pa::kWB) || pa_overlap(oa, n * pa::kWA, a, table_rows * pa::kWA) ||
+      pa_overlap(oa, n * pa::kWA, b, table_rows * pa::kWB) || pa_overlap(ob, n * pa::kWB, a, table_rows * pa::kWA) ||
+      pa_overlap(ob, n * pa::kWB, b, table_rows * pa::kWB))
+    PL_FAIL(PL_EINVAL, "%s: aliased pointers (the outputs overlap each other or a source)", fn);
+  const struct { const char* name; float v; bool nonneg; } par[] = {
+      {"p_flip", aug->p_flip, true},         {"flip_offset", aug->flip_offset, false},   {"max_rot", aug->max_rot, true},
+      {"scale_range", aug->scale_range, true}, {"max_shift", aug->max_shift, true},      {"jitter_sigma", aug->jitter_sigma, true},
+      {"cx", aug->cx, false},                {"cy", aug->cy, false}};
+  for (const auto& q : par) {
+    if (!(fabsf(q.v) <= 3.402823466e38f)) PL_FAIL(PL_EINVAL, "%s: %s is not finite", fn, q.name);
+    if (q.nonneg && q.v < 0.f) PL_FAIL(PL_EINVAL, "%s: %s=%g is negative", fn, q.name, (double)q.v);
+  }
+  if (aug->scale_range >= 1.f) PL_FAIL(PL_EINVAL, "%s: scale_range=%g must be below 1", fn, (double)aug->scale_range);
+  *plan = pa::plan_of(aug->p_flip, dropout_threshold(aug->p_flip), aug->flip_offset, aug->max_rot, aug->scale_range,
+                      aug->max_shift, aug->jitter_sigma, aug->cx, aug->cy, aug->seed, epoch);
+  return PL_OK;
+}
+
+extern "C" int pl_pose_augment_gather(const float* a, const float* b, const int64_t* src_idx, const int64_t* row_id,
+                                      int64_t n, int64_t table_rows, float* oa, float* ob, const PLPoseAug* aug,
+                                      uint64_t epoch, void* stream) {
+  pa::Plan plan;
+  PL_TRY(pose_augment_args("pl_pose_augment_gather", a, b, src_idx, row_id, n, table_rows, oa, ob, aug, epoch, &plan));
+  constexpr int per = NTHR / PA_LANES;
+  hipLaunchKernelGGL(pose_augment_gather_kernel, dim3((unsigned)((n + per - 1) / per)), dim3(NTHR), 0, (hipStream_t)stream,
+                     a, b, src_idx, row_id, n, table_rows, oa, ob, plan);
+  PL_CHECK_LAUNCH("pose_augment_gather");
+  return PL_OK;
+}
+
+extern "C" int pl_pose_augment_host(const float* a, const float* b, const int64_t* src_idx, const int64_t* row_id, int64_t n,
+                                    int64_t table_rows, float* oa, float* ob, const PLPoseAug* aug, uint64_t epoch) {
+  pa::Plan plan;
+  PL_TRY(pose_augment_args("pl_pose_augment_host", a, b, src_idx, row_id, n, table_rows, oa, ob, aug, epoch, &plan));
+  for (int64_t k = 0; k < n; ++k) {
+    const int64_t src = src_idx ? src_idx[k] : k;
+    if (src < 0 || src >= table_rows)
+      PL_FAIL(PL_EINVAL, "pl_pose_augment_host: src_idx[%lld]=%lld is outside the table", (long long)k, (long long)src);
+  }
+  for (int64_t k = 0; k < n; ++k) {
+    const int64_t src = src_idx ? src_idx[k] : k;
+    pa::augment_pose(plan, (uint64_t)row_id[k], a + src * pa::kWA, b + src * pa::kWB, oa + k * pa::kWA, ob + k * pa::kWB);
+  }
   return PL_OK;
 }
 

@@ -12,7 +12,16 @@ batches ahead; the consumer only waits on an event.
 
 Data parallel: every rank draws the same permutation (same seed) and takes its `dp.shard_rows`
 slice of each global batch of `batch_size * world` rows.
+
+Train-time augmentation (`PoseAugment`: horizontal flip, in-plane rotation, 2-D scale, shift and Gaussian jitter; the
+reference's commented-out H36_dataset.py:98-117 and train_1.py:83-84) happens inside the launch that builds the batch
+(pl_pose_augment_gather, csrc/pose_augment.h).  Every draw of a pose is a function of (seed, epoch, dataset row), so a run
+replays bit for bit under another batch size, rank count or feeder mode.
 """
+import ctypes
+import dataclasses
+import math
+
 import torch
 
 from . import _lib
@@ -59,17 +68,108 @@ def epoch_steps(n_rows, batch_size, *, drop_last=False, world=1):
     return full + (1 if (world == 1 or tail // world >= 2) else 0)
 
 
+@dataclasses.dataclass(frozen=True)
+class PoseAugment:
+    """Seeded train-time augmentation of (17,2)/(17,3) pose pairs (csrc/pose_augment.h has the definition).
+
+    2-D: flip (flip_pose's joint swap, x -> flip_offset - x) with probability p_flip, rotate about `centre` by an angle
+    uniform in [-max_rot, max_rot) radians, scale about `centre` by a factor uniform in [1 - scale_range, 1 + scale_range),
+    shift by (tx, ty) uniform in [-max_shift, max_shift), add N(0, jitter_sigma^2) noise to every coordinate.
+    3-D: the same flip (x -> -x) and the same rotation of (x, y); z, scale and shift leave the root-relative target alone.
+    flip_offset is 1 for image-normalised x in [0, 1] and 0 for zero-mean standardised inputs.  A parameter of 0 switches
+    its stage off exactly; the default object changes no bit."""
+    p_flip: float = 0.0
+    flip_offset: float = 1.0
+    max_rot: float = 0.0
+    scale_range: float = 0.0
+    max_shift: float = 0.0
+    jitter_sigma: float = 0.0
+    centre: tuple = (0.5, 0.5)
+    seed: int = 0
+
+    def __post_init__(self):
+        centre = tuple(float(c) for c in self.centre)
+        if len(centre) != 2:
+            raise ValueError("centre is (cx, cy)")
+        object.__setattr__(self, "centre", centre)
+        for name in ("p_flip", "flip_offset", "max_rot", "scale_range", "max_shift", "jitter_sigma"):
+            object.__setattr__(self, name, float(getattr(self, name)))
+        for name, v in (("flip_offset", self.flip_offset), ("cx", centre[0]), ("cy", centre[1])):
+            if not math.isfinite(v):
+                raise ValueError(f"{name} must be finite")
+        for name in ("p_flip", "max_rot", "scale_range", "max_shift", "jitter_sigma"):
+            v = getattr(self, name)
+            if not math.isfinite(v) or v < 0.0:
+                raise ValueError(f"{name} must be finite and >= 0, got {v}")
+        if self.scale_range >= 1.0:
+            raise ValueError("scale_range must be below 1")
+        seed = int(self.seed)
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError("seed is a uint64")
+        object.__setattr__(self, "seed", seed)
+
+    def struct(self):
+        """The PLPoseAug the library reads."""
+        return _lib.PLPoseAug(self.p_flip, self.flip_offset, self.max_rot, self.scale_range, self.max_shift,
+                              self.jitter_sigma, self.centre[0], self.centre[1], self.seed)
+
+
+def _augment_launch(a, b, src_idx, row_ids, nb, table_rows, oa, ob, aug_struct, epoch):
+    """One pl_pose_augment_gather on torch's current stream; src_idx None = the rows of a, b in order."""
+    _lib.check(_lib.lib().pl_pose_augment_gather(a.data_ptr(), b.data_ptr(), src_idx.data_ptr() if src_idx is not None else None,
+                                                 row_ids.data_ptr(), nb, table_rows, oa.data_ptr(), ob.data_ptr(),
+                                                 ctypes.byref(aug_struct), int(epoch), _lib.current_stream_ptr()),
+               "pl_pose_augment_gather")
+
+
+def augment_poses(y1, y2, augment, row_ids=None, epoch=0):
+    """`augment` applied to a batch that came from somewhere else: y1 (B,17,2), y2 (B,17,3) fp32 device tensors -> new
+    (y1, y2) tensors; the inputs are untouched and nothing synchronises (one launch on the current stream).
+
+    A pose's draws are a function of (augment.seed, epoch, row id) only.  Pass the poses' DATASET indices as `row_ids`
+    (int64, B of them) -- or at least an `epoch` that changes from call to call -- to get fresh draws: with the default
+    row_ids = arange(B) and a fixed epoch, pose k of every batch is flipped, turned and jittered the same way."""
+    if not isinstance(augment, PoseAugment):
+        raise TypeError("augment must be a PoseAugment")
+    _lib.require_device_tensor(y1, "y1")
+    _lib.require_device_tensor(y2, "y2")
+    if y1.dim() != 3 or y2.dim() != 3 or tuple(y1.shape[1:]) != (17, 2) or tuple(y2.shape[1:]) != (17, 3) \
+            or y1.shape[0] != y2.shape[0] or y1.shape[0] == 0 or y1.device != y2.device:
+        raise ValueError("augment_poses expects y1 (B,17,2) and y2 (B,17,3) on one device, B >= 1")
+    nb = y1.shape[0]
+    if row_ids is None:
+        row_ids = torch.arange(nb, dtype=torch.int64, device=y1.device)
+    else:
+        row_ids = torch.as_tensor(row_ids).to(device=y1.device, dtype=torch.int64).contiguous()
+        if row_ids.shape != (nb,):
+            raise ValueError("row_ids holds one dataset index per pose")
+    oa, ob = torch.empty_like(y1), torch.empty_like(y2)
+    with _lib.on_device(y1.device):
+        _augment_launch(y1, y2, None, row_ids, nb, nb, oa, ob, augment.struct(), epoch)
+    return oa, ob
+
+
 class PoseFeeder:
     """Iterable of (y1 [b,17,2], y2 [b,17,3]) fp32 device batches over one epoch; call
-    set_epoch(e) between epochs (as with DistributedSampler) for a fresh permutation."""
+    set_epoch(e) between epochs (as with DistributedSampler) for a fresh permutation.
+    augment: a PoseAugment applied inside the launch that builds the batch, with the epoch of set_epoch and the poses'
+    dataset rows as the identity of the draws (None: the plain gather)."""
 
     def __init__(self, x2d, y3d, batch_size, *, device="cuda", shuffle=True, seed=0, drop_last=False,
-                 rank=0, world=1, resident=True, prefetch=2):
+                 rank=0, world=1, resident=True, prefetch=2, augment=None):
         x2d, y3d = torch.as_tensor(x2d), torch.as_tensor(y3d)
         if x2d.shape[0] != y3d.shape[0] or x2d.shape[0] == 0:
             raise ValueError("x2d and y3d need the same, non-zero number of poses")
         self.n = x2d.shape[0]
         self.shape_a, self.shape_b = tuple(x2d.shape[1:]), tuple(y3d.shape[1:])
+        if augment is not None:
+            if not isinstance(augment, PoseAugment):
+                raise TypeError("augment must be a PoseAugment or None")
+            if self.shape_a != (17, 2) or self.shape_b != (17, 3):
+                raise ValueError(f"augmentation is defined for (N,17,2)/(N,17,3) tables, got {tuple(x2d.shape)} / "
+                                 f"{tuple(y3d.shape)}")
+        self.augment = augment
+        self._aug = augment.struct() if augment is not None else None
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _lib.PoseliftError("PoseFeeder feeds an MI355X (ROCm) device; there is no CPU path")
@@ -99,7 +199,7 @@ class PoseFeeder:
         return self._iter_resident() if self.resident else self._iter_streamed()
 
     def _iter_resident(self):
-        batches = self._indices()
+        batches, epoch = self._indices(), self.epoch
         if not batches:
             return
         # one H2D of the whole epoch's permutation (8 B per pose), then only device work
@@ -110,18 +210,25 @@ class PoseFeeder:
             oa = torch.empty((nb,) + self.shape_a, dtype=torch.float32, device=self.device)
             ob = torch.empty((nb,) + self.shape_b, dtype=torch.float32, device=self.device)
             with _lib.on_device(self.device):
-                _lib.check(L.pl_gather_rows2(self.a.data_ptr(), self.wa, self.b.data_ptr(), self.wb,
-                                             idx_all[at:at + nb].data_ptr(), nb, self.n, oa.data_ptr(), ob.data_ptr(),
-                                             _lib.current_stream_ptr()), "pl_gather_rows2")
+                if self._aug is not None:           # the permutation slice is both the source row and the draws' identity
+                    idx = idx_all[at:at + nb]
+                    _augment_launch(self.a, self.b, idx, idx, nb, self.n, oa, ob, self._aug, epoch)
+                else:
+                    _lib.check(L.pl_gather_rows2(self.a.data_ptr(), self.wa, self.b.data_ptr(), self.wb,
+                                                 idx_all[at:at + nb].data_ptr(), nb, self.n, oa.data_ptr(), ob.data_ptr(),
+                                                 _lib.current_stream_ptr()), "pl_gather_rows2")
             at += nb
             yield oa, ob
 
     def _iter_streamed(self):
-        batches = self._indices()
+        batches, epoch = self._indices(), self.epoch
         slots, inflight = self.prefetch + 1, []
         stage = [(torch.empty(self.batch_size, self.wa).pin_memory(), torch.empty(self.batch_size, self.wb).pin_memory())
                  for _ in range(slots)]
         free_events = [None] * slots                      # consumer done with the slot's previous batch
+        # augmentation: the batch's dataset rows ride the same copy (8 B per pose); they are the identity of its draws
+        stage_idx = [torch.empty(self.batch_size, dtype=torch.int64).pin_memory() for _ in range(slots)] \
+            if self._aug is not None else None
 
         def launch(k, idx):
             slot = k % slots
@@ -134,20 +241,32 @@ class PoseFeeder:
             with torch.cuda.stream(self._copy_stream):
                 da = ha.to(self.device, non_blocking=True).view((nb,) + self.shape_a)
                 db = hb.to(self.device, non_blocking=True).view((nb,) + self.shape_b)
+                di = None
+                if stage_idx is not None:
+                    hi = stage_idx[slot][:nb]
+                    hi.copy_(idx)
+                    di = hi.to(self.device, non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record(self._copy_stream)
             free_events[slot] = ev
-            return da, db, ev
+            return da, db, di, ev
 
         nxt = 0
         while nxt < len(batches) and len(inflight) < self.prefetch:
             inflight.append(launch(nxt, batches[nxt]))
             nxt += 1
         while inflight:
-            da, db, ev = inflight.pop(0)
+            da, db, di, ev = inflight.pop(0)
             torch.cuda.current_stream(self.device).wait_event(ev)
             da.record_stream(torch.cuda.current_stream(self.device))
             db.record_stream(torch.cuda.current_stream(self.device))
+            if di is not None:                            # one launch on the consumer's stream, behind the event wait
+                di.record_stream(torch.cuda.current_stream(self.device))
+                nb = di.numel()
+                oa, ob = torch.empty_like(da), torch.empty_like(db)
+                with _lib.on_device(self.device):
+                    _augment_launch(da, db, None, di, nb, nb, oa, ob, self._aug, epoch)
+                da, db = oa, ob
             if nxt < len(batches):
                 inflight.append(launch(nxt, batches[nxt]))
                 nxt += 1

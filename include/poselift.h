@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define PL_VERSION 113 /* 0.1.13: + PLClipRecord, pl_grad_norm_scratch_bytes, pl_grad_norm_clip, pl_adamw_flat_clip, pl_adamw_flat_dev_clip, pl_adamw_flat_planes_clip (gradient-norm clipping and non-finite skip on the device); 0.1.12: + pl_pose_errors, pl_pose_errors_host, pl_pose_metrics_scratch_bytes, pl_pose_metrics_accum (evaluation: MPJPE / N-MPJPE / P-MPJPE, PCK counts, per group); 0.1.11: + pl_vit_*_bf16, pl_vit_bf16_pack (MyViT "bf16p": bf16 operand carriers written by their producers); 0.1.10: + pl_vit_* (the MyViT transformer lifter); 0.1.9: + pl_conv2d_planes_fwd_hw, pl_conv2d_planes_wgrad_hw (the stem on the planes GEMM); 0.1.8: + pl_lifter_train_step, pl_lifter_step_carries_adamw; 0.1.7: + pl_workspace_bitmap_format (small-batch layer kernels); 0.1.6: + pl_counter_add; 0.1.5: + pl_flip_pose_ex, pl_flip_w_nhwc (phase5 Flip branch); 0.1.4: + pl_planes_split_strided; 0.1.3: + pl_bn_join_bwd (0.1.2: operand-plane outputs of the BatchNorm / join kernels, pl_gemm_planes_raw) */
+#define PL_VERSION 114 /* 0.1.14: + PLPoseAug, pl_pose_augment_gather, pl_pose_augment_host (seeded train-time pose augmentation inside the batch gather); 0.1.13: + PLClipRecord, pl_grad_norm_scratch_bytes, pl_grad_norm_clip, pl_adamw_flat_clip, pl_adamw_flat_dev_clip, pl_adamw_flat_planes_clip (gradient-norm clipping and non-finite skip on the device); 0.1.12: + pl_pose_errors, pl_pose_errors_host, pl_pose_metrics_scratch_bytes, pl_pose_metrics_accum (evaluation: MPJPE / N-MPJPE / P-MPJPE, PCK counts, per group); 0.1.11: + pl_vit_*_bf16, pl_vit_bf16_pack (MyViT "bf16p": bf16 operand carriers written by their producers); 0.1.10: + pl_vit_* (the MyViT transformer lifter); 0.1.9: + pl_conv2d_planes_fwd_hw, pl_conv2d_planes_wgrad_hw (the stem on the planes GEMM); 0.1.8: + pl_lifter_train_step, pl_lifter_step_carries_adamw; 0.1.7: + pl_workspace_bitmap_format (small-batch layer kernels); 0.1.6: + pl_counter_add; 0.1.5: + pl_flip_pose_ex, pl_flip_w_nhwc (phase5 Flip branch); 0.1.4: + pl_planes_split_strided; 0.1.3: + pl_bn_join_bwd (0.1.2: operand-plane outputs of the BatchNorm / join kernels, pl_gemm_planes_raw) */
 
 typedef enum PLStatus {
   PL_OK = 0,
@@ -364,6 +364,35 @@ int pl_nhwc_to_nchw(const float* in, int64_t B, int64_t P, int64_t C, float* out
  * [0, table_rows) (the caller's permutation; not checked on the device). */
 int pl_gather_rows2(const float* a, int64_t wa, const float* b, int64_t wb, const int64_t* idx,
                     int64_t n, int64_t table_rows, float* oa, float* ob, void* stream);
+
+/* The same batch with seeded train-time augmentation applied where the rows are read (csrc/pose_augment.h has the
+ * definition; the reference leaves it commented out, per sample, at phase3_direct/my_HybrIK/H36_dataset.py:98-117 and
+ * phase1_lifting/train_1.py:83-84).  Poses are 17 joints: a [rows][34] = (17,2), b [rows][51] = (17,3).
+ *   2-D: flip (flip_pose's joint swap, x -> flip_offset - x), rotate about (cx, cy), scale about (cx, cy), translate, add
+ *        Gaussian noise;   3-D: flip (x -> -x), rotate (x, y) by the same angle; z untouched.
+ * Image x right / y down, the 3-D target camera-frame and root-relative; scale and translation leave it alone (weak
+ * perspective).  A parameter of 0 switches its stage off exactly: the all-zero PLPoseAug writes pl_gather_rows2's bits.
+ * Every draw of a pose is a Philox4x32-10 function of (seed, epoch, row_id) -- never of the batch size, the position in
+ * the batch or the rank -- on a key tagged apart from the dropout stream. */
+typedef struct PLPoseAug {
+  float p_flip;       /* probability of the horizontal flip: <= 0 never, >= 1 always */
+  float flip_offset;  /* 2-D flip is x -> flip_offset - x: 1 for image-normalised x (utils.py:391), 0 for zero-mean inputs */
+  float max_rot;      /* rotation angle uniform in [-max_rot, max_rot) radians */
+  float scale_range;  /* 2-D scale uniform in [1 - scale_range, 1 + scale_range); < 1 */
+  float max_shift;    /* 2-D translation (tx, ty), each uniform in [-max_shift, max_shift) */
+  float jitter_sigma; /* std of the Gaussian noise on every 2-D coordinate (train_1.py:84 used 0.05) */
+  float cx, cy;       /* centre of rotation and scale in 2-D */
+  uint64_t seed;
+} PLPoseAug;
+/* oa[k], ob[k] = augment(a[s], b[s]; draws of row_id[k]), s = src_idx[k], or k when src_idx is NULL (an already gathered
+ * batch: n <= table_rows), k < n.  src_idx, row_id: int64; an s outside [0, table_rows) reads nothing and gives a NaN
+ * pose on the device, PL_EINVAL on the host.  The outputs may overlap neither each other nor a source.  Negative or
+ * non-finite parameters and scale_range >= 1 are PL_EINVAL.  One launch on `stream`; no allocation, no synchronisation.
+ * pl_pose_augment_host: the same inline text compiled for the CPU, on host pointers (a test hook). */
+int pl_pose_augment_gather(const float* a, const float* b, const int64_t* src_idx, const int64_t* row_id, int64_t n,
+                           int64_t table_rows, float* oa, float* ob, const PLPoseAug* aug, uint64_t epoch, void* stream);
+int pl_pose_augment_host(const float* a, const float* b, const int64_t* src_idx, const int64_t* row_id, int64_t n,
+                         int64_t table_rows, float* oa, float* ob, const PLPoseAug* aug, uint64_t epoch);
 
 /* ---- loss / metric / optimiser -------------------------------------------------- */
 /* torch.nn.MSELoss(reduction="mean") + its backward  train_1.py:37,94-95.
