@@ -52,6 +52,12 @@ __global__ void pad_rows_kernel(const float* __restrict__ w, int rows, int K, in
   out[t] = k < K ? w[(size_t)r * K + k] : 0.f;
 }
 
+// torch's max-pool rule, taps in (kh, kw) order from m = -inf: a tap replaces the running maximum where it is larger OR a
+// NaN -- so a window that holds a NaN gives NaN, and its LAST NaN tap is the one the gradient goes to; otherwise the first
+// maximum.  The index forward and the recomputing backward follow it; the plain forward needs the value alone and takes
+// max_nan, the same value (a NaN wins; of -0.0 and +0.0 it returns +0.0, as its fmaxf did).
+__device__ __forceinline__ bool pool_take(float v, float m) { return v > m || v != v; }
+
 __global__ __launch_bounds__(NTHR) void maxpool3x3s2_nhwc_kernel(const float* __restrict__ x, int H, int W, int C,
                                                                  int Ho, int Wo, int64_t n4,
                                                                  float* __restrict__ y) {
@@ -71,7 +77,7 @@ __global__ __launch_bounds__(NTHR) void maxpool3x3s2_nhwc_kernel(const float* __
       const int ih = oh * 2 - 1 + kh, iw = ow * 2 - 1 + kw;
       if ((unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W) {
         const float4 v = *reinterpret_cast<const float4*>(x + ((b * H + ih) * W + iw) * C + c);
-        m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
+        m.x = max_nan(m.x, v.x); m.y = max_nan(m.y, v.y); m.z = max_nan(m.z, v.z); m.w = max_nan(m.w, v.w);
       }
     }
   *reinterpret_cast<float4*>(y + t * 4) = m;
@@ -79,7 +85,7 @@ __global__ __launch_bounds__(NTHR) void maxpool3x3s2_nhwc_kernel(const float* __
 
 // backward of the 3x3 / stride 2 / pad 1 max-pool: one thread per INPUT float4; an input pixel lies in at most
 // 2 x 2 windows, and it receives a window's gradient where it is that window's FIRST maximum in (kh, kw) order
-// (torch's tie rule) -- recomputed from x and y, no index tensor, no atomics.
+// (torch's tie rule; in a window that holds NaNs, the last NaN tap: pool_take) -- recomputed from x, no index tensor, no atomics.
 __global__ __launch_bounds__(NTHR) void maxpool3x3s2_nhwc_bwd_kernel(const float* __restrict__ x,
                                                                      const float* __restrict__ dy, int H, int W, int C,
                                                                      int Ho, int Wo, int64_t n4,
@@ -101,8 +107,8 @@ __global__ __launch_bounds__(NTHR) void maxpool3x3s2_nhwc_bwd_kernel(const float
       if (kh0 < 0 || kh0 > 2 || kw0 < 0 || kw0 > 2) continue;
       const float4 gv = *reinterpret_cast<const float4*>(dy + ((b * Ho + oh) * Wo + ow) * C + c);
       const float gs[4] = {gv.x, gv.y, gv.z, gv.w};
-      bool first[4] = {true, true, true, true};                               // no earlier tap holds a value >= ours
-      bool ismax[4] = {true, true, true, true};                               // no later tap holds a value > ours
+      bool first[4] = {true, true, true, true};       // no earlier tap holds a value >= ours (or a NaN, unless ours is one)
+      bool ismax[4] = {true, true, true, true};       // no later tap holds a value > ours, or a NaN
 #pragma unroll
       for (int kh = 0; kh < 3; ++kh)
 #pragma unroll
@@ -114,8 +120,8 @@ __global__ __launch_bounds__(NTHR) void maxpool3x3s2_nhwc_bwd_kernel(const float
           const bool earlier = kh * 3 + kw < kh0 * 3 + kw0;
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
-            if (earlier) first[j] = first[j] && !(os[j] >= xs[j]);
-            else ismax[j] = ismax[j] && !(os[j] > xs[j]);
+            if (earlier) first[j] = first[j] && !(os[j] >= xs[j] || (os[j] != os[j] && xs[j] == xs[j]));
+            else ismax[j] = ismax[j] && !pool_take(os[j], xs[j]);
           }
         }
 #pragma unroll
@@ -153,7 +159,7 @@ __global__ __launch_bounds__(NTHR) void maxpool3x3s2_nhwc_idx_kernel(const float
         const float vs[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-          if (!any || vs[j] > m[j]) { m[j] = vs[j]; k[j] = (unsigned char)(kh * 3 + kw); }
+          if (!any || pool_take(vs[j], m[j])) { m[j] = vs[j]; k[j] = (unsigned char)(kh * 3 + kw); }
         any = true;
       }
     }
@@ -428,7 +434,7 @@ __global__ __launch_bounds__(NTHR) void stem7x7_c3_kernel(const float* __restric
     for (int j = 0; j < 4; ++j) {
       float t = acc[4 * q + j];
       if (scale) t = fmaf(t, scale[4 * q + j], shift[4 * q + j]);
-      if (relu) t = fmaxf(t, 0.f);
+      if (relu) t = relu_f(t);
       o[j] = t;
     }
     out[q] = make_float4(o[0], o[1], o[2], o[3]);
@@ -569,7 +575,7 @@ __global__ __launch_bounds__(NTHR) void reduce_slabs_epi_kernel(const float* __r
   for (int j = 0; j < 4; ++j) {
     if (bias) o[j] += bias[c + j];
     if (scale) o[j] = fmaf(o[j], scale[c + j], shift[c + j]);
-    if (relu == 1) o[j] = fmaxf(o[j], 0.f);
+    if (relu == 1) o[j] = relu_f(o[j]);
   }
   if (resid) {
     const float4 q = reinterpret_cast<const float4*>(resid)[t];
@@ -577,7 +583,7 @@ __global__ __launch_bounds__(NTHR) void reduce_slabs_epi_kernel(const float* __r
   }
   if (relu == 2) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = fmaxf(o[j], 0.f);
+    for (int j = 0; j < 4; ++j) o[j] = relu_f(o[j]);
   }
   reinterpret_cast<float4*>(y)[t] = make_float4(o[0], o[1], o[2], o[3]);
 }

@@ -274,7 +274,7 @@ __global__ __launch_bounds__(NTHR) void bn_colstats_kernel(const float* __restri
   }
 }
 
-// out = relu(a + b), bitmap of (out > 0): the residual join of a Bottleneck (Resnet.py:90-91) in training mode
+// out = relu(a + b), bitmap of relu_on(out) (positive or NaN): the residual join of a Bottleneck (Resnet.py:90-91) in training mode
 __global__ __launch_bounds__(NTHR) void add_relu_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                         float* __restrict__ out, uint64_t* __restrict__ bits, int B,
                                                         int H, PlaneOut po) {
@@ -293,7 +293,7 @@ __global__ __launch_bounds__(NTHR) void add_relu_kernel(const float* __restrict_
     uint64_t word = 0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const bool on = active && o[j] > 0.f;
+      const bool on = active && relu_on(o[j]);
       o[j] = on ? o[j] : 0.f;
       const uint64_t m = __ballot(on);
       if (lane == j) word = m;
@@ -378,7 +378,7 @@ __device__ __forceinline__ void bn_apply_row(
   float o[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    on[j] = active && keep[j] && (norelu || y[j] > 0.f);
+    on[j] = active && keep[j] && (norelu || relu_on(y[j]));
     o[j] = on[j] ? y[j] * kscale : 0.f;
   }
   uint64_t word = 0;

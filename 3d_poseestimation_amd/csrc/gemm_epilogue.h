@@ -41,9 +41,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, float* __restri
           v += bias;
           if (p.addend && cok && (!EDGE || row < p.M)) v += p.addend[(size_t)row * p.ldc + col];
           if (p.col_scale) v = fmaf(v, scale, shift);
-          if (p.relu == 1) v = fmaxf(v, 0.f);
+          if (p.relu == 1) v = relu_f(v);
           if (p.resid && cok && (!EDGE || row < p.M)) v += p.resid[(size_t)row * p.ldc + col];
-          if (p.relu == 2) v = fmaxf(v, 0.f);
+          if (p.relu == 2) v = relu_f(v);
         }
         acc[a][b][r] = v;
         if (!EDGE || row < p.M) ssum += v;

@@ -211,7 +211,7 @@ __device__ __forceinline__ void gemm_epilogue_vec(const GemmArgs& p, float* __re
       for (int r = 0; r < 16; ++r) {
         float v = acc[a][b][r] + bias;
         if (p.col_scale) v = fmaf(v, scale, shift);
-        if (p.relu == 1) v = fmaxf(v, 0.f);
+        if (p.relu == 1) v = relu_f(v);
         ldsw[(a * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * 64 + b * 32 + i] = v;
       }
   }
@@ -226,7 +226,7 @@ __device__ __forceinline__ void gemm_epilogue_vec(const GemmArgs& p, float* __re
       const float4 q = *reinterpret_cast<const float4*>(p.resid + o);
       v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w;
     }
-    if (p.relu == 2) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+    if (p.relu == 2) { v.x = relu_f(v.x); v.y = relu_f(v.y); v.z = relu_f(v.z); v.w = relu_f(v.w); }
     *reinterpret_cast<float4*>(C + o) = v;
   }
 }

@@ -82,7 +82,7 @@ __device__ __forceinline__ void staged_epilogue(const PlanesKern& k, float* __re
     if (e.relu == 1) {
 #pragma unroll
       for (int it = 0; it < 16; ++it) {
-        v[it].x = fmaxf(v[it].x, 0.f); v[it].y = fmaxf(v[it].y, 0.f); v[it].z = fmaxf(v[it].z, 0.f); v[it].w = fmaxf(v[it].w, 0.f);
+        v[it].x = relu_f(v[it].x); v[it].y = relu_f(v[it].y); v[it].z = relu_f(v[it].z); v[it].w = relu_f(v[it].w);
       }
     }
     if (e.resid) {
@@ -95,7 +95,7 @@ __device__ __forceinline__ void staged_epilogue(const PlanesKern& k, float* __re
     if (e.relu == 2) {
 #pragma unroll
       for (int it = 0; it < 16; ++it) {
-        v[it].x = fmaxf(v[it].x, 0.f); v[it].y = fmaxf(v[it].y, 0.f); v[it].z = fmaxf(v[it].z, 0.f); v[it].w = fmaxf(v[it].w, 0.f);
+        v[it].x = relu_f(v[it].x); v[it].y = relu_f(v[it].y); v[it].z = relu_f(v[it].z); v[it].w = relu_f(v[it].w);
       }
     }
   }
@@ -166,8 +166,8 @@ __device__ __forceinline__ void staged_epilogue(const PlanesKern& k, float* __re
     }
     m2 = xadd_rows(m2);
     sd = xadd_rows(sd);
-    m2.x = fmaxf(fmaf(-sd.x * inv, sd.x, m2.x), 0.f); m2.y = fmaxf(fmaf(-sd.y * inv, sd.y, m2.y), 0.f);
-    m2.z = fmaxf(fmaf(-sd.z * inv, sd.z, m2.z), 0.f); m2.w = fmaxf(fmaf(-sd.w * inv, sd.w, m2.w), 0.f);
+    m2.x = relu_f(fmaf(-sd.x * inv, sd.x, m2.x)); m2.y = relu_f(fmaf(-sd.y * inv, sd.y, m2.y));
+    m2.z = relu_f(fmaf(-sd.z * inv, sd.z, m2.z)); m2.w = relu_f(fmaf(-sd.w * inv, sd.w, m2.w));
     // (the consumers walk 2 ceil(M / 128) groups, empty ones included -- gemm_stat_groups; a wave block of a 256-row tile
     //  below that has no group)
     if (lr == 0 && cok && (!EDGE || (m0 >> 6) + wm < 2 * ((e.M + 127) >> 7))) {

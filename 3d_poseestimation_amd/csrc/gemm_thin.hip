@@ -125,9 +125,9 @@ __global__ __launch_bounds__(NTHR) void thin_reduce_kernel(GemmArgs p, const flo
       const float4 sc = ld4(p.col_scale + c), sh = ld4(p.col_shift + c);
       a.x = fmaf(a.x, sc.x, sh.x); a.y = fmaf(a.y, sc.y, sh.y); a.z = fmaf(a.z, sc.z, sh.z); a.w = fmaf(a.w, sc.w, sh.w);
     }
-    if (p.relu == 1) { a.x = fmaxf(a.x, 0.f); a.y = fmaxf(a.y, 0.f); a.z = fmaxf(a.z, 0.f); a.w = fmaxf(a.w, 0.f); }
+    if (p.relu == 1) { a.x = relu_f(a.x); a.y = relu_f(a.y); a.z = relu_f(a.z); a.w = relu_f(a.w); }
     if (p.resid) { const float4 t = ld4(p.resid + o); a.x += t.x; a.y += t.y; a.z += t.z; a.w += t.w; }
-    if (p.relu == 2) { a.x = fmaxf(a.x, 0.f); a.y = fmaxf(a.y, 0.f); a.z = fmaxf(a.z, 0.f); a.w = fmaxf(a.w, 0.f); }
+    if (p.relu == 2) { a.x = relu_f(a.x); a.y = relu_f(a.y); a.z = relu_f(a.z); a.w = relu_f(a.w); }
     st4(p.C + o, a);
   }
   if (!p.stat_sum) return;                     // (kernel-uniform)

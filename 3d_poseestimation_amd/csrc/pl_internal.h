@@ -14,6 +14,15 @@
 namespace pl {
 
 constexpr int kWave = 64;
+// ReLU as torch computes it, the one form every kernel uses: a NaN stays a NaN (fmaxf returns the other operand, and
+// `v > 0 ? v : 0` takes a NaN for "off").  relu_f is IEEE 754-2019 maximum(v, +0) -- one v_maximum3_f32 on gfx950, where
+// fmaxf is a canonicalising v_max plus the v_max -- and gives finite v the bits fmaxf(v, 0.f) gave, -0.0f -> +0.0f included.
+// relu_on is the matching bitmap / gradient decision: the gradient passes where the input is positive OR NaN (torch's
+// threshold_backward).
+__device__ __forceinline__ bool relu_on(float v) { return !(v <= 0.f); }
+__device__ __forceinline__ float relu_f(float v) { return __builtin_elementwise_maximum(v, 0.f); }
+// the same maximum between two values: a NaN on either side wins (max-pool's window maximum)
+__device__ __forceinline__ float max_nan(float a, float b) { return __builtin_elementwise_maximum(a, b); }
 // template arguments chosen at run time travel to the one launch site of a kernel template as values of these types
 template <bool V> using Bool = std::integral_constant<bool, V>;
 template <int V> using Int = std::integral_constant<int, V>;

@@ -355,10 +355,10 @@ __device__ __forceinline__ float4 eval_tail(const FwdArgs& p, float4 z, const Fw
   const float sx = q.ga.x * (1.0f / sqrtf(q.rvar.x + p.eps)), sy = q.ga.y * (1.0f / sqrtf(q.rvar.y + p.eps));
   const float sz = q.ga.z * (1.0f / sqrtf(q.rvar.z + p.eps)), sw = q.ga.w * (1.0f / sqrtf(q.rvar.w + p.eps));
   float4 y;
-  y.x = fmaxf(fmaf(z.x, sx, fmaf(q.bias.x - q.rmean.x, sx, q.be.x)), 0.f) + q.rv.x;
-  y.y = fmaxf(fmaf(z.y, sy, fmaf(q.bias.y - q.rmean.y, sy, q.be.y)), 0.f) + q.rv.y;
-  y.z = fmaxf(fmaf(z.z, sz, fmaf(q.bias.z - q.rmean.z, sz, q.be.z)), 0.f) + q.rv.z;
-  y.w = fmaxf(fmaf(z.w, sw, fmaf(q.bias.w - q.rmean.w, sw, q.be.w)), 0.f) + q.rv.w;
+  y.x = relu_f(fmaf(z.x, sx, fmaf(q.bias.x - q.rmean.x, sx, q.be.x))) + q.rv.x;
+  y.y = relu_f(fmaf(z.y, sy, fmaf(q.bias.y - q.rmean.y, sy, q.be.y))) + q.rv.y;
+  y.z = relu_f(fmaf(z.z, sz, fmaf(q.bias.z - q.rmean.z, sz, q.be.z))) + q.rv.z;
+  y.w = relu_f(fmaf(z.w, sw, fmaf(q.bias.w - q.rmean.w, sw, q.be.w))) + q.rv.w;
   st4(p.act + (size_t)r * p.H + c, y);
   if (p.outp) store_planes4(PlaneDst{p.outp, p.outp + p.o_plane, kActPlaneScale, 2, 0, p.range, p.site}, (size_t)r * p.H + c, y);
   return y;
@@ -436,7 +436,7 @@ __device__ __forceinline__ float4 fwd_tail(const FwdArgs& p, float4 z, const Fwd
   uint64_t word = 0;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const bool on = live && keep[j] && (norelu || y[j] > 0.f);
+    const bool on = live && keep[j] && (norelu || relu_on(y[j]));
     o[j] = on ? y[j] * p.kscale : 0.f;
     const uint64_t bal = __ballot(on);
     if (lane == j) word = bal;

@@ -571,7 +571,7 @@ __global__ void __launch_bounds__(NT) vit_head_fwd(const float* __restrict__ z, 
   if (t >= T) return;
   float acc[kHeadMaxOut] = {0.f, 0.f, 0.f, 0.f};
   for (int k = lane; k < K; k += kWave) {
-    const float r = fmaxf(z[(size_t)t * K + k], 0.f);
+    const float r = relu_f(z[(size_t)t * K + k]);
     for (int o = 0; o < out_d; ++o) acc[o] = fmaf(r, W[o * K + k], acc[o]);
   }
   for (int o = 0; o < out_d; ++o) {
@@ -580,7 +580,7 @@ __global__ void __launch_bounds__(NT) vit_head_fwd(const float* __restrict__ z, 
   }
 }
 
-// dz[t][k] = [z > 0] sum_o dy[t][o] W[o][k]; partial[chunk] = dW [out_d][K], then db [out_d]
+// dz[t][k] = [z > 0 or NaN] sum_o dy[t][o] W[o][k]; partial[chunk] = dW [out_d][K], then db [out_d]
 __global__ void __launch_bounds__(NT) vit_head_bwd(const float* __restrict__ dy, const float* __restrict__ z, int T, int K,
                                                    const float* __restrict__ W, int out_d, float* __restrict__ dz,
                                                    float* __restrict__ part) {
@@ -605,7 +605,7 @@ __global__ void __launch_bounds__(NT) vit_head_bwd(const float* __restrict__ dy,
     for (int m = 0; m < kHeadMaxK / kWave; ++m) {
       const int k = lane + m * kWave;
       if (k < K) {
-        const float zz = z[(size_t)t * K + k], r = fmaxf(zz, 0.f);
+        const float zz = z[(size_t)t * K + k], r = relu_f(zz);
         float s = 0.f;
 #pragma unroll
         for (int o = 0; o < kHeadMaxOut; ++o)
@@ -613,7 +613,7 @@ __global__ void __launch_bounds__(NT) vit_head_bwd(const float* __restrict__ dy,
             s = fmaf(g[o], W[o * K + k], s);
             dw[o][m] = fmaf(g[o], r, dw[o][m]);
           }
-        dz[(size_t)t * K + k] = zz > 0.f ? s : 0.f;
+        dz[(size_t)t * K + k] = relu_on(zz) ? s : 0.f;
       }
     }
   }

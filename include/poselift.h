@@ -757,7 +757,7 @@ int pl_softargmax_hm_dl_scale(const float* gcoords, const float* gsq, int64_t ro
  *   pl_vit_attn_bwd  : dqkv from qkv, lse and dO (P recomputed)
  *   pl_vit_gelu_*    : exact GELU 0.5 u (1 + erf(u / sqrt 2)); du = dy GELU'(u)
  *   pl_vit_head_fwd  : y = relu(z) W^T + b  (z [T][K], W [out_d][K]); K <= 256, out_d <= 4
- *   pl_vit_head_bwd  : dz = [z > 0] dy W; dWb [out_d*K + out_d] = dW, then db
+ *   pl_vit_head_bwd  : dz = [!(z <= 0)] dy W (a NaN z passes, as torch); dWb [out_d*K + out_d] = dW, then db
  *   pl_vit_planes_dyn: PL_F16X3 operand planes of x [rows][cols] (cols % 4 == 0) in a [rows_pad][cols] carrier (rows
  *                      past `rows` zero: a padded contraction for the TN weight gradients) with S the power of two
  *                      that maps max |x| into [2^13, 2^14), chosen on the device; scale (device, 3 floats) = {S, 1/S,

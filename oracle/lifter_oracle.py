@@ -124,7 +124,9 @@ def _hidden_fwd(st, lin, bnp, a_in, train, use_bn, keep, p, dtype, update_runnin
         c.update(mean=mean, var=var, rstd=rstd, zhat=zhat, bn_train=train)
     else:
         y = z
-    rmask = y > 0
+    # torch.relu / threshold_backward: "on" is not (y <= 0), so a NaN stays a NaN going forward and passes the gradient
+    # going back (y > 0 would zero both; identical on finite y)
+    rmask = ~(y <= 0)
     if on is not None:
         scale = dtype(1)
         if train and 0 < p < 1:
@@ -142,7 +144,9 @@ def _hidden_fwd(st, lin, bnp, a_in, train, use_bn, keep, p, dtype, update_runnin
             keep = np.zeros_like(rmask)
         else:
             scale = dtype(np.float32(1.0) / (np.float32(1.0) - np.float32(p)))
-        y = np.where(keep, y * scale, dtype(0))
+        # torch multiplies by the mask: a dropped NaN or +inf is NaN * 0 = NaN, every finite (here: non-negative) value +0.
+        # (The library selects and makes it 0: pinned in tests/test_gpu_nonfinite.py, DESIGN.md "Non-finite values".)
+        y = np.where(keep, y * scale, np.where(np.isfinite(y), dtype(0), dtype(np.nan)))
         c.update(keep=keep, scale=scale)
     else:
         c.update(keep=None, scale=dtype(1))
