@@ -86,6 +86,17 @@ class PLPoseAug(ctypes.Structure):
                 ("cx", ctypes.c_float), ("cy", ctypes.c_float), ("seed", ctypes.c_uint64)]
 
 
+FRAME_U8, FRAME_F32 = 0, 1
+
+
+class PLFrameWarp(ctypes.Structure):
+    _fields_ = [("src", ctypes.c_void_p), ("src_dtype", ctypes.c_int32), ("C", ctypes.c_int32), ("N", ctypes.c_int64),
+                ("Hs", ctypes.c_int64), ("Ws", ctypes.c_int64), ("src_idx", ctypes.c_void_p), ("row_id", ctypes.c_void_p),
+                ("n", ctypes.c_int64), ("out", ctypes.c_void_p), ("Ho", ctypes.c_int64), ("Wo", ctypes.c_int64),
+                ("scale", ctypes.c_float), ("fill", ctypes.c_float), ("aug", ctypes.POINTER(PLPoseAug)),
+                ("epoch", ctypes.c_uint64)]
+
+
 _c = ctypes
 _P = ctypes.c_void_p
 _D = ctypes.POINTER(PLDesc)
@@ -191,6 +202,8 @@ SIGNATURES = {
     "pl_gather_rows2": (_c.c_int, [_P, _c.c_int64, _P, _c.c_int64, _P, _c.c_int64, _c.c_int64, _P, _P, _P]),
     "pl_pose_augment_gather": (_c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_int64, _P, _P, _c.POINTER(PLPoseAug), _c.c_uint64, _P]),
     "pl_pose_augment_host": (_c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_int64, _P, _P, _c.POINTER(PLPoseAug), _c.c_uint64]),
+    "pl_frame_warp_gather": (_c.c_int, [_c.POINTER(PLFrameWarp), _P]),
+    "pl_frame_warp_host": (_c.c_int, [_c.POINTER(PLFrameWarp)]),
     "pl_flip_tta_pack": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _c.c_int64, _P]),
     "pl_flip_tta_merge": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _c.c_int64, _P]),
     "pl_softargmax_dl_scale": (_c.c_int, [_P, _c.c_int64, _c.c_int, _P, _P]),

@@ -2004,6 +2004,7 @@ extern "C" int pl_gather_rows2(const float* a, int64_t wa, const float* b, int64
 }
 
 // Argument checks shared by pl_pose_augment_gather and pl_pose_augment_host; on success *plan is what the transform reads.
+// pose_aug_plan is the part about the PLPoseAug itself, which the frame warp (frame_warp.hip) reads too.
 static bool pa_overlap(const float* x, int64_t nx, const float* y, int64_t ny) {
   const uintptr_t x0 = (uintptr_t)x, x1 = x0 + (uintptr_t)nx * sizeof(float);
   const uintptr_t y0 = (uintptr_t)y, y1 = y0 + (uintptr_t)ny * sizeof(float);
@@ -2021,6 +2022,10 @@ static int pose_augment_args(const char* fn, const float* a, const float* b, con
       pa_overlap(oa, n * pa::kWA, b, table_rows * pa::kWB) || pa_overlap(ob, n * pa::kWB, a, table_rows * pa::kWA) ||
       pa_overlap(ob, n * pa::kWB, b, table_rows * pa::kWB))
     PL_FAIL(PL_EINVAL, "%s: aliased pointers (the outputs overlap each other or a source)", fn);
+  return pose_aug_plan(fn, aug, epoch, plan);
+}
+
+int pl::pose_aug_plan(const char* fn, const PLPoseAug* aug, uint64_t epoch, pa::Plan* plan) {
   const struct { const char* name; float v; bool nonneg; } par[] = {
       {"p_flip", aug->p_flip, true},         {"flip_offset", aug->flip_offset, false},   {"max_rot", aug->max_rot, true},
       {"scale_range", aug->scale_range, true}, {"max_shift", aug->max_shift, true},      {"jitter_sigma", aug->jitter_sigma, true},

@@ -451,6 +451,10 @@ int launch_colsum_partial(const float* X, int rows, int cols, float* part, hipSt
 // eval-mode fold: scale = gamma*rsqrt(rv+eps), shift = (bias - rm)*scale + beta  (bn) or 1, bias
 int launch_bn_fold_eval(const float* bias, const BnParams* bn, int H, float* scale, float* shift, hipStream_t s);
 int launch_fill(float* p, int64_t n, float v, hipStream_t s);
+// the checks of a PLPoseAug's parameters (fn: the entry point named in the message) and the plan the transforms of
+// pose_augment.h and frame_warp.h read
+namespace pa { struct Plan; }
+int pose_aug_plan(const char* fn, const PLPoseAug* aug, uint64_t epoch, pa::Plan* plan);
 // the flat AdamW step over p, g, m, v [n] (adamw_kernel's only launch site).  in: the kernel's own argument block (adamw.h);
 // lr_dev / t_dev, the plane fields (adamw_planes) and the clip record are the optional parts, zero when absent
 struct AdamWArgs {

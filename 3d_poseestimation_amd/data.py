@@ -17,6 +17,12 @@ Train-time augmentation (`PoseAugment`: horizontal flip, in-plane rotation, 2-D 
 reference's commented-out H36_dataset.py:98-117 and train_1.py:83-84) happens inside the launch that builds the batch
 (pl_pose_augment_gather, csrc/pose_augment.h).  Every draw of a pose is a function of (seed, epoch, dataset row), so a run
 replays bit for bit under another batch size, rank count or feeder mode.
+
+Frames (`FrameFeeder`, `augment_frames`): the image networks read [B,256,256,3] fp32 NHWC frames that the reference prepares per
+sample on DataLoader workers (H36_dataset.py:129-131 `cv2.resize(frame,(256,256))`, `frame/256.0`).  Here the frames stay a
+uint8 table -- a quarter of the fp32 bytes, resident or pinned -- and one launch (pl_frame_warp_gather, csrc/frame_warp.h)
+gathers, resizes, scales and warps a batch by the very draws its poses get: frame, 2-D pose and 3-D pose of a dataset row
+always agree.
 """
 import ctypes
 import dataclasses
@@ -271,3 +277,159 @@ class PoseFeeder:
                 inflight.append(launch(nxt, batches[nxt]))
                 nxt += 1
             yield da, db
+
+
+def _frame_augment_struct(augment):
+    """The PLPoseAug a frame warp reads (None: plain resize)."""
+    if augment is None:
+        return None
+    if not isinstance(augment, PoseAugment):
+        raise TypeError("augment must be a PoseAugment or None")
+    if augment.p_flip > 0.0 and augment.flip_offset != 1.0:
+        raise ValueError("a frame flip mirrors about the image centre: p_flip > 0 needs flip_offset = 1 "
+                         f"(image-normalised 2-D poses), got {augment.flip_offset}")
+    return augment.struct()
+
+
+def _frame_geometry(frames, out_hw, scale, fill):
+    """(dtype code, (Ho, Wo), scale, fill) of a [N,Hs,Ws,3] uint8 / fp32 frame table."""
+    if frames.dim() != 4 or frames.shape[3] != 3 or min(frames.shape) == 0:
+        raise ValueError(f"frames are [N,Hs,Ws,3] (NHWC), got {tuple(frames.shape)}")
+    if frames.dtype not in (torch.uint8, torch.float32):
+        raise ValueError(f"frames are uint8 or float32, got {frames.dtype}")
+    ho, wo = (int(v) for v in out_hw)
+    if ho <= 0 or wo <= 0:
+        raise ValueError("out_hw is (Ho, Wo), both positive")
+    u8 = frames.dtype == torch.uint8
+    if scale is None:
+        scale = 1.0 / 256.0 if u8 else 1.0               # H36_dataset.py:131 frame/256.0
+    return (_lib.FRAME_U8 if u8 else _lib.FRAME_F32), (ho, wo), float(scale), float(fill)
+
+
+def _frame_launch(table, code, src_idx, row_ids, nb, out, scale, fill, aug_struct, epoch):
+    """One pl_frame_warp_gather on torch's current stream; src_idx None = the frames of `table` in order."""
+    args = _lib.PLFrameWarp(table.data_ptr(), code, 3, table.shape[0], table.shape[1], table.shape[2],
+                            src_idx.data_ptr() if src_idx is not None else None,
+                            row_ids.data_ptr() if row_ids is not None else None, nb, out.data_ptr(), out.shape[1],
+                            out.shape[2], scale, fill, ctypes.pointer(aug_struct) if aug_struct is not None else None,
+                            int(epoch))
+    _lib.check(_lib.lib().pl_frame_warp_gather(ctypes.byref(args), _lib.current_stream_ptr()), "pl_frame_warp_gather")
+
+
+def augment_frames(frames, augment, row_ids=None, epoch=0, out_hw=(256, 256), fill=0.0, scale=None):
+    """`augment` applied to the frames of a batch: frames [B,Hs,Ws,3] uint8 or fp32 on the device -> a new [B,Ho,Wo,3] fp32
+    tensor, resized (bilinear, cv2.resize's half-pixel convention), multiplied by `scale` (default 1/256 for uint8, the
+    reference's frame/256.0, and 1 for fp32) and flipped, turned, scaled and shifted exactly as augment_poses moves the 2-D
+    poses of the same (row_ids, epoch); pixels whose source lies outside the frame are `fill`.  One launch on the current
+    stream, nothing synchronises.  row_ids and epoch as in augment_poses; augment=None is the plain resize."""
+    aug = _frame_augment_struct(augment)
+    if not isinstance(frames, torch.Tensor):
+        raise TypeError("frames must be a tensor")
+    code, (ho, wo), scale, fill = _frame_geometry(frames, out_hw, scale, fill)
+    _lib.require_device_tensor(frames, "frames", dtype=frames.dtype)
+    nb = frames.shape[0]
+    if row_ids is None:
+        row_ids = torch.arange(nb, dtype=torch.int64, device=frames.device)
+    else:
+        row_ids = torch.as_tensor(row_ids).to(device=frames.device, dtype=torch.int64).contiguous()
+        if row_ids.shape != (nb,):
+            raise ValueError("row_ids holds one dataset index per frame")
+    out = torch.empty((nb, ho, wo, 3), dtype=torch.float32, device=frames.device)
+    with _lib.on_device(frames.device):
+        _frame_launch(frames, code, None, row_ids, nb, out, scale, fill, aug, epoch)
+    return out
+
+
+class FrameFeeder:
+    """Iterable of (frame [b,Ho,Wo,3], y1 [b,17,2], y2 [b,17,3]) fp32 device batches over one epoch: a PoseFeeder whose
+    batches come with their frames.  frames: a [N,Hs,Ws,3] uint8 (or fp32) table, one frame per pose row.  The permutation
+    (epoch_indices) and the identity of the draws -- (augment.seed, epoch, dataset row) -- are the same for all three
+    tensors.  resident: the table on the device, two launches per batch (poses, frames); else the table in pinned memory,
+    batches gathered into pinned staging and copied on a side stream `prefetch` batches ahead, the warp on the consumer's
+    stream behind the copy's event."""
+
+    def __init__(self, frames, x2d, y3d, batch_size, *, out_hw=(256, 256), augment=None, device="cuda", shuffle=True,
+                 seed=0, drop_last=False, rank=0, world=1, resident=True, prefetch=2):
+        self._aug = _frame_augment_struct(augment)
+        frames = torch.as_tensor(frames)
+        self._code, self.out_hw, self._scale, self._fill = _frame_geometry(frames, out_hw, None, 0.0)
+        self.poses = PoseFeeder(x2d, y3d, batch_size, device=device, shuffle=shuffle, seed=seed, drop_last=drop_last,
+                                rank=rank, world=world, resident=resident, prefetch=prefetch, augment=augment)
+        if frames.shape[0] != self.poses.n:
+            raise ValueError("frames, x2d and y3d need the same number of rows")
+        self.device, self.resident, self.prefetch = self.poses.device, resident, self.poses.prefetch
+        frames = frames.contiguous()
+        if resident:
+            self.frames = frames.to(self.device)
+        else:
+            self.frames = frames.pin_memory()
+            self._copy_stream = torch.cuda.Stream(self.device)
+
+    def set_epoch(self, epoch):
+        self.poses.set_epoch(epoch)
+
+    def __len__(self):
+        return len(self.poses)
+
+    def __iter__(self):
+        frames = self._iter_resident() if self.resident else self._iter_streamed()
+        for frame, (y1, y2) in zip(frames, self.poses):
+            yield frame, y1, y2
+
+    def _warp(self, table, src_idx, row_ids, nb, epoch):
+        out = torch.empty((nb,) + self.out_hw + (3,), dtype=torch.float32, device=self.device)
+        with _lib.on_device(self.device):
+            _frame_launch(table, self._code, src_idx, row_ids, nb, out, self._scale, self._fill, self._aug, epoch)
+        return out
+
+    def _iter_resident(self):
+        batches, epoch = self.poses._indices(), self.poses.epoch
+        if not batches:
+            return
+        sizes = [t.numel() for t in batches]
+        idx_all = torch.cat(batches).to(self.device, non_blocking=True)
+        at = 0
+        for nb in sizes:                                  # the permutation slice is both the source frame and the draws' identity
+            idx = idx_all[at:at + nb]
+            at += nb
+            yield self._warp(self.frames, idx, idx, nb, epoch)
+
+    def _iter_streamed(self):
+        batches, epoch = self.poses._indices(), self.poses.epoch
+        bs = self.poses.batch_size
+        slots, inflight = self.prefetch + 1, []
+        stage = [torch.empty((bs,) + tuple(self.frames.shape[1:]), dtype=self.frames.dtype).pin_memory() for _ in range(slots)]
+        stage_idx = [torch.empty(bs, dtype=torch.int64).pin_memory() for _ in range(slots)]
+        free_events = [None] * slots                      # consumer done with the slot's previous batch
+
+        def launch(k, idx):
+            slot = k % slots
+            nb = idx.numel()
+            hf, hi = stage[slot][:nb], stage_idx[slot][:nb]
+            if free_events[slot] is not None:
+                free_events[slot].synchronize()           # staging buffer no longer being copied from
+            torch.index_select(self.frames, 0, idx, out=hf)
+            hi.copy_(idx)
+            with torch.cuda.stream(self._copy_stream):
+                df = hf.to(self.device, non_blocking=True)
+                di = hi.to(self.device, non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record(self._copy_stream)
+            free_events[slot] = ev
+            return df, di, ev
+
+        nxt = 0
+        while nxt < len(batches) and len(inflight) < self.prefetch:
+            inflight.append(launch(nxt, batches[nxt]))
+            nxt += 1
+        while inflight:
+            df, di, ev = inflight.pop(0)
+            cur = torch.cuda.current_stream(self.device)
+            cur.wait_event(ev)
+            df.record_stream(cur)
+            di.record_stream(cur)
+            out = self._warp(df, None, di, di.numel(), epoch)     # one launch on the consumer's stream, behind the event wait
+            if nxt < len(batches):
+                inflight.append(launch(nxt, batches[nxt]))
+                nxt += 1
+            yield out

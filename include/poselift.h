@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define PL_VERSION 114 /* 0.1.14: + PLPoseAug, pl_pose_augment_gather, pl_pose_augment_host (seeded train-time pose augmentation inside the batch gather); 0.1.13: + PLClipRecord, pl_grad_norm_scratch_bytes, pl_grad_norm_clip, pl_adamw_flat_clip, pl_adamw_flat_dev_clip, pl_adamw_flat_planes_clip (gradient-norm clipping and non-finite skip on the device); 0.1.12: + pl_pose_errors, pl_pose_errors_host, pl_pose_metrics_scratch_bytes, pl_pose_metrics_accum (evaluation: MPJPE / N-MPJPE / P-MPJPE, PCK counts, per group); 0.1.11: + pl_vit_*_bf16, pl_vit_bf16_pack (MyViT "bf16p": bf16 operand carriers written by their producers); 0.1.10: + pl_vit_* (the MyViT transformer lifter); 0.1.9: + pl_conv2d_planes_fwd_hw, pl_conv2d_planes_wgrad_hw (the stem on the planes GEMM); 0.1.8: + pl_lifter_train_step, pl_lifter_step_carries_adamw; 0.1.7: + pl_workspace_bitmap_format (small-batch layer kernels); 0.1.6: + pl_counter_add; 0.1.5: + pl_flip_pose_ex, pl_flip_w_nhwc (phase5 Flip branch); 0.1.4: + pl_planes_split_strided; 0.1.3: + pl_bn_join_bwd (0.1.2: operand-plane outputs of the BatchNorm / join kernels, pl_gemm_planes_raw) */
+#define PL_VERSION 115 /* 0.1.15: + PLFrameWarp, pl_frame_warp_gather, pl_frame_warp_host (frame gather + resize + the pose augmentation's warp in one launch); 0.1.14: + PLPoseAug, pl_pose_augment_gather, pl_pose_augment_host (seeded train-time pose augmentation inside the batch gather); 0.1.13: + PLClipRecord, pl_grad_norm_scratch_bytes, pl_grad_norm_clip, pl_adamw_flat_clip, pl_adamw_flat_dev_clip, pl_adamw_flat_planes_clip (gradient-norm clipping and non-finite skip on the device); 0.1.12: + pl_pose_errors, pl_pose_errors_host, pl_pose_metrics_scratch_bytes, pl_pose_metrics_accum (evaluation: MPJPE / N-MPJPE / P-MPJPE, PCK counts, per group); 0.1.11: + pl_vit_*_bf16, pl_vit_bf16_pack (MyViT "bf16p": bf16 operand carriers written by their producers); 0.1.10: + pl_vit_* (the MyViT transformer lifter); 0.1.9: + pl_conv2d_planes_fwd_hw, pl_conv2d_planes_wgrad_hw (the stem on the planes GEMM); 0.1.8: + pl_lifter_train_step, pl_lifter_step_carries_adamw; 0.1.7: + pl_workspace_bitmap_format (small-batch layer kernels); 0.1.6: + pl_counter_add; 0.1.5: + pl_flip_pose_ex, pl_flip_w_nhwc (phase5 Flip branch); 0.1.4: + pl_planes_split_strided; 0.1.3: + pl_bn_join_bwd (0.1.2: operand-plane outputs of the BatchNorm / join kernels, pl_gemm_planes_raw) */
 
 typedef enum PLStatus {
   PL_OK = 0,
@@ -393,6 +393,46 @@ int pl_pose_augment_gather(const float* a, const float* b, const int64_t* src_id
                            int64_t table_rows, float* oa, float* ob, const PLPoseAug* aug, uint64_t epoch, void* stream);
 int pl_pose_augment_host(const float* a, const float* b, const int64_t* src_idx, const int64_t* row_id, int64_t n,
                          int64_t table_rows, float* oa, float* ob, const PLPoseAug* aug, uint64_t epoch);
+
+/* The frames of the same rows, gathered, resized, normalised and augmented in one launch (csrc/frame_warp.h has the
+ * definition; the reference resizes per sample on the host, H36_dataset.py:129-131 `cv2.resize(frame,(256,256))`,
+ * `frame/256.0`, and leaves `cv2.flip(frame,1)` next to flip_pose commented out, :98-117).  The decisions flip, rotation,
+ * scale and shift of a frame are those of pl_pose_augment_gather for the same (seed, epoch, row_id): frame, 2-D pose and 3-D
+ * pose of a dataset row always agree.  jitter_sigma is pose noise and touches no frame.
+ *   src [N][Hs][Ws][3] uint8 or fp32 -> out [n][Ho][Wo][3] fp32; sample k reads frame s = src_idx[k] (k when src_idx is NULL)
+ *   with the draws of row_id[k].  Output pixel (i, j), every stage whose parameter is 0 skipped:
+ *     u = (j + 0.5) / Wo, v = (i + 0.5) / Ho          (pixel centres, image-normalised: the 2-D pose's coordinates)
+ *     u -= tx, v -= ty;  u = (u - cx) / sc + cx, v likewise;  (du, dv) = (u - cx, v - cy): u = (c du + s dv) + cx,
+ *     v = (-s du + c dv) + cy;  flipped: u = 1 - u    (the pose transform undone in reverse order)
+ *     xs = u Ws - 0.5, ys = v Hs - 0.5;  outside [-0.5, Ws - 0.5] x [-0.5, Hs - 0.5]: `fill` on all three channels
+ *     else clamp to [0, Ws - 1] x [0, Hs - 1], x0 = floor(xs), x1 = min(x0 + 1, Ws - 1), y likewise, and
+ *     value = scale * ((1 - fy) ((1 - fx) p00 + fx p01) + fy ((1 - fx) p10 + fx p11))
+ *   With aug NULL or all stages off this is bilinear resizing in cv2.resize's half-pixel convention (no antialiasing).
+ *   Every operation is rounded on its own; the flip is taken as xs = (Ws - 1) - xs and, with shift, scale and rotation all
+ *   off, xs = (j + 0.5) (Ws / Wo) - 0.5 (ys likewise), so a same-size resize copies scale * p exactly and a flip mirrors it.
+ * A frame flip mirrors about the image centre: p_flip > 0 with flip_offset != 1 is PL_EINVAL; the other PLPoseAug checks are
+ * pl_pose_augment_gather's.  C != 3 and non-positive sizes are PL_ESHAPE, a null table PL_EINVAL; an s outside [0, N) gives a
+ * NaN frame on the device and PL_EINVAL on the host.  row_id may be NULL when aug is. */
+enum { PL_FRAME_U8 = 0, PL_FRAME_F32 = 1 };
+typedef struct PLFrameWarp {
+  const void* src;          /* [N][Hs][Ws][C] */
+  int32_t src_dtype;        /* PL_FRAME_U8 or PL_FRAME_F32 */
+  int32_t C;                /* 3 */
+  int64_t N, Hs, Ws;
+  const int64_t* src_idx;   /* [n] or NULL */
+  const int64_t* row_id;    /* [n] */
+  int64_t n;
+  float* out;               /* [n][Ho][Wo][C] */
+  int64_t Ho, Wo;
+  float scale;              /* the reference's frame/256.0: 1/256 for uint8 tables; 1 keeps fp32 values */
+  float fill;               /* value of pixels whose source position lies outside the frame */
+  const PLPoseAug* aug;     /* NULL: plain resize */
+  uint64_t epoch;
+} PLFrameWarp;
+/* pl_frame_warp_gather: one launch on `stream`; no allocation, no synchronisation.
+ * pl_frame_warp_host: the same inline text compiled for the CPU, on host pointers (a test hook). */
+int pl_frame_warp_gather(const PLFrameWarp* a, void* stream);
+int pl_frame_warp_host(const PLFrameWarp* a);
 
 /* ---- loss / metric / optimiser -------------------------------------------------- */
 /* torch.nn.MSELoss(reduction="mean") + its backward  train_1.py:37,94-95.
