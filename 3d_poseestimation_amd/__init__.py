@@ -15,6 +15,7 @@ from .losses import TriangleLoss, heatmap_mse, l1_loss, l1_terms  # noqa: F401
 from .metrics import AUC_THRESHOLDS, PoseMetrics, pose_errors, procrustes_align  # noqa: F401
 from .backbone import Model_2D, Model_3D, ResNet  # noqa: F401
 from .data import FrameFeeder, PoseAugment, PoseFeeder, augment_frames, augment_poses, epoch_indices  # noqa: F401
+from .pose_table import H36M_17_OF_32, PoseStats, PoseTransform, pose_stats, prepare_poses  # noqa: F401
 from .vit import MyViT  # noqa: F401
 from .range_guard import PoseliftRangeError  # noqa: F401
-from . import arena, backbone, conv, data, dp, gradclip, layout, metrics, range_guard, synth, vit  # noqa: F401
+from . import arena, backbone, conv, data, dp, gradclip, layout, metrics, pose_table, range_guard, synth, vit  # noqa: F401

@@ -133,6 +133,8 @@ SIGNATURES = {
     "pl_mpjpe_accum": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _P, _P, _P]),
     "pl_pose_errors": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _P, _P, _P]),
     "pl_pose_errors_host": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _P, _P]),
+    "pl_pose_errors_t": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _P, _P, _P, _P, _P]),
+    "pl_mpjpe_accum_t": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _P, _P, _P, _P, _P]),
     "pl_pose_metrics_scratch_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int64, _c.c_int, _c.c_int]),
     "pl_pose_metrics_accum": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _P, _c.c_int, _P, _c.c_int, _P, _P, _P, _P, _P]),
     "pl_adamw_flat": (_c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_float, _c.c_float, _c.c_float,
@@ -202,6 +204,18 @@ SIGNATURES = {
     "pl_gather_rows2": (_c.c_int, [_P, _c.c_int64, _P, _c.c_int64, _P, _c.c_int64, _c.c_int64, _P, _P, _P]),
     "pl_pose_augment_gather": (_c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_int64, _P, _P, _c.POINTER(PLPoseAug), _c.c_uint64, _P]),
     "pl_pose_augment_host": (_c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_int64, _P, _P, _c.POINTER(PLPoseAug), _c.c_uint64]),
+    "pl_pose_augment_gather_t": (_c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_int64, _P, _P, _c.POINTER(PLPoseAug), _c.c_uint64,
+                                            _P, _P, _P, _P, _P]),
+    "pl_pose_augment_host_t": (_c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_int64, _P, _P, _c.POINTER(PLPoseAug), _c.c_uint64,
+                                          _P, _P, _P, _P]),
+    "pl_pose_prepare": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _c.c_int64, _P, _c.c_int64, _P, _P, _c.c_int64, _c.c_int, _P, _P]),
+    "pl_pose_prepare_host": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _c.c_int64, _P, _c.c_int64, _P, _P, _c.c_int64, _c.c_int, _P]),
+    "pl_pose_stats_chunk_rows": (_c.c_int64, []),
+    "pl_pose_stats_scratch_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int64]),
+    "pl_pose_stats": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _P, _P, _P]),
+    "pl_pose_stats_host": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _P]),
+    "pl_pose_affine": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _P, _P, _c.c_int, _P, _P]),
+    "pl_pose_affine_host": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _P, _P, _c.c_int, _P]),
     "pl_frame_warp_gather": (_c.c_int, [_c.POINTER(PLFrameWarp), _P]),
     "pl_frame_warp_host": (_c.c_int, [_c.POINTER(PLFrameWarp)]),
     "pl_flip_tta_pack": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _c.c_int64, _P]),

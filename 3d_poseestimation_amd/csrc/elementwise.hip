@@ -14,6 +14,7 @@
 #include "bn_pieces.h"
 #include "philox.h"
 #include "pose_augment.h"
+#include "pose_table.h"
 #include <stdlib.h>
 
 #include <algorithm>
@@ -1228,14 +1229,29 @@ __global__ __launch_bounds__(64) void l1_final_kernel(const float* __restrict__ 
 }
 
 // ---- loss_MPJPE --------------------------------------------------------------------------
+// XF (pl_mpjpe_accum_t): both tensors are taken out of the model's space as they are loaded, x = y div[c] + sub[c] over
+// the 3 J columns of a pose (pose_table.h invert1); XF = false is the kernel as it was.
+template <bool XF>
 __global__ void mpjpe_partial_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
-                                     int B, int J, int rpc, float* __restrict__ part) {
+                                     int B, int J, int rpc, float* __restrict__ part, const float* __restrict__ sub,
+                                     const float* __restrict__ div) {
   const int r0 = blockIdx.x * rpc, r1 = min(B, r0 + rpc);
   for (int j = threadIdx.x; j < J; j += blockDim.x) {
     float s = 0.f;
+    float sb[3] = {0.f, 0.f, 0.f}, dv[3] = {1.f, 1.f, 1.f};
+    if constexpr (XF) {
+      for (int d = 0; d < 3; ++d) { sb[d] = sub[3 * j + d]; dv[d] = div[3 * j + d]; }
+    }
     for (int r = r0; r < r1; ++r) {
       const size_t o = ((size_t)r * J + j) * 3;
-      const float dx = pred[o] - tgt[o], dy = pred[o + 1] - tgt[o + 1], dz = pred[o + 2] - tgt[o + 2];
+      float dx, dy, dz;
+      if constexpr (XF) {
+        dx = pt::invert1(pred[o], sb[0], dv[0]) - pt::invert1(tgt[o], sb[0], dv[0]);
+        dy = pt::invert1(pred[o + 1], sb[1], dv[1]) - pt::invert1(tgt[o + 1], sb[1], dv[1]);
+        dz = pt::invert1(pred[o + 2], sb[2], dv[2]) - pt::invert1(tgt[o + 2], sb[2], dv[2]);
+      } else {
+        dx = pred[o] - tgt[o]; dy = pred[o + 1] - tgt[o + 1]; dz = pred[o + 2] - tgt[o + 2];
+      }
       s += sqrtf(fmaf(dx, dx, fmaf(dy, dy, dz * dz)));
     }
     part[(size_t)blockIdx.x * J + j] = s;
@@ -1355,12 +1371,19 @@ __global__ void gather_rows2_kernel(const float* __restrict__ a, int wa, const f
 // consecutive lanes store consecutive floats, and load them too unless the pose is flipped (then joints swap inside the
 // 340-byte row).  Every stage test is on a kernel argument, the same in all lanes; with all stages off the kernel is
 // gather_rows2's copy.  A source index outside [0, table_rows) reads nothing and yields a NaN pose.
+// XF (pl_pose_augment_gather_t): every output element goes through its column's transform (pose_table.h apply1) after
+// the augmentation, a's 34 columns by (xf.sa, xf.da), b's 51 by (xf.sb, xf.db), either pair nullable.  XF = false is the
+// kernel as it was and reads no field of xf.
 constexpr int PA_LANES = 32;
+struct PoseXf {
+  const float *sa, *da, *sb, *db;
+};
+template <bool XF>
 __global__ __launch_bounds__(NTHR) void pose_augment_gather_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                                    const int64_t* __restrict__ src_idx,
                                                                    const int64_t* __restrict__ row_id, int64_t n,
                                                                    int64_t table_rows, float* __restrict__ oa,
-                                                                   float* __restrict__ ob, pa::Plan p) {
+                                                                   float* __restrict__ ob, pa::Plan p, PoseXf xf) {
   const int gl = threadIdx.x & (PA_LANES - 1);
   const int64_t k = (int64_t)blockIdx.x * (NTHR / PA_LANES) + (threadIdx.x / PA_LANES);
   if (k >= n) return;                                   // a whole group leaves; no shuffle below crosses a group
@@ -1411,6 +1434,9 @@ __global__ __launch_bounds__(NTHR) void pose_augment_gather_kernel(const float* 
       const int j = e >> 1, d = e & 1, sj = q.flip ? pa::flip_src_joint(j) : j;
       float v = bad;
       if (ok) v = pa::elem2d(p, q, d, ar[sj * 2 + d], rot ? ar[sj * 2 + (d ^ 1)] : 0.f, it == 0 ? nz_lo : nz_hi);
+      if constexpr (XF) {
+        if (xf.sa) v = pt::apply1(v, xf.sa[e], xf.da[e]);
+      }
       oar[e] = v;
     } else if (e < pa::kRow) {
       const int c = e - pa::kWA, j = c / 3, d = c - 3 * j, sj = q.flip ? pa::flip_src_joint(j) : j;
@@ -1418,6 +1444,9 @@ __global__ __launch_bounds__(NTHR) void pose_augment_gather_kernel(const float* 
       if (ok) {
         v = br[sj * 3 + d];
         if (d != 2) v = pa::elem3d(p, q, d, v, rot ? br[sj * 3 + (d ^ 1)] : 0.f);
+      }
+      if constexpr (XF) {
+        if (xf.sb) v = pt::apply1(v, xf.sb[c], xf.db[c]);
       }
       obr[c] = v;
     }
@@ -1821,20 +1850,37 @@ extern "C" size_t pl_mpjpe_scratch_bytes(int64_t B, int64_t joints) {
   return (size_t)mpjpe_chunks(B) * (size_t)(joints > 0 ? joints : 1) * sizeof(float);
 }
 
-extern "C" int pl_mpjpe_accum(const float* pred, const float* tgt, int64_t B, int64_t joints,
-                              float* metric, void* scratch, void* stream) {
-  if (!pred || !tgt || !metric || !scratch) PL_FAIL(PL_EINVAL, "pl_mpjpe_accum: null pointer");
-  if (B <= 0 || joints <= 0 || joints > 1024) PL_FAIL(PL_ESHAPE, "pl_mpjpe_accum: B=%lld joints=%lld", (long long)B, (long long)joints);
+// mpjpe_partial_kernel's only launch site; sub == nullptr: the plain instantiation
+static int launch_mpjpe(const char* fn, const float* pred, const float* tgt, int64_t B, int64_t joints, const float* sub,
+                        const float* div, float* metric, void* scratch, void* stream) {
+  if (!pred || !tgt || !metric || !scratch) PL_FAIL(PL_EINVAL, "%s: null pointer", fn);
+  if (B <= 0 || joints <= 0 || joints > 1024) PL_FAIL(PL_ESHAPE, "%s: B=%lld joints=%lld", fn, (long long)B, (long long)joints);
   hipStream_t s = (hipStream_t)stream;
   const int nc = mpjpe_chunks(B);
   const int rpc = (int)((B + nc - 1) / nc);
-  hipLaunchKernelGGL(mpjpe_partial_kernel, dim3(nc), dim3(64), 0, s, pred, tgt, (int)B, (int)joints, rpc,
-                     (float*)scratch);
+  if (sub)
+    hipLaunchKernelGGL(mpjpe_partial_kernel<true>, dim3(nc), dim3(64), 0, s, pred, tgt, (int)B, (int)joints, rpc,
+                       (float*)scratch, sub, div);
+  else
+    hipLaunchKernelGGL(mpjpe_partial_kernel<false>, dim3(nc), dim3(64), 0, s, pred, tgt, (int)B, (int)joints, rpc,
+                       (float*)scratch, (const float*)nullptr, (const float*)nullptr);
   PL_CHECK_LAUNCH("mpjpe_partial");
   hipLaunchKernelGGL(mpjpe_final_kernel, dim3(1), dim3(64), 0, s, (const float*)scratch, nc, (int)joints,
                      metric);
   PL_CHECK_LAUNCH("mpjpe_final");
   return PL_OK;
+}
+
+extern "C" int pl_mpjpe_accum(const float* pred, const float* tgt, int64_t B, int64_t joints,
+                              float* metric, void* scratch, void* stream) {
+  return launch_mpjpe("pl_mpjpe_accum", pred, tgt, B, joints, nullptr, nullptr, metric, scratch, stream);
+}
+
+extern "C" int pl_mpjpe_accum_t(const float* pred, const float* tgt, int64_t B, int64_t joints, const float* sub_or_null,
+                                const float* div_or_null, float* metric, void* scratch, void* stream) {
+  if ((sub_or_null != nullptr) != (div_or_null != nullptr)) PL_FAIL(PL_EINVAL, "pl_mpjpe_accum_t: sub and div come together");
+  if (sub_or_null && joints > pt::kMaxJoints) PL_FAIL(PL_ESHAPE, "pl_mpjpe_accum_t: joints=%lld with a transform (at most %d)", (long long)joints, pt::kMaxJoints);
+  return launch_mpjpe("pl_mpjpe_accum_t", pred, tgt, B, joints, sub_or_null, div_or_null, metric, scratch, stream);
 }
 
 // (same-box sweep, B = 64 step: 256 / 512 / 1024 / 2048 blocks -> 0.1297 / 0.1289 / 0.1295 / 0.1304 ms; B = 4096: no difference)
@@ -2040,16 +2086,44 @@ int pl::pose_aug_plan(const char* fn, const PLPoseAug* aug, uint64_t epoch, pa::
   return PL_OK;
 }
 
+// pose_augment_gather_kernel's only launch site; no transform at all: the plain instantiation
+static int launch_pose_augment(const char* fn, const float* a, const float* b, const int64_t* src_idx, const int64_t* row_id,
+                               int64_t n, int64_t table_rows, float* oa, float* ob, const PLPoseAug* aug, uint64_t epoch,
+                               const PoseXf& xf, void* stream) {
+  pa::Plan plan;
+  PL_TRY(pose_augment_args(fn, a, b, src_idx, row_id, n, table_rows, oa, ob, aug, epoch, &plan));
+  constexpr int per = NTHR / PA_LANES;
+  const dim3 grid((unsigned)((n + per - 1) / per));
+  if (xf.sa || xf.sb)
+    hipLaunchKernelGGL(pose_augment_gather_kernel<true>, grid, dim3(NTHR), 0, (hipStream_t)stream, a, b, src_idx, row_id, n,
+                       table_rows, oa, ob, plan, xf);
+  else
+    hipLaunchKernelGGL(pose_augment_gather_kernel<false>, grid, dim3(NTHR), 0, (hipStream_t)stream, a, b, src_idx, row_id, n,
+                       table_rows, oa, ob, plan, xf);
+  PL_CHECK_LAUNCH("pose_augment_gather");
+  return PL_OK;
+}
+
+static int pose_xf_args(const char* fn, const float* sub_a, const float* div_a, const float* sub_b, const float* div_b) {
+  if ((sub_a != nullptr) != (div_a != nullptr) || (sub_b != nullptr) != (div_b != nullptr))
+    PL_FAIL(PL_EINVAL, "%s: a transform is a (sub, div) pair", fn);
+  return PL_OK;
+}
+
 extern "C" int pl_pose_augment_gather(const float* a, const float* b, const int64_t* src_idx, const int64_t* row_id,
                                       int64_t n, int64_t table_rows, float* oa, float* ob, const PLPoseAug* aug,
                                       uint64_t epoch, void* stream) {
-  pa::Plan plan;
-  PL_TRY(pose_augment_args("pl_pose_augment_gather", a, b, src_idx, row_id, n, table_rows, oa, ob, aug, epoch, &plan));
-  constexpr int per = NTHR / PA_LANES;
-  hipLaunchKernelGGL(pose_augment_gather_kernel, dim3((unsigned)((n + per - 1) / per)), dim3(NTHR), 0, (hipStream_t)stream,
-                     a, b, src_idx, row_id, n, table_rows, oa, ob, plan);
-  PL_CHECK_LAUNCH("pose_augment_gather");
-  return PL_OK;
+  return launch_pose_augment("pl_pose_augment_gather", a, b, src_idx, row_id, n, table_rows, oa, ob, aug, epoch,
+                             PoseXf{nullptr, nullptr, nullptr, nullptr}, stream);
+}
+
+extern "C" int pl_pose_augment_gather_t(const float* a, const float* b, const int64_t* src_idx, const int64_t* row_id,
+                                        int64_t n, int64_t table_rows, float* oa, float* ob, const PLPoseAug* aug,
+                                        uint64_t epoch, const float* sub_a, const float* div_a, const float* sub_b,
+                                        const float* div_b, void* stream) {
+  PL_TRY(pose_xf_args("pl_pose_augment_gather_t", sub_a, div_a, sub_b, div_b));
+  return launch_pose_augment("pl_pose_augment_gather_t", a, b, src_idx, row_id, n, table_rows, oa, ob, aug, epoch,
+                             PoseXf{sub_a, div_a, sub_b, div_b}, stream);
 }
 
 extern "C" int pl_pose_augment_host(const float* a, const float* b, const int64_t* src_idx, const int64_t* row_id, int64_t n,
@@ -2064,6 +2138,18 @@ extern "C" int pl_pose_augment_host(const float* a, const float* b, const int64_
   for (int64_t k = 0; k < n; ++k) {
     const int64_t src = src_idx ? src_idx[k] : k;
     pa::augment_pose(plan, (uint64_t)row_id[k], a + src * pa::kWA, b + src * pa::kWB, oa + k * pa::kWA, ob + k * pa::kWB);
+  }
+  return PL_OK;
+}
+
+extern "C" int pl_pose_augment_host_t(const float* a, const float* b, const int64_t* src_idx, const int64_t* row_id, int64_t n,
+                                      int64_t table_rows, float* oa, float* ob, const PLPoseAug* aug, uint64_t epoch,
+                                      const float* sub_a, const float* div_a, const float* sub_b, const float* div_b) {
+  PL_TRY(pose_xf_args("pl_pose_augment_host_t", sub_a, div_a, sub_b, div_b));
+  PL_TRY(pl_pose_augment_host(a, b, src_idx, row_id, n, table_rows, oa, ob, aug, epoch));
+  for (int64_t k = 0; k < n; ++k) {
+    for (int e = 0; sub_a && e < pa::kWA; ++e) oa[k * pa::kWA + e] = pt::apply1(oa[k * pa::kWA + e], sub_a[e], div_a[e]);
+    for (int e = 0; sub_b && e < pa::kWB; ++e) ob[k * pa::kWB + e] = pt::apply1(ob[k * pa::kWB + e], sub_b[e], div_b[e]);
   }
   return PL_OK;
 }

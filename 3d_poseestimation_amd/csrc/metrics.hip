@@ -4,6 +4,7 @@
 
 #include "pl_internal.h"
 #include "pose_metrics.h"
+#include "pose_table.h"
 
 namespace pl {
 namespace {
@@ -14,9 +15,13 @@ constexpr int kPoseBlock = 64;        // poses per workgroup = lanes of its one 
 // reading its own pose from global memory would stride 12 J bytes between lanes); a pose's row is padded to an odd number
 // of floats so the 64 lanes, each walking its own row, fall on distinct banks.  pose_errors_one() leaves the aligned pose
 // in the prediction's row and e[j][m] in the target's row; both leave the LDS coalesced again.
+// XF (pl_pose_errors_t): both tensors are in a model's space; column c of a pose is taken back, x = y div[c] + sub[c]
+// (pose_table.h invert1), on its way into the LDS.  XF = false is the kernel as it was and reads neither pointer.
+template <bool XF>
 __global__ __launch_bounds__(kPoseBlock) void pose_errors_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
                                                                  int64_t B, int J, float* __restrict__ err,
-                                                                 float* __restrict__ aligned) {
+                                                                 float* __restrict__ aligned, const float* __restrict__ sub,
+                                                                 const float* __restrict__ div) {
   extern __shared__ __align__(16) float lds[];
   const int W = 3 * J, S = W | 1;
   float* lp = lds;
@@ -37,8 +42,13 @@ __global__ __launch_bounds__(kPoseBlock) void pose_errors_kernel(const float* __
       int r = row, c = col;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        lp[r * S + c] = ep[k];
-        lt[r * S + c] = et[k];
+        if constexpr (XF) {
+          lp[r * S + c] = pt::invert1(ep[k], sub[c], div[c]);
+          lt[r * S + c] = pt::invert1(et[k], sub[c], div[c]);
+        } else {
+          lp[r * S + c] = ep[k];
+          lt[r * S + c] = et[k];
+        }
         if (++c == W) { c = 0; ++r; }
       }
       row += drow; col += dcol;
@@ -46,8 +56,13 @@ __global__ __launch_bounds__(kPoseBlock) void pose_errors_kernel(const float* __
     }
     for (int i = 4 * n4 + tid; i < n; i += kPoseBlock) {   // at most 3 floats
       const int r = i / W, c = i - r * W;
-      lp[r * S + c] = gp[i];
-      lt[r * S + c] = gt[i];
+      if constexpr (XF) {
+        lp[r * S + c] = pt::invert1(gp[i], sub[c], div[c]);
+        lt[r * S + c] = pt::invert1(gt[i], sub[c], div[c]);
+      } else {
+        lp[r * S + c] = gp[i];
+        lt[r * S + c] = gt[i];
+      }
     }
   }
   __syncthreads();
@@ -211,16 +226,32 @@ int check_pose_args(const char* who, const float* pred, const float* tgt, int64_
 
 using namespace pl;
 
-extern "C" int pl_pose_errors(const float* pred, const float* tgt, int64_t B, int64_t J, float* err,
-                              float* aligned_or_null, void* stream) {
-  PL_TRY(check_pose_args("pl_pose_errors", pred, tgt, B, J, err, aligned_or_null));
+// pose_errors_kernel's only launch site; sub == nullptr: the plain instantiation
+static int launch_pose_errors(const char* who, const float* pred, const float* tgt, int64_t B, int64_t J, float* err,
+                              float* aligned_or_null, const float* sub, const float* div, void* stream) {
+  PL_TRY(check_pose_args(who, pred, tgt, B, J, err, aligned_or_null));
   const int S = (3 * (int)J) | 1;
   const size_t lds = (size_t)2 * kPoseBlock * S * sizeof(float);      // 49,664 B at J = 32
   const unsigned grid = (unsigned)((B + kPoseBlock - 1) / kPoseBlock);
-  hipLaunchKernelGGL(pose_errors_kernel, dim3(grid), dim3(kPoseBlock), lds, (hipStream_t)stream, pred, tgt, B, (int)J, err,
-                     aligned_or_null);
+  if (sub)
+    hipLaunchKernelGGL(pose_errors_kernel<true>, dim3(grid), dim3(kPoseBlock), lds, (hipStream_t)stream, pred, tgt, B, (int)J,
+                       err, aligned_or_null, sub, div);
+  else
+    hipLaunchKernelGGL(pose_errors_kernel<false>, dim3(grid), dim3(kPoseBlock), lds, (hipStream_t)stream, pred, tgt, B, (int)J,
+                       err, aligned_or_null, (const float*)nullptr, (const float*)nullptr);
   PL_CHECK_LAUNCH("pose_errors");
   return PL_OK;
+}
+
+extern "C" int pl_pose_errors(const float* pred, const float* tgt, int64_t B, int64_t J, float* err,
+                              float* aligned_or_null, void* stream) {
+  return launch_pose_errors("pl_pose_errors", pred, tgt, B, J, err, aligned_or_null, nullptr, nullptr, stream);
+}
+
+extern "C" int pl_pose_errors_t(const float* pred, const float* tgt, int64_t B, int64_t J, const float* sub_or_null,
+                                const float* div_or_null, float* err, float* aligned_or_null, void* stream) {
+  if ((sub_or_null != nullptr) != (div_or_null != nullptr)) PL_FAIL(PL_EINVAL, "pl_pose_errors_t: sub and div come together");
+  return launch_pose_errors("pl_pose_errors_t", pred, tgt, B, J, err, aligned_or_null, sub_or_null, div_or_null, stream);
 }
 
 extern "C" int pl_pose_errors_host(const float* pred, const float* tgt, int64_t B, int64_t J, float* err,

@@ -18,6 +18,10 @@ reference's commented-out H36_dataset.py:98-117 and train_1.py:83-84) happens in
 (pl_pose_augment_gather, csrc/pose_augment.h).  Every draw of a pose is a function of (seed, epoch, dataset row), so a run
 replays bit for bit under another batch size, rank count or feeder mode.
 
+Tables stay raw.  `transform_2d=` / `transform_3d=` (pose_table.PoseTransform: standardise, normalise) are applied to each
+batch AFTER the augmentation, in the same launch (pl_pose_augment_gather_t): a flip of standardised coordinates is no
+mirror image unless the statistics are left/right symmetric, and jitter, shift and centre are in image units.
+
 Frames (`FrameFeeder`, `augment_frames`): the image networks read [B,256,256,3] fp32 NHWC frames that the reference prepares per
 sample on DataLoader workers (H36_dataset.py:129-131 `cv2.resize(frame,(256,256))`, `frame/256.0`).  Here the frames stay a
 uint8 table -- a quarter of the fp32 bytes, resident or pinned -- and one launch (pl_frame_warp_gather, csrc/frame_warp.h)
@@ -32,6 +36,7 @@ import torch
 
 from . import _lib
 from .dp import shard_rows
+from .pose_table import transform_pair
 
 
 def epoch_indices(n_rows, batch_size, *, epoch=0, seed=0, shuffle=True, drop_last=False, rank=0, world=1):
@@ -82,8 +87,10 @@ class PoseAugment:
     uniform in [-max_rot, max_rot) radians, scale about `centre` by a factor uniform in [1 - scale_range, 1 + scale_range),
     shift by (tx, ty) uniform in [-max_shift, max_shift), add N(0, jitter_sigma^2) noise to every coordinate.
     3-D: the same flip (x -> -x) and the same rotation of (x, y); z, scale and shift leave the root-relative target alone.
-    flip_offset is 1 for image-normalised x in [0, 1] and 0 for zero-mean standardised inputs.  A parameter of 0 switches
-    its stage off exactly; the default object changes no bit."""
+    flip_offset is 1 for image-normalised x in [0, 1].  Augment RAW poses: keep the tables raw and pass the feeder (or
+    augment_poses) `transform_2d=` / `transform_3d=`, which standardise the batch after the augmentation in the same
+    launch -- on standardised coordinates the flip is no mirror image and the other parameters lose their units.  A
+    parameter of 0 switches its stage off exactly; the default object changes no bit."""
     p_flip: float = 0.0
     flip_offset: float = 1.0
     max_rot: float = 0.0
@@ -120,21 +127,40 @@ class PoseAugment:
                               self.jitter_sigma, self.centre[0], self.centre[1], self.seed)
 
 
-def _augment_launch(a, b, src_idx, row_ids, nb, table_rows, oa, ob, aug_struct, epoch):
-    """One pl_pose_augment_gather on torch's current stream; src_idx None = the rows of a, b in order."""
+def _augment_launch(a, b, src_idx, row_ids, nb, table_rows, oa, ob, aug_struct, epoch, xf=None):
+    """One pl_pose_augment_gather on torch's current stream; src_idx None = the rows of a, b in order.
+    xf: (sub_a, div_a, sub_b, div_b) device pointers of the transforms (_transforms) -> pl_pose_augment_gather_t."""
+    if xf is not None:
+        _lib.check(_lib.lib().pl_pose_augment_gather_t(a.data_ptr(), b.data_ptr(),
+                                                       src_idx.data_ptr() if src_idx is not None else None,
+                                                       row_ids.data_ptr(), nb, table_rows, oa.data_ptr(), ob.data_ptr(),
+                                                       ctypes.byref(aug_struct), int(epoch), xf[0], xf[1], xf[2], xf[3],
+                                                       _lib.current_stream_ptr()),
+                   "pl_pose_augment_gather_t")
+        return
     _lib.check(_lib.lib().pl_pose_augment_gather(a.data_ptr(), b.data_ptr(), src_idx.data_ptr() if src_idx is not None else None,
                                                  row_ids.data_ptr(), nb, table_rows, oa.data_ptr(), ob.data_ptr(),
                                                  ctypes.byref(aug_struct), int(epoch), _lib.current_stream_ptr()),
                "pl_pose_augment_gather")
 
 
-def augment_poses(y1, y2, augment, row_ids=None, epoch=0):
+def _transforms(transform_2d, transform_3d, device):
+    """((sub_a, div_a, sub_b, div_b), tensors kept alive) of the optional pair; (None, None) when both are None."""
+    if transform_2d is None and transform_3d is None:
+        return None, None
+    sa, da, keep_a = transform_pair(transform_2d, (17, 2), device, "transform_2d")
+    sb, db, keep_b = transform_pair(transform_3d, (17, 3), device, "transform_3d")
+    return (sa, da, sb, db), (keep_a, keep_b)
+
+
+def augment_poses(y1, y2, augment, row_ids=None, epoch=0, transform_2d=None, transform_3d=None):
     """`augment` applied to a batch that came from somewhere else: y1 (B,17,2), y2 (B,17,3) fp32 device tensors -> new
     (y1, y2) tensors; the inputs are untouched and nothing synchronises (one launch on the current stream).
 
     A pose's draws are a function of (augment.seed, epoch, row id) only.  Pass the poses' DATASET indices as `row_ids`
     (int64, B of them) -- or at least an `epoch` that changes from call to call -- to get fresh draws: with the default
-    row_ids = arange(B) and a fixed epoch, pose k of every batch is flipped, turned and jittered the same way."""
+    row_ids = arange(B) and a fixed epoch, pose k of every batch is flipped, turned and jittered the same way.
+    transform_2d / transform_3d: PoseTransforms applied to the augmented poses in the same launch."""
     if not isinstance(augment, PoseAugment):
         raise TypeError("augment must be a PoseAugment")
     _lib.require_device_tensor(y1, "y1")
@@ -150,8 +176,9 @@ def augment_poses(y1, y2, augment, row_ids=None, epoch=0):
         if row_ids.shape != (nb,):
             raise ValueError("row_ids holds one dataset index per pose")
     oa, ob = torch.empty_like(y1), torch.empty_like(y2)
+    xf, _keep = _transforms(transform_2d, transform_3d, y1.device)
     with _lib.on_device(y1.device):
-        _augment_launch(y1, y2, None, row_ids, nb, nb, oa, ob, augment.struct(), epoch)
+        _augment_launch(y1, y2, None, row_ids, nb, nb, oa, ob, augment.struct(), epoch, xf)
     return oa, ob
 
 
@@ -159,10 +186,13 @@ class PoseFeeder:
     """Iterable of (y1 [b,17,2], y2 [b,17,3]) fp32 device batches over one epoch; call
     set_epoch(e) between epochs (as with DistributedSampler) for a fresh permutation.
     augment: a PoseAugment applied inside the launch that builds the batch, with the epoch of set_epoch and the poses'
-    dataset rows as the identity of the draws (None: the plain gather)."""
+    dataset rows as the identity of the draws (None: the plain gather).
+    transform_2d / transform_3d: PoseTransforms (pose_table) applied to every batch after the augmentation, in the same
+    launch; the tables stay raw.  With a transform and no augmentation the batch is built by the augmented gather with
+    every stage off: a copy plus the transform, still one launch."""
 
     def __init__(self, x2d, y3d, batch_size, *, device="cuda", shuffle=True, seed=0, drop_last=False,
-                 rank=0, world=1, resident=True, prefetch=2, augment=None):
+                 rank=0, world=1, resident=True, prefetch=2, augment=None, transform_2d=None, transform_3d=None):
         x2d, y3d = torch.as_tensor(x2d), torch.as_tensor(y3d)
         if x2d.shape[0] != y3d.shape[0] or x2d.shape[0] == 0:
             raise ValueError("x2d and y3d need the same, non-zero number of poses")
@@ -179,6 +209,15 @@ class PoseFeeder:
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _lib.PoseliftError("PoseFeeder feeds an MI355X (ROCm) device; there is no CPU path")
+        self.transform_2d, self.transform_3d = transform_2d, transform_3d
+        self._xf = self._xf_keep = None
+        if transform_2d is not None or transform_3d is not None:
+            if self.shape_a != (17, 2) or self.shape_b != (17, 3):
+                raise ValueError(f"transforms ride in the augmented gather, defined for (N,17,2)/(N,17,3) tables, got "
+                                 f"{tuple(x2d.shape)} / {tuple(y3d.shape)}")
+            self._xf, self._xf_keep = _transforms(transform_2d, transform_3d, self.device)
+            if self._aug is None:
+                self._aug = PoseAugment().struct()          # every stage off: the kernel copies, then transforms
         a = x2d.reshape(self.n, -1).to(torch.float32).contiguous()        # train_1.py:80 .float()
         b = y3d.reshape(self.n, -1).to(torch.float32).contiguous()
         self.wa, self.wb = a.shape[1], b.shape[1]
@@ -218,7 +257,7 @@ class PoseFeeder:
             with _lib.on_device(self.device):
                 if self._aug is not None:           # the permutation slice is both the source row and the draws' identity
                     idx = idx_all[at:at + nb]
-                    _augment_launch(self.a, self.b, idx, idx, nb, self.n, oa, ob, self._aug, epoch)
+                    _augment_launch(self.a, self.b, idx, idx, nb, self.n, oa, ob, self._aug, epoch, self._xf)
                 else:
                     _lib.check(L.pl_gather_rows2(self.a.data_ptr(), self.wa, self.b.data_ptr(), self.wb,
                                                  idx_all[at:at + nb].data_ptr(), nb, self.n, oa.data_ptr(), ob.data_ptr(),
@@ -271,7 +310,7 @@ class PoseFeeder:
                 nb = di.numel()
                 oa, ob = torch.empty_like(da), torch.empty_like(db)
                 with _lib.on_device(self.device):
-                    _augment_launch(da, db, None, di, nb, nb, oa, ob, self._aug, epoch)
+                    _augment_launch(da, db, None, di, nb, nb, oa, ob, self._aug, epoch, self._xf)
                 da, db = oa, ob
             if nxt < len(batches):
                 inflight.append(launch(nxt, batches[nxt]))
@@ -346,15 +385,16 @@ class FrameFeeder:
     (epoch_indices) and the identity of the draws -- (augment.seed, epoch, dataset row) -- are the same for all three
     tensors.  resident: the table on the device, two launches per batch (poses, frames); else the table in pinned memory,
     batches gathered into pinned staging and copied on a side stream `prefetch` batches ahead, the warp on the consumer's
-    stream behind the copy's event."""
+    stream behind the copy's event.  transform_2d / transform_3d: as in PoseFeeder, on the pose outputs; frames are unchanged."""
 
     def __init__(self, frames, x2d, y3d, batch_size, *, out_hw=(256, 256), augment=None, device="cuda", shuffle=True,
-                 seed=0, drop_last=False, rank=0, world=1, resident=True, prefetch=2):
+                 seed=0, drop_last=False, rank=0, world=1, resident=True, prefetch=2, transform_2d=None, transform_3d=None):
         self._aug = _frame_augment_struct(augment)
         frames = torch.as_tensor(frames)
         self._code, self.out_hw, self._scale, self._fill = _frame_geometry(frames, out_hw, None, 0.0)
         self.poses = PoseFeeder(x2d, y3d, batch_size, device=device, shuffle=shuffle, seed=seed, drop_last=drop_last,
-                                rank=rank, world=world, resident=resident, prefetch=prefetch, augment=augment)
+                                rank=rank, world=world, resident=resident, prefetch=prefetch, augment=augment,
+                                transform_2d=transform_2d, transform_3d=transform_3d)
         if frames.shape[0] != self.poses.n:
             raise ValueError("frames, x2d and y3d need the same number of rows")
         self.device, self.resident, self.prefetch = self.poses.device, resident, self.poses.prefetch

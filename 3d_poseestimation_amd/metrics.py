@@ -10,10 +10,14 @@ the host.
 The reference reports protocol 1 only (train_1.py:19-23,100-104: loss_MPJPE / epoch_mpjpe_mm here).  Definitions and
 degenerate rules: include/poselift.h and DESIGN.md ("Evaluation metrics").  All arithmetic is in libposelift.so; tensors
 that are computed on must live on the ROCm device.
+
+denorm= (a pose_table.PoseTransform): prediction and target are in a model's standardised space and are taken back to the
+raw units as the launch loads them (pl_pose_errors_t), so errors and the P-MPJPE alignment are those of the poses.
 """
 import torch
 
 from . import _lib
+from .pose_table import transform_pair
 
 METRICS = ("mpjpe", "n_mpjpe", "p_mpjpe")
 AUC_THRESHOLDS = tuple(round(0.005 * i, 3) for i in range(31))          # 0 ... 0.150 m
@@ -29,27 +33,33 @@ def _pose_pair(pred, target):
     return pred, target
 
 
-def _errors(pred, target, want_aligned):
+def _errors(pred, target, want_aligned, denorm=None):
     pred, target = _pose_pair(pred, target)
     B, J, _ = target.shape
     err = torch.empty((3, B, J), dtype=torch.float32, device=target.device)
     aligned = torch.empty_like(pred) if want_aligned else None
     with _lib.on_device(target.device):
-        rc = _lib.lib().pl_pose_errors(pred.data_ptr(), target.data_ptr(), B, J, err.data_ptr(),
-                                       aligned.data_ptr() if want_aligned else None, _lib.current_stream_ptr())
+        if denorm is None:
+            rc = _lib.lib().pl_pose_errors(pred.data_ptr(), target.data_ptr(), B, J, err.data_ptr(),
+                                           aligned.data_ptr() if want_aligned else None, _lib.current_stream_ptr())
+        else:
+            sub, div, _keep = transform_pair(denorm, (J, 3), target.device, "denorm")
+            rc = _lib.lib().pl_pose_errors_t(pred.data_ptr(), target.data_ptr(), B, J, sub, div, err.data_ptr(),
+                                             aligned.data_ptr() if want_aligned else None, _lib.current_stream_ptr())
     _lib.check(rc, "pl_pose_errors")
     return err, aligned
 
 
-def pose_errors(pred, target):
+def pose_errors(pred, target, denorm=None):
     """(B, J, 3), (B, J, 3) -> (3, B, J): per pose and joint, [0] ||P - T||, [1] ||s P - T|| with the best scale s,
-    [2] ||a R (P - muP) + muT - T|| with the best proper rotation R and scale a (3 <= J <= 32)."""
-    return _errors(pred, target, False)[0]
+    [2] ||a R (P - muP) + muT - T|| with the best proper rotation R and scale a (3 <= J <= 32).
+    denorm: the PoseTransform whose space both tensors are in; they are inverted as they are loaded."""
+    return _errors(pred, target, False, denorm)[0]
 
 
-def procrustes_align(pred, target):
-    """The prediction after the P-MPJPE alignment, a R (P - muP) + muT, (B, J, 3)."""
-    return _errors(pred, target, True)[1]
+def procrustes_align(pred, target, denorm=None):
+    """The prediction after the P-MPJPE alignment, a R (P - muP) + muT, (B, J, 3); with denorm, in the raw units."""
+    return _errors(pred, target, True, denorm)[1]
 
 
 def summarise(sums, counts, n_poses, thresholds, group_names=None):
@@ -119,10 +129,10 @@ class PoseMetrics:
         for t in (self.sums, self.counts, self.n_poses):
             t.zero_()
 
-    def update(self, pred, target, group_ids=None):
+    def update(self, pred, target, group_ids=None, denorm=None):
         """Adds B poses: two library calls, three launches, no synchronisation.  group_ids: (B,) integer tensor on the
-        device (None: group 0)."""
-        err = pose_errors(pred, target)
+        device (None: group 0).  denorm: as in pose_errors (no further launch)."""
+        err = pose_errors(pred, target, denorm)
         _, B, J = err.shape
         if J != self.joints:
             raise ValueError(f"PoseMetrics was built for {self.joints} joints, got {J}")

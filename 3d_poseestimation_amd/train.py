@@ -11,6 +11,7 @@ import torch
 from torch.autograd.graph import increment_version
 
 from . import _lib, gradclip
+from .pose_table import transform_pair
 
 
 class _MSEFn(torch.autograd.Function):
@@ -47,9 +48,11 @@ def mse_loss(pred, tgt):
     return _MSEFn.apply(pred.contiguous(), tgt.contiguous())
 
 
-def loss_MPJPE(prediction, target, out=None):
+def loss_MPJPE(prediction, target, out=None, denorm=None):
     """train_1.py:19-23: (B,J,3),(B,J,3) -> (J,) sum over the batch of per-joint L2 errors.
-    With `out`, accumulates into it (the reference's `train_metric_3d +=`)."""
+    With `out`, accumulates into it (the reference's `train_metric_3d +=`).
+    denorm: the pose_table.PoseTransform whose space both tensors are in; they are inverted as they are loaded
+    (pl_mpjpe_accum_t; the reference's `* std + mean`, main.py:473-474), so the errors are in the raw units."""
     prediction, target = prediction.detach().contiguous(), target.detach().contiguous()
     _lib.require_device_tensor(prediction, "prediction")
     _lib.require_device_tensor(target, "target")
@@ -59,8 +62,13 @@ def loss_MPJPE(prediction, target, out=None):
     metric = out if out is not None else torch.zeros(J, dtype=torch.float32, device=target.device)
     scratch = torch.empty(_lib.lib().pl_mpjpe_scratch_bytes(B, J), dtype=torch.uint8, device=target.device)
     with _lib.on_device(target.device):
-        rc = _lib.lib().pl_mpjpe_accum(prediction.data_ptr(), target.data_ptr(), B, J, metric.data_ptr(),
-                                       scratch.data_ptr(), _lib.current_stream_ptr())
+        if denorm is None:
+            rc = _lib.lib().pl_mpjpe_accum(prediction.data_ptr(), target.data_ptr(), B, J, metric.data_ptr(),
+                                           scratch.data_ptr(), _lib.current_stream_ptr())
+        else:
+            sub, div, _keep = transform_pair(denorm, (J, 3), target.device, "denorm")
+            rc = _lib.lib().pl_mpjpe_accum_t(prediction.data_ptr(), target.data_ptr(), B, J, sub, div, metric.data_ptr(),
+                                             scratch.data_ptr(), _lib.current_stream_ptr())
     _lib.check(rc, "pl_mpjpe_accum")
     return metric
 
@@ -394,17 +402,24 @@ def predict_flip_tta(model, y1, out_dims=3):
 
 
 @torch.no_grad()
-def eval_step(model, y1, y2, metric_out=None, flip=False, meter=None, group_ids=None):
+def eval_step(model, y1, y2, metric_out=None, flip=False, meter=None, group_ids=None, denorm=None):
     """train_1.py:112-145 body (model must be in eval mode): forward, MSE, loss_MPJPE.
     flip=True: flip test-time augmentation (predict_flip_tta).
     meter: a metrics.PoseMetrics that also takes this batch (P-MPJPE, N-MPJPE, PCK; group_ids (B,) = e.g. the action of
-    each pose); like everything here it only enqueues work."""
+    each pose); like everything here it only enqueues work.
+    denorm: the pose_table.PoseTransform of the 3-D targets (y2 and the model's output are in its space).  The MSE stays
+    in the model's space, as the reference's loss does; `metric` and the meter are in the raw units, both tensors inverted
+    inside the launches that read them (no launch more than without).  y2_hat is returned as the model gave it."""
+    if flip and denorm is not None:
+        raise ValueError("eval_step: flip=True mirrors image-normalised poses and cannot run on transformed ones; compose it: "
+                         "a = model(T2.apply(raw2d)), b = model(T2.apply(flip_pose(raw2d))), then "
+                         "flip_average(T3.invert(b), T3.invert(a)) is the prediction in raw units")
     y1, y2 = y1.float(), y2.float()
     y2_hat = predict_flip_tta(model, y1, y2.shape[-1]).reshape(y2.shape) if flip else model(y1).reshape(y2.shape)
     loss = mse_loss(y2_hat, y2)
-    metric = loss_MPJPE(y2_hat, y2, out=metric_out)
+    metric = loss_MPJPE(y2_hat, y2, out=metric_out, denorm=denorm)
     if meter is not None:
-        meter.update(y2_hat, y2, group_ids)
+        meter.update(y2_hat, y2, group_ids, denorm=denorm)
     return loss, metric, y2_hat
 
 

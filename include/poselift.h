@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define PL_VERSION 115 /* 0.1.15: + PLFrameWarp, pl_frame_warp_gather, pl_frame_warp_host (frame gather + resize + the pose augmentation's warp in one launch); 0.1.14: + PLPoseAug, pl_pose_augment_gather, pl_pose_augment_host (seeded train-time pose augmentation inside the batch gather); 0.1.13: + PLClipRecord, pl_grad_norm_scratch_bytes, pl_grad_norm_clip, pl_adamw_flat_clip, pl_adamw_flat_dev_clip, pl_adamw_flat_planes_clip (gradient-norm clipping and non-finite skip on the device); 0.1.12: + pl_pose_errors, pl_pose_errors_host, pl_pose_metrics_scratch_bytes, pl_pose_metrics_accum (evaluation: MPJPE / N-MPJPE / P-MPJPE, PCK counts, per group); 0.1.11: + pl_vit_*_bf16, pl_vit_bf16_pack (MyViT "bf16p": bf16 operand carriers written by their producers); 0.1.10: + pl_vit_* (the MyViT transformer lifter); 0.1.9: + pl_conv2d_planes_fwd_hw, pl_conv2d_planes_wgrad_hw (the stem on the planes GEMM); 0.1.8: + pl_lifter_train_step, pl_lifter_step_carries_adamw; 0.1.7: + pl_workspace_bitmap_format (small-batch layer kernels); 0.1.6: + pl_counter_add; 0.1.5: + pl_flip_pose_ex, pl_flip_w_nhwc (phase5 Flip branch); 0.1.4: + pl_planes_split_strided; 0.1.3: + pl_bn_join_bwd (0.1.2: operand-plane outputs of the BatchNorm / join kernels, pl_gemm_planes_raw) */
+#define PL_VERSION 116 /* 0.1.16: + pl_pose_prepare, pl_pose_stats, pl_pose_affine and their _host forms, pl_pose_stats_scratch_bytes, pl_pose_stats_chunk_rows, pl_pose_augment_gather_t, pl_pose_augment_host_t, pl_pose_errors_t, pl_mpjpe_accum_t (pose tables: prepare, statistics, the per-column transform and its way back inside the batch, error and metric launches); 0.1.15: + PLFrameWarp, pl_frame_warp_gather, pl_frame_warp_host (frame gather + resize + the pose augmentation's warp in one launch); 0.1.14: + PLPoseAug, pl_pose_augment_gather, pl_pose_augment_host (seeded train-time pose augmentation inside the batch gather); 0.1.13: + PLClipRecord, pl_grad_norm_scratch_bytes, pl_grad_norm_clip, pl_adamw_flat_clip, pl_adamw_flat_dev_clip, pl_adamw_flat_planes_clip (gradient-norm clipping and non-finite skip on the device); 0.1.12: + pl_pose_errors, pl_pose_errors_host, pl_pose_metrics_scratch_bytes, pl_pose_metrics_accum (evaluation: MPJPE / N-MPJPE / P-MPJPE, PCK counts, per group); 0.1.11: + pl_vit_*_bf16, pl_vit_bf16_pack (MyViT "bf16p": bf16 operand carriers written by their producers); 0.1.10: + pl_vit_* (the MyViT transformer lifter); 0.1.9: + pl_conv2d_planes_fwd_hw, pl_conv2d_planes_wgrad_hw (the stem on the planes GEMM); 0.1.8: + pl_lifter_train_step, pl_lifter_step_carries_adamw; 0.1.7: + pl_workspace_bitmap_format (small-batch layer kernels); 0.1.6: + pl_counter_add; 0.1.5: + pl_flip_pose_ex, pl_flip_w_nhwc (phase5 Flip branch); 0.1.4: + pl_planes_split_strided; 0.1.3: + pl_bn_join_bwd (0.1.2: operand-plane outputs of the BatchNorm / join kernels, pl_gemm_planes_raw) */
 
 typedef enum PLStatus {
   PL_OK = 0,
@@ -376,7 +376,7 @@ int pl_gather_rows2(const float* a, int64_t wa, const float* b, int64_t wb, cons
  * the batch or the rank -- on a key tagged apart from the dropout stream. */
 typedef struct PLPoseAug {
   float p_flip;       /* probability of the horizontal flip: <= 0 never, >= 1 always */
-  float flip_offset;  /* 2-D flip is x -> flip_offset - x: 1 for image-normalised x (utils.py:391), 0 for zero-mean inputs */
+  float flip_offset;  /* 2-D flip is x -> flip_offset - x: 1 for image-normalised x (utils.py:391); augment raw poses and standardise behind it (pl_pose_augment_gather_t) */
   float max_rot;      /* rotation angle uniform in [-max_rot, max_rot) radians */
   float scale_range;  /* 2-D scale uniform in [1 - scale_range, 1 + scale_range); < 1 */
   float max_shift;    /* 2-D translation (tx, ty), each uniform in [-max_shift, max_shift) */
@@ -393,6 +393,60 @@ int pl_pose_augment_gather(const float* a, const float* b, const int64_t* src_id
                            int64_t table_rows, float* oa, float* ob, const PLPoseAug* aug, uint64_t epoch, void* stream);
 int pl_pose_augment_host(const float* a, const float* b, const int64_t* src_idx, const int64_t* row_id, int64_t n,
                          int64_t table_rows, float* oa, float* ob, const PLPoseAug* aug, uint64_t epoch);
+
+/* pl_pose_augment_gather with two nullable per-column transforms (pose tables, below), applied to each output element
+ * AFTER the augmentation: oa's 34 columns become (v - sub_a[c]) / div_a[c], ob's 51 (v - sub_b[c]) / div_b[c]; a column
+ * with div == 0 becomes 0.  Tables stay raw, so flip, rotation, scale, shift and jitter keep their image units, and the
+ * batch leaves standardised in the same launch.  A transform is a (sub, div) pair of device (host: _host_t) arrays; with
+ * both pairs NULL the call is pl_pose_augment_gather, the same kernel instantiation.  The NaN pose of a bad source index goes
+ * through the transform like any value. */
+int pl_pose_augment_gather_t(const float* a, const float* b, const int64_t* src_idx, const int64_t* row_id, int64_t n,
+                             int64_t table_rows, float* oa, float* ob, const PLPoseAug* aug, uint64_t epoch,
+                             const float* sub_a, const float* div_a, const float* sub_b, const float* div_b, void* stream);
+int pl_pose_augment_host_t(const float* a, const float* b, const int64_t* src_idx, const int64_t* row_id, int64_t n,
+                           int64_t table_rows, float* oa, float* ob, const PLPoseAug* aug, uint64_t epoch,
+                           const float* sub_a, const float* div_a, const float* sub_b, const float* div_b);
+
+/* ---- pose tables: prepare, statistics, the per-column transform (csrc/pose_table.h has the definitions) ---------------
+ * What the reference does per frame and per joint in Python before training and undoes before it measures
+ * (phase3_direct/my_HybrIK/H36_dataset.py:303-379 read_data, :205-300 process_data; phase1_lifting/main.py:473-474).
+ *
+ * pl_pose_prepare: raw [N][Jsrc][D] fp32 (D in {2, 3}, 1 <= Jsrc <= 64) -> out [N][J][D] (1 <= J <= 32), stages in the
+ * reference's order, a stage that is off not run at all:
+ *   pick        out[n][j] = raw[n][pick[j]]; pick: HOST int32 [J] or NULL (then J == Jsrc).  An index outside [0, Jsrc)
+ *               is PL_ESHAPE and nothing is launched.                                                      (:335)
+ *   camera view D = 3, on when cameras != NULL (cam_id then too; with D = 2: PL_ESHAPE).  cameras [C][7] fp64 =
+ *               (t0, t1, t2, w, x, y, z): translation in the poses' units (the caller divides millimetres by 1000) and
+ *               the orientation quaternion; cam_id [N] int32.  v = q (0, (double)p - t) q*, both Hamilton products term
+ *               by term in utils.py:328-335's order, fp64, no contraction, rounded to fp32 once.  A cam_id outside
+ *               [0, C) reads no camera and makes every element of that row NaN.                            (:357-360)
+ *   zero_centre joints 1..J-1 minus joint 0 in fp32; joint 0 becomes +0.                                  (:209-211, :288-289)
+ * out may not overlap raw.  One launch.
+ *
+ * pl_pose_stats: x [N][W] fp32, W = J D <= 96 -> out [4][W] fp64 on the device: mean, std (population, two passes about
+ * the mean: sqrt(sum (x - mean)^2 / N), :215-222), min, max.  fp64 accumulation, no atomics, four launches, nothing on
+ * the host in between; every sum in an order that depends on (N, W) alone (chunks of pl_pose_stats_chunk_rows() rows),
+ * so the same table gives the same bits on every run and stream.  A NaN makes all four values of its column NaN and no
+ * other column's; +inf gives mean = max = inf, std = NaN (numpy's answers).  A constant column (min == max) has mean =
+ * that value exactly and std = +0.  scratch >= pl_pose_stats_scratch_bytes(N, W), 8-byte aligned.
+ *
+ * pl_pose_affine: x [N][W] -> y [N][W], per column (sub[c], div[c]) fp32.  invert = 0: y = (x - sub) / div, a correctly
+ * rounded division (:272, :283; normalisation :269, :279-280 are the same form).  invert != 0: x = y div + sub, two
+ * roundings (main.py:473-474).  A column with div == 0 applies to 0 and inverts to sub -- the zeroed root joint and any
+ * constant column; the reference keeps 0/0 = NaN there.  y == x (in place) is allowed, any other overlap is PL_EINVAL.
+ *
+ * The _host forms run the same inline text on host pointers (test hooks). */
+int pl_pose_prepare(const float* raw, int64_t N, int64_t Jsrc, int64_t D, const int32_t* pick_or_null, int64_t J,
+                    const int32_t* cam_id_or_null, const double* cameras_or_null, int64_t C, int zero_centre, float* out,
+                    void* stream);
+int pl_pose_prepare_host(const float* raw, int64_t N, int64_t Jsrc, int64_t D, const int32_t* pick_or_null, int64_t J,
+                         const int32_t* cam_id_or_null, const double* cameras_or_null, int64_t C, int zero_centre, float* out);
+int64_t pl_pose_stats_chunk_rows(void);
+size_t pl_pose_stats_scratch_bytes(int64_t N, int64_t W);
+int pl_pose_stats(const float* x, int64_t N, int64_t W, double* out /* [4][W] */, void* scratch, void* stream);
+int pl_pose_stats_host(const float* x, int64_t N, int64_t W, double* out);
+int pl_pose_affine(const float* x, int64_t N, int64_t W, const float* sub, const float* div, int invert, float* y, void* stream);
+int pl_pose_affine_host(const float* x, int64_t N, int64_t W, const float* sub, const float* div, int invert, float* y);
 
 /* The frames of the same rows, gathered, resized, normalised and augmented in one launch (csrc/frame_warp.h has the
  * definition; the reference resizes per sample on the host, H36_dataset.py:129-131 `cv2.resize(frame,(256,256))`,
@@ -465,6 +519,11 @@ int pl_l1_terms_fwd_bwd(const PLL1Term* terms, int nterms, float grad_scale, flo
 size_t pl_mpjpe_scratch_bytes(int64_t B, int64_t joints);
 int pl_mpjpe_accum(const float* pred, const float* tgt, int64_t B, int64_t joints,
                    float* metric, void* scratch, void* stream);
+/* The same on tensors in a model's space: with (sub, div) [3 joints] given (joints <= 32), prediction and target are taken
+ * back as they are loaded, x = y div[c] + sub[c] (pl_pose_affine's inverse, its div == 0 rule included), so the metric is
+ * in the raw units.  Both NULL: pl_mpjpe_accum, the same kernel instantiation. */
+int pl_mpjpe_accum_t(const float* pred, const float* tgt, int64_t B, int64_t joints, const float* sub_or_null,
+                     const float* div_or_null, float* metric, void* scratch, void* stream);
 
 /* ---- evaluation: MPJPE, N-MPJPE, P-MPJPE per pose and joint; sums and PCK counts per group --------------------------
  * The reference reports protocol-1 MPJPE only (train_1.py:19-23,100-104); these are the other columns of the usual
@@ -482,6 +541,11 @@ int pl_mpjpe_accum(const float* pred, const float* tgt, int64_t B, int64_t joint
 int pl_pose_errors(const float* pred, const float* tgt, int64_t B, int64_t J, float* err /* [3][B][J] */,
                    float* aligned_or_null, void* stream);
 int pl_pose_errors_host(const float* pred, const float* tgt, int64_t B, int64_t J, float* err, float* aligned_or_null);
+/* pl_pose_errors on tensors in a model's space: with (sub, div) [3 J] given, prediction and target are taken back as they
+ * are loaded, x = y div[c] + sub[c] (pl_pose_affine's inverse), so errors, alignment and the aligned pose are those of the
+ * raw poses.  Both NULL: pl_pose_errors, the same kernel instantiation. */
+int pl_pose_errors_t(const float* pred, const float* tgt, int64_t B, int64_t J, const float* sub_or_null,
+                     const float* div_or_null, float* err /* [3][B][J] */, float* aligned_or_null, void* stream);
 /* Accumulate err [3][B][J] (pl_pose_errors) into per-group totals, in place:
  *   sums   [G][3][J]     fp32   += sum of errors of the poses of group g
  *   counts [G][3][T][J]  int64  += number of those errors <= thr[t] (inclusive)        (may be NULL when n_thr = 0)
