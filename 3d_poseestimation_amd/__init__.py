@@ -12,6 +12,7 @@ from .train import (cycle_step, epoch_mpjpe_mm, eval_step, flip_average, flip_fr
 from .heads import (gaussian_heatmap, heatmap_law, soft_argmax_2d, soft_argmax_2d_hm, soft_argmax_3d,  # noqa: F401
                     soft_argmax_3d_hm, soft_argmax_3d_nhwc, soft_argmax_3d_nhwc_hm)
 from .losses import TriangleLoss, heatmap_mse, l1_loss, l1_terms  # noqa: F401
+from .criterion import PoseCriterion  # noqa: F401
 from .metrics import AUC_THRESHOLDS, PoseMetrics, pose_errors, procrustes_align  # noqa: F401
 from .backbone import Model_2D, Model_3D, ResNet  # noqa: F401
 from .data import FrameFeeder, PoseAugment, PoseFeeder, augment_frames, augment_poses, epoch_indices  # noqa: F401

@@ -63,6 +63,13 @@ class PLAdamWStep(ctypes.Structure):
                 ("t", ctypes.c_int64), ("t_dev", ctypes.c_void_p)]
 
 
+CRIT_MSE, CRIT_L1, CRIT_SMOOTH_L1, CRIT_MPJPE = 0, 1, 2, 3
+
+
+class PLCriterion(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int32), ("group", ctypes.c_int32), ("beta", ctypes.c_float), ("weights", ctypes.c_void_p)]
+
+
 class PLClipRecord(ctypes.Structure):
     _fields_ = [("norm", ctypes.c_float), ("coef", ctypes.c_float), ("finite", ctypes.c_uint32), ("skip", ctypes.c_uint32),
                 ("skipped", ctypes.c_uint64)]
@@ -125,6 +132,12 @@ SIGNATURES = {
     "pl_lifter_step_carries_adamw": (_c.c_int, [_D, _c.c_int64]),
     "pl_lifter_train_step": (_c.c_int, [_D, _P, _P, _c.c_int64, _P, _c.c_size_t, _c.c_uint64, _c.c_uint64,
                                         _P, _P, _P, _c.POINTER(PLAdamWStep), _P]),
+    "pl_lifter_train_fwd_bwd_crit": (_c.c_int, [_D, _P, _P, _c.c_int64, _P, _c.c_size_t, _c.c_uint64, _c.c_uint64,
+                                                _c.POINTER(PLCriterion), _P, _P, _P, _c.c_int, _c.c_int, _P]),
+    "pl_lifter_train_step_crit": (_c.c_int, [_D, _P, _P, _c.c_int64, _P, _c.c_size_t, _c.c_uint64, _c.c_uint64,
+                                             _c.POINTER(PLCriterion), _P, _P, _P, _c.POINTER(PLAdamWStep), _P]),
+    "pl_pose_loss_scratch_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int64, _c.POINTER(PLCriterion)]),
+    "pl_pose_loss_fwd_bwd": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _c.POINTER(PLCriterion), _c.c_float, _P, _P, _P, _P]),
     "pl_mse_scratch_bytes": (_c.c_size_t, [_c.c_int64]),
     "pl_mse_fwd_bwd": (_c.c_int, [_P, _P, _c.c_int64, _c.c_float, _P, _P, _P, _P]),
     "pl_l1_scratch_bytes": (_c.c_size_t, [_c.c_int]),

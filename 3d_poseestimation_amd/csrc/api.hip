@@ -778,6 +778,7 @@ struct BwdCtx {
   bool top_fused;               // the output layer and the top hidden layer's BatchNorm backward in one launch (dz of that layer: DZ)
   float* loss_out;              // the fused train step: the loss is finalised by a launch of this range
   int n_loss_part;              //   ... from this many partial sums in w.mse
+  float loss_inv_n;             //   ... times this (1 / (B O); the mpjpe criterion: 1 / (B J))
   // the AdamW step carried by the backward launches (pl_lifter_train_step) or run behind them
   const PLAdamWStep* adam;
   bool adam_rides;
@@ -844,7 +845,7 @@ int bwd_output(BwdCtx& c) {
     SmallTopBwdArgs a = {};
     a.dy = c.dy; a.W2 = W2; a.h = h; a.B = Bi; a.H = H; a.O = O; a.gout = c.GA(); a.dW2 = gW2; a.db2 = gb2;
     a.top = c.bn_layer(w.L - 1); a.kscale = c.kscale; a.dz_top = c.DZ();
-    a.mpart = c.buf(w.mse); a.np = c.n_loss_part; a.inv_n = 1.0f / (float)((int64_t)Bi * O); a.loss = c.loss_out;
+    a.mpart = c.buf(w.mse); a.np = c.n_loss_part; a.inv_n = c.loss_inv_n; a.loss = c.loss_out;
     a.tick = const_cast<uint64_t*>(c.d->step_dev);
     return launch_small_top_bwd(a, c.s);
   }
@@ -1031,7 +1032,7 @@ int bwd_layer_linear(BwdCtx& c, int l) {
 // mse_final_kernel's sum) and the device step counter ticks there, instead of in a launch of their own after the forward.
 static int bwd_impl(const PLDesc* d, const float* x, const float* dy, int64_t B, void* ws, size_t ws_bytes,
                     float* dx, float* grads, void* stream, bool do_output, int l_hi, int l_lo, bool eval_bn = false,
-                    float* loss_out = nullptr, int loss_partials = 0, const PLAdamWStep* adam = nullptr) {
+                    float* loss_out = nullptr, int n_loss_part = 0, float loss_inv_n = 0.f, const PLAdamWStep* adam = nullptr) {
   PL_TRY(check_desc(d, true));
   if (!x || !dy || !grads) PL_FAIL(PL_EINVAL, "pl_lifter_bwd: null x/dy/flat_grads");
   if (B <= 0) PL_FAIL(PL_ESHAPE, "pl_lifter_bwd: B=%lld", (long long)B);
@@ -1045,7 +1046,8 @@ static int bwd_impl(const PLDesc* d, const float* x, const float* dy, int64_t B,
   c.sl = !eval_bn && w.small_layer;
   c.top_fused = do_output && !eval_bn && w.top_fused && l_hi == w.L - 1 && l_hi >= l_lo;
   c.loss_out = loss_out;
-  c.n_loss_part = loss_partials > 0 ? loss_partials : mse_partials(B * c.O);   // partial sums of the loss in w.mse
+  c.n_loss_part = n_loss_part;                   // partial sums of the loss in w.mse, their sum times loss_inv_n = the loss
+  c.loss_inv_n = loss_inv_n;
   c.adam = adam;
   c.adam_rides = adam && c.top_fused && l_lo == 0 && w.adam_rides;
   if (do_output) PL_TRY(bwd_output(c));
@@ -1057,7 +1059,7 @@ static int bwd_impl(const PLDesc* d, const float* x, const float* dy, int64_t B,
   uint64_t* tick = nullptr;
   if (loss_out && !c.top_fused) {
     c.job(f32(ws, w.mse), loss_out, c.n_loss_part, 1, 2, 0);
-    inv_n = 1.0f / (float)(B * c.O);
+    inv_n = loss_inv_n;
     tick = const_cast<uint64_t*>(d->step_dev);
   }
   if (!c.jobs.empty()) PL_TRY(launch_reduce_rows_multi(c.jobs.data(), (int)c.jobs.size(), inv_n, tick, c.s));
@@ -1383,13 +1385,18 @@ extern "C" int pl_prof_read(double min_flops, double max_flops, double* ms_total
 // fused train step: forward (training mode) + MSE(mean) + backward in one call
 // ---------------------------------------------------------------------------------------
 static int train_fwd_bwd_impl(const PLDesc* d, const float* x, const float* target, int64_t B, void* ws, size_t ws_bytes,
-                              uint64_t seed, uint64_t step, float* y, float* loss, float* grads, int hi, int lo, void* stream,
-                              const PLAdamWStep* adam);
+                              uint64_t seed, uint64_t step, const PLCriterion* crit, float* y, float* loss, float* grads, int hi,
+                              int lo, void* stream, const PLAdamWStep* adam);
 
+extern "C" int pl_lifter_train_fwd_bwd_crit(const PLDesc* d, const float* x, const float* target, int64_t B, void* ws,
+                                            size_t ws_bytes, uint64_t seed, uint64_t step, const PLCriterion* crit, float* y,
+                                            float* loss, float* grads, int hi, int lo, void* stream) {
+  return train_fwd_bwd_impl(d, x, target, B, ws, ws_bytes, seed, step, crit, y, loss, grads, hi, lo, stream, nullptr);
+}
 extern "C" int pl_lifter_train_fwd_bwd(const PLDesc* d, const float* x, const float* target, int64_t B, void* ws,
                                        size_t ws_bytes, uint64_t seed, uint64_t step, float* y, float* loss,
                                        float* grads, int hi, int lo, void* stream) {
-  return train_fwd_bwd_impl(d, x, target, B, ws, ws_bytes, seed, step, y, loss, grads, hi, lo, stream, nullptr);
+  return pl_lifter_train_fwd_bwd_crit(d, x, target, B, ws, ws_bytes, seed, step, nullptr, y, loss, grads, hi, lo, stream);
 }
 
 extern "C" int pl_lifter_step_carries_adamw(const PLDesc* d, int64_t B) {
@@ -1397,29 +1404,39 @@ extern "C" int pl_lifter_step_carries_adamw(const PLDesc* d, int64_t B) {
   return B > 0 && plan(d, B).adam_rides ? 1 : 0;
 }
 
-extern "C" int pl_lifter_train_step(const PLDesc* d, const float* x, const float* target, int64_t B, void* ws, size_t ws_bytes,
-                                    uint64_t seed, uint64_t step, float* y, float* loss, float* grads, const PLAdamWStep* opt,
-                                    void* stream) {
+extern "C" int pl_lifter_train_step_crit(const PLDesc* d, const float* x, const float* target, int64_t B, void* ws,
+                                         size_t ws_bytes, uint64_t seed, uint64_t step, const PLCriterion* crit, float* y,
+                                         float* loss, float* grads, const PLAdamWStep* opt, void* stream) {
   if (!opt || !opt->m || !opt->v || (opt->lr_dev != nullptr) != (opt->t_dev != nullptr) || opt->t < (opt->t_dev ? 0 : 1))
     PL_FAIL(PL_EINVAL, "pl_lifter_train_step: bad optimizer description");
   if (!d) PL_FAIL(PL_EINVAL, "descriptor is NULL");
-  return train_fwd_bwd_impl(d, x, target, B, ws, ws_bytes, seed, step, y, loss, grads, 1 + 2 * d->num_stage, 0, stream, opt);
+  return train_fwd_bwd_impl(d, x, target, B, ws, ws_bytes, seed, step, crit, y, loss, grads, 1 + 2 * d->num_stage, 0, stream, opt);
+}
+extern "C" int pl_lifter_train_step(const PLDesc* d, const float* x, const float* target, int64_t B, void* ws, size_t ws_bytes,
+                                    uint64_t seed, uint64_t step, float* y, float* loss, float* grads, const PLAdamWStep* opt,
+                                    void* stream) {
+  return pl_lifter_train_step_crit(d, x, target, B, ws, ws_bytes, seed, step, nullptr, y, loss, grads, opt, stream);
 }
 
 static int train_fwd_bwd_impl(const PLDesc* d, const float* x, const float* target, int64_t B, void* ws, size_t ws_bytes,
-                              uint64_t seed, uint64_t step, float* y, float* loss, float* grads, int hi, int lo, void* stream,
-                              const PLAdamWStep* adam) {
+                              uint64_t seed, uint64_t step, const PLCriterion* crit, float* y, float* loss, float* grads, int hi,
+                              int lo, void* stream, const PLAdamWStep* adam) {
   PL_TRY(check_desc(d, true));
   if (!x || !target || !y || !loss || !grads) PL_FAIL(PL_EINVAL, "pl_lifter_train_fwd_bwd: null pointer");
   if (B <= 0) PL_FAIL(PL_ESHAPE, "pl_lifter_train_fwd_bwd: B=%lld", (long long)B);
   PL_TRY(check_range(d, hi, lo, "pl_lifter_train_fwd_bwd"));
+  Crit cr;
+  PL_TRY(crit_resolve(crit, d->out_dim, cr, "pl_lifter_train_fwd_bwd"));
   const Ws w = plan(d, B);
   PL_TRY(check_ws(w, ws, ws_bytes));
   float* dy = f32(ws, w.dyout);
   const int L = 1 + 2 * d->num_stage;
+  // the partial sums the loss pass of this route leaves in w.mse, and what their sum is multiplied by
+  const int n_part = w.loss == Loss::SmallMse ? small_loss_partials(cr, (int)B, d->out_dim)
+                     : w.loss == Loss::FromSlabs ? loss_partials(Crit{}, B, d->out_dim) : loss_partials(cr, B, d->out_dim);
   if (hi == L && w.loss == Loss::PartialOnly) {
     PL_TRY(pl_lifter_fwd_train(d, x, y, B, ws, ws_bytes, seed, step, nullptr, stream));
-    PL_TRY(mse_partial_only(y, target, B * d->out_dim, 1.0f, dy, f32(ws, w.mse), stream));
+    PL_TRY(loss_partial_only(y, target, B, d->out_dim, cr, 1.0f, dy, f32(ws, w.mse), stream, "pl_lifter_train_fwd_bwd"));
   } else if (hi == L) {
     // the forward leaves the output Linear's slabs, the MSE pass adds them up
     const int H = d->hidden, O = d->out_dim;
@@ -1428,12 +1445,12 @@ static int train_fwd_bwd_impl(const PLDesc* d, const float* x, const float* targ
     if (w.loss == Loss::SmallMse) {
       SmallHeadArgs h = {};
       h.ypart = f32(ws, w.slabs); h.NS = H / 16; h.B = (int)B; h.O = O; h.bias = bias; h.y = y;
-      h.tgt = target; h.grad_scale = 1.0f; h.dpred = dy; h.mpart = f32(ws, w.mse);
+      h.tgt = target; h.grad_scale = 1.0f; h.dpred = dy; h.mpart = f32(ws, w.mse); h.crit = cr;
       PL_TRY(launch_small_mse(h, (hipStream_t)stream));
     } else
-      PL_TRY(mse_partial_from_slabs(f32(ws, w.slabs), skinny_narrow_out_splits((int)B, H), (int)B, O, bias, target, 1.0f, y, dy,
-                                    f32(ws, w.mse), stream));
+      PL_TRY(loss_partial_from_slabs(f32(ws, w.slabs), skinny_narrow_out_splits((int)B, H), (int)B, O, bias, target, cr, 1.0f, y,
+                                     dy, f32(ws, w.mse), stream));
   }
   return bwd_impl(d, x, dy, B, ws, ws_bytes, nullptr, grads, stream, hi == L, hi == L ? L - 1 : hi, lo, false,
-                  hi == L ? loss : nullptr, w.loss == Loss::SmallMse ? small_mse_partials((int)B, d->out_dim) : 0, adam);
+                  hi == L ? loss : nullptr, n_part, crit_inv_n(cr, B * d->out_dim), adam);
 }

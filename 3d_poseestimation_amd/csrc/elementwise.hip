@@ -1125,30 +1125,69 @@ __global__ void fill_kernel(float* p, int64_t n, float v) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) p[i] = v;
 }
 
-// ---- MSE(mean) forward + backward ---------------------------------------------------------
+// ---- the criterion (mean) forward + backward: MSE, and the other pointwise kinds of pose_criterion.h ------------------------
+// C: the criterion type, W: per-joint weights (k.w[(i mod O) / G]).  <Pointwise<PL_CRIT_MSE>, false> is the MSE kernel as
+// it always was: d, fmaf(d, d, acc), d * coef, block_sum.
+template <class C, bool W>
 __global__ __launch_bounds__(NTHR) void mse_partial_kernel(const float* __restrict__ pred,
                                                            const float* __restrict__ tgt, int64_t n,
-                                                           float coef, float* __restrict__ dpred,
+                                                           CritK k, float* __restrict__ dpred,
                                                            float* __restrict__ part) {
   __shared__ float sm[4];
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   float acc = 0.f;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     const float d = pred[i] - tgt[i];
-    acc = fmaf(d, d, acc);
-    if (dpred) dpred[i] = d * coef;
+    if constexpr (W) {
+      const float w = k.w[(int)(i % k.O) / k.G];
+      acc = C::add_w(acc, d, w, k);
+      if (dpred) dpred[i] = C::grad(d, k) * w;
+    } else {
+      acc = C::add(acc, d, k);
+      if (dpred) dpred[i] = C::grad(d, k);
+    }
   }
   const float t = block_sum(acc, sm);
   if (threadIdx.x == 0) part[blockIdx.x] = t;
 }
 
+// The grouped kind (mpjpe) has an element map of its own: a thread takes whole joints -- the G coordinates of joint i are
+// elements i G .. i G + G - 1 of the flat [B][O] tensors -- so no joint is shared between threads, let alone workgroups.
+// nj = B J joints, J joints per row (the weight of joint i is k.w[i mod J]).
+template <int G, bool W>
+__global__ __launch_bounds__(NTHR) void mpjpe_loss_partial_kernel(const float* __restrict__ pred,
+                                                                  const float* __restrict__ tgt, int64_t nj, int J,
+                                                                  CritK k, float* __restrict__ dpred,
+                                                                  float* __restrict__ part) {
+  __shared__ float sm[4];
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  float acc = 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nj; i += stride) {
+    float p[G], t[G], d[G], g[G];
+#pragma unroll
+    for (int c = 0; c < G; ++c) { p[c] = pred[i * G + c]; t[c] = tgt[i * G + c]; }
+    const float w = W ? k.w[(int)(i % J)] : 1.f;
+#pragma unroll
+    for (int c = 0; c < G; ++c) d[c] = p[c] - t[c];
+    const float r = joint_norm_grad<G>(d, W ? k.coef * w : k.coef, g);
+    acc = W ? fmaf(w, r, acc) : acc + r;
+    if (dpred) {
+#pragma unroll
+      for (int c = 0; c < G; ++c) dpred[i * G + c] = g[c];
+    }
+  }
+  const float tsum = block_sum(acc, sm);
+  if (threadIdx.x == 0) part[blockIdx.x] = tsum;
+}
+
 // mse_partial_kernel with pred[i] formed on the fly from the output Linear's split-K slabs (part[s][r][64 padded columns]) and
 // stored: y[i] = bias[n] + slabs in order -- skinny_narrow_out_reduce_kernel's sum -- then the same d, fmaf and block_sum on the
 // same thread -> element map: y, dpred and the partials equal the two-launch route's bit for bit.  NS slabs, N columns.
-template <int NS, int N>
+// C, W: the criterion and its weights as in mse_partial_kernel (the weight of each element loaded with its slabs).
+template <int NS, int N, class C, bool W>
 __global__ __launch_bounds__(NTHR) void mse_partial_from_slabs_kernel(const float* __restrict__ part, int B,
                                                                       const float* __restrict__ bias,
-                                                                      const float* __restrict__ tgt, float coef,
+                                                                      const float* __restrict__ tgt, CritK k,
                                                                       float* __restrict__ y, float* __restrict__ dpred,
                                                                       float* __restrict__ mpart) {
   __shared__ float sm[4];
@@ -1157,7 +1196,7 @@ __global__ __launch_bounds__(NTHR) void mse_partial_from_slabs_kernel(const floa
   const size_t slab = (size_t)B * 64;
   float acc = 0.f;
   for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i0 < n; i0 += 4 * stride) {
-    float u[4][NS], t[4], bs[4];
+    float u[4][NS], t[4], bs[4], wq[4];
     int64_t idx[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {                       // up to four elements of this thread: every load issued first
@@ -1169,6 +1208,7 @@ __global__ __launch_bounds__(NTHR) void mse_partial_from_slabs_kernel(const floa
       for (int s = 0; s < NS; ++s) u[q][s] = ok ? p[(size_t)s * slab] : 0.f;
       t[q] = ok ? tgt[idx[q]] : 0.f;
       bs[q] = (ok && bias) ? bias[c] : 0.f;
+      if constexpr (W) wq[q] = k.w[c / k.G];
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -1178,8 +1218,68 @@ __global__ __launch_bounds__(NTHR) void mse_partial_from_slabs_kernel(const floa
       for (int s = 0; s < NS; ++s) a += u[q][s];
       y[idx[q]] = a;
       const float d = a - t[q];
-      acc = fmaf(d, d, acc);
-      dpred[idx[q]] = d * coef;
+      if constexpr (W) {
+        acc = C::add_w(acc, d, wq[q], k);
+        dpred[idx[q]] = C::grad(d, k) * wq[q];
+      } else {
+        acc = C::add(acc, d, k);
+        dpred[idx[q]] = C::grad(d, k);
+      }
+    }
+  }
+  const float tsum = block_sum(acc, sm);
+  if (threadIdx.x == 0) mpart[blockIdx.x] = tsum;
+}
+
+// The grouped kind on the slabs, with its own element map: a thread takes whole joints (two per pass; the 2 G NS slab
+// loads, the targets, the biases and the weights all issued before the first add), y[i] = bias + slabs in the same order.
+template <int NS, int N, int G, bool W>
+__global__ __launch_bounds__(NTHR) void mpjpe_partial_from_slabs_kernel(const float* __restrict__ part, int B,
+                                                                        const float* __restrict__ bias,
+                                                                        const float* __restrict__ tgt, CritK k,
+                                                                        float* __restrict__ y, float* __restrict__ dpred,
+                                                                        float* __restrict__ mpart) {
+  static_assert(N % G == 0, "whole joints per row");
+  constexpr int J = N / G, Q = 2;
+  __shared__ float sm[4];
+  const int64_t nj = (int64_t)B * J;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const size_t slab = (size_t)B * 64;
+  float acc = 0.f;
+  for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i0 < nj; i0 += Q * stride) {
+    float u[Q][G][NS], t[Q][G], bs[Q][G], wq[Q];
+    int64_t idx[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+      idx[q] = i0 + q * stride;
+      const bool ok = idx[q] < nj;
+      const int r = ok ? (int)(idx[q] / J) : 0, j = ok ? (int)(idx[q] - (int64_t)r * J) : 0;
+      const float* p = part + (size_t)r * 64 + j * G;
+#pragma unroll
+      for (int c = 0; c < G; ++c) {
+#pragma unroll
+        for (int s = 0; s < NS; ++s) u[q][c][s] = ok ? p[(size_t)s * slab + c] : 0.f;
+        t[q][c] = ok ? tgt[idx[q] * G + c] : 0.f;
+        bs[q][c] = (ok && bias) ? bias[j * G + c] : 0.f;
+      }
+      wq[q] = W ? k.w[j] : 1.f;
+    }
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+      if (idx[q] >= nj) continue;
+      float d[G], g[G];
+#pragma unroll
+      for (int c = 0; c < G; ++c) {
+        float a = bs[q][c];
+#pragma unroll
+        for (int s = 0; s < NS; ++s) a += u[q][c][s];
+        y[idx[q] * G + c] = a;
+        d[c] = a - t[q][c];
+      }
+      const float r = joint_norm_grad<G>(d, W ? k.coef * wq[q] : k.coef, g);
+      acc = W ? fmaf(wq[q], r, acc) : acc + r;
+#pragma unroll
+      for (int c = 0; c < G; ++c) dpred[idx[q] * G + c] = g[c];
     }
   }
   const float tsum = block_sum(acc, sm);
@@ -1786,56 +1886,120 @@ static int mse_blocks(int64_t n) {
 
 extern "C" size_t pl_mse_scratch_bytes(int64_t n) { return (size_t)mse_blocks(n > 0 ? n : 1) * sizeof(float); }
 
-namespace pl {
-int mse_fwd_bwd_tick(const float* pred, const float* tgt, int64_t n, float grad_scale, float* dpred, float* loss_out,
-                     void* scratch, uint64_t* tick, void* stream);
+int pl::crit_resolve(const PLCriterion* crit, int64_t O, Crit& out, const char* who) {
+  out = Crit{};
+  if (!crit) return PL_OK;
+  if (crit->kind < PL_CRIT_MSE || crit->kind > PL_CRIT_MPJPE) PL_FAIL(PL_EINVAL, "%s: criterion kind %d", who, (int)crit->kind);
+  if (crit->kind == PL_CRIT_SMOOTH_L1 && !(crit->beta > 0.f && crit->beta <= 3.0e38f))
+    PL_FAIL(PL_EINVAL, "%s: smooth_l1 needs a finite beta > 0 (beta = 0 is l1), got %g", who, (double)crit->beta);
+  if (crit->group < 1 || O % crit->group != 0)
+    PL_FAIL(PL_ESHAPE, "%s: %lld outputs are not whole joints of %d coordinates", who, (long long)O, (int)crit->group);
+  if (crit->kind == PL_CRIT_MPJPE && crit->group > kCritMaxGroup)
+    PL_FAIL(PL_ESHAPE, "%s: mpjpe takes joints of at most %d coordinates, got %d", who, kCritMaxGroup, (int)crit->group);
+  out.kind = crit->kind; out.G = crit->group; out.w = crit->weights;
+  out.beta = crit->kind == PL_CRIT_SMOOTH_L1 ? crit->beta : 1.0f;
+  return PL_OK;
+}
+
+extern "C" size_t pl_pose_loss_scratch_bytes(int64_t B, int64_t O, const PLCriterion* crit) {
+  (void)crit;                       // (the grouped kind's B J joints need no more workgroups than B O elements do)
+  return pl_mse_scratch_bytes(B > 0 && O > 0 ? B * O : 1);
 }
 
 extern "C" int pl_mse_fwd_bwd(const float* pred, const float* tgt, int64_t n, float grad_scale,
                               float* dpred, float* loss_out, void* scratch, void* stream) {
-  return mse_fwd_bwd_tick(pred, tgt, n, grad_scale, dpred, loss_out, scratch, nullptr, stream);
+  if (n <= 0) PL_FAIL(PL_ESHAPE, "pl_mse_fwd_bwd: n = %lld", (long long)n);
+  return loss_fwd_bwd_tick(pred, tgt, 1, n, Crit{}, grad_scale, dpred, loss_out, scratch, nullptr, stream, "pl_mse_fwd_bwd");
 }
 
-// the first half of mse_fwd_bwd_tick: dpred and the per-workgroup partial sums; the loss itself is summed later by a kind-2
-// job of launch_reduce_rows_multi (R = mse_partials(n), inv_n = 1 / n)
-int pl::mse_partial_only(const float* pred, const float* tgt, int64_t n, float grad_scale, float* dpred, void* scratch,
-                         void* stream) {
-  if (!pred || !tgt || !scratch) PL_FAIL(PL_EINVAL, "pl_mse_fwd_bwd: null pointer");
-  if (n <= 0) PL_FAIL(PL_ESHAPE, "pl_mse_fwd_bwd: n = %lld", (long long)n);
-  hipLaunchKernelGGL(mse_partial_kernel, dim3(mse_blocks(n)), dim3(NTHR), 0, (hipStream_t)stream, pred, tgt, n,
-                     grad_scale * 2.0f / (float)n, dpred, (float*)scratch);
+extern "C" int pl_pose_loss_fwd_bwd(const float* pred, const float* tgt, int64_t B, int64_t O, const PLCriterion* crit,
+                                    float grad_scale, float* dpred, float* loss, void* scratch, void* stream) {
+  if (B <= 0 || O <= 0) PL_FAIL(PL_ESHAPE, "pl_pose_loss_fwd_bwd: B=%lld O=%lld", (long long)B, (long long)O);
+  Crit c;
+  PL_TRY(crit_resolve(crit, O, c, "pl_pose_loss_fwd_bwd"));
+  return loss_fwd_bwd_tick(pred, tgt, B, O, c, grad_scale, dpred, loss, scratch, nullptr, stream, "pl_pose_loss_fwd_bwd");
+}
+
+// the first half of loss_fwd_bwd_tick: dpred and the per-workgroup partial sums (loss_partials of them); the loss itself is
+// summed later by a kind-2 job of launch_reduce_rows_multi (inv_n = crit_inv_n)
+int pl::loss_partials(const Crit& c, int64_t B, int64_t O) { return mse_blocks(c.kind == PL_CRIT_MPJPE ? B * O / c.G : B * O); }
+int pl::loss_partial_only(const float* pred, const float* tgt, int64_t B, int64_t O, const Crit& c, float grad_scale, float* dpred,
+                          void* scratch, void* stream, const char* who) {
+  if (!pred || !tgt || !scratch) PL_FAIL(PL_EINVAL, "%s: null pointer", who);
+  const int64_t n = B * O;
+  if (n <= 0) PL_FAIL(PL_ESHAPE, "%s: n = %lld", who, (long long)n);
+  // (the weight index of element i is (i mod O) / G in 32-bit arithmetic; the plain MSE call passes its n as O and reads none)
+  if ((c.w || c.kind == PL_CRIT_MPJPE) && O > INT32_MAX) PL_FAIL(PL_ESHAPE, "%s: O = %lld", who, (long long)O);
+  const CritK k = crit_consts(c, grad_scale, n, O > INT32_MAX ? 1 : (int)O);
+  const dim3 grid(loss_partials(c, B, O)), block(NTHR);
+  hipStream_t s = (hipStream_t)stream;
+  float* part = (float*)scratch;
+  if (c.kind == PL_CRIT_MPJPE) {
+    const int J = (int)(O / c.G);
+    group_dispatch(c, [&](auto g, auto w) {
+      hipLaunchKernelGGL((mpjpe_loss_partial_kernel<decltype(g)::value, decltype(w)::value>), grid, block, 0, s, pred, tgt, n / c.G, J,
+                         k, dpred, part);
+      return 0;
+    });
+  } else {
+    crit_dispatch(c, [&](auto crit, auto w) {
+      using C = decltype(crit);
+      if constexpr (!C::grouped)
+        hipLaunchKernelGGL((mse_partial_kernel<C, decltype(w)::value>), grid, block, 0, s, pred, tgt, n, k, dpred, part);
+      return 0;
+    });
+  }
   PL_CHECK_LAUNCH("mse_partial");
   return PL_OK;
 }
-int pl::mse_partials(int64_t n) { return mse_blocks(n); }
 
-// y = bias + slabs, dpred, MSE partials in one launch (mse_partial_from_slabs_kernel); false: shape not specialised
+// y = bias + slabs, dpred, loss partials in one launch (mse_partial_from_slabs_kernel); false: shape not specialised
 bool pl::mse_from_slabs_supported(int splits, int N) { return splits == 8 && (N == 51 || N == 34); }
-int pl::mse_partial_from_slabs(const float* part, int splits, int B, int N, const float* bias, const float* tgt, float grad_scale,
-                               float* y, float* dpred, void* scratch, void* stream) {
+namespace {
+template <int N>
+void launch_from_slabs(const Crit& c, const CritK& k, dim3 grid, hipStream_t s, const float* part, int B, const float* bias,
+                       const float* tgt, float* y, float* dpred, float* mpart) {
+  const dim3 block(NTHR);
+  if (c.kind == PL_CRIT_MPJPE) {
+    group_dispatch(c, [&](auto g, auto w) {
+      constexpr int G = decltype(g)::value;
+      if constexpr (N % G == 0)
+        hipLaunchKernelGGL((mpjpe_partial_from_slabs_kernel<8, N, G, decltype(w)::value>), grid, block, 0, s, part, B, bias, tgt, k, y,
+                           dpred, mpart);
+      return 0;
+    });
+  } else {
+    crit_dispatch(c, [&](auto crit, auto w) {
+      using C = decltype(crit);
+      if constexpr (!C::grouped)
+        hipLaunchKernelGGL((mse_partial_from_slabs_kernel<8, N, C, decltype(w)::value>), grid, block, 0, s, part, B, bias, tgt, k, y,
+                           dpred, mpart);
+      return 0;
+    });
+  }
+}
+}  // namespace
+int pl::loss_partial_from_slabs(const float* part, int splits, int B, int N, const float* bias, const float* tgt, const Crit& c,
+                                float grad_scale, float* y, float* dpred, void* scratch, void* stream) {
   if (!part || !tgt || !y || !dpred || !scratch) PL_FAIL(PL_EINVAL, "mse_partial_from_slabs: null pointer");
-  if (!mse_from_slabs_supported(splits, N) || B < 1) PL_FAIL(PL_ESHAPE, "mse_partial_from_slabs: splits=%d N=%d", splits, N);
+  if (!mse_from_slabs_supported(splits, N) || B < 1 || N % c.G != 0)
+    PL_FAIL(PL_ESHAPE, "mse_partial_from_slabs: splits=%d N=%d group=%d", splits, N, c.G);
   const int64_t n = (int64_t)B * N;
-  const float coef = grad_scale * 2.0f / (float)n;
-  const dim3 grid(mse_blocks(n)), block(NTHR);
-  if (N == 51) hipLaunchKernelGGL((mse_partial_from_slabs_kernel<8, 51>), grid, block, 0, (hipStream_t)stream, part, B, bias, tgt, coef, y, dpred, (float*)scratch);
-  else hipLaunchKernelGGL((mse_partial_from_slabs_kernel<8, 34>), grid, block, 0, (hipStream_t)stream, part, B, bias, tgt, coef, y, dpred, (float*)scratch);
+  const CritK k = crit_consts(c, grad_scale, n, N);
+  // (the grouped kind runs the same number of workgroups over its B J joints: the same count of partials either way)
+  const dim3 grid(mse_blocks(n));
+  if (N == 51) launch_from_slabs<51>(c, k, grid, (hipStream_t)stream, part, B, bias, tgt, y, dpred, (float*)scratch);
+  else launch_from_slabs<34>(c, k, grid, (hipStream_t)stream, part, B, bias, tgt, y, dpred, (float*)scratch);
   PL_CHECK_LAUNCH("mse_partial_from_slabs");
   return PL_OK;
 }
 
-int pl::mse_fwd_bwd_tick(const float* pred, const float* tgt, int64_t n, float grad_scale, float* dpred,
-                         float* loss_out, void* scratch, uint64_t* tick, void* stream) {
-  if (!pred || !tgt || !loss_out || !scratch) PL_FAIL(PL_EINVAL, "pl_mse_fwd_bwd: null pointer");
-  if (n <= 0) PL_FAIL(PL_ESHAPE, "pl_mse_fwd_bwd: n = %lld", (long long)n);
-  hipStream_t s = (hipStream_t)stream;
-  const int nb = mse_blocks(n);
-  const float coef = grad_scale * 2.0f / (float)n;
-  hipLaunchKernelGGL(mse_partial_kernel, dim3(nb), dim3(NTHR), 0, s, pred, tgt, n, coef, dpred,
-                     (float*)scratch);
-  PL_CHECK_LAUNCH("mse_partial");
-  hipLaunchKernelGGL(mse_final_kernel, dim3(1), dim3(NTHR), 0, s, (const float*)scratch, nb,
-                     1.0f / (float)n, loss_out, tick);
+int pl::loss_fwd_bwd_tick(const float* pred, const float* tgt, int64_t B, int64_t O, const Crit& c, float grad_scale, float* dpred,
+                          float* loss_out, void* scratch, uint64_t* tick, void* stream, const char* who) {
+  if (!loss_out) PL_FAIL(PL_EINVAL, "%s: null pointer", who);
+  PL_TRY(loss_partial_only(pred, tgt, B, O, c, grad_scale, dpred, scratch, stream, who));
+  hipLaunchKernelGGL(mse_final_kernel, dim3(1), dim3(NTHR), 0, (hipStream_t)stream, (const float*)scratch, loss_partials(c, B, O),
+                     crit_inv_n(c, B * O), loss_out, tick);
   PL_CHECK_LAUNCH("mse_final");
   return PL_OK;
 }

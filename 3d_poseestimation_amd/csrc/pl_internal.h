@@ -10,6 +10,7 @@
 #include "../../include/poselift.h"
 #include "adamw.h"
 #include "philox.h"
+#include "pose_criterion.h"
 
 namespace pl {
 
@@ -248,9 +249,10 @@ struct BnApplyArgs {
   BnFinalizeArgs fin;
 };
 int launch_bn_apply(const BnApplyArgs& a, hipStream_t s);
-// pl_mse_fwd_bwd + (tick != NULL) tick[0] += 1 once the loss is written (PLDesc.step_dev, graph replay)
-int mse_fwd_bwd_tick(const float* pred, const float* tgt, int64_t n, float grad_scale, float* dpred, float* loss_out,
-                     void* scratch, uint64_t* tick, void* stream);
+// pl_pose_loss_fwd_bwd (pl_mse_fwd_bwd: Crit{}, B = 1, O = n) + (tick != NULL) tick[0] += 1 once the loss is written
+// (PLDesc.step_dev, graph replay)
+int loss_fwd_bwd_tick(const float* pred, const float* tgt, int64_t B, int64_t O, const Crit& c, float grad_scale, float* dpred,
+                      float* loss_out, void* scratch, uint64_t* tick, void* stream, const char* who);
 
 int bwd_row_chunks(int B, int H);
 // pass 1: partial column sums of dy and dy*zhat, dy = g * bits * keep_scale
@@ -351,6 +353,7 @@ int launch_small_layer_fwd(const SmallLayerFwdArgs& a, hipStream_t s);
 int launch_small_layer_eval(const SmallLayerFwdArgs& a, hipStream_t s);
 // the output Linear from the NS slabs the last hidden layer's launch left: y = bias + their sum (launch_small_out reads
 // these fields alone) and, launch_small_mse, dpred = grad_scale * 2 (y - tgt) / (B O) and the MSE partials in mpart
+// (crit: the criterion in MSE's place; its partials: small_loss_partials)
 struct SmallHeadArgs {
   const float* ypart;
   int NS, B, O;
@@ -359,6 +362,7 @@ struct SmallHeadArgs {
   const float* tgt;
   float grad_scale;
   float *dpred, *mpart;
+  Crit crit;
 };
 int launch_small_out(const SmallHeadArgs& a, hipStream_t s);
 // the Linear alone with the statistics partials of a tile GEMM's epilogue, for TRAINING batches of 65 ... 512 rows: the tile
@@ -375,6 +379,7 @@ struct SmallLinearStatsArgs {
 };
 int launch_small_linear_stats(const SmallLinearStatsArgs& a, hipStream_t s);
 int small_mse_partials(int B, int O);     // partial sums launch_small_mse leaves in mpart (<= 64)
+int small_loss_partials(const Crit& c, int B, int O);      // ... with a criterion: the grouped kind counts 64 joints a workgroup
 int launch_small_mse(const SmallHeadArgs& a, hipStream_t s);
 // g = dz W (+ addend) -> gout (or NULL), then the BatchNorm backward of the layer below -> dz_lo
 struct SmallLayerBwdArgs {
@@ -436,12 +441,13 @@ struct RowJob {
   int R, H, kind, transK;
 };
 int launch_reduce_rows_multi(const RowJob* jobs, int njobs, float loss_inv_n, uint64_t* loss_tick, hipStream_t s);
-int mse_partial_only(const float* pred, const float* tgt, int64_t n, float grad_scale, float* dpred, void* scratch, void* stream);
-int mse_partials(int64_t n);
-// the output Linear's slab reduce folded into the MSE partial pass (fused train step; bit-identical to the two launches)
+int loss_partial_only(const float* pred, const float* tgt, int64_t B, int64_t O, const Crit& c, float grad_scale, float* dpred,
+                      void* scratch, void* stream, const char* who);
+int loss_partials(const Crit& c, int64_t B, int64_t O);
+// the output Linear's slab reduce folded into the loss partial pass (fused train step; bit-identical to the two launches)
 bool mse_from_slabs_supported(int splits, int N);
-int mse_partial_from_slabs(const float* part, int splits, int B, int N, const float* bias, const float* tgt, float grad_scale,
-                           float* y, float* dpred, void* scratch, void* stream);
+int loss_partial_from_slabs(const float* part, int splits, int B, int N, const float* bias, const float* tgt, const Crit& c,
+                            float grad_scale, float* y, float* dpred, void* scratch, void* stream);
 // out[r][c] = bias[c] + sum_s slabs[s][r][c]
 int launch_reduce_slabs_bias(const float* slabs, int nslab, int rows, int cols, const float* bias,
                              float* out, hipStream_t s);

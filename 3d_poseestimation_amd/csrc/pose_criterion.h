@@ -1,0 +1,129 @@
+// The pointwise part of the lifter's training criterion (include/poselift.h PLCriterion) as compile-time
+// types: every loss kernel is written once over a criterion type and a has-weights flag, the kind is chosen at the launch,
+// and no element loop branches on it.  d = prediction - target (fp32), w = the joint's weight, k = CritK.
+//
+//   kind        accumulated term                         gradient of the element
+//   mse         fmaf(d, d, acc)   [fmaf(w d, d, acc)]    d * coef                       coef = s * 2 / n
+//   l1          acc + |d|         [fmaf(w, |d|, acc)]    d > 0 ? coef : d < 0 ? -coef : 0            coef = s / n
+//   smooth_l1   acc + rho(d)      [fmaf(w, rho, acc)]    |d| >= beta ? (d > 0 ? coef : -coef) : d * cb   cb = coef / beta
+//               rho = |d| >= beta ? |d| - hb : d * d * qb          hb = beta / 2, qb = 0.5 / beta
+//   mpjpe       acc + r           [fmaf(w, r, acc)]      ss == 0 ? 0 : d_g * (cw / r)   coef = s / (B J), cw = coef [* w]
+//               ss = d_0 d_0, then fmaf(d_g, d_g, ss); r = sqrtf(ss)
+// The weighted gradient of the three pointwise kinds is (the unweighted one) * w.  The MSE entries are the expressions the
+// MSE kernels always had: that instantiation's bits do not move.  A NaN d takes the `else` arm of every comparison: L1's
+// gradient is 0, smooth-L1's d * cb = NaN, MPJPE's whole joint NaN (ss is NaN, not 0) -- torch's sets.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <type_traits>
+
+#include "../../include/poselift.h"
+
+namespace pl {
+
+// A criterion resolved against a shape [B][O]: what the launchers hand their kernels (crit_resolve, elementwise.hip).
+struct Crit {
+  int kind = PL_CRIT_MSE;
+  int G = 1;                    // coordinates per joint; O = J * G
+  float beta = 1.0f;
+  const float* w = nullptr;     // J device floats, or NULL = all ones
+};
+// crit == NULL: plain MSE.  PL_EINVAL: unknown kind, beta <= 0 or not finite on smooth_l1; PL_ESHAPE: group < 1, O % group,
+// group > kCritMaxGroup on mpjpe (a joint's coordinates live in one thread's registers).
+constexpr int kCritMaxGroup = 4;
+int crit_resolve(const PLCriterion* crit, int64_t O, Crit& out, const char* who);
+
+// the constants of one launch, computed once on the host in fp32
+struct CritK {
+  float coef, cb, beta, hb, qb;
+  const float* w;
+  int O, G;
+};
+inline CritK crit_consts(const Crit& c, float grad_scale, int64_t n /* = B O */, int O) {
+  CritK k = {};
+  switch (c.kind) {
+    case PL_CRIT_MSE: k.coef = grad_scale * 2.0f / (float)n; break;
+    case PL_CRIT_MPJPE: k.coef = grad_scale / (float)(n / c.G); break;
+    default: k.coef = grad_scale / (float)n; break;
+  }
+  k.beta = c.beta; k.cb = k.coef / c.beta; k.hb = 0.5f * c.beta; k.qb = 0.5f / c.beta;
+  k.w = c.w; k.O = O; k.G = c.G;
+  return k;
+}
+// what the summed partials are multiplied by: 1 / (B O), for mpjpe 1 / (B J)
+inline float crit_inv_n(const Crit& c, int64_t n /* = B O */) { return 1.0f / (float)(c.kind == PL_CRIT_MPJPE ? n / c.G : n); }
+
+template <int KIND>
+struct Pointwise;
+template <>
+struct Pointwise<PL_CRIT_MSE> {
+  static constexpr bool grouped = false;
+  static __device__ __forceinline__ float first(float d, const CritK&) { return d * d; }
+  static __device__ __forceinline__ float add(float acc, float d, const CritK&) { return fmaf(d, d, acc); }
+  static __device__ __forceinline__ float add_w(float acc, float d, float w, const CritK&) { return fmaf(w * d, d, acc); }
+  static __device__ __forceinline__ float grad(float d, const CritK& k) { return d * k.coef; }
+};
+template <>
+struct Pointwise<PL_CRIT_L1> {
+  static constexpr bool grouped = false;
+  static __device__ __forceinline__ float first(float d, const CritK&) { return fabsf(d); }
+  static __device__ __forceinline__ float add(float acc, float d, const CritK&) { return acc + fabsf(d); }
+  static __device__ __forceinline__ float add_w(float acc, float d, float w, const CritK&) { return fmaf(w, fabsf(d), acc); }
+  static __device__ __forceinline__ float grad(float d, const CritK& k) { return d > 0.f ? k.coef : (d < 0.f ? -k.coef : 0.f); }
+};
+template <>
+struct Pointwise<PL_CRIT_SMOOTH_L1> {
+  static constexpr bool grouped = false;
+  static __device__ __forceinline__ float first(float d, const CritK& k) {
+    const float a = fabsf(d);
+    return a >= k.beta ? a - k.hb : d * d * k.qb;
+  }
+  static __device__ __forceinline__ float add(float acc, float d, const CritK& k) { return acc + first(d, k); }
+  static __device__ __forceinline__ float add_w(float acc, float d, float w, const CritK& k) { return fmaf(w, first(d, k), acc); }
+  static __device__ __forceinline__ float grad(float d, const CritK& k) {
+    return fabsf(d) >= k.beta ? (d > 0.f ? k.coef : -k.coef) : d * k.cb;
+  }
+};
+template <>
+struct Pointwise<PL_CRIT_MPJPE> {
+  static constexpr bool grouped = true;
+};
+
+// one joint of the grouped kind: d[G] in, gradient g[G] out, returns r = ||d||
+template <int G>
+__device__ __forceinline__ float joint_norm_grad(const float (&d)[G], float cw, float (&g)[G]) {
+  float ss = d[0] * d[0];
+#pragma unroll
+  for (int c = 1; c < G; ++c) ss = fmaf(d[c], d[c], ss);
+  const float r = sqrtf(ss);
+  const float q = cw / r;
+#pragma unroll
+  for (int c = 0; c < G; ++c) g[c] = ss == 0.f ? 0.f : d[c] * q;
+  return r;
+}
+
+// (kind, has weights) -> f(Pointwise<kind>{}, std::bool_constant<W>{}): the one place a launch turns the run-time kind into types
+template <class F>
+inline int crit_dispatch(const Crit& c, F&& f) {
+  const bool w = c.w != nullptr;
+  switch (c.kind) {
+    case PL_CRIT_MSE: return w ? f(Pointwise<PL_CRIT_MSE>{}, std::true_type{}) : f(Pointwise<PL_CRIT_MSE>{}, std::false_type{});
+    case PL_CRIT_L1: return w ? f(Pointwise<PL_CRIT_L1>{}, std::true_type{}) : f(Pointwise<PL_CRIT_L1>{}, std::false_type{});
+    case PL_CRIT_SMOOTH_L1:
+      return w ? f(Pointwise<PL_CRIT_SMOOTH_L1>{}, std::true_type{}) : f(Pointwise<PL_CRIT_SMOOTH_L1>{}, std::false_type{});
+    default: return w ? f(Pointwise<PL_CRIT_MPJPE>{}, std::true_type{}) : f(Pointwise<PL_CRIT_MPJPE>{}, std::false_type{});
+  }
+}
+// ... and the group size of the grouped kind: f(std::integral_constant<int, G>{}, std::bool_constant<W>{}), G = 1 .. kCritMaxGroup
+template <class F>
+inline int group_dispatch(const Crit& c, F&& f) {
+  const bool w = c.w != nullptr;
+  switch (c.G) {
+    case 1: return w ? f(std::integral_constant<int, 1>{}, std::true_type{}) : f(std::integral_constant<int, 1>{}, std::false_type{});
+    case 2: return w ? f(std::integral_constant<int, 2>{}, std::true_type{}) : f(std::integral_constant<int, 2>{}, std::false_type{});
+    case 3: return w ? f(std::integral_constant<int, 3>{}, std::true_type{}) : f(std::integral_constant<int, 3>{}, std::false_type{});
+    default: return w ? f(std::integral_constant<int, 4>{}, std::true_type{}) : f(std::integral_constant<int, 4>{}, std::false_type{});
+  }
+}
+
+}  // namespace pl

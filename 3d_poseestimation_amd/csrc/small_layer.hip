@@ -859,9 +859,12 @@ __global__ __launch_bounds__(NTHR) void small_top_bwd_kernel(TopArgs p) {
 // partial sum of (y - t)^2: the MSE forward + backward of the fused train step at small batch (nn.MSELoss, train_1.py:64-66).
 // Four lanes per element, a quarter of the slabs each (all of a lane's loads in flight: one round trip), combined in a fixed
 // order: (q0 + q1) + (q2 + q3).  64 elements per workgroup.
+// C, W (pose_criterion.h): the criterion in MSE's place and its per-joint weights (one element, one weight per lane group);
+// <Pointwise<PL_CRIT_MSE>, false> is the kernel as it always was.
 constexpr int kMseElems = 64;
+template <class C, bool W>
 __global__ __launch_bounds__(256) void small_mse_kernel(const float* __restrict__ ypart, int NS, int B, int O,
-                                                        const float* __restrict__ bias, const float* __restrict__ tgt, float coef,
+                                                        const float* __restrict__ bias, const float* __restrict__ tgt, CritK k,
                                                         float* __restrict__ y, float* __restrict__ dpred, float* __restrict__ mpart) {
   __shared__ float red[4];
   const int n = B * O, tid = threadIdx.x;
@@ -887,11 +890,74 @@ __global__ __launch_bounds__(256) void small_mse_kernel(const float* __restrict_
     y[i] = a;
     if (tgt) {
       const float d = a - tgt[i];
-      acc = d * d;
-      dpred[i] = d * coef;
+      if constexpr (W) {
+        const float w = k.w[o / k.G];
+        acc = C::add_w(0.f, d, w, k);
+        dpred[i] = C::grad(d, k) * w;
+      } else {
+        acc = C::first(d, k);
+        dpred[i] = C::grad(d, k);
+      }
     }
   }
   if (!tgt) return;                                          // (evaluation: y is all there is; kernel-uniform)
+#pragma unroll
+  for (int w = 32; w >= 1; w >>= 1) acc += __shfl_xor(acc, w);
+  if ((tid & 63) == 0) red[tid >> 6] = acc;
+  __syncthreads();
+  if (tid == 0) mpart[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// The grouped kind (mpjpe) with an element map of its own: four lanes per JOINT, 64 joints per workgroup (no joint is shared
+// between workgroups).  Each lane sums a quarter of the slabs of all G coordinates -- G x 16 loads in flight per pass, one round
+// trip -- and the quarters combine per coordinate in small_mse_kernel's order, (q0 + q1) + (q2 + q3), + bias: y has the bits
+// the pointwise map gives it.  Lane 0 of the group then holds the whole joint.  ceil(B J / 64) <= 64 partials.
+template <int G, bool W>
+__global__ __launch_bounds__(256) void small_mpjpe_kernel(const float* __restrict__ ypart, int NS, int B, int O,
+                                                          const float* __restrict__ bias, const float* __restrict__ tgt, CritK k,
+                                                          float* __restrict__ y, float* __restrict__ dpred, float* __restrict__ mpart) {
+  __shared__ float red[4];
+  const int J = O / G, nj = B * J, tid = threadIdx.x;
+  const int i = blockIdx.x * kMseElems + (tid >> 2), q = tid & 3;
+  const bool ok = i < nj;
+  const int r = ok ? i / J : 0, j = ok ? i - r * J : 0;
+  const size_t slab = (size_t)B * 64;
+  const int per = (NS + 3) >> 2;
+  const float* src = ypart + (size_t)r * 64 + j * G + (size_t)(q * per) * slab;
+  float a[G];
+#pragma unroll
+  for (int c = 0; c < G; ++c) a[c] = 0.f;
+  for (int s0 = 0; s0 < per; s0 += 16) {
+    float u[G][16];
+#pragma unroll
+    for (int c = 0; c < G; ++c)
+#pragma unroll
+      for (int m = 0; m < 16; ++m) u[c][m] = (ok && s0 + m < per && q * per + s0 + m < NS) ? src[(size_t)(s0 + m) * slab + c] : 0.f;
+#pragma unroll
+    for (int c = 0; c < G; ++c)
+#pragma unroll
+      for (int m = 0; m < 16; ++m) a[c] += u[c][m];
+  }
+#pragma unroll
+  for (int c = 0; c < G; ++c) {
+    a[c] += __shfl_xor(a[c], 1);
+    a[c] += __shfl_xor(a[c], 2);
+  }
+  float acc = 0.f;
+  if (ok && q == 0) {
+    float d[G], g[G];
+#pragma unroll
+    for (int c = 0; c < G; ++c) {
+      if (bias) a[c] += bias[j * G + c];
+      y[i * G + c] = a[c];
+      d[c] = a[c] - tgt[i * G + c];
+    }
+    const float w = W ? k.w[j] : 1.f;
+    const float nr = joint_norm_grad<G>(d, W ? k.coef * w : k.coef, g);
+    acc = W ? w * nr : nr;
+#pragma unroll
+    for (int c = 0; c < G; ++c) dpred[i * G + c] = g[c];
+  }
 #pragma unroll
   for (int w = 32; w >= 1; w >>= 1) acc += __shfl_xor(acc, w);
   if ((tid & 63) == 0) red[tid >> 6] = acc;
@@ -923,8 +989,8 @@ bool small_top_ok(int O) {
 // the output Linear of an evaluation forward from the slabs the last hidden layer's launch left: y = bias + sum of slabs
 int launch_small_out(const SmallHeadArgs& a, hipStream_t s) {
   if (!a.ypart || !a.y || a.NS < 1 || a.B < 1 || !small_top_ok(a.O)) PL_FAIL(PL_EINVAL, "small_out: bad arguments");
-  hipLaunchKernelGGL(small_mse_kernel, dim3((a.B * a.O + kMseElems - 1) / kMseElems), dim3(256), 0, s, a.ypart, a.NS, a.B, a.O,
-                     a.bias, (const float*)nullptr, 0.f, a.y, (float*)nullptr, (float*)nullptr);
+  hipLaunchKernelGGL((small_mse_kernel<Pointwise<PL_CRIT_MSE>, false>), dim3((a.B * a.O + kMseElems - 1) / kMseElems), dim3(256), 0,
+                     s, a.ypart, a.NS, a.B, a.O, a.bias, (const float*)nullptr, CritK{}, a.y, (float*)nullptr, (float*)nullptr);
   PL_CHECK_LAUNCH("small_out");
   return PL_OK;
 }
@@ -1077,13 +1143,32 @@ int launch_small_layer_bwd(const SmallLayerBwdArgs& a, hipStream_t s) {
 
 int small_mse_partials(int B, int O) { return (B * O + kMseElems - 1) / kMseElems; }
 
+int small_loss_partials(const Crit& c, int B, int O) {
+  return c.kind == PL_CRIT_MPJPE ? (B * (O / c.G) + kMseElems - 1) / kMseElems : small_mse_partials(B, O);
+}
+
 int launch_small_mse(const SmallHeadArgs& a, hipStream_t s) {
-  if (!a.ypart || !a.tgt || !a.y || !a.dpred || !a.mpart || a.NS < 1 || a.B < 1 || a.B > ROWS || !small_top_ok(a.O))
+  const Crit& c = a.crit;
+  if (!a.ypart || !a.tgt || !a.y || !a.dpred || !a.mpart || a.NS < 1 || a.B < 1 || a.B > ROWS || !small_top_ok(a.O) || c.G < 1 ||
+      a.O % c.G != 0 || (c.kind == PL_CRIT_MPJPE && c.G > kCritMaxGroup))
     PL_FAIL(PL_EINVAL, "small_mse: bad arguments");
-  const int np = small_mse_partials(a.B, a.O);
-  const float coef = a.grad_scale * 2.0f / (float)(a.B * a.O);
-  hipLaunchKernelGGL(small_mse_kernel, dim3(np), dim3(256), 0, s, a.ypart, a.NS, a.B, a.O, a.bias, a.tgt, coef, a.y, a.dpred,
-                     a.mpart);
+  const dim3 grid(small_loss_partials(c, a.B, a.O)), block(256);
+  const CritK k = crit_consts(c, a.grad_scale, (int64_t)a.B * a.O, a.O);
+  if (c.kind == PL_CRIT_MPJPE) {
+    group_dispatch(c, [&](auto g, auto w) {
+      hipLaunchKernelGGL((small_mpjpe_kernel<decltype(g)::value, decltype(w)::value>), grid, block, 0, s, a.ypart, a.NS, a.B, a.O,
+                         a.bias, a.tgt, k, a.y, a.dpred, a.mpart);
+      return 0;
+    });
+  } else {
+    crit_dispatch(c, [&](auto crit, auto w) {
+      using C = decltype(crit);
+      if constexpr (!C::grouped)
+        hipLaunchKernelGGL((small_mse_kernel<C, decltype(w)::value>), grid, block, 0, s, a.ypart, a.NS, a.B, a.O, a.bias, a.tgt, k,
+                           a.y, a.dpred, a.mpart);
+      return 0;
+    });
+  }
   PL_CHECK_LAUNCH("small_mse");
   return PL_OK;
 }

@@ -533,15 +533,19 @@ class LinearModel(nn.Module):
         <= 64 rows whose hidden layers run as one launch each)?"""
         return _lib.lib().pl_lifter_step_carries_adamw(ctypes.byref(self._desc), int(B)) == 1
 
-    def fused_train_fwd_bwd(self, x2, target, sync=None, step_dev=None, adamw=None):
+    def fused_train_fwd_bwd(self, x2, target, sync=None, step_dev=None, adamw=None, criterion=None):
         """forward + MSE(mean) + backward in one library call (two when a data-parallel sync wants
         the upper layers' gradients early).  Returns (loss, y) device tensors; parameter gradients
         land in the flat arena and stay attached as .grad views.
+        criterion (a criterion.PoseCriterion, or None = MSE): the loss in MSE's place, on every route and in the same launches
+        (pl_lifter_train_fwd_bwd_crit / pl_lifter_train_step_crit; None calls the entry points it always did).
         step_dev (graph capture, train.GraphedTrainStep): device counter of completed steps; the dropout stream
         of the captured launches uses (the step number at capture) + *step_dev.
         adamw (a _lib.PLAdamWStep from FlatAdamW._step_struct; no sync): the optimizer step as well, in the same call
         (pl_lifter_train_step) -- the parameters are updated in place."""
         B = x2.shape[0]
+        # (checked before anything is counted or launched; the struct points into the criterion's weights)
+        crit = ctypes.byref(criterion.struct(self.output_size, x2.device)) if criterion is not None else None
         ws = self._acquire_workspace(B)
         try:
             y = torch.empty(B, self.output_size, dtype=torch.float32, device=x2.device)
@@ -558,17 +562,29 @@ class LinearModel(nn.Module):
                 self._mark_wplanes()
 
             def call(hi, lo):
-                self._guarded(ws, lambda: L.pl_lifter_train_fwd_bwd(
-                    ctypes.byref(self._desc), x2.data_ptr(), target.data_ptr(), B, ws["buf"].data_ptr(), ws["bytes"],
-                    self._seed, self._step, y.data_ptr(), loss.data_ptr(), grads.data_ptr(), hi, lo,
-                    _lib.current_stream_ptr()), "pl_lifter_train_fwd_bwd")
+                if crit is None:
+                    self._guarded(ws, lambda: L.pl_lifter_train_fwd_bwd(
+                        ctypes.byref(self._desc), x2.data_ptr(), target.data_ptr(), B, ws["buf"].data_ptr(), ws["bytes"],
+                        self._seed, self._step, y.data_ptr(), loss.data_ptr(), grads.data_ptr(), hi, lo,
+                        _lib.current_stream_ptr()), "pl_lifter_train_fwd_bwd")
+                else:
+                    self._guarded(ws, lambda: L.pl_lifter_train_fwd_bwd_crit(
+                        ctypes.byref(self._desc), x2.data_ptr(), target.data_ptr(), B, ws["buf"].data_ptr(), ws["bytes"],
+                        self._seed, self._step, crit, y.data_ptr(), loss.data_ptr(), grads.data_ptr(), hi, lo,
+                        _lib.current_stream_ptr()), "pl_lifter_train_fwd_bwd_crit")
             if adamw is not None:
                 if sync is not None:
                     raise _lib.PoseliftError("fused_train_fwd_bwd: the in-call AdamW step and a gradient sync exclude each other")
-                self._guarded(ws, lambda: L.pl_lifter_train_step(
-                    ctypes.byref(self._desc), x2.data_ptr(), target.data_ptr(), B, ws["buf"].data_ptr(), ws["bytes"],
-                    self._seed, self._step, y.data_ptr(), loss.data_ptr(), grads.data_ptr(), ctypes.byref(adamw),
-                    _lib.current_stream_ptr()), "pl_lifter_train_step")
+                if crit is None:
+                    self._guarded(ws, lambda: L.pl_lifter_train_step(
+                        ctypes.byref(self._desc), x2.data_ptr(), target.data_ptr(), B, ws["buf"].data_ptr(), ws["bytes"],
+                        self._seed, self._step, y.data_ptr(), loss.data_ptr(), grads.data_ptr(), ctypes.byref(adamw),
+                        _lib.current_stream_ptr()), "pl_lifter_train_step")
+                else:
+                    self._guarded(ws, lambda: L.pl_lifter_train_step_crit(
+                        ctypes.byref(self._desc), x2.data_ptr(), target.data_ptr(), B, ws["buf"].data_ptr(), ws["bytes"],
+                        self._seed, self._step, crit, y.data_ptr(), loss.data_ptr(), grads.data_ptr(), ctypes.byref(adamw),
+                        _lib.current_stream_ptr()), "pl_lifter_train_step_crit")
             elif sync is not None and sync.world() > 1 and _overlap_ok(sync):
                 for hi, lo, a_lo, a_hi in self._bwd_ranges():
                     call(hi, lo)

@@ -148,24 +148,32 @@ def epoch_mpjpe_mm(metric_sum, n_samples, num_of_joints=17, zero_centre=True):
     return m
 
 
-def _fusable(model, optimizer, y1, y2):
+def _fusable(model, optimizer, y1, y2, criterion=None):
+    from .criterion import PoseCriterion
     from .model import LinearModel
     from .optim import FlatAdamW
-    return (isinstance(model, LinearModel) and isinstance(optimizer, FlatAdamW) and optimizer._model is model
+    return ((criterion is None or isinstance(criterion, PoseCriterion)) and isinstance(model, LinearModel) and isinstance(optimizer, FlatAdamW) and optimizer._model is model
             and model.training and torch.is_grad_enabled() and not y1.requires_grad and y1.is_cuda and y2.is_cuda
             and model._inject_keep is None and model._arenas_intact()
             and y2.numel() == y2.shape[0] * model.output_size
             and y1.numel() == y1.shape[0] * model.input_size)
 
 
-def train_step(model, optimizer, y1, y2, grad_sync=None):
+def _criterion_loss(criterion, y2_hat, y2):
+    return mse_loss(y2_hat, y2) if criterion is None else criterion(y2_hat, y2)
+
+
+def train_step(model, optimizer, y1, y2, grad_sync=None, criterion=None):
     """One train_1.py:75-100 step: zero_grad, forward, reshape (B,J,3), MSE(mean), backward,
     [gradient all-reduce], optimizer.step.  Returns (loss, y2_hat) as device tensors -- the
     caller decides when to pay the host sync the reference pays every step (train_1.py:98).
     grad_sync: optional callable(model) -> grad_scale, e.g. dp.GradSync; attach it with
-    model.set_grad_sync(grad_sync) to have its all-reduce overlapped with the backward pass."""
+    model.set_grad_sync(grad_sync) to have its all-reduce overlapped with the backward pass.
+    criterion: a criterion.PoseCriterion in MSE's place (the reference's `# loss_function = torch.nn.L1Loss()` toggle,
+    train_1.py:36-37; smooth-L1, MPJPE, per-joint weights).  LinearModel + FlatAdamW keep the fused step -- the same
+    launches, AdamW riding at B <= 64, the data-parallel ranges; every other model runs criterion(y2_hat, y2) under autograd."""
     y1, y2 = y1.float(), y2.float()
-    if _fusable(model, optimizer, y1, y2):
+    if _fusable(model, optimizer, y1, y2, criterion):
         # the whole step is three library calls: fwd+loss+bwd, [all-reduce], AdamW.  Same kernels,
         # same results as the autograd route below; `zero_grad` is implicit (gradients are overwritten)
         with _lib.on_device(y1.device):
@@ -176,15 +184,16 @@ def train_step(model, optimizer, y1, y2, grad_sync=None):
                 # (not with max_grad_norm / skip_nonfinite: the norm of the whole gradient has to exist before any update)
                 adamw = optimizer._step_struct(float(optimizer.param_groups[0]["lr"]), None, optimizer._t + 1, None)
                 if adamw is not None:
-                    loss, y2_hat = model.fused_train_fwd_bwd(x2, t2, None, adamw=adamw)
+                    loss, y2_hat = model.fused_train_fwd_bwd(x2, t2, None, adamw=adamw, criterion=criterion)
                     optimizer._advance_host(1)
                     return loss, y2_hat.reshape(y2.shape)
-            loss, y2_hat = model.fused_train_fwd_bwd(x2, t2, grad_sync if model._grad_sync is grad_sync else None)
+            loss, y2_hat = model.fused_train_fwd_bwd(x2, t2, grad_sync if model._grad_sync is grad_sync else None,
+                                                     criterion=criterion)
         optimizer.step(grad_scale=grad_sync(model) if grad_sync is not None else 1.0)
         return loss, y2_hat.reshape(y2.shape)
     optimizer.zero_grad()
     y2_hat = model(y1).reshape(y2.shape)
-    loss = mse_loss(y2_hat, y2)
+    loss = _criterion_loss(criterion, y2_hat, y2)
     loss.backward()
     if grad_sync is not None:
         optimizer.step(grad_scale=grad_sync(model))
@@ -204,11 +213,16 @@ class GraphedTrainStep:
     What changes from step to step lives in device memory and is advanced INSIDE the graph: the dropout stream's
     step number and AdamW's t come from one device counter (PLDesc.step_dev, the AdamW launch's t_dev), the learning rate
     from a device scalar the host refreshes when a scheduler changed it.  Single process (a captured RCCL
-    all-reduce is not wired); LinearModel + FlatAdamW; fixed batch shape."""
+    all-reduce is not wired); LinearModel + FlatAdamW; fixed batch shape.
+    criterion (a criterion.PoseCriterion, None = MSE): its kind, beta and coords are fixed at capture (changing them on the
+    object afterwards does nothing to the graph); the address of its joint_weights is baked into the captured launches, the
+    step keeps the criterion alive, and in-place edits of the weights are seen by the next replay (moving the criterion
+    to another device or replacing the tensor needs a new GraphedTrainStep: __call__ refuses)."""
 
-    def __init__(self, model, optimizer, y1, y2):
+    def __init__(self, model, optimizer, y1, y2, criterion=None):
         y1, y2 = y1.float(), y2.float()
-        if not _fusable(model, optimizer, y1, y2) or model._grad_sync is not None:
+        self.criterion = criterion
+        if not _fusable(model, optimizer, y1, y2, criterion) or model._grad_sync is not None:
             raise _lib.PoseliftError("GraphedTrainStep needs a training-mode LinearModel on the GPU with its FlatAdamW "
                                      "and no gradient sync attached")
         self.model, self.opt = model, optimizer
@@ -226,7 +240,7 @@ class GraphedTrainStep:
             state = [model.flat_params, model._bn_running, model._bn_batches] + optimizer._capture_state()
             snap = [t.clone() for t in state]
             step0, t0 = model._step, optimizer._t
-            train_step(model, optimizer, self._x, self._y.reshape(self._out_shape))
+            train_step(model, optimizer, self._x, self._y.reshape(self._out_shape), criterion=criterion)
             for dst, src in zip(state, snap):
                 dst.copy_(src)
             model._step = step0
@@ -243,10 +257,11 @@ class GraphedTrainStep:
             self._in_call = adamw is not None
             with torch.cuda.graph(self.graph):
                 if adamw is not None:        # small batches: the optimizer step is inside the same call's launches
-                    self.loss, y_hat = model.fused_train_fwd_bwd(self._x, self._y, None, step_dev=self._tick, adamw=adamw)
+                    self.loss, y_hat = model.fused_train_fwd_bwd(self._x, self._y, None, step_dev=self._tick, adamw=adamw,
+                                                                 criterion=criterion)
                     self._refreshes_planes = False
                 else:
-                    self.loss, y_hat = model.fused_train_fwd_bwd(self._x, self._y, None, step_dev=self._tick)
+                    self.loss, y_hat = model.fused_train_fwd_bwd(self._x, self._y, None, step_dev=self._tick, criterion=criterion)
                     self._refreshes_planes = optimizer._enqueue_dev(lr_dev, t0, self._tick)
             self.y_hat = y_hat.reshape(self._out_shape)
             model._step = step0                                              # capturing ran nothing
@@ -262,8 +277,9 @@ class GraphedTrainStep:
         return self._x, self._y
 
     def _baked_ptrs(self):
+        w = self.criterion.joint_weights if self.criterion is not None else None
         return (self.model.flat_params.data_ptr(), self.opt._m.data_ptr() if self.opt._m is not None else 0,
-                self.opt._v.data_ptr() if self.opt._v is not None else 0)
+                self.opt._v.data_ptr() if self.opt._v is not None else 0, w.data_ptr() if w is not None else 0)
 
     def __call__(self, y1, y2):
         self._lr_dev.refresh(self.opt.param_groups[0]["lr"])                     # ReduceLROnPlateau et al. (train_1.py:106)
@@ -274,8 +290,9 @@ class GraphedTrainStep:
         # not the device counter the captured launches read: re-seed it when both moved together, refuse otherwise
         ds, dt = self.model._step - self._step0, self.opt._t - self._t0
         if self.model._seed != self._seed0 or self._baked_ptrs() != self._ptrs:
-            raise _lib.PoseliftError("GraphedTrainStep: the dropout seed or an arena address changed after capture "
-                                     "(manual_seed, optimizer.load_state_dict, .to()): capture a new GraphedTrainStep")
+            raise _lib.PoseliftError("GraphedTrainStep: the dropout seed, an arena address or the criterion's weight tensor "
+                                     "changed after capture (manual_seed, optimizer.load_state_dict, .to()): capture a new "
+                                     "GraphedTrainStep")
         if ds != dt or ds < 0:
             raise _lib.PoseliftError(f"GraphedTrainStep: the model ran {ds} steps since capture but the optimizer {dt}: "
                                      "the graph advances both from one device counter -- capture a new one")
@@ -315,7 +332,8 @@ class GraphedModuleStep:
     puts parameters, buffers and optimizer state back exactly as they were, so the first replay is the model's first step.
     Fixed shapes; single process; the optimizer must keep its step state on the device (torch: capturable=True; give lr as
     a tensor to change it between replays).  forward(*inputs) is whatever the module's forward takes; loss_fn(output,
-    target)."""
+    target) -- a criterion.PoseCriterion is one (its launch pair is captured like any other: kind, beta and coords as they
+    are at construction, joint_weights edited in place are seen by replays)."""
 
     def __init__(self, model, optimizer, loss_fn, inputs, target, warmup=2):
         inputs = tuple(inputs) if isinstance(inputs, (tuple, list)) else (inputs,)
@@ -402,8 +420,9 @@ def predict_flip_tta(model, y1, out_dims=3):
 
 
 @torch.no_grad()
-def eval_step(model, y1, y2, metric_out=None, flip=False, meter=None, group_ids=None, denorm=None):
+def eval_step(model, y1, y2, metric_out=None, flip=False, meter=None, group_ids=None, denorm=None, criterion=None):
     """train_1.py:112-145 body (model must be in eval mode): forward, MSE, loss_MPJPE.
+    criterion: a criterion.PoseCriterion -- `loss` is then that criterion's value, not the MSE.
     flip=True: flip test-time augmentation (predict_flip_tta).
     meter: a metrics.PoseMetrics that also takes this batch (P-MPJPE, N-MPJPE, PCK; group_ids (B,) = e.g. the action of
     each pose); like everything here it only enqueues work.
@@ -416,7 +435,7 @@ def eval_step(model, y1, y2, metric_out=None, flip=False, meter=None, group_ids=
                          "flip_average(T3.invert(b), T3.invert(a)) is the prediction in raw units")
     y1, y2 = y1.float(), y2.float()
     y2_hat = predict_flip_tta(model, y1, y2.shape[-1]).reshape(y2.shape) if flip else model(y1).reshape(y2.shape)
-    loss = mse_loss(y2_hat, y2)
+    loss = _criterion_loss(criterion, y2_hat, y2)
     metric = loss_MPJPE(y2_hat, y2, out=metric_out, denorm=denorm)
     if meter is not None:
         meter.update(y2_hat, y2, group_ids, denorm=denorm)

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define PL_VERSION 116 /* 0.1.16: + pl_pose_prepare, pl_pose_stats, pl_pose_affine and their _host forms, pl_pose_stats_scratch_bytes, pl_pose_stats_chunk_rows, pl_pose_augment_gather_t, pl_pose_augment_host_t, pl_pose_errors_t, pl_mpjpe_accum_t (pose tables: prepare, statistics, the per-column transform and its way back inside the batch, error and metric launches); 0.1.15: + PLFrameWarp, pl_frame_warp_gather, pl_frame_warp_host (frame gather + resize + the pose augmentation's warp in one launch); 0.1.14: + PLPoseAug, pl_pose_augment_gather, pl_pose_augment_host (seeded train-time pose augmentation inside the batch gather); 0.1.13: + PLClipRecord, pl_grad_norm_scratch_bytes, pl_grad_norm_clip, pl_adamw_flat_clip, pl_adamw_flat_dev_clip, pl_adamw_flat_planes_clip (gradient-norm clipping and non-finite skip on the device); 0.1.12: + pl_pose_errors, pl_pose_errors_host, pl_pose_metrics_scratch_bytes, pl_pose_metrics_accum (evaluation: MPJPE / N-MPJPE / P-MPJPE, PCK counts, per group); 0.1.11: + pl_vit_*_bf16, pl_vit_bf16_pack (MyViT "bf16p": bf16 operand carriers written by their producers); 0.1.10: + pl_vit_* (the MyViT transformer lifter); 0.1.9: + pl_conv2d_planes_fwd_hw, pl_conv2d_planes_wgrad_hw (the stem on the planes GEMM); 0.1.8: + pl_lifter_train_step, pl_lifter_step_carries_adamw; 0.1.7: + pl_workspace_bitmap_format (small-batch layer kernels); 0.1.6: + pl_counter_add; 0.1.5: + pl_flip_pose_ex, pl_flip_w_nhwc (phase5 Flip branch); 0.1.4: + pl_planes_split_strided; 0.1.3: + pl_bn_join_bwd (0.1.2: operand-plane outputs of the BatchNorm / join kernels, pl_gemm_planes_raw) */
+#define PL_VERSION 117 /* 0.1.17: + PLCriterion, pl_pose_loss_scratch_bytes, pl_pose_loss_fwd_bwd, pl_lifter_train_fwd_bwd_crit, pl_lifter_train_step_crit (the train step's criterion: mse, l1, smooth_l1, mpjpe, weighted per joint); 0.1.16: + pl_pose_prepare, pl_pose_stats, pl_pose_affine and their _host forms, pl_pose_stats_scratch_bytes, pl_pose_stats_chunk_rows, pl_pose_augment_gather_t, pl_pose_augment_host_t, pl_pose_errors_t, pl_mpjpe_accum_t (pose tables: prepare, statistics, the per-column transform and its way back inside the batch, error and metric launches); 0.1.15: + PLFrameWarp, pl_frame_warp_gather, pl_frame_warp_host (frame gather + resize + the pose augmentation's warp in one launch); 0.1.14: + PLPoseAug, pl_pose_augment_gather, pl_pose_augment_host (seeded train-time pose augmentation inside the batch gather); 0.1.13: + PLClipRecord, pl_grad_norm_scratch_bytes, pl_grad_norm_clip, pl_adamw_flat_clip, pl_adamw_flat_dev_clip, pl_adamw_flat_planes_clip (gradient-norm clipping and non-finite skip on the device); 0.1.12: + pl_pose_errors, pl_pose_errors_host, pl_pose_metrics_scratch_bytes, pl_pose_metrics_accum (evaluation: MPJPE / N-MPJPE / P-MPJPE, PCK counts, per group); 0.1.11: + pl_vit_*_bf16, pl_vit_bf16_pack (MyViT "bf16p": bf16 operand carriers written by their producers); 0.1.10: + pl_vit_* (the MyViT transformer lifter); 0.1.9: + pl_conv2d_planes_fwd_hw, pl_conv2d_planes_wgrad_hw (the stem on the planes GEMM); 0.1.8: + pl_lifter_train_step, pl_lifter_step_carries_adamw; 0.1.7: + pl_workspace_bitmap_format (small-batch layer kernels); 0.1.6: + pl_counter_add; 0.1.5: + pl_flip_pose_ex, pl_flip_w_nhwc (phase5 Flip branch); 0.1.4: + pl_planes_split_strided; 0.1.3: + pl_bn_join_bwd (0.1.2: operand-plane outputs of the BatchNorm / join kernels, pl_gemm_planes_raw) */
 
 typedef enum PLStatus {
   PL_OK = 0,
@@ -214,6 +214,52 @@ int pl_lifter_step_carries_adamw(const PLDesc* d, int64_t B);
 int pl_lifter_train_step(const PLDesc* d, const float* x, const float* target, int64_t B, void* workspace,
                          size_t workspace_bytes, uint64_t seed, uint64_t step, float* y, float* loss, float* flat_grads,
                          const PLAdamWStep* opt, void* stream);
+
+/* ---- the train step's criterion (PARITY UNPINNED beyond MSELoss / L1Loss: the reference names only those two --
+ * train_1.py:36-37, main.py:404-405, phase5_loop/losses.py:21, train_project.py:39 -- the oracle of the rest is torch) ----
+ * pred, tgt [B][O] fp32, O = J * group (group = coordinates per joint: 3 lifter, 2 projector, 1 = no grouping), d = pred -
+ * tgt, w_j = weights[j] (J device floats, NULL = all ones; they need not sum to anything), s = grad_scale.
+ *
+ *   kind        loss                                        d loss / d pred, element (b, j, g)
+ *   mse         sum w_j d^2 / (B O)                         s 2 w_j d / (B O)
+ *   l1          sum w_j |d| / (B O)                         s w_j sign(d) / (B O), 0 at d = 0
+ *   smooth_l1   sum w_j rho(d) / (B O), rho = d^2 / (2 beta) if |d| < beta else |d| - beta / 2  (nn.SmoothL1Loss, beta > 0)
+ *                                                           s w_j (d / beta or sign(d)) / (B O)
+ *   mpjpe       sum_{b,j} w_j ||d_bj||_2 / (B J)            s w_j d / (||d_bj|| B J), 0 for the whole joint where ||d_bj|| = 0
+ *
+ * smooth_l1 with beta = 0 is rejected (use l1); Huber(delta) = delta * smooth_l1(beta = delta).  O % group != 0 is PL_ESHAPE,
+ * and so is group > 4 on mpjpe.  Non-finite values come out where torch's do: l1's gradient at a NaN d is 0, smooth_l1's is
+ * NaN, one NaN coordinate makes its whole joint's mpjpe gradient NaN.
+ * The gradient in fp32, as computed (d = fl(pred - tgt); every product and quotient below rounded once):
+ *   mse         (d * coef) [* w_j]                          coef = s * 2 / (float)(B O)
+ *   l1          +-coef [* w_j], 0                           coef = s / (float)(B O)
+ *   smooth_l1   |d| >= beta ? +-coef : d * cb  [* w_j]      cb = coef / beta
+ *   mpjpe       d_g * (cw / r)                              coef = s / (float)(B J), cw = coef [* w_j], r = sqrtf(ss),
+ *                                                           ss = d_0 d_0, then fmaf(d_g, d_g, ss) for g = 1 ..
+ * All sums are taken in a fixed order without atomics: the same inputs give the same bits, eagerly or replayed.
+ * A NULL criterion is plain MSE everywhere, and plain MSE runs the kernels and writes the bits it always did. */
+typedef enum PLCriterionKind { PL_CRIT_MSE = 0, PL_CRIT_L1 = 1, PL_CRIT_SMOOTH_L1 = 2, PL_CRIT_MPJPE = 3 } PLCriterionKind;
+typedef struct PLCriterion {
+  int32_t kind;         /* a PLCriterionKind */
+  int32_t group;        /* G >= 1 */
+  float beta;           /* smooth_l1 only */
+  const float* weights; /* device, O / group floats, or NULL */
+} PLCriterion;
+/* The criterion alone: loss (1 device float) and, dpred != NULL, its gradient [B][O], in one launch pair.  Any J.
+ * scratch >= pl_pose_loss_scratch_bytes(B, O, crit).  pl_mse_fwd_bwd is the crit == NULL case of the same implementation. */
+size_t pl_pose_loss_scratch_bytes(int64_t B, int64_t O, const PLCriterion* crit);
+int pl_pose_loss_fwd_bwd(const float* pred, const float* tgt, int64_t B, int64_t O, const PLCriterion* crit, float grad_scale,
+                         float* dpred /* may be NULL */, float* loss, void* scratch, void* stream);
+/* pl_lifter_train_fwd_bwd and pl_lifter_train_step with that criterion in place of MSELoss (crit == NULL: they ARE those
+ * calls): the same (hi, lo) ranges, the same PLAdamWStep, the device step counter ticks at the same point, no launch more
+ * than the MSE step on any route; identical results to pl_lifter_fwd_train, pl_pose_loss_fwd_bwd and pl_lifter_bwd in a row.
+ * out_dim <= 64 routes (the small-batch layer kernels) take J <= 64 by construction. */
+int pl_lifter_train_fwd_bwd_crit(const PLDesc* d, const float* x, const float* target, int64_t B, void* workspace,
+                                 size_t workspace_bytes, uint64_t seed, uint64_t step, const PLCriterion* crit, float* y,
+                                 float* loss, float* flat_grads, int hi, int lo, void* stream);
+int pl_lifter_train_step_crit(const PLDesc* d, const float* x, const float* target, int64_t B, void* workspace,
+                              size_t workspace_bytes, uint64_t seed, uint64_t step, const PLCriterion* crit, float* y,
+                              float* loss, float* flat_grads, const PLAdamWStep* opt, void* stream);
 
 /* The 3-D head forward on NHWC logits [B][H][W][J*64] (depth_dim 64, the conv path's layout): same
  * coords [B*J][3] and stats [B*J][5] as pl_softargmax_fwd(ncoord 3, centred 1).  Model.py:94-133. */
