@@ -104,6 +104,14 @@ class PLFrameWarp(ctypes.Structure):
                 ("epoch", ctypes.c_uint64)]
 
 
+CROP_BBOX, CROP_ROOT = 0, 1
+
+
+class PLPoseCrop(ctypes.Structure):
+    _fields_ = [("margin", ctypes.c_float), ("centre", ctypes.c_int32), ("min_side", ctypes.c_float),
+                ("reserved", ctypes.c_int32), ("Hs", ctypes.c_int64), ("Ws", ctypes.c_int64)]
+
+
 _c = ctypes
 _P = ctypes.c_void_p
 _D = ctypes.POINTER(PLDesc)
@@ -231,6 +239,20 @@ SIGNATURES = {
     "pl_pose_affine_host": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _P, _P, _c.c_int, _P]),
     "pl_frame_warp_gather": (_c.c_int, [_c.POINTER(PLFrameWarp), _P]),
     "pl_frame_warp_host": (_c.c_int, [_c.POINTER(PLFrameWarp)]),
+    "pl_pose_augment_gather_crop": (_c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_int64, _P, _P, _c.POINTER(PLPoseAug), _c.c_uint64,
+                                               _c.POINTER(PLPoseCrop), _P, _P]),
+    "pl_pose_augment_gather_crop_t": (_c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_int64, _P, _P, _c.POINTER(PLPoseAug),
+                                                 _c.c_uint64, _P, _P, _P, _P, _c.POINTER(PLPoseCrop), _P, _P]),
+    "pl_pose_augment_host_crop": (_c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_int64, _P, _P, _c.POINTER(PLPoseAug), _c.c_uint64,
+                                             _c.POINTER(PLPoseCrop), _P]),
+    "pl_pose_augment_host_crop_t": (_c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_int64, _P, _P, _c.POINTER(PLPoseAug), _c.c_uint64,
+                                               _P, _P, _P, _P, _c.POINTER(PLPoseCrop), _P]),
+    "pl_frame_warp_gather_crop": (_c.c_int, [_c.POINTER(PLFrameWarp), _c.POINTER(PLPoseCrop), _P, _P]),
+    "pl_frame_warp_host_crop": (_c.c_int, [_c.POINTER(PLFrameWarp), _c.POINTER(PLPoseCrop), _P]),
+    "pl_pose_crop_boxes": (_c.c_int, [_P, _c.c_int64, _c.POINTER(PLPoseCrop), _P, _P]),
+    "pl_pose_crop_boxes_host": (_c.c_int, [_P, _c.c_int64, _c.POINTER(PLPoseCrop), _P]),
+    "pl_crop_poses": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int, _P, _P]),
+    "pl_crop_poses_host": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int, _P]),
     "pl_flip_tta_pack": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _c.c_int64, _P]),
     "pl_flip_tta_merge": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _c.c_int64, _P]),
     "pl_softargmax_dl_scale": (_c.c_int, [_P, _c.c_int64, _c.c_int, _P, _P]),

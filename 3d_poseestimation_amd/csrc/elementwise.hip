@@ -14,6 +14,7 @@
 #include "bn_pieces.h"
 #include "philox.h"
 #include "pose_augment.h"
+#include "frame_crop.h"
 #include "pose_table.h"
 #include <stdlib.h>
 
@@ -1474,16 +1475,28 @@ __global__ void gather_rows2_kernel(const float* __restrict__ a, int wa, const f
 // XF (pl_pose_augment_gather_t): every output element goes through its column's transform (pose_table.h apply1) after
 // the augmentation, a's 34 columns by (xf.sa, xf.da), b's 51 by (xf.sb, xf.db), either pair nullable.  XF = false is the
 // kernel as it was and reads no field of xf.
+// CROP (the _crop entry points): the person-centred crop of frame_crop.h in front of the augmentation.  Lane e of a group
+// holds elements e and e + 32 of the SOURCE row a (even elements x, odd y), so the extent of the pose is a min / max
+// reduction over the lanes of one parity -- xor shuffles of width 32 by 2, 4, 8, 16 -- and one exchange by 1 for the other
+// coordinate's; the finiteness of all 34 is an AND over all 32 lanes.  Every lane then holds the same box
+// (fc::box_from_extent, the text the frame warp and the host run), crops the source coordinates elem2d reads, and lanes
+// 0..3 write boxes[k][4] = (x0, y0, side, side).  A bad source index: NaN box.  CROP = false is the kernel as it was and
+// reads no field of crop.
 constexpr int PA_LANES = 32;
 struct PoseXf {
   const float *sa, *da, *sb, *db;
 };
-template <bool XF>
+struct PoseCrop {
+  fc::Spec spec;
+  float* boxes;
+};
+template <bool XF, bool CROP>
 __global__ __launch_bounds__(NTHR) void pose_augment_gather_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                                    const int64_t* __restrict__ src_idx,
                                                                    const int64_t* __restrict__ row_id, int64_t n,
                                                                    int64_t table_rows, float* __restrict__ oa,
-                                                                   float* __restrict__ ob, pa::Plan p, PoseXf xf) {
+                                                                   float* __restrict__ ob, pa::Plan p, PoseXf xf,
+                                                                   PoseCrop crop) {
   const int gl = threadIdx.x & (PA_LANES - 1);
   const int64_t k = (int64_t)blockIdx.x * (NTHR / PA_LANES) + (threadIdx.x / PA_LANES);
   if (k >= n) return;                                   // a whole group leaves; no shuffle below crosses a group
@@ -1525,6 +1538,24 @@ __global__ __launch_bounds__(NTHR) void pose_augment_gather_kernel(const float* 
 
   const bool rot = p.max_rot != 0.f;
   const float bad = __int_as_float(0x7fc00000);
+  fc::Box box = {bad, bad, bad};
+  if constexpr (CROP) {
+    const float e0 = ar[gl], e1 = gl < pa::kWA - PA_LANES ? ar[gl + PA_LANES] : e0;
+    float lo = fminf(e0, e1), hi = fmaxf(e0, e1);
+    int fin = fc::finite1(e0) && fc::finite1(e1);
+#pragma unroll
+    for (int m = 2; m < PA_LANES; m <<= 1) {
+      lo = fminf(lo, __shfl_xor(lo, m, PA_LANES));
+      hi = fmaxf(hi, __shfl_xor(hi, m, PA_LANES));
+    }
+#pragma unroll
+    for (int m = 1; m < PA_LANES; m <<= 1) fin &= __shfl_xor(fin, m, PA_LANES);
+    const float lo2 = __shfl_xor(lo, 1, PA_LANES), hi2 = __shfl_xor(hi, 1, PA_LANES);   // the other coordinate's extent
+    const float rx = __shfl(e0, 0, PA_LANES), ry = __shfl(e0, 1, PA_LANES);
+    const bool isx = (gl & 1) == 0;
+    if (ok) box = fc::box_from_extent(crop.spec, isx ? lo : lo2, isx ? hi : hi2, isx ? lo2 : lo, isx ? hi2 : hi, rx, ry, fin != 0);
+    if (gl < 4) crop.boxes[k * 4 + gl] = gl == 0 ? box.x0 : gl == 1 ? box.y0 : box.side;
+  }
   float* oar = oa + k * pa::kWA;
   float* obr = ob + k * pa::kWB;
 #pragma unroll
@@ -1533,7 +1564,14 @@ __global__ __launch_bounds__(NTHR) void pose_augment_gather_kernel(const float* 
     if (e < pa::kWA) {
       const int j = e >> 1, d = e & 1, sj = q.flip ? pa::flip_src_joint(j) : j;
       float v = bad;
-      if (ok) v = pa::elem2d(p, q, d, ar[sj * 2 + d], rot ? ar[sj * 2 + (d ^ 1)] : 0.f, it == 0 ? nz_lo : nz_hi);
+      if (ok) {
+        float sv = ar[sj * 2 + d], su = rot ? ar[sj * 2 + (d ^ 1)] : 0.f;
+        if constexpr (CROP) {
+          sv = fc::crop1(crop.spec, box, d, sv);
+          if (rot) su = fc::crop1(crop.spec, box, d ^ 1, su);
+        }
+        v = pa::elem2d(p, q, d, sv, su, it == 0 ? nz_lo : nz_hi);
+      }
       if constexpr (XF) {
         if (xf.sa) v = pt::apply1(v, xf.sa[e], xf.da[e]);
       }
@@ -1551,6 +1589,31 @@ __global__ __launch_bounds__(NTHR) void pose_augment_gather_kernel(const float* 
       obr[c] = v;
     }
   }
+}
+
+// ---- crop boxes and poses between image and crop coordinates (data.py crop_boxes, crop_poses, uncrop_poses): frame_crop.h ----
+// one thread per pose: its 34 floats, fc::box_of_pose, boxes[k][4] = (x0, y0, side, side)
+__global__ __launch_bounds__(NTHR) void pose_crop_boxes_kernel(const float* __restrict__ a, int64_t n, fc::Spec c,
+                                                               float* __restrict__ boxes) {
+  const int64_t k = (int64_t)blockIdx.x * NTHR + threadIdx.x;
+  if (k >= n) return;
+  const fc::Box b = fc::box_of_pose(c, a + k * pa::kWA);
+  float* o = boxes + k * 4;
+  o[0] = b.x0; o[1] = b.y0; o[2] = b.side; o[3] = b.side;
+}
+
+// one thread per coordinate of p [n][17][2] with boxes [n][4].  INV = false: image-normalised -> crop-normalised (fc::crop1);
+// INV = true: back (fc::uncrop1).  offset = 0 drops x0 / y0: both maps are affine per element, so the backward pass of
+// either is the same instantiation with offset = 0 on the incoming gradient.
+template <bool INV>
+__global__ __launch_bounds__(NTHR) void crop_poses_kernel(const float* __restrict__ p, const float* __restrict__ boxes,
+                                                          int64_t total, fc::Spec c, int offset, float* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * NTHR + threadIdx.x;
+  if (i >= total) return;
+  const float* bx = boxes + (i / pa::kWA) * 4;
+  const fc::Box b = {bx[0], bx[1], bx[2]};
+  const int d = (int)(i & 1);
+  out[i] = INV ? fc::uncrop1(c, b, d, p[i], offset != 0) : fc::crop1(c, b, d, p[i], offset != 0);
 }
 
 // ---- flat AdamW (torch single-tensor update order): AdamWIn, adamw_consts, adamw_one in adamw.h ---------
@@ -2250,20 +2313,52 @@ int pl::pose_aug_plan(const char* fn, const PLPoseAug* aug, uint64_t epoch, pa::
   return PL_OK;
 }
 
-// pose_augment_gather_kernel's only launch site; no transform at all: the plain instantiation
+// The checks of a PLPoseCrop (fn: the entry point named in the message) and the spec frame_crop.h reads; the frame warp
+// (frame_warp.hip) reads it too.  A crop's flip mirrors about the crop's centre, so it carries the frame warp's flip check.
+int pl::crop_spec(const char* fn, const PLPoseCrop* c, const PLPoseAug* aug, fc::Spec* spec) {
+  if (!(fabsf(c->margin) <= 3.402823466e38f) || c->margin <= 0.f)
+    PL_FAIL(PL_EINVAL, "%s: crop margin=%g must be finite and > 0", fn, (double)c->margin);
+  if (!(c->min_side >= 1.f) || c->min_side > fc::kMaxSide || c->min_side != floorf(c->min_side))
+    PL_FAIL(PL_EINVAL, "%s: crop min_side=%g must be an integer in [1, 2^20]", fn, (double)c->min_side);
+  if (c->centre != PL_CROP_BBOX && c->centre != PL_CROP_ROOT) PL_FAIL(PL_EINVAL, "%s: crop centre=%d", fn, (int)c->centre);
+  if (c->Hs <= 0 || c->Ws <= 0 || c->Hs > (1 << 22) || c->Ws > (1 << 22))
+    PL_FAIL(PL_ESHAPE, "%s: crop frame size Hs=%lld Ws=%lld", fn, (long long)c->Hs, (long long)c->Ws);
+  if (aug && aug->p_flip > 0.f && aug->flip_offset != 1.f)
+    PL_FAIL(PL_EINVAL, "%s: flip_offset=%g: a flip of a cropped pose mirrors about the crop's centre (flip_offset 1)", fn,
+            (double)aug->flip_offset);
+  *spec = fc::Spec{c->margin, c->min_side, (float)c->Hs, (float)c->Ws, c->centre == PL_CROP_ROOT};
+  return PL_OK;
+}
+
+static int pose_crop_args(const char* fn, const PLPoseCrop* crop, const PLPoseAug* aug, const float* a, int64_t table_rows,
+                          const float* oa, const float* ob, int64_t n, float* boxes, PoseCrop* pc) {
+  pc->boxes = nullptr;
+  if (!crop) return PL_OK;
+  if (!boxes) PL_FAIL(PL_EINVAL, "%s: null pointer (boxes)", fn);
+  if (!aug) PL_FAIL(PL_EINVAL, "%s: null pointer", fn);
+  PL_TRY(crop_spec(fn, crop, aug, &pc->spec));
+  if (pa_overlap(boxes, n * 4, oa, n * pa::kWA) || pa_overlap(boxes, n * 4, ob, n * pa::kWB) ||
+      pa_overlap(boxes, n * 4, a, table_rows * pa::kWA))
+    PL_FAIL(PL_EINVAL, "%s: aliased pointers (boxes overlaps an output or the source)", fn);
+  pc->boxes = boxes;
+  return PL_OK;
+}
+
+// pose_augment_gather_kernel's only launch site; no transform and no crop at all: the plain instantiation
 static int launch_pose_augment(const char* fn, const float* a, const float* b, const int64_t* src_idx, const int64_t* row_id,
                                int64_t n, int64_t table_rows, float* oa, float* ob, const PLPoseAug* aug, uint64_t epoch,
-                               const PoseXf& xf, void* stream) {
+                               const PoseXf& xf, const PLPoseCrop* crop, float* boxes, void* stream) {
   pa::Plan plan;
+  PoseCrop pc = {};
   PL_TRY(pose_augment_args(fn, a, b, src_idx, row_id, n, table_rows, oa, ob, aug, epoch, &plan));
+  PL_TRY(pose_crop_args(fn, crop, aug, a, table_rows, oa, ob, n, boxes, &pc));
   constexpr int per = NTHR / PA_LANES;
   const dim3 grid((unsigned)((n + per - 1) / per));
-  if (xf.sa || xf.sb)
-    hipLaunchKernelGGL(pose_augment_gather_kernel<true>, grid, dim3(NTHR), 0, (hipStream_t)stream, a, b, src_idx, row_id, n,
-                       table_rows, oa, ob, plan, xf);
-  else
-    hipLaunchKernelGGL(pose_augment_gather_kernel<false>, grid, dim3(NTHR), 0, (hipStream_t)stream, a, b, src_idx, row_id, n,
-                       table_rows, oa, ob, plan, xf);
+  const bool t = xf.sa || xf.sb;
+  auto kernel = pc.boxes ? (t ? pose_augment_gather_kernel<true, true> : pose_augment_gather_kernel<false, true>)
+                         : (t ? pose_augment_gather_kernel<true, false> : pose_augment_gather_kernel<false, false>);
+  hipLaunchKernelGGL(kernel, grid, dim3(NTHR), 0, (hipStream_t)stream, a, b, src_idx, row_id, n, table_rows, oa, ob, plan, xf,
+                     pc);
   PL_CHECK_LAUNCH("pose_augment_gather");
   return PL_OK;
 }
@@ -2278,7 +2373,7 @@ extern "C" int pl_pose_augment_gather(const float* a, const float* b, const int6
                                       int64_t n, int64_t table_rows, float* oa, float* ob, const PLPoseAug* aug,
                                       uint64_t epoch, void* stream) {
   return launch_pose_augment("pl_pose_augment_gather", a, b, src_idx, row_id, n, table_rows, oa, ob, aug, epoch,
-                             PoseXf{nullptr, nullptr, nullptr, nullptr}, stream);
+                             PoseXf{nullptr, nullptr, nullptr, nullptr}, nullptr, nullptr, stream);
 }
 
 extern "C" int pl_pose_augment_gather_t(const float* a, const float* b, const int64_t* src_idx, const int64_t* row_id,
@@ -2287,7 +2382,7 @@ extern "C" int pl_pose_augment_gather_t(const float* a, const float* b, const in
                                         const float* div_b, void* stream) {
   PL_TRY(pose_xf_args("pl_pose_augment_gather_t", sub_a, div_a, sub_b, div_b));
   return launch_pose_augment("pl_pose_augment_gather_t", a, b, src_idx, row_id, n, table_rows, oa, ob, aug, epoch,
-                             PoseXf{sub_a, div_a, sub_b, div_b}, stream);
+                             PoseXf{sub_a, div_a, sub_b, div_b}, nullptr, nullptr, stream);
 }
 
 extern "C" int pl_pose_augment_host(const float* a, const float* b, const int64_t* src_idx, const int64_t* row_id, int64_t n,
@@ -2314,6 +2409,131 @@ extern "C" int pl_pose_augment_host_t(const float* a, const float* b, const int6
   for (int64_t k = 0; k < n; ++k) {
     for (int e = 0; sub_a && e < pa::kWA; ++e) oa[k * pa::kWA + e] = pt::apply1(oa[k * pa::kWA + e], sub_a[e], div_a[e]);
     for (int e = 0; sub_b && e < pa::kWB; ++e) ob[k * pa::kWB + e] = pt::apply1(ob[k * pa::kWB + e], sub_b[e], div_b[e]);
+  }
+  return PL_OK;
+}
+
+extern "C" int pl_pose_augment_gather_crop(const float* a, const float* b, const int64_t* src_idx, const int64_t* row_id,
+                                           int64_t n, int64_t table_rows, float* oa, float* ob, const PLPoseAug* aug,
+                                           uint64_t epoch, const PLPoseCrop* crop, float* boxes, void* stream) {
+  return launch_pose_augment("pl_pose_augment_gather_crop", a, b, src_idx, row_id, n, table_rows, oa, ob, aug, epoch,
+                             PoseXf{nullptr, nullptr, nullptr, nullptr}, crop, boxes, stream);
+}
+
+extern "C" int pl_pose_augment_gather_crop_t(const float* a, const float* b, const int64_t* src_idx, const int64_t* row_id,
+                                             int64_t n, int64_t table_rows, float* oa, float* ob, const PLPoseAug* aug,
+                                             uint64_t epoch, const float* sub_a, const float* div_a, const float* sub_b,
+                                             const float* div_b, const PLPoseCrop* crop, float* boxes, void* stream) {
+  PL_TRY(pose_xf_args("pl_pose_augment_gather_crop_t", sub_a, div_a, sub_b, div_b));
+  return launch_pose_augment("pl_pose_augment_gather_crop_t", a, b, src_idx, row_id, n, table_rows, oa, ob, aug, epoch,
+                             PoseXf{sub_a, div_a, sub_b, div_b}, crop, boxes, stream);
+}
+
+static int pose_augment_host_crop(const char* fn, const float* a, const float* b, const int64_t* src_idx,
+                                  const int64_t* row_id, int64_t n, int64_t table_rows, float* oa, float* ob,
+                                  const PLPoseAug* aug, uint64_t epoch, const PLPoseCrop* crop, float* boxes) {
+  pa::Plan plan;
+  PoseCrop pc = {};
+  PL_TRY(pose_augment_args(fn, a, b, src_idx, row_id, n, table_rows, oa, ob, aug, epoch, &plan));
+  PL_TRY(pose_crop_args(fn, crop, aug, a, table_rows, oa, ob, n, boxes, &pc));
+  for (int64_t k = 0; k < n; ++k) {
+    const int64_t src = src_idx ? src_idx[k] : k;
+    if (src < 0 || src >= table_rows)
+      PL_FAIL(PL_EINVAL, "%s: src_idx[%lld]=%lld is outside the table", fn, (long long)k, (long long)src);
+  }
+  for (int64_t k = 0; k < n; ++k) {
+    const int64_t src = src_idx ? src_idx[k] : k;
+    const float *ar = a + src * pa::kWA, *br = b + src * pa::kWB;
+    if (!pc.boxes) { pa::augment_pose(plan, (uint64_t)row_id[k], ar, br, oa + k * pa::kWA, ob + k * pa::kWB); continue; }
+    fc::Box box;
+    fc::augment_pose(pc.spec, plan, (uint64_t)row_id[k], ar, br, oa + k * pa::kWA, ob + k * pa::kWB, &box);
+    float* o = boxes + k * 4;
+    o[0] = box.x0; o[1] = box.y0; o[2] = box.side; o[3] = box.side;
+  }
+  return PL_OK;
+}
+
+extern "C" int pl_pose_augment_host_crop(const float* a, const float* b, const int64_t* src_idx, const int64_t* row_id,
+                                         int64_t n, int64_t table_rows, float* oa, float* ob, const PLPoseAug* aug,
+                                         uint64_t epoch, const PLPoseCrop* crop, float* boxes) {
+  return pose_augment_host_crop("pl_pose_augment_host_crop", a, b, src_idx, row_id, n, table_rows, oa, ob, aug, epoch, crop,
+                                boxes);
+}
+
+extern "C" int pl_pose_augment_host_crop_t(const float* a, const float* b, const int64_t* src_idx, const int64_t* row_id,
+                                           int64_t n, int64_t table_rows, float* oa, float* ob, const PLPoseAug* aug,
+                                           uint64_t epoch, const float* sub_a, const float* div_a, const float* sub_b,
+                                           const float* div_b, const PLPoseCrop* crop, float* boxes) {
+  PL_TRY(pose_xf_args("pl_pose_augment_host_crop_t", sub_a, div_a, sub_b, div_b));
+  PL_TRY(pose_augment_host_crop("pl_pose_augment_host_crop_t", a, b, src_idx, row_id, n, table_rows, oa, ob, aug, epoch, crop,
+                                boxes));
+  for (int64_t k = 0; k < n; ++k) {
+    for (int e = 0; sub_a && e < pa::kWA; ++e) oa[k * pa::kWA + e] = pt::apply1(oa[k * pa::kWA + e], sub_a[e], div_a[e]);
+    for (int e = 0; sub_b && e < pa::kWB; ++e) ob[k * pa::kWB + e] = pt::apply1(ob[k * pa::kWB + e], sub_b[e], div_b[e]);
+  }
+  return PL_OK;
+}
+
+static int crop_boxes_args(const char* fn, const float* x2d, int64_t n, const PLPoseCrop* crop, float* boxes, fc::Spec* spec) {
+  if (!x2d || !boxes || !crop) PL_FAIL(PL_EINVAL, "%s: null pointer", fn);
+  if (n <= 0 || n > (int64_t)INT32_MAX * NTHR / pa::kWA) PL_FAIL(PL_ESHAPE, "%s: n=%lld", fn, (long long)n);
+  if (pa_overlap(boxes, n * 4, x2d, n * pa::kWA)) PL_FAIL(PL_EINVAL, "%s: aliased pointers (boxes overlaps the poses)", fn);
+  return crop_spec(fn, crop, nullptr, spec);
+}
+
+extern "C" int pl_pose_crop_boxes(const float* x2d, int64_t n, const PLPoseCrop* crop, float* boxes, void* stream) {
+  fc::Spec spec;
+  PL_TRY(crop_boxes_args("pl_pose_crop_boxes", x2d, n, crop, boxes, &spec));
+  hipLaunchKernelGGL(pose_crop_boxes_kernel, dim3((unsigned)((n + NTHR - 1) / NTHR)), dim3(NTHR), 0, (hipStream_t)stream, x2d,
+                     n, spec, boxes);
+  PL_CHECK_LAUNCH("pose_crop_boxes");
+  return PL_OK;
+}
+
+extern "C" int pl_pose_crop_boxes_host(const float* x2d, int64_t n, const PLPoseCrop* crop, float* boxes) {
+  fc::Spec spec;
+  PL_TRY(crop_boxes_args("pl_pose_crop_boxes_host", x2d, n, crop, boxes, &spec));
+  for (int64_t k = 0; k < n; ++k) {
+    const fc::Box b = fc::box_of_pose(spec, x2d + k * pa::kWA);
+    float* o = boxes + k * 4;
+    o[0] = b.x0; o[1] = b.y0; o[2] = b.side; o[3] = b.side;
+  }
+  return PL_OK;
+}
+
+static int crop_poses_args(const char* fn, const float* p, const float* boxes, int64_t n, int64_t Hs, int64_t Ws, float* out,
+                           fc::Spec* spec) {
+  if (!p || !boxes || !out) PL_FAIL(PL_EINVAL, "%s: null pointer", fn);
+  if (n <= 0 || n > (int64_t)INT32_MAX * NTHR / pa::kWA) PL_FAIL(PL_ESHAPE, "%s: n=%lld", fn, (long long)n);
+  if (Hs <= 0 || Ws <= 0 || Hs > (1 << 22) || Ws > (1 << 22))
+    PL_FAIL(PL_ESHAPE, "%s: frame size Hs=%lld Ws=%lld", fn, (long long)Hs, (long long)Ws);
+  if (pa_overlap(out, n * pa::kWA, boxes, n * 4) || pa_overlap(out, n * pa::kWA, p, n * pa::kWA))
+    PL_FAIL(PL_EINVAL, "%s: aliased pointers (out overlaps boxes or p)", fn);
+  *spec = fc::Spec{1.f, 1.f, (float)Hs, (float)Ws, 0};
+  return PL_OK;
+}
+
+extern "C" int pl_crop_poses(const float* p, const float* boxes, int64_t n, int64_t Hs, int64_t Ws, int invert, int offset,
+                             float* out, void* stream) {
+  fc::Spec spec;
+  PL_TRY(crop_poses_args("pl_crop_poses", p, boxes, n, Hs, Ws, out, &spec));
+  const int64_t total = n * pa::kWA;
+  const dim3 grid((unsigned)((total + NTHR - 1) / NTHR));
+  auto kernel = invert ? crop_poses_kernel<true> : crop_poses_kernel<false>;
+  hipLaunchKernelGGL(kernel, grid, dim3(NTHR), 0, (hipStream_t)stream, p, boxes, total, spec, offset, out);
+  PL_CHECK_LAUNCH("crop_poses");
+  return PL_OK;
+}
+
+extern "C" int pl_crop_poses_host(const float* p, const float* boxes, int64_t n, int64_t Hs, int64_t Ws, int invert, int offset,
+                                  float* out) {
+  fc::Spec spec;
+  PL_TRY(crop_poses_args("pl_crop_poses_host", p, boxes, n, Hs, Ws, out, &spec));
+  for (int64_t i = 0; i < n * pa::kWA; ++i) {
+    const float* bx = boxes + (i / pa::kWA) * 4;
+    const fc::Box b = {bx[0], bx[1], bx[2]};
+    const int d = (int)(i & 1);
+    out[i] = invert ? fc::uncrop1(spec, b, d, p[i], offset != 0) : fc::crop1(spec, b, d, p[i], offset != 0);
   }
   return PL_OK;
 }

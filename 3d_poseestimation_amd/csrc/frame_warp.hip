@@ -1,5 +1,6 @@
 // Frame feed (data.py FrameFeeder, augment_frames): gather + bilinear resize + scale + the pose augmentation's flip, rotation,
 // scale and shift of a batch of frames in one launch.  frame_warp.h has the definition; the host entry point runs the same text.
+#include "frame_crop.h"
 #include "frame_warp.h"
 #include "pl_internal.h"
 
@@ -43,17 +44,30 @@ __device__ __forceinline__ void unpack_taps(const TapWords& w, int64_t off, int 
 
 // PACKED (uint8 tables whose base is 4-byte aligned): the packed tap loads above; otherwise frame_warp.h's own loads.  A source
 // index outside [0, N) reads frame 0 and writes a NaN frame.
-template <typename T, bool VEC, bool PACKED>
+// CROP (pl_frame_warp_gather_crop): the per-sample preamble also computes the row's box from its source 2-D pose,
+// x2d[s][34] (row 0 for a bad index), with fc::box_of_pose -- the text the pose launch's box comes from, so the two launches
+// agree bit for bit without talking to each other.  Every thread reads the 34 floats itself: their address depends on
+// blockIdx.y and kernel arguments alone, so they are workgroup-uniform loads (136 bytes per workgroup out of L2) and need
+// neither LDS nor a barrier.  The source position is then fc::source_position; the border rule, the taps and the packed
+// path's guard are unchanged, and a NaN box writes a NaN frame like a bad index.  CROP = false is the kernel as it was and
+// reads neither x2d nor crop.
+template <typename T, bool VEC, bool PACKED, bool CROP>
 __global__ __launch_bounds__(FW_THREADS) void frame_warp_gather_kernel(const T* __restrict__ src, int64_t N,
                                                                        const int64_t* __restrict__ src_idx,
                                                                        const int64_t* __restrict__ row_id,
-                                                                       float* __restrict__ out, fw::Geom g, pa::Plan p) {
+                                                                       float* __restrict__ out, fw::Geom g, pa::Plan p,
+                                                                       const float* __restrict__ x2d, fc::Spec crop) {
   static_assert(!PACKED || sizeof(T) == 1, "packed taps are bytes");
   const int64_t k = blockIdx.y;
   const int64_t s = src_idx ? src_idx[k] : k;
-  const bool ok = s >= 0 && s < N;
+  bool ok = s >= 0 && s < N;
   const bool draws = pa::needs_call(p, 0) || pa::needs_call(p, 1);
   const pa::Pose q = fw::pose_of(p, draws ? (uint64_t)row_id[k] : 0);
+  fc::Box box = {0.f, 0.f, 1.f};
+  if constexpr (CROP) {
+    box = fc::box_of_pose(crop, x2d + (ok ? s : 0) * pa::kWA);
+    ok = ok && fc::box_ok(box);
+  }
   const int64_t frame_elems = (int64_t)g.Hs * g.Ws * 3, frame_off = (ok ? s : 0) * frame_elems;
   float* o = out + k * ((int64_t)g.Ho * g.Wo * 3);
   const int wq = (g.Wo + 3) >> 2, nquad = g.Ho * wq;
@@ -70,7 +84,9 @@ __global__ __launch_bounds__(FW_THREADS) void frame_warp_gather_kernel(const T* 
 #pragma unroll
     for (int t = 0; t < 4; ++t) {         // a pixel past the row's end (tail path) is computed as the row's last and not stored
       float xs, ys;
-      fw::source_position(p, q, g, i, VEC || j0 + t < g.Wo ? j0 + t : g.Wo - 1, xs, ys);
+      const int j = VEC || j0 + t < g.Wo ? j0 + t : g.Wo - 1;
+      if constexpr (CROP) fc::source_position(p, q, g, box, i, j, xs, ys);
+      else fw::source_position(p, q, g, i, j, xs, ys);
       tp[t] = fw::taps_of(g, xs, ys);
       if constexpr (PACKED) {
         off0[t] = frame_off + (tp[t].y0 * g.Ws + tp[t].x0) * 3;
@@ -118,26 +134,39 @@ __global__ __launch_bounds__(FW_THREADS) void frame_warp_gather_kernel(const T* 
   }
 }
 
+// what a crop adds to a launch: the source poses and the spec; x2d null = no crop
+struct WarpCrop {
+  const float* x2d;
+  fc::Spec spec;
+};
+
+// frame_warp_gather_kernel's only launch site
 template <typename T, bool VEC, bool PACKED>
-void launch_frame_warp(const PLFrameWarp& a, const fw::Geom& g, const pa::Plan& p, hipStream_t s) {
+void launch_frame_warp(const PLFrameWarp& a, const fw::Geom& g, const pa::Plan& p, const WarpCrop& c, hipStream_t s) {
   const int wq = (g.Wo + 3) >> 2, nquad = g.Ho * wq, per = FW_THREADS * FW_QUADS;
-  hipLaunchKernelGGL((frame_warp_gather_kernel<T, VEC, PACKED>), dim3((unsigned)((nquad + per - 1) / per), (unsigned)a.n),
-                     dim3(FW_THREADS), 0, s, (const T*)a.src, a.N, a.src_idx, a.row_id, a.out, g, p);
+  auto kernel = c.x2d ? frame_warp_gather_kernel<T, VEC, PACKED, true> : frame_warp_gather_kernel<T, VEC, PACKED, false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((nquad + per - 1) / per), (unsigned)a.n), dim3(FW_THREADS), 0, s, (const T*)a.src,
+                     a.N, a.src_idx, a.row_id, a.out, g, p, c.x2d, c.spec);
 }
 
 template <typename T>
-void warp_host(const PLFrameWarp& a, const fw::Geom& g, const pa::Plan& p) {
+void warp_host(const PLFrameWarp& a, const fw::Geom& g, const pa::Plan& p, const WarpCrop& c) {
   const bool draws = pa::needs_call(p, 0) || pa::needs_call(p, 1);
   for (int64_t k = 0; k < a.n; ++k) {
     const int64_t s = a.src_idx ? a.src_idx[k] : k;
     const pa::Pose q = fw::pose_of(p, draws ? (uint64_t)a.row_id[k] : 0);
     const T* frame = (const T*)a.src + s * ((int64_t)g.Hs * g.Ws * 3);
     float* o = a.out + k * ((int64_t)g.Ho * g.Wo * 3);
+    fc::Box box = {0.f, 0.f, 1.f};
+    if (c.x2d) box = fc::box_of_pose(c.spec, c.x2d + s * pa::kWA);
     for (int i = 0; i < g.Ho; ++i)
       for (int j = 0; j < g.Wo; ++j) {
         float xs, ys;
-        fw::source_position(p, q, g, i, j, xs, ys);
-        fw::sample(frame, g, xs, ys, o + (i * g.Wo + j) * 3);
+        float* px = o + (i * g.Wo + j) * 3;
+        if (!c.x2d) fw::source_position(p, q, g, i, j, xs, ys);
+        else if (fc::box_ok(box)) fc::source_position(p, q, g, box, i, j, xs, ys);
+        else { px[0] = NAN; px[1] = NAN; px[2] = NAN; continue; }
+        fw::sample(frame, g, xs, ys, px);
       }
   }
 }
@@ -178,36 +207,70 @@ int frame_warp_args(const char* fn, const PLFrameWarp* a, fw::Geom* g, pa::Plan*
   return PL_OK;
 }
 
+// the crop's part of the checks, behind frame_warp_args; crop null: *c says "no crop"
+int frame_crop_args(const char* fn, const PLFrameWarp* a, const PLPoseCrop* crop, const float* x2d, WarpCrop* c) {
+  *c = WarpCrop{};
+  if (!crop) return PL_OK;
+  if (!x2d) PL_FAIL(PL_EINVAL, "%s: null pointer (x2d)", fn);
+  PL_TRY(crop_spec(fn, crop, a->aug, &c->spec));
+  if (crop->Hs != a->Hs || crop->Ws != a->Ws)
+    PL_FAIL(PL_ESHAPE, "%s: the crop's frame is %lld x %lld, the table's %lld x %lld", fn, (long long)crop->Hs,
+            (long long)crop->Ws, (long long)a->Hs, (long long)a->Ws);
+  const uintptr_t x0 = (uintptr_t)x2d, x1 = x0 + (uintptr_t)((a->src_idx ? a->N : a->n) * pa::kWA * 4);
+  const uintptr_t o0 = (uintptr_t)a->out, o1 = o0 + (uintptr_t)(a->n * a->Ho * a->Wo * 3 * 4);
+  if (x0 < o1 && o0 < x1) PL_FAIL(PL_EINVAL, "%s: aliased pointers (the output overlaps x2d)", fn);
+  c->x2d = x2d;
+  return PL_OK;
+}
+
+// the body of both device entry points
+int frame_warp_gather(const char* fn, const PLFrameWarp* a, const PLPoseCrop* crop, const float* x2d, void* stream) {
+  fw::Geom g;
+  pa::Plan plan;
+  WarpCrop c;
+  PL_TRY(frame_warp_args(fn, a, &g, &plan));
+  PL_TRY(frame_crop_args(fn, a, crop, x2d, &c));
+  const bool vec = (g.Wo & 3) == 0 && ((uintptr_t)a->out & 15) == 0;
+  const bool u8 = a->src_dtype == PL_FRAME_U8;
+  hipStream_t s = (hipStream_t)stream;
+  if (!u8) vec ? launch_frame_warp<float, true, false>(*a, g, plan, c, s) : launch_frame_warp<float, false, false>(*a, g, plan, c, s);
+  else if (((uintptr_t)a->src & 3) == 0)
+    vec ? launch_frame_warp<uint8_t, true, true>(*a, g, plan, c, s) : launch_frame_warp<uint8_t, false, true>(*a, g, plan, c, s);
+  else vec ? launch_frame_warp<uint8_t, true, false>(*a, g, plan, c, s) : launch_frame_warp<uint8_t, false, false>(*a, g, plan, c, s);
+  PL_CHECK_LAUNCH("frame_warp_gather");
+  return PL_OK;
+}
+
+int frame_warp_host(const char* fn, const PLFrameWarp* a, const PLPoseCrop* crop, const float* x2d) {
+  fw::Geom g;
+  pa::Plan plan;
+  WarpCrop c;
+  PL_TRY(frame_warp_args(fn, a, &g, &plan));
+  PL_TRY(frame_crop_args(fn, a, crop, x2d, &c));
+  for (int64_t k = 0; k < a->n; ++k) {
+    const int64_t s = a->src_idx ? a->src_idx[k] : k;
+    if (s < 0 || s >= a->N) PL_FAIL(PL_EINVAL, "%s: src_idx[%lld]=%lld is outside the table", fn, (long long)k, (long long)s);
+  }
+  if (a->src_dtype == PL_FRAME_U8) warp_host<uint8_t>(*a, g, plan, c);
+  else warp_host<float>(*a, g, plan, c);
+  return PL_OK;
+}
+
 }  // namespace
 }  // namespace pl
 
 using namespace pl;
 
 extern "C" int pl_frame_warp_gather(const PLFrameWarp* a, void* stream) {
-  fw::Geom g;
-  pa::Plan plan;
-  PL_TRY(frame_warp_args("pl_frame_warp_gather", a, &g, &plan));
-  const bool vec = (g.Wo & 3) == 0 && ((uintptr_t)a->out & 15) == 0;
-  const bool u8 = a->src_dtype == PL_FRAME_U8;
-  hipStream_t s = (hipStream_t)stream;
-  if (!u8) vec ? launch_frame_warp<float, true, false>(*a, g, plan, s) : launch_frame_warp<float, false, false>(*a, g, plan, s);
-  else if (((uintptr_t)a->src & 3) == 0)
-    vec ? launch_frame_warp<uint8_t, true, true>(*a, g, plan, s) : launch_frame_warp<uint8_t, false, true>(*a, g, plan, s);
-  else vec ? launch_frame_warp<uint8_t, true, false>(*a, g, plan, s) : launch_frame_warp<uint8_t, false, false>(*a, g, plan, s);
-  PL_CHECK_LAUNCH("frame_warp_gather");
-  return PL_OK;
+  return frame_warp_gather("pl_frame_warp_gather", a, nullptr, nullptr, stream);
 }
 
-extern "C" int pl_frame_warp_host(const PLFrameWarp* a) {
-  fw::Geom g;
-  pa::Plan plan;
-  PL_TRY(frame_warp_args("pl_frame_warp_host", a, &g, &plan));
-  for (int64_t k = 0; k < a->n; ++k) {
-    const int64_t s = a->src_idx ? a->src_idx[k] : k;
-    if (s < 0 || s >= a->N)
-      PL_FAIL(PL_EINVAL, "pl_frame_warp_host: src_idx[%lld]=%lld is outside the table", (long long)k, (long long)s);
-  }
-  if (a->src_dtype == PL_FRAME_U8) warp_host<uint8_t>(*a, g, plan);
-  else warp_host<float>(*a, g, plan);
-  return PL_OK;
+extern "C" int pl_frame_warp_host(const PLFrameWarp* a) { return frame_warp_host("pl_frame_warp_host", a, nullptr, nullptr); }
+
+extern "C" int pl_frame_warp_gather_crop(const PLFrameWarp* a, const PLPoseCrop* crop, const float* x2d, void* stream) {
+  return frame_warp_gather("pl_frame_warp_gather_crop", a, crop, x2d, stream);
+}
+
+extern "C" int pl_frame_warp_host_crop(const PLFrameWarp* a, const PLPoseCrop* crop, const float* x2d) {
+  return frame_warp_host("pl_frame_warp_host_crop", a, crop, x2d);
 }

@@ -461,6 +461,9 @@ int launch_fill(float* p, int64_t n, float v, hipStream_t s);
 // pose_augment.h and frame_warp.h read
 namespace pa { struct Plan; }
 int pose_aug_plan(const char* fn, const PLPoseAug* aug, uint64_t epoch, pa::Plan* plan);
+// the checks of a PLPoseCrop (and of the flip of the PLPoseAug that goes with it, nullable) and the spec frame_crop.h reads
+namespace fc { struct Spec; }
+int crop_spec(const char* fn, const PLPoseCrop* crop, const PLPoseAug* aug, fc::Spec* spec);
 // the flat AdamW step over p, g, m, v [n] (adamw_kernel's only launch site).  in: the kernel's own argument block (adamw.h);
 // lr_dev / t_dev, the plane fields (adamw_planes) and the clip record are the optional parts, zero when absent
 struct AdamWArgs {

@@ -27,6 +27,12 @@ sample on DataLoader workers (H36_dataset.py:129-131 `cv2.resize(frame,(256,256)
 uint8 table -- a quarter of the fp32 bytes, resident or pinned -- and one launch (pl_frame_warp_gather, csrc/frame_warp.h)
 gathers, resizes, scales and warps a batch by the very draws its poses get: frame, 2-D pose and 3-D pose of a dataset row
 always agree.
+
+Person-centred crops (`PersonCrop`, `crop=`): the reference's "cropping using the gt 2d as bounding box" (H36_dataset.py:120-126)
+always selects the whole frame.  With a crop both launches take a square box from the row's source 2-D pose (csrc/frame_crop.h,
+the same inline text in both, so they agree bit for bit): the frame launch resizes the box instead of the frame, the pose
+launch puts the 2-D pose into crop coordinates in front of the augmentation and writes the boxes, which `uncrop_poses` /
+`crop_poses` (train.py) use to move predictions between crop and image coordinates.
 """
 import ctypes
 import dataclasses
@@ -127,9 +133,71 @@ class PoseAugment:
                               self.jitter_sigma, self.centre[0], self.centre[1], self.seed)
 
 
-def _augment_launch(a, b, src_idx, row_ids, nb, table_rows, oa, ob, aug_struct, epoch, xf=None):
+@dataclasses.dataclass(frozen=True)
+class PersonCrop:
+    """Person-centred square crop taken from each row's 2-D pose (csrc/frame_crop.h has the definition).
+
+    The box of a row comes from its SOURCE image-normalised 2-D pose and the source frame size: its side is `margin` times
+    the larger extent of the 17 joints in source pixels, rounded up, at least `min_side`; it is centred on the middle of the
+    extent (centre="bbox") or on joint 0 (centre="root", what the reference's dead crop aimed at), and its corner is rounded
+    to whole source pixels.  The part of a box outside the frame is `fill`.  The 2-D pose goes into crop coordinates
+    ([0, 1] across the box) in front of every augmentation stage, so a PoseAugment's centre (0.5, 0.5) is the crop's centre;
+    the 3-D pose is untouched.  A pose with a non-finite coordinate, or a side above 2^20, gives a NaN box, frame and 2-D pose."""
+    margin: float = 1.25
+    centre: str = "bbox"
+    min_side: int = 8
+
+    def __post_init__(self):
+        margin = float(self.margin)
+        if not math.isfinite(margin) or margin <= 0.0:
+            raise ValueError(f"margin must be finite and > 0, got {margin}")
+        object.__setattr__(self, "margin", margin)
+        if self.centre not in ("bbox", "root"):
+            raise ValueError(f"centre is 'bbox' or 'root', got {self.centre!r}")
+        if float(self.min_side) != int(self.min_side) or not 1 <= int(self.min_side) <= 2 ** 20:
+            raise ValueError(f"min_side is an integer in [1, 2^20], got {self.min_side}")
+        object.__setattr__(self, "min_side", int(self.min_side))
+
+    def struct(self, frame_hw):
+        """The PLPoseCrop the library reads, for source frames of frame_hw = (Hs, Ws)."""
+        hs, ws = (int(v) for v in frame_hw)
+        if hs <= 0 or ws <= 0:
+            raise ValueError("frame_hw is (Hs, Ws), both positive")
+        return _lib.PLPoseCrop(self.margin, _lib.CROP_ROOT if self.centre == "root" else _lib.CROP_BBOX, float(self.min_side),
+                               0, hs, ws)
+
+
+def _crop_struct(crop, frame_hw, augment=None):
+    """The PLPoseCrop of a PersonCrop (None: no crop), with the check a flip needs."""
+    if crop is None:
+        return None
+    if not isinstance(crop, PersonCrop):
+        raise TypeError("crop must be a PersonCrop or None")
+    if frame_hw is None:
+        raise ValueError("a crop needs frame_hw = (Hs, Ws), the source frames' size")
+    if augment is not None and augment.p_flip > 0.0 and augment.flip_offset != 1.0:
+        raise ValueError("a flip of a cropped pose mirrors about the crop's centre: p_flip > 0 needs flip_offset = 1, got "
+                         f"{augment.flip_offset}")
+    return crop.struct(frame_hw)
+
+
+def _augment_launch(a, b, src_idx, row_ids, nb, table_rows, oa, ob, aug_struct, epoch, xf=None, crop=None, boxes=None):
     """One pl_pose_augment_gather on torch's current stream; src_idx None = the rows of a, b in order.
-    xf: (sub_a, div_a, sub_b, div_b) device pointers of the transforms (_transforms) -> pl_pose_augment_gather_t."""
+    xf: (sub_a, div_a, sub_b, div_b) device pointers of the transforms (_transforms) -> pl_pose_augment_gather_t.
+    crop: a PLPoseCrop and boxes its (nb, 4) output -> the _crop forms of the same two entry points."""
+    if crop is not None:
+        L, src = _lib.lib(), src_idx.data_ptr() if src_idx is not None else None
+        if xf is not None:
+            _lib.check(L.pl_pose_augment_gather_crop_t(a.data_ptr(), b.data_ptr(), src, row_ids.data_ptr(), nb, table_rows,
+                                                       oa.data_ptr(), ob.data_ptr(), ctypes.byref(aug_struct), int(epoch),
+                                                       xf[0], xf[1], xf[2], xf[3], ctypes.byref(crop), boxes.data_ptr(),
+                                                       _lib.current_stream_ptr()), "pl_pose_augment_gather_crop_t")
+        else:
+            _lib.check(L.pl_pose_augment_gather_crop(a.data_ptr(), b.data_ptr(), src, row_ids.data_ptr(), nb, table_rows,
+                                                     oa.data_ptr(), ob.data_ptr(), ctypes.byref(aug_struct), int(epoch),
+                                                     ctypes.byref(crop), boxes.data_ptr(), _lib.current_stream_ptr()),
+                       "pl_pose_augment_gather_crop")
+        return
     if xf is not None:
         _lib.check(_lib.lib().pl_pose_augment_gather_t(a.data_ptr(), b.data_ptr(),
                                                        src_idx.data_ptr() if src_idx is not None else None,
@@ -153,16 +221,20 @@ def _transforms(transform_2d, transform_3d, device):
     return (sa, da, sb, db), (keep_a, keep_b)
 
 
-def augment_poses(y1, y2, augment, row_ids=None, epoch=0, transform_2d=None, transform_3d=None):
+def augment_poses(y1, y2, augment, row_ids=None, epoch=0, transform_2d=None, transform_3d=None, crop=None, frame_hw=None):
     """`augment` applied to a batch that came from somewhere else: y1 (B,17,2), y2 (B,17,3) fp32 device tensors -> new
     (y1, y2) tensors; the inputs are untouched and nothing synchronises (one launch on the current stream).
 
     A pose's draws are a function of (augment.seed, epoch, row id) only.  Pass the poses' DATASET indices as `row_ids`
     (int64, B of them) -- or at least an `epoch` that changes from call to call -- to get fresh draws: with the default
     row_ids = arange(B) and a fixed epoch, pose k of every batch is flipped, turned and jittered the same way.
-    transform_2d / transform_3d: PoseTransforms applied to the augmented poses in the same launch."""
+    transform_2d / transform_3d: PoseTransforms applied to the augmented poses in the same launch.
+    crop: a PersonCrop, with frame_hw = (Hs, Ws) of the source frames: y1 goes into the crop coordinates of its own box in
+    front of the augmentation (a transform_2d then needs statistics of crop coordinates) and the call returns
+    (y1, y2, boxes), boxes (B,4) fp32 = (x0, y0, side, side) in source pixels -- what uncrop_poses takes."""
     if not isinstance(augment, PoseAugment):
         raise TypeError("augment must be a PoseAugment")
+    crop_s = _crop_struct(crop, frame_hw, augment)
     _lib.require_device_tensor(y1, "y1")
     _lib.require_device_tensor(y2, "y2")
     if y1.dim() != 3 or y2.dim() != 3 or tuple(y1.shape[1:]) != (17, 2) or tuple(y2.shape[1:]) != (17, 3) \
@@ -177,9 +249,27 @@ def augment_poses(y1, y2, augment, row_ids=None, epoch=0, transform_2d=None, tra
             raise ValueError("row_ids holds one dataset index per pose")
     oa, ob = torch.empty_like(y1), torch.empty_like(y2)
     xf, _keep = _transforms(transform_2d, transform_3d, y1.device)
+    boxes = torch.empty((nb, 4), dtype=torch.float32, device=y1.device) if crop_s is not None else None
     with _lib.on_device(y1.device):
-        _augment_launch(y1, y2, None, row_ids, nb, nb, oa, ob, augment.struct(), epoch, xf)
-    return oa, ob
+        _augment_launch(y1, y2, None, row_ids, nb, nb, oa, ob, augment.struct(), epoch, xf, crop_s, boxes)
+    return (oa, ob) if boxes is None else (oa, ob, boxes)
+
+
+def crop_boxes(x2d, crop, frame_hw):
+    """The boxes (B,4) fp32 = (x0, y0, side, side), in source pixels, that `crop` (a PersonCrop) takes from the
+    image-normalised 2-D poses x2d (B,17,2) of frames of frame_hw = (Hs, Ws): the boxes the feeder's two launches compute for
+    the same rows, bit for bit.  One launch on the current stream."""
+    crop_s = _crop_struct(crop, frame_hw)
+    if crop_s is None:
+        raise TypeError("crop must be a PersonCrop")
+    _lib.require_device_tensor(x2d, "x2d")
+    if x2d.dim() != 3 or tuple(x2d.shape[1:]) != (17, 2) or x2d.shape[0] == 0:
+        raise ValueError("crop_boxes expects x2d (B,17,2), B >= 1")
+    boxes = torch.empty((x2d.shape[0], 4), dtype=torch.float32, device=x2d.device)
+    with _lib.on_device(x2d.device):
+        _lib.check(_lib.lib().pl_pose_crop_boxes(x2d.data_ptr(), x2d.shape[0], ctypes.byref(crop_s), boxes.data_ptr(),
+                                                 _lib.current_stream_ptr()), "pl_pose_crop_boxes")
+    return boxes
 
 
 class PoseFeeder:
@@ -189,10 +279,13 @@ class PoseFeeder:
     dataset rows as the identity of the draws (None: the plain gather).
     transform_2d / transform_3d: PoseTransforms (pose_table) applied to every batch after the augmentation, in the same
     launch; the tables stay raw.  With a transform and no augmentation the batch is built by the augmented gather with
-    every stage off: a copy plus the transform, still one launch."""
+    every stage off: a copy plus the transform, still one launch.
+    crop: a PersonCrop with frame_hw = (Hs, Ws) of the source frames: the batches are (y1, y2, boxes), y1 in the crop
+    coordinates of its own box (in front of the augmentation, same launch) and boxes (b,4) fp32 on the device."""
 
     def __init__(self, x2d, y3d, batch_size, *, device="cuda", shuffle=True, seed=0, drop_last=False,
-                 rank=0, world=1, resident=True, prefetch=2, augment=None, transform_2d=None, transform_3d=None):
+                 rank=0, world=1, resident=True, prefetch=2, augment=None, transform_2d=None, transform_3d=None,
+                 crop=None, frame_hw=None):
         x2d, y3d = torch.as_tensor(x2d), torch.as_tensor(y3d)
         if x2d.shape[0] != y3d.shape[0] or x2d.shape[0] == 0:
             raise ValueError("x2d and y3d need the same, non-zero number of poses")
@@ -218,6 +311,14 @@ class PoseFeeder:
             self._xf, self._xf_keep = _transforms(transform_2d, transform_3d, self.device)
             if self._aug is None:
                 self._aug = PoseAugment().struct()          # every stage off: the kernel copies, then transforms
+        self.crop = crop
+        self._crop = _crop_struct(crop, frame_hw, augment)
+        if self._crop is not None:
+            if self.shape_a != (17, 2) or self.shape_b != (17, 3):
+                raise ValueError(f"a crop rides in the augmented gather, defined for (N,17,2)/(N,17,3) tables, got "
+                                 f"{tuple(x2d.shape)} / {tuple(y3d.shape)}")
+            if self._aug is None:
+                self._aug = PoseAugment().struct()          # every stage off: the kernel crops and copies
         a = x2d.reshape(self.n, -1).to(torch.float32).contiguous()        # train_1.py:80 .float()
         b = y3d.reshape(self.n, -1).to(torch.float32).contiguous()
         self.wa, self.wb = a.shape[1], b.shape[1]
@@ -257,13 +358,17 @@ class PoseFeeder:
             with _lib.on_device(self.device):
                 if self._aug is not None:           # the permutation slice is both the source row and the draws' identity
                     idx = idx_all[at:at + nb]
-                    _augment_launch(self.a, self.b, idx, idx, nb, self.n, oa, ob, self._aug, epoch, self._xf)
+                    boxes = torch.empty((nb, 4), dtype=torch.float32, device=self.device) if self._crop is not None else None
+                    _augment_launch(self.a, self.b, idx, idx, nb, self.n, oa, ob, self._aug, epoch, self._xf, self._crop, boxes)
                 else:
                     _lib.check(L.pl_gather_rows2(self.a.data_ptr(), self.wa, self.b.data_ptr(), self.wb,
                                                  idx_all[at:at + nb].data_ptr(), nb, self.n, oa.data_ptr(), ob.data_ptr(),
                                                  _lib.current_stream_ptr()), "pl_gather_rows2")
             at += nb
-            yield oa, ob
+            if self._crop is not None:
+                yield oa, ob, boxes
+            else:
+                yield oa, ob
 
     def _iter_streamed(self):
         batches, epoch = self._indices(), self.epoch
@@ -309,13 +414,17 @@ class PoseFeeder:
                 di.record_stream(torch.cuda.current_stream(self.device))
                 nb = di.numel()
                 oa, ob = torch.empty_like(da), torch.empty_like(db)
+                boxes = torch.empty((nb, 4), dtype=torch.float32, device=self.device) if self._crop is not None else None
                 with _lib.on_device(self.device):
-                    _augment_launch(da, db, None, di, nb, nb, oa, ob, self._aug, epoch, self._xf)
+                    _augment_launch(da, db, None, di, nb, nb, oa, ob, self._aug, epoch, self._xf, self._crop, boxes)
                 da, db = oa, ob
             if nxt < len(batches):
                 inflight.append(launch(nxt, batches[nxt]))
                 nxt += 1
-            yield da, db
+            if self._crop is not None:
+                yield da, db, boxes
+            else:
+                yield da, db
 
 
 def _frame_augment_struct(augment):
@@ -345,26 +454,36 @@ def _frame_geometry(frames, out_hw, scale, fill):
     return (_lib.FRAME_U8 if u8 else _lib.FRAME_F32), (ho, wo), float(scale), float(fill)
 
 
-def _frame_launch(table, code, src_idx, row_ids, nb, out, scale, fill, aug_struct, epoch):
-    """One pl_frame_warp_gather on torch's current stream; src_idx None = the frames of `table` in order."""
+def _frame_launch(table, code, src_idx, row_ids, nb, out, scale, fill, aug_struct, epoch, crop=None, x2d=None):
+    """One pl_frame_warp_gather on torch's current stream; src_idx None = the frames of `table` in order.
+    crop: a PLPoseCrop and x2d the source 2-D poses, indexed like the frames -> pl_frame_warp_gather_crop."""
     args = _lib.PLFrameWarp(table.data_ptr(), code, 3, table.shape[0], table.shape[1], table.shape[2],
                             src_idx.data_ptr() if src_idx is not None else None,
                             row_ids.data_ptr() if row_ids is not None else None, nb, out.data_ptr(), out.shape[1],
                             out.shape[2], scale, fill, ctypes.pointer(aug_struct) if aug_struct is not None else None,
                             int(epoch))
+    if crop is not None:
+        _lib.check(_lib.lib().pl_frame_warp_gather_crop(ctypes.byref(args), ctypes.byref(crop), x2d.data_ptr(),
+                                                        _lib.current_stream_ptr()), "pl_frame_warp_gather_crop")
+        return
     _lib.check(_lib.lib().pl_frame_warp_gather(ctypes.byref(args), _lib.current_stream_ptr()), "pl_frame_warp_gather")
 
 
-def augment_frames(frames, augment, row_ids=None, epoch=0, out_hw=(256, 256), fill=0.0, scale=None):
+def augment_frames(frames, augment, row_ids=None, epoch=0, out_hw=(256, 256), fill=0.0, scale=None, crop=None, x2d=None):
     """`augment` applied to the frames of a batch: frames [B,Hs,Ws,3] uint8 or fp32 on the device -> a new [B,Ho,Wo,3] fp32
     tensor, resized (bilinear, cv2.resize's half-pixel convention), multiplied by `scale` (default 1/256 for uint8, the
     reference's frame/256.0, and 1 for fp32) and flipped, turned, scaled and shifted exactly as augment_poses moves the 2-D
     poses of the same (row_ids, epoch); pixels whose source lies outside the frame are `fill`.  One launch on the current
-    stream, nothing synchronises.  row_ids and epoch as in augment_poses; augment=None is the plain resize."""
+    stream, nothing synchronises.  row_ids and epoch as in augment_poses; augment=None is the plain resize.
+    crop: a PersonCrop, with x2d (B,17,2) the frames' SOURCE image-normalised 2-D poses (not augment_poses' output): each
+    frame is cropped to its pose's box before everything else -- the box augment_poses(crop=) and crop_boxes return."""
     aug = _frame_augment_struct(augment)
     if not isinstance(frames, torch.Tensor):
         raise TypeError("frames must be a tensor")
     code, (ho, wo), scale, fill = _frame_geometry(frames, out_hw, scale, fill)
+    crop_s = _crop_struct(crop, frames.shape[1:3])
+    if crop_s is not None and x2d is None:
+        raise ValueError("a crop needs x2d, the frames' source 2-D poses")
     _lib.require_device_tensor(frames, "frames", dtype=frames.dtype)
     nb = frames.shape[0]
     if row_ids is None:
@@ -373,9 +492,13 @@ def augment_frames(frames, augment, row_ids=None, epoch=0, out_hw=(256, 256), fi
         row_ids = torch.as_tensor(row_ids).to(device=frames.device, dtype=torch.int64).contiguous()
         if row_ids.shape != (nb,):
             raise ValueError("row_ids holds one dataset index per frame")
+    if crop_s is not None:
+        _lib.require_device_tensor(x2d, "x2d")
+        if tuple(x2d.shape) != (nb, 17, 2) or x2d.device != frames.device:
+            raise ValueError("x2d holds one (17,2) pose per frame, on the frames' device")
     out = torch.empty((nb, ho, wo, 3), dtype=torch.float32, device=frames.device)
     with _lib.on_device(frames.device):
-        _frame_launch(frames, code, None, row_ids, nb, out, scale, fill, aug, epoch)
+        _frame_launch(frames, code, None, row_ids, nb, out, scale, fill, aug, epoch, crop_s, x2d)
     return out
 
 
@@ -385,16 +508,27 @@ class FrameFeeder:
     (epoch_indices) and the identity of the draws -- (augment.seed, epoch, dataset row) -- are the same for all three
     tensors.  resident: the table on the device, two launches per batch (poses, frames); else the table in pinned memory,
     batches gathered into pinned staging and copied on a side stream `prefetch` batches ahead, the warp on the consumer's
-    stream behind the copy's event.  transform_2d / transform_3d: as in PoseFeeder, on the pose outputs; frames are unchanged."""
+    stream behind the copy's event.  transform_2d / transform_3d: as in PoseFeeder, on the pose outputs; frames are unchanged.
+    crop: a PersonCrop: the batches are (frame, y1, y2, boxes).  Each frame is the person-centred square box of its row,
+    taken from the row's source 2-D pose, resized to out_hw -- still the same two launches, each of which computes the box
+    for itself from the same text; y1 is in crop coordinates ([0, 1] across the box), and so is what Model_2D learns to
+    predict; boxes (b,4) fp32 = (x0, y0, side, side) in source pixels stays on the device.  Predictions go back to image
+    coordinates with uncrop_poses(pred, boxes, frame_hw) (differentiable) before the lifter, the metrics or TriangleLoss see
+    them, and a projector's output goes into crop coordinates with crop_poses; cycle_step itself knows nothing about crops --
+    INTEGRATION.md has the wrapper that composes the two.  The streamed mode stages the batch's x2d rows beside its frames."""
 
     def __init__(self, frames, x2d, y3d, batch_size, *, out_hw=(256, 256), augment=None, device="cuda", shuffle=True,
-                 seed=0, drop_last=False, rank=0, world=1, resident=True, prefetch=2, transform_2d=None, transform_3d=None):
+                 seed=0, drop_last=False, rank=0, world=1, resident=True, prefetch=2, transform_2d=None, transform_3d=None,
+                 crop=None):
         self._aug = _frame_augment_struct(augment)
         frames = torch.as_tensor(frames)
         self._code, self.out_hw, self._scale, self._fill = _frame_geometry(frames, out_hw, None, 0.0)
+        self.crop = crop
+        self._crop = _crop_struct(crop, frames.shape[1:3], augment)
         self.poses = PoseFeeder(x2d, y3d, batch_size, device=device, shuffle=shuffle, seed=seed, drop_last=drop_last,
                                 rank=rank, world=world, resident=resident, prefetch=prefetch, augment=augment,
-                                transform_2d=transform_2d, transform_3d=transform_3d)
+                                transform_2d=transform_2d, transform_3d=transform_3d, crop=crop,
+                                frame_hw=frames.shape[1:3] if crop is not None else None)
         if frames.shape[0] != self.poses.n:
             raise ValueError("frames, x2d and y3d need the same number of rows")
         self.device, self.resident, self.prefetch = self.poses.device, resident, self.poses.prefetch
@@ -413,13 +547,14 @@ class FrameFeeder:
 
     def __iter__(self):
         frames = self._iter_resident() if self.resident else self._iter_streamed()
-        for frame, (y1, y2) in zip(frames, self.poses):
-            yield frame, y1, y2
+        for frame, pose_batch in zip(frames, self.poses):      # (y1, y2), with a crop (y1, y2, boxes)
+            yield (frame,) + tuple(pose_batch)
 
-    def _warp(self, table, src_idx, row_ids, nb, epoch):
+    def _warp(self, table, src_idx, row_ids, nb, epoch, x2d=None):
         out = torch.empty((nb,) + self.out_hw + (3,), dtype=torch.float32, device=self.device)
         with _lib.on_device(self.device):
-            _frame_launch(table, self._code, src_idx, row_ids, nb, out, self._scale, self._fill, self._aug, epoch)
+            _frame_launch(table, self._code, src_idx, row_ids, nb, out, self._scale, self._fill, self._aug, epoch,
+                          self._crop, x2d)
         return out
 
     def _iter_resident(self):
@@ -432,7 +567,7 @@ class FrameFeeder:
         for nb in sizes:                                  # the permutation slice is both the source frame and the draws' identity
             idx = idx_all[at:at + nb]
             at += nb
-            yield self._warp(self.frames, idx, idx, nb, epoch)
+            yield self._warp(self.frames, idx, idx, nb, epoch, self.poses.a if self._crop is not None else None)
 
     def _iter_streamed(self):
         batches, epoch = self.poses._indices(), self.poses.epoch
@@ -440,6 +575,8 @@ class FrameFeeder:
         slots, inflight = self.prefetch + 1, []
         stage = [torch.empty((bs,) + tuple(self.frames.shape[1:]), dtype=self.frames.dtype).pin_memory() for _ in range(slots)]
         stage_idx = [torch.empty(bs, dtype=torch.int64).pin_memory() for _ in range(slots)]
+        # a crop: the batch's source 2-D poses (136 B per frame) ride the same copy; the warp takes its boxes from them
+        stage_x2d = [torch.empty(bs, self.poses.wa).pin_memory() for _ in range(slots)] if self._crop is not None else None
         free_events = [None] * slots                      # consumer done with the slot's previous batch
 
         def launch(k, idx):
@@ -450,25 +587,31 @@ class FrameFeeder:
                 free_events[slot].synchronize()           # staging buffer no longer being copied from
             torch.index_select(self.frames, 0, idx, out=hf)
             hi.copy_(idx)
+            if stage_x2d is not None:
+                hx = stage_x2d[slot][:nb]
+                torch.index_select(self.poses.a, 0, idx, out=hx)
             with torch.cuda.stream(self._copy_stream):
                 df = hf.to(self.device, non_blocking=True)
                 di = hi.to(self.device, non_blocking=True)
+                dx = hx.to(self.device, non_blocking=True) if stage_x2d is not None else None
                 ev = torch.cuda.Event()
                 ev.record(self._copy_stream)
             free_events[slot] = ev
-            return df, di, ev
+            return df, di, dx, ev
 
         nxt = 0
         while nxt < len(batches) and len(inflight) < self.prefetch:
             inflight.append(launch(nxt, batches[nxt]))
             nxt += 1
         while inflight:
-            df, di, ev = inflight.pop(0)
+            df, di, dx, ev = inflight.pop(0)
             cur = torch.cuda.current_stream(self.device)
             cur.wait_event(ev)
             df.record_stream(cur)
             di.record_stream(cur)
-            out = self._warp(df, None, di, di.numel(), epoch)     # one launch on the consumer's stream, behind the event wait
+            if dx is not None:
+                dx.record_stream(cur)
+            out = self._warp(df, None, di, di.numel(), epoch, dx)     # one launch on the consumer's stream, behind the event wait
             if nxt < len(batches):
                 inflight.append(launch(nxt, batches[nxt]))
                 nxt += 1

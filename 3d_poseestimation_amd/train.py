@@ -125,6 +125,49 @@ def flip_average(a, b):
     return _FlipAvgFn.apply(a, b, 0.5)
 
 
+def _crop_map(p, boxes, frame_hw, invert, offset):
+    out = torch.empty_like(p)
+    with _lib.on_device(p.device):
+        rc = _lib.lib().pl_crop_poses(p.data_ptr(), boxes.data_ptr(), p.shape[0], int(frame_hw[0]), int(frame_hw[1]), invert,
+                                      offset, out.data_ptr(), _lib.current_stream_ptr())
+    _lib.check(rc, "pl_crop_poses")
+    return out
+
+
+class _CropPosesFn(torch.autograd.Function):
+    """(B,17,2) poses between image and crop coordinates (csrc/frame_crop.h crop1 / uncrop1).  Both maps are affine per
+    element, so the backward pass is the same kernel on the gradient without the offset."""
+
+    @staticmethod
+    def forward(ctx, p, boxes, frame_hw, invert):
+        p, boxes = p.contiguous(), boxes.detach().contiguous()
+        _lib.require_device_tensor(p, "p")
+        _lib.require_device_tensor(boxes, "boxes")
+        if p.dim() != 3 or tuple(p.shape[1:]) != (17, 2) or p.shape[0] == 0 or tuple(boxes.shape) != (p.shape[0], 4) \
+                or boxes.device != p.device:
+            raise ValueError("crop_poses / uncrop_poses expect p (B,17,2) and boxes (B,4) on one device, B >= 1")
+        ctx.boxes, ctx.frame_hw, ctx.invert = boxes, frame_hw, invert
+        return _crop_map(p, boxes, frame_hw, invert, 1)
+
+    @staticmethod
+    def backward(ctx, g):
+        dp = _crop_map(g.contiguous(), ctx.boxes, ctx.frame_hw, ctx.invert, 0) if ctx.needs_input_grad[0] else None
+        return dp, None, None, None
+
+
+def crop_poses(p, boxes, frame_hw):
+    """Image-normalised 2-D poses p (B,17,2) -> the crop coordinates of boxes (B,4) = (x0, y0, side, side) (FrameFeeder(crop=),
+    augment_poses(crop=), crop_boxes) in frames of frame_hw = (Hs, Ws): x' = (x Ws - x0) / side, y' = (y Hs - y0) / side.
+    Differentiable in p; one launch.  What a projector's output goes through before it meets Model_2D's."""
+    return _CropPosesFn.apply(p, boxes, tuple(frame_hw), 0)
+
+
+def uncrop_poses(p, boxes, frame_hw):
+    """The way back: crop coordinates -> image-normalised, x = (x' side + x0) / Ws, y = (y' side + y0) / Hs.  Differentiable
+    in p; one launch.  Model_2D's output on cropped frames goes through this before the lifter, the metrics or TriangleLoss."""
+    return _CropPosesFn.apply(p, boxes, tuple(frame_hw), 1)
+
+
 def flip_frames_nhwc(frame_nhwc):
     """torch.flip(frame, (3,)) of train_5 copy.py:176 (width of the NCHW frame) on the NHWC frames this path keeps."""
     f = frame_nhwc.contiguous()

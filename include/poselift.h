@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define PL_VERSION 117 /* 0.1.17: + PLCriterion, pl_pose_loss_scratch_bytes, pl_pose_loss_fwd_bwd, pl_lifter_train_fwd_bwd_crit, pl_lifter_train_step_crit (the train step's criterion: mse, l1, smooth_l1, mpjpe, weighted per joint); 0.1.16: + pl_pose_prepare, pl_pose_stats, pl_pose_affine and their _host forms, pl_pose_stats_scratch_bytes, pl_pose_stats_chunk_rows, pl_pose_augment_gather_t, pl_pose_augment_host_t, pl_pose_errors_t, pl_mpjpe_accum_t (pose tables: prepare, statistics, the per-column transform and its way back inside the batch, error and metric launches); 0.1.15: + PLFrameWarp, pl_frame_warp_gather, pl_frame_warp_host (frame gather + resize + the pose augmentation's warp in one launch); 0.1.14: + PLPoseAug, pl_pose_augment_gather, pl_pose_augment_host (seeded train-time pose augmentation inside the batch gather); 0.1.13: + PLClipRecord, pl_grad_norm_scratch_bytes, pl_grad_norm_clip, pl_adamw_flat_clip, pl_adamw_flat_dev_clip, pl_adamw_flat_planes_clip (gradient-norm clipping and non-finite skip on the device); 0.1.12: + pl_pose_errors, pl_pose_errors_host, pl_pose_metrics_scratch_bytes, pl_pose_metrics_accum (evaluation: MPJPE / N-MPJPE / P-MPJPE, PCK counts, per group); 0.1.11: + pl_vit_*_bf16, pl_vit_bf16_pack (MyViT "bf16p": bf16 operand carriers written by their producers); 0.1.10: + pl_vit_* (the MyViT transformer lifter); 0.1.9: + pl_conv2d_planes_fwd_hw, pl_conv2d_planes_wgrad_hw (the stem on the planes GEMM); 0.1.8: + pl_lifter_train_step, pl_lifter_step_carries_adamw; 0.1.7: + pl_workspace_bitmap_format (small-batch layer kernels); 0.1.6: + pl_counter_add; 0.1.5: + pl_flip_pose_ex, pl_flip_w_nhwc (phase5 Flip branch); 0.1.4: + pl_planes_split_strided; 0.1.3: + pl_bn_join_bwd (0.1.2: operand-plane outputs of the BatchNorm / join kernels, pl_gemm_planes_raw) */
+#define PL_VERSION 118 /* 0.1.18: + PLPoseCrop, pl_pose_augment_gather_crop, pl_pose_augment_gather_crop_t, pl_pose_augment_host_crop, pl_pose_augment_host_crop_t, pl_frame_warp_gather_crop, pl_frame_warp_host_crop, pl_pose_crop_boxes, pl_pose_crop_boxes_host, pl_crop_poses, pl_crop_poses_host (person-centred crop from each row's 2-D pose inside the two batch launches); 0.1.17: + PLCriterion, pl_pose_loss_scratch_bytes, pl_pose_loss_fwd_bwd, pl_lifter_train_fwd_bwd_crit, pl_lifter_train_step_crit (the train step's criterion: mse, l1, smooth_l1, mpjpe, weighted per joint); 0.1.16: + pl_pose_prepare, pl_pose_stats, pl_pose_affine and their _host forms, pl_pose_stats_scratch_bytes, pl_pose_stats_chunk_rows, pl_pose_augment_gather_t, pl_pose_augment_host_t, pl_pose_errors_t, pl_mpjpe_accum_t (pose tables: prepare, statistics, the per-column transform and its way back inside the batch, error and metric launches); 0.1.15: + PLFrameWarp, pl_frame_warp_gather, pl_frame_warp_host (frame gather + resize + the pose augmentation's warp in one launch); 0.1.14: + PLPoseAug, pl_pose_augment_gather, pl_pose_augment_host (seeded train-time pose augmentation inside the batch gather); 0.1.13: + PLClipRecord, pl_grad_norm_scratch_bytes, pl_grad_norm_clip, pl_adamw_flat_clip, pl_adamw_flat_dev_clip, pl_adamw_flat_planes_clip (gradient-norm clipping and non-finite skip on the device); 0.1.12: + pl_pose_errors, pl_pose_errors_host, pl_pose_metrics_scratch_bytes, pl_pose_metrics_accum (evaluation: MPJPE / N-MPJPE / P-MPJPE, PCK counts, per group); 0.1.11: + pl_vit_*_bf16, pl_vit_bf16_pack (MyViT "bf16p": bf16 operand carriers written by their producers); 0.1.10: + pl_vit_* (the MyViT transformer lifter); 0.1.9: + pl_conv2d_planes_fwd_hw, pl_conv2d_planes_wgrad_hw (the stem on the planes GEMM); 0.1.8: + pl_lifter_train_step, pl_lifter_step_carries_adamw; 0.1.7: + pl_workspace_bitmap_format (small-batch layer kernels); 0.1.6: + pl_counter_add; 0.1.5: + pl_flip_pose_ex, pl_flip_w_nhwc (phase5 Flip branch); 0.1.4: + pl_planes_split_strided; 0.1.3: + pl_bn_join_bwd (0.1.2: operand-plane outputs of the BatchNorm / join kernels, pl_gemm_planes_raw) */
 
 typedef enum PLStatus {
   PL_OK = 0,
@@ -533,6 +533,65 @@ typedef struct PLFrameWarp {
  * pl_frame_warp_host: the same inline text compiled for the CPU, on host pointers (a test hook). */
 int pl_frame_warp_gather(const PLFrameWarp* a, void* stream);
 int pl_frame_warp_host(const PLFrameWarp* a);
+
+/* ---- person-centred crop taken from each row's 2-D pose (csrc/frame_crop.h has the definition) --------------------------
+ * The reference crops "using the gt 2d as bounding box" (phase3_direct/my_HybrIK/H36_dataset.py:120-126) with a slice
+ * min(0, ..) : max(1000, ..) that always selects the whole frame; without a crop the entry points above reproduce that.
+ * Here the box is real and rides in the same two launches.  Box of a row, from its SOURCE 2-D pose a[17][2]
+ * (image-normalised, x right and y down) and the source frame size (Hs, Ws):
+ *   ex = (xmax - xmin) Ws, ey = (ymax - ymin) Hs over the 17 joints;  side = max(ceil(margin max(ex, ey)), min_side)
+ *   centre PL_CROP_BBOX: ccx = (0.5 (xmin + xmax)) Ws, ccy = (0.5 (ymin + ymax)) Hs;  PL_CROP_ROOT: ccx = a[0][0] Ws, ccy = a[0][1] Hs
+ *   x0 = rint(ccx - 0.5 side), y0 = rint(ccy - 0.5 side)      integers (ties to even), may be negative or past the frame
+ * A non-finite coordinate anywhere in the pose, or a side above 2^20, makes the box NaN.  boxes [n][4] fp32 = (x0, y0, side, side).
+ * Pose: a'x = (ax Ws - x0) / side, a'y = (ay Hs - y0) / side, in front of every augmentation stage, which then run unchanged
+ * on a' ((cx, cy) = (0.5, 0.5) is the crop's centre; p_flip > 0 needs flip_offset 1); the 3-D pose is untouched.  A transform
+ * (the _t forms) still applies last: its statistics must then be statistics of crop coordinates.
+ * Frame: (u, v) of pl_frame_warp_gather are crop-normalised and the source position goes through the crop-local one,
+ *   xl = u side - 0.5 (shift, scale and rotation all off: xl = (j + 0.5) (side / Wo) - 0.5);  flipped: xl = (side - 1) - xl;
+ *   xs = xl + x0   (ys likewise), then the border rule and the taps of the FRAME: what lies outside it is `fill`.
+ * Exact in fp32: side == Wo == Ho copies scale * frame[y0:y0+Ho, x0:x0+Wo], with a flip its mirror image, and
+ * side == 2 Wo == 2 Ho is the 2 x 2 block mean.  A NaN box gives a NaN frame and a NaN 2-D pose.  The frame launch computes
+ * the box from x2d by the same inline text as the pose launch: the two agree bit for bit without talking to each other.
+ * margin not finite or <= 0, min_side < 1, not an integer or above 2^20, and a centre out of range are PL_EINVAL; Hs, Ws
+ * outside [1, 2^22] (or, for a frame warp, other than the table's) PL_ESHAPE. */
+enum { PL_CROP_BBOX = 0, PL_CROP_ROOT = 1 };
+typedef struct PLPoseCrop {
+  float margin;      /* box side = margin x the larger extent of the pose, in source pixels; > 0 */
+  int32_t centre;    /* PL_CROP_BBOX: the middle of the pose's extent; PL_CROP_ROOT: joint 0 (the reference's choice, :126) */
+  float min_side;    /* smallest side, source pixels: an integer in [1, 2^20] */
+  int32_t reserved;  /* 0 */
+  int64_t Hs, Ws;    /* the source frame the image-normalised poses refer to */
+} PLPoseCrop;
+/* The crop forms of the pose gathers: the same arguments, then crop and boxes [n][4] (an output).  crop NULL: the call IS the
+ * entry point without _crop (same kernel instantiation, boxes not read).  A bad source index gives a NaN box. */
+int pl_pose_augment_gather_crop(const float* a, const float* b, const int64_t* src_idx, const int64_t* row_id, int64_t n,
+                                int64_t table_rows, float* oa, float* ob, const PLPoseAug* aug, uint64_t epoch,
+                                const PLPoseCrop* crop, float* boxes, void* stream);
+int pl_pose_augment_gather_crop_t(const float* a, const float* b, const int64_t* src_idx, const int64_t* row_id, int64_t n,
+                                  int64_t table_rows, float* oa, float* ob, const PLPoseAug* aug, uint64_t epoch,
+                                  const float* sub_a, const float* div_a, const float* sub_b, const float* div_b,
+                                  const PLPoseCrop* crop, float* boxes, void* stream);
+int pl_pose_augment_host_crop(const float* a, const float* b, const int64_t* src_idx, const int64_t* row_id, int64_t n,
+                              int64_t table_rows, float* oa, float* ob, const PLPoseAug* aug, uint64_t epoch,
+                              const PLPoseCrop* crop, float* boxes);
+int pl_pose_augment_host_crop_t(const float* a, const float* b, const int64_t* src_idx, const int64_t* row_id, int64_t n,
+                                int64_t table_rows, float* oa, float* ob, const PLPoseAug* aug, uint64_t epoch,
+                                const float* sub_a, const float* div_a, const float* sub_b, const float* div_b,
+                                const PLPoseCrop* crop, float* boxes);
+/* The crop form of the frame warp.  x2d: the rows' SOURCE 2-D poses, indexed like the frames: [N][34] read through src_idx,
+ * or a gathered [n][34] block when src_idx is NULL.  crop NULL: the call IS pl_frame_warp_gather (x2d not read). */
+int pl_frame_warp_gather_crop(const PLFrameWarp* a, const PLPoseCrop* crop, const float* x2d, void* stream);
+int pl_frame_warp_host_crop(const PLFrameWarp* a, const PLPoseCrop* crop, const float* x2d);
+/* boxes [n][4] of poses x2d [n][34] alone: one launch; _host: the same inline text on host pointers. */
+int pl_pose_crop_boxes(const float* x2d, int64_t n, const PLPoseCrop* crop, float* boxes, void* stream);
+int pl_pose_crop_boxes_host(const float* x2d, int64_t n, const PLPoseCrop* crop, float* boxes);
+/* Poses p [n][17][2] between image and crop coordinates by boxes [n][4]: invert = 0: out = (p W - x0) / side (W = Ws for x,
+ * Hs for y); invert != 0: out = (p side + x0) / W.  offset = 0 leaves x0, y0 out: both maps are affine per element, so the
+ * backward pass of either is the same call with offset = 0 on the incoming gradient (its factor, W / side or side / W, alone).
+ * out may overlap neither input.  One launch. */
+int pl_crop_poses(const float* p, const float* boxes, int64_t n, int64_t Hs, int64_t Ws, int invert, int offset, float* out,
+                  void* stream);
+int pl_crop_poses_host(const float* p, const float* boxes, int64_t n, int64_t Hs, int64_t Ws, int invert, int offset, float* out);
 
 /* ---- loss / metric / optimiser -------------------------------------------------- */
 /* torch.nn.MSELoss(reduction="mean") + its backward  train_1.py:37,94-95.

@@ -58,11 +58,13 @@ def torch_resize(table, idx):
     return y.permute(0, 2, 3, 1).contiguous()
 
 
-def _ours(table, idx, aug):
-    """One launch: the gather is the kernel's src_idx (data.py _frame_launch, what FrameFeeder's resident mode calls)."""
+def _ours(table, idx, aug, x2d=None):
+    """One launch: the gather is the kernel's src_idx (data.py _frame_launch, what FrameFeeder's resident mode calls).
+    x2d: the table's source 2-D poses -> the launch with crop=PersonCrop() (pl_frame_warp_gather_crop)."""
     out = torch.empty((idx.numel(), HO, WO, 3), dtype=torch.float32, device=dev)
     st = pkg.data._frame_augment_struct(aug)
-    pkg.data._frame_launch(table, pkg._lib.FRAME_U8, idx, idx, idx.numel(), out, 1.0 / 256.0, 0.0, st, 3)
+    crop = pkg.PersonCrop().struct(table.shape[1:3]) if x2d is not None else None
+    pkg.data._frame_launch(table, pkg._lib.FRAME_U8, idx, idx, idx.numel(), out, 1.0 / 256.0, 0.0, st, 3, crop, x2d)
     return out
 
 
@@ -78,6 +80,9 @@ for hs, ws in ((1000, 1002), (256, 256)):
     table = torch.randint(0, 256, (n_frames, hs, ws, 3), dtype=torch.uint8, device=dev, generator=g)
     perm = torch.randperm(n_frames, generator=g, device=dev)
     batches = [perm[k * B:(k + 1) * B].contiguous() for k in range(NB)]
+    # crop rows: 17 joints spread over 0.32 of the frame about a centre in [0.3, 0.7)^2 -- boxes of about 400 px on the large table
+    x2d = (0.3 + 0.4 * torch.rand(n_frames, 1, 2, generator=g, device=dev)
+           + 0.32 * (torch.rand(n_frames, 17, 2, generator=g, device=dev) - 0.5)).contiguous()
     variants = []
     for name, aug in AUGS:
         ours = lambda k, aug=aug: _ours(table, batches[k % NB], aug)
@@ -85,6 +90,8 @@ for hs, ws in ((1000, 1002), (256, 256)):
         variants.append((f"pl_frame_warp_gather, {name}", ours, True))
         variants.append((f"torch index + float/256 + affine_grid + grid_sample, {name}",
                          lambda k, thetas=thetas: torch_warp(table, batches[k % NB], thetas[k % NB]), False))
+        if name != "flip (p = 0.5)":
+            variants.append((f"pl_frame_warp_gather_crop, {name} + crop", lambda k, aug=aug: _ours(table, batches[k % NB], aug, x2d), True))
         if aug is None:
             variants.append(("torch index + float/256 + F.interpolate, plain", lambda k: torch_resize(table, batches[k % NB]), False))
 
