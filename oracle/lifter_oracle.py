@@ -82,7 +82,7 @@ def init_state(in_dim, out_dim, hidden, num_stage, rng, dtype=np.float32,
 # --------------------------------------------------------------------------
 # forward
 # --------------------------------------------------------------------------
-def _hidden_fwd(st, lin, bnp, a_in, train, use_bn, keep, p, dtype, update_running, on=None):
+def _hidden_fwd(st, lin, bnp, a_in, train, use_bn, keep, p, dtype, update_running, on=None, q=None):
     """Linear -> [BN] -> ReLU -> Dropout   (baselineModel.py:33-37 / 90-94).
 
     on: optional boolean (B,H) "positive and kept" decisions taken from the implementation
@@ -90,11 +90,17 @@ def _hidden_fwd(st, lin, bnp, a_in, train, use_bn, keep, p, dtype, update_runnin
     of zero may land on either side in two correct fp32 evaluations, and the sample then
     enters or leaves whole rows of dW.  Forcing the decisions removes that from a comparison;
     the caller checks separately that every forced decision that differs from the oracle's
-    own sits on such a round-off-sized pre-activation (cache['on_disagree'])."""
+    own sits on such a round-off-sized pre-activation (cache['on_disagree']).
+
+    q: optional rounding of the GEMM operands (forward's operand_round): z = q(a_in) q(W)^T + b; the backward finds it
+    in the cache."""
     W = st[lin + ".weight"].astype(dtype)
     b = st[lin + ".bias"].astype(dtype)
-    z = a_in @ W.T + b
-    c = {"a_in": a_in, "z": z}
+    if q is None:
+        z = a_in @ W.T + b
+    else:
+        z = q(a_in).astype(dtype) @ q(W).astype(dtype).T + b
+    c = {"a_in": a_in, "z": z, "q": q}
     B = z.shape[0]
     if use_bn:
         gamma = st[bnp + ".weight"].astype(dtype)
@@ -156,11 +162,18 @@ def _hidden_fwd(st, lin, bnp, a_in, train, use_bn, keep, p, dtype, update_runnin
 
 
 def forward(st, x, *, num_stage=2, train=False, use_bn=True, p_dropout=0.5,
-            keep_masks=None, dtype=np.float32, update_running=True, on_masks=None):
+            keep_masks=None, dtype=np.float32, update_running=True, on_masks=None, operand_round=None):
     """LinearModel.forward (baselineModel.py:87-102).
 
     keep_masks: list of 1+2*num_stage boolean (B,H) keep masks, required when
     train and 0 < p_dropout < 1.  Returns (y (B,out_dim), cache).
+
+    operand_round: optional callable array -> array, the emulation of the library's bf16 arithmetic (PL_BF16): the
+    hidden x hidden Linears (hidden layers 1 ... 2 num_stage) round BOTH GEMM operands with it, forward
+    z = q(a_in) q(W)^T + b and -- backward() reads it from the cache -- dW = q(dz)^T q(a_in), da = q(dz) q(W); the first
+    Linear, the output Linear, the biases, BatchNorm and every bias / BatchNorm gradient stay unrounded, as in the
+    library (csrc/api.hip: activation, dz and weight planes of layers 1 ..., nothing else).  None (the default) is the
+    reference's arithmetic, bit for bit what it was.
     """
     x = np.asarray(x)
     B = x.shape[0]
@@ -181,8 +194,8 @@ def forward(st, x, *, num_stage=2, train=False, use_bn=True, p_dropout=0.5,
     caches.append(c)
     for s in range(num_stage):                                # :97-98
         i1, i2 = 1 + 2 * s, 2 + 2 * s
-        y, c1 = _hidden_fwd(st, *names[i1], h, train, use_bn, km(i1), p_dropout, dtype, update_running, om(i1))
-        y, c2 = _hidden_fwd(st, *names[i2], y, train, use_bn, km(i2), p_dropout, dtype, update_running, om(i2))
+        y, c1 = _hidden_fwd(st, *names[i1], h, train, use_bn, km(i1), p_dropout, dtype, update_running, om(i1), operand_round)
+        y, c2 = _hidden_fwd(st, *names[i2], y, train, use_bn, km(i2), p_dropout, dtype, update_running, om(i2), operand_round)
         caches += [c1, c2]
         h = h + y                                             # :45
     W = st["w2.weight"].astype(dtype)
@@ -217,17 +230,26 @@ def _hidden_bwd(st, lin, bnp, c, g, use_bn, dtype):
     else:
         dz = dy
     W = st[lin + ".weight"].astype(dtype)
-    grads[lin + ".weight"] = dz.T @ c["a_in"]
+    q = c.get("q")
     grads[lin + ".bias"] = dz.sum(axis=0, dtype=dtype)
-    return dz @ W, grads
+    if q is None:
+        grads[lin + ".weight"] = dz.T @ c["a_in"]
+        return dz @ W, grads
+    dzq = q(dz).astype(dtype)
+    grads[lin + ".weight"] = dzq.T @ q(c["a_in"]).astype(dtype)
+    return dzq @ q(W).astype(dtype), grads
 
 
-def backward(st, cache, dout):
-    """Gradients of every parameter and of the (flattened) input."""
+def backward(st, cache, dout, operand_round=None):
+    """Gradients of every parameter and of the (flattened) input.  operand_round: as forward()'s, for a cache whose
+    forward ran without it (default: what the forward used, layer by layer)."""
     dtype = cache["dtype"]
     S, use_bn = cache["num_stage"], cache["use_bn"]
     names = hidden_layer_names(S)
     L = cache["layers"]
+    if operand_round is not None:
+        for c in L[1:]:
+            c["q"] = operand_round
     dout = np.asarray(dout).astype(dtype)
     grads = {}
     W = st["w2.weight"].astype(dtype)

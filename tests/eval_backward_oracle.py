@@ -19,12 +19,26 @@ import numpy as np
 
 from oracle import lifter_oracle as orc
 
+# the reference alone on "bf16-256x256-dual" (see BOUNDS["bf16-emulated"]): output error of max (the second call's), dx max-abs
+# of max, largest relative L2 (dx)
+EMULATED_MEASURED = dict(y=7.0e-4, dx_max=5.9e-4, rel_l2=9.1e-5)
+
 # kind -> the project's own bounds.  Decisions: _assert_decisions_consistent (test_gpu_parity.py) made relative to the
 # layer's largest pre-ReLU value; bf16: the flip rule of the bf16 gates.  Errors: the eval forward's 2e-5 of max, the
 # existing dx bound of test_eval_mode_backward_vs_torch_twin, the 2e-4 / 8e-2 relative-L2 bounds of the gradient gates.
 BOUNDS = {
     "fp32-grade": dict(flip_frac=1e-4, flip_abs=None, flip_rel=1e-4, y=2e-5, dx_max=5e-4, rel_l2=2e-4),
     "bf16": dict(flip_frac=0.02, flip_abs=0.2, flip_rel=None, y=3e-2, dx_max=None, rel_l2=8e-2),
+    # bf16 against the EMULATED oracle (reference(..., operand_round=bf16_oracle.operand_round): the hidden x hidden GEMMs on
+    # bf16-rounded operands, as the library's): the fp32-grade error bounds, widened only where rounding ties ask for it.
+    # An fp32-perturbed activation or dz may round to the neighbouring bf16 value; what that costs was measured on the CPU
+    # from the reference alone -- the emulated oracle in fp32 against the same in fp64, on the inputs of
+    # "bf16-256x256-dual": EMULATED_MEASURED -- y 7.0e-4 of max, dx max-abs 5.9e-4 of max, relative L2 at most 9.1e-5 -- and
+    # each gate is twice that or the fp32-grade bound, whichever is larger: y 1.4e-3, dx max-abs 1.18e-3, relative L2 2e-4
+    # (tests/test_bf16_oracle_host.py re-measures and holds the reference alone to these gates).  Decisions: the flip rule
+    # of the bf16 gates.
+    "bf16-emulated": dict(flip_frac=0.02, flip_abs=0.2, flip_rel=None, y=max(2 * EMULATED_MEASURED["y"], 2e-5),
+                          dx_max=max(2 * EMULATED_MEASURED["dx_max"], 5e-4), rel_l2=max(2 * EMULATED_MEASURED["rel_l2"], 2e-4)),
 }
 
 PLANES_CHAIN, PLANES_DUAL = "planes_gemm_chain_kernel", "planes_gemm_dual_kernel"
@@ -86,19 +100,20 @@ def loss_grads(ya, ta, yb, tb, dtype):
     return dya, dyb
 
 
-def reference(st, xa, ta, xb, tb, S, bn, masks_a=None, masks_b=None, dtype=np.float64):
+def reference(st, xa, ta, xb, tb, S, bn, masks_a=None, masks_b=None, dtype=np.float64, operand_round=None):
     """The two-call graph on the oracle.  masks_*: per hidden layer the (B, H) boolean ReLU decisions to force in that call
     (cache['layers'][l]['on_disagree'] then holds |pre-ReLU| wherever they differ from the oracle's own).
     Returns outputs, dx (of the first call alone), parameter gradients summed over the two calls, both caches and the
     arguments (compare() replays them in fp32)."""
-    kw = dict(num_stage=S, train=False, use_bn=bn, dtype=dtype)
+    kw = dict(num_stage=S, train=False, use_bn=bn, dtype=dtype, operand_round=operand_round)
     ya, ca = orc.forward(st, xa, on_masks=masks_a, **kw)
     yb, cb = orc.forward(st, xb, on_masks=masks_b, **kw)
     dya, dyb = loss_grads(ya, ta, yb, tb, dtype)
     ga, dx = orc.backward(st, ca, dya)
     gb, _ = orc.backward(st, cb, dyb)
     return dict(ya=ya, yb=yb, dx=dx, grads={k: ga[k] + gb[k] for k in ga}, cache_a=ca, cache_b=cb,
-                inputs=dict(st=st, xa=xa, ta=ta, xb=xb, tb=tb, S=S, bn=bn, masks_a=masks_a, masks_b=masks_b))
+                inputs=dict(st=st, xa=xa, ta=ta, xb=xb, tb=tb, S=S, bn=bn, masks_a=masks_a, masks_b=masks_b,
+                            operand_round=operand_round))
 
 
 def decisions_of(cache):
@@ -173,7 +188,8 @@ def compare(got, ref, kind):
     want = set(orc.param_names(S, bn_params=bn))
     assert set(got["grads"]) == want, sorted(set(got["grads"]) ^ want)
     err = _errors(got, ref)
-    r32 = reference(st, inp["xa"], inp["ta"], inp["xb"], inp["tb"], S, bn, inp["masks_a"], inp["masks_b"], dtype=np.float32)
+    r32 = reference(st, inp["xa"], inp["ta"], inp["xb"], inp["tb"], S, bn, inp["masks_a"], inp["masks_b"], dtype=np.float32,
+                    operand_round=inp.get("operand_round"))
     e32 = _errors(r32, ref)
     report["errors"] = err
     report["ratios"] = {k: (v / e32[k] if e32[k] > 0 else (0.0 if v == 0 else float("inf"))) for k, v in err.items()}

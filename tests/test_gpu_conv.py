@@ -11,6 +11,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import bf16_oracle as bo
 from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
@@ -764,6 +765,14 @@ def test_conv_planes_stride2_autograd_vs_torch_fp64(pkg, mode, B, H, W, Cin, Cou
     assert float((got - want).abs().max()) <= tol * float(want.abs().max()) * nterm, route
     wantw = w64.grad
     assert float((wd.grad.cpu().double() - wantw).abs().max()) <= tol * float(wantw.abs().max()) * (B * Ho * Wo) ** 0.5, route
+    if mode == "bf16p":
+        # one bf16 plane per operand IS the RNE rounding of x, w and dz: around the fp64 result of the rounded operands
+        # (tests/bf16_oracle.py) the f16x3 row's bounds hold on all three data-gradient routes
+        refr, _ = bo.conv_reference(x, w, 2, pad)
+        wantx, wantw = bo.conv_grads_reference(x, w, dz, 2, pad)
+        assert float((z.detach().cpu().double() - refr).abs().max()) <= 3e-6 * float(refr.abs().max()) * 4
+        assert float((got - wantx).abs().max()) <= 3e-6 * float(wantx.abs().max()) * nterm, route
+        assert float((wd.grad.cpu().double() - wantw).abs().max()) <= 3e-6 * float(wantw.abs().max()) * (B * Ho * Wo) ** 0.5, route
 
 
 @pytest.mark.parametrize("mode", ["f16x3", "bf16p"])
@@ -801,6 +810,14 @@ def test_stem_on_the_planes_gemm_vs_torch_fp64(pkg, mode, B, H, W):
     assert float((sums - rows.sum(0)).abs().max()) <= (tol * 40) * float(rows.abs().sum(0).max())
     wantw = w64.grad
     assert float((wd.grad.cpu().double() - wantw).abs().max()) <= tol * float(wantw.abs().max()) * (B * H * W / 4) ** 0.5
+    if mode == "bf16p":
+        # against the fp64 result of the bf16-rounded frames, weights and dz (tests/bf16_oracle.py): the f16x3 row's bounds
+        refr, _ = bo.conv_reference(x, w, 2, 3)
+        _, wantw = bo.conv_grads_reference(x, w, dz, 2, 3)
+        assert float((z.detach().cpu().double() - refr).abs().max()) <= 3e-6 * float(refr.abs().max()) * 4
+        rows = refr.reshape(-1, 64)
+        assert float((sums - rows.sum(0)).abs().max()) <= (3e-6 * 40) * float(rows.abs().sum(0).max())
+        assert float((wd.grad.cpu().double() - wantw).abs().max()) <= 3e-6 * float(wantw.abs().max()) * (B * H * W / 4) ** 0.5
 
 
 @pytest.mark.parametrize("B,H,W,Cin,Cout,K,stride,pad", [

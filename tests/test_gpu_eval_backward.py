@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import bf16_oracle as bo
 import eval_backward_oracle as ebo
 from oracle import lifter_oracle as orc
 
@@ -97,6 +98,13 @@ def _check_case(pkg, case, st, inputs, tag, mpjpe_gate=True):
     ref = ebo.reference(st, xa, ta, xb, tb, case.S, case.bn, got["masks_a"], got["masks_b"])
     rep = ebo.compare(got, ref, kind)
     print(f"eval-backward {tag}: {ebo.summary(rep)}")
+    if kind == "bf16":
+        # ... and, tightly, against the emulated oracle: the same graph with the hidden x hidden GEMMs on bf16-rounded operands
+        # (BOUNDS["bf16-emulated"]: the fp32-grade bounds plus what rounding ties cost the reference alone)
+        emu = ebo.reference(st, xa, ta, xb, tb, case.S, case.bn, got["masks_a"], got["masks_b"], operand_round=bo.operand_round)
+        rep_emu = ebo.compare(got, emu, "bf16-emulated")
+        print(f"eval-backward {tag}, emulated oracle: {ebo.summary(rep_emu)}; errors y {rep_emu['errors']['y']:.2e} "
+              f"yb {rep_emu['errors']['yb']:.2e} dx max {rep_emu['errors']['dx_max']:.2e} dx L2 {rep_emu['errors']['dx']:.2e}")
     # ---- the nothing-saved eval forward agrees: each of the two forwards is held to BOUNDS[kind]["y"] of max |y| from fp64,
     # so they are within twice that of each other; and, on O(1) outputs of 17 joints, the 1e-3 mm gate of
     # test_eval_mode_backward_vs_torch_twin
