@@ -187,32 +187,39 @@ def conv2d_nhwc_wgrad(x, dy, kernel_size, stride=1, padding=0, arith="bf16x6"):
 def conv2d_nhwc_dgrad(dy, w_ohwi, in_hw, stride=1, padding=0, arith="bf16x6"):
     """Input gradient of conv2d_nhwc: dy [B,Ho,Wo,Cout], w [Cout,KH,KW,Cin] -> dx [B,H,W,Cin].  No kernel of its
     own: stride 1 is the forward convolution of dy with the flipped filter, channels swapped; stride 2 (3x3 pad 1
-    and 1x1 pad 0, the backbone's two cases, even H and W) is the transposed convolution
-    dx[2*oh - pad + kh] += dy[oh] * w[kh], i.e. deconv4x4s2_nhwc with the filter placed inside a 4x4 one."""
+    and 1x1 pad 0, the backbone's two cases, any H and W) is the transposed convolution
+    dx[2*oh - pad + kh] += dy[oh] * w[kh], i.e. deconv4x4s2_nhwc with the filter placed inside a 4x4 one -- computed on
+    the 2 Ho x 2 Wo map and, where H or W is odd, cropped to H x W: the dropped last row / column is the padding position
+    the forward read as zero, its gradient belongs to no input.  Other kernels and strides: NotImplementedError."""
     Cout, KH, KW, Cin = w_ohwi.shape
-    H, W = in_hw
+    H, W = (int(v) for v in in_hw)
     if stride == 1:
         wf = w_ohwi.flip(1, 2).permute(3, 1, 2, 0).contiguous()            # [Cin][KH][KW][Cout]
         dx = conv2d_nhwc(dy, wf, 1, KH - 1 - padding, arith=arith)
         if dx.shape[1:3] != (H, W):
             raise ValueError("conv2d_nhwc_dgrad: input size does not match")
         return dx
-    if stride == 2 and H % 2 == 0 and W % 2 == 0 and KH == 1 and KW == 1 and padding == 0:
+    if stride != 2 or KH != KW or (KH, padding) not in ((3, 1), (1, 0)):
+        raise NotImplementedError(f"conv2d_nhwc_dgrad: stride {stride}, kernel {KH}x{KW}, padding {padding}, input {H}x{W} "
+                                  "(stride 1, or stride 2 with 3x3 / pad 1 or 1x1 / pad 0)")
+    B, Ho, Wo, _ = dy.shape
+    if (Ho, Wo) != ((H - 1) // 2 + 1, (W - 1) // 2 + 1):
+        raise ValueError(f"conv2d_nhwc_dgrad: dy {Ho}x{Wo} is not the stride-2 output of a {H}x{W} input")
+    if KH == 1:
         # dy W on the even pixels: one GEMM ([M][Cout] x [Cout][Cin], the OHWI filter read as [Cin][1][1][Cout]^T)
-        B, Ho, Wo, _ = dy.shape
         t = conv2d_nhwc(dy, w_ohwi.reshape(Cout, Cin).t().contiguous().reshape(Cin, 1, 1, Cout), 1, 0, arith=arith)
-        dx = torch.empty(B, H, W, Cin, dtype=torch.float32, device=dy.device)
+        dx = torch.empty(B, 2 * Ho, 2 * Wo, Cin, dtype=torch.float32, device=dy.device)
         with _lib.on_device(dy.device):
             rc = _lib.lib().pl_upsample2x_zero_nhwc(t.data_ptr(), B, Ho, Wo, Cin, dx.data_ptr(), _lib.current_stream_ptr())
         _lib.check(rc, "pl_upsample2x_zero_nhwc")
-        return dx
-    if stride == 2 and H % 2 == 0 and W % 2 == 0 and (KH, padding) in ((3, 1), (1, 0)) and KH == KW:
-        # ConvTranspose2d weight [in = Cout][out = Cin][4][4]; with padding 1: kh -> kh, with padding 0: kh -> kh + 1
+    else:
+        # ConvTranspose2d weight [in = Cout][out = Cin][4][4] with the 3x3 filter at kh, kw = 0 .. 2 (padding 1)
         w4 = torch.zeros(Cout, Cin, 4, 4, dtype=torch.float32, device=w_ohwi.device)
-        o = 1 - padding
-        w4[:, :, o:o + KH, o:o + KW] = w_ohwi.permute(0, 3, 1, 2)
-        return deconv4x4s2_nhwc(dy, deconv_subkernels(w4), arith=arith)
-    raise NotImplementedError(f"conv2d_nhwc_dgrad: stride {stride}, kernel {KH}, padding {padding}, input {H}x{W}")
+        w4[:, :, :3, :3] = w_ohwi.permute(0, 3, 1, 2)
+        dx = deconv4x4s2_nhwc(dy, deconv_subkernels(w4), arith=arith)
+    if (2 * Ho, 2 * Wo) != (H, W):
+        dx = dx[:, :H, :W].contiguous()
+    return dx
 
 
 def maxpool3x3s2_nhwc(x):

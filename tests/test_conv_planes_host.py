@@ -95,6 +95,35 @@ def test_deconv_planes_forward_names_share_their_checks(pkg):
         assert rc == EINVAL and word in msg, (word, rc, msg)
 
 
+def test_direct_conv_scratch_queries_answer_for_the_route_of_each_rectangular_case(pkg):
+    """pl_conv2d_nhwc_scratch_bytes_ex / pl_conv2d_nhwc_wgrad_scratch_bytes on the shapes tests/test_gpu_conv_shapes.py runs
+    (tests/conv_shape_cases.py): the bytes of the route each row names -- none, splits x M x Cout floats of split-K slabs,
+    the im2col buffer (forward: pixels and weight rows padded to whole K tiles; weight gradient: pixels x taps, unpadded),
+    or the stem weight gradient's one partial per workgroup -- so a wrapper that sizes its scratch by the query hands the
+    kernels of that route exactly what they index."""
+    import conv_shape_cases as cs
+    L = pkg.lib()
+    for name, geom, bn, relu, res, bias, kernels, scratch in cs.FWD_CASES:
+        B, H, W, Cin, Cout, k, stride, pad = geom
+        got = L.pl_conv2d_nhwc_scratch_bytes_ex(B, H, W, Cin, Cout, k, k, stride, pad, int(bias), int(res), relu)
+        assert got == cs.fwd_scratch_bytes(geom, scratch), (name, got)
+        assert (got > 0) == (scratch[0] != "none"), name
+    for name, geom, kernels, scratch, _ in cs.WGRAD_CASES:
+        B, H, W, Cin, Cout, k, stride, pad = geom
+        got = L.pl_conv2d_nhwc_wgrad_scratch_bytes(B, H, W, Cin, Cout, k, k, stride, pad)
+        assert got == cs.wgrad_scratch_bytes(geom, scratch), (name, got)
+    # the two sides of the stem weight gradient's LDS limit, as the cases assume them
+    wo = {name: cs.out_hw(geom)[1] for name, geom, *_ in cs.WGRAD_CASES}
+    assert wo["stem widest row"] == cs.STEM_WGRAD_MAX_WO and wo["stem past the widest row"] == cs.STEM_WGRAD_MAX_WO + 1
+    assert (cs.STEM_WGRAD_MAX_WO * 64 + 7 * (2 * cs.STEM_WGRAD_MAX_WO + 5) * 3) * 4 == 64868 <= 65536
+    # the stride-1 data gradient is the forward convolution of dy (Cout channels in, Cin out): no scratch on these shapes
+    for name, geom, _, _, dgrad in cs.WGRAD_CASES:
+        B, H, W, Cin, Cout, k, stride, pad = geom
+        if dgrad is not None and stride == 1:
+            Ho, Wo = cs.out_hw(geom)
+            assert L.pl_conv2d_nhwc_scratch_bytes_ex(B, Ho, Wo, Cout, Cin, k, k, 1, k - 1 - pad, 0, 0, 0) == 0, name
+
+
 def test_split_k_tail_of_gemm_and_weight_gradient(pkg):
     """pl_gemm_planes_raw and pl_conv2d_planes_wgrad[_hw] share the split-K launch: a problem the library splits over K
     needs slabs (and, for the GEMM, takes no bias or statistics)."""

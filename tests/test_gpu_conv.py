@@ -260,6 +260,92 @@ def test_model3d_any_batch_size(pkg, B):
     assert float((part - full[:B]).abs().max()) < 2e-4
 
 
+def _torch_cpu_logits(m, frames_nchw):
+    """The heat-map logits of a Model_3D / Model_2D in eval mode from its stock nn modules on the CPU (NCHW), as
+    test_model3d_eval_forward_vs_torch_cpu spells them out."""
+    with torch.no_grad():
+        r = m.preact
+        x = F.max_pool2d(F.relu(r.bn1(r.conv1(frames_nchw))), 3, 2, 1)
+        for li in (1, 2, 3, 4):
+            for blk in getattr(r, f"layer{li}"):
+                idn = x if blk.downsample is None else blk.downsample(x)
+                o = F.relu(blk.bn1(blk.conv1(x)))
+                o = F.relu(blk.bn2(blk.conv2(o)))
+                x = F.relu(blk.bn3(blk.conv3(o)) + idn)
+        return m.final_layer(m.deconv_layers(x))
+
+
+def _logit_side(n):
+    """Side of the heat-map logits for a frame side n: five stride-2 stages (each (n - 1) // 2 + 1), three doublings."""
+    for _ in range(5):
+        n = (n - 1) // 2 + 1
+    return 8 * n
+
+
+def _rect_frames(B, H, W, seed):
+    """Seeded NHWC frames of any shape (synth.seeded_frames is square)."""
+    return torch.rand(B, H, W, 3, generator=torch.Generator().manual_seed(seed))
+
+
+@pytest.mark.parametrize("dtype,H,W,planes_eval", [("f16x3", 64, 96, True),      # the whole-planes eval route
+                                                   ("f16x3", 72, 104, False),    # not multiples of 32: the direct eval route
+                                                   ("bf16x6", 64, 96, False)])
+def test_model3d_eval_forward_rectangular_vs_torch_cpu(pkg, dtype, H, W, planes_eval):
+    """test_model3d_eval_forward_vs_torch_cpu on frames that are not square and, at 72 x 104, not a multiple of 32 (maps of
+    18x26, 9x13, 5x7 and 3x4 in front of the stride-2 blocks): the same reference, the same 3e-4 lscale / 2e-3 bounds, on each
+    eval route."""
+    from oracle import heads_oracle
+    m = pkg.Model_3D(compute_dtype=dtype).eval()
+    m.load_state_dict(pkg.synth.seeded_state(m.state_dict(), 31))
+    with torch.no_grad():
+        m.final_layer.weight.mul_(1e-4)
+        m.final_layer.bias.mul_(0.1)
+    frames = _rect_frames(2, H, W, 33)
+    logits_ref = _torch_cpu_logits(m, frames.permute(0, 3, 1, 2))
+    want = heads_oracle.soft_argmax(logits_ref.double().numpy(), 17, 64, True)
+    md = m.to(DEV)
+    assert md.preact._planes_eval_ok(frames.to(DEV)) == planes_eval
+    logits = md.heatmap_logits(frames.to(DEV))
+    # H / 4 x W / 4 where 32 divides both; 72 x 104 ends on a 3 x 4 map, 24 x 32 logits -- in stock torch as well
+    assert (_logit_side(64), _logit_side(96), _logit_side(72), _logit_side(104)) == (16, 24, 24, 32)
+    assert tuple(logits.shape) == (2, 1088, _logit_side(H), _logit_side(W)) == tuple(logits_ref.shape)
+    lscale = float(logits_ref.abs().max())
+    assert float((logits.cpu() - logits_ref).abs().max()) < 3e-4 * lscale
+    got = md(frames.to(DEV)).cpu().numpy()
+    assert got.shape == (2, 51)
+    assert np.abs(got - want.reshape(2, 51)).max() < 2e-3
+
+
+def test_model2d_eval_forward_rectangular_vs_torch_cpu(pkg):
+    """test_model2d_eval_forward_vs_torch_cpu on NCHW frames of 64 x 96, its 1e-3 bound."""
+    from oracle import heads_oracle
+    m = pkg.Model_2D().eval()
+    m.load_state_dict(pkg.synth.seeded_state(m.state_dict(), 41))
+    with torch.no_grad():
+        m.final_layer.weight.mul_(1e-4)
+    frames = _rect_frames(2, 64, 96, 43).permute(0, 3, 1, 2).contiguous()               # NCHW [2, 3, 64, 96]
+    logits_ref = _torch_cpu_logits(m, frames)
+    assert tuple(logits_ref.shape) == (2, 17, 16, 24)
+    want = heads_oracle.soft_argmax(logits_ref.double().numpy(), 17, 1, False)
+    got = m.to(DEV)(frames.to(DEV)).cpu().numpy()
+    assert got.shape == (2, 34) and np.abs(got - want.reshape(2, 34)).max() < 1e-3
+
+
+@pytest.mark.parametrize("dtype", ["f16x3", "bf16x6"])
+def test_model3d_batch_rows_independent_on_a_rectangular_map(pkg, dtype):
+    """test_model3d_any_batch_size on 64 x 96 frames: the first row of a batch of two is what the row alone gives (2e-4)."""
+    m = pkg.Model_3D(compute_dtype=dtype).eval()
+    m.load_state_dict(pkg.synth.seeded_state(m.state_dict(), 31))
+    with torch.no_grad():
+        m.final_layer.weight.mul_(1e-4)
+    m = m.to(DEV)
+    frames = _rect_frames(2, 64, 96, 78).to(DEV)
+    full = m(frames)
+    part = m(frames[:1])
+    assert part.shape == (1, 51)
+    assert float((part - full[:1]).abs().max()) < 2e-4
+
+
 @pytest.mark.parametrize("B,H,Cin,Cout,k,stride,pad", [
     (4, 32, 128, 128, 3, 1, 1),      # layer2 conv2
     (4, 32, 128, 128, 3, 2, 1),      # stride on the 3x3
@@ -391,22 +477,31 @@ def test_maxpool_backward_vs_torch(pkg, shape):
     assert rc == 0 and torch.equal(dx.cpu(), want)
 
 
-@pytest.mark.parametrize("size,dtype", [(64, "bf16x6"), (256, "bf16x6"), (64, "f16x3"), (256, "f16x3")])
-def test_model3d_train_step_vs_torch_autograd(pkg, size, dtype):
+@pytest.mark.parametrize("hw,dtype", [((64, 64), "bf16x6"), ((256, 256), "bf16x6"), ((64, 64), "f16x3"), ((256, 256), "f16x3"),
+                                      ((64, 96), "bf16x6"), ((64, 96), "f16x3"), ((72, 104), "bf16x6"), ((72, 104), "f16x3")],
+                         ids=["64-bf16x6", "256-bf16x6", "64-f16x3", "256-f16x3",
+                              "64x96-bf16x6", "64x96-f16x3", "72x104-bf16x6", "72x104-f16x3"])
+def test_model3d_train_step_vs_torch_autograd(pkg, hw, dtype):
     """Model_3D in TRAINING mode end to end on the library's differentiable pieces (53 convolutions with dgrad and
     wgrad, 56 BatchNorms on batch statistics, max-pool, three transposed convolutions, biased 1x1, soft-argmax)
     against the same stock modules under torch autograd on the CPU in fp64: loss and parameter gradients.
     size 256 = BASELINE configs[3]'s real frame size (phase4_joined/train.py:69-89 on 256 x 256 frames: 64 x 64 x 64
     heat-map volumes, 8 x 8 layer4 maps); 64 is the quick case.  dtype "f16x3": the Bottlenecks' 1x1 convolutions (forward,
     data and weight gradients) on the planes GEMM with operand planes written by the BatchNorm / join kernels
-    (conv.py, bottom) -- at 256 every block qualifies, at 64 layer3 / layer4 fall back block by block."""
+    (conv.py, bottom) -- at 256 every block qualifies, at 64 layer3 / layer4 fall back block by block.
+    Rectangular frames (seeded uniform noise: synth.seeded_frames is square): 64 x 96 stays even all the way down; 72 x 104 puts
+    maps of 18x26, 9x13, 5x7 and 3x4 in front of the stride-2 blocks (the cropped stride-2 data gradient,
+    conv.conv2d_nhwc_dgrad) and, at two frames, has no map of whole 32-row tiles (936, 234, 70, 24 pixels) and fails
+    stem_planes_supported: the f16x3 model takes the direct kernels block by block there, while at 64 x 96 its stem, layer1 and
+    layer2 run on the planes GEMM and layer3 / layer4 fall back."""
     import copy
     torch.manual_seed(7)
     m = pkg.Model_3D(compute_dtype=dtype).train()
     m.load_state_dict(pkg.synth.seeded_state(m.state_dict(), 51))
     with torch.no_grad():
         m.final_layer.weight.mul_(1e-3)
-    frames = pkg.synth.seeded_frames(2, 52, size=size)
+    H, W = hw
+    frames = pkg.synth.seeded_frames(2, 52, size=H) if H == W else _rect_frames(2, H, W, 52)
     target = torch.randn(2, 51)
     torch.set_num_threads(min(16, os.cpu_count() or 1))
     def torch_step(dtype):
