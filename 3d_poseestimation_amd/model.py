@@ -317,6 +317,12 @@ class LinearModel(nn.Module):
         self._seed, self._step = int(seed) & 0xFFFFFFFFFFFFFFFF, int(step)
         return self
 
+    def dropout_state(self):
+        """Position of the Philox dropout stream as the keywords of manual_seed(): {'seed', 'step'} (step = training
+        forwards so far).  It is not part of state_dict() (its keys are the reference's): a checkpoint stores it beside the
+        model's and the resuming script calls `model.manual_seed(**ckpt['dropout'])` after load_state_dict."""
+        return {"seed": int(self._seed), "step": int(self._step)}
+
     def set_grad_sync(self, sync, cuts=None):
         """Attach a dp.GradSync: backward then all-reduces the upper layers' gradients while the
         lower layers are still being computed (see pl_lifter_bwd_layers).
