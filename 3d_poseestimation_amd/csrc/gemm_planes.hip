@@ -350,20 +350,174 @@ __device__ __forceinline__ void acc_epilogue(const PlanesKern& k, plp::f32x4v (&
   staged_epilogue<EDGE>(k, C, v, m0, n0, wm, wn, lane);
 }
 
-// the backward pair chained in one workgroup per CU (gemm_planes16.h CHAIN): grid = the number of dX tiles = dW items
-template <int MODE>
+// dX's epilogue of the chained pair, handed from computing wave w to loader wave 4 + w (gemm_planes16.h HAND-OFF): what
+// staged_epilogue<false> does for a dX problem -- skip-gradient addend, the g store, BatchNorm-backward pass 1 of the layer
+// below (the host takes this form for nothing else: chain_hand_ok) -- one row-quad `it` at a time.  `blk` is the 64 x 64
+// block of the wave this lane writes (computing) or stands in for (loader); lane (lr = lane >> 4, lc = 4 (lane & 15)) of the
+// loader owns what staged_epilogue's lane owns, every element sees the same operations in the same order, the column sums run
+// over it = 0 .. 15 in registers and leave through the same butterfly.
+// ADD / BNR: addend / bnr_* present -- compile-time, so that every step issues a fixed number of vector-memory operations.
+struct NoHand { static constexpr bool kOn = false; };
+template <int MODE, bool ADD, bool BNR>
+struct ChainHand {
+  static constexpr bool kOn = true;
+  static constexpr int D = plp::kChainAhead;
+  // vector-memory operations of chunk(J): the loads of row-quad J, the g store of row-quad J - D
+  static constexpr int vm_ops(int j) {
+    return (j >= 0 && j < plp::kChainChunks ? (ADD ? 1 : 0) + (BNR ? 3 : 0) : 0) + (j >= D && j - D < plp::kChainChunks ? 1 : 0);
+  }
+  const PlanesKern& k;
+  float* blk;
+  int lane;
+  size_t o0 = 0;
+  int rg = 0, cb = 0, col0 = 0, wpr = 0, bit = 0;
+  const uint64_t* bw0 = nullptr;
+  float4 mu, rs, s1, s2;
+  float mxd = 0.f, mxz = 0.f;
+  float4 qa[D], zz[D];                             // row-quads in flight (slot = row-quad % D; the indices are compile-time):
+  ulonglong2 w01[D], w23[D];                       // addend, saved z, the bitmap's four words
+
+  __device__ __forceinline__ ChainHand(const PlanesKern& k_, float* blk_, int lane_) : k(k_), blk(blk_), lane(lane_) {}
+
+  // computing wave: the block as acc_epilogue stages it, in the accumulator layout (row 16 rt + 4 q + r, column 16 ct + c)
+  __device__ __forceinline__ void put(plp::f32x4v (&acc)[plp::ModeCfg<MODE>::NACC][4][4]) const {
+    const float os = MODE == plp::kF16x3 ? (k.dyn_inv ? k.out_scale * k.dyn_inv[0] : k.out_scale) : 1.f;
+    const int q = lane >> 4, c = lane & 15;
+#pragma unroll
+    for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          float x = acc[0][rt][ct][r];
+          if constexpr (MODE == plp::kF16x3) x = fmaf(acc[1][rt][ct][r], 1.0f / plp::kF16LoScale, x) * os;
+          blk[plp::hand_idx(rt * 16 + 4 * q + r, ct * 16 + c)] = x;
+        }
+  }
+
+  // loader wave, before item 1's first step
+  __device__ __forceinline__ void begin(const int m0, const int n0, const int wm, const int wn) {
+    const GemmArgs& e = k.e;
+    const int lr = lane >> 4, lc = (lane & 15) * 4;
+    const int row0 = m0 + wm * 64 + lr;
+    col0 = n0 + wn * 64 + lc;
+    o0 = (size_t)row0 * e.ldc + col0;
+    rg = (m0 >> 6) + wm;                           // 64-row block of the whole matrix
+    cb = (n0 >> 6) + wn;
+    s1 = make_float4(0.f, 0.f, 0.f, 0.f); s2 = s1;
+    if constexpr (BNR) {
+      wpr = ((e.N + 255) >> 8) * 4;
+      bit = (col0 & 255) >> 2;
+      bw0 = e.bnr_bits + (size_t)row0 * wpr + (col0 >> 8) * 4;
+      mu = *reinterpret_cast<const float4*>(e.bnr_mean + col0);
+      rs = *reinterpret_cast<const float4*>(e.bnr_rstd + col0);
+    }
+  }
+
+  template <int J>
+  __device__ __forceinline__ void chunk(std::integral_constant<int, J>) {
+    const GemmArgs& e = k.e;
+    float4 nq, nz;
+    ulonglong2 n01, n23;
+    if constexpr (J < plp::kChainChunks) {
+      const size_t o = o0 + (size_t)J * 4 * e.ldc;
+      if constexpr (ADD) nq = *reinterpret_cast<const float4*>(e.addend + o);
+      if constexpr (BNR) {
+        nz = *reinterpret_cast<const float4*>(e.bnr_z + o);
+        const uint64_t* bw = bw0 + (size_t)(4 * J) * wpr;
+        n01 = *reinterpret_cast<const ulonglong2*>(bw);
+        n23 = *reinterpret_cast<const ulonglong2*>(bw + 2);
+      }
+    }
+    if constexpr (J >= D && J - D < plp::kChainChunks) {
+      constexpr int it = J - D, sl = it % D;
+      // (the read as an instruction of its own: hipcc lets no LDS load it knows of pass an LDS-DMA that might alias it -- it put
+      //  vmcnt(loads of this step) in front of a plain load, i.e. waited for the k-tile issued a moment ago, every step)
+      plp::f32x4v hv;
+      const uint32_t ha = (uint32_t)(size_t)(__attribute__((address_space(3))) float*)(blk + plp::hand_idx(4 * it + (lane >> 4), (lane & 15) * 4));
+      asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(hv) : "v"(ha) : "memory");
+      float4 v = make_float4(hv[0], hv[1], hv[2], hv[3]);
+      if constexpr (ADD) { v.x += qa[sl].x; v.y += qa[sl].y; v.z += qa[sl].z; v.w += qa[sl].w; }
+      float* dst = e.C + o0 + (size_t)it * 4 * e.ldc;
+      if (k.nt_store) {
+        typedef float f4v __attribute__((ext_vector_type(4)));
+        const f4v q = {v.x, v.y, v.z, v.w};
+        __builtin_nontemporal_store(q, reinterpret_cast<f4v*>(dst));
+      } else {
+        *reinterpret_cast<float4*>(dst) = v;
+      }
+      if constexpr (BNR) {
+        const float ks = e.bnr_kscale;
+        const float d0 = ((w01[sl].x >> bit) & 1ull) ? v.x * ks : 0.f;
+        const float d1 = ((w01[sl].y >> bit) & 1ull) ? v.y * ks : 0.f;
+        const float d2 = ((w23[sl].x >> bit) & 1ull) ? v.z * ks : 0.f;
+        const float d3 = ((w23[sl].y >> bit) & 1ull) ? v.w * ks : 0.f;
+        const float z0 = (zz[sl].x - mu.x) * rs.x, z1 = (zz[sl].y - mu.y) * rs.y;
+        const float z2 = (zz[sl].z - mu.z) * rs.z, z3 = (zz[sl].w - mu.w) * rs.w;
+        s1.x += d0; s1.y += d1; s1.z += d2; s1.w += d3;
+        s2.x = fmaf(d0, z0, s2.x); s2.y = fmaf(d1, z1, s2.y); s2.z = fmaf(d2, z2, s2.z); s2.w = fmaf(d3, z3, s2.w);
+        mxd = fmaxf(fmaxf(mxd, fmaxf(fabsf(d0), fabsf(d1))), fmaxf(fabsf(d2), fabsf(d3)));
+        mxz = fmaxf(fmaxf(mxz, fmaxf(fabsf(z0), fabsf(z1))), fmaxf(fabsf(z2), fabsf(z3)));
+        // the sums are read after the loop only: without this hipcc sinks the whole chain down there and keeps sixteen
+        // row-quads of loaded z and bitmap words alive for it (23-31 VGPRs spilled: scratch traffic inside the counted steps)
+        asm volatile("" : "+v"(s1.x), "+v"(s1.y), "+v"(s1.z), "+v"(s1.w), "+v"(s2.x), "+v"(s2.y), "+v"(s2.z), "+v"(s2.w),
+                          "+v"(mxd), "+v"(mxz));
+      }
+    }
+    if constexpr (J < plp::kChainChunks) {
+      if constexpr (ADD) qa[J % D] = nq;
+      if constexpr (BNR) { zz[J % D] = nz; w01[J % D] = n01; w23[J % D] = n23; }
+    }
+  }
+
+  // loader wave, after the last barrier: one partial row per 64-row block, in staged_epilogue's order
+  __device__ __forceinline__ void finish() {
+    if constexpr (BNR) {
+      const GemmArgs& e = k.e;
+      const int N = e.N;
+      s1 = xadd_rows(s1);
+      s2 = xadd_rows(s2);
+      if ((lane >> 4) == 0) {
+        *reinterpret_cast<float4*>(e.bnr_part_dy + (size_t)rg * N + col0) = s1;
+        *reinterpret_cast<float4*>(e.bnr_part_dyz + (size_t)rg * N + col0) = s2;
+      }
+      if (e.bnr_amax) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { mxd = fmaxf(mxd, __shfl_xor(mxd, o)); mxz = fmaxf(mxz, __shfl_xor(mxz, o)); }
+        if (lane == 0) {
+          float* q = e.bnr_amax + ((size_t)rg * (N >> 6) + cb) * 2;
+          q[0] = mxd; q[1] = mxz;
+        }
+      }
+    }
+  }
+};
+
+// the backward pair chained in one workgroup per CU (gemm_planes16.h CHAIN): grid = the number of dX tiles = dW items.
+// HAND: dX's epilogue on the loader waves, under dW's MFMAs (ADD / BNR: what that epilogue holds); else both epilogues on the
+// computing waves, staged through 34 KB behind the ring.
+template <int MODE, bool HAND, bool ADD = false, bool BNR = false>
 __global__ __launch_bounds__(512) void planes_gemm_chain_kernel(PlanesKern k0, PlanesKern k1) {
-  __shared__ __attribute__((aligned(16))) char lds[ring_bytes<MODE>() + stage_bytes<32>()];
+  constexpr int BEHIND = HAND ? plp::kHandBytes : stage_bytes<32>();
+  static_assert(ring_bytes<MODE>() + BEHIND <= 160 * 1024 && stage_bytes<32>() <= plp::kHandBytes, "LDS per CU");
+  __shared__ __attribute__((aligned(16))) char lds[ring_bytes<MODE>() + BEHIND];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wm = (wave & 3) >> 1, wn = wave & 1;
+  // (HAND: dW's epilogue stages through the hand-off blocks, which the loaders left before the loop's last barriers)
   float* ldsw = reinterpret_cast<float*>(lds + ring_bytes<MODE>()) + (wave & 3) * 32 * 68;
   auto epi0 = [&](plp::f32x4v (&acc)[plp::ModeCfg<MODE>::NACC][4][4], const int m0, const int n0, const int slice) {
-    acc_epilogue<MODE, 32, false>(k0, acc, ldsw, m0, n0, slice, wm, wn, lane);
+    if constexpr (!HAND) acc_epilogue<MODE, 32, false>(k0, acc, ldsw, m0, n0, slice, wm, wn, lane);
   };
   auto epi1 = [&](plp::f32x4v (&acc)[plp::ModeCfg<MODE>::NACC][4][4], const int m0, const int n0, const int slice) {
     acc_epilogue<MODE, 32, false>(k1, acc, ldsw, m0, n0, slice, wm, wn, lane);
   };
-  plp::planes_run16_chain<MODE>(k0.p, k1.p, blockIdx.x, gridDim.x, lds, epi0, epi1);
+  if constexpr (HAND) {
+    ChainHand<MODE, ADD, BNR> hand(k0, reinterpret_cast<float*>(lds + ring_bytes<MODE>()) + (wave & 3) * 64 * 64, lane);
+    plp::planes_run16_chain<MODE>(k0.p, k1.p, blockIdx.x, gridDim.x, lds, hand, epi0, epi1);
+  } else {
+    NoHand hand;
+    plp::planes_run16_chain<MODE>(k0.p, k1.p, blockIdx.x, gridDim.x, lds, hand, epi0, epi1);
+  }
 }
 
 // backward pair of one layer in one launch: workgroups [0, n0) run dX = dz W (NN), the rest dW = dz^T a (TN, split-K
@@ -481,16 +635,36 @@ int launch_routed(GemmLayout layout, const PlanesRoute& r, const PlanesKern& k, 
 }
 
 // the backward pair: chained (one workgroup per dX tile that goes on to a dW item, operands streaming across) or side by side
-enum class PairRoute { Chain, Dual };
+// ChainHand: the chained kernel with dX's epilogue on the loader waves (gemm_planes16.h HAND-OFF)
+enum class PairRoute { Chain, ChainHand, Dual };
+// what ChainHand's epilogue covers: a plain g store with, at most, the skip-gradient addend and BatchNorm-backward pass 1
+bool chain_hand_ok(const GemmArgs& e) {
+  return e.C && splits_of(e) == 1 && !e.bias && !e.col_scale && !e.relu && !e.resid && !e.cpl_kind && !e.stat_sum && !e.scat_on;
+}
 PairRoute pair_route(const PlanesGemmArgs& nn, const PlanesGemmArgs& tn) {
   const int ts = splits_of(tn.e);
   const bool chain = grid_of(nn) == grid_of(tn) && nn.e.K % 32 == 0 && nn.e.K >= 64 && tn.e.K % (32 * ts) == 0 && tn.e.K >= 32 * ts;
-  return chain ? PairRoute::Chain : PairRoute::Dual;
+  if (!chain) return PairRoute::Dual;
+  // the hand-off spreads dX's epilogue over k-steps 2 .. 2 + kChainChunks of every dW slice and must be done before the
+  // slice's last step: nk1 = K1 / (32 splits) >= kChainMinNk1 (20: H >= 640 in the lifter); shorter slices keep the epilogue
+  // on the computing waves
+  const int nk1 = tn.e.K / (32 * ts);
+  return nk1 >= plp::kChainMinNk1 && chain_hand_ok(nn.e) ? PairRoute::ChainHand : PairRoute::Chain;
 }
 template <int MODE>
 void launch_pair(PairRoute r, const PlanesKern& k0, const PlanesKern& k1, int g0, int g1, hipStream_t s) {
-  if (r == PairRoute::Chain) hipLaunchKernelGGL((planes_gemm_chain_kernel<MODE>), dim3(g0), dim3(512), 0, s, k0, k1);
-  else hipLaunchKernelGGL((planes_gemm_dual_kernel<MODE>), dim3(g0 + g1), dim3(512), 0, s, k0, k1, g0);
+  const dim3 block(512);
+  if (r == PairRoute::ChainHand) {
+    auto launch = [&](auto ADD, auto BNR) {
+      hipLaunchKernelGGL((planes_gemm_chain_kernel<MODE, true, decltype(ADD)::value, decltype(BNR)::value>), dim3(g0), block, 0, s, k0, k1);
+    };
+    auto with_bnr = [&](auto ADD) { if (k0.e.bnr_z) launch(ADD, Bool<true>{}); else launch(ADD, Bool<false>{}); };
+    if (k0.e.addend) with_bnr(Bool<true>{}); else with_bnr(Bool<false>{});
+  } else if (r == PairRoute::Chain) {
+    hipLaunchKernelGGL((planes_gemm_chain_kernel<MODE, false>), dim3(g0), block, 0, s, k0, k1);
+  } else {
+    hipLaunchKernelGGL((planes_gemm_dual_kernel<MODE>), dim3(g0 + g1), block, 0, s, k0, k1, g0);
+  }
 }
 
 }  // namespace
@@ -603,7 +777,7 @@ int launch_gemm_planes_pair(const PlanesGemmArgs& nn, const PlanesGemmArgs& tn, 
   if (nn.mode == plp::kF16x3) launch_pair<plp::kF16x3>(r, k0, k1, grid_of(nn), grid_of(tn), s);
   else launch_pair<plp::kBf16>(r, k0, k1, grid_of(nn), grid_of(tn), s);
   prof_end(prof, s);
-  PL_CHECK_LAUNCH(r == PairRoute::Chain ? "gemm_planes_chain" : "gemm_planes_dual");
+  PL_CHECK_LAUNCH(r == PairRoute::Dual ? "gemm_planes_dual" : "gemm_planes_chain");
   return PL_OK;
 }
 

@@ -20,6 +20,8 @@
 //  main loop -- every computing wave touching its block's lines BEFORE the loop, by LDS-DMA into a scratch KiB (no register,
 //  no wait), so that the burst would find them in the memory-side cache: 0.6395 / 0.6349 against 0.6269 / 0.6221: worse.)
 #pragma once
+#include <utility>
+
 #include "gemm_planes.h"
 
 namespace plp {
@@ -445,11 +447,48 @@ __device__ __forceinline__ void planes_run16(const PlanesArgs& p, const int bloc
 // two problems as two rounds of workgroups: when a CU's dX workgroup retired (after an epilogue that pulls the skip
 // gradient, the saved z and the bitmap: 50 MB chip-wide, no MFMA running anywhere) a dW workgroup had to be dispatched,
 // fetch its first k-tiles and fill its pipeline.  Here the loader waves issue dW's first k-tiles while the computing waves
-// are in dX's epilogue (which stages through LDS of its own, behind the ring), and nothing is re-dispatched.
+// are in dX's epilogue, and nothing is re-dispatched.  LDS behind the ring: short K1 slices -- 34 KB through which both
+// epilogues stage on the computing waves; the hand-off form below -- the four 16 KB hand-off blocks (ring + 64 KB = the CU's
+// 160 KB with two fp16 planes), which dW's epilogue, after the loop, stages through once the loaders are done with them.
 // Whole tiles, K0 and every K1 slice whole 32-k tiles, as many dX tiles as dW items (the host checks).
-template <int MODE, class Epi0, class Epi1>
+//
+// HAND-OFF (Hand::kOn; the host takes it where K1's slices are long enough, kChainMinNk1): dX's epilogue leaves the computing
+// waves.  After dX's last k-step computing wave w writes its 64 x 64 fp32 block -- the values acc_epilogue stages -- into a
+// region of LDS of its own behind the ring (hand.put), zeroes its accumulators and enters dW's k-loop at once; loader wave
+// 4 + w takes the block over and runs the epilogue on it one row-quad (4 rows x 64 columns) per k-step, between its DMA
+// issue and the step's barrier, with the lane <-> element mapping, the operations per element and the order of every
+// partial sum of staged_epilogue (gemm_planes.hip: ChainHand).  In stream steps (loader iteration kt of item 1 = the
+// barrier of step nk0 - 2 + kt):
+//   kt = kChainFirst + j, j = 0 .. kChainChunks + kChainAhead - 1:
+//        the global loads of row-quad j (skip gradient, saved z, bitmap; j < kChainChunks) -- they need nothing of the block and
+//        start while the computing waves are still in dX's last two steps -- then the LDS read, the arithmetic and the g store
+//        of row-quad j - kChainAhead: its loads were issued kChainAhead steps (2.3 us at 0.78 us per step) earlier, more
+//        than a trip to HBM under load.  The block is visible to the loaders after the barrier of step nk0 (that of kt = 2),
+//        so the first read is at kt >= 3.
+//   later kt                  plain; the column sums and the amax leave after the last barrier
+// Every wave still executes one barrier per k-step plus the three outside the loop: the loaders' step count does not depend
+// on the epilogue.  vmcnt counts loads, stores and LDS-DMA together in issue order, so every step issues a FIXED number of
+// them (an absent addend / BatchNorm pass is a template parameter of the hand, never a run-time branch) and the wait before
+// the barrier of a step is vmcnt(everything issued after k-tile g+1's DMAs) = the rest of the previous step + this step.
+constexpr int kChainChunks = 16;                                   // row-quads of a 64-row block, one per k-step
+constexpr int kChainAhead = 3;                                     // steps between a row-quad's loads and its arithmetic
+constexpr int kChainFirst = 0;                                     // item-1 loader iteration that carries row-quad 0's loads
+constexpr int kChainMinNk1 = kChainFirst + kChainChunks + kChainAhead + 1;     // the last row-quad leaves before the loop's last step
+static_assert(kChainFirst + kChainAhead >= 3, "the hand-off block is complete after the barrier of item-1 iteration 2");
+constexpr int kHandBytes = 4 * 64 * 64 * 4;                        // four 64 x 64 fp32 blocks, row stride 64 floats
+
+// float index of element (row, col) of a hand-off block: the 16-byte chunk of the 256-byte row is XORed with 4 ((row >> 2) & 3).
+// Accumulator layout (ds_write_b32: lane (q, c) writes row 16 rt + 4 q + r, column 16 ct + c): the two q of a 32-lane half
+// land on the two halves of the 32-bank row -- conflict-free; epilogue layout (ds_read_b128: lane (lr, ch) reads row
+// 4 it + lr, chunk ch): the XOR is the same for the whole instruction, every 16-lane group covers 16 distinct chunks.
+__device__ __forceinline__ int hand_idx(const int row, const int col) { return row * 64 + (col ^ (((row >> 2) & 3) << 4)); }
+
+template <class F, int... J>
+__device__ __forceinline__ void unroll_ints(F&& f, std::integer_sequence<int, J...>) { (f(std::integral_constant<int, J>{}), ...); }
+
+template <int MODE, class Hand, class Epi0, class Epi1>
 __device__ __forceinline__ void planes_run16_chain(const PlanesArgs& p0, const PlanesArgs& p1, const int block_id, const int nwork,
-                                                   char* __restrict__ lds, Epi0&& epi0, Epi1&& epi1) {
+                                                   char* __restrict__ lds, Hand& hand, Epi0&& epi0, Epi1&& epi1) {
   static_assert(MODE == kF16x3 || MODE == kBf16, "two fp16 planes or one bf16 plane");
   constexpr int NPL = ModeCfg<MODE>::NPL, NACC = ModeCfg<MODE>::NACC;
   using Cf = PlanesCfg<32, NPL, 3>;
@@ -538,9 +577,26 @@ __device__ __forceinline__ void planes_run16_chain(const PlanesArgs& p0, const P
     wait_vmcnt<Cf::NDMA>();
     barrier();
     for (int g = 0; g + 2 < nk0; ++g) { issue0(g + 2); wait_vmcnt<Cf::NDMA>(); barrier(); }
-    for (int kt = 0; kt < nk1; ++kt) { issue1(kt); wait_vmcnt<Cf::NDMA>(); barrier(); }       // steps nk0 - 2 .. total - 3
+    if constexpr (!Hand::kOn) {
+      for (int kt = 0; kt < nk1; ++kt) { issue1(kt); wait_vmcnt<Cf::NDMA>(); barrier(); }     // steps nk0 - 2 .. total - 3
+    } else {
+      // (host: nk1 >= kChainMinNk1)  nk1 iterations as above, kChainChunks + kChainAhead of them with a piece of dX's epilogue
+      hand.begin(m00, n00, wm, wn);
+      for (int kt = 0; kt < kChainFirst; ++kt) { issue1(kt); wait_vmcnt<Cf::NDMA>(); barrier(); }
+      unroll_ints([&](auto jc) {
+        constexpr int J = decltype(jc)::value;
+        issue1(kChainFirst + J);
+        __builtin_amdgcn_sched_barrier(0);           // the DMAs first: what follows them is what the next step's wait counts
+        hand.chunk(jc);
+        wait_vmcnt<Hand::vm_ops(J - 1) + Cf::NDMA + Hand::vm_ops(J)>();
+        barrier();
+      }, std::make_integer_sequence<int, kChainChunks + kChainAhead>{});
+      // (the first of these waits for the last row-quad's store as well: vmcnt(NDMA) leaves only this step's DMAs in flight)
+      for (int kt = kChainFirst + kChainChunks + kChainAhead; kt < nk1; ++kt) { issue1(kt); wait_vmcnt<Cf::NDMA>(); barrier(); }
+    }
     wait_vmcnt<0>(); barrier();
     wait_vmcnt<0>(); barrier();
+    if constexpr (Hand::kOn) hand.finish();
     return;
   }
 
@@ -641,7 +697,7 @@ __device__ __forceinline__ void planes_run16_chain(const PlanesArgs& p0, const P
   zero_acc();
   nk = nk0;
   if (nk > 0) run_item(F_{});
-  epi0(acc, m00, n00, 0);
+  if constexpr (Hand::kOn) hand.put(acc); else epi0(acc, m00, n00, 0);
   zero_acc();
   nk = nk1;
   if (nk > 0) run_item(T_{});
