@@ -138,6 +138,7 @@ SIGNATURES = {
     "pl_lifter_train_fwd_bwd": (_c.c_int, [_D, _P, _P, _c.c_int64, _P, _c.c_size_t, _c.c_uint64, _c.c_uint64,
                                            _P, _P, _P, _c.c_int, _c.c_int, _P]),
     "pl_lifter_step_carries_adamw": (_c.c_int, [_D, _c.c_int64]),
+    "pl_lifter_bwd_slab_rides": (_c.c_int, [_D, _c.c_int64, _c.c_int, _c.c_int]),
     "pl_lifter_train_step": (_c.c_int, [_D, _P, _P, _c.c_int64, _P, _c.c_size_t, _c.c_uint64, _c.c_uint64,
                                         _P, _P, _P, _c.POINTER(PLAdamWStep), _P]),
     "pl_lifter_train_fwd_bwd_crit": (_c.c_int, [_D, _P, _P, _c.c_int64, _P, _c.c_size_t, _c.c_uint64, _c.c_uint64,

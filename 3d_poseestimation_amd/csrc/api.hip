@@ -784,6 +784,8 @@ struct BwdCtx {
   bool adam_rides;
   // bias gradients and split-K slabs = column sums of partials; all of them are reduced by ONE launch at the end
   std::vector<RowJob> jobs;
+  // ... but for the slab sum of the layer above where the next pair launch carries it (slab_sum_rides_below): R > 0
+  RowJob pending = {};
 
   float* buf(size_t off) const { return f32(ws, off); }
   float* GA() const { return buf(w.ga); }
@@ -831,6 +833,29 @@ BnrEpilogue bnr_of(const BwdCtx& c, int l) {
 void set_bnr(GemmArgs& e, const BnrEpilogue& b) {     // the planes GEMM carries it in its epilogue fields
   e.bnr_z = b.z; e.bnr_bits = b.bits; e.bnr_mean = b.mean; e.bnr_rstd = b.rstd; e.bnr_kscale = b.kscale;
   e.bnr_part_dy = b.part_dy; e.bnr_part_dyz = b.part_dyz; e.bnr_amax = b.amax;
+}
+
+// The backward pair of a hidden layer on the planes, as its route decisions read it: shapes, mode, split and the two outputs
+// (every such layer's pair has the same shapes).  The operands and what rides in dX's epilogue are the caller's to add.
+void pair_problems(const Ws& w, int H, int B, float* g_out, float* dw_out, PlanesGemmArgs& nn, PlanesGemmArgs& tn) {
+  const int64_t BH = (int64_t)B * H;
+  nn = planes_args(w.pkind, nullptr, BH, H, nullptr, (int64_t)H * H, H, g_out, B, H, H, 1.0f / kWeightPlaneScale, nullptr);
+  tn = planes_args(w.pkind, nullptr, BH, H, nullptr, BH, H, dw_out, H, H, B, 1.0f / kActPlaneScale, nullptr);
+  tn.e.split_k = tn_splits(H, H, B);
+}
+// Is the split-K sum of layer l's weight gradient carried by the chained launch of layer l - 1's pair (gemm_planes16.h SLAB
+// RIDE) rather than by the range's reduce launch?  Both layers run the planes pair in this call's range [.., l_lo], layer l
+// leaves slabs, and the GEMM says its launch can take them (planes_pair_carries_slab_sum: the route, the slab count, the
+// deal over the loader waves and dX's step count).
+bool slab_sum_rides_below(const Ws& w, int H, int B, int l, int l_lo) {
+  if (l - 1 < l_lo || l - 1 < 1 || l >= w.L) return false;
+  if (w.layer[l].bwd != Bwd::PlanesPair || w.layer[l - 1].bwd != Bwd::PlanesPair) return false;
+  const int splits = tn_splits(H, H, B);
+  if (splits <= 1) return false;
+  static float placeholder[4];                     // outputs that exist, for the route's sake; nothing is launched from here
+  PlanesGemmArgs nn, tn;
+  pair_problems(w, H, B, placeholder, placeholder, nn, tn);
+  return planes_pair_carries_slab_sum(nn, tn, splits, (int64_t)H * H);
 }
 
 // The output layer (LinearModel.w2): dW = dy^T h, db = sum dy, g = dy W -> GA.  Three routes.
@@ -946,18 +971,25 @@ int bwd_layer_linear(BwdCtx& c, int l) {
   if (c.planes_pair(l)) {
     // dX = dz W (NN) and dW = dz^T a (TN, split-K slabs) on the planes: one launch
     float* dzs = c.dzs(l);
-    const int64_t BH = c.BH();
     const int splits = tn_splits(H, H, Bi);
-    PlanesGemmArgs nn = planes_args(w.pkind, u16(c.ws, w.dzp), BH, H, wplane(d, w, c.ws, l), (int64_t)H * H, H,
-                                    (l % 2 == 1) ? GA : GB, Bi, H, H, 1.0f / kWeightPlaneScale, dzs ? dzs + 1 : nullptr);
+    // this layer's own slabs: combined by the launch of the pair below where that carries the sum, else by the range's one
+    // reduce launch; nothing reads them or gW in between
+    float* wsl = c.buf(w.wslab[l]);
+    PlanesGemmArgs nn, tn;
+    pair_problems(w, H, Bi, (l % 2 == 1) ? GA : GB, splits > 1 ? wsl : ly.gW, nn, tn);
+    nn.A = tn.A = u16(c.ws, w.dzp);
+    nn.B = wplane(d, w, c.ws, l);
+    tn.B = u16(c.ws, w.actp[l - 1]);
+    if (w.pkind == 2) nn.dyn_inv = tn.dyn_inv = dzs ? dzs + 1 : nullptr;
     if (l % 2 == 1) nn.e.addend = GA;
     if (!c.eval_bn && w.layer[l - 1].bnr_fused) set_bnr(nn.e, bnr_of(c, l - 1));      // pass 1 of the layer below, on the block just produced
-    float* wsl = c.buf(w.wslab[l]);                  // this layer's own slabs: combined by the range's one reduce launch
-    PlanesGemmArgs tn = planes_args(w.pkind, u16(c.ws, w.dzp), BH, H, u16(c.ws, w.actp[l - 1]), BH, H,
-                                    splits > 1 ? wsl : ly.gW, H, H, Bi, 1.0f / kActPlaneScale, dzs ? dzs + 1 : nullptr);
-    tn.e.split_k = splits;
-    PL_TRY(launch_gemm_planes_pair(nn, tn, s));
-    if (splits > 1) c.job(wsl, ly.gW, splits, H * H, 1, 0);
+    const SlabSum above = {c.pending.part, c.pending.out, c.pending.R, (int64_t)c.pending.H};
+    PL_TRY(launch_gemm_planes_pair(nn, tn, c.pending.R > 0 ? &above : nullptr, s));
+    c.pending = RowJob{};
+    if (splits > 1) {
+      const RowJob sum = {wsl, ly.gW, splits, H * H, 1, 0};
+      if (slab_sum_rides_below(w, H, Bi, l, c.l_lo)) c.pending = sum; else c.jobs.push_back(sum);
+    }
   } else if (l > 0) {
     // off the planes path: dX = dz W (+ the skip gradient a residual block's first Linear receives in GA, added in the
     // epilogue) and dW = dz^T a_in
@@ -1055,6 +1087,7 @@ static int bwd_impl(const PLDesc* d, const float* x, const float* dy, int64_t B,
     PL_TRY(bwd_layer_bn(c, l));
     PL_TRY(bwd_layer_linear(c, l));
   }
+  if (c.pending.R > 0) c.jobs.push_back(c.pending);       // (slab_sum_rides_below promised a launch that then took it: none is left)
   float inv_n = 0.f;
   uint64_t* tick = nullptr;
   if (loss_out && !c.top_fused) {
@@ -1402,6 +1435,16 @@ extern "C" int pl_lifter_train_fwd_bwd(const PLDesc* d, const float* x, const fl
 extern "C" int pl_lifter_step_carries_adamw(const PLDesc* d, int64_t B) {
   PL_TRY(check_desc(d, false));
   return B > 0 && plan(d, B).adam_rides ? 1 : 0;
+}
+
+extern "C" int pl_lifter_bwd_slab_rides(const PLDesc* d, int64_t B, int hi, int lo) {
+  PL_TRY(check_desc(d, false));
+  PL_TRY(check_range(d, hi, lo, "pl_lifter_bwd_slab_rides"));
+  if (B <= 0 || B > INT32_MAX) return 0;
+  const Ws w = plan(d, B);
+  int n = 0;
+  for (int l = hi < w.L ? hi : w.L - 1; l > lo; --l) n += pl::slab_sum_rides_below(w, d->hidden, (int)B, l, lo) ? 1 : 0;
+  return n;
 }
 
 extern "C" int pl_lifter_train_step_crit(const PLDesc* d, const float* x, const float* target, int64_t B, void* ws,

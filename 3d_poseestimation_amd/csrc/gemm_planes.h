@@ -60,6 +60,15 @@ struct PlanesArgs {
   int cv_cin, cv_h, cv_w, cv_ho, cv_wo, cv_kw, cv_stride, cv_stride_w, cv_pad_h, cv_pad_w;
 };
 
+// A split-K sum that rides on the loader waves of a chained launch (gemm_planes16.h SLAB RIDE): out[i] = ((s0[i] + s1[i]) +
+// s2[i]) + s3[i] over n4 float4, slab r at part + r * stride floats.  part == NULL: no ride.
+struct SlabRide {
+  const float* part;
+  float* out;
+  long long stride;
+  int R, n4;
+};
+
 template <int BKX, int NPL, int NST = 3>
 struct PlanesCfg {
   static constexpr int OPP = 128 * BKX * 2;     // one plane of one operand tile, bytes

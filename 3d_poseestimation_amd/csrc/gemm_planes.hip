@@ -497,7 +497,7 @@ struct ChainHand {
 // HAND: dX's epilogue on the loader waves, under dW's MFMAs (ADD / BNR: what that epilogue holds); else both epilogues on the
 // computing waves, staged through 34 KB behind the ring.
 template <int MODE, bool HAND, bool ADD = false, bool BNR = false>
-__global__ __launch_bounds__(512) void planes_gemm_chain_kernel(PlanesKern k0, PlanesKern k1) {
+__global__ __launch_bounds__(512) void planes_gemm_chain_kernel(PlanesKern k0, PlanesKern k1, plp::SlabRide ride) {
   constexpr int BEHIND = HAND ? plp::kHandBytes : stage_bytes<32>();
   static_assert(ring_bytes<MODE>() + BEHIND <= 160 * 1024 && stage_bytes<32>() <= plp::kHandBytes, "LDS per CU");
   __shared__ __attribute__((aligned(16))) char lds[ring_bytes<MODE>() + BEHIND];
@@ -513,10 +513,10 @@ __global__ __launch_bounds__(512) void planes_gemm_chain_kernel(PlanesKern k0, P
   };
   if constexpr (HAND) {
     ChainHand<MODE, ADD, BNR> hand(k0, reinterpret_cast<float*>(lds + ring_bytes<MODE>()) + (wave & 3) * 64 * 64, lane);
-    plp::planes_run16_chain<MODE>(k0.p, k1.p, blockIdx.x, gridDim.x, lds, hand, epi0, epi1);
+    plp::planes_run16_chain<MODE>(k0.p, k1.p, ride, blockIdx.x, gridDim.x, lds, hand, epi0, epi1);
   } else {
     NoHand hand;
-    plp::planes_run16_chain<MODE>(k0.p, k1.p, blockIdx.x, gridDim.x, lds, hand, epi0, epi1);
+    plp::planes_run16_chain<MODE>(k0.p, k1.p, ride, blockIdx.x, gridDim.x, lds, hand, epi0, epi1);
   }
 }
 
@@ -651,17 +651,27 @@ PairRoute pair_route(const PlanesGemmArgs& nn, const PlanesGemmArgs& tn) {
   const int nk1 = tn.e.K / (32 * ts);
   return nk1 >= plp::kChainMinNk1 && chain_hand_ok(nn.e) ? PairRoute::ChainHand : PairRoute::Chain;
 }
+// Can the pair's launch carry a split-K sum -- `slabs` slabs of n floats -- on its loader waves (gemm_planes16.h SLAB RIDE)?
+// Only the hand-off form has the ride; its arithmetic exists for four slabs; the float4s are dealt kRideChunks to a loader
+// lane over grid x 4 waves x 64 lanes, exactly (which, chained, means B = H x 4: the lifter's H = 1024 at B = 4096); and
+// the ride's kRideChunks + kChainAhead steps, from loader iteration kRideFirst on, must lie within dX's nk0 - 2 iterations.
+bool pair_carries_slab_sum(const PlanesGemmArgs& nn, const PlanesGemmArgs& tn, int slabs, int64_t n) {
+  if (pair_route(nn, tn) != PairRoute::ChainHand) return false;
+  const int nk0 = nn.e.K / 32;
+  return slabs == plp::kRideSlabs && n == (int64_t)plp::kRideChunks * 4 * 64 * 4 * grid_of(nn) && nk0 >= plp::kRideMinNk0;
+}
 template <int MODE>
-void launch_pair(PairRoute r, const PlanesKern& k0, const PlanesKern& k1, int g0, int g1, hipStream_t s) {
+void launch_pair(PairRoute r, const PlanesKern& k0, const PlanesKern& k1, const plp::SlabRide& ride, int g0, int g1, hipStream_t s) {
   const dim3 block(512);
   if (r == PairRoute::ChainHand) {
     auto launch = [&](auto ADD, auto BNR) {
-      hipLaunchKernelGGL((planes_gemm_chain_kernel<MODE, true, decltype(ADD)::value, decltype(BNR)::value>), dim3(g0), block, 0, s, k0, k1);
+      hipLaunchKernelGGL((planes_gemm_chain_kernel<MODE, true, decltype(ADD)::value, decltype(BNR)::value>), dim3(g0), block, 0, s, k0, k1,
+                         ride);
     };
     auto with_bnr = [&](auto ADD) { if (k0.e.bnr_z) launch(ADD, Bool<true>{}); else launch(ADD, Bool<false>{}); };
     if (k0.e.addend) with_bnr(Bool<true>{}); else with_bnr(Bool<false>{});
   } else if (r == PairRoute::Chain) {
-    hipLaunchKernelGGL((planes_gemm_chain_kernel<MODE, false>), dim3(g0), block, 0, s, k0, k1);
+    hipLaunchKernelGGL((planes_gemm_chain_kernel<MODE, false>), dim3(g0), block, 0, s, k0, k1, plp::SlabRide{});
   } else {
     hipLaunchKernelGGL((planes_gemm_dual_kernel<MODE>), dim3(g0 + g1), block, 0, s, k0, k1, g0);
   }
@@ -768,14 +778,27 @@ int launch_gemm_planes(GemmLayout layout, const PlanesGemmArgs& a, hipStream_t s
   return PL_OK;
 }
 
-int launch_gemm_planes_pair(const PlanesGemmArgs& nn, const PlanesGemmArgs& tn, hipStream_t s) {
+bool planes_pair_carries_slab_sum(const PlanesGemmArgs& nn, const PlanesGemmArgs& tn, int slabs, int64_t n) {
+  return pair_carries_slab_sum(nn, tn, slabs, n);
+}
+
+int launch_gemm_planes_pair(const PlanesGemmArgs& nn, const PlanesGemmArgs& tn, const SlabSum* sum, hipStream_t s) {
   if (!planes_gemm_ok(kNN, nn) || !planes_gemm_ok(kTN, tn) || nn.mode != tn.mode || is_edge(nn) || is_edge(tn))
     PL_FAIL(PL_ESHAPE, "gemm_planes_pair: unsupported problems");
   const PlanesKern k0 = kern_of(nn), k1 = kern_of(tn);
   const PairRoute r = pair_route(nn, tn);
+  plp::SlabRide ride = {};
+  if (sum) {
+    // the caller asked planes_pair_carries_slab_sum first: a sum this launch cannot carry is an error, not a silent drop
+    if (!sum->part || !sum->out || !pair_carries_slab_sum(nn, tn, sum->slabs, sum->n))
+      PL_FAIL(PL_ESHAPE, "gemm_planes_pair: cannot carry a sum of %d slabs of %lld floats", sum->slabs, (long long)sum->n);
+    if ((reinterpret_cast<uintptr_t>(sum->part) | reinterpret_cast<uintptr_t>(sum->out)) & 15)
+      PL_FAIL(PL_EINVAL, "gemm_planes_pair: slab sum alignment");
+    ride.part = sum->part; ride.out = sum->out; ride.stride = sum->n; ride.R = sum->slabs; ride.n4 = (int)(sum->n / 4);
+  }
   void* prof = prof_begin_flops(2.0 * nn.e.M * nn.e.N * nn.e.K + 2.0 * tn.e.M * tn.e.N * tn.e.K, s);
-  if (nn.mode == plp::kF16x3) launch_pair<plp::kF16x3>(r, k0, k1, grid_of(nn), grid_of(tn), s);
-  else launch_pair<plp::kBf16>(r, k0, k1, grid_of(nn), grid_of(tn), s);
+  if (nn.mode == plp::kF16x3) launch_pair<plp::kF16x3>(r, k0, k1, ride, grid_of(nn), grid_of(tn), s);
+  else launch_pair<plp::kBf16>(r, k0, k1, ride, grid_of(nn), grid_of(tn), s);
   prof_end(prof, s);
   PL_CHECK_LAUNCH(r == PairRoute::Dual ? "gemm_planes_dual" : "gemm_planes_chain");
   return PL_OK;

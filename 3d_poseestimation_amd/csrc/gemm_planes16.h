@@ -486,9 +486,75 @@ __device__ __forceinline__ int hand_idx(const int row, const int col) { return r
 template <class F, int... J>
 __device__ __forceinline__ void unroll_ints(F&& f, std::integer_sequence<int, J...>) { (f(std::integral_constant<int, J>{}), ...); }
 
+// SLAB RIDE (Hand::kOn form; the host decides, gemm_planes.hip pair_carries_slab_sum): in dX's half of the launch the loader
+// waves have nothing to do between their DMA issue and the step's barrier.  There they add up the kRideSlabs split-K slabs the
+// chained launch of the layer ABOVE left -- complete at this kernel's boundary, read by nothing before the launches behind
+// this one -- with the arithmetic of reduce_rows_multi_kernel's R == 4 branch: ((s0 + s1) + s2) + s3 per float4, one store.
+// The n4 float4 are dealt over the launch's loader waves: wave wv = 4 block + (wave - 4) of nwaves = 4 grid owns, as chunk j,
+// float4 (j nwaves + wv) 64 + lane (1 KB contiguous per instruction), j < kRideChunks; the host checks n4 = kRideChunks x 64
+// nwaves, so every index is owned exactly once and none lies past the end.  Schedule, in loader iterations g of item 0:
+//   g = kRideFirst + j, j = 0 .. kRideChunks + kChainAhead - 1:
+//        behind the step's DMAs the four slab loads of chunk j (j < kRideChunks), then the sums and the store of chunk
+//        j - kChainAhead; the wait before the barrier is vmcnt(rest of the previous step + this step), as in the hand-off
+//   every other g             plain
+// The ride is a kernel-uniform switch taken OUTSIDE the k-loop (a scalar branch on the slab pointer): either loop issues a fixed
+// number of vector-memory operations per step.  No LDS, no barrier of its own; its registers are dead before hand.begin().
+constexpr int kRideSlabs = 4;                                      // slabs per sum (the lifter's tn_splits at H = 1024)
+constexpr int kRideChunks = 4;                                     // float4 per loader lane: 16 / kRideSlabs where B = H x splits
+constexpr int kRideFirst = 12;                                     // item-0 loader iteration that carries chunk 0's loads
+constexpr int kRideMinNk0 = kRideFirst + kRideChunks + kChainAhead + 2;        // the last chunk leaves within dX's nk0 - 2 iterations
+
+struct SlabRider {
+  static constexpr int D = kChainAhead;
+  // vector-memory operations of chunk(J): the slab loads of chunk J, the store of chunk J - D
+  static constexpr int vm_ops(int j) { return (j >= 0 && j < kRideChunks ? kRideSlabs : 0) + (j >= D && j - D < kRideChunks ? 1 : 0); }
+  const float* src;
+  float* dst;
+  size_t stride, step;
+  float4 a[D], b1[D], b2[D], b3[D];                // chunks in flight (slot = chunk % D; the indices are compile-time)
+
+  __device__ __forceinline__ void begin(const SlabRide& r, const int wv, const int nwaves, const int lane) {
+    const size_t o = ((size_t)wv * 64 + lane) * 4;
+    src = r.part + o;
+    dst = r.out + o;
+    stride = (size_t)r.stride;
+    step = (size_t)nwaves * 64 * 4;
+  }
+
+  template <int J>
+  __device__ __forceinline__ void chunk(std::integral_constant<int, J>) {
+    // (nontemporal both ways: the slabs are read once and gW is next read by AdamW, many launches on.  With plain loads and a
+    //  plain store the 21 MB per launch went through the L2s the GEMM's operand tiles live in: the reduce launch shrank by 8 us
+    //  and the GEMM launches of the step grew by as much -- same-box A/B, profiles/chain_slab_ride_ab.txt)
+    auto ld = [](const float* p) {
+      const f32x4v t = __builtin_nontemporal_load(reinterpret_cast<const f32x4v*>(p));
+      return make_float4(t[0], t[1], t[2], t[3]);
+    };
+    float4 na, n1, n2, n3;
+    if constexpr (J < kRideChunks) {
+      const float* q = src + J * step;
+      na = ld(q);
+      n1 = ld(q + stride);
+      n2 = ld(q + 2 * stride);
+      n3 = ld(q + 3 * stride);
+    }
+    if constexpr (J >= D && J - D < kRideChunks) {
+      constexpr int it = J - D, sl = it % D;
+      float4 v = a[sl];
+      v.x += b1[sl].x; v.y += b1[sl].y; v.z += b1[sl].z; v.w += b1[sl].w;
+      v.x += b2[sl].x; v.y += b2[sl].y; v.z += b2[sl].z; v.w += b2[sl].w;
+      v.x += b3[sl].x; v.y += b3[sl].y; v.z += b3[sl].z; v.w += b3[sl].w;
+      asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w));       // the sum as written, in this step
+      const f32x4v t = {v.x, v.y, v.z, v.w};
+      __builtin_nontemporal_store(t, reinterpret_cast<f32x4v*>(dst + it * step));
+    }
+    if constexpr (J < kRideChunks) { a[J % D] = na; b1[J % D] = n1; b2[J % D] = n2; b3[J % D] = n3; }
+  }
+};
+
 template <int MODE, class Hand, class Epi0, class Epi1>
-__device__ __forceinline__ void planes_run16_chain(const PlanesArgs& p0, const PlanesArgs& p1, const int block_id, const int nwork,
-                                                   char* __restrict__ lds, Hand& hand, Epi0&& epi0, Epi1&& epi1) {
+__device__ __forceinline__ void planes_run16_chain(const PlanesArgs& p0, const PlanesArgs& p1, const SlabRide& ride, const int block_id,
+                                                   const int nwork, char* __restrict__ lds, Hand& hand, Epi0&& epi0, Epi1&& epi1) {
   static_assert(MODE == kF16x3 || MODE == kBf16, "two fp16 planes or one bf16 plane");
   constexpr int NPL = ModeCfg<MODE>::NPL, NACC = ModeCfg<MODE>::NACC;
   using Cf = PlanesCfg<32, NPL, 3>;
@@ -576,7 +642,26 @@ __device__ __forceinline__ void planes_run16_chain(const PlanesArgs& p0, const P
     issue0(1);
     wait_vmcnt<Cf::NDMA>();
     barrier();
-    for (int g = 0; g + 2 < nk0; ++g) { issue0(g + 2); wait_vmcnt<Cf::NDMA>(); barrier(); }
+    bool rides = false;
+    if constexpr (Hand::kOn) rides = ride.part != nullptr;        // kernel-uniform: a scalar branch, outside the k-loop
+    if (!rides) {
+      for (int g = 0; g + 2 < nk0; ++g) { issue0(g + 2); wait_vmcnt<Cf::NDMA>(); barrier(); }
+    } else {
+      // (host: nk0 >= kRideMinNk0)  the same nk0 - 2 iterations, kRideChunks + kChainAhead of them with a piece of the slab sum
+      SlabRider rd;
+      rd.begin(ride, block_id * 4 + lw, nwork * 4, lane);
+      for (int g = 0; g < kRideFirst; ++g) { issue0(g + 2); wait_vmcnt<Cf::NDMA>(); barrier(); }
+      unroll_ints([&](auto jc) {
+        constexpr int J = decltype(jc)::value;
+        issue0(kRideFirst + J + 2);
+        __builtin_amdgcn_sched_barrier(0);
+        rd.chunk(jc);
+        wait_vmcnt<SlabRider::vm_ops(J - 1) + Cf::NDMA + SlabRider::vm_ops(J)>();
+        barrier();
+      }, std::make_integer_sequence<int, kRideChunks + kChainAhead>{});
+      // (the first of these waits for the last chunk's store as well)
+      for (int g = kRideFirst + kRideChunks + kChainAhead; g + 2 < nk0; ++g) { issue0(g + 2); wait_vmcnt<Cf::NDMA>(); barrier(); }
+    }
     if constexpr (!Hand::kOn) {
       for (int kt = 0; kt < nk1; ++kt) { issue1(kt); wait_vmcnt<Cf::NDMA>(); barrier(); }     // steps nk0 - 2 .. total - 3
     } else {

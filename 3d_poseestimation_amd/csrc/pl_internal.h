@@ -176,8 +176,13 @@ struct PlanesRoute {
 };
 PlanesRoute planes_route(GemmLayout layout, const PlanesGemmArgs& a, int ncu);
 int launch_gemm_planes(GemmLayout layout, const PlanesGemmArgs& a, hipStream_t s);
-// dX = dz W (NN) and dW = dz^T a (TN, split-K slabs) of one layer in ONE launch
-int launch_gemm_planes_pair(const PlanesGemmArgs& nn, const PlanesGemmArgs& tn, hipStream_t s);
+// dX = dz W (NN) and dW = dz^T a (TN, split-K slabs) of one layer in ONE launch.  `sum` (or NULL): a split-K sum of another
+// layer that the launch carries on its loader waves -- out[n] = the slabs part + r n, r < slabs, added in slab order, with
+// the arithmetic of launch_reduce_rows_multi's kind-1 job; nothing else may touch part or out while the launch runs.  Ask
+// planes_pair_carries_slab_sum first: a sum the launch cannot carry is an error.
+struct SlabSum { const float* part; float* out; int slabs; int64_t n; };
+bool planes_pair_carries_slab_sum(const PlanesGemmArgs& nn, const PlanesGemmArgs& tn, int slabs, int64_t n);
+int launch_gemm_planes_pair(const PlanesGemmArgs& nn, const PlanesGemmArgs& tn, const SlabSum* sum, hipStream_t s);
 // x [n] fp32 -> planes (static scale); n % 4 == 0, 16-byte aligned
 int launch_split_planes(const float* x, int64_t n, const PlaneOut& out, hipStream_t s);
 // PlaneOut of a caller's planes buffer ([2][n] fp16 for PL_F16X3, [n] bf16 for PL_BF16; NULL -> kind 0)
