@@ -5,7 +5,7 @@ alias module at the repository root.
 """
 from ._lib import PoseliftError, lib  # noqa: F401
 from .model import Linear, LinearModel, weight_init  # noqa: F401
-from .optim import FlatAdamW  # noqa: F401
+from .optim import FlatAdamW, FlatOptimizer  # noqa: F401
 from .arena import FlatAdam, ModuleArena  # noqa: F401
 from .train import (crop_poses, cycle_step, epoch_mpjpe_mm, eval_step, flip_average, flip_frames_nhwc, flip_pose, loss_MPJPE, mse_loss,  # noqa: F401
                     predict_flip_tta, train_step, uncrop_poses, GraphedTrainStep, GraphedModuleStep)

@@ -57,10 +57,14 @@ class PLAdamWPlanes(ctypes.Structure):
                 ("reserved", ctypes.c_int32), ("seg", PLAdamWSeg * ADAMW_MAX_SEGS)]
 
 
+class PLEma(ctypes.Structure):
+    _fields_ = [("e", ctypes.c_void_p), ("decay", ctypes.c_float), ("warmup", ctypes.c_int32), ("t0", ctypes.c_int64)]
+
+
 class PLAdamWStep(ctypes.Structure):
     _fields_ = [("m", ctypes.c_void_p), ("v", ctypes.c_void_p), ("lr", ctypes.c_float), ("lr_dev", ctypes.c_void_p),
                 ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float), ("weight_decay", ctypes.c_float),
-                ("t", ctypes.c_int64), ("t_dev", ctypes.c_void_p)]
+                ("t", ctypes.c_int64), ("t_dev", ctypes.c_void_p), ("ema", ctypes.POINTER(PLEma))]
 
 
 CRIT_MSE, CRIT_L1, CRIT_SMOOTH_L1, CRIT_MPJPE = 0, 1, 2, 3
@@ -174,6 +178,10 @@ SIGNATURES = {
                                           _c.c_float, _c.c_int64, _P, _c.c_float, _P, _P]),
     "pl_adamw_flat_planes_clip": (_c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_float, _P, _c.c_float, _c.c_float, _c.c_float,
                                              _c.c_float, _c.c_int64, _P, _c.c_float, _c.POINTER(PLAdamWPlanes), _P, _P]),
+    "pl_adamw_flat_planes_clip_ema": (_c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_float, _P, _c.c_float, _c.c_float, _c.c_float,
+                                                 _c.c_float, _c.c_int64, _P, _c.c_float, _c.POINTER(PLAdamWPlanes), _P,
+                                                 _c.POINTER(PLEma), _P]),
+    "pl_swap_f32": (_c.c_int, [_P, _P, _c.c_int64, _P]),
     "pl_wplanes_bytes": (_c.c_size_t, [_D]),
     "pl_wplanes_layer_bytes": (_c.c_size_t, [_D]),
     "pl_weight_plane_scale": (_c.c_float, []),

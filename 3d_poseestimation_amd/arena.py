@@ -86,14 +86,16 @@ class FlatAdam(FlatOptimizer):
     """torch.optim.Adam(module.parameters(), lr, betas, eps) as one library launch over the module's flat arenas."""
 
     def __init__(self, module, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable=False,
-                 decoupled_weight_decay=False, max_grad_norm=None, skip_nonfinite=False):
+                 decoupled_weight_decay=False, max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=False):
         if weight_decay != 0.0 and not decoupled_weight_decay:
             raise NotImplementedError("FlatAdam: Adam's coupled L2 weight decay is not implemented (the reference uses 0); "
                                       "decoupled_weight_decay=True is AdamW")
         self.arena = a = arena_of(module)
+        self._module = module
         super().__init__(a.params, dict(lr=lr, betas=betas, eps=eps, weight_decay=float(weight_decay),
                                         capturable=bool(capturable), decoupled_weight_decay=bool(decoupled_weight_decay),
-                                        max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite))
+                                        max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite,
+                                        ema_decay=ema_decay, ema_warmup=ema_warmup))
         self._m, self._v = torch.zeros_like(a.flat), torch.zeros_like(a.flat)
         dev = a.flat.device
         # _t / _t_dev: ATTEMPTED steps, as in the base; taken = attempted - the clip record's skipped count
@@ -104,11 +106,22 @@ class FlatAdam(FlatOptimizer):
         for p, o in zip(a.params, a.offsets):
             n = p.numel()
             self.state[p] = {"step": step, "exp_avg": self._m[o:o + n].view(p.shape), "exp_avg_sq": self._v[o:o + n].view(p.shape)}
+        self._ema_bind()                 # (ema_decay: the EMA arena beside m and v, a copy of the parameters as they are now)
 
     def _arenas(self):
         return self.arena.flat, self.arena.grad
 
+    def _param_offsets(self):
+        return list(zip(self.arena.params, self.arena.offsets))
+
+    def _ema_module(self):
+        return self._module
+
+    def _attempted_host(self):
+        return int(self._t_dev.item()) if self.param_groups[0].get("capturable", False) else self._t
+
     def load_state_dict(self, state_dict):
+        keep = self._ema_options()
         super().load_state_dict(state_dict)
         a = self.arena
         t = 0
@@ -122,6 +135,7 @@ class FlatAdam(FlatOptimizer):
         self._t = t
         self._step_tensor.fill_(t)
         self._forget_skipped()
+        self._ema_after_load(keep)
 
     def state_dict(self):
         """'step' reports TAKEN steps (attempted - skipped); the live state keeps counting attempts (capturable: on the
@@ -143,6 +157,7 @@ class FlatAdam(FlatOptimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        self._check_live("optimizer.step()")
         a, g = self.arena, self.param_groups[0]
         if not a.intact():
             raise _lib.PoseliftError("FlatAdam: the module's parameters left their arena (.to() / .data reassigned): "

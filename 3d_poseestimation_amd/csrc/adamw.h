@@ -87,6 +87,31 @@ __device__ __forceinline__ AdamWK adamw_consts_clip(const AdamWIn& a, const PLCl
   return k;
 }
 
+// ---- averaged (EMA) weights: e <- e + (p_new - e) (1 - d_n), kept by the launch that holds the new p in registers ----------
+// PLEma (poselift.h) is what the kernels are given.  n = t_taken - t0 is the 1-based count of this EMA update, from the
+// inputs the bias corrections use (t + *t_dev, minus the record's skipped count behind pl_grad_norm_clip), so a captured graph
+// advances it by itself; d_n = decay, or min(decay, (1 + n) / (10 + n)) with warmup; 1 - d_n is formed in double and
+// rounded once.  A skipped step never gets here (e stays bitwise, like p, m, v) and so does not count in n.
+template <class A>
+__device__ __forceinline__ float ema_omd(const A& a, const PLClipRecord* clip, const PLEma& ema) {
+  const int64_t taken = a.t + (a.t_dev ? (int64_t)a.t_dev[0] : 0) - (clip ? (int64_t)clip->skipped : 0);
+  const double n = (double)(taken - ema.t0);
+  double d = (double)ema.decay;
+  if (ema.warmup) d = fmin(d, (1.0 + n) / (10.0 + n));
+  return (float)(1.0 - d);
+}
+
+// the kernel argument of a kernel templated on whether it keeps the average: nothing, or the PLEma
+template <bool EMA>
+struct EmaArg {};
+template <>
+struct EmaArg<true> {
+  PLEma v;
+};
+
+// fp32, exactly two roundings (the difference, the fused multiply-add), on every route
+__device__ __forceinline__ void ema_one(float& e, float p_new, float omd) { e = __fmaf_rn(p_new - e, omd, e); }
+
 __device__ __forceinline__ void adamw_one(float& p, float g, float& m, float& v, const AdamWK& k) {
   g *= k.gscale;
   p *= k.decay;
@@ -97,9 +122,12 @@ __device__ __forceinline__ void adamw_one(float& p, float g, float& m, float& v,
 }
 
 
-// p, m, v (and g read) of elements [4 i0, n) in float4 steps of `stride` threads: the loop of adamw_kernel without the planes
+// p, m, v (and g read) of elements [4 i0, n) in float4 steps of `stride` threads: the loop of adamw_kernel without the planes.
+// EMA: the average e beside them, from the registers that hold the new p (EMA = false is the loop as it was: e, omd unused)
+template <bool EMA = false>
 __device__ __forceinline__ void adamw_span(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                           float* __restrict__ v, int64_t n4, int64_t i0, int64_t stride, const AdamWK& k) {
+                                           float* __restrict__ v, int64_t n4, int64_t i0, int64_t stride, const AdamWK& k,
+                                           float* __restrict__ e = nullptr, float omd = 0.f) {
   for (int64_t i = i0; i < n4; i += stride) {
     float4 pv = *reinterpret_cast<const float4*>(p + 4 * i), mv = *reinterpret_cast<const float4*>(m + 4 * i);
     float4 vv = *reinterpret_cast<const float4*>(v + 4 * i);
@@ -111,6 +139,14 @@ __device__ __forceinline__ void adamw_span(float* __restrict__ p, const float* _
     *reinterpret_cast<float4*>(p + 4 * i) = pv;
     *reinterpret_cast<float4*>(m + 4 * i) = mv;
     *reinterpret_cast<float4*>(v + 4 * i) = vv;
+    if constexpr (EMA) {
+      float4 ev = *reinterpret_cast<const float4*>(e + 4 * i);
+      ema_one(ev.x, pv.x, omd);
+      ema_one(ev.y, pv.y, omd);
+      ema_one(ev.z, pv.z, omd);
+      ema_one(ev.w, pv.w, omd);
+      *reinterpret_cast<float4*>(e + 4 * i) = ev;
+    }
   }
 }
 

@@ -813,6 +813,12 @@ struct BwdCtx {
     r.t = adam->t; r.lr_dev = adam->lr_dev; r.t_dev = adam->t_dev;
     return r;
   }
+  // ... and that slice of the averaged weights (adam->ema set)
+  PLEma ema_at(int64_t lo) const {
+    PLEma e = *adam->ema;
+    e.e += lo;
+    return e;
+  }
 };
 
 // BatchNorm-backward pass 1 of layer l inside the epilogue of the GEMM that produces its incoming gradient
@@ -1014,7 +1020,9 @@ int bwd_layer_linear(BwdCtx& c, int l) {
       // launch before) and everything above them up to where the launch before started -- the weight matrix of layer
       // l + 1 (its gradient, too), or the output layer behind the top hidden layer
       AdamWRide ar = {};
+      PLEma er = {};
       if (c.adam_rides) ar = c.ride(c.P.off[4 * l + 1], l == w.L - 1 ? c.P.total : c.P.off[4 * (l + 1) + 1]);
+      if (c.adam_rides && c.adam->ema) er = c.ema_at(c.P.off[4 * l + 1]);
       SmallLayerBwdArgs a = {};
       a.dz = DZl; a.W = ly.W; a.B = Bi; a.H = H; a.K = H;
       if (l % 2 == 1) { a.addend = GA; a.gout = GA; }
@@ -1023,6 +1031,7 @@ int bwd_layer_linear(BwdCtx& c, int l) {
       if (w1) { a.x1 = c.x; a.dW1 = c.grads + c.P.off[0]; }
       a.K1 = d->in_dim;
       if (c.adam_rides) a.adam = &ar;
+      if (c.adam_rides && c.adam->ema) a.ema = &er;
       PL_TRY(launch_small_layer_bwd(a, s));
       return dw_rides ? PL_OK : launch_gemm_f32(kTN, t, s);
     }
@@ -1102,7 +1111,7 @@ static int bwd_impl(const PLDesc* d, const float* x, const float* dy, int64_t B,
     // (the same fields as ride(); pl_lifter_train_step checked that lr_dev and t_dev go together)
     const AdamWArgs a = {const_cast<float*>(d->params), grads, adam->m, adam->v, n,
                          {adam->lr, adam->beta1, adam->beta2, adam->eps, adam->weight_decay, 1.0f, adam->t, adam->lr_dev,
-                          adam->t_dev}};
+                          adam->t_dev}, adam->ema};
     PL_TRY(launch_adamw(a, c.s));
   }
   return PL_OK;
@@ -1452,6 +1461,7 @@ extern "C" int pl_lifter_train_step_crit(const PLDesc* d, const float* x, const 
                                          float* loss, float* grads, const PLAdamWStep* opt, void* stream) {
   if (!opt || !opt->m || !opt->v || (opt->lr_dev != nullptr) != (opt->t_dev != nullptr) || opt->t < (opt->t_dev ? 0 : 1))
     PL_FAIL(PL_EINVAL, "pl_lifter_train_step: bad optimizer description");
+  if (opt->ema) PL_TRY(check_ema(*opt->ema, "pl_lifter_train_step"));
   if (!d) PL_FAIL(PL_EINVAL, "descriptor is NULL");
   return train_fwd_bwd_impl(d, x, target, B, ws, ws_bytes, seed, step, crit, y, loss, grads, 1 + 2 * d->num_stage, 0, stream, opt);
 }

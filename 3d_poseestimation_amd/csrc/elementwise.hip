@@ -1620,10 +1620,13 @@ __global__ __launch_bounds__(NTHR) void crop_poses_kernel(const float* __restric
 // CLIP: the step behind pl_grad_norm_clip (in.clip set).  A skipped step writes no p, m, v; it still writes the operand
 // planes, from the unchanged parameters -- the host marks them current after every launch (optim.FlatAdamW._launch), and
 // they may have been stale before it (load_state_dict).  CLIP = false is the kernel as it was.
-template <bool CLIP>
+// EMA: the averaged weights e (PLEma, the parameter arena's layout) follow from the registers that hold the new p -- float4
+// beside p, m, v, the scalar tail likewise; a skipped step leaves e alone.  EMA = false takes an empty EmaArg and is the kernel
+// as it was.
+template <bool CLIP, bool EMA>
 __global__ __launch_bounds__(NTHR) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                      float* __restrict__ m, float* __restrict__ v,
-                                                     int64_t n, AdamWIn in, int vec) {
+                                                     int64_t n, AdamWIn in, int vec, EmaArg<EMA> ema) {
   if constexpr (CLIP) {
     if (in.clip->skip) {
       if (!in.nseg) return;
@@ -1646,6 +1649,12 @@ __global__ __launch_bounds__(NTHR) void adamw_kernel(float* __restrict__ p, cons
   const AdamWK k = [&] { if constexpr (CLIP) return adamw_consts_clip(in, in.clip); else return adamw_consts(in); }();
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  float* __restrict__ e = nullptr;
+  float omd = 0.f;
+  if constexpr (EMA) {
+    e = ema.v.e;
+    omd = ema_omd(in, CLIP ? in.clip : nullptr, ema.v);
+  }
   if (vec) {
     const int64_t n4 = n >> 2;
     for (; i < n4; i += stride) {
@@ -1656,6 +1665,14 @@ __global__ __launch_bounds__(NTHR) void adamw_kernel(float* __restrict__ p, cons
       adamw_one(pv.z, gv.z, mv.z, vv.z, k);
       adamw_one(pv.w, gv.w, mv.w, vv.w, k);
       st4(p + 4 * i, pv); st4(m + 4 * i, mv); st4(v + 4 * i, vv);
+      if constexpr (EMA) {
+        float4 ev = ld4(e + 4 * i);
+        ema_one(ev.x, pv.x, omd);
+        ema_one(ev.y, pv.y, omd);
+        ema_one(ev.z, pv.z, omd);
+        ema_one(ev.w, pv.w, omd);
+        st4(e + 4 * i, ev);
+      }
       if (in.nseg) {                      // segment starts and lengths are multiples of 4: a float4 lies inside one
         const int64_t e = 4 * i;
 #pragma unroll 1
@@ -1671,7 +1688,29 @@ __global__ __launch_bounds__(NTHR) void adamw_kernel(float* __restrict__ p, cons
     }
     i = (n4 << 2) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   }
-  for (; i < n; i += stride) adamw_one(p[i], g[i], m[i], v[i], k);
+  for (; i < n; i += stride) {
+    adamw_one(p[i], g[i], m[i], v[i], k);
+    if constexpr (EMA) ema_one(e[i], p[i], omd);
+  }
+}
+
+// a <-> b over n floats, in place: float4 body, scalar tail (optim.FlatOptimizer.averaged_weights: parameters <-> their average)
+__global__ __launch_bounds__(NTHR) void swap_f32_kernel(float* __restrict__ a, float* __restrict__ b, int64_t n, int vec) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (vec) {
+    const int64_t n4 = n >> 2;
+    for (; i < n4; i += stride) {
+      const float4 av = ld4(a + 4 * i), bv = ld4(b + 4 * i);
+      st4(a + 4 * i, bv); st4(b + 4 * i, av);
+    }
+    i = (n4 << 2) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  }
+  for (; i < n; i += stride) {
+    const float t = a[i];
+    a[i] = b[i];
+    b[i] = t;
+  }
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -2113,18 +2152,32 @@ extern "C" int pl_mpjpe_accum_t(const float* pred, const float* tgt, int64_t B, 
 // (same-box sweep, B = 64 step: 256 / 512 / 1024 / 2048 blocks -> 0.1297 / 0.1289 / 0.1295 / 0.1304 ms; B = 4096: no difference)
 constexpr int kAdamBlocks = 512;
 
+// PLEma as every entry that takes one checks it, before anything is launched
+int pl::check_ema(const PLEma& ema, const char* who) {
+  if (!ema.e || !aligned16(ema.e)) PL_FAIL(PL_EINVAL, "%s: ema: e is null or not 16-byte aligned", who);
+  if (!(ema.decay >= 0.f && ema.decay < 1.f)) PL_FAIL(PL_EINVAL, "%s: ema: decay=%g is outside [0, 1)", who, (double)ema.decay);
+  if (ema.t0 < 0) PL_FAIL(PL_EINVAL, "%s: ema: t0=%lld < 0", who, (long long)ema.t0);
+  return PL_OK;
+}
+
 int pl::launch_adamw(const AdamWArgs& a, hipStream_t s) {
   const AdamWIn& in = a.in;
   if (!a.p || !a.g || !a.m || !a.v) PL_FAIL(PL_EINVAL, "pl_adamw_flat: null pointer");
   if (a.n <= 0 || in.t < (in.t_dev ? 0 : 1)) PL_FAIL(PL_ESHAPE, "pl_adamw_flat: n=%lld t=%lld", (long long)a.n, (long long)in.t);
   if (reinterpret_cast<uintptr_t>(in.clip) & 7) PL_FAIL(PL_EINVAL, "pl_adamw_flat: clip record must be 8-byte aligned");
+  if (a.ema) PL_TRY(check_ema(*a.ema, "pl_adamw_flat"));
   const int vec = aligned16(a.p) && aligned16(a.g) && aligned16(a.m) && aligned16(a.v);
   int64_t work = vec ? (a.n >> 2) : a.n;
   int blocks = (int)((work + NTHR - 1) / NTHR);
   if (blocks > kAdamBlocks) blocks = kAdamBlocks;
   if (blocks < 1) blocks = 1;
-  if (in.clip) hipLaunchKernelGGL(adamw_kernel<true>, dim3(blocks), dim3(NTHR), 0, s, a.p, a.g, a.m, a.v, a.n, in, vec);
-  else hipLaunchKernelGGL(adamw_kernel<false>, dim3(blocks), dim3(NTHR), 0, s, a.p, a.g, a.m, a.v, a.n, in, vec);
+  const EmaArg<false> off = {};
+  const EmaArg<true> on = {a.ema ? *a.ema : PLEma{}};
+  const dim3 grid(blocks), block(NTHR);
+  if (a.ema && in.clip) hipLaunchKernelGGL((adamw_kernel<true, true>), grid, block, 0, s, a.p, a.g, a.m, a.v, a.n, in, vec, on);
+  else if (a.ema) hipLaunchKernelGGL((adamw_kernel<false, true>), grid, block, 0, s, a.p, a.g, a.m, a.v, a.n, in, vec, on);
+  else if (in.clip) hipLaunchKernelGGL((adamw_kernel<true, false>), grid, block, 0, s, a.p, a.g, a.m, a.v, a.n, in, vec, off);
+  else hipLaunchKernelGGL((adamw_kernel<false, false>), grid, block, 0, s, a.p, a.g, a.m, a.v, a.n, in, vec, off);
   PL_CHECK_LAUNCH("adamw");
   return PL_OK;
 }
@@ -2191,6 +2244,39 @@ extern "C" int pl_adamw_flat_planes_clip(float* p, const float* g, float* m, flo
   a.in.clip = clip;
   PL_TRY(adamw_planes(planes, a));
   return launch_adamw(a, (hipStream_t)stream);
+}
+
+extern "C" int pl_adamw_flat_planes_clip_ema(float* p, const float* g, float* m, float* v, int64_t n, float lr,
+                                             const float* lr_dev, float beta1, float beta2, float eps, float weight_decay,
+                                             int64_t t, const uint64_t* t_dev, float grad_scale, const PLAdamWPlanes* planes,
+                                             const PLClipRecord* clip, const PLEma* ema, void* stream) {
+  if (!ema)
+    return pl_adamw_flat_planes_clip(p, g, m, v, n, lr, lr_dev, beta1, beta2, eps, weight_decay, t, t_dev, grad_scale, planes, clip,
+                                     stream);
+  if ((lr_dev != nullptr) != (t_dev != nullptr)) PL_FAIL(PL_EINVAL, "pl_adamw_flat_planes: lr_dev and t_dev go together");
+  PL_TRY(check_ema(*ema, "pl_adamw_flat_planes_clip_ema"));
+  if (n < 0) PL_FAIL(PL_EINVAL, "pl_adamw_flat_planes_clip_ema: n=%lld", (long long)n);
+  AdamWArgs a = {p, g, m, v, n, {lr, beta1, beta2, eps, weight_decay, grad_scale, t, lr_dev, t_dev}};
+  a.in.clip = clip;
+  a.ema = ema;
+  PL_TRY(adamw_planes(planes, a));
+  return launch_adamw(a, (hipStream_t)stream);
+}
+
+extern "C" int pl_swap_f32(float* a, float* b, int64_t n, void* stream) {
+  if (!a || !b || a == b) PL_FAIL(PL_EINVAL, "pl_swap_f32: null or aliased pointers");
+  if ((reinterpret_cast<uintptr_t>(a) & 3) || (reinterpret_cast<uintptr_t>(b) & 3))
+    PL_FAIL(PL_EINVAL, "pl_swap_f32: pointers must be 4-byte aligned");
+  if (n < 0) PL_FAIL(PL_EINVAL, "pl_swap_f32: n=%lld", (long long)n);
+  if ((a < b ? b - a : a - b) < n) PL_FAIL(PL_EINVAL, "pl_swap_f32: the two ranges overlap");
+  if (n == 0) return PL_OK;
+  const int vec = aligned16(a) && aligned16(b);
+  const int64_t work = vec ? (n >> 2) + (n & 3) : n;
+  int blocks = (int)std::min<int64_t>(kAdamBlocks, (work + NTHR - 1) / NTHR);
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(swap_f32_kernel, dim3(blocks), dim3(NTHR), 0, (hipStream_t)stream, a, b, n, vec);
+  PL_CHECK_LAUNCH("swap_f32");
+  return PL_OK;
 }
 
 extern "C" int pl_adamw_flat_planes(float* p, const float* g, float* m, float* v, int64_t n, float lr, const float* lr_dev,

@@ -401,6 +401,7 @@ struct SmallLayerBwdArgs {
   float* dW1;
   int K1;
   const struct AdamWRide* adam; // optional: a slice of the AdamW step on spare workgroups (adamw.h)
+  const PLEma* ema;             // optional, with adam: that slice's averaged weights (e: the slice's, beside adam->p)
 };
 int launch_small_layer_bwd(const SmallLayerBwdArgs& a, hipStream_t s);
 // the whole top of the backward pass: g = dy W2 -> gout, the BatchNorm backward of the last hidden layer -> dz_top, dW2, db2
@@ -478,8 +479,10 @@ struct AdamWArgs {
   float* v;
   int64_t n;
   AdamWIn in;
+  const PLEma* ema;             // optional: the averaged weights follow in the same launch (e: beside p, for the same [n])
 };
 int launch_adamw(const AdamWArgs& a, hipStream_t s);
+int check_ema(const PLEma& ema, const char* who);
 
 // ---------------------------------------------------------------------------------
 // skinny layers (skinny.hip): 34 -> H and H -> 51, MFMA straight from registers

@@ -729,15 +729,22 @@ __device__ __forceinline__ void first_wgrad(float4 d, const float* __restrict__ 
   }
 }
 
-template <int STEPS>
-__global__ __launch_bounds__(NTHR) void small_bwd_kernel(BwdArgs p) {
+// EMA: the AdamW slice's workgroups keep the averaged weights too (PLEma, adamw.h); EMA = false takes an empty EmaArg and is
+// the kernel as it was.
+template <int STEPS, bool EMA>
+__global__ __launch_bounds__(NTHR) void small_bwd_kernel(BwdArgs p, EmaArg<EMA> ema) {
   __shared__ float part[NWAVE * ROWS * COLS];
   __shared__ float stage[NWAVE * STAGE];
   __shared__ float4 sm[12][4];
   if ((int)blockIdx.x >= p.nblk_dx + p.nblk_dw) {       // (workgroup-uniform)
     const AdamWK k = adamw_consts(p.adam);
-    adamw_span(p.adam.p, p.adam.g, p.adam.m, p.adam.v, p.adam.n >> 2,
-               (int64_t)(blockIdx.x - p.nblk_dx - p.nblk_dw) * NTHR + threadIdx.x, (int64_t)p.nblk_adam * NTHR, k);
+    if constexpr (EMA)
+      adamw_span<true>(p.adam.p, p.adam.g, p.adam.m, p.adam.v, p.adam.n >> 2,
+                       (int64_t)(blockIdx.x - p.nblk_dx - p.nblk_dw) * NTHR + threadIdx.x, (int64_t)p.nblk_adam * NTHR, k,
+                       ema.v.e, ema_omd(p.adam, nullptr, ema.v));
+    else
+      adamw_span(p.adam.p, p.adam.g, p.adam.m, p.adam.v, p.adam.n >> 2,
+                 (int64_t)(blockIdx.x - p.nblk_dx - p.nblk_dw) * NTHR + threadIdx.x, (int64_t)p.nblk_adam * NTHR, k);
     return;
   }
   if ((int)blockIdx.x >= p.nblk_dx) {
@@ -1129,12 +1136,22 @@ int launch_small_layer_bwd(const SmallLayerBwdArgs& a, hipStream_t s) {
     p.nblk_adam = (int)std::min<int64_t>(kSmallAdamBlocks, (r.n / 4 + NTHR - 1) / NTHR);
     extra += p.nblk_adam;
   }
+  const bool ema = a.ema && p.nblk_adam > 0;           // (no slice: nothing to average in this launch)
+  if (ema) PL_TRY(check_ema(*a.ema, "small_layer_bwd"));
   const dim3 grid(H / COLS + extra), block(NTHR);
   void* prof = prof_begin_flops(2.0 * B * H * K * (a.dW ? 2 : 1), s);
-  switch (K / (NWAVE * 32)) {
-    case 1: hipLaunchKernelGGL(small_bwd_kernel<1>, grid, block, 0, s, p); break;
-    case 2: hipLaunchKernelGGL(small_bwd_kernel<2>, grid, block, 0, s, p); break;
-    default: hipLaunchKernelGGL(small_bwd_kernel<4>, grid, block, 0, s, p); break;
+  const EmaArg<false> off = {};
+  const EmaArg<true> on = {ema ? *a.ema : PLEma{}};
+  if (ema) {
+    switch (K / (NWAVE * 32)) {
+      case 1: hipLaunchKernelGGL((small_bwd_kernel<1, true>), grid, block, 0, s, p, on); break;
+      case 2: hipLaunchKernelGGL((small_bwd_kernel<2, true>), grid, block, 0, s, p, on); break;
+      default: hipLaunchKernelGGL((small_bwd_kernel<4, true>), grid, block, 0, s, p, on); break;
+    }
+  } else switch (K / (NWAVE * 32)) {
+    case 1: hipLaunchKernelGGL((small_bwd_kernel<1, false>), grid, block, 0, s, p, off); break;
+    case 2: hipLaunchKernelGGL((small_bwd_kernel<2, false>), grid, block, 0, s, p, off); break;
+    default: hipLaunchKernelGGL((small_bwd_kernel<4, false>), grid, block, 0, s, p, off); break;
   }
   prof_end(prof, s);
   PL_CHECK_LAUNCH("small_layer_bwd");

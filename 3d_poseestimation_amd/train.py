@@ -216,6 +216,8 @@ def train_step(model, optimizer, y1, y2, grad_sync=None, criterion=None):
     train_1.py:36-37; smooth-L1, MPJPE, per-joint weights).  LinearModel + FlatAdamW keep the fused step -- the same
     launches, AdamW riding at B <= 64, the data-parallel ranges; every other model runs criterion(y2_hat, y2) under autograd."""
     y1, y2 = y1.float(), y2.float()
+    if getattr(optimizer, "_swapped", False):
+        optimizer._check_live("train_step")
     if _fusable(model, optimizer, y1, y2, criterion):
         # the whole step is three library calls: fwd+loss+bwd, [all-reduce], AdamW.  Same kernels,
         # same results as the autograd route below; `zero_grad` is implicit (gradients are overwritten)
@@ -293,6 +295,9 @@ class GraphedTrainStep:
             # max_grad_norm / skip_nonfinite: the captured sequence is fwd+bwd, the norm pass, one AdamW launch; max_norm is
             # read from a device scalar the optimizer refreshes like the learning rate here, the skipped count from its record
             self._clip_mode = optimizer._replay_refresh()
+            # the averaged weights: whether the step keeps them, ema_decay / ema_warmup, the update count's base and the
+            # arena's address are all baked into the captured launches (the update count itself advances on the device)
+            self._ema_sig = optimizer._ema_signature()
             torch.cuda.synchronize(dev)
             self.graph = torch.cuda.CUDAGraph()
             adamw = (optimizer._step_struct(0.0, lr_dev, t0, self._tick)
@@ -322,10 +327,16 @@ class GraphedTrainStep:
     def _baked_ptrs(self):
         w = self.criterion.joint_weights if self.criterion is not None else None
         return (self.model.flat_params.data_ptr(), self.opt._m.data_ptr() if self.opt._m is not None else 0,
-                self.opt._v.data_ptr() if self.opt._v is not None else 0, w.data_ptr() if w is not None else 0)
+                self.opt._v.data_ptr() if self.opt._v is not None else 0, w.data_ptr() if w is not None else 0,
+                self.opt._e.data_ptr() if self.opt._e is not None else 0)
 
     def __call__(self, y1, y2):
+        self.opt._check_live("a GraphedTrainStep replay")
         self._lr_dev.refresh(self.opt.param_groups[0]["lr"])                     # ReduceLROnPlateau et al. (train_1.py:106)
+        if self.opt._ema_signature() != self._ema_sig:
+            raise _lib.PoseliftError("GraphedTrainStep: ema_decay / ema_warmup were switched on, off or changed after capture, or "
+                                     "the averaged weights were re-loaded (their constants and address are baked into the "
+                                     "captured launches): capture a new one")
         if self.opt._replay_refresh() != self._clip_mode:
             raise _lib.PoseliftError("GraphedTrainStep: max_grad_norm / skip_nonfinite were switched on or off after capture "
                                      "(their value may change, not whether the step has a norm pass): capture a new one")
@@ -393,6 +404,13 @@ class GraphedModuleStep:
         self._state = list(model.parameters()) + list(model.buffers())      # what a replay writes behind autograd's back
         self._in = tuple(t.detach().clone() for t in inputs)
         self._target = target.detach().clone()
+        # arena.FlatAdam with ema_decay: the averaged weights exist before the warm-up steps (which the restore below then
+        # undoes like the moments); what the captured launches bake in about them is checked at every replay
+        self._ema_sig = None
+        if hasattr(optimizer, "_ema_signature"):
+            optimizer._check_live("GraphedModuleStep")
+            optimizer._ema_bind()
+            self._ema_sig = optimizer._ema_signature()
         with _lib.on_device(dev):
             torch.cuda.synchronize(dev)
             state = [t for t in model.state_dict().values()]
@@ -429,6 +447,11 @@ class GraphedModuleStep:
 
     def __call__(self, inputs, target):
         inputs = tuple(inputs) if isinstance(inputs, (tuple, list)) else (inputs,)
+        if hasattr(self.opt, "_ema_signature"):
+            self.opt._check_live("a GraphedModuleStep replay")
+            if self.opt._ema_signature() != self._ema_sig:
+                raise _lib.PoseliftError("GraphedModuleStep: ema_decay / ema_warmup were switched on, off or changed after "
+                                         "capture, or the averaged weights were re-loaded: capture a new one")
         for dst, src in zip(self._in, inputs):
             dst.copy_(src)
         self._target.copy_(target)
@@ -463,7 +486,7 @@ def predict_flip_tta(model, y1, out_dims=3):
 
 
 @torch.no_grad()
-def eval_step(model, y1, y2, metric_out=None, flip=False, meter=None, group_ids=None, denorm=None, criterion=None):
+def eval_step(model, y1, y2, metric_out=None, flip=False, meter=None, group_ids=None, denorm=None, criterion=None, ema=None):
     """train_1.py:112-145 body (model must be in eval mode): forward, MSE, loss_MPJPE.
     criterion: a criterion.PoseCriterion -- `loss` is then that criterion's value, not the MSE.
     flip=True: flip test-time augmentation (predict_flip_tta).
@@ -471,7 +494,13 @@ def eval_step(model, y1, y2, metric_out=None, flip=False, meter=None, group_ids=
     each pose); like everything here it only enqueues work.
     denorm: the pose_table.PoseTransform of the 3-D targets (y2 and the model's output are in its space).  The MSE stays
     in the model's space, as the reference's loss does; `metric` and the meter are in the raw units, both tensors inverted
-    inside the launches that read them (no launch more than without).  y2_hat is returned as the model gave it."""
+    inside the launches that read them (no launch more than without).  y2_hat is returned as the model gave it.
+    ema: the model's flat optimizer built with ema_decay -- the step runs on the averaged weights, i.e. inside
+    `with ema.averaged_weights():` (BatchNorm running statistics stay the live ones)."""
+    if ema is not None:
+        with ema.averaged_weights():
+            return eval_step(model, y1, y2, metric_out=metric_out, flip=flip, meter=meter, group_ids=group_ids, denorm=denorm,
+                             criterion=criterion)
     if flip and denorm is not None:
         raise ValueError("eval_step: flip=True mirrors image-normalised poses and cannot run on transformed ones; compose it: "
                          "a = model(T2.apply(raw2d)), b = model(T2.apply(flip_pose(raw2d))), then "

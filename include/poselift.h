@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define PL_VERSION 119 /* 0.1.19: + pl_lifter_bwd_slab_rides (how many split-K sums of weight gradients ride in chained GEMM launches); 0.1.18: + PLPoseCrop, pl_pose_augment_gather_crop, pl_pose_augment_gather_crop_t, pl_pose_augment_host_crop, pl_pose_augment_host_crop_t, pl_frame_warp_gather_crop, pl_frame_warp_host_crop, pl_pose_crop_boxes, pl_pose_crop_boxes_host, pl_crop_poses, pl_crop_poses_host (person-centred crop from each row's 2-D pose inside the two batch launches); 0.1.17: + PLCriterion, pl_pose_loss_scratch_bytes, pl_pose_loss_fwd_bwd, pl_lifter_train_fwd_bwd_crit, pl_lifter_train_step_crit (the train step's criterion: mse, l1, smooth_l1, mpjpe, weighted per joint); 0.1.16: + pl_pose_prepare, pl_pose_stats, pl_pose_affine and their _host forms, pl_pose_stats_scratch_bytes, pl_pose_stats_chunk_rows, pl_pose_augment_gather_t, pl_pose_augment_host_t, pl_pose_errors_t, pl_mpjpe_accum_t (pose tables: prepare, statistics, the per-column transform and its way back inside the batch, error and metric launches); 0.1.15: + PLFrameWarp, pl_frame_warp_gather, pl_frame_warp_host (frame gather + resize + the pose augmentation's warp in one launch); 0.1.14: + PLPoseAug, pl_pose_augment_gather, pl_pose_augment_host (seeded train-time pose augmentation inside the batch gather); 0.1.13: + PLClipRecord, pl_grad_norm_scratch_bytes, pl_grad_norm_clip, pl_adamw_flat_clip, pl_adamw_flat_dev_clip, pl_adamw_flat_planes_clip (gradient-norm clipping and non-finite skip on the device); 0.1.12: + pl_pose_errors, pl_pose_errors_host, pl_pose_metrics_scratch_bytes, pl_pose_metrics_accum (evaluation: MPJPE / N-MPJPE / P-MPJPE, PCK counts, per group); 0.1.11: + pl_vit_*_bf16, pl_vit_bf16_pack (MyViT "bf16p": bf16 operand carriers written by their producers); 0.1.10: + pl_vit_* (the MyViT transformer lifter); 0.1.9: + pl_conv2d_planes_fwd_hw, pl_conv2d_planes_wgrad_hw (the stem on the planes GEMM); 0.1.8: + pl_lifter_train_step, pl_lifter_step_carries_adamw; 0.1.7: + pl_workspace_bitmap_format (small-batch layer kernels); 0.1.6: + pl_counter_add; 0.1.5: + pl_flip_pose_ex, pl_flip_w_nhwc (phase5 Flip branch); 0.1.4: + pl_planes_split_strided; 0.1.3: + pl_bn_join_bwd (0.1.2: operand-plane outputs of the BatchNorm / join kernels, pl_gemm_planes_raw) */
+#define PL_VERSION 120 /* 0.1.20: + PLEma, PLAdamWStep.ema, pl_adamw_flat_planes_clip_ema, pl_swap_f32 (averaged weights kept inside the AdamW launches); 0.1.19: + pl_lifter_bwd_slab_rides (how many split-K sums of weight gradients ride in chained GEMM launches); 0.1.18: + PLPoseCrop, pl_pose_augment_gather_crop, pl_pose_augment_gather_crop_t, pl_pose_augment_host_crop, pl_pose_augment_host_crop_t, pl_frame_warp_gather_crop, pl_frame_warp_host_crop, pl_pose_crop_boxes, pl_pose_crop_boxes_host, pl_crop_poses, pl_crop_poses_host (person-centred crop from each row's 2-D pose inside the two batch launches); 0.1.17: + PLCriterion, pl_pose_loss_scratch_bytes, pl_pose_loss_fwd_bwd, pl_lifter_train_fwd_bwd_crit, pl_lifter_train_step_crit (the train step's criterion: mse, l1, smooth_l1, mpjpe, weighted per joint); 0.1.16: + pl_pose_prepare, pl_pose_stats, pl_pose_affine and their _host forms, pl_pose_stats_scratch_bytes, pl_pose_stats_chunk_rows, pl_pose_augment_gather_t, pl_pose_augment_host_t, pl_pose_errors_t, pl_mpjpe_accum_t (pose tables: prepare, statistics, the per-column transform and its way back inside the batch, error and metric launches); 0.1.15: + PLFrameWarp, pl_frame_warp_gather, pl_frame_warp_host (frame gather + resize + the pose augmentation's warp in one launch); 0.1.14: + PLPoseAug, pl_pose_augment_gather, pl_pose_augment_host (seeded train-time pose augmentation inside the batch gather); 0.1.13: + PLClipRecord, pl_grad_norm_scratch_bytes, pl_grad_norm_clip, pl_adamw_flat_clip, pl_adamw_flat_dev_clip, pl_adamw_flat_planes_clip (gradient-norm clipping and non-finite skip on the device); 0.1.12: + pl_pose_errors, pl_pose_errors_host, pl_pose_metrics_scratch_bytes, pl_pose_metrics_accum (evaluation: MPJPE / N-MPJPE / P-MPJPE, PCK counts, per group); 0.1.11: + pl_vit_*_bf16, pl_vit_bf16_pack (MyViT "bf16p": bf16 operand carriers written by their producers); 0.1.10: + pl_vit_* (the MyViT transformer lifter); 0.1.9: + pl_conv2d_planes_fwd_hw, pl_conv2d_planes_wgrad_hw (the stem on the planes GEMM); 0.1.8: + pl_lifter_train_step, pl_lifter_step_carries_adamw; 0.1.7: + pl_workspace_bitmap_format (small-batch layer kernels); 0.1.6: + pl_counter_add; 0.1.5: + pl_flip_pose_ex, pl_flip_w_nhwc (phase5 Flip branch); 0.1.4: + pl_planes_split_strided; 0.1.3: + pl_bn_join_bwd (0.1.2: operand-plane outputs of the BatchNorm / join kernels, pl_gemm_planes_raw) */
 
 typedef enum PLStatus {
   PL_OK = 0,
@@ -201,6 +201,23 @@ int pl_lifter_train_fwd_bwd(const PLDesc* d, const float* x, const float* target
  * one small launch updates the bottom of the arena (first layer, first residual Linear).  Otherwise: one pl_adamw_flat(_dev)
  * launch behind the backward pass.  Same element arithmetic as pl_adamw_flat either way.  The caller's persistent weight
  * planes (PLDesc.wplanes) are stale afterwards. */
+/* Averaged (EMA) weights kept by the launch that updates the parameters: e has the parameter arena's layout and alignment
+ * (16 bytes), and for every element the step updates, from the registers that hold the new parameter p_new,
+ *     e = fmaf(p_new - e, omd, e)                  fp32, two roundings (the difference, the fused multiply-add)
+ *     omd = (float)(1.0 - d_n), formed on the device in double: d_n = decay (warmup == 0), else min(decay, (1 + n) / (10 + n))
+ *     n = t_taken - t0, the 1-based count of this update: t_taken = t + *t_dev - clip->skipped, the step number the bias
+ *         corrections use; t0 = the taken-step count when the average was started (or loaded)
+ * A step skipped by its clip record leaves e bitwise untouched, like p, m, v, and so does not count in n.
+ * decay in [0, 1), e != NULL and 16-byte aligned, t0 >= 0: anything else is PL_EINVAL. */
+typedef struct PLEma {
+  float* e;
+  float decay;
+  int32_t warmup;
+  int64_t t0;
+} PLEma;
+/* a <-> b over n floats in place (float4 where both are 16-byte aligned, scalar tail); the ranges must not overlap.
+ * Evaluating with the averaged weights is this call over the parameter and EMA arenas, and once more to return. */
+int pl_swap_f32(float* a, float* b, int64_t n, void* stream);
 typedef struct PLAdamWStep {
   float* m;
   float* v;
@@ -209,6 +226,7 @@ typedef struct PLAdamWStep {
   float beta1, beta2, eps, weight_decay;
   int64_t t;
   const uint64_t* t_dev;
+  const PLEma* ema; /* NULL, or the averaged weights of the whole arena: they follow inside the same launches (0.1.20) */
 } PLAdamWStep;
 int pl_lifter_step_carries_adamw(const PLDesc* d, int64_t B);
 /* How many split-K sums of hidden layers' weight gradients a backward over layers hi .. lo (as in pl_lifter_bwd_layers) of B
@@ -777,6 +795,13 @@ int pl_adamw_flat_dev_clip(float* p, const float* g, float* m, float* v, int64_t
 int pl_adamw_flat_planes_clip(float* p, const float* g, float* m, float* v, int64_t n, float lr, const float* lr_dev,
                               float beta1, float beta2, float eps, float weight_decay, int64_t t, const uint64_t* t_dev,
                               float grad_scale, const PLAdamWPlanes* planes, const PLClipRecord* clip, void* stream);
+
+/* pl_adamw_flat_planes_clip with the averaged weights of [p, p + n) kept in the same launch (ema->e: beside p).  ema == NULL:
+ * exactly pl_adamw_flat_planes_clip -- the kernels it always launched, the bits it always wrote. */
+int pl_adamw_flat_planes_clip_ema(float* p, const float* g, float* m, float* v, int64_t n, float lr, const float* lr_dev,
+                                  float beta1, float beta2, float eps, float weight_decay, int64_t t, const uint64_t* t_dev,
+                                  float grad_scale, const PLAdamWPlanes* planes, const PLClipRecord* clip, const PLEma* ema,
+                                  void* stream);
 
 /* Layout of the caller-owned weight-plane buffer PLDesc.wplanes: pl_wplanes_bytes() bytes (0: this descriptor has no
  * planes path); the planes of hidden layer l (1 <= l < n_hidden) start at byte (l - 1) * pl_wplanes_layer_bytes(d):
