@@ -317,6 +317,15 @@ def conv2d_bias_nhwc_autograd(x, w_ohwi, bias, stride=1, padding=0, arith="bf16x
     return _Conv2dFn.apply(x, w_ohwi, bias, stride, padding, arith)
 
 
+def _bn_replicas(rows, C):
+    """csrc/elementwise.hip bn_replicas: the BatchNorm kernels work on a narrow map [rows][C] -- and lay out its ReLU bitmap --
+    as [rows / R][R C]."""
+    r = 4 if C <= 64 else (2 if C <= 128 else 1)
+    while r > 1 and (rows % r != 0 or rows // r < 2):
+        r >>= 1
+    return r
+
+
 def _bn_fwd(ctx, z, identity, gamma, beta, running_mean, running_var, batches, eps, momentum, *, relu, f32, planes, link, mode):
     """Training-mode BatchNorm of z [..., C] over every leading dimension (+ identity, when given) (+ ReLU): the output as
     fp32 (f32), as a carrier of its operand planes in `mode` (planes), or both -- returns (y, yp), [rows][C] or None.  With
@@ -378,7 +387,10 @@ def _bn_bwd(ctx, g2, need, gp2=None, join=False):
                 return
             dy = g2
             if join:
-                rc = L.pl_mask_add_by_bits(g2.data_ptr(), gp, bits.data_ptr(), rows, C, dx.data_ptr(), _lib.current_stream_ptr())
+                # (the bitmap is the forward's, in ITS view of a narrow map: the masked sum is elementwise, so it takes that view)
+                R = _bn_replicas(rows, C)
+                rc = L.pl_mask_add_by_bits(g2.data_ptr(), gp, bits.data_ptr(), rows // R, C * R, dx.data_ptr(),
+                                           _lib.current_stream_ptr())
                 _lib.check(rc, "pl_mask_add_by_bits")
                 dy = dx     # (dy = dx where the join's bitmap is set: masking the masked sum again changes nothing)
             rc = L.pl_bn_train_bwd_ex(dy.data_ptr(), bits.data_ptr(), z2.data_ptr(), mean.data_ptr(), rstd.data_ptr(),

@@ -122,7 +122,18 @@ int64_t pl_param_tensors(const PLDesc* d);            /* 4*n_hidden + 2         
 int64_t pl_param_offset(const PLDesc* d, int64_t i);  /* floats, multiple of 64     */
 int64_t pl_param_numel(const PLDesc* d, int64_t i);
 int64_t pl_param_arena_floats(const PLDesc* d);       /* padded arena length        */
-/* Workspace for B rows: saved activations, masks, BN statistics, gradient scratch. */
+/* Workspace for B rows: saved activations, masks, BN statistics, gradient scratch.
+ *
+ * UNINITIALISED MEMORY.  The workspace, every `scratch` argument of this header and every output buffer may hold
+ * anything on entry, non-finite bit patterns included: the library reads no word of them that an earlier launch of
+ * the same call sequence (a forward before its backward, a backward before the optimizer step that takes its slabs)
+ * did not write, and it uses no memset.  A result never depends on what these buffers held.  And the library never
+ * writes outside the bytes it asked for: pl_workspace_bytes / pl_*_scratch_bytes bytes from the pointer it was given,
+ * an output's own extent.  The one exception is the f16x3 range-guard record (PL_RANGE_SITES words, below), an
+ * accumulator "zeroed by the caller"; state that calls accumulate into -- PLClipRecord's skipped count, the metric
+ * sums and counts, an `out` a loss adds to, AdamW's moments -- is the caller's to initialise and is not scratch.
+ * tests/test_gpu_scratch_independence.py holds both halves, bit for bit, for every kernel of csrc/: each __global__
+ * function is launched by one of its cases or listed there as exempt, with the reason. */
 size_t pl_workspace_bytes(const PLDesc* d, int64_t B);
 /* Debug/test view into the workspace.  which: 0 z (pre-BN GEMM output), 1 act (layer
  * output incl. residual), 2 keep&relu bitmap, 3 batch mean, 4 batch rstd.           */
@@ -268,7 +279,9 @@ typedef struct PLCriterion {
   const float* weights; /* device, O / group floats, or NULL */
 } PLCriterion;
 /* The criterion alone: loss (1 device float) and, dpred != NULL, its gradient [B][O], in one launch pair.  Any J.
- * scratch >= pl_pose_loss_scratch_bytes(B, O, crit).  pl_mse_fwd_bwd is the crit == NULL case of the same implementation. */
+ * scratch >= pl_pose_loss_scratch_bytes(B, O, crit).  pl_mse_fwd_bwd is the crit == NULL case of the same implementation.
+ * (Here and for every *_scratch_bytes below: scratch may hold anything on entry, NaN bit patterns included, and nothing
+ * is written outside the bytes the query answered -- UNINITIALISED MEMORY at pl_workspace_bytes.) */
 size_t pl_pose_loss_scratch_bytes(int64_t B, int64_t O, const PLCriterion* crit);
 int pl_pose_loss_fwd_bwd(const float* pred, const float* tgt, int64_t B, int64_t O, const PLCriterion* crit, float grad_scale,
                          float* dpred /* may be NULL */, float* loss, void* scratch, void* stream);

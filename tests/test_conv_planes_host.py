@@ -151,3 +151,26 @@ def test_split_k_tail_of_gemm_and_weight_gradient(pkg):
                             (dict(stride=0), ESHAPE, b"geometry"), (dict(H=1, W=1, k=5, pad=0), ESHAPE, b"geometry")):
         for rc, msg in wgrad(**bad):
             assert rc == code and word in msg, (bad, rc, msg)
+
+
+def test_bn_replicas_of_conv_py_is_the_rule_of_the_batchnorm_kernels(pkg):
+    """conv._bn_replicas is a copy of csrc/elementwise.hip bn_replicas (the view [rows / R][R C] the BatchNorm kernels take of a
+    narrow map, and lay its ReLU bitmap out in): the join's masked sum reads the bitmap in that view.  The C rule is static,
+    so the copy is tied to it twice: the function's text is the text the copy was made from -- whoever changes the rule
+    changes both -- and pl_bn_join_bwd, which refuses exactly the maps with R != 1, refuses every map the copy folds."""
+    import os
+    import re
+    import __graft_entry__ as ge
+    with open(os.path.join(ge.CSRC, "elementwise.hip")) as f:
+        m = re.search(r"static int bn_replicas\(int64_t rows, int64_t C\) \{(.*?)\n\}", f.read(), re.S)
+    assert m and " ".join(m.group(1).split()) == ("int r = C <= 64 ? 4 : (C <= 128 ? 2 : 1); "
+                                                  "while (r > 1 && (rows % r != 0 || rows / r < 2)) r >>= 1; return r;")
+    R = pkg.conv._bn_replicas
+    want = {(120, 64): 4, (122, 64): 2, (65, 64): 1, (65, 24): 1, (4, 64): 2, (6, 32): 2, (2, 64): 1, (3, 8): 1, (8, 64): 4,
+            (66, 128): 2, (67, 128): 1, (2, 128): 1, (4, 128): 2, (120, 132): 1, (65, 256): 1, (4096, 2048): 1, (33792, 64): 4}
+    assert {k: R(*k) for k in want} == want
+    L = pkg.lib()
+    for (rows, C), r in want.items():
+        if r != 1:                                 # (R == 1 would pass validation and launch on these pointers: never called)
+            rc, msg = _call(L, "pl_bn_join_bwd", one, one, one, one, one, one, one, rows, C, one, one, one, one, one, None, 0, None)
+            assert rc == ESHAPE and b"narrower than one 256-column strip" in msg, (rows, C, msg)
