@@ -318,7 +318,7 @@ def conv2d_bias_nhwc_autograd(x, w_ohwi, bias, stride=1, padding=0, arith="bf16x
 
 
 def _bn_replicas(rows, C):
-    """csrc/elementwise.hip bn_replicas: the BatchNorm kernels work on a narrow map [rows][C] -- and lay out its ReLU bitmap --
+    """csrc/batchnorm.hip bn_replicas: the BatchNorm kernels work on a narrow map [rows][C] -- and lay out its ReLU bitmap --
     as [rows / R][R C]."""
     r = 4 if C <= 64 else (2 if C <= 128 else 1)
     while r > 1 and (rows % r != 0 or rows // r < 2):

@@ -1,4 +1,4 @@
-// The flat AdamW step's device pieces, shared by the optimizer kernel (elementwise.hip) and the small-batch backward launches
+// The flat AdamW step's device pieces, shared by the optimizer kernel (optim.hip) and the small-batch backward launches
 // that carry a slice of the step (small_layer.hip): torch.optim.AdamW's single-tensor update order
 // (phase1_lifting/train_1.py:39 optimizer, :89 step).
 #pragma once

@@ -1,6 +1,6 @@
 // C ABI of libposelift.so: arena layout, workspace plan and the forward / backward
 // launch sequences of the lifter (include/poselift.h).  Host code only; every kernel
-// lives in gemm_f32.hip / elementwise.hip.
+// lives in the kernel files (gemm_*.hip, batchnorm.hip, reduce.hip, criterion.hip, optim.hip, ...).
 //
 // Layer numbering used everywhere: hidden layer 0 is LinearModel.w1/batch_norm1
 // (baselineModel.py:67-68,90-94); residual block s owns hidden layers 1+2s (its w1) and

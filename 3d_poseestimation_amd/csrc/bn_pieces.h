@@ -1,4 +1,4 @@
-// Pieces of the BatchNorm statistics finalize shared by the kernels that do it (elementwise.hip, small_layer.hip).
+// Pieces of the BatchNorm statistics finalize shared by the kernels that do it (batchnorm.hip, small_layer.hip).
 // Floating-point contraction is OFF inside them: "SyncBN == one process on the concatenated batch, bit for bit" is a tested
 // property, and it must not depend on what the compiler contracts.
 #pragma once

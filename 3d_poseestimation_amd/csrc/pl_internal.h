@@ -183,10 +183,6 @@ int launch_gemm_planes(GemmLayout layout, const PlanesGemmArgs& a, hipStream_t s
 struct SlabSum { const float* part; float* out; int slabs; int64_t n; };
 bool planes_pair_carries_slab_sum(const PlanesGemmArgs& nn, const PlanesGemmArgs& tn, int slabs, int64_t n);
 int launch_gemm_planes_pair(const PlanesGemmArgs& nn, const PlanesGemmArgs& tn, const SlabSum* sum, hipStream_t s);
-// x [n] fp32 -> planes (static scale); n % 4 == 0, 16-byte aligned
-int launch_split_planes(const float* x, int64_t n, const PlaneOut& out, hipStream_t s);
-// PlaneOut of a caller's planes buffer ([2][n] fp16 for PL_F16X3, [n] bf16 for PL_BF16; NULL -> kind 0)
-int plane_out_of(int mode, void* planes, int64_t n, float scale, const float* dyn, PlaneOut* po, const char* who);
 
 int launch_gemm_f32(GemmLayout layout, const GemmArgs& a, hipStream_t s);
 // M <= kThinGemmMaxM rows (NT, NN): the contraction split over the chip, exact fp32 MFMA, slabs + one reduce/epilogue
@@ -203,7 +199,7 @@ void prof_end(void* rec, hipStream_t s);
 int prof_read(double min_flops, double max_flops, double* ms_total, int64_t* launches, double* flops_total);
 
 // ---------------------------------------------------------------------------------
-// streaming kernels (elementwise.hip)
+// streaming kernels: BatchNorm (batchnorm.hip)
 // ---------------------------------------------------------------------------------
 inline int bitmap_words_per_row(int H) { return ((H + 255) / 256) * 4; }
 
@@ -254,10 +250,6 @@ struct BnApplyArgs {
   BnFinalizeArgs fin;
 };
 int launch_bn_apply(const BnApplyArgs& a, hipStream_t s);
-// pl_pose_loss_fwd_bwd (pl_mse_fwd_bwd: Crit{}, B = 1, O = n) + (tick != NULL) tick[0] += 1 once the loss is written
-// (PLDesc.step_dev, graph replay)
-int loss_fwd_bwd_tick(const float* pred, const float* tgt, int64_t B, int64_t O, const Crit& c, float grad_scale, float* dpred,
-                      float* loss_out, void* scratch, uint64_t* tick, void* stream, const char* who);
 
 int bwd_row_chunks(int B, int H);
 // pass 1: partial column sums of dy and dy*zhat, dy = g * bits * keep_scale
@@ -290,6 +282,25 @@ struct BnBwdFinalizeArgs {
   int amax_world;               // 0: 1
 };
 int launch_bn_bwd_finalize(const BnBwdFinalizeArgs& a, hipStream_t s);
+// pass 2: dz = c0*(dy - c1 - zhat*c2)  (bn) or dz = dy (no bn); partial column sums of dz
+struct BnBwdDzArgs {
+  const float* g;
+  BnSaved saved;
+  const float* coef;
+  float keep_scale;
+  int bn, B, H;
+  int Hc;                       // 0: H
+  int rc;                       // row chunks (grid.y); 0: bwd_row_chunks(B, H)
+  float* dz;                    // NULL: planes only
+  float* part_db;
+  PlaneOut planes;              // kind != 0: also write dz as GEMM operand planes
+};
+int launch_bn_bwd_dz(const BnBwdDzArgs& a, hipStream_t s);
+// eval-mode fold: scale = gamma*rsqrt(rv+eps), shift = (bias - rm)*scale + beta  (bn) or 1, bias
+int launch_bn_fold_eval(const float* bias, const BnParams* bn, int H, float* scale, float* shift, hipStream_t s);
+// eval-mode BatchNorm for the saved-state forward: mean := running mean, rstd := rsqrt(running var + eps), scale, shift
+// (reads a.bn, a.H and the four outputs)
+int launch_bn_eval_stats(const BnFinalizeArgs& a, hipStream_t s);
 // Small batches (B <= kBnSmallRows, local statistics, fp32 outputs): statistics + finalize + apply of a hidden layer in ONE
 // launch (a workgroup owns a 256-column strip for all rows, held in registers), and pass 1 + finalize + dz + bias gradient
 // of its backward.  Measured same-box (bench.py --batch B): B = 64 0.305 -> 0.280 ms per step; B = 100 / 127 with sixteen
@@ -318,6 +329,82 @@ struct BnSmallBwdArgs {
   float* dz;
 };
 int launch_bn_small_bwd(const BnSmallBwdArgs& a, hipStream_t s);
+
+// ---------------------------------------------------------------------------------
+// streaming kernels: fixed-order sums (reduce.hip)
+// ---------------------------------------------------------------------------------
+// out[i] = sum_s slabs[s*n + i]
+int launch_reduce_slabs(const float* slabs, int nslab, int64_t n, float* out, hipStream_t s);
+// njobs independent out[c] = sum_r part[r][c] reductions in one launch
+// kind 2 (at most one job): out[0] = (sum of the R MSE partials) * loss_inv_n, then loss_tick[0] += 1 -- mse_final_kernel
+struct RowJob {
+  const float* part;
+  float* out;
+  int R, H, kind, transK;
+};
+int launch_reduce_rows_multi(const RowJob* jobs, int njobs, float loss_inv_n, uint64_t* loss_tick, hipStream_t s);
+// out[r][c] = bias[c] + sum_s slabs[s][r][c]
+int launch_reduce_slabs_bias(const float* slabs, int nslab, int rows, int cols, const float* bias,
+                             float* out, hipStream_t s);
+// partial column sums of X[rows][cols] -> part[RC][cols], RC = colsum_chunks(rows)
+int colsum_chunks(int rows);
+int launch_colsum_partial(const float* X, int rows, int cols, float* part, hipStream_t s);
+int launch_fill(float* p, int64_t n, float v, hipStream_t s);
+
+// ---------------------------------------------------------------------------------
+// streaming kernels: operand planes of a tensor no producer kernel splits (planes_split.hip)
+// ---------------------------------------------------------------------------------
+// x [n] fp32 -> planes (static scale); n % 4 == 0, 16-byte aligned
+int launch_split_planes(const float* x, int64_t n, const PlaneOut& out, hipStream_t s);
+// PlaneOut of a caller's planes buffer ([2][n] fp16 for PL_F16X3, [n] bf16 for PL_BF16; NULL -> kind 0)
+int plane_out_of(int mode, void* planes, int64_t n, float scale, const float* dyn, PlaneOut* po, const char* who);
+
+// ---------------------------------------------------------------------------------
+// streaming kernels: the train criterion (criterion.hip)
+// ---------------------------------------------------------------------------------
+// pl_pose_loss_fwd_bwd (pl_mse_fwd_bwd: Crit{}, B = 1, O = n) + (tick != NULL) tick[0] += 1 once the loss is written
+// (PLDesc.step_dev, graph replay)
+int loss_fwd_bwd_tick(const float* pred, const float* tgt, int64_t B, int64_t O, const Crit& c, float grad_scale, float* dpred,
+                      float* loss_out, void* scratch, uint64_t* tick, void* stream, const char* who);
+int loss_partial_only(const float* pred, const float* tgt, int64_t B, int64_t O, const Crit& c, float grad_scale, float* dpred,
+                      void* scratch, void* stream, const char* who);
+int loss_partials(const Crit& c, int64_t B, int64_t O);
+// the output Linear's slab reduce folded into the loss partial pass (fused train step; bit-identical to the two launches)
+bool mse_from_slabs_supported(int splits, int N);
+int loss_partial_from_slabs(const float* part, int splits, int B, int N, const float* bias, const float* tgt, const Crit& c,
+                            float grad_scale, float* y, float* dpred, void* scratch, void* stream);
+
+// ---------------------------------------------------------------------------------
+// streaming kernels: the flat optimizer (optim.hip)
+// ---------------------------------------------------------------------------------
+// the flat AdamW step over p, g, m, v [n] (adamw_kernel's only launch site).  in: the kernel's own argument block (adamw.h);
+// lr_dev / t_dev, the plane fields (adamw_planes) and the clip record are the optional parts, zero when absent
+struct AdamWArgs {
+  float* p;
+  const float* g;
+  float* m;
+  float* v;
+  int64_t n;
+  AdamWIn in;
+  const PLEma* ema;             // optional: the averaged weights follow in the same launch (e: beside p, for the same [n])
+};
+int launch_adamw(const AdamWArgs& a, hipStream_t s);
+int check_ema(const PLEma& ema, const char* who);
+
+// ---------------------------------------------------------------------------------
+// streaming kernels: the pose feed (pose_feed.hip)
+// ---------------------------------------------------------------------------------
+// the checks of a PLPoseAug's parameters (fn: the entry point named in the message) and the plan the transforms of
+// pose_augment.h and frame_warp.h read
+namespace pa { struct Plan; }
+int pose_aug_plan(const char* fn, const PLPoseAug* aug, uint64_t epoch, pa::Plan* plan);
+// the checks of a PLPoseCrop (and of the flip of the PLPoseAug that goes with it, nullable) and the spec frame_crop.h reads
+namespace fc { struct Spec; }
+int crop_spec(const char* fn, const PLPoseCrop* crop, const PLPoseAug* aug, fc::Spec* spec);
+
+// ---------------------------------------------------------------------------------
+// small batches (small_layer.hip)
+// ---------------------------------------------------------------------------------
 // Small batches, hidden layers behind the first (small_layer.hip): a workgroup owns 16 columns for all B <= 64 rows, so one
 // launch is Linear + BatchNorm1d (batch statistics) + ReLU + Dropout (+ skip) forward, and one launch is dX = dz W (+ skip
 // gradient) followed by the BatchNorm backward of the layer below.  Their ReLU & keep bitmap is in the "tile format" of
@@ -419,70 +506,6 @@ struct SmallTopBwdArgs {
   uint64_t* tick;
 };
 int launch_small_top_bwd(const SmallTopBwdArgs& a, hipStream_t s);
-// eval-mode BatchNorm for the saved-state forward: mean := running mean, rstd := rsqrt(running var + eps), scale, shift
-// (reads a.bn, a.H and the four outputs)
-int launch_bn_eval_stats(const BnFinalizeArgs& a, hipStream_t s);
-// pass 2: dz = c0*(dy - c1 - zhat*c2)  (bn) or dz = dy (no bn); partial column sums of dz
-struct BnBwdDzArgs {
-  const float* g;
-  BnSaved saved;
-  const float* coef;
-  float keep_scale;
-  int bn, B, H;
-  int Hc;                       // 0: H
-  int rc;                       // row chunks (grid.y); 0: bwd_row_chunks(B, H)
-  float* dz;                    // NULL: planes only
-  float* part_db;
-  PlaneOut planes;              // kind != 0: also write dz as GEMM operand planes
-};
-int launch_bn_bwd_dz(const BnBwdDzArgs& a, hipStream_t s);
-
-// out[i] = sum_s slabs[s*n + i]
-int launch_reduce_slabs(const float* slabs, int nslab, int64_t n, float* out, hipStream_t s);
-// njobs independent out[c] = sum_r part[r][c] reductions in one launch
-// kind 2 (at most one job): out[0] = (sum of the R MSE partials) * loss_inv_n, then loss_tick[0] += 1 -- mse_final_kernel
-struct RowJob {
-  const float* part;
-  float* out;
-  int R, H, kind, transK;
-};
-int launch_reduce_rows_multi(const RowJob* jobs, int njobs, float loss_inv_n, uint64_t* loss_tick, hipStream_t s);
-int loss_partial_only(const float* pred, const float* tgt, int64_t B, int64_t O, const Crit& c, float grad_scale, float* dpred,
-                      void* scratch, void* stream, const char* who);
-int loss_partials(const Crit& c, int64_t B, int64_t O);
-// the output Linear's slab reduce folded into the loss partial pass (fused train step; bit-identical to the two launches)
-bool mse_from_slabs_supported(int splits, int N);
-int loss_partial_from_slabs(const float* part, int splits, int B, int N, const float* bias, const float* tgt, const Crit& c,
-                            float grad_scale, float* y, float* dpred, void* scratch, void* stream);
-// out[r][c] = bias[c] + sum_s slabs[s][r][c]
-int launch_reduce_slabs_bias(const float* slabs, int nslab, int rows, int cols, const float* bias,
-                             float* out, hipStream_t s);
-// partial column sums of X[rows][cols] -> part[RC][cols], RC = colsum_chunks(rows)
-int colsum_chunks(int rows);
-int launch_colsum_partial(const float* X, int rows, int cols, float* part, hipStream_t s);
-// eval-mode fold: scale = gamma*rsqrt(rv+eps), shift = (bias - rm)*scale + beta  (bn) or 1, bias
-int launch_bn_fold_eval(const float* bias, const BnParams* bn, int H, float* scale, float* shift, hipStream_t s);
-int launch_fill(float* p, int64_t n, float v, hipStream_t s);
-// the checks of a PLPoseAug's parameters (fn: the entry point named in the message) and the plan the transforms of
-// pose_augment.h and frame_warp.h read
-namespace pa { struct Plan; }
-int pose_aug_plan(const char* fn, const PLPoseAug* aug, uint64_t epoch, pa::Plan* plan);
-// the checks of a PLPoseCrop (and of the flip of the PLPoseAug that goes with it, nullable) and the spec frame_crop.h reads
-namespace fc { struct Spec; }
-int crop_spec(const char* fn, const PLPoseCrop* crop, const PLPoseAug* aug, fc::Spec* spec);
-// the flat AdamW step over p, g, m, v [n] (adamw_kernel's only launch site).  in: the kernel's own argument block (adamw.h);
-// lr_dev / t_dev, the plane fields (adamw_planes) and the clip record are the optional parts, zero when absent
-struct AdamWArgs {
-  float* p;
-  const float* g;
-  float* m;
-  float* v;
-  int64_t n;
-  AdamWIn in;
-  const PLEma* ema;             // optional: the averaged weights follow in the same launch (e: beside p, for the same [n])
-};
-int launch_adamw(const AdamWArgs& a, hipStream_t s);
-int check_ema(const PLEma& ema, const char* who);
 
 // ---------------------------------------------------------------------------------
 // skinny layers (skinny.hip): 34 -> H and H -> 51, MFMA straight from registers

@@ -21,7 +21,7 @@
 
 namespace pl {
 
-// A criterion resolved against a shape [B][O]: what the launchers hand their kernels (crit_resolve, elementwise.hip).
+// A criterion resolved against a shape [B][O]: what the launchers hand their kernels (crit_resolve, criterion.hip).
 struct Crit {
   int kind = PL_CRIT_MSE;
   int G = 1;                    // coordinates per joint; O = J * G

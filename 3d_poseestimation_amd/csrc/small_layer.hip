@@ -347,7 +347,7 @@ __device__ __forceinline__ FwdPre fwd_prefetch(const FwdArgs& p, int c) {
   return q;
 }
 // the evaluation tail: y = relu(z s + t) (+ residual) with s = gamma / sqrt(running_var + eps), t = (bias - running_mean) s +
-// beta -- bn_fold_eval_kernel's fold and the GEMM epilogue's order (elementwise.hip, gemm_epilogue.h)
+// beta -- bn_fold_eval_kernel's fold and the GEMM epilogue's order (batchnorm.hip, gemm_epilogue.h)
 __device__ __forceinline__ float4 eval_tail(const FwdArgs& p, float4 z, const FwdPre& q, int c) {
   const int tid = threadIdx.x, r = tid >> 2;
   const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -407,7 +407,7 @@ __device__ __forceinline__ float4 fwd_tail(const FwdArgs& p, float4 z, const Fwd
     }
   }
   if (p.nbt && blockIdx.x == 0 && tid == 0) p.nbt[0] += 1;
-  // ReLU, dropout, bitmap, residual (element order of bn_apply_row, elementwise.hip)
+  // ReLU, dropout, bitmap, residual (element order of bn_apply_row, batchnorm.hip)
   uint32_t c3 = p.c3, k1 = p.k1;
   dropout_replay_step(c3, k1, p.seed_hi, p.step_dev);
   const int mode = p.mode & 7;
@@ -628,7 +628,7 @@ struct BnLo {
   const uint64_t* bits;
   float *dz, *dgamma, *dbeta, *dbias;
   float kscale;
-  int B, H, rowbits;                      // rowbits: the bitmap is in the row format of bn_apply_row (elementwise.hip)
+  int B, H, rowbits;                      // rowbits: the bitmap is in the row format of bn_apply_row (batchnorm.hip)
 };
 // what the tail reads from memory besides g: requested before the contraction that produces g
 struct BnPre { float4 zl, mu, rs, ga; uint64_t bw[4]; int bit; };

@@ -154,14 +154,14 @@ def test_split_k_tail_of_gemm_and_weight_gradient(pkg):
 
 
 def test_bn_replicas_of_conv_py_is_the_rule_of_the_batchnorm_kernels(pkg):
-    """conv._bn_replicas is a copy of csrc/elementwise.hip bn_replicas (the view [rows / R][R C] the BatchNorm kernels take of a
+    """conv._bn_replicas is a copy of csrc/batchnorm.hip bn_replicas (the view [rows / R][R C] the BatchNorm kernels take of a
     narrow map, and lay its ReLU bitmap out in): the join's masked sum reads the bitmap in that view.  The C rule is static,
     so the copy is tied to it twice: the function's text is the text the copy was made from -- whoever changes the rule
     changes both -- and pl_bn_join_bwd, which refuses exactly the maps with R != 1, refuses every map the copy folds."""
     import os
     import re
     import __graft_entry__ as ge
-    with open(os.path.join(ge.CSRC, "elementwise.hip")) as f:
+    with open(os.path.join(ge.CSRC, "batchnorm.hip")) as f:
         m = re.search(r"static int bn_replicas\(int64_t rows, int64_t C\) \{(.*?)\n\}", f.read(), re.S)
     assert m and " ".join(m.group(1).split()) == ("int r = C <= 64 ? 4 : (C <= 128 ? 2 : 1); "
                                                   "while (r > 1 && (rows % r != 0 || rows / r < 2)) r >>= 1; return r;")
