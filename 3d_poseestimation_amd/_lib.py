@@ -418,6 +418,21 @@ def on_device(dev):
     return torch.cuda.device(dev)
 
 
+def aligned16(t):
+    """`t` itself when its storage starts on a 16-byte boundary, else a copy that does (every fresh allocation does).
+    The entry points refuse a caller's pointer that a kernel reads or writes 16 bytes at a time and that is not 16-byte
+    aligned ("Alignment contract of caller pointers"); a contiguous view of a larger tensor -- table[n:],
+    table[i * B:(i + 1) * B] -- need not be.  The copy is an autograd op, so gradients still reach a misaligned leaf.  On the
+    aligned path this is one integer test: no sync, no allocation."""
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def require_aligned16_out(t, name):
+    """An `out=` tensor that a kernel writes in place cannot be copied behind the caller's back: refuse it by name."""
+    if t.data_ptr() % 16 != 0:
+        raise PoseliftError(f"{name} must be 16-byte aligned (data_ptr() % 16 == {t.data_ptr() % 16}): it is written in place")
+
+
 def require_device_tensor(t, name, dtype=torch.float32):
     if not t.is_cuda:
         raise PoseliftError(

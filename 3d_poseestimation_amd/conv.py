@@ -137,7 +137,8 @@ def conv2d_nhwc(x, w_ohwi, stride=1, padding=0, scale=None, shift=None, bias=Non
                 arith="bf16x6"):
     """x [B,H,W,Cin] fp32 -> [B,Ho,Wo,Cout] fp32.  relu: 0 none, 1 ReLU then + resid, 2 + resid then ReLU.
     arith: "bf16x6" (fp32-grade) or "bf16" (operands rounded to bf16: the throughput mode)."""
-    x, w = x.contiguous(), w_ohwi.contiguous()
+    # (a contiguous view such as frames[1:] may start off 16 bytes: the implicit-GEMM kernels refuse that)
+    x, w = _lib.aligned16(x.contiguous()), _lib.aligned16(w_ohwi.contiguous())
     _lib.require_device_tensor(x, "x")
     _lib.require_device_tensor(w, "weight")
     if x.dim() != 4 or w.dim() != 4 or w.shape[3] != x.shape[3]:
@@ -148,6 +149,7 @@ def conv2d_nhwc(x, w_ohwi, stride=1, padding=0, scale=None, shift=None, bias=Non
     y = torch.empty(B, Ho, Wo, Cout, dtype=torch.float32, device=x.device)
     opt = [_opt(scale, "scale", Cout), _opt(shift, "shift", Cout), _opt(bias, "bias", Cout),
            _opt(resid, "resid", y.numel())]
+    opt[3] = _lib.aligned16(opt[3]) if opt[3] is not None else None
     ptr = [t.data_ptr() if t is not None else None for t in opt]
     L = _lib.lib()
     nbytes = L.pl_conv2d_nhwc_scratch_bytes_ex(B, H, W, Cin, Cout, KH, KW, stride, padding, int(bias is not None),
@@ -163,7 +165,7 @@ def conv2d_nhwc(x, w_ohwi, stride=1, padding=0, scale=None, shift=None, bias=Non
 
 def conv2d_nhwc_wgrad(x, dy, kernel_size, stride=1, padding=0, arith="bf16x6"):
     """Weight gradient of conv2d_nhwc: x [B,H,W,Cin], dy [B,Ho,Wo,Cout] -> dw [Cout,KH,KW,Cin] (OHWI)."""
-    x, dy = x.contiguous(), dy.contiguous()
+    x, dy = _lib.aligned16(x.contiguous()), _lib.aligned16(dy.contiguous())
     _lib.require_device_tensor(x, "x")
     _lib.require_device_tensor(dy, "dy")
     B, H, W, Cin = x.shape
@@ -223,7 +225,7 @@ def conv2d_nhwc_dgrad(dy, w_ohwi, in_hw, stride=1, padding=0, arith="bf16x6"):
 
 
 def maxpool3x3s2_nhwc(x):
-    x = x.contiguous()
+    x = _lib.aligned16(x.contiguous())
     _lib.require_device_tensor(x, "x")
     B, H, W, C = x.shape
     y = torch.empty(B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C, dtype=torch.float32, device=x.device)
@@ -235,7 +237,7 @@ def maxpool3x3s2_nhwc(x):
 
 def deconv4x4s2_nhwc(x, w_sub, scale=None, shift=None, relu=0, arith="bf16x6"):
     """x [B,Hi,Wi,Cin] -> [B,2Hi,2Wi,Cout]; w_sub from deconv_subkernels()."""
-    x, w = x.contiguous(), w_sub.contiguous()
+    x, w = _lib.aligned16(x.contiguous()), _lib.aligned16(w_sub.contiguous())
     _lib.require_device_tensor(x, "x")
     _lib.require_device_tensor(w, "w_sub")
     B, Hi, Wi, Cin = x.shape
@@ -333,8 +335,9 @@ def _bn_fwd(ctx, z, identity, gamma, beta, running_mean, running_var, batches, e
     Saves what _bn_bwd needs on ctx.  (Here and in _bn_bwd the library is handed mode 0 next to a NULL planes pointer.)"""
     shape = z.shape
     C = shape[-1]
-    z2 = z.contiguous().reshape(-1, C)
-    id2 = identity.contiguous().reshape(-1, C) if identity is not None else None
+    # (the streaming kernels read z and the identity 16 bytes at a time: a contiguous view that starts off 16 bytes is copied)
+    z2 = _lib.aligned16(z.contiguous()).reshape(-1, C)
+    id2 = _lib.aligned16(identity.contiguous()).reshape(-1, C) if identity is not None else None
     rows = z2.shape[0]
     dev, L = z2.device, _lib.lib()
     y = torch.empty_like(z2) if f32 else None
@@ -419,7 +422,7 @@ class _BNFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        dz, _, dgamma, dbeta = _bn_bwd(ctx, dy.contiguous().reshape(-1, ctx.shape[-1]), ctx.needs_input_grad[1:3])
+        dz, _, dgamma, dbeta = _bn_bwd(ctx, _lib.aligned16(dy.contiguous()).reshape(-1, ctx.shape[-1]), ctx.needs_input_grad[1:3])
         return dz.reshape(ctx.shape), dgamma, dbeta, None, None, None, None, None, None, None, None, None
 
 
@@ -443,8 +446,8 @@ class _BNJoinFn(torch.autograd.Function):
         if g is None:
             return (None,) * 10
         C = ctx.shape[-1]
-        dz, dx, dgamma, dbeta = _bn_bwd(ctx, g.contiguous().reshape(-1, C), ctx.needs_input_grad[2:4],
-                                        gp.contiguous().reshape(-1, C) if gp is not None else None, join=True)
+        dz, dx, dgamma, dbeta = _bn_bwd(ctx, _lib.aligned16(g.contiguous()).reshape(-1, C), ctx.needs_input_grad[2:4],
+                                        _lib.aligned16(gp.contiguous()).reshape(-1, C) if gp is not None else None, join=True)
         return dz.reshape(ctx.shape), dx.reshape(ctx.shape), dgamma, dbeta, None, None, None, None, None, None
 
 
@@ -485,7 +488,7 @@ class _AddReLUFn(torch.autograd.Function):
         if a.shape != b.shape:
             raise ValueError("add_relu: shapes differ")
         C = a.shape[-1]
-        a2, b2 = a.contiguous().reshape(-1, C), b.contiguous().reshape(-1, C)
+        a2, b2 = _lib.aligned16(a.contiguous()).reshape(-1, C), _lib.aligned16(b.contiguous()).reshape(-1, C)
         _lib.require_device_tensor(a2, "a")
         _lib.require_device_tensor(b2, "b")
         rows = a2.shape[0]
@@ -510,8 +513,8 @@ class _AddReLUFn(torch.autograd.Function):
             g, gp = gp, None
         if g is None:
             return None, None, None
-        g2 = g.contiguous().reshape(-1, C)
-        gp2 = gp.contiguous().reshape(-1, C) if gp is not None else None
+        g2 = _lib.aligned16(g.contiguous()).reshape(-1, C)
+        gp2 = _lib.aligned16(gp.contiguous()).reshape(-1, C) if gp is not None else None
         dx = torch.empty_like(g2)
         with _lib.on_device(g2.device):
             rc = _lib.lib().pl_mask_add_by_bits(g2.data_ptr(), gp2.data_ptr() if gp2 is not None else None, bits.data_ptr(),
@@ -552,7 +555,7 @@ class _MaxPoolFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         (idx,) = ctx.saved_tensors
-        dy = dy.contiguous()
+        dy = _lib.aligned16(dy.contiguous())
         B, H, W, C = ctx.in_shape
         dx = torch.empty(B, H, W, C, dtype=torch.float32, device=dy.device)
         with _lib.on_device(dy.device):
@@ -563,7 +566,7 @@ class _MaxPoolFn(torch.autograd.Function):
 
 
 def maxpool3x3s2_nhwc_autograd(x):
-    return _MaxPoolFn.apply(x.contiguous())
+    return _MaxPoolFn.apply(_lib.aligned16(x.contiguous()))
 
 
 class _DeconvFn(torch.autograd.Function):
@@ -670,7 +673,7 @@ def _planes_of(t, scale, mode=_lib.PL_F16X3):
     carrier uses the first half of its bytes."""
     if not t.is_contiguous() and 1 <= t.dim() <= 4 and t.shape[-1] % 4 == 0 and t.dtype == torch.float32 and t.numel() > 0:
         return _planes_of_strided(t, t.shape, t.stride(), 0, scale, mode)       # (a permuted / transposed weight view)
-    t = t.contiguous()
+    t = _lib.aligned16(t.contiguous())
     out = torch.empty_like(t)
     with _lib.on_device(t.device):
         rc = _lib.lib().pl_planes_split(t.data_ptr(), t.numel(), mode, float(scale), out.data_ptr(),
@@ -690,6 +693,8 @@ def _gemm_planes_raw(layout, a, a_rows_cols, b, b_rows_cols, M, N, K, out_scale,
     With a bias the launch is never split over K (no slabs: a problem the library would split is its error to report)."""
     L = _lib.lib()
     dev = a.device
+    if out is not None:
+        _lib.require_aligned16_out(out, "out")           # (the GEMM's staged epilogue writes C 16 bytes at a time)
     C = torch.empty(M, N, device=dev) if out is None else out
     splits = L.pl_gemm_planes_splits(M, N, K) if bias is None else 1
     slabs = torch.empty(splits * M * N, device=dev) if splits > 1 else None

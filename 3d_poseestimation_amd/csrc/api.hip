@@ -553,6 +553,7 @@ extern "C" int pl_lifter_fwd_eval(const PLDesc* d, const float* x, float* y, int
                                   size_t ws_bytes, void* stream) {
   PL_TRY(check_desc(d, true));
   if (!x || !y) PL_FAIL(PL_EINVAL, "pl_lifter_fwd_eval: null x/y");
+  // (x meets element code -- small_first_fwd_kernel -- or launch_gemm_f32's own gate here: no alignment is asked of it)
   if (B <= 0) PL_FAIL(PL_ESHAPE, "pl_lifter_fwd_eval: B=%lld", (long long)B);
   const Ws w = plan(d, B);
   PL_TRY(check_ws(w, ws, ws_bytes));
@@ -651,6 +652,9 @@ static int fwd_saved_impl(const PLDesc* d, const float* x, float* y, int64_t B, 
                           bool defer_out_reduce) {
   PL_TRY(check_desc(d, true));
   if (!x || !y) PL_FAIL(PL_EINVAL, "pl_lifter_fwd_train: null x/y");
+  // x: the first Linear on skinny.hip stages whole 64-row groups of it as float4 (skinny_wide_out_kernel).  y is written by
+  // element kernels or behind launch_gemm_f32's own gate.
+  PL_REQUIRE_ALIGNED16("pl_lifter_fwd_train", x);
   if (B <= 0) PL_FAIL(PL_ESHAPE, "pl_lifter_fwd_train: B=%lld", (long long)B);
   if (d->bn && B < 2 && !eval_bn)
     PL_FAIL(PL_EBATCH, "Expected more than 1 value per channel when training (B=%lld)", (long long)B);
@@ -1076,6 +1080,9 @@ static int bwd_impl(const PLDesc* d, const float* x, const float* dy, int64_t B,
                     float* loss_out = nullptr, int n_loss_part = 0, float loss_inv_n = 0.f, const PLAdamWStep* adam = nullptr) {
   PL_TRY(check_desc(d, true));
   if (!x || !dy || !grads) PL_FAIL(PL_EINVAL, "pl_lifter_bwd: null x/dy/flat_grads");
+  // dy: g = dy W5 on skinny.hip stages it as float4, as the forward does x.  x is read by element here (skinny_wide_in_kernel,
+  // first_wgrad) or behind launch_gemm_f32's gate; dx leaves through that GEMM's gated epilogue.
+  PL_REQUIRE_ALIGNED16("pl_lifter_bwd", dy);
   if (B <= 0) PL_FAIL(PL_ESHAPE, "pl_lifter_bwd: B=%lld", (long long)B);
   const Ws w = plan(d, B);
   PL_TRY(check_ws(w, ws, ws_bytes));
@@ -1196,6 +1203,11 @@ extern "C" int pl_gemm_planes(int layout, int mode, const float* A, const float*
   if (layout < 0 || layout > 2) PL_FAIL(PL_EINVAL, "pl_gemm_planes: layout %d", layout);
   if (mode != PL_F16X3 && mode != PL_BF16) PL_FAIL(PL_EDTYPE, "pl_gemm_planes: mode %d", mode);
   if (!A || !Bm || !C || !scratch) PL_FAIL(PL_EINVAL, "pl_gemm_planes: null pointer");
+  // A, Bm: split_planes_kernel reads float4; C, bias: the planes GEMM's staged epilogue moves 16 bytes at a time
+  PL_REQUIRE_ALIGNED16("pl_gemm_planes", A);
+  PL_REQUIRE_ALIGNED16("pl_gemm_planes", Bm);
+  PL_REQUIRE_ALIGNED16("pl_gemm_planes", C);
+  PL_REQUIRE_ALIGNED16("pl_gemm_planes", bias);
   if (M <= 0 || N <= 0 || K <= 0 || M * K >= (1ll << 29) || N * K >= (1ll << 29)) PL_FAIL(PL_ESHAPE, "pl_gemm_planes: bad shape");
   if (!(scale_a > 0.f) || !(scale_b > 0.f)) PL_FAIL(PL_EINVAL, "pl_gemm_planes: scales must be positive powers of two");
   hipStream_t s = (hipStream_t)stream;
@@ -1248,6 +1260,11 @@ extern "C" int pl_gemm_planes_raw(int layout, int mode, const void* A, int64_t a
   if (layout < 0 || layout > 2) PL_FAIL(PL_EINVAL, "pl_gemm_planes_raw: layout %d", layout);
   if (mode != PL_F16X3 && mode != PL_BF16) PL_FAIL(PL_EDTYPE, "pl_gemm_planes_raw: mode %d", mode);
   if (!A || !Bm || !C) PL_FAIL(PL_EINVAL, "pl_gemm_planes_raw: null pointer");
+  PL_REQUIRE_ALIGNED16("pl_gemm_planes_raw", A);             // (operand planes: 16-byte LDS-DMA; C, bias, stat: the staged epilogue)
+  PL_REQUIRE_ALIGNED16("pl_gemm_planes_raw", Bm);
+  PL_REQUIRE_ALIGNED16("pl_gemm_planes_raw", C);
+  PL_REQUIRE_ALIGNED16("pl_gemm_planes_raw", bias);
+  PL_REQUIRE_ALIGNED16("pl_gemm_planes_raw", stat);
   if (M <= 0 || N <= 0 || K <= 0 || M > INT32_MAX || N > INT32_MAX || K > INT32_MAX || lda > INT32_MAX || ldb > INT32_MAX)
     PL_FAIL(PL_ESHAPE, "pl_gemm_planes_raw: bad shape");
   PlanesGemmArgs g = {};
@@ -1476,6 +1493,7 @@ static int train_fwd_bwd_impl(const PLDesc* d, const float* x, const float* targ
                               int lo, void* stream, const PLAdamWStep* adam) {
   PL_TRY(check_desc(d, true));
   if (!x || !target || !y || !loss || !grads) PL_FAIL(PL_EINVAL, "pl_lifter_train_fwd_bwd: null pointer");
+  PL_REQUIRE_ALIGNED16("pl_lifter_train_fwd_bwd", x);        // (target, y and loss: element kernels only -- criterion.hip, small_layer.hip)
   if (B <= 0) PL_FAIL(PL_ESHAPE, "pl_lifter_train_fwd_bwd: B=%lld", (long long)B);
   PL_TRY(check_range(d, hi, lo, "pl_lifter_train_fwd_bwd"));
   Crit cr;

@@ -1182,6 +1182,12 @@ extern "C" int pl_bn_train_fwd_ex(const float* z, int64_t rows, int64_t C, const
                                   float* y, uint64_t* bits, float* mean, float* rstd, void* scratch, void* y_planes,
                                   int planes_mode, const float* gemm_stat, const float* join, void* stream) {
   if (!z || !gamma || !beta || (!y && !y_planes) || !bits || !mean || !rstd || !scratch) PL_FAIL(PL_EINVAL, "pl_bn_train_fwd: null pointer");
+  // the streaming kernels take z, join and y as float4 and the bitmap as 64-bit words (bn_colstats_kernel, bn_apply_rows);
+  // gamma, beta, mean, rstd and the running statistics only meet element code (bn_finalize_kernel)
+  PL_REQUIRE_ALIGNED16("pl_bn_train_fwd", z);
+  PL_REQUIRE_ALIGNED16("pl_bn_train_fwd", y);
+  PL_REQUIRE_ALIGNED16("pl_bn_train_fwd", bits);
+  PL_REQUIRE_ALIGNED16("pl_bn_train_fwd", join);
   pl::PlaneOut ypo;
   PL_TRY(pl::plane_out_of(planes_mode, y_planes, rows * C, pl::kConvActPlaneScale, nullptr, &ypo, "pl_bn_train_fwd_ex"));
   pl::range_watch(ypo, PL_RANGE_SITE_CONV_ACT);
@@ -1241,6 +1247,14 @@ extern "C" int pl_bn_train_bwd_ex(const float* dy, const uint64_t* bits, const f
                                   void* scratch, void* dz_planes, int planes_mode, float* dz_scale, void* stream) {
   if (!dy || !bits || !z || !mean || !rstd || !gamma || (!dz && !dz_planes) || !dgamma || !dbeta || !scratch)
     PL_FAIL(PL_EINVAL, "pl_bn_train_bwd: null pointer");
+  // float4 / 64-bit in bn_bwd_reduce_kernel and bn_bwd_dz_kernel (mean and rstd: four columns per lane); gamma, dgamma and
+  // dbeta only meet element code (bn_bwd_finalize_kernel)
+  PL_REQUIRE_ALIGNED16("pl_bn_train_bwd", dy);
+  PL_REQUIRE_ALIGNED16("pl_bn_train_bwd", bits);
+  PL_REQUIRE_ALIGNED16("pl_bn_train_bwd", z);
+  PL_REQUIRE_ALIGNED16("pl_bn_train_bwd", mean);
+  PL_REQUIRE_ALIGNED16("pl_bn_train_bwd", rstd);
+  PL_REQUIRE_ALIGNED16("pl_bn_train_bwd", dz);
   if (rows < 2 || rows > INT32_MAX || C <= 0 || (C & 3)) PL_FAIL(PL_ESHAPE, "pl_bn_train_bwd: rows=%lld C=%lld", (long long)rows, (long long)C);
   const bool scaled = dz_planes && planes_mode == PL_F16X3;
   if (scaled && !dz_scale) PL_FAIL(PL_EINVAL, "pl_bn_train_bwd_ex: fp16 planes of dz need dz_scale");
@@ -1260,6 +1274,14 @@ extern "C" int pl_bn_join_bwd(const float* g, const float* g2, const uint64_t* b
                               float* dbeta, void* scratch, void* dz_planes, int planes_mode, float* dz_scale, void* stream) {
   if (!g || !bits || !z || !mean || !rstd || !gamma || !dx || (!dz && !dz_planes) || !dgamma || !dbeta || !scratch)
     PL_FAIL(PL_EINVAL, "pl_bn_join_bwd: null pointer");
+  PL_REQUIRE_ALIGNED16("pl_bn_join_bwd", g);                 // (as pl_bn_train_bwd_ex; g2 and dx: bn_bwd_reduce_kernel's join)
+  PL_REQUIRE_ALIGNED16("pl_bn_join_bwd", g2);
+  PL_REQUIRE_ALIGNED16("pl_bn_join_bwd", bits);
+  PL_REQUIRE_ALIGNED16("pl_bn_join_bwd", z);
+  PL_REQUIRE_ALIGNED16("pl_bn_join_bwd", mean);
+  PL_REQUIRE_ALIGNED16("pl_bn_join_bwd", rstd);
+  PL_REQUIRE_ALIGNED16("pl_bn_join_bwd", dx);
+  PL_REQUIRE_ALIGNED16("pl_bn_join_bwd", dz);
   if (rows < 2 || rows > INT32_MAX || C <= 0 || (C & 3)) PL_FAIL(PL_ESHAPE, "pl_bn_join_bwd: rows=%lld C=%lld", (long long)rows, (long long)C);
   if (pl::bn_replicas(rows, C) != 1) PL_FAIL(PL_ESHAPE, "pl_bn_join_bwd: C=%lld is narrower than one 256-column strip", (long long)C);
   const bool scaled = dz_planes && planes_mode == PL_F16X3;
@@ -1281,6 +1303,10 @@ extern "C" int pl_add_relu_fwd(const float* a, const float* b, int64_t rows, int
 extern "C" int pl_add_relu_fwd_ex(const float* a, const float* b, int64_t rows, int64_t C, float* out, uint64_t* bits,
                                   void* out_planes, int planes_mode, void* stream) {
   if (!a || !b || !out || !bits) PL_FAIL(PL_EINVAL, "pl_add_relu_fwd: null pointer");
+  PL_REQUIRE_ALIGNED16("pl_add_relu_fwd", a);                // (add_relu_kernel: float4 rows, 64-bit bitmap words)
+  PL_REQUIRE_ALIGNED16("pl_add_relu_fwd", b);
+  PL_REQUIRE_ALIGNED16("pl_add_relu_fwd", out);
+  PL_REQUIRE_ALIGNED16("pl_add_relu_fwd", bits);
   if (rows <= 0 || rows > INT32_MAX || C <= 0 || (C & 3)) PL_FAIL(PL_ESHAPE, "pl_add_relu_fwd: rows=%lld C=%lld", (long long)rows, (long long)C);
   pl::PlaneOut po;
   PL_TRY(pl::plane_out_of(planes_mode, out_planes, rows * C, pl::kConvActPlaneScale, nullptr, &po, "pl_add_relu_fwd_ex"));
@@ -1301,6 +1327,10 @@ extern "C" int pl_mask_by_bits(const float* g, const uint64_t* bits, int64_t row
 extern "C" int pl_mask_add_by_bits(const float* g, const float* g2, const uint64_t* bits, int64_t rows, int64_t C, float* dx,
                                    void* stream) {
   if (!g || !bits || !dx) PL_FAIL(PL_EINVAL, "pl_mask_by_bits: null pointer");
+  PL_REQUIRE_ALIGNED16("pl_mask_by_bits", g);                // (mask_by_bits_kernel: float4 rows, 64-bit bitmap words)
+  PL_REQUIRE_ALIGNED16("pl_mask_by_bits", g2);
+  PL_REQUIRE_ALIGNED16("pl_mask_by_bits", bits);
+  PL_REQUIRE_ALIGNED16("pl_mask_by_bits", dx);
   if (rows <= 0 || rows > INT32_MAX || C <= 0 || (C & 3)) PL_FAIL(PL_ESHAPE, "pl_mask_by_bits: rows=%lld C=%lld", (long long)rows, (long long)C);
   const int strips = ((int)C + 255) / 256;
   dim3 grid(strips, pl::stream_rows_grid((int)rows, strips));

@@ -716,6 +716,10 @@ extern "C" int pl_conv2d_nhwc_fwd(const float* x, int64_t B, int64_t H, int64_t 
                                   const float* shift, const float* bias, int relu, const float* resid, float* y,
                                   int arith, void* scratch, size_t scratch_bytes, void* stream) {
   if (!x || !w || !y) PL_FAIL(PL_EINVAL, "pl_conv2d_nhwc_fwd: null pointer");
+  // y and resid: float4 in stem7x7_c3_kernel and reduce_slabs_epi_kernel.  x and w: element code (the stem, im2col), behind
+  // launch_gemm_f32's gate (1x1) or refused by conv_fwd_check (the implicit GEMM).
+  PL_REQUIRE_ALIGNED16("pl_conv2d_nhwc_fwd", y);
+  PL_REQUIRE_ALIGNED16("pl_conv2d_nhwc_fwd", resid);
   if (arith != PL_BF16X6 && arith != PL_BF16) PL_FAIL(PL_EDTYPE, "pl_conv2d_nhwc_fwd: arith %d (PL_BF16X6 or PL_BF16)", arith);
   if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || KH <= 0 || KW <= 0 || stride <= 0 || pad < 0)
     PL_FAIL(PL_ESHAPE, "pl_conv2d_nhwc_fwd: bad geometry");
@@ -730,6 +734,8 @@ extern "C" int pl_conv2d_nhwc_fwd(const float* x, int64_t B, int64_t H, int64_t 
 extern "C" int pl_maxpool3x3s2_nhwc(const float* x, int64_t B, int64_t H, int64_t W, int64_t C, float* y,
                                     void* stream) {
   if (!x || !y) PL_FAIL(PL_EINVAL, "pl_maxpool3x3s2_nhwc: null pointer");
+  PL_REQUIRE_ALIGNED16("pl_maxpool3x3s2_nhwc", x);
+  PL_REQUIRE_ALIGNED16("pl_maxpool3x3s2_nhwc", y);
   if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 3)) PL_FAIL(PL_ESHAPE, "pl_maxpool3x3s2_nhwc: C %% 4 == 0 needed");
   const int64_t Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
   const int64_t n4 = B * Ho * Wo * (C >> 2);
@@ -751,6 +757,7 @@ extern "C" int pl_deconv4x4s2_nhwc_fwd(const float* x, int64_t B, int64_t Hi, in
                                        int relu, float* y, int arith, void* scratch, size_t scratch_bytes,
                                        void* stream) {
   if (!x || !w_sub || !y || !scratch) PL_FAIL(PL_EINVAL, "pl_deconv4x4s2_nhwc_fwd: null pointer");
+  PL_REQUIRE_ALIGNED16("pl_deconv4x4s2_nhwc_fwd", y);              // (deconv_interleave_kernel; x and w_sub: conv_fwd_check)
   if (arith != PL_BF16X6 && arith != PL_BF16) PL_FAIL(PL_EDTYPE, "pl_deconv4x4s2_nhwc_fwd: arith %d", arith);
   if (B <= 0 || Hi <= 0 || Wi <= 0 || Cin <= 0 || Cout <= 0 || (Cout & 3)) PL_FAIL(PL_ESHAPE, "pl_deconv4x4s2_nhwc_fwd: bad geometry");
   if ((scale != nullptr) != (shift != nullptr)) PL_FAIL(PL_EINVAL, "pl_deconv4x4s2_nhwc_fwd: scale without shift");
@@ -843,6 +850,7 @@ extern "C" int pl_conv2d_nhwc_wgrad(const float* x, int64_t B, int64_t H, int64_
                                     void* scratch, size_t scratch_bytes, void* stream) {
   if (arith != PL_BF16X6 && arith != PL_BF16) PL_FAIL(PL_EDTYPE, "pl_conv2d_nhwc_wgrad: arith %d (PL_BF16X6 or PL_BF16)", arith);
   if (!x || !dy || !dw) PL_FAIL(PL_EINVAL, "pl_conv2d_nhwc_wgrad: null pointer");
+  PL_REQUIRE_ALIGNED16("pl_conv2d_nhwc_wgrad", dy);                // (stem7x7_c3_wgrad_kernel stages rows of dy as float4)
   if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || KH <= 0 || KW <= 0 || stride <= 0 || pad < 0)
     PL_FAIL(PL_ESHAPE, "pl_conv2d_nhwc_wgrad: bad geometry");
   const int64_t Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
@@ -902,6 +910,9 @@ extern "C" int pl_conv2d_nhwc_wgrad(const float* x, int64_t B, int64_t H, int64_
 extern "C" int pl_maxpool3x3s2_nhwc_bwd(const float* x, const float* dy, int64_t B, int64_t H, int64_t W, int64_t C,
                                         float* dx, void* stream) {
   if (!x || !dy || !dx) PL_FAIL(PL_EINVAL, "pl_maxpool3x3s2_nhwc_bwd: null pointer");
+  PL_REQUIRE_ALIGNED16("pl_maxpool3x3s2_nhwc_bwd", x);
+  PL_REQUIRE_ALIGNED16("pl_maxpool3x3s2_nhwc_bwd", dy);
+  PL_REQUIRE_ALIGNED16("pl_maxpool3x3s2_nhwc_bwd", dx);
   if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 3)) PL_FAIL(PL_ESHAPE, "pl_maxpool3x3s2_nhwc_bwd: C %% 4 == 0 needed");
   const int64_t Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
   const int64_t n4 = B * H * W * (C >> 2);
@@ -960,6 +971,8 @@ extern "C" int pl_colsum_planes(const void* planes, int planes_mode, int64_t row
 extern "C" int pl_upsample2x_zero_nhwc(const float* x, int64_t B, int64_t Hi, int64_t Wi, int64_t C, float* y,
                                        void* stream) {
   if (!x || !y) PL_FAIL(PL_EINVAL, "pl_upsample2x_zero_nhwc: null pointer");
+  PL_REQUIRE_ALIGNED16("pl_upsample2x_zero_nhwc", x);
+  PL_REQUIRE_ALIGNED16("pl_upsample2x_zero_nhwc", y);
   if (B <= 0 || Hi <= 0 || Wi <= 0 || C <= 0 || (C & 3)) PL_FAIL(PL_ESHAPE, "pl_upsample2x_zero_nhwc: C %% 4 == 0 needed");
   const int64_t n4 = B * 4 * Hi * Wi * (C >> 2);
   if (n4 > (int64_t)INT32_MAX * NTHR) PL_FAIL(PL_ESHAPE, "pl_upsample2x_zero_nhwc: too large");
@@ -972,6 +985,8 @@ extern "C" int pl_upsample2x_zero_nhwc(const float* x, int64_t B, int64_t Hi, in
 extern "C" int pl_maxpool3x3s2_nhwc_idx(const float* x, int64_t B, int64_t H, int64_t W, int64_t C, float* y,
                                         unsigned char* idx, void* stream) {
   if (!x || !y || !idx) PL_FAIL(PL_EINVAL, "pl_maxpool3x3s2_nhwc_idx: null pointer");
+  PL_REQUIRE_ALIGNED16("pl_maxpool3x3s2_nhwc_idx", x);
+  PL_REQUIRE_ALIGNED16("pl_maxpool3x3s2_nhwc_idx", y);
   if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 3)) PL_FAIL(PL_ESHAPE, "pl_maxpool3x3s2_nhwc_idx: C %% 4 == 0 needed");
   if (reinterpret_cast<uintptr_t>(idx) & 3) PL_FAIL(PL_EINVAL, "pl_maxpool3x3s2_nhwc_idx: idx not 4-byte aligned");
   const int64_t Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
@@ -987,6 +1002,8 @@ extern "C" int pl_maxpool3x3s2_nhwc_idx(const float* x, int64_t B, int64_t H, in
 extern "C" int pl_maxpool3x3s2_nhwc_bwd_idx(const unsigned char* idx, const float* dy, int64_t B, int64_t H, int64_t W,
                                             int64_t C, float* dx, void* stream) {
   if (!idx || !dy || !dx) PL_FAIL(PL_EINVAL, "pl_maxpool3x3s2_nhwc_bwd_idx: null pointer");
+  PL_REQUIRE_ALIGNED16("pl_maxpool3x3s2_nhwc_bwd_idx", dy);
+  PL_REQUIRE_ALIGNED16("pl_maxpool3x3s2_nhwc_bwd_idx", dx);
   if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 3)) PL_FAIL(PL_ESHAPE, "pl_maxpool3x3s2_nhwc_bwd_idx: C %% 4 == 0 needed");
   if (reinterpret_cast<uintptr_t>(idx) & 3) PL_FAIL(PL_EINVAL, "pl_maxpool3x3s2_nhwc_bwd_idx: idx not 4-byte aligned");
   const int64_t Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;

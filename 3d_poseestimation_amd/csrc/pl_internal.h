@@ -43,6 +43,14 @@ void set_error(const char* fmt, ...);
       PL_FAIL(PL_EHIP, "%s: launch failed: %s", what, hipGetErrorString(e__)); \
   } while (0)
 
+// The alignment contract of caller pointers: an entry point refuses, before any launch, a caller's pointer that a
+// kernel behind it reads or writes wider than 4 bytes and that is not 16-byte aligned.  NULL (an optional pointer) passes.
+#define PL_REQUIRE_ALIGNED16(who, ptr)                                       \
+  do {                                                                       \
+    if (reinterpret_cast<uintptr_t>(ptr) & 15)                               \
+      PL_FAIL(PL_EINVAL, "%s: %s not 16-byte aligned", who, #ptr);           \
+  } while (0)
+
 #define PL_TRY(expr)        \
   do {                      \
     int rc__ = (expr);      \

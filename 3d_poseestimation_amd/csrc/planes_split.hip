@@ -74,6 +74,7 @@ extern "C" float pl_conv_act_plane_scale(void) { return pl::kConvActPlaneScale; 
 
 extern "C" int pl_planes_split(const float* x, int64_t n, int mode, float scale, void* planes, void* stream) {
   if (!x || !planes || n <= 0 || !(scale > 0.f)) PL_FAIL(PL_EINVAL, "pl_planes_split: bad arguments");
+  PL_REQUIRE_ALIGNED16("pl_planes_split", x);                // (split_planes_kernel reads float4; planes: plane_out_of)
   pl::PlaneOut po;
   PL_TRY(pl::plane_out_of(mode, planes, n, scale, nullptr, &po, "pl_planes_split"));
   pl::range_watch(po, pl::split_site(scale));

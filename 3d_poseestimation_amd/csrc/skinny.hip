@@ -73,7 +73,8 @@ __global__ __launch_bounds__(NTHR) void skinny_wide_out_kernel(
   }
   const float b = bias ? bias[c] : 0.f;
   if (r_base + RG <= B) {
-    // the 64 narrow rows are ONE contiguous run of 64 K floats (16-byte aligned: 64 K * 4 is a multiple of 16): three or four
+    // the 64 narrow rows are ONE contiguous run of 64 K floats, 16-byte aligned because X is (the caller's x or dy: the lifter
+    // entry points of api.hip refuse a misaligned one before any launch) and 64 K * 4 is a multiple of 16: three or four
     // 16-byte loads per thread, all requested before the first LDS write.  (The element loop below kept one 4-byte load in
     // flight per thread: nine -- K = 51: thirteen -- dependent round trips before the first MFMA, most of the kernel's time.)
     constexpr int N4 = RG * K / 4, IT = (N4 + NTHR - 1) / NTHR;

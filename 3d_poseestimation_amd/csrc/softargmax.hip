@@ -483,7 +483,7 @@ int launch_softargmax_bwd(const BwdArgs& a, const char* who, const HmArgs* hm, h
   if (!a.logits || !a.stats || !a.gcoords || !a.dlogits || (hm && (!hm->target || !a.gsq)))
     PL_FAIL(PL_EINVAL, "%s: null pointer", who);
   if ((reinterpret_cast<uintptr_t>(a.logits) | reinterpret_cast<uintptr_t>(a.dlogits)) & 15)
-    PL_FAIL(PL_EINVAL, "%s: tensors not 16-byte aligned", who);
+    PL_FAIL(PL_EINVAL, "%s: logits / dlogits not 16-byte aligned", who);
   PL_TRY(check_dims(who, a.BJ, a.D, a.H, a.W, a.ncoord, true, 65535 * 64));
   if (a.BJ > 65535) PL_FAIL(PL_ESHAPE, "%s: BJ=%lld > 65535 (split the batch)", who, (long long)a.BJ);
   HmIn in;
@@ -537,7 +537,7 @@ int launch_softargmax_nhwc_bwd(const NhwcBwdArgs& a, const char* who, const HmAr
   if (!a.logits || !a.stats || !a.gcoords || (!a.dlogits && !a.dl_planes) || (hm && (!hm->target || !a.gsq)))
     PL_FAIL(PL_EINVAL, "%s: null pointer", who);
   if ((reinterpret_cast<uintptr_t>(a.logits) | reinterpret_cast<uintptr_t>(a.dlogits)) & 15)
-    PL_FAIL(PL_EINVAL, "%s: tensors not 16-byte aligned", who);
+    PL_FAIL(PL_EINVAL, "%s: logits / dlogits not 16-byte aligned", who);
   PL_TRY(check_nhwc_dims(who, a.B, a.J, a.H, a.W));
   const int64_t n4 = a.B * a.H * a.W * a.J * 16;
   if (n4 > (int64_t)INT32_MAX * NTHR) PL_FAIL(PL_ESHAPE, "%s: too large", who);

@@ -763,7 +763,7 @@ static int ln_fwd(const char* who, const float* x, const float* add, int64_t T, 
     PL_FAIL(PL_EINVAL, "%s: null pointer", who);
   if (!aligned16(x) || (add && (!aligned16(add) || !aligned16(x_out))) || (y && !aligned16(y)) ||
       (g1 && !aligned16(g1)) || (b1 && !aligned16(b1)) || (g2 && !aligned16(g2)) || (b2 && !aligned16(b2)))
-    PL_FAIL(PL_EINVAL, "%s: pointers must be 16-byte aligned", who);
+    PL_FAIL(PL_EINVAL, "%s: x / add / x_out / y / g1 / b1 / g2 / b2 must be 16-byte aligned", who);
   PL_TRY(carrier_check(y_bf16, T, rows_pad, H, who));
   const int64_t rows = y_bf16 ? rows_pad : T;      // (the carrier kernel also zeroes the padding rows)
   hipLaunchKernelGGL(y_bf16 ? vit_ln_fwd<true> : vit_ln_fwd<false>, dim3(blocks_for(rows, NT / kWave)), dim3(NT), 0,
@@ -798,7 +798,7 @@ static int ln_bwd(const char* who, const float* dy, const float* dres, const flo
     PL_FAIL(PL_EINVAL, "%s: null pointer", who);
   if (!aligned16(dy) || !aligned16(x) || (dx && !aligned16(dx)) || (dres && !aligned16(dres)) || !aligned16(g1) ||
       (b1 && !aligned16(b1)) || (g2 && !aligned16(g2)))
-    PL_FAIL(PL_EINVAL, "%s: pointers must be 16-byte aligned", who);
+    PL_FAIL(PL_EINVAL, "%s: dy / x / dx / dres / g1 / b1 / g2 must be 16-byte aligned", who);
   PL_TRY(carrier_check(dx_bf16, T, rows_pad, H, who));
   hipStream_t s = (hipStream_t)stream;
   const int64_t nch = chunks_of(T);
@@ -979,7 +979,7 @@ extern "C" int pl_vit_planes_dyn(const float* x, int64_t rows, int64_t cols, int
     PL_FAIL(PL_ESHAPE, "pl_vit_planes_dyn: rows=%lld cols=%lld rows_pad=%lld", (long long)rows, (long long)cols,
             (long long)rows_pad);
   if (!aligned16(x) || (reinterpret_cast<uintptr_t>(planes) & 7) || ((rows_pad * cols) & 3))
-    PL_FAIL(PL_EINVAL, "pl_vit_planes_dyn: misaligned operand");
+    PL_FAIL(PL_EINVAL, "pl_vit_planes_dyn: misaligned operand (x must be 16-byte aligned, planes 8-byte, rows_pad * cols %% 4 == 0)");
   hipStream_t s = (hipStream_t)stream;
   const int64_t n = rows * cols;
   const int nb = (int)std::min<int64_t>(kAmaxBlocks, std::max<int64_t>(1, (n + 4 * NT - 1) / (4 * NT)));

@@ -164,7 +164,7 @@ def head_nchw(logits, num_joints, depth_dim, hm=None, centred=None):
     B, C, H, W = logits.shape
     if C != num_joints * depth_dim:
         raise ValueError(f"expected {num_joints * depth_dim} channels, got {C}")
-    x = logits.contiguous().float()
+    x = _lib.aligned16(logits.contiguous().float())     # (both passes read the logits 16 bytes at a time)
     _lib.require_device_tensor(x, "heat-map logits")
     BJ = B * num_joints
     node_args = _node_args(hm, (W, H, depth_dim), centred, BJ, ncoord, x.device)
@@ -173,7 +173,7 @@ def head_nchw(logits, num_joints, depth_dim, hm=None, centred=None):
 
 def head_nhwc(logits, num_joints, hm=None, link=None):
     """What the two NHWC functions below do; hm as in head_nchw, link: conv.PlaneLink of the final convolution or None."""
-    x = logits.contiguous()
+    x = _lib.aligned16(logits.contiguous())             # (the backward reads the logits 16 bytes at a time)
     _lib.require_device_tensor(x, "heat-map logits")
     B, H, W, C = x.shape
     if C != num_joints * 64:

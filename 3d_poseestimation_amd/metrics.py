@@ -26,6 +26,7 @@ MAX_GROUPS = MAX_THRESHOLDS = 32
 
 def _pose_pair(pred, target):
     pred, target = pred.detach().float().contiguous(), target.detach().float().contiguous()
+    pred, target = _lib.aligned16(pred), _lib.aligned16(target)     # (pose_errors_kernel loads both 16 bytes at a time)
     _lib.require_device_tensor(pred, "pred")
     _lib.require_device_tensor(target, "target")
     if target.dim() != 3 or target.shape[2] != 3 or pred.shape != target.shape:

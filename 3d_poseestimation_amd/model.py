@@ -69,7 +69,7 @@ class _LifterEvalFn(torch.autograd.Function):
             raise _lib.PoseliftError("second backward through the same LinearModel forward (retain_graph): the saved "
                                      "activations were released after the first one -- run the forward again")
         try:
-            dx = model._run_bwd(x2, gy.contiguous(), ws, ctx.need_dx, last_graph=False, eval_mode=True)
+            dx = model._run_bwd(x2, _lib.aligned16(gy.contiguous()), ws, ctx.need_dx, last_graph=False, eval_mode=True)
         finally:
             ctx.ticket.close()
             model._release_workspace(ws, ctx.token)
@@ -125,7 +125,7 @@ class _LifterFn(torch.autograd.Function):
                                      "activations were released after the first one -- run the forward again")
         last = model._live_graphs == 1
         try:
-            dx = model._run_bwd(x2, gy.contiguous(), ws, ctx.need_dx, last_graph=last)
+            dx = model._run_bwd(x2, _lib.aligned16(gy.contiguous()), ws, ctx.need_dx, last_graph=last)
         finally:
             ctx.ticket.close()
             model._release_workspace(ws, ctx.token)
@@ -550,6 +550,7 @@ class LinearModel(nn.Module):
         adamw (a _lib.PLAdamWStep from FlatAdamW._step_struct; no sync): the optimizer step as well, in the same call
         (pl_lifter_train_step) -- the parameters are updated in place."""
         B = x2.shape[0]
+        x2 = _lib.aligned16(x2)               # (the library stages x 16 bytes at a time; the target only meets element kernels)
         # (checked before anything is counted or launched; the struct points into the criterion's weights)
         crit = ctypes.byref(criterion.struct(self.output_size, x2.device)) if criterion is not None else None
         ws = self._acquire_workspace(B)
@@ -625,6 +626,9 @@ class LinearModel(nn.Module):
             raise _lib.PoseliftError(f"x on {x2.device}, parameters on {self._flat.device}")
         with _lib.on_device(x2.device):
             if self.training:
+                # (a contiguous view, table[n:], may start off 16 bytes: the saved-activation forwards stage x 16 bytes at a
+                #  time and refuse that; the plain eval forward below reads it behind the GEMM's own gate and takes any view)
+                x2 = _lib.aligned16(x2)
                 ws = self._acquire_workspace(B)
                 needs_graph = torch.is_grad_enabled() and (
                     x2.requires_grad or any(p.requires_grad for p in self._param_list))
@@ -636,7 +640,7 @@ class LinearModel(nn.Module):
                     self._release_workspace(ws)
             ws = self._acquire_workspace(B)
             if torch.is_grad_enabled() and (x2.requires_grad or any(p.requires_grad for p in self._param_list)):
-                return _LifterEvalFn.apply(x2, self, ws, *self._param_list)
+                return _LifterEvalFn.apply(_lib.aligned16(x2), self, ws, *self._param_list)
             try:
                 y = torch.empty(B, self.output_size, dtype=torch.float32, device=x2.device)
                 self._mark_wplanes()

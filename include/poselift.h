@@ -14,6 +14,12 @@
  *   - every call enqueues work on `stream` and returns; nothing synchronises.
  *   - return value: PL_OK (0) or a negative PLStatus; pl_last_error() gives the
  *     thread-local message.  Nothing throws across the ABI.
+ *   - alignment: a device pointer that a kernel behind an entry point reads or
+ *     writes 16 bytes at a time must be 16-byte aligned, else the call returns
+ *     PL_EINVAL before any launch with a message naming the argument ("x not
+ *     16-byte aligned").  A contiguous VIEW of a larger tensor (table + n * 34)
+ *     need not be: copy it first.  Pointers only element code touches may sit at
+ *     any 4-byte boundary.  DESIGN.md 3h lists every entry point and pointer.
  */
 #ifndef POSELIFT_H_
 #define POSELIFT_H_
@@ -29,7 +35,7 @@ extern "C" {
 
 typedef enum PLStatus {
   PL_OK = 0,
-  PL_EINVAL = -1,       /* null pointer / bad enum / misaligned arena            */
+  PL_EINVAL = -1,       /* null pointer / bad enum / misaligned pointer          */
   PL_ESHAPE = -2,       /* unsupported shape (hidden % 4 != 0, dims <= 0, ...)   */
   PL_EDTYPE = -3,       /* unsupported compute dtype                             */
   PL_EBATCH = -4,       /* B < 2 with training-mode BatchNorm (torch raises too) */
