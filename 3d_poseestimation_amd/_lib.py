@@ -74,6 +74,22 @@ class PLCriterion(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int32), ("group", ctypes.c_int32), ("beta", ctypes.c_float), ("weights", ctypes.c_void_p)]
 
 
+CRIT_HAS_SKELETON = 0x100
+RHO_L1, RHO_MSE = 0, 1
+SKELETON_MAX_JOINTS, SKELETON_MAX_BONES, SKELETON_MAX_PAIRS = 32, 31, 16
+
+
+class PLSkeleton(ctypes.Structure):
+    _fields_ = [("joints", ctypes.c_int32), ("bones", ctypes.c_int32), ("pairs", ctypes.c_int32), ("rho", ctypes.c_int32),
+                ("bone_child", ctypes.c_void_p), ("bone_parent", ctypes.c_void_p), ("pair_a", ctypes.c_void_p),
+                ("pair_b", ctypes.c_void_p), ("term_weights", ctypes.c_void_p), ("sub", ctypes.c_void_p), ("div", ctypes.c_void_p)]
+
+
+class PLSkeletonCriterion(PLCriterion):
+    """PLCriterion base; then the skeleton (poselift.h): byref() of one goes wherever a PLCriterion* does"""
+    _fields_ = [("skeleton", ctypes.POINTER(PLSkeleton))]
+
+
 class PLClipRecord(ctypes.Structure):
     _fields_ = [("norm", ctypes.c_float), ("coef", ctypes.c_float), ("finite", ctypes.c_uint32), ("skip", ctypes.c_uint32),
                 ("skipped", ctypes.c_uint64)]
@@ -151,6 +167,9 @@ SIGNATURES = {
                                              _c.POINTER(PLCriterion), _P, _P, _P, _c.POINTER(PLAdamWStep), _P]),
     "pl_pose_loss_scratch_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int64, _c.POINTER(PLCriterion)]),
     "pl_pose_loss_fwd_bwd": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _c.POINTER(PLCriterion), _c.c_float, _P, _P, _P, _P]),
+    "pl_bone_lengths": (_c.c_int, [_P, _c.c_int64, _c.c_int32, _c.POINTER(PLSkeleton), _P, _P]),
+    "pl_skeleton_terms_host": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int32, _c.POINTER(PLSkeleton), _c.c_float, _P, _P, _P]),
+    "pl_skeleton_abi_bytes": (_c.c_size_t, [_c.c_int]),
     "pl_mse_scratch_bytes": (_c.c_size_t, [_c.c_int64]),
     "pl_mse_fwd_bwd": (_c.c_int, [_P, _P, _c.c_int64, _c.c_float, _P, _P, _P, _P]),
     "pl_l1_scratch_bytes": (_c.c_size_t, [_c.c_int]),

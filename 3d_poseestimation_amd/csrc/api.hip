@@ -265,7 +265,10 @@ Ws plan(const PLDesc* d, int64_t B) {
   w.slabs = take(slab);
   w.outpart = take((size_t)std::max(colsum_chunks((int)B), skinny_in_chunks((int)B)) * d->out_dim * 4);
   w.dyout = take((size_t)B * d->out_dim * 4);                 // d loss / d y of the fused train step
-  w.mse = take(std::max(pl_mse_scratch_bytes(B * d->out_dim), (size_t)256));        // (64 partials of launch_small_mse)
+  // (64 partials of launch_small_mse.  The loss partials moved to the end of the workspace when the skeleton terms' partials
+  // joined them, below; these bytes stay reserved so that every other buffer keeps the address it had)
+  const size_t mse_bytes = std::max(pl_mse_scratch_bytes(B * d->out_dim), (size_t)256);
+  take(mse_bytes);
   w.dzp = w.amax = w.dzscale = 0;
   w.skp_out = take((size_t)skinny_in_chunks((int)B) * d->out_dim * H * 4);
   w.skp_in = take((size_t)skinny_in_chunks((int)B) * d->in_dim * H * 4);
@@ -281,6 +284,8 @@ Ws plan(const PLDesc* d, int64_t B) {
   }
   if (d->dtype == PL_F16X3 && B <= kThinGemmMaxM)
     for (int l = 0; l + 1 < w.L; ++l) w.sactp.push_back(take(w.act_bytes));           // two fp16 planes = 4 B per element
+  // the loss pass's partial sums and, behind them, those of the skeleton terms (skeleton.hip): one run for the finalisers
+  w.mse = take(mse_bytes + sk::kMaxGroups * sizeof(float));
   w.total = o;
 
   const int world = sync_world(d);
@@ -1503,8 +1508,8 @@ static int train_fwd_bwd_impl(const PLDesc* d, const float* x, const float* targ
   float* dy = f32(ws, w.dyout);
   const int L = 1 + 2 * d->num_stage;
   // the partial sums the loss pass of this route leaves in w.mse, and what their sum is multiplied by
-  const int n_part = w.loss == Loss::SmallMse ? small_loss_partials(cr, (int)B, d->out_dim)
-                     : w.loss == Loss::FromSlabs ? loss_partials(Crit{}, B, d->out_dim) : loss_partials(cr, B, d->out_dim);
+  int n_part = w.loss == Loss::SmallMse ? small_loss_partials(cr, (int)B, d->out_dim)
+               : w.loss == Loss::FromSlabs ? loss_partials(Crit{}, B, d->out_dim) : loss_partials(cr, B, d->out_dim);
   if (hi == L && w.loss == Loss::PartialOnly) {
     PL_TRY(pl_lifter_fwd_train(d, x, y, B, ws, ws_bytes, seed, step, nullptr, stream));
     PL_TRY(loss_partial_only(y, target, B, d->out_dim, cr, 1.0f, dy, f32(ws, w.mse), stream, "pl_lifter_train_fwd_bwd"));
@@ -1521,6 +1526,13 @@ static int train_fwd_bwd_impl(const PLDesc* d, const float* x, const float* targ
     } else
       PL_TRY(loss_partial_from_slabs(f32(ws, w.slabs), skinny_narrow_out_splits((int)B, H), (int)B, O, bias, target, cr, 1.0f, y,
                                      dy, f32(ws, w.mse), stream));
+  }
+  if (hi == L && cr.has_sk) {
+    // the skeleton terms, on every route the same launch: y, dy and the route's partials are in memory; it adds into dy and
+    // appends its own partials, which the route's finaliser sums with the rest
+    PL_TRY(launch_skeleton_terms(cr, y, target, B, d->out_dim, 1.0f, crit_inv_n(cr, B * d->out_dim), dy, f32(ws, w.mse) + n_part,
+                                 stream, "pl_lifter_train_fwd_bwd"));
+    n_part += skeleton_partials(B);
   }
   return bwd_impl(d, x, dy, B, ws, ws_bytes, nullptr, grads, stream, hi == L, hi == L ? L - 1 : hi, lo, false,
                   hi == L ? loss : nullptr, n_part, crit_inv_n(cr, B * d->out_dim), adam);

@@ -4,6 +4,7 @@
 // They replace, on the reference path, mse_loss (train_1.py:37,94) and loss_MPJPE (train_1.py:19-23).
 #include "pl_internal.h"
 #include "pose_table.h"
+#include "skeleton_terms.h"
 #include "streaming.h"
 
 namespace pl {
@@ -312,15 +313,21 @@ int launch_mpjpe(const char* fn, const float* pred, const float* tgt, int64_t B,
 int crit_resolve(const PLCriterion* crit, int64_t O, Crit& out, const char* who) {
   out = Crit{};
   if (!crit) return PL_OK;
-  if (crit->kind < PL_CRIT_MSE || crit->kind > PL_CRIT_MPJPE) PL_FAIL(PL_EINVAL, "%s: criterion kind %d", who, (int)crit->kind);
-  if (crit->kind == PL_CRIT_SMOOTH_L1 && !(crit->beta > 0.f && crit->beta <= 3.0e38f))
+  // (a kind outside the four, -1 included, is refused before anything past PLCriterion is read)
+  const int kind = crit->kind & PL_CRIT_HAS_SKELETON ? crit->kind & ~PL_CRIT_HAS_SKELETON : crit->kind;
+  if (kind < PL_CRIT_MSE || kind > PL_CRIT_MPJPE) PL_FAIL(PL_EINVAL, "%s: criterion kind %d", who, (int)crit->kind);
+  if (kind == PL_CRIT_SMOOTH_L1 && !(crit->beta > 0.f && crit->beta <= 3.0e38f))
     PL_FAIL(PL_EINVAL, "%s: smooth_l1 needs a finite beta > 0 (beta = 0 is l1), got %g", who, (double)crit->beta);
   if (crit->group < 1 || O % crit->group != 0)
     PL_FAIL(PL_ESHAPE, "%s: %lld outputs are not whole joints of %d coordinates", who, (long long)O, (int)crit->group);
-  if (crit->kind == PL_CRIT_MPJPE && crit->group > kCritMaxGroup)
+  if (kind == PL_CRIT_MPJPE && crit->group > kCritMaxGroup)
     PL_FAIL(PL_ESHAPE, "%s: mpjpe takes joints of at most %d coordinates, got %d", who, kCritMaxGroup, (int)crit->group);
-  out.kind = crit->kind; out.G = crit->group; out.w = crit->weights;
-  out.beta = crit->kind == PL_CRIT_SMOOTH_L1 ? crit->beta : 1.0f;
+  out.kind = kind; out.G = crit->group; out.w = crit->weights;
+  out.beta = kind == PL_CRIT_SMOOTH_L1 ? crit->beta : 1.0f;
+  if (const PLSkeleton* sk = crit_skeleton(crit)) {
+    PL_TRY(skeleton_check(sk, O, crit->group, who));
+    out.has_sk = true; out.sk = *sk;
+  }
   return PL_OK;
 }
 
@@ -378,7 +385,12 @@ int loss_fwd_bwd_tick(const float* pred, const float* tgt, int64_t B, int64_t O,
                       float* loss_out, void* scratch, uint64_t* tick, void* stream, const char* who) {
   if (!loss_out) PL_FAIL(PL_EINVAL, "%s: null pointer", who);
   PL_TRY(loss_partial_only(pred, tgt, B, O, c, grad_scale, dpred, scratch, stream, who));
-  hipLaunchKernelGGL(mse_final_kernel, dim3(1), dim3(NTHR), 0, (hipStream_t)stream, (const float*)scratch, loss_partials(c, B, O),
+  int np = loss_partials(c, B, O);
+  if (c.has_sk) {
+    PL_TRY(launch_skeleton_terms(c, pred, tgt, B, O, grad_scale, crit_inv_n(c, B * O), dpred, (float*)scratch + np, stream, who));
+    np += skeleton_partials(B);
+  }
+  hipLaunchKernelGGL(mse_final_kernel, dim3(1), dim3(NTHR), 0, (hipStream_t)stream, (const float*)scratch, np,
                      crit_inv_n(c, B * O), loss_out, tick);
   PL_CHECK_LAUNCH("mse_final");
   return PL_OK;
@@ -389,8 +401,8 @@ int loss_fwd_bwd_tick(const float* pred, const float* tgt, int64_t B, int64_t O,
 extern "C" size_t pl_mse_scratch_bytes(int64_t n) { return (size_t)pl::mse_blocks(n > 0 ? n : 1) * sizeof(float); }
 
 extern "C" size_t pl_pose_loss_scratch_bytes(int64_t B, int64_t O, const PLCriterion* crit) {
-  (void)crit;                       // (the grouped kind's B J joints need no more workgroups than B O elements do)
-  return pl_mse_scratch_bytes(B > 0 && O > 0 ? B * O : 1);
+  // (the grouped kind's B J joints need no more workgroups than B O elements do; the skeleton pass appends its partials)
+  return pl_mse_scratch_bytes(B > 0 && O > 0 ? B * O : 1) + (pl::crit_skeleton(crit) ? pl::sk::kMaxGroups * sizeof(float) : 0);
 }
 
 extern "C" int pl_mse_fwd_bwd(const float* pred, const float* tgt, int64_t n, float grad_scale,

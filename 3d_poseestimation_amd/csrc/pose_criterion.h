@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "../../include/poselift.h"
+#include "skeleton_terms.h"
 
 namespace pl {
 
@@ -27,7 +28,21 @@ struct Crit {
   int G = 1;                    // coordinates per joint; O = J * G
   float beta = 1.0f;
   const float* w = nullptr;     // J device floats, or NULL = all ones
+  bool has_sk = false;          // the skeleton terms (skeleton.hip) follow the loss pass: one launch more
+  PLSkeleton sk = {};           // ... a validated copy
 };
+// the skeleton a criterion carries (PL_CRIT_HAS_SKELETON in kind, PLSkeletonCriterion), or NULL
+inline const PLSkeleton* crit_skeleton(const PLCriterion* crit) {
+  return crit && (crit->kind & PL_CRIT_HAS_SKELETON) ? reinterpret_cast<const PLSkeletonCriterion*>(crit)->skeleton : nullptr;
+}
+// The skeleton pass on [B][O] tensors after the base loss pass wrote dpred and its partials: adds into dpred (NULL: the value
+// only) and writes skeleton_partials(B) partial sums to part, pre-scaled so that their sum times inv_n (the base criterion's
+// crit_inv_n) is lambda_bone L_bone + lambda_sym L_sym.  skeleton_terms_kernel's only launch site.
+int skeleton_partials(int64_t B);
+int launch_skeleton_terms(const Crit& c, const float* pred, const float* tgt, int64_t B, int64_t O, float grad_scale, float inv_n,
+                          float* dpred, float* part, void* stream, const char* who);
+// PL_ESHAPE / PL_EINVAL as include/poselift.h lists them; G = the criterion's group
+int skeleton_check(const PLSkeleton* sk, int64_t O, int G, const char* who);
 // crit == NULL: plain MSE.  PL_EINVAL: unknown kind, beta <= 0 or not finite on smooth_l1; PL_ESHAPE: group < 1, O % group,
 // group > kCritMaxGroup on mpjpe (a joint's coordinates live in one thread's registers).
 constexpr int kCritMaxGroup = 4;

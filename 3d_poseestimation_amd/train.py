@@ -325,9 +325,10 @@ class GraphedTrainStep:
         return self._x, self._y
 
     def _baked_ptrs(self):
-        w = self.criterion.joint_weights if self.criterion is not None else None
+        # (the criterion's joint weights and, with a skeleton, its tables, term_weights and transform)
+        crit = self.criterion.device_ptrs() if self.criterion is not None else ()
         return (self.model.flat_params.data_ptr(), self.opt._m.data_ptr() if self.opt._m is not None else 0,
-                self.opt._v.data_ptr() if self.opt._v is not None else 0, w.data_ptr() if w is not None else 0,
+                self.opt._v.data_ptr() if self.opt._v is not None else 0, crit,
                 self.opt._e.data_ptr() if self.opt._e is not None else 0)
 
     def __call__(self, y1, y2):

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define PL_VERSION 120 /* 0.1.20: + PLEma, PLAdamWStep.ema, pl_adamw_flat_planes_clip_ema, pl_swap_f32 (averaged weights kept inside the AdamW launches); 0.1.19: + pl_lifter_bwd_slab_rides (how many split-K sums of weight gradients ride in chained GEMM launches); 0.1.18: + PLPoseCrop, pl_pose_augment_gather_crop, pl_pose_augment_gather_crop_t, pl_pose_augment_host_crop, pl_pose_augment_host_crop_t, pl_frame_warp_gather_crop, pl_frame_warp_host_crop, pl_pose_crop_boxes, pl_pose_crop_boxes_host, pl_crop_poses, pl_crop_poses_host (person-centred crop from each row's 2-D pose inside the two batch launches); 0.1.17: + PLCriterion, pl_pose_loss_scratch_bytes, pl_pose_loss_fwd_bwd, pl_lifter_train_fwd_bwd_crit, pl_lifter_train_step_crit (the train step's criterion: mse, l1, smooth_l1, mpjpe, weighted per joint); 0.1.16: + pl_pose_prepare, pl_pose_stats, pl_pose_affine and their _host forms, pl_pose_stats_scratch_bytes, pl_pose_stats_chunk_rows, pl_pose_augment_gather_t, pl_pose_augment_host_t, pl_pose_errors_t, pl_mpjpe_accum_t (pose tables: prepare, statistics, the per-column transform and its way back inside the batch, error and metric launches); 0.1.15: + PLFrameWarp, pl_frame_warp_gather, pl_frame_warp_host (frame gather + resize + the pose augmentation's warp in one launch); 0.1.14: + PLPoseAug, pl_pose_augment_gather, pl_pose_augment_host (seeded train-time pose augmentation inside the batch gather); 0.1.13: + PLClipRecord, pl_grad_norm_scratch_bytes, pl_grad_norm_clip, pl_adamw_flat_clip, pl_adamw_flat_dev_clip, pl_adamw_flat_planes_clip (gradient-norm clipping and non-finite skip on the device); 0.1.12: + pl_pose_errors, pl_pose_errors_host, pl_pose_metrics_scratch_bytes, pl_pose_metrics_accum (evaluation: MPJPE / N-MPJPE / P-MPJPE, PCK counts, per group); 0.1.11: + pl_vit_*_bf16, pl_vit_bf16_pack (MyViT "bf16p": bf16 operand carriers written by their producers); 0.1.10: + pl_vit_* (the MyViT transformer lifter); 0.1.9: + pl_conv2d_planes_fwd_hw, pl_conv2d_planes_wgrad_hw (the stem on the planes GEMM); 0.1.8: + pl_lifter_train_step, pl_lifter_step_carries_adamw; 0.1.7: + pl_workspace_bitmap_format (small-batch layer kernels); 0.1.6: + pl_counter_add; 0.1.5: + pl_flip_pose_ex, pl_flip_w_nhwc (phase5 Flip branch); 0.1.4: + pl_planes_split_strided; 0.1.3: + pl_bn_join_bwd (0.1.2: operand-plane outputs of the BatchNorm / join kernels, pl_gemm_planes_raw) */
+#define PL_VERSION 121 /* 0.1.21: + PLSkeleton, PLSkeletonCriterion, PL_CRIT_HAS_SKELETON, pl_bone_lengths, pl_skeleton_terms_host, pl_skeleton_abi_bytes (bone-length and left/right symmetry terms of the criterion, one launch more per step); 0.1.20: + PLEma, PLAdamWStep.ema, pl_adamw_flat_planes_clip_ema, pl_swap_f32 (averaged weights kept inside the AdamW launches); 0.1.19: + pl_lifter_bwd_slab_rides (how many split-K sums of weight gradients ride in chained GEMM launches); 0.1.18: + PLPoseCrop, pl_pose_augment_gather_crop, pl_pose_augment_gather_crop_t, pl_pose_augment_host_crop, pl_pose_augment_host_crop_t, pl_frame_warp_gather_crop, pl_frame_warp_host_crop, pl_pose_crop_boxes, pl_pose_crop_boxes_host, pl_crop_poses, pl_crop_poses_host (person-centred crop from each row's 2-D pose inside the two batch launches); 0.1.17: + PLCriterion, pl_pose_loss_scratch_bytes, pl_pose_loss_fwd_bwd, pl_lifter_train_fwd_bwd_crit, pl_lifter_train_step_crit (the train step's criterion: mse, l1, smooth_l1, mpjpe, weighted per joint); 0.1.16: + pl_pose_prepare, pl_pose_stats, pl_pose_affine and their _host forms, pl_pose_stats_scratch_bytes, pl_pose_stats_chunk_rows, pl_pose_augment_gather_t, pl_pose_augment_host_t, pl_pose_errors_t, pl_mpjpe_accum_t (pose tables: prepare, statistics, the per-column transform and its way back inside the batch, error and metric launches); 0.1.15: + PLFrameWarp, pl_frame_warp_gather, pl_frame_warp_host (frame gather + resize + the pose augmentation's warp in one launch); 0.1.14: + PLPoseAug, pl_pose_augment_gather, pl_pose_augment_host (seeded train-time pose augmentation inside the batch gather); 0.1.13: + PLClipRecord, pl_grad_norm_scratch_bytes, pl_grad_norm_clip, pl_adamw_flat_clip, pl_adamw_flat_dev_clip, pl_adamw_flat_planes_clip (gradient-norm clipping and non-finite skip on the device); 0.1.12: + pl_pose_errors, pl_pose_errors_host, pl_pose_metrics_scratch_bytes, pl_pose_metrics_accum (evaluation: MPJPE / N-MPJPE / P-MPJPE, PCK counts, per group); 0.1.11: + pl_vit_*_bf16, pl_vit_bf16_pack (MyViT "bf16p": bf16 operand carriers written by their producers); 0.1.10: + pl_vit_* (the MyViT transformer lifter); 0.1.9: + pl_conv2d_planes_fwd_hw, pl_conv2d_planes_wgrad_hw (the stem on the planes GEMM); 0.1.8: + pl_lifter_train_step, pl_lifter_step_carries_adamw; 0.1.7: + pl_workspace_bitmap_format (small-batch layer kernels); 0.1.6: + pl_counter_add; 0.1.5: + pl_flip_pose_ex, pl_flip_w_nhwc (phase5 Flip branch); 0.1.4: + pl_planes_split_strided; 0.1.3: + pl_bn_join_bwd (0.1.2: operand-plane outputs of the BatchNorm / join kernels, pl_gemm_planes_raw) */
 
 typedef enum PLStatus {
   PL_OK = 0,
@@ -301,6 +301,58 @@ int pl_lifter_train_fwd_bwd_crit(const PLDesc* d, const float* x, const float* t
 int pl_lifter_train_step_crit(const PLDesc* d, const float* x, const float* target, int64_t B, void* workspace,
                               size_t workspace_bytes, uint64_t seed, uint64_t step, const PLCriterion* crit, float* y,
                               float* loss, float* flat_grads, const PLAdamWStep* opt, void* stream);
+
+/* ---- the skeleton terms of the criterion: bone lengths and left/right symmetry (PARITY UNPINNED: the reference has no
+ * such loss; the oracle is torch autograd in fp64) ----
+ * A skeleton on J joints (2 <= J <= 32) of G coordinates (G = the criterion's group, 2 or 3; J G = O) has K bones (c_k, p_k),
+ * child and parent joint, 1 <= K <= 31, and S >= 0 symmetric pairs (k_L, k_R) of bone indices, S <= 16.  With the optional
+ * inverse transform (sub, div, each [J G]: the numbers PoseTransform.invert uses) both tensors are first taken to raw
+ * units, P = pred div + sub, T = tgt div + sub; without one P = pred, T = tgt.  lh_k = ||P_c - P_p||, l_k = ||T_c - T_p||,
+ *
+ *   L_bone = 1 / (B K) sum_{b,k} rho(lh_k - l_k)         L_sym = 1 / (B S) sum_{b,(kL,kR)} rho(lh_kL - lh_kR)   (prediction only)
+ *   loss   = the base criterion + lambda_bone L_bone + lambda_sym L_sym,          rho(e) = |e| (l1) or e^2 (mse)
+ *
+ * d lh / d P_c = (P_c - P_p) / lh, 0 for the whole bone where lh == 0 (mpjpe's rule); rho'(0) = 0 for l1; the chain rule
+ * through a transform multiplies by div per coordinate (a div == 0 column gets gradient 0); grad_scale multiplies everything.
+ * The two lambdas are read by the kernel from device memory (term_weights): a weight schedule needs no re-capture of a graph,
+ * and a lambda of 0 contributes exactly 0 to loss and gradient.  The terms cost one launch more per call; all sums are in a
+ * fixed order without atomics.  Indices are the caller's contract: nothing here checks them against J or K,
+ * nor that a bone joins two different joints and a pair two different bones.
+ * In fp32, as computed (every operation rounded once; s = grad_scale):
+ *   P = fl(fl(pred * div) + sub);  d_g = P_c,g - P_p,g;  ss = d_0 d_0, then fmaf(d_g, d_g, ss);  lh = sqrtf(ss)
+ *   e = lh - l (pairs: lh_a - lh_b);  u_k = rho'(e) wb with wb = lambda_bone * cb, cb = s / (float)(B K): l1 +-wb or 0, mse
+ *   e * (2 wb); then for each pair in order v = rho'(e) ws (ws = lambda_sym * cs, cs = s / (float)(B S)), u_a += v, u_b -= v
+ *   r_k = lh_k == 0 ? 0 : u_k / lh_k;  x = d_g * r_k;  bones in order: g[c] += x [* div_c], g[p] -= x [* div_p];  dpred += g
+ * Non-finite values come out where torch's do: a NaN coordinate of pred makes the loss NaN and the gradient NaN on every
+ * coordinate of both joints of each bone that touches it, and leaves joints of clean bones and other poses alone.
+ *
+ * A criterion carries a skeleton as an extension of PLCriterion: set PL_CRIT_HAS_SKELETON in `kind` of a
+ * PLSkeletonCriterion's base and pass &sc.base wherever a PLCriterion* goes.  Without the flag nothing past PLCriterion is
+ * read, so every existing caller -- and a zero-initialised or NULL criterion -- behaves exactly as before.
+ * PL_ESHAPE: joints * group != O, group not 2 or 3, joints, bones or pairs out of range; PL_EINVAL: a null table or
+ * term_weights, an unknown rho, only one of sub / div. */
+#define PL_CRIT_HAS_SKELETON 0x100
+typedef struct PLSkeleton {
+  int32_t joints, bones, pairs, rho;       /* rho: 0 = l1, 1 = mse */
+  const int32_t* bone_child; const int32_t* bone_parent;       /* device, [bones] */
+  const int32_t* pair_a; const int32_t* pair_b;                /* device, [pairs] bone indices, or NULL */
+  const float* term_weights;                                   /* device, {lambda_bone, lambda_sym} */
+  const float* sub; const float* div;                          /* device, [joints * group], or both NULL */
+} PLSkeleton;
+typedef struct PLSkeletonCriterion {
+  PLCriterion base;                        /* base.kind = a PLCriterionKind | PL_CRIT_HAS_SKELETON */
+  const PLSkeleton* skeleton;              /* NULL = none */
+} PLSkeletonCriterion;
+/* lengths [B][K] of poses [B][J][group] (raw units when the skeleton has a transform); reads only the bone table and
+ * sub / div of *sk (pairs, rho and term_weights may be anything). */
+int pl_bone_lengths(const float* poses, int64_t B, int32_t group, const PLSkeleton* sk, float* lengths, void* stream);
+/* Test hooks.  pl_skeleton_terms_host: the same inline arithmetic compiled for the CPU -- every pointer, those inside *sk
+ * included, is a host pointer.  *loss = lambda_bone L_bone + lambda_sym L_sym; dpred ([B][J G], may be NULL) is ADDED INTO;
+ * lengths ([B][K], may be NULL) receives the prediction's bone lengths.
+ * pl_skeleton_abi_bytes: sizeof of PLCriterion (0), PLSkeleton (1), PLSkeletonCriterion (2) as the library was compiled. */
+int pl_skeleton_terms_host(const float* pred, const float* tgt, int64_t B, int32_t group, const PLSkeleton* sk,
+                           float grad_scale, float* dpred, float* loss, float* lengths);
+size_t pl_skeleton_abi_bytes(int which);
 
 /* The 3-D head forward on NHWC logits [B][H][W][J*64] (depth_dim 64, the conv path's layout): same
  * coords [B*J][3] and stats [B*J][5] as pl_softargmax_fwd(ncoord 3, centred 1).  Model.py:94-133. */
