@@ -12,10 +12,10 @@ from .train import (crop_poses, cycle_step, epoch_mpjpe_mm, eval_step, flip_aver
 from .heads import (gaussian_heatmap, heatmap_law, soft_argmax_2d, soft_argmax_2d_hm, soft_argmax_3d,  # noqa: F401
                     soft_argmax_3d_hm, soft_argmax_3d_nhwc, soft_argmax_3d_nhwc_hm)
 from .losses import TriangleLoss, heatmap_mse, l1_loss, l1_terms  # noqa: F401
-from .criterion import H36M_SKELETON, PoseCriterion, Skeleton, bone_lengths  # noqa: F401
+from .criterion import H36M_SKELETON, PoseCriterion, Skeleton, bone_lengths, normalize_row_weights  # noqa: F401
 from .metrics import AUC_THRESHOLDS, PoseMetrics, pose_errors, procrustes_align  # noqa: F401
 from .backbone import Model_2D, Model_3D, ResNet  # noqa: F401
-from .data import (FrameFeeder, PersonCrop, PoseAugment, PoseFeeder, augment_frames, augment_poses, crop_boxes,  # noqa: F401
+from .data import (FrameFeeder, PersonCrop, PoseAugment, PoseFeeder, augment_frames, augment_poses, crop_boxes, gather_row_weights,  # noqa: F401
                    epoch_indices)
 from .pose_table import H36M_17_OF_32, PoseStats, PoseTransform, pose_stats, prepare_poses  # noqa: F401
 from .vit import MyViT  # noqa: F401

@@ -90,6 +90,14 @@ class PLSkeletonCriterion(PLCriterion):
     _fields_ = [("skeleton", ctypes.POINTER(PLSkeleton))]
 
 
+CRIT_HAS_ROW_WEIGHTS = 0x200
+
+
+class PLRowWeightsCriterion(PLSkeletonCriterion):
+    """PLSkeletonCriterion sc; then row_weights (poselift.h): byref() of one goes wherever a PLCriterion* does"""
+    _fields_ = [("row_weights", ctypes.c_void_p)]
+
+
 class PLClipRecord(ctypes.Structure):
     _fields_ = [("norm", ctypes.c_float), ("coef", ctypes.c_float), ("finite", ctypes.c_uint32), ("skip", ctypes.c_uint32),
                 ("skipped", ctypes.c_uint64)]
@@ -170,6 +178,7 @@ SIGNATURES = {
     "pl_bone_lengths": (_c.c_int, [_P, _c.c_int64, _c.c_int32, _c.POINTER(PLSkeleton), _P, _P]),
     "pl_skeleton_terms_host": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int32, _c.POINTER(PLSkeleton), _c.c_float, _P, _P, _P]),
     "pl_skeleton_abi_bytes": (_c.c_size_t, [_c.c_int]),
+    "pl_criterion_abi_bytes": (_c.c_size_t, [_c.c_int]),
     "pl_mse_scratch_bytes": (_c.c_size_t, [_c.c_int64]),
     "pl_mse_fwd_bwd": (_c.c_int, [_P, _P, _c.c_int64, _c.c_float, _P, _P, _P, _P]),
     "pl_l1_scratch_bytes": (_c.c_size_t, [_c.c_int]),
@@ -252,6 +261,8 @@ SIGNATURES = {
     "pl_nhwc_to_nchw": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _c.c_int64, _P, _P]),
     "pl_gather_rows2": (_c.c_int, [_P, _c.c_int64, _P, _c.c_int64, _P, _c.c_int64, _c.c_int64, _P, _P, _P]),
     "pl_pose_augment_gather": (_c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_int64, _P, _P, _c.POINTER(PLPoseAug), _c.c_uint64, _P]),
+    "pl_row_weights_gather": (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int64, _c.c_int64, _P, _c.POINTER(PLPoseAug), _c.c_uint64, _P]),
+    "pl_row_weights_gather_host": (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int64, _c.c_int64, _P, _c.POINTER(PLPoseAug), _c.c_uint64]),
     "pl_pose_augment_host": (_c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_int64, _P, _P, _c.POINTER(PLPoseAug), _c.c_uint64]),
     "pl_pose_augment_gather_t": (_c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_int64, _P, _P, _c.POINTER(PLPoseAug), _c.c_uint64,
                                             _P, _P, _P, _P, _P]),

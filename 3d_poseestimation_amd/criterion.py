@@ -119,11 +119,38 @@ def bone_lengths(poses, skeleton, denorm=None):
     return out
 
 
+def normalize_row_weights(row_weights):
+    """rw * (B J / sum rw), zeros where sum rw == 0: with these weights the criterion's fixed 1 / (B O) (mpjpe: 1 / (B J))
+    normaliser gives the masked / weighted MEAN -- the loss divided by the total weight instead of the element count.
+    Plain torch ops on the tensor's device; nothing synchronises.  (Under data parallelism each rank normalises by its own
+    rows' sum.)"""
+    rw = row_weights.float()
+    total = rw.sum()
+    scale = torch.where(total == 0, torch.zeros_like(total), rw.numel() / total)
+    return rw * scale
+
+
+def check_row_weights(row_weights, B, J, device, who="PoseCriterion"):
+    """The (B, J) fp32 contiguous device tensor the library reads, from what a caller passed: ValueError on a wrong shape or
+    requires_grad (there is no gradient with respect to the weights); a non-fp32 tensor (a bool mask) is converted with
+    .float() and a non-contiguous one with .contiguous() -- either is a copy, so later in-place edits of the caller's tensor
+    are not seen."""
+    if not torch.is_tensor(row_weights):
+        raise TypeError(f"{who}: row_weights must be a tensor")
+    if row_weights.requires_grad:
+        raise ValueError(f"{who}: row_weights requires grad, and the criterion has no gradient with respect to its weights")
+    if tuple(row_weights.shape) != (B, J):
+        raise ValueError(f"{who}: row_weights has shape {tuple(row_weights.shape)}, the batch ({B}, {J}) = (poses, joints)")
+    if row_weights.device != device:
+        raise ValueError(f"{who}: row_weights on {row_weights.device}, the tensors on {device}")
+    return row_weights.float().contiguous()
+
+
 class _PoseLossFn(torch.autograd.Function):
     """value and gradient in the same launch pair (pl_pose_loss_fwd_bwd), like train._MSEFn"""
 
     @staticmethod
-    def forward(ctx, pred, tgt, crit):
+    def forward(ctx, pred, tgt, crit, rw=None):
         _lib.require_device_tensor(pred, "pred")
         _lib.require_device_tensor(tgt, "target")
         B = pred.shape[0]
@@ -133,7 +160,7 @@ class _PoseLossFn(torch.autograd.Function):
         loss = torch.empty((), dtype=torch.float32, device=pred.device)
         L = _lib.lib()
         with _lib.on_device(pred.device):
-            st = crit.struct(O, pred.device)
+            st = crit.struct(O, pred.device, rw)
             scratch = torch.empty(L.pl_pose_loss_scratch_bytes(B, O, ctypes.byref(st)), dtype=torch.uint8, device=pred.device)
             rc = L.pl_pose_loss_fwd_bwd(pred.data_ptr(), tgt.data_ptr(), B, O, ctypes.byref(st), 1.0,
                                         dpred.data_ptr() if need else None, loss.data_ptr(), scratch.data_ptr(),
@@ -146,12 +173,12 @@ class _PoseLossFn(torch.autograd.Function):
     def backward(ctx, g):
         d = ctx.dpred
         ctx.dpred = None
-        return (d.mul_(g) if d is not None else None), None, None
+        return (d.mul_(g) if d is not None else None), None, None, None
 
 
 class PoseCriterion(torch.nn.Module):
     """crit = PoseCriterion(kind="mse", beta=1.0, joint_weights=None, coords=3, skeleton=None, bone_weight=0.0,
-    symmetry_weight=0.0, bone_rho="l1", denorm=None); loss = crit(pred, target).
+    symmetry_weight=0.0, bone_rho="l1", denorm=None); loss = crit(pred, target, row_weights=None).
 
     kind           "mse" | "l1" | "smooth_l1" | "mpjpe"
     beta           smooth_l1's threshold, > 0 (beta = 0 is "l1"; Huber(delta) = delta * smooth_l1(beta=delta))
@@ -169,7 +196,19 @@ class PoseCriterion(torch.nn.Module):
 
     pred, target: (B, J * coords) or (B, J, coords) fp32 on the device.  The mean is over B * J * coords elements, for
     "mpjpe" over B * J joints; the weights need not sum to anything.  Pass it as train_step(..., criterion=crit),
-    GraphedTrainStep(..., criterion=crit), eval_step(..., criterion=crit) or as a GraphedModuleStep's loss_fn."""
+    GraphedTrainStep(..., criterion=crit), eval_step(..., criterion=crit) or as a GraphedModuleStep's loss_fn.
+
+    row_weights    (B, J) on the tensors' device, or None: the weight of joint j of POSE b -- a visibility mask, a detector's
+                   or a pseudo-label's confidence, a per-row weight broadcast over the joints, zeros on padding rows.  The
+                   effective weight is row_weights[b, j], times joint_weights[j] when there are both (one fp32 product);
+                   it stands where the joint weight stands, on every route of the fused step, in the same launches.  The
+                   normaliser stays 1 / (B * J * coords) (mpjpe: 1 / (B * J)): normalize_row_weights(rw) rescales the
+                   weights so that the loss is the weighted mean.  Not differentiable (requires_grad raises ValueError).
+                   fp32 contiguous tensors are read in place; any other dtype (a bool mask) is converted with .float(),
+                   which is a copy.  Not with a skeleton (ValueError): the bone terms have no per-pose weights yet.
+                   Weights MULTIPLY, as joint_weights do and as torch's (w * elementwise).mean() does: 0 * NaN = NaN, so a
+                   zero weight does not hide a non-finite prediction or target.  Targets that code "missing" as NaN need
+                   target = torch.nan_to_num(target) next to the mask that zeroes those joints."""
 
     def __init__(self, kind="mse", beta=1.0, joint_weights=None, coords=3, skeleton=None, bone_weight=0.0, symmetry_weight=0.0,
                  bone_rho="l1", denorm=None):
@@ -239,11 +278,20 @@ class PoseCriterion(torch.nn.Module):
                                      "move the criterion with .to(device)")
         return t.data_ptr() if t is not None else None
 
-    def struct(self, O, device):
+    def struct(self, O, device, row_weights=None):
         """The _lib.PLCriterion of a call on [B][O] tensors of `device` (it points into the buffers: keep self alive); with a
-        skeleton the _lib.PLSkeletonCriterion that extends it."""
+        skeleton the _lib.PLSkeletonCriterion that extends it; with row_weights (what check_row_weights returned: keep it
+        alive as well) the _lib.PLRowWeightsCriterion."""
         self.check_outputs(O)
+        if row_weights is not None and self.skeleton is not None:
+            raise ValueError("PoseCriterion: row_weights with a skeleton are not built (the bone terms have no per-pose weights)")
         w = self._on(self.joint_weights, "joint_weights", device, torch.float32)
+        if row_weights is not None:
+            if row_weights.dim() != 2 or row_weights.shape[1] != O // self.coords:
+                raise ValueError(f"PoseCriterion: row_weights {tuple(row_weights.shape)} for {O // self.coords} joints")
+            st = _lib.PLRowWeightsCriterion(KINDS[self.kind] | _lib.CRIT_HAS_ROW_WEIGHTS, self.coords, self.beta, w)
+            st.row_weights = self._on(row_weights, "row_weights", device, torch.float32)
+            return st
         if self.skeleton is None:
             return _lib.PLCriterion(KINDS[self.kind], self.coords, self.beta, w)
         if self.term_weights is None or self.term_weights.numel() != 2:
@@ -257,7 +305,16 @@ class PoseCriterion(torch.nn.Module):
         st.skeleton = ctypes.pointer(sk)          # (the struct keeps sk alive)
         return st
 
-    def forward(self, pred, target):
+    def row_weights_for(self, row_weights, B, O, device):
+        """check_row_weights against a (B, O) batch of this criterion (None stays None); ValueError with a skeleton"""
+        if row_weights is None:
+            return None
+        if self.skeleton is not None:
+            raise ValueError("PoseCriterion: row_weights with a skeleton are not built (the bone terms have no per-pose weights)")
+        self.check_outputs(O)
+        return check_row_weights(row_weights, B, O // self.coords, device)
+
+    def forward(self, pred, target, row_weights=None):
         if pred.shape != target.shape:
             raise ValueError(f"PoseCriterion: shapes differ: {tuple(pred.shape)} vs {tuple(target.shape)}")
         if pred.dim() == 3 and pred.shape[2] != self.coords:
@@ -265,4 +322,5 @@ class PoseCriterion(torch.nn.Module):
         if pred.dim() not in (2, 3) or pred.shape[0] < 1:
             raise ValueError("PoseCriterion expects (B, J * coords) or (B, J, coords) tensors, B >= 1")
         self.check_outputs(pred.numel() // pred.shape[0])
-        return _PoseLossFn.apply(pred.contiguous(), target.contiguous(), self)
+        rw = self.row_weights_for(row_weights, pred.shape[0], pred.numel() // pred.shape[0], pred.device)
+        return _PoseLossFn.apply(pred.contiguous(), target.contiguous(), self, rw)

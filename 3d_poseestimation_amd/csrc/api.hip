@@ -1502,7 +1502,7 @@ static int train_fwd_bwd_impl(const PLDesc* d, const float* x, const float* targ
   if (B <= 0) PL_FAIL(PL_ESHAPE, "pl_lifter_train_fwd_bwd: B=%lld", (long long)B);
   PL_TRY(check_range(d, hi, lo, "pl_lifter_train_fwd_bwd"));
   Crit cr;
-  PL_TRY(crit_resolve(crit, d->out_dim, cr, "pl_lifter_train_fwd_bwd"));
+  PL_TRY(crit_resolve(crit, B, d->out_dim, cr, "pl_lifter_train_fwd_bwd"));
   const Ws w = plan(d, B);
   PL_TRY(check_ws(w, ws, ws_bytes));
   float* dy = f32(ws, w.dyout);

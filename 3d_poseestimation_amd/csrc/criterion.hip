@@ -11,9 +11,10 @@ namespace pl {
 namespace {
 
 // ---- the criterion (mean) forward + backward: MSE, and the other pointwise kinds of pose_criterion.h ------------------------
-// C: the criterion type, W: per-joint weights (k.w[(i mod O) / G]).  <Pointwise<PL_CRIT_MSE>, false> is the MSE kernel as
-// it always was: d, fmaf(d, d, acc), d * coef, block_sum.
-template <class C, bool W>
+// C: the criterion type, W: the weights (pose_criterion.h) -- kWJoint: k.w[(i mod O) / G]; kWRow: k.rw[i / G], loaded with
+// the element's operands (n <= INT32_MAX there), times k.w[...] when there are joint weights too.
+// <Pointwise<PL_CRIT_MSE>, kWNone> is the MSE kernel as it always was: d, fmaf(d, d, acc), d * coef, block_sum.
+template <class C, int W>
 __global__ __launch_bounds__(NTHR) void mse_partial_kernel(const float* __restrict__ pred,
                                                            const float* __restrict__ tgt, int64_t n,
                                                            CritK k, float* __restrict__ dpred,
@@ -22,8 +23,14 @@ __global__ __launch_bounds__(NTHR) void mse_partial_kernel(const float* __restri
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   float acc = 0.f;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    float rwv = 0.f, wj = 0.f;                          // (kWRow: both weight loads issued with pred and tgt, before d)
+    if constexpr (W == kWRow) { rwv = k.rw[(int)i / k.G]; wj = joint_weight_or_one(k, (int)i % k.O / k.G); }
     const float d = pred[i] - tgt[i];
-    if constexpr (W) {
+    if constexpr (W == kWRow) {
+      const float w = wj * rwv;
+      acc = C::add_w(acc, d, w, k);
+      if (dpred) dpred[i] = C::grad(d, k) * w;
+    } else if constexpr (W == kWJoint) {
       const float w = k.w[(int)(i % k.O) / k.G];
       acc = C::add_w(acc, d, w, k);
       if (dpred) dpred[i] = C::grad(d, k) * w;
@@ -38,8 +45,8 @@ __global__ __launch_bounds__(NTHR) void mse_partial_kernel(const float* __restri
 
 // The grouped kind (mpjpe) has an element map of its own: a thread takes whole joints -- the G coordinates of joint i are
 // elements i G .. i G + G - 1 of the flat [B][O] tensors -- so no joint is shared between threads, let alone workgroups.
-// nj = B J joints, J joints per row (the weight of joint i is k.w[i mod J]).
-template <int G, bool W>
+// nj = B J joints, J joints per row (the weight of joint i is k.w[i mod J]; kWRow: k.rw[i], times k.w[i mod J] if any).
+template <int G, int W>
 __global__ __launch_bounds__(NTHR) void mpjpe_loss_partial_kernel(const float* __restrict__ pred,
                                                                   const float* __restrict__ tgt, int64_t nj, int J,
                                                                   CritK k, float* __restrict__ dpred,
@@ -51,9 +58,12 @@ __global__ __launch_bounds__(NTHR) void mpjpe_loss_partial_kernel(const float* _
     float p[G], t[G], d[G], g[G];
 #pragma unroll
     for (int c = 0; c < G; ++c) { p[c] = pred[i * G + c]; t[c] = tgt[i * G + c]; }
-    const float w = W ? k.w[(int)(i % J)] : 1.f;
+    float w, wj = 1.f;
+    if constexpr (W == kWRow) { w = k.rw[i]; wj = joint_weight_or_one(k, (int)i % J); }
+    else w = W ? k.w[(int)(i % J)] : 1.f;
 #pragma unroll
     for (int c = 0; c < G; ++c) d[c] = p[c] - t[c];
+    if constexpr (W == kWRow) w = wj * w;
     const float r = joint_norm_grad<G>(d, W ? k.coef * w : k.coef, g);
     acc = W ? fmaf(w, r, acc) : acc + r;
     if (dpred) {
@@ -68,8 +78,9 @@ __global__ __launch_bounds__(NTHR) void mpjpe_loss_partial_kernel(const float* _
 // mse_partial_kernel with pred[i] formed on the fly from the output Linear's split-K slabs (part[s][r][64 padded columns]) and
 // stored: y[i] = bias[n] + slabs in order -- skinny_narrow_out_reduce_kernel's sum -- then the same d, fmaf and block_sum on the
 // same thread -> element map: y, dpred and the partials equal the two-launch route's bit for bit.  NS slabs, N columns.
-// C, W: the criterion and its weights as in mse_partial_kernel (the weight of each element loaded with its slabs).
-template <int NS, int N, class C, bool W>
+// C, W: the criterion and its weights as in mse_partial_kernel (the weight of each element loaded with its slabs; kWRow:
+// k.rw[r J + c / G] and, with joint weights, k.w[c / G], both in that first group of loads, their product formed once).
+template <int NS, int N, class C, int W>
 __global__ __launch_bounds__(NTHR) void mse_partial_from_slabs_kernel(const float* __restrict__ part, int B,
                                                                       const float* __restrict__ bias,
                                                                       const float* __restrict__ tgt, CritK k,
@@ -81,7 +92,7 @@ __global__ __launch_bounds__(NTHR) void mse_partial_from_slabs_kernel(const floa
   const size_t slab = (size_t)B * 64;
   float acc = 0.f;
   for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i0 < n; i0 += 4 * stride) {
-    float u[4][NS], t[4], bs[4], wq[4];
+    float u[4][NS], t[4], bs[4], wq[4], wj[4];
     int64_t idx[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {                       // up to four elements of this thread: every load issued first
@@ -93,7 +104,8 @@ __global__ __launch_bounds__(NTHR) void mse_partial_from_slabs_kernel(const floa
       for (int s = 0; s < NS; ++s) u[q][s] = ok ? p[(size_t)s * slab] : 0.f;
       t[q] = ok ? tgt[idx[q]] : 0.f;
       bs[q] = (ok && bias) ? bias[c] : 0.f;
-      if constexpr (W) wq[q] = k.w[c / k.G];
+      if constexpr (W == kWRow) { wq[q] = ok ? k.rw[r * (N / k.G) + c / k.G] : 0.f; wj[q] = joint_weight_or_one(k, c / k.G); }
+      else if constexpr (W == kWJoint) wq[q] = k.w[c / k.G];
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -103,7 +115,8 @@ __global__ __launch_bounds__(NTHR) void mse_partial_from_slabs_kernel(const floa
       for (int s = 0; s < NS; ++s) a += u[q][s];
       y[idx[q]] = a;
       const float d = a - t[q];
-      if constexpr (W) {
+      if constexpr (W == kWRow) wq[q] = wj[q] * wq[q];
+      if constexpr (W != kWNone) {
         acc = C::add_w(acc, d, wq[q], k);
         dpred[idx[q]] = C::grad(d, k) * wq[q];
       } else {
@@ -118,7 +131,7 @@ __global__ __launch_bounds__(NTHR) void mse_partial_from_slabs_kernel(const floa
 
 // The grouped kind on the slabs, with its own element map: a thread takes whole joints (two per pass; the 2 G NS slab
 // loads, the targets, the biases and the weights all issued before the first add), y[i] = bias + slabs in the same order.
-template <int NS, int N, int G, bool W>
+template <int NS, int N, int G, int W>
 __global__ __launch_bounds__(NTHR) void mpjpe_partial_from_slabs_kernel(const float* __restrict__ part, int B,
                                                                         const float* __restrict__ bias,
                                                                         const float* __restrict__ tgt, CritK k,
@@ -132,7 +145,7 @@ __global__ __launch_bounds__(NTHR) void mpjpe_partial_from_slabs_kernel(const fl
   const size_t slab = (size_t)B * 64;
   float acc = 0.f;
   for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i0 < nj; i0 += Q * stride) {
-    float u[Q][G][NS], t[Q][G], bs[Q][G], wq[Q];
+    float u[Q][G][NS], t[Q][G], bs[Q][G], wq[Q], wj[Q];
     int64_t idx[Q];
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
@@ -147,7 +160,8 @@ __global__ __launch_bounds__(NTHR) void mpjpe_partial_from_slabs_kernel(const fl
         t[q][c] = ok ? tgt[idx[q] * G + c] : 0.f;
         bs[q][c] = (ok && bias) ? bias[j * G + c] : 0.f;
       }
-      wq[q] = W ? k.w[j] : 1.f;
+      if constexpr (W == kWRow) { wq[q] = ok ? k.rw[idx[q]] : 0.f; wj[q] = joint_weight_or_one(k, j); }
+      else wq[q] = W ? k.w[j] : 1.f;
     }
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
@@ -161,6 +175,7 @@ __global__ __launch_bounds__(NTHR) void mpjpe_partial_from_slabs_kernel(const fl
         y[idx[q] * G + c] = a;
         d[c] = a - t[q][c];
       }
+      if constexpr (W == kWRow) wq[q] = wj[q] * wq[q];
       const float r = joint_norm_grad<G>(d, W ? k.coef * wq[q] : k.coef, g);
       acc = W ? fmaf(wq[q], r, acc) : acc + r;
 #pragma unroll
@@ -310,11 +325,12 @@ int launch_mpjpe(const char* fn, const float* pred, const float* tgt, int64_t B,
 
 }  // namespace
 
-int crit_resolve(const PLCriterion* crit, int64_t O, Crit& out, const char* who) {
+int crit_resolve(const PLCriterion* crit, int64_t B, int64_t O, Crit& out, const char* who) {
   out = Crit{};
   if (!crit) return PL_OK;
-  // (a kind outside the four, -1 included, is refused before anything past PLCriterion is read)
-  const int kind = crit->kind & PL_CRIT_HAS_SKELETON ? crit->kind & ~PL_CRIT_HAS_SKELETON : crit->kind;
+  // (a kind outside the four, -1 included, is refused before anything past PLCriterion is read: no negative kind has a flag)
+  constexpr int flags = PL_CRIT_HAS_SKELETON | PL_CRIT_HAS_ROW_WEIGHTS;
+  const int kind = crit->kind > 0 && (crit->kind & flags) ? crit->kind & ~flags : crit->kind;
   if (kind < PL_CRIT_MSE || kind > PL_CRIT_MPJPE) PL_FAIL(PL_EINVAL, "%s: criterion kind %d", who, (int)crit->kind);
   if (kind == PL_CRIT_SMOOTH_L1 && !(crit->beta > 0.f && crit->beta <= 3.0e38f))
     PL_FAIL(PL_EINVAL, "%s: smooth_l1 needs a finite beta > 0 (beta = 0 is l1), got %g", who, (double)crit->beta);
@@ -324,6 +340,13 @@ int crit_resolve(const PLCriterion* crit, int64_t O, Crit& out, const char* who)
     PL_FAIL(PL_ESHAPE, "%s: mpjpe takes joints of at most %d coordinates, got %d", who, kCritMaxGroup, (int)crit->group);
   out.kind = kind; out.G = crit->group; out.w = crit->weights;
   out.beta = kind == PL_CRIT_SMOOTH_L1 ? crit->beta : 1.0f;
+  if (crit->kind > 0 && (crit->kind & PL_CRIT_HAS_ROW_WEIGHTS)) {
+    if (!(out.rw = crit_row_weights(crit))) PL_FAIL(PL_EINVAL, "%s: PL_CRIT_HAS_ROW_WEIGHTS with a null row_weights", who);
+    if (crit->kind & PL_CRIT_HAS_SKELETON)
+      PL_FAIL(PL_EINVAL, "%s: row weights together with the skeleton terms are not built (the bone terms have no per-pose weights yet)", who);
+    if (B < 1 || B > INT32_MAX / O)
+      PL_FAIL(PL_ESHAPE, "%s: row weights index B O = %lld x %lld elements in 32 bits", who, (long long)B, (long long)O);
+  }
   if (const PLSkeleton* sk = crit_skeleton(crit)) {
     PL_TRY(skeleton_check(sk, O, crit->group, who));
     out.has_sk = true; out.sk = *sk;
@@ -415,7 +438,7 @@ extern "C" int pl_pose_loss_fwd_bwd(const float* pred, const float* tgt, int64_t
                                     float grad_scale, float* dpred, float* loss, void* scratch, void* stream) {
   if (B <= 0 || O <= 0) PL_FAIL(PL_ESHAPE, "pl_pose_loss_fwd_bwd: B=%lld O=%lld", (long long)B, (long long)O);
   pl::Crit c;
-  PL_TRY(pl::crit_resolve(crit, O, c, "pl_pose_loss_fwd_bwd"));
+  PL_TRY(pl::crit_resolve(crit, B, O, c, "pl_pose_loss_fwd_bwd"));
   return pl::loss_fwd_bwd_tick(pred, tgt, B, O, c, grad_scale, dpred, loss, scratch, nullptr, stream, "pl_pose_loss_fwd_bwd");
 }
 

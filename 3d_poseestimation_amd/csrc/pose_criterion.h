@@ -1,6 +1,7 @@
 // The pointwise part of the lifter's training criterion (include/poselift.h PLCriterion) as compile-time
-// types: every loss kernel is written once over a criterion type and a has-weights flag, the kind is chosen at the launch,
-// and no element loop branches on it.  d = prediction - target (fp32), w = the joint's weight, k = CritK.
+// types: every loss kernel is written once over a criterion type and a weights state (none, per joint, per pose and
+// joint: DESIGN 3d.2b), the kind is chosen at the launch, and no element loop branches on it.
+// d = prediction - target (fp32), w = the joint's (effective) weight, k = CritK.
 //
 //   kind        accumulated term                         gradient of the element
 //   mse         fmaf(d, d, acc)   [fmaf(w d, d, acc)]    d * coef                       coef = s * 2 / n
@@ -28,6 +29,7 @@ struct Crit {
   int G = 1;                    // coordinates per joint; O = J * G
   float beta = 1.0f;
   const float* w = nullptr;     // J device floats, or NULL = all ones
+  const float* rw = nullptr;    // [B][J] device floats, the per-pose joint weights (PL_CRIT_HAS_ROW_WEIGHTS), or NULL
   bool has_sk = false;          // the skeleton terms (skeleton.hip) follow the loss pass: one launch more
   PLSkeleton sk = {};           // ... a validated copy
 };
@@ -43,16 +45,22 @@ int launch_skeleton_terms(const Crit& c, const float* pred, const float* tgt, in
                           float* dpred, float* part, void* stream, const char* who);
 // PL_ESHAPE / PL_EINVAL as include/poselift.h lists them; G = the criterion's group
 int skeleton_check(const PLSkeleton* sk, int64_t O, int G, const char* who);
+// the row weights a criterion carries (PL_CRIT_HAS_ROW_WEIGHTS in kind, PLRowWeightsCriterion), or NULL
+inline const float* crit_row_weights(const PLCriterion* crit) {
+  return crit && (crit->kind & PL_CRIT_HAS_ROW_WEIGHTS) ? reinterpret_cast<const PLRowWeightsCriterion*>(crit)->row_weights : nullptr;
+}
 // crit == NULL: plain MSE.  PL_EINVAL: unknown kind, beta <= 0 or not finite on smooth_l1; PL_ESHAPE: group < 1, O % group,
-// group > kCritMaxGroup on mpjpe (a joint's coordinates live in one thread's registers).
+// group > kCritMaxGroup on mpjpe (a joint's coordinates live in one thread's registers).  Row weights: PL_EINVAL when NULL
+// under their flag or together with a skeleton, PL_ESHAPE when B O > INT32_MAX.
 constexpr int kCritMaxGroup = 4;
-int crit_resolve(const PLCriterion* crit, int64_t O, Crit& out, const char* who);
+int crit_resolve(const PLCriterion* crit, int64_t B, int64_t O, Crit& out, const char* who);
 
 // the constants of one launch, computed once on the host in fp32
 struct CritK {
   float coef, cb, beta, hb, qb;
   const float* w;
   int O, G;
+  const float* rw;
 };
 inline CritK crit_consts(const Crit& c, float grad_scale, int64_t n /* = B O */, int O) {
   CritK k = {};
@@ -62,7 +70,7 @@ inline CritK crit_consts(const Crit& c, float grad_scale, int64_t n /* = B O */,
     default: k.coef = grad_scale / (float)n; break;
   }
   k.beta = c.beta; k.cb = k.coef / c.beta; k.hb = 0.5f * c.beta; k.qb = 0.5f / c.beta;
-  k.w = c.w; k.O = O; k.G = c.G;
+  k.w = c.w; k.O = O; k.G = c.G; k.rw = c.rw;
   return k;
 }
 // what the summed partials are multiplied by: 1 / (B O), for mpjpe 1 / (B J)
@@ -117,27 +125,40 @@ __device__ __forceinline__ float joint_norm_grad(const float (&d)[G], float cw, 
   return r;
 }
 
-// (kind, has weights) -> f(Pointwise<kind>{}, std::bool_constant<W>{}): the one place a launch turns the run-time kind into types
+// The weights of a launch, the W template parameter of every loss kernel: none, one per joint (k.w[j]), or one per pose and
+// joint (k.rw[b J + j], times k.w[j] when the criterion has joint weights too: a kernel-argument test, the same in every
+// lane -- the row-weight instantiation serves both, so the old two keep their text).
+constexpr int kWNone = 0, kWJoint = 1, kWRow = 2;
+template <int W>
+using WeightsC = std::integral_constant<int, W>;
+// The effective weight W_bj of the row-weight instantiation in two steps, so that no product (and with it no wait for a
+// load) stands between the loads of an element: joint_weight_or_one is issued with the element's other loads -- only the
+// load is under the kernel-uniform test -- and the one fp32 product w_j * rw[b][j] is formed where the weight is first
+// used.  Without joint weights w_j = 1 and fl(1 * r) = r: the bits of the row weight itself.
+__device__ __forceinline__ float joint_weight_or_one(const CritK& k, int j) { return k.w ? k.w[j] : 1.f; }
+
+// (kind, weights) -> f(Pointwise<kind>{}, WeightsC<W>{}): the one place a launch turns the run-time kind into types
+template <class F, class P>
+inline int weights_dispatch(const Crit& c, F&& f, P p) {
+  return c.rw ? f(p, WeightsC<kWRow>{}) : c.w ? f(p, WeightsC<kWJoint>{}) : f(p, WeightsC<kWNone>{});
+}
 template <class F>
 inline int crit_dispatch(const Crit& c, F&& f) {
-  const bool w = c.w != nullptr;
   switch (c.kind) {
-    case PL_CRIT_MSE: return w ? f(Pointwise<PL_CRIT_MSE>{}, std::true_type{}) : f(Pointwise<PL_CRIT_MSE>{}, std::false_type{});
-    case PL_CRIT_L1: return w ? f(Pointwise<PL_CRIT_L1>{}, std::true_type{}) : f(Pointwise<PL_CRIT_L1>{}, std::false_type{});
-    case PL_CRIT_SMOOTH_L1:
-      return w ? f(Pointwise<PL_CRIT_SMOOTH_L1>{}, std::true_type{}) : f(Pointwise<PL_CRIT_SMOOTH_L1>{}, std::false_type{});
-    default: return w ? f(Pointwise<PL_CRIT_MPJPE>{}, std::true_type{}) : f(Pointwise<PL_CRIT_MPJPE>{}, std::false_type{});
+    case PL_CRIT_MSE: return weights_dispatch(c, f, Pointwise<PL_CRIT_MSE>{});
+    case PL_CRIT_L1: return weights_dispatch(c, f, Pointwise<PL_CRIT_L1>{});
+    case PL_CRIT_SMOOTH_L1: return weights_dispatch(c, f, Pointwise<PL_CRIT_SMOOTH_L1>{});
+    default: return weights_dispatch(c, f, Pointwise<PL_CRIT_MPJPE>{});
   }
 }
-// ... and the group size of the grouped kind: f(std::integral_constant<int, G>{}, std::bool_constant<W>{}), G = 1 .. kCritMaxGroup
+// ... and the group size of the grouped kind: f(std::integral_constant<int, G>{}, WeightsC<W>{}), G = 1 .. kCritMaxGroup
 template <class F>
 inline int group_dispatch(const Crit& c, F&& f) {
-  const bool w = c.w != nullptr;
   switch (c.G) {
-    case 1: return w ? f(std::integral_constant<int, 1>{}, std::true_type{}) : f(std::integral_constant<int, 1>{}, std::false_type{});
-    case 2: return w ? f(std::integral_constant<int, 2>{}, std::true_type{}) : f(std::integral_constant<int, 2>{}, std::false_type{});
-    case 3: return w ? f(std::integral_constant<int, 3>{}, std::true_type{}) : f(std::integral_constant<int, 3>{}, std::false_type{});
-    default: return w ? f(std::integral_constant<int, 4>{}, std::true_type{}) : f(std::integral_constant<int, 4>{}, std::false_type{});
+    case 1: return weights_dispatch(c, f, std::integral_constant<int, 1>{});
+    case 2: return weights_dispatch(c, f, std::integral_constant<int, 2>{});
+    case 3: return weights_dispatch(c, f, std::integral_constant<int, 3>{});
+    default: return weights_dispatch(c, f, std::integral_constant<int, 4>{});
   }
 }
 

@@ -236,6 +236,65 @@ __global__ __launch_bounds__(NTHR) void pose_augment_gather_kernel(const float* 
   }
 }
 
+// ---- the per-pose joint weights of a batch (data.py PoseFeeder(weights=), gather_row_weights): the weights follow the joints ----
+// out[k][j] = w[s][flipped_k ? flip_src_joint(j) : j].  p is the batch's plan with every stage but the flip switched off, so
+// decide0 -- the function the pose gather's lane 0 runs on the same words -- returns the flip bit and nothing else is
+// computed.  One thread per output float, one draw per pose and wavefront (shared by a shuffle); rw_flipped and rw_elem are
+// written once for the kernel and the host entry point.
+PLA_HD bool rw_flipped(const pa::Plan& p, uint64_t row) {
+  pa::Pose q = {p.flip_mode == 2, 1.f, 0.f, 1.f, 0.f, 0.f};
+  if (pa::needs_call(p, 0)) {
+    uint32_t w[4];
+    pa::draw(p, row, 0, w);
+    pa::decide0(p, w, q);
+  }
+  return q.flip != 0;
+}
+PLA_HD float rw_elem(const float* w, int64_t s, int J, int j, bool flipped) {
+  return w[s * J + (flipped ? pa::flip_src_joint(j) : j)];
+}
+__global__ __launch_bounds__(NTHR) void row_weights_gather_kernel(const float* __restrict__ w, const int64_t* __restrict__ src_idx,
+                                                                  const int64_t* __restrict__ row_id, int64_t n,
+                                                                  int64_t table_rows, int J, float* __restrict__ out,
+                                                                  pa::Plan p) {
+  const int64_t t = (int64_t)blockIdx.x * NTHR + threadIdx.x;
+  const bool in = t < n * J;                            // (nobody leaves before the shuffle)
+  const int64_t k = in ? t / J : 0;
+  const int j = (int)(t - k * J);
+  bool flipped = p.flip_mode == 2;
+  if (p.flip_mode == 1) {                               // a kernel argument: the same in every lane
+    // one draw per pose and wavefront: the pose's first element inside the wavefront makes it, the others read it
+    const int64_t wave0 = t - (threadIdx.x & (warpSize - 1));
+    const int64_t first = k * J > wave0 ? k * J : wave0;
+    int f = 0;
+    if (in && t == first) f = rw_flipped(p, (uint64_t)row_id[k]);
+    flipped = __shfl(f, (int)(first - wave0)) != 0;
+  }
+  if (!in) return;
+  const int64_t s = src_idx ? src_idx[k] : k;
+  float v = __int_as_float(0x7fc00000);
+  if (s >= 0 && s < table_rows) v = rw_elem(w, s, J, j, flipped);
+  out[t] = v;
+}
+
+// the checks both entry points share; on success *plan holds the flip and nothing else
+bool pa_overlap(const float* x, int64_t nx, const float* y, int64_t ny);
+int row_weights_args(const char* fn, const float* w, const int64_t* src_idx, const int64_t* row_id, int64_t n,
+                     int64_t table_rows, int64_t J, float* out, const PLPoseAug* aug, uint64_t epoch, pa::Plan* plan) {
+  if (!w || !out) PL_FAIL(PL_EINVAL, "%s: null pointer", fn);
+  if (n <= 0 || table_rows <= 0 || J < 1 || J > 4096 || n > (int64_t)INT32_MAX * NTHR / J || table_rows > INT64_MAX / (4 * J))
+    PL_FAIL(PL_ESHAPE, "%s: n=%lld rows=%lld J=%lld", fn, (long long)n, (long long)table_rows, (long long)J);
+  if (!src_idx && n > table_rows)
+    PL_FAIL(PL_ESHAPE, "%s: n=%lld exceeds the %lld rows of an ungathered batch", fn, (long long)n, (long long)table_rows);
+  if (pa_overlap(out, n * J, w, table_rows * J)) PL_FAIL(PL_EINVAL, "%s: aliased pointers (out overlaps the table)", fn);
+  PLPoseAug off = {};
+  PL_TRY(pose_aug_plan(fn, aug ? aug : &off, epoch, plan));
+  plan->max_rot = plan->scale_range = plan->max_shift = plan->sigma = 0.f;
+  if (plan->flip_mode != 0 && J != 17) PL_FAIL(PL_ESHAPE, "%s: a flip swaps the left and right of 17 joints, J=%lld", fn, (long long)J);
+  if (plan->flip_mode == 1 && !row_id) PL_FAIL(PL_EINVAL, "%s: null pointer (row_id)", fn);
+  return PL_OK;
+}
+
 // ---- crop boxes and poses between image and crop coordinates (data.py crop_boxes, crop_poses, uncrop_poses): frame_crop.h ----
 // one thread per pose: its 34 floats, fc::box_of_pose, boxes[k][4] = (x0, y0, side, side)
 __global__ __launch_bounds__(NTHR) void pose_crop_boxes_kernel(const float* __restrict__ a, int64_t n, fc::Spec c,
@@ -480,6 +539,33 @@ extern "C" int pl_pose_augment_gather(const float* a, const float* b, const int6
                                       uint64_t epoch, void* stream) {
   return pl::launch_pose_augment("pl_pose_augment_gather", a, b, src_idx, row_id, n, table_rows, oa, ob, aug, epoch,
                              pl::PoseXf{nullptr, nullptr, nullptr, nullptr}, nullptr, nullptr, stream);
+}
+
+extern "C" int pl_row_weights_gather(const float* w, const int64_t* src_idx, const int64_t* row_id, int64_t n, int64_t table_rows,
+                                     int64_t J, float* out, const PLPoseAug* aug, uint64_t epoch, void* stream) {
+  pl::pa::Plan plan;
+  PL_TRY(pl::row_weights_args("pl_row_weights_gather", w, src_idx, row_id, n, table_rows, J, out, aug, epoch, &plan));
+  const int64_t total = n * J;
+  hipLaunchKernelGGL(pl::row_weights_gather_kernel, dim3((unsigned)((total + pl::NTHR - 1) / pl::NTHR)), dim3(pl::NTHR), 0,
+                     (hipStream_t)stream, w, src_idx, row_id, n, table_rows, (int)J, out, plan);
+  PL_CHECK_LAUNCH("row_weights_gather");
+  return PL_OK;
+}
+
+extern "C" int pl_row_weights_gather_host(const float* w, const int64_t* src_idx, const int64_t* row_id, int64_t n,
+                                          int64_t table_rows, int64_t J, float* out, const PLPoseAug* aug, uint64_t epoch) {
+  pl::pa::Plan plan;
+  PL_TRY(pl::row_weights_args("pl_row_weights_gather_host", w, src_idx, row_id, n, table_rows, J, out, aug, epoch, &plan));
+  for (int64_t k = 0; k < n; ++k) {
+    const int64_t s = src_idx ? src_idx[k] : k;
+    if (s < 0 || s >= table_rows)
+      PL_FAIL(PL_EINVAL, "pl_row_weights_gather_host: src_idx[%lld]=%lld is outside the table", (long long)k, (long long)s);
+  }
+  for (int64_t k = 0; k < n; ++k) {
+    const bool flipped = pl::rw_flipped(plan, plan.flip_mode == 1 ? (uint64_t)row_id[k] : 0);
+    for (int j = 0; j < (int)J; ++j) out[k * J + j] = pl::rw_elem(w, src_idx ? src_idx[k] : k, (int)J, j, flipped);
+  }
+  return PL_OK;
 }
 
 extern "C" int pl_pose_augment_gather_t(const float* a, const float* b, const int64_t* src_idx, const int64_t* row_id,

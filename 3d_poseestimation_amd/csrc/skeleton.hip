@@ -284,3 +284,7 @@ extern "C" int pl_skeleton_terms_host(const float* pred, const float* tgt, int64
 extern "C" size_t pl_skeleton_abi_bytes(int which) {
   return which == 0 ? sizeof(PLCriterion) : which == 1 ? sizeof(PLSkeleton) : which == 2 ? sizeof(PLSkeletonCriterion) : 0;
 }
+
+extern "C" size_t pl_criterion_abi_bytes(int which) {
+  return which == 3 ? sizeof(PLRowWeightsCriterion) : which >= 0 && which < 3 ? pl_skeleton_abi_bytes(which) : 0;
+}

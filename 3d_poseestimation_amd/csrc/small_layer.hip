@@ -866,10 +866,11 @@ __global__ __launch_bounds__(NTHR) void small_top_bwd_kernel(TopArgs p) {
 // partial sum of (y - t)^2: the MSE forward + backward of the fused train step at small batch (nn.MSELoss, train_1.py:64-66).
 // Four lanes per element, a quarter of the slabs each (all of a lane's loads in flight: one round trip), combined in a fixed
 // order: (q0 + q1) + (q2 + q3).  64 elements per workgroup.
-// C, W (pose_criterion.h): the criterion in MSE's place and its per-joint weights (one element, one weight per lane group);
-// <Pointwise<PL_CRIT_MSE>, false> is the kernel as it always was.
+// C, W (pose_criterion.h): the criterion in MSE's place and its weights (one element, one weight per lane group; kWRow:
+// k.rw[i / G], loaded by lane 0 of the group in front of the slab loads); <Pointwise<PL_CRIT_MSE>, kWNone> is the kernel as
+// it always was.
 constexpr int kMseElems = 64;
-template <class C, bool W>
+template <class C, int W>
 __global__ __launch_bounds__(256) void small_mse_kernel(const float* __restrict__ ypart, int NS, int B, int O,
                                                         const float* __restrict__ bias, const float* __restrict__ tgt, CritK k,
                                                         float* __restrict__ y, float* __restrict__ dpred, float* __restrict__ mpart) {
@@ -881,6 +882,10 @@ __global__ __launch_bounds__(256) void small_mse_kernel(const float* __restrict_
   const size_t slab = (size_t)B * 64;
   const int per = (NS + 3) >> 2;
   const float* src = ypart + (size_t)r * 64 + o + (size_t)(q * per) * slab;
+  float rwv = 0.f, wjv = 0.f;                                // (kWRow: loads only here; their product where it is used)
+  if constexpr (W == kWRow) {
+    if (ok && q == 0 && tgt) { rwv = k.rw[i / k.G]; wjv = joint_weight_or_one(k, o / k.G); }
+  }
   float a = 0.f;
   for (int s0 = 0; s0 < per; s0 += 16) {
     float u[16];
@@ -897,7 +902,11 @@ __global__ __launch_bounds__(256) void small_mse_kernel(const float* __restrict_
     y[i] = a;
     if (tgt) {
       const float d = a - tgt[i];
-      if constexpr (W) {
+      if constexpr (W == kWRow) {
+        const float w = wjv * rwv;
+        acc = C::add_w(0.f, d, w, k);
+        dpred[i] = C::grad(d, k) * w;
+      } else if constexpr (W == kWJoint) {
         const float w = k.w[o / k.G];
         acc = C::add_w(0.f, d, w, k);
         dpred[i] = C::grad(d, k) * w;
@@ -919,7 +928,7 @@ __global__ __launch_bounds__(256) void small_mse_kernel(const float* __restrict_
 // between workgroups).  Each lane sums a quarter of the slabs of all G coordinates -- G x 16 loads in flight per pass, one round
 // trip -- and the quarters combine per coordinate in small_mse_kernel's order, (q0 + q1) + (q2 + q3), + bias: y has the bits
 // the pointwise map gives it.  Lane 0 of the group then holds the whole joint.  ceil(B J / 64) <= 64 partials.
-template <int G, bool W>
+template <int G, int W>
 __global__ __launch_bounds__(256) void small_mpjpe_kernel(const float* __restrict__ ypart, int NS, int B, int O,
                                                           const float* __restrict__ bias, const float* __restrict__ tgt, CritK k,
                                                           float* __restrict__ y, float* __restrict__ dpred, float* __restrict__ mpart) {
@@ -931,6 +940,10 @@ __global__ __launch_bounds__(256) void small_mpjpe_kernel(const float* __restric
   const size_t slab = (size_t)B * 64;
   const int per = (NS + 3) >> 2;
   const float* src = ypart + (size_t)r * 64 + j * G + (size_t)(q * per) * slab;
+  float rwv = 0.f, wjv = 0.f;                                // (kWRow: the joint's weights, loaded in front of the slab loads)
+  if constexpr (W == kWRow) {
+    if (ok && q == 0) { rwv = k.rw[i]; wjv = joint_weight_or_one(k, j); }
+  }
   float a[G];
 #pragma unroll
   for (int c = 0; c < G; ++c) a[c] = 0.f;
@@ -959,7 +972,9 @@ __global__ __launch_bounds__(256) void small_mpjpe_kernel(const float* __restric
       y[i * G + c] = a[c];
       d[c] = a[c] - tgt[i * G + c];
     }
-    const float w = W ? k.w[j] : 1.f;
+    float w;
+    if constexpr (W == kWRow) w = wjv * rwv;
+    else w = W ? k.w[j] : 1.f;
     const float nr = joint_norm_grad<G>(d, W ? k.coef * w : k.coef, g);
     acc = W ? w * nr : nr;
 #pragma unroll
@@ -996,7 +1011,7 @@ bool small_top_ok(int O) {
 // the output Linear of an evaluation forward from the slabs the last hidden layer's launch left: y = bias + sum of slabs
 int launch_small_out(const SmallHeadArgs& a, hipStream_t s) {
   if (!a.ypart || !a.y || a.NS < 1 || a.B < 1 || !small_top_ok(a.O)) PL_FAIL(PL_EINVAL, "small_out: bad arguments");
-  hipLaunchKernelGGL((small_mse_kernel<Pointwise<PL_CRIT_MSE>, false>), dim3((a.B * a.O + kMseElems - 1) / kMseElems), dim3(256), 0,
+  hipLaunchKernelGGL((small_mse_kernel<Pointwise<PL_CRIT_MSE>, kWNone>), dim3((a.B * a.O + kMseElems - 1) / kMseElems), dim3(256), 0,
                      s, a.ypart, a.NS, a.B, a.O, a.bias, (const float*)nullptr, CritK{}, a.y, (float*)nullptr, (float*)nullptr);
   PL_CHECK_LAUNCH("small_out");
   return PL_OK;

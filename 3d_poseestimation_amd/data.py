@@ -255,6 +255,47 @@ def augment_poses(y1, y2, augment, row_ids=None, epoch=0, transform_2d=None, tra
     return (oa, ob) if boxes is None else (oa, ob, boxes)
 
 
+def _weights_launch(w, src_idx, row_ids, nb, table_rows, J, out, aug_struct, epoch):
+    """One pl_row_weights_gather on torch's current stream; src_idx None = the rows of w in order, aug_struct None = no flip"""
+    _lib.check(_lib.lib().pl_row_weights_gather(w.data_ptr(), src_idx.data_ptr() if src_idx is not None else None,
+                                                row_ids.data_ptr() if row_ids is not None else None, nb, table_rows, J,
+                                                out.data_ptr(), ctypes.byref(aug_struct) if aug_struct is not None else None,
+                                                int(epoch), _lib.current_stream_ptr()), "pl_row_weights_gather")
+
+
+def gather_row_weights(table_or_batch, augment=None, row_ids=None, epoch=0, src_idx=None):
+    """The per-pose joint weights (PoseCriterion's row_weights) of a batch that augment_poses built: the companion call for
+    batches from another loader.  table_or_batch (N, J) device tensor -> (B, J) fp32, out[k] = table[src_idx[k]] (src_idx
+    None: the rows in order, B = N) with the left / right joints swapped where `augment` (the PoseAugment given to
+    augment_poses, with the same row_ids and epoch) flipped pose k -- the weights follow the joints; no other stage moves
+    a joint.  augment None or p_flip = 0: a plain gather, any J; otherwise J = 17.  One small launch, nothing synchronises;
+    a src_idx outside the table gives a NaN row."""
+    if augment is not None and not isinstance(augment, PoseAugment):
+        raise TypeError("augment must be a PoseAugment or None")
+    _lib.require_device_tensor(table_or_batch, "table_or_batch")
+    if table_or_batch.dim() != 2 or table_or_batch.shape[0] == 0 or table_or_batch.shape[1] == 0:
+        raise ValueError("gather_row_weights expects a (N, J) table, N, J >= 1")
+    w = table_or_batch.float().contiguous()
+    n, J = w.shape
+    if augment is not None and augment.p_flip > 0.0 and J != 17:
+        raise ValueError(f"a flip swaps the left and right of 17 joints, the table has {J}")
+    if src_idx is not None:
+        src_idx = torch.as_tensor(src_idx).to(device=w.device, dtype=torch.int64).contiguous()
+        if src_idx.dim() != 1 or src_idx.numel() == 0:
+            raise ValueError("src_idx holds one table row per pose")
+    nb = src_idx.numel() if src_idx is not None else n
+    if row_ids is None:
+        row_ids = src_idx if src_idx is not None else torch.arange(nb, dtype=torch.int64, device=w.device)
+    else:
+        row_ids = torch.as_tensor(row_ids).to(device=w.device, dtype=torch.int64).contiguous()
+        if row_ids.shape != (nb,):
+            raise ValueError("row_ids holds one dataset index per pose")
+    out = torch.empty((nb, J), dtype=torch.float32, device=w.device)
+    with _lib.on_device(w.device):
+        _weights_launch(w, src_idx, row_ids, nb, n, J, out, augment.struct() if augment is not None else None, epoch)
+    return out
+
+
 def crop_boxes(x2d, crop, frame_hw):
     """The boxes (B,4) fp32 = (x0, y0, side, side), in source pixels, that `crop` (a PersonCrop) takes from the
     image-normalised 2-D poses x2d (B,17,2) of frames of frame_hw = (Hs, Ws): the boxes the feeder's two launches compute for
@@ -281,11 +322,16 @@ class PoseFeeder:
     launch; the tables stay raw.  With a transform and no augmentation the batch is built by the augmented gather with
     every stage off: a copy plus the transform, still one launch.
     crop: a PersonCrop with frame_hw = (Hs, Ws) of the source frames: the batches are (y1, y2, boxes), y1 in the crop
-    coordinates of its own box (in front of the augmentation, same launch) and boxes (b,4) fp32 on the device."""
+    coordinates of its own box (in front of the augmentation, same launch) and boxes (b,4) fp32 on the device.
+    weights: a (N, J) table of per-pose joint weights (visibility, confidence; PoseCriterion's row_weights), resident or
+    pinned like the pose tables (streamed: it rides the same staged copy).  Every batch tuple gains w (b, J) fp32 as its
+    LAST item -- after boxes when there is a crop -- built by one small launch more (pl_row_weights_gather) from the batch's
+    rows and the epoch of set_epoch: where the augmentation flipped a pose its weights swap left and right with the joints
+    (J = 17 with a flip); without an augmentation it is the plain table[idx]."""
 
     def __init__(self, x2d, y3d, batch_size, *, device="cuda", shuffle=True, seed=0, drop_last=False,
                  rank=0, world=1, resident=True, prefetch=2, augment=None, transform_2d=None, transform_3d=None,
-                 crop=None, frame_hw=None):
+                 crop=None, frame_hw=None, weights=None):
         x2d, y3d = torch.as_tensor(x2d), torch.as_tensor(y3d)
         if x2d.shape[0] != y3d.shape[0] or x2d.shape[0] == 0:
             raise ValueError("x2d and y3d need the same, non-zero number of poses")
@@ -325,10 +371,23 @@ class PoseFeeder:
         self.batch_size, self.shuffle, self.seed, self.drop_last = batch_size, shuffle, seed, drop_last
         self.rank, self.world, self.resident, self.prefetch = rank, world, resident, max(1, int(prefetch))
         self.epoch = 0
+        self.w = None
+        if weights is not None:
+            w = torch.as_tensor(weights)
+            if w.dim() != 2 or w.shape[0] != self.n or w.shape[1] < 1:
+                raise ValueError(f"weights is a (N, J) table with one row per pose, got {tuple(w.shape)} for {self.n} poses")
+            if augment is not None and augment.p_flip > 0.0 and w.shape[1] != 17:
+                raise ValueError(f"a flip swaps the left and right of 17 joints, the weights table has {w.shape[1]}")
+            self.w = w.to(torch.float32).contiguous()
+            self.wj = self.w.shape[1]
+        # (the weights see the flip of the batch's augmentation and nothing else of it; no augmentation: no flip)
+        self._waug = augment.struct() if augment is not None else None
         if resident:
             self.a, self.b = a.to(self.device), b.to(self.device)
+            self.w = self.w.to(self.device) if self.w is not None else None
         else:
             self.a, self.b = a.pin_memory(), b.pin_memory()
+            self.w = self.w.pin_memory() if self.w is not None else None
             self._copy_stream = torch.cuda.Stream(self.device)
 
     def set_epoch(self, epoch):
@@ -364,11 +423,13 @@ class PoseFeeder:
                     _lib.check(L.pl_gather_rows2(self.a.data_ptr(), self.wa, self.b.data_ptr(), self.wb,
                                                  idx_all[at:at + nb].data_ptr(), nb, self.n, oa.data_ptr(), ob.data_ptr(),
                                                  _lib.current_stream_ptr()), "pl_gather_rows2")
+                if self.w is not None:
+                    idx = idx_all[at:at + nb]
+                    ow = torch.empty((nb, self.wj), dtype=torch.float32, device=self.device)
+                    _weights_launch(self.w, idx, idx, nb, self.n, self.wj, ow, self._waug, epoch)
             at += nb
-            if self._crop is not None:
-                yield oa, ob, boxes
-            else:
-                yield oa, ob
+            out = (oa, ob, boxes) if self._crop is not None else (oa, ob)
+            yield out + (ow,) if self.w is not None else out
 
     def _iter_streamed(self):
         batches, epoch = self._indices(), self.epoch
@@ -379,6 +440,7 @@ class PoseFeeder:
         # augmentation: the batch's dataset rows ride the same copy (8 B per pose); they are the identity of its draws
         stage_idx = [torch.empty(self.batch_size, dtype=torch.int64).pin_memory() for _ in range(slots)] \
             if self._aug is not None else None
+        stage_w = [torch.empty(self.batch_size, self.wj).pin_memory() for _ in range(slots)] if self.w is not None else None
 
         def launch(k, idx):
             slot = k % slots
@@ -388,9 +450,14 @@ class PoseFeeder:
                 free_events[slot].synchronize()           # staging buffer no longer being copied from
             torch.index_select(self.a, 0, idx, out=ha)
             torch.index_select(self.b, 0, idx, out=hb)
+            hw = None
+            if stage_w is not None:
+                hw = stage_w[slot][:nb]
+                torch.index_select(self.w, 0, idx, out=hw)
             with torch.cuda.stream(self._copy_stream):
                 da = ha.to(self.device, non_blocking=True).view((nb,) + self.shape_a)
                 db = hb.to(self.device, non_blocking=True).view((nb,) + self.shape_b)
+                dw = hw.to(self.device, non_blocking=True) if hw is not None else None
                 di = None
                 if stage_idx is not None:
                     hi = stage_idx[slot][:nb]
@@ -399,19 +466,28 @@ class PoseFeeder:
                 ev = torch.cuda.Event()
                 ev.record(self._copy_stream)
             free_events[slot] = ev
-            return da, db, di, ev
+            return da, db, di, dw, ev
 
         nxt = 0
         while nxt < len(batches) and len(inflight) < self.prefetch:
             inflight.append(launch(nxt, batches[nxt]))
             nxt += 1
         while inflight:
-            da, db, di, ev = inflight.pop(0)
+            da, db, di, dw, ev = inflight.pop(0)
             torch.cuda.current_stream(self.device).wait_event(ev)
             da.record_stream(torch.cuda.current_stream(self.device))
             db.record_stream(torch.cuda.current_stream(self.device))
-            if di is not None:                            # one launch on the consumer's stream, behind the event wait
+            if di is not None:
                 di.record_stream(torch.cuda.current_stream(self.device))
+            if dw is not None:                            # (read on the consumer's stream whether or not a launch follows)
+                dw.record_stream(torch.cuda.current_stream(self.device))
+            if dw is not None and self._waug is not None:  # the staged rows are in batch order: only the flip is left to do
+                nb = dw.shape[0]
+                ow = torch.empty_like(dw)
+                with _lib.on_device(self.device):
+                    _weights_launch(dw, None, di, nb, nb, self.wj, ow, self._waug, epoch)
+                dw = ow
+            if di is not None and self._aug is not None:  # one launch on the consumer's stream, behind the event wait
                 nb = di.numel()
                 oa, ob = torch.empty_like(da), torch.empty_like(db)
                 boxes = torch.empty((nb, 4), dtype=torch.float32, device=self.device) if self._crop is not None else None
@@ -421,10 +497,8 @@ class PoseFeeder:
             if nxt < len(batches):
                 inflight.append(launch(nxt, batches[nxt]))
                 nxt += 1
-            if self._crop is not None:
-                yield da, db, boxes
-            else:
-                yield da, db
+            out = (da, db, boxes) if self._crop is not None else (da, db)
+            yield out + (dw,) if dw is not None else out
 
 
 def _frame_augment_struct(augment):

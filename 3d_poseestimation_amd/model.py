@@ -539,12 +539,14 @@ class LinearModel(nn.Module):
         <= 64 rows whose hidden layers run as one launch each)?"""
         return _lib.lib().pl_lifter_step_carries_adamw(ctypes.byref(self._desc), int(B)) == 1
 
-    def fused_train_fwd_bwd(self, x2, target, sync=None, step_dev=None, adamw=None, criterion=None):
+    def fused_train_fwd_bwd(self, x2, target, sync=None, step_dev=None, adamw=None, criterion=None, row_weights=None):
         """forward + MSE(mean) + backward in one library call (two when a data-parallel sync wants
         the upper layers' gradients early).  Returns (loss, y) device tensors; parameter gradients
         land in the flat arena and stay attached as .grad views.
         criterion (a criterion.PoseCriterion, or None = MSE): the loss in MSE's place, on every route and in the same launches
         (pl_lifter_train_fwd_bwd_crit / pl_lifter_train_step_crit; None calls the entry points it always did).
+        row_weights ((B, J), criterion.PoseCriterion's; needs a criterion): the per-pose joint weights of these B rows, carried
+        by the same calls on every route, the (hi, lo) ranges of a gradient sync included.
         step_dev (graph capture, train.GraphedTrainStep): device counter of completed steps; the dropout stream
         of the captured launches uses (the step number at capture) + *step_dev.
         adamw (a _lib.PLAdamWStep from FlatAdamW._step_struct; no sync): the optimizer step as well, in the same call
@@ -552,7 +554,11 @@ class LinearModel(nn.Module):
         B = x2.shape[0]
         x2 = _lib.aligned16(x2)               # (the library stages x 16 bytes at a time; the target only meets element kernels)
         # (checked before anything is counted or launched; the struct points into the criterion's weights)
-        crit = ctypes.byref(criterion.struct(self.output_size, x2.device)) if criterion is not None else None
+        if row_weights is not None:
+            if criterion is None:
+                raise ValueError("fused_train_fwd_bwd: row_weights need a criterion (its coords say what a joint is)")
+            row_weights = criterion.row_weights_for(row_weights, B, self.output_size, x2.device)
+        crit = ctypes.byref(criterion.struct(self.output_size, x2.device, row_weights)) if criterion is not None else None
         ws = self._acquire_workspace(B)
         try:
             y = torch.empty(B, self.output_size, dtype=torch.float32, device=x2.device)

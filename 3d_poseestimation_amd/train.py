@@ -202,11 +202,18 @@ def _fusable(model, optimizer, y1, y2, criterion=None):
             and y1.numel() == y1.shape[0] * model.input_size)
 
 
-def _criterion_loss(criterion, y2_hat, y2):
+def _criterion_loss(criterion, y2_hat, y2, row_weights=None):
+    if row_weights is not None:
+        return criterion(y2_hat, y2, row_weights=row_weights)
     return mse_loss(y2_hat, y2) if criterion is None else criterion(y2_hat, y2)
 
 
-def train_step(model, optimizer, y1, y2, grad_sync=None, criterion=None):
+def _need_criterion(row_weights, criterion, who):
+    if row_weights is not None and criterion is None:
+        raise ValueError(f"{who}: row_weights need criterion= (a PoseCriterion: its coords say what a joint is)")
+
+
+def train_step(model, optimizer, y1, y2, grad_sync=None, criterion=None, row_weights=None):
     """One train_1.py:75-100 step: zero_grad, forward, reshape (B,J,3), MSE(mean), backward,
     [gradient all-reduce], optimizer.step.  Returns (loss, y2_hat) as device tensors -- the
     caller decides when to pay the host sync the reference pays every step (train_1.py:98).
@@ -214,7 +221,10 @@ def train_step(model, optimizer, y1, y2, grad_sync=None, criterion=None):
     model.set_grad_sync(grad_sync) to have its all-reduce overlapped with the backward pass.
     criterion: a criterion.PoseCriterion in MSE's place (the reference's `# loss_function = torch.nn.L1Loss()` toggle,
     train_1.py:36-37; smooth-L1, MPJPE, per-joint weights).  LinearModel + FlatAdamW keep the fused step -- the same
-    launches, AdamW riding at B <= 64, the data-parallel ranges; every other model runs criterion(y2_hat, y2) under autograd."""
+    launches, AdamW riding at B <= 64, the data-parallel ranges; every other model runs criterion(y2_hat, y2) under autograd.
+    row_weights: (B, J) per-pose joint weights for the criterion (PoseCriterion's row_weights; ValueError without a
+    criterion), carried on every one of those routes; under a GradSync they are the weights of this rank's own rows."""
+    _need_criterion(row_weights, criterion, "train_step")
     y1, y2 = y1.float(), y2.float()
     if getattr(optimizer, "_swapped", False):
         optimizer._check_live("train_step")
@@ -229,16 +239,17 @@ def train_step(model, optimizer, y1, y2, grad_sync=None, criterion=None):
                 # (not with max_grad_norm / skip_nonfinite: the norm of the whole gradient has to exist before any update)
                 adamw = optimizer._step_struct(float(optimizer.param_groups[0]["lr"]), None, optimizer._t + 1, None)
                 if adamw is not None:
-                    loss, y2_hat = model.fused_train_fwd_bwd(x2, t2, None, adamw=adamw, criterion=criterion)
+                    loss, y2_hat = model.fused_train_fwd_bwd(x2, t2, None, adamw=adamw, criterion=criterion,
+                                                             row_weights=row_weights)
                     optimizer._advance_host(1)
                     return loss, y2_hat.reshape(y2.shape)
             loss, y2_hat = model.fused_train_fwd_bwd(x2, t2, grad_sync if model._grad_sync is grad_sync else None,
-                                                     criterion=criterion)
+                                                     criterion=criterion, row_weights=row_weights)
         optimizer.step(grad_scale=grad_sync(model) if grad_sync is not None else 1.0)
         return loss, y2_hat.reshape(y2.shape)
     optimizer.zero_grad()
     y2_hat = model(y1).reshape(y2.shape)
-    loss = _criterion_loss(criterion, y2_hat, y2)
+    loss = _criterion_loss(criterion, y2_hat, y2, row_weights)
     loss.backward()
     if grad_sync is not None:
         optimizer.step(grad_scale=grad_sync(model))
@@ -262,11 +273,20 @@ class GraphedTrainStep:
     criterion (a criterion.PoseCriterion, None = MSE): its kind, beta and coords are fixed at capture (changing them on the
     object afterwards does nothing to the graph); the address of its joint_weights is baked into the captured launches, the
     step keeps the criterion alive, and in-place edits of the weights are seen by the next replay (moving the criterion
-    to another device or replacing the tensor needs a new GraphedTrainStep: __call__ refuses)."""
+    to another device or replacing the tensor needs a new GraphedTrainStep: __call__ refuses).
+    row_weights ((B, J), with a criterion): the step captures a static (B, J) fp32 buffer, `step.row_weights`, which the
+    captured launches read; step(x, y, row_weights=rw) copies rw into it (unless rw IS that buffer), and in-place edits of
+    the buffer are seen by the next replay.  A step captured with row weights refuses a call without them, and one
+    captured without refuses a call with them (the launches differ)."""
 
-    def __init__(self, model, optimizer, y1, y2, criterion=None):
+    def __init__(self, model, optimizer, y1, y2, criterion=None, row_weights=None):
+        _need_criterion(row_weights, criterion, "GraphedTrainStep")
         y1, y2 = y1.float(), y2.float()
         self.criterion = criterion
+        self.row_weights = None
+        if row_weights is not None:
+            self.row_weights = criterion.row_weights_for(row_weights, y1.shape[0], y2.numel() // y2.shape[0], y2.device).clone()
+        row_weights = self.row_weights
         if not _fusable(model, optimizer, y1, y2, criterion) or model._grad_sync is not None:
             raise _lib.PoseliftError("GraphedTrainStep needs a training-mode LinearModel on the GPU with its FlatAdamW "
                                      "and no gradient sync attached")
@@ -285,7 +305,7 @@ class GraphedTrainStep:
             state = [model.flat_params, model._bn_running, model._bn_batches] + optimizer._capture_state()
             snap = [t.clone() for t in state]
             step0, t0 = model._step, optimizer._t
-            train_step(model, optimizer, self._x, self._y.reshape(self._out_shape), criterion=criterion)
+            train_step(model, optimizer, self._x, self._y.reshape(self._out_shape), criterion=criterion, row_weights=row_weights)
             for dst, src in zip(state, snap):
                 dst.copy_(src)
             model._step = step0
@@ -306,10 +326,11 @@ class GraphedTrainStep:
             with torch.cuda.graph(self.graph):
                 if adamw is not None:        # small batches: the optimizer step is inside the same call's launches
                     self.loss, y_hat = model.fused_train_fwd_bwd(self._x, self._y, None, step_dev=self._tick, adamw=adamw,
-                                                                 criterion=criterion)
+                                                                 criterion=criterion, row_weights=row_weights)
                     self._refreshes_planes = False
                 else:
-                    self.loss, y_hat = model.fused_train_fwd_bwd(self._x, self._y, None, step_dev=self._tick, criterion=criterion)
+                    self.loss, y_hat = model.fused_train_fwd_bwd(self._x, self._y, None, step_dev=self._tick, criterion=criterion,
+                                                                 row_weights=row_weights)
                     self._refreshes_planes = optimizer._enqueue_dev(lr_dev, t0, self._tick)
             self.y_hat = y_hat.reshape(self._out_shape)
             model._step = step0                                              # capturing ran nothing
@@ -331,7 +352,14 @@ class GraphedTrainStep:
                 self.opt._v.data_ptr() if self.opt._v is not None else 0, crit,
                 self.opt._e.data_ptr() if self.opt._e is not None else 0)
 
-    def __call__(self, y1, y2):
+    def __call__(self, y1, y2, row_weights=None):
+        if (row_weights is None) != (self.row_weights is None):
+            raise ValueError("GraphedTrainStep: captured " + ("with" if self.row_weights is not None else "without") +
+                             " row_weights and called " + ("without" if row_weights is None else "with") +
+                             " them: the captured launches differ -- capture a new one")
+        if row_weights is not None and (tuple(row_weights.shape) != tuple(self.row_weights.shape) or row_weights.requires_grad):
+            raise ValueError(f"GraphedTrainStep: row_weights {tuple(row_weights.shape)} (requires_grad={row_weights.requires_grad}),"
+                             f" captured {tuple(self.row_weights.shape)}")
         self.opt._check_live("a GraphedTrainStep replay")
         self._lr_dev.refresh(self.opt.param_groups[0]["lr"])                     # ReduceLROnPlateau et al. (train_1.py:106)
         if self.opt._ema_signature() != self._ema_sig:
@@ -359,6 +387,8 @@ class GraphedTrainStep:
             self._x.copy_(y1.reshape(self._x.shape))
         if y2.data_ptr() != self._y.data_ptr():
             self._y.copy_(y2.reshape(self._y.shape))
+        if row_weights is not None and row_weights.data_ptr() != self.row_weights.data_ptr():
+            self.row_weights.copy_(row_weights)
         if not self._in_call:
             self.model._ensure_wplanes()     # parameters changed behind the graph's back (load_state_dict, ...)
         self.graph.replay()
@@ -388,7 +418,9 @@ class GraphedModuleStep:
     Fixed shapes; single process; the optimizer must keep its step state on the device (torch: capturable=True; give lr as
     a tensor to change it between replays).  forward(*inputs) is whatever the module's forward takes; loss_fn(output,
     target) -- a criterion.PoseCriterion is one (its launch pair is captured like any other: kind, beta and coords as they
-    are at construction, joint_weights edited in place are seen by replays)."""
+    are at construction, joint_weights edited in place are seen by replays).  For per-pose weights loss_fn may close over a
+    static (B, J) weights tensor, loss_fn = lambda out, tgt: crit(out, tgt, row_weights=rw): the captured launches read rw's
+    memory, so fill it in place (rw.copy_(...)) before each replay."""
 
     def __init__(self, model, optimizer, loss_fn, inputs, target, warmup=2):
         inputs = tuple(inputs) if isinstance(inputs, (tuple, list)) else (inputs,)
@@ -487,9 +519,12 @@ def predict_flip_tta(model, y1, out_dims=3):
 
 
 @torch.no_grad()
-def eval_step(model, y1, y2, metric_out=None, flip=False, meter=None, group_ids=None, denorm=None, criterion=None, ema=None):
+def eval_step(model, y1, y2, metric_out=None, flip=False, meter=None, group_ids=None, denorm=None, criterion=None, ema=None,
+              row_weights=None):
     """train_1.py:112-145 body (model must be in eval mode): forward, MSE, loss_MPJPE.
     criterion: a criterion.PoseCriterion -- `loss` is then that criterion's value, not the MSE.
+    row_weights: (B, J) per-pose joint weights of that criterion's value (ValueError without a criterion); `metric` and the
+    meter are not weighted.
     flip=True: flip test-time augmentation (predict_flip_tta).
     meter: a metrics.PoseMetrics that also takes this batch (P-MPJPE, N-MPJPE, PCK; group_ids (B,) = e.g. the action of
     each pose); like everything here it only enqueues work.
@@ -498,17 +533,18 @@ def eval_step(model, y1, y2, metric_out=None, flip=False, meter=None, group_ids=
     inside the launches that read them (no launch more than without).  y2_hat is returned as the model gave it.
     ema: the model's flat optimizer built with ema_decay -- the step runs on the averaged weights, i.e. inside
     `with ema.averaged_weights():` (BatchNorm running statistics stay the live ones)."""
+    _need_criterion(row_weights, criterion, "eval_step")
     if ema is not None:
         with ema.averaged_weights():
             return eval_step(model, y1, y2, metric_out=metric_out, flip=flip, meter=meter, group_ids=group_ids, denorm=denorm,
-                             criterion=criterion)
+                             criterion=criterion, row_weights=row_weights)
     if flip and denorm is not None:
         raise ValueError("eval_step: flip=True mirrors image-normalised poses and cannot run on transformed ones; compose it: "
                          "a = model(T2.apply(raw2d)), b = model(T2.apply(flip_pose(raw2d))), then "
                          "flip_average(T3.invert(b), T3.invert(a)) is the prediction in raw units")
     y1, y2 = y1.float(), y2.float()
     y2_hat = predict_flip_tta(model, y1, y2.shape[-1]).reshape(y2.shape) if flip else model(y1).reshape(y2.shape)
-    loss = _criterion_loss(criterion, y2_hat, y2)
+    loss = _criterion_loss(criterion, y2_hat, y2, row_weights)
     metric = loss_MPJPE(y2_hat, y2, out=metric_out, denorm=denorm)
     if meter is not None:
         meter.update(y2_hat, y2, group_ids, denorm=denorm)

@@ -354,6 +354,32 @@ int pl_skeleton_terms_host(const float* pred, const float* tgt, int64_t B, int32
                            float grad_scale, float* dpred, float* loss, float* lengths);
 size_t pl_skeleton_abi_bytes(int which);
 
+/* ---- per-pose joint weights ("row weights") of the criterion (PARITY UNPINNED: the oracle is torch's (W * elementwise).mean()) ----
+ * rw [B][J] fp32 on the device, contiguous, J = O / group: the weight of joint j of pose b.  The effective weight is
+ *   W_bj = rw[b][j]                    without per-joint weights (base.weights == NULL)
+ *   W_bj = fl(w_j * rw[b][j])          with both: one fp32 product, formed once per element (mpjpe: per joint)
+ * and W_bj stands wherever w_j stands in the table of PLCriterion above; nothing else changes.  The normaliser stays
+ * 1 / (B O) (mpjpe: 1 / (B J)) whatever the weights sum to.  Weights multiply: a zero weight does not hide a NaN
+ * (0 * NaN = NaN), as in torch.  There is no gradient with respect to rw.  The weight of flat element i of [B][O] is
+ * rw[i / group]: same element map, same order of every sum, same number of partials and launches as the per-joint-weighted
+ * criterion; rw[b][j] = w_j gives the bits of weights = w, and all-ones rw the bits of the unweighted criterion.
+ *
+ * Row weights ride behind PLCriterion as the skeleton does: set PL_CRIT_HAS_ROW_WEIGHTS in `kind` of sc.base and pass
+ * &x.sc.base wherever a PLCriterion* goes (pl_pose_loss_fwd_bwd, pl_pose_loss_scratch_bytes, pl_lifter_train_fwd_bwd_crit,
+ * pl_lifter_train_step_crit; under (hi, lo) ranges the weights are those of the call's own rows).  Without the flag nothing
+ * past the skeleton extension is read.  Checked before anything is launched or counted:
+ *   PL_EINVAL  the flag with a NULL row_weights; the flag together with PL_CRIT_HAS_SKELETON (the bone terms are not
+ *              weighted per pose yet: the combination is not built)
+ *   PL_ESHAPE  the flag with B O > INT32_MAX (the index arithmetic of the row-weight instantiations is 32-bit) */
+#define PL_CRIT_HAS_ROW_WEIGHTS 0x200
+typedef struct PLRowWeightsCriterion {
+  PLSkeletonCriterion sc;                  /* sc.base.kind = a PLCriterionKind | PL_CRIT_HAS_ROW_WEIGHTS; sc.skeleton unread without its flag */
+  const float* row_weights;                /* device, [B][O / group] */
+} PLRowWeightsCriterion;
+/* Test hook: sizeof of PLCriterion (0), PLSkeleton (1), PLSkeletonCriterion (2), PLRowWeightsCriterion (3) as the library was
+ * compiled, 0 for anything else.  (pl_skeleton_abi_bytes keeps answering 0 for 3, as its callers pin.) */
+size_t pl_criterion_abi_bytes(int which);
+
 /* The 3-D head forward on NHWC logits [B][H][W][J*64] (depth_dim 64, the conv path's layout): same
  * coords [B*J][3] and stats [B*J][5] as pl_softargmax_fwd(ncoord 3, centred 1).  Model.py:94-133. */
 int pl_softargmax3d_nhwc_fwd(const float* logits, int64_t B, int64_t J, int64_t H, int64_t W,
@@ -532,6 +558,18 @@ int pl_pose_augment_gather(const float* a, const float* b, const int64_t* src_id
                            int64_t table_rows, float* oa, float* ob, const PLPoseAug* aug, uint64_t epoch, void* stream);
 int pl_pose_augment_host(const float* a, const float* b, const int64_t* src_idx, const int64_t* row_id, int64_t n,
                          int64_t table_rows, float* oa, float* ob, const PLPoseAug* aug, uint64_t epoch);
+
+/* The per-pose joint weights (PLRowWeightsCriterion) of the same batch: out[k][j] = w[s][flipped_k ? flip_src_joint(j) : j],
+ * s = src_idx[k], or k when src_idx is NULL; w [table_rows][J], out [n][J].  flipped_k is the flip bit
+ * pl_pose_augment_gather forms for (aug->seed, epoch, row_id[k]) -- the same functions of csrc/pose_augment.h -- so the
+ * weights follow the joints through the left/right swap; no other stage moves a joint.  aug == NULL or p_flip <= 0: a plain
+ * gather, any J >= 1 (row_id may then be NULL); otherwise J = 17, else PL_ESHAPE.  An s outside [0, table_rows) writes a NaN
+ * row on the device and is PL_EINVAL on the host.  One small launch; pl_row_weights_gather_host: the same inline text on
+ * host pointers (a test hook). */
+int pl_row_weights_gather(const float* w, const int64_t* src_idx, const int64_t* row_id, int64_t n, int64_t table_rows,
+                          int64_t J, float* out, const PLPoseAug* aug, uint64_t epoch, void* stream);
+int pl_row_weights_gather_host(const float* w, const int64_t* src_idx, const int64_t* row_id, int64_t n, int64_t table_rows,
+                               int64_t J, float* out, const PLPoseAug* aug, uint64_t epoch);
 
 /* pl_pose_augment_gather with two nullable per-column transforms (pose tables, below), applied to each output element
  * AFTER the augmentation: oa's 34 columns become (v - sub_a[c]) / div_a[c], ob's 51 (v - sub_b[c]) / div_b[c]; a column
