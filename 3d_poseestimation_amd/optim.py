@@ -111,6 +111,15 @@ class FlatOptimizer(torch.optim.Optimizer):
             return None
         return (decay, warmup, int(self._ema_t0), self._e.data_ptr() if self._e is not None else 0)
 
+    def _hyper_signature(self):
+        """What a captured step bakes into its launches BY VALUE about the update itself: betas, eps, weight_decay (and
+        whether it is applied: arena.FlatAdam's decoupled_weight_decay).  lr and max_norm are read from device scalars and t
+        from a device counter, so they may change between replays; these may not (train.GraphedTrainStep /
+        GraphedModuleStep refuse the replay)."""
+        g = self.param_groups[0]
+        return (float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
+                bool(g.get("decoupled_weight_decay", True)))
+
     def _ema_after_load(self, keep):
         """load_state_dict: `keep` = this optimizer's own (ema_decay, ema_warmup), which a loaded state does not replace.
         With ema_decay: a state that carries the averages continues them (and their update count); one that does not starts

@@ -258,6 +258,18 @@ def train_step(model, optimizer, y1, y2, grad_sync=None, criterion=None, row_wei
     return loss, y2_hat
 
 
+def _check_hyper(who, optimizer, captured):
+    """betas / eps / weight_decay of a flat optimizer against what a captured step baked into its launches: a replay after a
+    change would use the old value in silence (the eager step follows param_groups), so it is refused -- like every
+    other host-side change a graph cannot follow."""
+    now = optimizer._hyper_signature()
+    if now != captured:
+        names = ("beta1", "beta2", "eps", "weight_decay", "decoupled_weight_decay")
+        what = ", ".join(f"{n} {a!r} -> {b!r}" for n, a, b in zip(names, captured, now) if a != b)
+        raise _lib.PoseliftError(f"{who}: {what} changed in param_groups after capture (betas, eps and weight_decay are baked "
+                                 "into the captured launches by value; lr is not): capture a new one")
+
+
 class GraphedTrainStep:
     """The train_1.py:75-100 step captured ONCE as a hipGraph (torch.cuda.graph) and replayed: the ~50 kernel launches
     of a step become one graph launch, which is what a launch-bound step wants (B = 64, BASELINE configs[0]: the
@@ -318,6 +330,8 @@ class GraphedTrainStep:
             # the averaged weights: whether the step keeps them, ema_decay / ema_warmup, the update count's base and the
             # arena's address are all baked into the captured launches (the update count itself advances on the device)
             self._ema_sig = optimizer._ema_signature()
+            # betas, eps and weight_decay are arguments of the captured launches (PLAdamWStep / the AdamW launch), by value
+            self._hyper_sig = optimizer._hyper_signature()
             torch.cuda.synchronize(dev)
             self.graph = torch.cuda.CUDAGraph()
             adamw = (optimizer._step_struct(0.0, lr_dev, t0, self._tick)
@@ -361,6 +375,7 @@ class GraphedTrainStep:
             raise ValueError(f"GraphedTrainStep: row_weights {tuple(row_weights.shape)} (requires_grad={row_weights.requires_grad}),"
                              f" captured {tuple(self.row_weights.shape)}")
         self.opt._check_live("a GraphedTrainStep replay")
+        _check_hyper("GraphedTrainStep", self.opt, self._hyper_sig)
         self._lr_dev.refresh(self.opt.param_groups[0]["lr"])                     # ReduceLROnPlateau et al. (train_1.py:106)
         if self.opt._ema_signature() != self._ema_sig:
             raise _lib.PoseliftError("GraphedTrainStep: ema_decay / ema_warmup were switched on, off or changed after capture, or "
@@ -416,7 +431,8 @@ class GraphedModuleStep:
     Construction runs `warmup` eager steps on the example batch (every kernel loaded, the allocator's pool sized) and then
     puts parameters, buffers and optimizer state back exactly as they were, so the first replay is the model's first step.
     Fixed shapes; single process; the optimizer must keep its step state on the device (torch: capturable=True; give lr as
-    a tensor to change it between replays).  forward(*inputs) is whatever the module's forward takes; loss_fn(output,
+    a tensor to change it between replays; arena.FlatAdam's float lr is followed as it is, and a change of its betas, eps or
+    weight_decay after capture is refused).  forward(*inputs) is whatever the module's forward takes; loss_fn(output,
     target) -- a criterion.PoseCriterion is one (its launch pair is captured like any other: kind, beta and coords as they
     are at construction, joint_weights edited in place are seen by replays).  For per-pose weights loss_fn may close over a
     static (B, J) weights tensor, loss_fn = lambda out, tgt: crit(out, tgt, row_weights=rw): the captured launches read rw's
@@ -439,11 +455,18 @@ class GraphedModuleStep:
         self._target = target.detach().clone()
         # arena.FlatAdam with ema_decay: the averaged weights exist before the warm-up steps (which the restore below then
         # undoes like the moments); what the captured launches bake in about them is checked at every replay
-        self._ema_sig = None
+        # ... so is what they bake in of the update (betas, eps, weight_decay: _check_hyper), and a float lr is refreshed into
+        # the device scalar the captured launch reads (a stock torch optimizer is left to torch's own rules: lr as a tensor)
+        self._ema_sig = self._hyper_sig = None
+        self._lr_is_tensor = False
         if hasattr(optimizer, "_ema_signature"):
             optimizer._check_live("GraphedModuleStep")
             optimizer._ema_bind()
             self._ema_sig = optimizer._ema_signature()
+            self._hyper_sig = optimizer._hyper_signature()
+            lr = optimizer.param_groups[0]["lr"]
+            self._lr_is_tensor = torch.is_tensor(lr)
+            self._lr_ptr = lr.data_ptr() if self._lr_is_tensor else None
         with _lib.on_device(dev):
             torch.cuda.synchronize(dev)
             state = [t for t in model.state_dict().values()]
@@ -485,6 +508,14 @@ class GraphedModuleStep:
             if self.opt._ema_signature() != self._ema_sig:
                 raise _lib.PoseliftError("GraphedModuleStep: ema_decay / ema_warmup were switched on, off or changed after "
                                          "capture, or the averaged weights were re-loaded: capture a new one")
+            _check_hyper("GraphedModuleStep", self.opt, self._hyper_sig)
+            lr = self.opt.param_groups[0]["lr"]
+            if torch.is_tensor(lr) != self._lr_is_tensor or (self._lr_is_tensor and lr.data_ptr() != self._lr_ptr):
+                raise _lib.PoseliftError("GraphedModuleStep: param_groups[0]['lr'] was a " +
+                                         ("tensor" if self._lr_is_tensor else "float") + " at capture and the captured launch "
+                                         "reads that memory: change its value, not the object -- or capture a new one")
+            if not self._lr_is_tensor and hasattr(self.opt, "_lr_dev"):
+                self.opt._lr_dev.refresh(lr)             # a scheduler's new float lr: FlatAdam.step() does not run in a replay
         for dst, src in zip(self._in, inputs):
             dst.copy_(src)
         self._target.copy_(target)

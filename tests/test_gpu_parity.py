@@ -859,21 +859,36 @@ def test_small_batch_fused_step_vs_autograd_route(pkg, monkeypatch, B, H, S):
     np.testing.assert_allclose(losses[0], losses[1], rtol=1e-5)
 
 
-@pytest.mark.parametrize("B,H,S,dtype", [(64, 1024, 2, "fp32"), (20, 256, 1, "fp32"), (9, 512, 0, "fp32"), (64, 1024, 2, "f16x3")])
-def test_small_batch_adamw_inside_the_backward_launches_is_bitwise_the_separate_launch(pkg, B, H, S, dtype):
+# hp: None = the defaults the test always ran with, or (betas, eps, weight_decay, the lr of the third step): a field of the
+# ride's constants hard-coded to its default, or an lr read once, would pass the default cases and cannot pass these
+_RIDE_HP = ((0.5, 0.9), 1e-3, 0.3, 3e-3)
+
+
+@pytest.mark.parametrize("B,H,S,dtype,hp", [
+    pytest.param(64, 1024, 2, "fp32", None, id="64-1024-2-fp32"), pytest.param(20, 256, 1, "fp32", None, id="20-256-1-fp32"),
+    pytest.param(9, 512, 0, "fp32", None, id="9-512-0-fp32"), pytest.param(64, 1024, 2, "f16x3", None, id="64-1024-2-f16x3"),
+    pytest.param(20, 256, 1, "fp32", _RIDE_HP, id="20-256-1-fp32-hp"), pytest.param(9, 512, 0, "fp32", _RIDE_HP, id="9-512-0-fp32-hp"),
+    pytest.param(64, 1024, 2, "f16x3", _RIDE_HP, id="64-1024-2-f16x3-hp")])
+def test_small_batch_adamw_inside_the_backward_launches_is_bitwise_the_separate_launch(pkg, B, H, S, dtype, hp):
     """pl_lifter_train_step at B <= 64: each backward launch carries a slice of the AdamW step on spare workgroups and one
     small launch updates the bottom of the arena.  Against fused_train_fwd_bwd + optimizer.step() (one AdamW launch over the
     whole arena): the same kernels produce the gradients, the element arithmetic is the same -- parameters, both moment
-    arenas and the losses of three steps are equal bit for bit."""
+    arenas and the losses of three steps are equal bit for bit.  With hp: non-default betas, eps and weight_decay, and a
+    learning rate changed in param_groups before the third step."""
     out = []
     for in_call in (True, False):
         torch.manual_seed(0)
         m = pkg.LinearModel(34, 51, linear_size=H, num_stage=S, p_dropout=0.5, compute_dtype=dtype).to(DEV).train()
         m.manual_seed(3)
-        opt = pkg.FlatAdamW(m, lr=1e-3, weight_decay=0.02)
+        if hp is None:
+            opt = pkg.FlatAdamW(m, lr=1e-3, weight_decay=0.02)
+        else:
+            opt = pkg.FlatAdamW(m, lr=1e-3, betas=hp[0], eps=hp[1], weight_decay=hp[2])
         assert m.step_carries_adamw(B) and not m.step_carries_adamw(128)
         losses = []
         for i in range(3):
+            if hp is not None and i == 2:
+                opt.param_groups[0]["lr"] = hp[3]
             x, y = pkg.synth.synthetic_batch(B, 40 + i, DEV)
             if in_call:
                 loss, _ = pkg.train_step(m, opt, x, y)
