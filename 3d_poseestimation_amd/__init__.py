@@ -18,6 +18,8 @@ from .backbone import Model_2D, Model_3D, ResNet  # noqa: F401
 from .data import (FrameFeeder, PersonCrop, PoseAugment, PoseFeeder, augment_frames, augment_poses, crop_boxes, gather_row_weights,  # noqa: F401
                    epoch_indices)
 from .pose_table import H36M_17_OF_32, PoseStats, PoseTransform, pose_stats, prepare_poses  # noqa: F401
+from .sequence import (SequenceLifter, TemporalFilter, coco_to_h36m, filter_tracks, load_keypoints_json, prepare_tracks,  # noqa: F401
+                       velocity_errors)
 from .vit import MyViT  # noqa: F401
 from .range_guard import PoseliftRangeError  # noqa: F401
-from . import arena, backbone, conv, data, dp, gradclip, layout, metrics, pose_table, range_guard, synth, vit  # noqa: F401
+from . import arena, backbone, conv, data, dp, gradclip, layout, metrics, pose_table, range_guard, sequence, synth, vit  # noqa: F401

@@ -276,6 +276,17 @@ SIGNATURES = {
     "pl_pose_stats_host": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _P]),
     "pl_pose_affine": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _P, _P, _c.c_int, _P, _P]),
     "pl_pose_affine_host": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _P, _P, _c.c_int, _P]),
+    "pl_track_remap": (_c.c_int, [_P, _c.c_int64, _c.c_int, _P, _P]),
+    "pl_track_remap_host": (_c.c_int, [_P, _c.c_int64, _c.c_int, _P]),
+    "pl_track_prepare": (_c.c_int, [_P, _c.c_int64, _c.c_int, _c.c_float, _c.c_float, _c.c_float, _c.c_int, _c.c_float, _P, _P, _P,
+                                    _P, _P]),
+    "pl_track_prepare_host": (_c.c_int, [_P, _c.c_int64, _c.c_int, _c.c_float, _c.c_float, _c.c_float, _c.c_int, _c.c_float, _P, _P,
+                                         _P, _P]),
+    "pl_track_filter_tile_frames": (_c.c_int, [_c.c_int64, _c.c_int64, _c.c_int]),
+    "pl_track_filter": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _c.c_int64, _P, _P, _P, _c.c_int, _P, _P]),
+    "pl_track_filter_host": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _c.c_int64, _P, _P, _P, _c.c_int, _P]),
+    "pl_track_velocity_errors": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _P, _c.c_int, _P, _P, _P, _P, _P]),
+    "pl_track_velocity_errors_host": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _P, _c.c_int, _P, _P, _P, _P]),
     "pl_frame_warp_gather": (_c.c_int, [_c.POINTER(PLFrameWarp), _P]),
     "pl_frame_warp_host": (_c.c_int, [_c.POINTER(PLFrameWarp)]),
     "pl_pose_augment_gather_crop": (_c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_int64, _P, _P, _c.POINTER(PLPoseAug), _c.c_uint64,

@@ -625,6 +625,53 @@ int pl_pose_stats_host(const float* x, int64_t N, int64_t W, double* out);
 int pl_pose_affine(const float* x, int64_t N, int64_t W, const float* sub, const float* div, int invert, float* y, void* stream);
 int pl_pose_affine_host(const float* x, int64_t N, int64_t W, const float* sub, const float* div, int invert, float* y);
 
+/* ---- video tracks: detector keypoints to filtered 3-D poses (csrc/track.h has the definitions) -----------------------
+ * The reference keeps one [17][3] (x, y, confidence) row per video frame, COCO-17 mapped to the H36M-17 layout, all zeros
+ * where nothing was detected (phase1_lifting/video2keypoints.py:14-57, :83-98).  PARITY UNPINNED: it remaps the two
+ * coordinate columns only and leaves the confidence column in COCO order (:94-95); here a joint's confidence follows it.
+ * Every entry is ONE launch on `stream`, allocates nothing and synchronises nothing; the _host forms run the same inline
+ * text on host pointers (test hooks).  seq_ids_or_null [T] int32: the frames of one video are contiguous; frame s is in frame
+ * t's sequence when every frame from t to s carries the same id; NULL = one sequence.  Nothing reads across a boundary.
+ * T outside [1, 8 INT32_MAX] is PL_ESHAPE; a null required pointer, outputs that overlap an input or each other: PL_EINVAL.
+ *
+ * pl_track_remap: det [T][17][3] -> out [T][17][3] in the H36M-17 layout.  layout PL_TRACK_COCO17: the arithmetic of
+ *   coco2h36m in fp32 in its order (a midpoint is (a + b) * 0.5f, joint 7 from the computed joints 0 and 8); a derived
+ *   joint's confidence is the minimum of its sources' (a NaN wins).  PL_TRACK_H36M17: a copy.
+ * pl_track_prepare: remap, scale (x / div_w, y / div_h: correctly rounded), validity (conf >= conf_thr, both coordinates
+ *   finite) and gap fill, max_gap G in 0..64, searched at most G frames each way inside the sequence:
+ *     state 0 valid         xy = the scaled detection                                   w = conf
+ *     state 1 interpolated  a < t < b found, b - a - 1 <= G: x_a + (x_b - x_a) * ((float)(t - a) / (float)(b - a))
+ *                                                                                       w = fill_conf * min(conf_a, conf_b)
+ *     state 2 held          one side found, the other side's search left the sequence  w = fill_conf * conf_side
+ *     state 3 lost          the detection's own scaled value where finite, else 0       w = 0
+ *   xy [T][17][2], w [T][17] fp32, state [T][17] uint8.  PL_EINVAL: div not positive and finite, conf_thr NaN, fill_conf
+ *   negative or not finite, max_gap outside 0..64, an unknown layout.
+ * pl_track_filter: x [T][J][D] (D in {2, 3}, J <= 32), w_or_null [T][J], taps [K] ON THE HOST, K odd and <= 65:
+ *     y[t][j][:] = (sum_k taps[k] w[s][j] x[s][j][:]) / (sum_k taps[k] w[s][j]),  s = t + k - K/2 inside t's sequence,
+ *   fp32 in increasing k, one correctly rounded division per element; a sample with w == 0 is skipped, NULL w is weight 1, a
+ *   denominator that is not positive gives y = x[t].  PL_EINVAL: K even or outside 1..65, a tap negative or not finite;
+ *   PL_ESHAPE: J or D out of range.  A workgroup stages pl_track_filter_tile_frames(J, D, K) frames plus halo in LDS.
+ * pl_track_velocity_errors: pred, tgt [T][J][3] -> out [T][J]: order 1 ||(p[t] - p[t-1]) - (g[t] - g[t-1])||, order 2 the
+ *   same with q[t+1] - 2 q[t] + q[t-1]; count [T] uint8 = 1 where the stencil lies inside t's sequence, out = 0 elsewhere.
+ *   (sub, div) [3 J] or both NULL: the poses are taken back first as pl_pose_errors_t does. */
+enum { PL_TRACK_COCO17 = 0, PL_TRACK_H36M17 = 1 };
+int pl_track_remap(const float* det, int64_t T, int layout, float* out, void* stream);
+int pl_track_remap_host(const float* det, int64_t T, int layout, float* out);
+int pl_track_prepare(const float* det, int64_t T, int layout, float div_w, float div_h, float conf_thr, int max_gap,
+                     float fill_conf, const int32_t* seq_ids_or_null, float* xy, float* w, uint8_t* state, void* stream);
+int pl_track_prepare_host(const float* det, int64_t T, int layout, float div_w, float div_h, float conf_thr, int max_gap,
+                          float fill_conf, const int32_t* seq_ids_or_null, float* xy, float* w, uint8_t* state);
+int pl_track_filter_tile_frames(int64_t J, int64_t D, int K);
+int pl_track_filter(const float* x, int64_t T, int64_t J, int64_t D, const float* w_or_null, const int32_t* seq_ids_or_null,
+                    const float* taps, int K, float* y, void* stream);
+int pl_track_filter_host(const float* x, int64_t T, int64_t J, int64_t D, const float* w_or_null,
+                         const int32_t* seq_ids_or_null, const float* taps, int K, float* y);
+int pl_track_velocity_errors(const float* pred, const float* tgt, int64_t T, int64_t J, const int32_t* seq_ids_or_null,
+                             int order, const float* sub_or_null, const float* div_or_null, float* out, uint8_t* count,
+                             void* stream);
+int pl_track_velocity_errors_host(const float* pred, const float* tgt, int64_t T, int64_t J, const int32_t* seq_ids_or_null,
+                                  int order, const float* sub_or_null, const float* div_or_null, float* out, uint8_t* count);
+
 /* The frames of the same rows, gathered, resized, normalised and augmented in one launch (csrc/frame_warp.h has the
  * definition; the reference resizes per sample on the host, H36_dataset.py:129-131 `cv2.resize(frame,(256,256))`,
  * `frame/256.0`, and leaves `cv2.flip(frame,1)` next to flip_pose commented out, :98-117).  The decisions flip, rotation,

@@ -200,6 +200,27 @@ def golden_g14():
     np.savez_compressed(os.path.join(OUT, "g14_heatmap_targets.npz"), **rec)
 
 
+def golden_g15():
+    """G15: a recorded video track of the reference, data only.  Frames 440-695 (256 frames) of `Walking 1.58860488`:
+    det   the detector track phase2_opp_mb/final_json_outputs/<video>.json, (x, y, confidence) in pixels, H36M-17 order
+    gt2d  the ground-truth 2-D track that ships beside it (<video>_GT.json)
+    mb3d  MotionBERT's 3-D track of the same video (phase2_opp_mb/MB_npy/Walking 1.mp4.npy), root at 0
+    The slice holds the track's one missing frame (all zeros) at local index 216."""
+    import json
+    d = "/root/reference/phase2_opp_mb"
+    lo, hi = 440, 696
+
+    def track(name):
+        with open(f"{d}/final_json_outputs/{name}") as f:
+            return np.asarray([np.asarray(fr["keypoints"], dtype=np.float64).reshape(17, 3) for fr in json.load(f)])
+    det = track("Walking 1.58860488.mp4.json")[lo:hi].astype(np.float32)
+    gt = track("Walking 1.58860488.mp4_GT.json")[lo:hi, :, :2].astype(np.float32)
+    mb = np.load(f"{d}/MB_npy/Walking 1.mp4.npy")[lo:hi].astype(np.float32)
+    assert det.shape == (256, 17, 3) and gt.shape == (256, 17, 2) and mb.shape == (256, 17, 3)
+    assert not det[216].any() and det[215].any() and det[217].any()
+    np.savez_compressed(os.path.join(OUT, "g15_video_tracks.npz"), det=det, gt2d=gt, mb3d=mb, first_frame=np.int64(lo))
+
+
 def main():
     only = None
     if "--only" in sys.argv:
@@ -214,6 +235,8 @@ def main():
             golden_g11()
         if "g14" in only:
             golden_g14()
+        if "g15" in only:
+            golden_g15()
         for f in sorted(os.listdir(OUT)):
             print(f, os.path.getsize(os.path.join(OUT, f)))
         return
@@ -377,6 +400,7 @@ def main():
                         sq_mean=np.float64((feat.double() ** 2).mean().item()))
     golden_g11()
     golden_g14()
+    golden_g15()
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))
 
