@@ -191,6 +191,10 @@ SIGNATURES = {
     "pl_mpjpe_accum_t": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _P, _P, _P, _P, _P]),
     "pl_pose_metrics_scratch_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int64, _c.c_int, _c.c_int]),
     "pl_pose_metrics_accum": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _P, _c.c_int, _P, _c.c_int, _P, _P, _P, _P, _P]),
+    "pl_pose_errors_w": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _P, _P, _P, _P, _P, _P]),
+    "pl_pose_errors_w_host": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _P, _P, _P, _P, _P]),
+    "pl_pose_metrics_w_scratch_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int64, _c.c_int, _c.c_int]),
+    "pl_pose_metrics_accum_w": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _P, _c.c_int, _P, _c.c_int, _P, _P, _P, _P, _P, _P]),
     "pl_adamw_flat": (_c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_float, _c.c_float, _c.c_float,
                                  _c.c_float, _c.c_float, _c.c_int64, _c.c_float, _P]),
     "pl_adamw_flat_dev": (_c.c_int, [_P, _P, _P, _P, _c.c_int64, _P, _c.c_float, _c.c_float, _c.c_float,

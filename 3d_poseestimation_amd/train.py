@@ -551,11 +551,14 @@ def predict_flip_tta(model, y1, out_dims=3):
 
 @torch.no_grad()
 def eval_step(model, y1, y2, metric_out=None, flip=False, meter=None, group_ids=None, denorm=None, criterion=None, ema=None,
-              row_weights=None):
+              row_weights=None, meter_weights=None):
     """train_1.py:112-145 body (model must be in eval mode): forward, MSE, loss_MPJPE.
     criterion: a criterion.PoseCriterion -- `loss` is then that criterion's value, not the MSE.
-    row_weights: (B, J) per-pose joint weights of that criterion's value (ValueError without a criterion); `metric` and the
-    meter are not weighted.
+    row_weights: (B, J) per-pose joint weights of that criterion's value (ValueError without a criterion); `metric` is not
+    weighted, and the meter has a keyword of its own:
+    meter_weights: (B, J) visibility of the targets for a meter built with PoseMetrics(visibility=True), handed to
+    meter.update(weights=): joints with weight > 0 fit the alignment and enter the masked table (metrics.py).  Independent
+    of row_weights (which stays the criterion's and still needs one); ValueError without a meter or with a plain meter.
     flip=True: flip test-time augmentation (predict_flip_tta).
     meter: a metrics.PoseMetrics that also takes this batch (P-MPJPE, N-MPJPE, PCK; group_ids (B,) = e.g. the action of
     each pose); like everything here it only enqueues work.
@@ -565,10 +568,12 @@ def eval_step(model, y1, y2, metric_out=None, flip=False, meter=None, group_ids=
     ema: the model's flat optimizer built with ema_decay -- the step runs on the averaged weights, i.e. inside
     `with ema.averaged_weights():` (BatchNorm running statistics stay the live ones)."""
     _need_criterion(row_weights, criterion, "eval_step")
+    if meter_weights is not None and (meter is None or not getattr(meter, "visibility", False)):
+        raise ValueError("eval_step: meter_weights= needs meter= a PoseMetrics built with visibility=True")
     if ema is not None:
         with ema.averaged_weights():
             return eval_step(model, y1, y2, metric_out=metric_out, flip=flip, meter=meter, group_ids=group_ids, denorm=denorm,
-                             criterion=criterion, row_weights=row_weights)
+                             criterion=criterion, row_weights=row_weights, meter_weights=meter_weights)
     if flip and denorm is not None:
         raise ValueError("eval_step: flip=True mirrors image-normalised poses and cannot run on transformed ones; compose it: "
                          "a = model(T2.apply(raw2d)), b = model(T2.apply(flip_pose(raw2d))), then "
@@ -578,7 +583,10 @@ def eval_step(model, y1, y2, metric_out=None, flip=False, meter=None, group_ids=
     loss = _criterion_loss(criterion, y2_hat, y2, row_weights)
     metric = loss_MPJPE(y2_hat, y2, out=metric_out, denorm=denorm)
     if meter is not None:
-        meter.update(y2_hat, y2, group_ids, denorm=denorm)
+        if meter_weights is not None:
+            meter.update(y2_hat, y2, group_ids, denorm=denorm, weights=meter_weights)
+        else:
+            meter.update(y2_hat, y2, group_ids, denorm=denorm)
     return loss, metric, y2_hat
 
 

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define PL_VERSION 121 /* 0.1.21: + PLSkeleton, PLSkeletonCriterion, PL_CRIT_HAS_SKELETON, pl_bone_lengths, pl_skeleton_terms_host, pl_skeleton_abi_bytes (bone-length and left/right symmetry terms of the criterion, one launch more per step); 0.1.20: + PLEma, PLAdamWStep.ema, pl_adamw_flat_planes_clip_ema, pl_swap_f32 (averaged weights kept inside the AdamW launches); 0.1.19: + pl_lifter_bwd_slab_rides (how many split-K sums of weight gradients ride in chained GEMM launches); 0.1.18: + PLPoseCrop, pl_pose_augment_gather_crop, pl_pose_augment_gather_crop_t, pl_pose_augment_host_crop, pl_pose_augment_host_crop_t, pl_frame_warp_gather_crop, pl_frame_warp_host_crop, pl_pose_crop_boxes, pl_pose_crop_boxes_host, pl_crop_poses, pl_crop_poses_host (person-centred crop from each row's 2-D pose inside the two batch launches); 0.1.17: + PLCriterion, pl_pose_loss_scratch_bytes, pl_pose_loss_fwd_bwd, pl_lifter_train_fwd_bwd_crit, pl_lifter_train_step_crit (the train step's criterion: mse, l1, smooth_l1, mpjpe, weighted per joint); 0.1.16: + pl_pose_prepare, pl_pose_stats, pl_pose_affine and their _host forms, pl_pose_stats_scratch_bytes, pl_pose_stats_chunk_rows, pl_pose_augment_gather_t, pl_pose_augment_host_t, pl_pose_errors_t, pl_mpjpe_accum_t (pose tables: prepare, statistics, the per-column transform and its way back inside the batch, error and metric launches); 0.1.15: + PLFrameWarp, pl_frame_warp_gather, pl_frame_warp_host (frame gather + resize + the pose augmentation's warp in one launch); 0.1.14: + PLPoseAug, pl_pose_augment_gather, pl_pose_augment_host (seeded train-time pose augmentation inside the batch gather); 0.1.13: + PLClipRecord, pl_grad_norm_scratch_bytes, pl_grad_norm_clip, pl_adamw_flat_clip, pl_adamw_flat_dev_clip, pl_adamw_flat_planes_clip (gradient-norm clipping and non-finite skip on the device); 0.1.12: + pl_pose_errors, pl_pose_errors_host, pl_pose_metrics_scratch_bytes, pl_pose_metrics_accum (evaluation: MPJPE / N-MPJPE / P-MPJPE, PCK counts, per group); 0.1.11: + pl_vit_*_bf16, pl_vit_bf16_pack (MyViT "bf16p": bf16 operand carriers written by their producers); 0.1.10: + pl_vit_* (the MyViT transformer lifter); 0.1.9: + pl_conv2d_planes_fwd_hw, pl_conv2d_planes_wgrad_hw (the stem on the planes GEMM); 0.1.8: + pl_lifter_train_step, pl_lifter_step_carries_adamw; 0.1.7: + pl_workspace_bitmap_format (small-batch layer kernels); 0.1.6: + pl_counter_add; 0.1.5: + pl_flip_pose_ex, pl_flip_w_nhwc (phase5 Flip branch); 0.1.4: + pl_planes_split_strided; 0.1.3: + pl_bn_join_bwd (0.1.2: operand-plane outputs of the BatchNorm / join kernels, pl_gemm_planes_raw) */
+#define PL_VERSION 122 /* 0.1.22: + pl_pose_errors_w, pl_pose_errors_w_host, pl_pose_metrics_w_scratch_bytes, pl_pose_metrics_accum_w (evaluation with missing joints: visibility-weighted alignment, masked sums and counts, per-joint visible counts); 0.1.21: + PLSkeleton, PLSkeletonCriterion, PL_CRIT_HAS_SKELETON, pl_bone_lengths, pl_skeleton_terms_host, pl_skeleton_abi_bytes (bone-length and left/right symmetry terms of the criterion, one launch more per step); 0.1.20: + PLEma, PLAdamWStep.ema, pl_adamw_flat_planes_clip_ema, pl_swap_f32 (averaged weights kept inside the AdamW launches); 0.1.19: + pl_lifter_bwd_slab_rides (how many split-K sums of weight gradients ride in chained GEMM launches); 0.1.18: + PLPoseCrop, pl_pose_augment_gather_crop, pl_pose_augment_gather_crop_t, pl_pose_augment_host_crop, pl_pose_augment_host_crop_t, pl_frame_warp_gather_crop, pl_frame_warp_host_crop, pl_pose_crop_boxes, pl_pose_crop_boxes_host, pl_crop_poses, pl_crop_poses_host (person-centred crop from each row's 2-D pose inside the two batch launches); 0.1.17: + PLCriterion, pl_pose_loss_scratch_bytes, pl_pose_loss_fwd_bwd, pl_lifter_train_fwd_bwd_crit, pl_lifter_train_step_crit (the train step's criterion: mse, l1, smooth_l1, mpjpe, weighted per joint); 0.1.16: + pl_pose_prepare, pl_pose_stats, pl_pose_affine and their _host forms, pl_pose_stats_scratch_bytes, pl_pose_stats_chunk_rows, pl_pose_augment_gather_t, pl_pose_augment_host_t, pl_pose_errors_t, pl_mpjpe_accum_t (pose tables: prepare, statistics, the per-column transform and its way back inside the batch, error and metric launches); 0.1.15: + PLFrameWarp, pl_frame_warp_gather, pl_frame_warp_host (frame gather + resize + the pose augmentation's warp in one launch); 0.1.14: + PLPoseAug, pl_pose_augment_gather, pl_pose_augment_host (seeded train-time pose augmentation inside the batch gather); 0.1.13: + PLClipRecord, pl_grad_norm_scratch_bytes, pl_grad_norm_clip, pl_adamw_flat_clip, pl_adamw_flat_dev_clip, pl_adamw_flat_planes_clip (gradient-norm clipping and non-finite skip on the device); 0.1.12: + pl_pose_errors, pl_pose_errors_host, pl_pose_metrics_scratch_bytes, pl_pose_metrics_accum (evaluation: MPJPE / N-MPJPE / P-MPJPE, PCK counts, per group); 0.1.11: + pl_vit_*_bf16, pl_vit_bf16_pack (MyViT "bf16p": bf16 operand carriers written by their producers); 0.1.10: + pl_vit_* (the MyViT transformer lifter); 0.1.9: + pl_conv2d_planes_fwd_hw, pl_conv2d_planes_wgrad_hw (the stem on the planes GEMM); 0.1.8: + pl_lifter_train_step, pl_lifter_step_carries_adamw; 0.1.7: + pl_workspace_bitmap_format (small-batch layer kernels); 0.1.6: + pl_counter_add; 0.1.5: + pl_flip_pose_ex, pl_flip_w_nhwc (phase5 Flip branch); 0.1.4: + pl_planes_split_strided; 0.1.3: + pl_bn_join_bwd (0.1.2: operand-plane outputs of the BatchNorm / join kernels, pl_gemm_planes_raw) */
 
 typedef enum PLStatus {
   PL_OK = 0,
@@ -841,6 +841,48 @@ size_t pl_pose_metrics_scratch_bytes(int64_t B, int64_t J, int groups, int n_thr
 int pl_pose_metrics_accum(const float* err, int64_t B, int64_t J, const int32_t* group_or_null, int groups,
                           const float* thr_or_null, int n_thr, float* sums, int64_t* counts, int64_t* n_poses,
                           void* scratch, void* stream);
+
+/* ---- evaluation with missing joints: per-pose joint weights (visibility) ----------------------------------------------
+ * weights [B][J] fp32, 4-byte aligned.  For pose b let w = weights[b], V = { j : w_j > 0 } and W = sum_V w_j.  A weight that
+ * is not > 0 (zero, negative or NaN) means "not visible"; nothing validates weights on the host, so nothing synchronises.
+ * err stays [3][B][J] and is written for every joint, visible or not:
+ *   err[0] MPJPE     ||P_j - T_j||, unchanged
+ *   err[1] N-MPJPE   ||s P_j - T_j||,  s = sum_V w_j P_j.T_j / sum_V w_j P_j.P_j   (0 when the denominator == 0)
+ *   err[2] P-MPJPE   ||a R (P_j - muP) + muT - T_j||,  muP = sum_V w_j P_j / W and muT likewise,
+ *                    M = sum_V w_j (P_j - muP)(T_j - muT)^T,  R = Horn's best proper rotation of N(M) (the same Jacobi
+ *                    route),  a = lambda / sum_V w_j ||P_j - muP||^2   (0 when that sum == 0)
+ * aligned = a R (P_j - muP) + muT for every joint: an invisible joint is carried by the transform fitted on the visible
+ * ones, and its error says how far the occluded joint lands.
+ * Sums over V are SELECTS, not products: a joint outside V is not read into any whole-pose sum, so a NaN or infinity at an
+ * invisible joint of the prediction or the target reaches only that joint's own three error cells and its aligned
+ * coordinates.  (The criterion's row weights multiply, there a zero weight times a NaN is a NaN; a NaN-coded missing ground
+ * truth is exactly the case this is for.)  A NaN at a visible joint behaves as in pl_pose_errors.  Everything centred is
+ * formed from differences to the FIRST VISIBLE joint: a collapsed visible subset is exactly 0 and an offset of 1000 m
+ * costs nothing.
+ * Degenerate: W == 0 (no visible joint): s = 0, a = 0, both centroids 0, finite outputs for finite inputs.  One visible
+ * joint: a = 0, that joint's P-MPJPE is 0.  Two visible joints, or visible joints on a line: the rotation about the line
+ * is undetermined; results are finite, the split of the error over the invisible joints is not pinned.
+ * c w (c > 0) gives the results of w, and all-ones weights those of pl_pose_errors, to rounding.
+ * weights_or_null == NULL and (sub, div) [3 J] both NULL: pl_pose_errors / pl_pose_errors_t, the same kernel
+ * instantiations, bit for bit.  pl_pose_errors_w_host: the same inline arithmetic on host pointers (a test hook). */
+int pl_pose_errors_w(const float* pred, const float* tgt, int64_t B, int64_t J, const float* weights_or_null,
+                     const float* sub_or_null, const float* div_or_null, float* err /* [3][B][J] */, float* aligned_or_null,
+                     void* stream);
+int pl_pose_errors_w_host(const float* pred, const float* tgt, int64_t B, int64_t J, const float* weights_or_null,
+                          const float* sub_or_null, const float* div_or_null, float* err, float* aligned_or_null);
+/* pl_pose_metrics_accum as a masked mean.  With v_bj = (weights[b][j] > 0), per group g of the poses:
+ *   sums   [G][3][J]     += sum_b v_bj err[m][b][j]
+ *   counts [G][3][T][J]  += number of b with v_bj and err[m][b][j] <= thr[t]
+ *   n_valid [G][J] int64 += sum_b v_bj                               (8-byte aligned)
+ *   n_poses [G + 1]      += poses of group g, fully invisible ones included (cell G: ids outside [0, G))
+ * The weights' magnitudes matter to the alignment only; the weight is read beside the error it gates and selects, so a
+ * non-finite error behind a weight that is not > 0 is in nothing.  The same two launches (the visible counts are one more
+ * job of the first grid), no atomics, a fixed order of every sum; scratch >= the _w_ size below, which is
+ * pl_pose_metrics_scratch_bytes plus 4 G J bytes per chunk. */
+size_t pl_pose_metrics_w_scratch_bytes(int64_t B, int64_t J, int groups, int n_thr);
+int pl_pose_metrics_accum_w(const float* err, const float* weights, int64_t B, int64_t J, const int32_t* group_or_null,
+                            int groups, const float* thr_or_null, int n_thr, float* sums, int64_t* counts, int64_t* n_poses,
+                            int64_t* n_valid, void* scratch, void* stream);
 
 /* *counter += delta on the stream (one thread).  The optimizer of a step replayed from a hipGraph keeps its step count on
  * the device: pl_adamw_flat_dev reads t = t_base + *t_dev, this call ticks it behind the update (arena.FlatAdam for the
