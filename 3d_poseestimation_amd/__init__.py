@@ -20,6 +20,7 @@ from .data import (FrameFeeder, PersonCrop, PoseAugment, PoseFeeder, augment_fra
 from .pose_table import H36M_17_OF_32, PoseStats, PoseTransform, pose_stats, prepare_poses  # noqa: F401
 from .sequence import (SequenceLifter, TemporalFilter, coco_to_h36m, filter_tracks, load_keypoints_json, prepare_tracks,  # noqa: F401
                        velocity_errors)
+from .camera import CameraTable, fit_translation, project_poses, reprojection_errors, reprojection_loss  # noqa: F401
 from .vit import MyViT  # noqa: F401
 from .range_guard import PoseliftRangeError  # noqa: F401
-from . import arena, backbone, conv, data, dp, gradclip, layout, metrics, pose_table, range_guard, sequence, synth, vit  # noqa: F401
+from . import arena, backbone, camera, conv, data, dp, gradclip, layout, metrics, pose_table, range_guard, sequence, synth, vit  # noqa: F401

@@ -291,6 +291,21 @@ SIGNATURES = {
     "pl_track_filter_host": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _c.c_int64, _P, _P, _P, _c.c_int, _P]),
     "pl_track_velocity_errors": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _P, _c.c_int, _P, _P, _P, _P, _P]),
     "pl_track_velocity_errors_host": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _P, _c.c_int, _P, _P, _P, _P]),
+    "pl_camera_project": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _P, _c.c_int64, _P, _P, _P, _P, _P, _P]),
+    "pl_camera_project_host": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _P, _c.c_int64, _P, _P, _P, _P, _P]),
+    "pl_camera_project_bwd": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _P, _c.c_int64, _P, _P, _P, _P, _P, _P, _P]),
+    "pl_camera_project_bwd_host": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _P, _c.c_int64, _P, _P, _P, _P, _P, _P]),
+    "pl_camera_reproj_errors": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _P, _c.c_int64, _P, _P, _P, _P, _c.c_float, _c.c_float,
+                                           _P, _P]),
+    "pl_camera_reproj_errors_host": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _P, _c.c_int64, _P, _P, _P, _P, _c.c_float,
+                                                _c.c_float, _P]),
+    "pl_camera_reproj_loss_scratch_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int64]),
+    "pl_camera_reproj_loss_fwd_bwd": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _P, _c.c_int64, _P, _P, _P, _P, _P, _c.c_int,
+                                                 _c.c_float, _c.c_float, _c.c_float, _P, _P, _P, _P, _P]),
+    "pl_camera_reproj_loss_fwd_bwd_host": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _P, _c.c_int64, _P, _P, _P, _P, _P, _c.c_int,
+                                                      _c.c_float, _c.c_float, _c.c_float, _P, _P, _P, _P]),
+    "pl_camera_fit_translation": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _P, _c.c_int64, _P, _P, _P, _P, _c.c_int, _P, _P, _P]),
+    "pl_camera_fit_translation_host": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _P, _c.c_int64, _P, _P, _P, _P, _c.c_int, _P, _P]),
     "pl_frame_warp_gather": (_c.c_int, [_c.POINTER(PLFrameWarp), _P]),
     "pl_frame_warp_host": (_c.c_int, [_c.POINTER(PLFrameWarp)]),
     "pl_pose_augment_gather_crop": (_c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_int64, _P, _P, _c.POINTER(PLPoseAug), _c.c_uint64,

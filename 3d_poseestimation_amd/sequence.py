@@ -7,7 +7,7 @@ definitions).
   TemporalFilter    odd, non-negative FIR taps (gaussian, box)
   filter_tracks     the confidence-weighted FIR along time                          pl_track_filter
   velocity_errors   MPJVE (order 1) and acceleration error (order 2)                pl_track_velocity_errors
-  SequenceLifter    prepare -> 2-D filter -> transform -> model -> denorm -> 3-D filter
+  SequenceLifter    prepare -> 2-D filter -> transform -> model -> denorm -> 3-D filter; locate(): + the root trajectory
   load_keypoints_json   the reference's recorded tracks (host only)
 
 Rows are frames: row t + 1 follows row t unless `seq_ids` (T,) int32 says otherwise -- the frames of one video carry one id
@@ -210,14 +210,27 @@ class SequenceLifter:
         self.transform_2d, self.denorm = transform_2d, denorm
         self.conf_thr, self.max_gap, self.fill_conf = float(conf_thr), int(max_gap), float(fill_conf)
         self.filter_2d, self.filter_3d, self.flip_tta, self.chunk = filter_2d, filter_3d, bool(flip_tta), int(chunk)
+        self._div_dev = {}
 
     @torch.no_grad()
     def lift(self, det, seq_ids=None):
         """det (T, 17, 3) -> (poses (T, 17, 3), w (T, 17), state (T, 17) uint8)."""
+        return self._lift(det, seq_ids, False)[:3]
+
+    def _pixels(self, xy):
+        """The prepared track back in pixels, xy * div: a new tensor (the transform below works in place on xy)."""
+        div = self._div_dev.get(xy.device)
+        if div is None:
+            div = self._div_dev[xy.device] = torch.tensor(self.div, dtype=torch.float32, device=xy.device)
+        return xy * div
+
+    def _lift(self, det, seq_ids, want_pixels):
+        """lift(), and the prepared 2-D track in pixels when asked for."""
         from .train import predict_flip_tta
         if self.model.training:
             raise ValueError("SequenceLifter.lift runs the model's eval forward: call model.eval() first")
         xy, w, state = prepare_tracks(det, self.layout, self.div, self.conf_thr, self.max_gap, self.fill_conf, seq_ids)
+        px = self._pixels(xy) if want_pixels else None
         if self.filter_2d is not None:
             xy = filter_tracks(xy, self.filter_2d, w, seq_ids)
         if self.transform_2d is not None:
@@ -232,4 +245,21 @@ class SequenceLifter:
             self.denorm.invert_(poses)
         if self.filter_3d is not None:
             poses = filter_tracks(poses, self.filter_3d, w, seq_ids)
-        return poses, w, state
+        return poses, w, state, px
+
+    @torch.no_grad()
+    def locate(self, det, cams, cam_ids=None, seq_ids=None, iters=3, filter_t=None):
+        """det (T, 17, 3) -> (poses (T, 17, 3), t (T, 3), rms (T,), w (T, 17), state (T, 17) uint8): lift(), then the root
+        translation of every frame in its camera's frame (camera.fit_translation: cams a CameraTable, cam_ids (T,) int32 or
+        None) fitted against the prepared 2-D track in pixels, xy * div, the joints weighted by the track's w (a lost joint
+        does not take part), then -- filter_t, a TemporalFilter -- the trajectory filtered along time inside its sequence,
+        frames whose fit is degenerate (rms NaN) weighing 0.  poses + t[:, None] are the camera-frame joints."""
+        from .camera import fit_translation
+        if filter_t is not None and not isinstance(filter_t, TemporalFilter):
+            raise TypeError("filter_t must be a TemporalFilter or None")
+        poses, w, state, px = self._lift(det, seq_ids, True)
+        t, rms = fit_translation(poses, px, cams, cam_ids=cam_ids, weights=w, iters=iters)
+        if filter_t is not None:
+            ok = torch.isfinite(rms).to(torch.float32).reshape(-1, 1)
+            t = filter_tracks(t.reshape(-1, 1, 3), filter_t, ok, seq_ids).reshape(-1, 3)
+        return poses, t, rms, w, state

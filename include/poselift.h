@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define PL_VERSION 122 /* 0.1.22: + pl_pose_errors_w, pl_pose_errors_w_host, pl_pose_metrics_w_scratch_bytes, pl_pose_metrics_accum_w (evaluation with missing joints: visibility-weighted alignment, masked sums and counts, per-joint visible counts); 0.1.21: + PLSkeleton, PLSkeletonCriterion, PL_CRIT_HAS_SKELETON, pl_bone_lengths, pl_skeleton_terms_host, pl_skeleton_abi_bytes (bone-length and left/right symmetry terms of the criterion, one launch more per step); 0.1.20: + PLEma, PLAdamWStep.ema, pl_adamw_flat_planes_clip_ema, pl_swap_f32 (averaged weights kept inside the AdamW launches); 0.1.19: + pl_lifter_bwd_slab_rides (how many split-K sums of weight gradients ride in chained GEMM launches); 0.1.18: + PLPoseCrop, pl_pose_augment_gather_crop, pl_pose_augment_gather_crop_t, pl_pose_augment_host_crop, pl_pose_augment_host_crop_t, pl_frame_warp_gather_crop, pl_frame_warp_host_crop, pl_pose_crop_boxes, pl_pose_crop_boxes_host, pl_crop_poses, pl_crop_poses_host (person-centred crop from each row's 2-D pose inside the two batch launches); 0.1.17: + PLCriterion, pl_pose_loss_scratch_bytes, pl_pose_loss_fwd_bwd, pl_lifter_train_fwd_bwd_crit, pl_lifter_train_step_crit (the train step's criterion: mse, l1, smooth_l1, mpjpe, weighted per joint); 0.1.16: + pl_pose_prepare, pl_pose_stats, pl_pose_affine and their _host forms, pl_pose_stats_scratch_bytes, pl_pose_stats_chunk_rows, pl_pose_augment_gather_t, pl_pose_augment_host_t, pl_pose_errors_t, pl_mpjpe_accum_t (pose tables: prepare, statistics, the per-column transform and its way back inside the batch, error and metric launches); 0.1.15: + PLFrameWarp, pl_frame_warp_gather, pl_frame_warp_host (frame gather + resize + the pose augmentation's warp in one launch); 0.1.14: + PLPoseAug, pl_pose_augment_gather, pl_pose_augment_host (seeded train-time pose augmentation inside the batch gather); 0.1.13: + PLClipRecord, pl_grad_norm_scratch_bytes, pl_grad_norm_clip, pl_adamw_flat_clip, pl_adamw_flat_dev_clip, pl_adamw_flat_planes_clip (gradient-norm clipping and non-finite skip on the device); 0.1.12: + pl_pose_errors, pl_pose_errors_host, pl_pose_metrics_scratch_bytes, pl_pose_metrics_accum (evaluation: MPJPE / N-MPJPE / P-MPJPE, PCK counts, per group); 0.1.11: + pl_vit_*_bf16, pl_vit_bf16_pack (MyViT "bf16p": bf16 operand carriers written by their producers); 0.1.10: + pl_vit_* (the MyViT transformer lifter); 0.1.9: + pl_conv2d_planes_fwd_hw, pl_conv2d_planes_wgrad_hw (the stem on the planes GEMM); 0.1.8: + pl_lifter_train_step, pl_lifter_step_carries_adamw; 0.1.7: + pl_workspace_bitmap_format (small-batch layer kernels); 0.1.6: + pl_counter_add; 0.1.5: + pl_flip_pose_ex, pl_flip_w_nhwc (phase5 Flip branch); 0.1.4: + pl_planes_split_strided; 0.1.3: + pl_bn_join_bwd (0.1.2: operand-plane outputs of the BatchNorm / join kernels, pl_gemm_planes_raw) */
+#define PL_VERSION 123 /* 0.1.23: + pl_camera_project, pl_camera_project_bwd, pl_camera_reproj_errors, pl_camera_reproj_loss_scratch_bytes, pl_camera_reproj_loss_fwd_bwd, pl_camera_fit_translation and their _host forms (cameras: projection with distortion, reprojection loss, root translation fitted to a 2-D track); 0.1.22: + pl_pose_errors_w, pl_pose_errors_w_host, pl_pose_metrics_w_scratch_bytes, pl_pose_metrics_accum_w (evaluation with missing joints: visibility-weighted alignment, masked sums and counts, per-joint visible counts); 0.1.21: + PLSkeleton, PLSkeletonCriterion, PL_CRIT_HAS_SKELETON, pl_bone_lengths, pl_skeleton_terms_host, pl_skeleton_abi_bytes (bone-length and left/right symmetry terms of the criterion, one launch more per step); 0.1.20: + PLEma, PLAdamWStep.ema, pl_adamw_flat_planes_clip_ema, pl_swap_f32 (averaged weights kept inside the AdamW launches); 0.1.19: + pl_lifter_bwd_slab_rides (how many split-K sums of weight gradients ride in chained GEMM launches); 0.1.18: + PLPoseCrop, pl_pose_augment_gather_crop, pl_pose_augment_gather_crop_t, pl_pose_augment_host_crop, pl_pose_augment_host_crop_t, pl_frame_warp_gather_crop, pl_frame_warp_host_crop, pl_pose_crop_boxes, pl_pose_crop_boxes_host, pl_crop_poses, pl_crop_poses_host (person-centred crop from each row's 2-D pose inside the two batch launches); 0.1.17: + PLCriterion, pl_pose_loss_scratch_bytes, pl_pose_loss_fwd_bwd, pl_lifter_train_fwd_bwd_crit, pl_lifter_train_step_crit (the train step's criterion: mse, l1, smooth_l1, mpjpe, weighted per joint); 0.1.16: + pl_pose_prepare, pl_pose_stats, pl_pose_affine and their _host forms, pl_pose_stats_scratch_bytes, pl_pose_stats_chunk_rows, pl_pose_augment_gather_t, pl_pose_augment_host_t, pl_pose_errors_t, pl_mpjpe_accum_t (pose tables: prepare, statistics, the per-column transform and its way back inside the batch, error and metric launches); 0.1.15: + PLFrameWarp, pl_frame_warp_gather, pl_frame_warp_host (frame gather + resize + the pose augmentation's warp in one launch); 0.1.14: + PLPoseAug, pl_pose_augment_gather, pl_pose_augment_host (seeded train-time pose augmentation inside the batch gather); 0.1.13: + PLClipRecord, pl_grad_norm_scratch_bytes, pl_grad_norm_clip, pl_adamw_flat_clip, pl_adamw_flat_dev_clip, pl_adamw_flat_planes_clip (gradient-norm clipping and non-finite skip on the device); 0.1.12: + pl_pose_errors, pl_pose_errors_host, pl_pose_metrics_scratch_bytes, pl_pose_metrics_accum (evaluation: MPJPE / N-MPJPE / P-MPJPE, PCK counts, per group); 0.1.11: + pl_vit_*_bf16, pl_vit_bf16_pack (MyViT "bf16p": bf16 operand carriers written by their producers); 0.1.10: + pl_vit_* (the MyViT transformer lifter); 0.1.9: + pl_conv2d_planes_fwd_hw, pl_conv2d_planes_wgrad_hw (the stem on the planes GEMM); 0.1.8: + pl_lifter_train_step, pl_lifter_step_carries_adamw; 0.1.7: + pl_workspace_bitmap_format (small-batch layer kernels); 0.1.6: + pl_counter_add; 0.1.5: + pl_flip_pose_ex, pl_flip_w_nhwc (phase5 Flip branch); 0.1.4: + pl_planes_split_strided; 0.1.3: + pl_bn_join_bwd (0.1.2: operand-plane outputs of the BatchNorm / join kernels, pl_gemm_planes_raw) */
 
 typedef enum PLStatus {
   PL_OK = 0,
@@ -671,6 +671,73 @@ int pl_track_velocity_errors(const float* pred, const float* tgt, int64_t T, int
                              void* stream);
 int pl_track_velocity_errors_host(const float* pred, const float* tgt, int64_t T, int64_t J, const int32_t* seq_ids_or_null,
                                   int order, const float* sub_or_null, const float* div_or_null, float* out, uint8_t* count);
+
+/* ---- cameras: projection, reprojection loss, root translation (csrc/camera.h has the definitions) ---------------------
+ * The reference carries the Human3.6M intrinsics (phase3_direct/my_HybrIK/utils.py:131-172) and never projects with them
+ * (Model.py:185-189 is commented out).  PARITY UNPINNED: the distortion model is the one in common use for these coefficients.
+ * Shared arguments: X [B][J][3] camera-frame (or, with t, root-relative) poses, J <= 32; cams [C][9] fp32 rows
+ * (fx, fy, cx, cy, k1, k2, k3, p1, p2); cam_ids_or_null [B] int32 (NULL: every pose uses row 0; an id outside [0, C) reads no
+ * row: every value of its pose that depends on the camera is NaN); t_or_null [B][3] added to every joint of its pose; (sub, div) [J][3] or both NULL:
+ * X is taken to raw units first, q = x div + sub, as pl_pose_errors_t does, and gradients are chained through div.
+ *   x = X/Z, y = Y/Z, r2 = x x + y y, rad = 1 + r2 (k1 + r2 (k2 + r2 k3)), tan = p1 x + p2 y,
+ *   u = fx (x (rad + tan) + p1 r2) + cx,  v = fy (y (rad + tan) + p2 r2) + cy
+ * in fp32, every operation rounded by itself, divisions and square roots correctly rounded, no clamp and no special case for
+ * Z <= 0.  Every entry enqueues on `stream` (the loss: two launches, the others one), allocates nothing and synchronises
+ * nothing; the _host forms run the same inline text on host pointers (test hooks) and give the same bits.  No tensor needs
+ * more than 4-byte alignment (the loss's scratch, fp64 partial sums: 8).  PL_ESHAPE: B outside [1, INT32_MAX], J outside [1, 32], C < 1; PL_EINVAL: a null required
+ * pointer, sub without div, outputs that overlap an input or each other, and what each entry names below.
+ *
+ * pl_camera_project: uv [B][J][2].
+ * pl_camera_project_bwd: duv [B][J][2] -> dX [B][J][3] by the analytic Jacobian, and dT_or_null [B][3] = the sum of the pose's
+ *   joint gradients in joint order (PL_EINVAL: dT without t).
+ * pl_camera_reproj_errors: err [B][J] = sqrtf(du du + dv dv), du = (u - target_u) / div_w, dv = (v - target_v) / div_h against
+ *   target [B][J][2]; div positive and finite (else PL_EINVAL), (1, 1) for pixels.
+ * pl_camera_reproj_loss_fwd_bwd: loss[0] and its gradient times grad_scale.  kind PL_REPROJ_L1: mean of |du| + |dv| over
+ *   B J 2 elements; PL_REPROJ_MSE: of du du + dv dv over B J 2; PL_REPROJ_L2: of the pixel distance over B J.
+ *   weights_or_null [B][J] MULTIPLY a joint's value (0 * NaN = NaN: a zero weight hides no NaN); the normaliser stays the
+ *   element count.  dX_or_null (NULL: the value alone), dT_or_null (needs t and dX).  scratch: at least
+ *   pl_camera_reproj_loss_scratch_bytes(B, J) bytes, 8-byte aligned, written before it is read.  The sums have a fixed order,
+ *   a function of (B, J) alone (camera.h).
+ * pl_camera_fit_translation: per pose the t [B][3] that places the root-relative X in front of its camera so that it
+ *   reprojects onto target [B][J][2] (pixels), and rms [B], the weighted RMS reprojection error after the last step.  A joint
+ *   takes part iff its weight is > 0 (weights SELECT here; NULL: all).  A linear initialisation that ignores distortion, then
+ *   `iters` (0..8, else PL_EINVAL) Gauss-Newton steps on the distorted model: a fixed count, no convergence test.  The 3 x 3
+ *   systems are accumulated and solved in fp64.  Fewer than two joints taking part, or a system whose determinant is not
+ *   positive (camera.h: kDetFloor): t and rms of that pose are NaN and no other pose is touched. */
+enum { PL_REPROJ_L1 = 0, PL_REPROJ_MSE = 1, PL_REPROJ_L2 = 2 };
+int pl_camera_project(const float* X, int64_t B, int64_t J, const float* cams, int64_t C, const int32_t* cam_ids_or_null,
+                      const float* t_or_null, const float* sub_or_null, const float* div_or_null, float* uv, void* stream);
+int pl_camera_project_host(const float* X, int64_t B, int64_t J, const float* cams, int64_t C, const int32_t* cam_ids_or_null,
+                           const float* t_or_null, const float* sub_or_null, const float* div_or_null, float* uv);
+int pl_camera_project_bwd(const float* X, const float* duv, int64_t B, int64_t J, const float* cams, int64_t C,
+                          const int32_t* cam_ids_or_null, const float* t_or_null, const float* sub_or_null,
+                          const float* div_or_null, float* dX, float* dT_or_null, void* stream);
+int pl_camera_project_bwd_host(const float* X, const float* duv, int64_t B, int64_t J, const float* cams, int64_t C,
+                               const int32_t* cam_ids_or_null, const float* t_or_null, const float* sub_or_null,
+                               const float* div_or_null, float* dX, float* dT_or_null);
+int pl_camera_reproj_errors(const float* X, const float* target, int64_t B, int64_t J, const float* cams, int64_t C,
+                            const int32_t* cam_ids_or_null, const float* t_or_null, const float* sub_or_null,
+                            const float* div_or_null, float div_w, float div_h, float* err, void* stream);
+int pl_camera_reproj_errors_host(const float* X, const float* target, int64_t B, int64_t J, const float* cams, int64_t C,
+                                 const int32_t* cam_ids_or_null, const float* t_or_null, const float* sub_or_null,
+                                 const float* div_or_null, float div_w, float div_h, float* err);
+size_t pl_camera_reproj_loss_scratch_bytes(int64_t B, int64_t J);
+int pl_camera_reproj_loss_fwd_bwd(const float* X, const float* target, int64_t B, int64_t J, const float* cams, int64_t C,
+                                  const int32_t* cam_ids_or_null, const float* t_or_null, const float* sub_or_null,
+                                  const float* div_or_null, const float* weights_or_null, int kind, float div_w, float div_h,
+                                  float grad_scale, float* dX_or_null, float* dT_or_null, float* loss, void* scratch,
+                                  void* stream);
+int pl_camera_reproj_loss_fwd_bwd_host(const float* X, const float* target, int64_t B, int64_t J, const float* cams, int64_t C,
+                                       const int32_t* cam_ids_or_null, const float* t_or_null, const float* sub_or_null,
+                                       const float* div_or_null, const float* weights_or_null, int kind, float div_w,
+                                       float div_h, float grad_scale, float* dX_or_null, float* dT_or_null, float* loss,
+                                       void* scratch);
+int pl_camera_fit_translation(const float* X, const float* target, int64_t B, int64_t J, const float* cams, int64_t C,
+                              const int32_t* cam_ids_or_null, const float* weights_or_null, const float* sub_or_null,
+                              const float* div_or_null, int iters, float* t, float* rms, void* stream);
+int pl_camera_fit_translation_host(const float* X, const float* target, int64_t B, int64_t J, const float* cams, int64_t C,
+                                   const int32_t* cam_ids_or_null, const float* weights_or_null, const float* sub_or_null,
+                                   const float* div_or_null, int iters, float* t, float* rms);
 
 /* The frames of the same rows, gathered, resized, normalised and augmented in one launch (csrc/frame_warp.h has the
  * definition; the reference resizes per sample on the host, H36_dataset.py:129-131 `cv2.resize(frame,(256,256))`,
